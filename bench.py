@@ -1,9 +1,11 @@
 #!/usr/bin/env python3
 """Headline benchmark: Mrays/s of the path-trace pass on the 250k-triangle scene at
-1920x1080 (BASELINE.json metric), with the HBM roofline of the trace kernel and a
-CPU baseline (the brute-force oracle) timed on the box's host cores.
+1920x1080 (BASELINE.json metric).  With --full it also reports the HBM roofline of
+the trace kernel and a CPU baseline (the brute-force oracle) timed on the box's host
+cores; a plain run sets up, warms up, times the K steps, counts their rays (untimed)
+and prints the result line.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
 One process per GPU.  A "step" = `--spp` more samples of the whole frame
@@ -57,11 +59,19 @@ def main():
     ap.add_argument("--gather", default="torch", choices=["torch", "native"],
                     help="the strips' gather: torch = all_gather_into_tensor on torch-owned buffers (the harness); native = crt_comm_* / "
                          "crt_gather, the RCCL all-gather issued by libcrt itself (what the Node host uses; the id travels through torch.distributed)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
     ap.add_argument("--opt", action="append", default=[], metavar="NAME=VALUE",
                     help="crt_set_option before the run (e.g. wf_pipes=1 for the single-pipe profile); noted in config")
     ap.add_argument("--cpu-crop", default="256x144", help="oracle sample: centre crop WxH at 1 spp")
+    ap.add_argument("--full", action="store_true",
+                    help="also what the headline does not need: HIP-event times of the traversal launches in the timed steps and "
+                         "the HBM roofline built on them (with the canonical BVH2 count and the kernel-alone pass), and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the frame they computed as DIR/<name>.npy (float32): accum_xyz [H,W,3] and "
+                         "rgba8 [H,W,4] (a fixed, seeded sample of pixels, with their indices in pixel_index, above 64 MB)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # Plain `python bench.py --gpus N`: start the N rank processes (one per GPU) before anything in THIS process
@@ -203,21 +213,24 @@ def main():
 
     full_check = os.environ.get("CRT_BENCH_CHECK") == "1"    # rehearsal: compare the gathered frame with a 1-GPU render
 
+    time_kernels = args.full and os.environ.get("CRT_BENCH_NOTK") != "1"
     r.reset()
     run_steps(args.warmup)
-    # from here on: HIP events around every launch of the traversal kernel, on the stream it is launched on
+    # --full, from here on: HIP events around every launch of the traversal kernel, on the stream it is launched on
     # (the event pairs are created now, outside the timed region)
-    if os.environ.get("CRT_BENCH_NOTK") != "1":
+    if time_kernels:
         r.set_option("time_kernels", args.steps * 40 * args.spp + 4096)
     barrier()
     t0 = time.perf_counter()
     run_steps(args.steps)
     barrier()
     elapsed = time.perf_counter() - t0
-    kernel_ms, launches = r.last_kernel_ms() if os.environ.get("CRT_BENCH_NOTK") != "1" else (1.0, 1)
+    kernel_ms, launches = r.last_kernel_ms() if time_kernels else (1.0, 1)
     r.set_option("time_kernels", 0)
     total_ms = elapsed * 1e3
     sf.gather(accum=True)      # final readout of the f32 XYZ accumulator (outside the timed steps)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, *sf.image())
     if full_check and (world > 1 or native) and rank == 0:
         acc_all, rgba_all = sf.image()
         ref = Renderer(local_rank)
@@ -248,7 +261,7 @@ def main():
     # per node).  Counted with the single-kernel form, which walks the BVH2 itself, on the first sample of the timed
     # range (per-ray counts are a property of the scene and the sample; the timed kernels walk the 4-wide tree).
     canon = None
-    if rank == 0:
+    if rank == 0 and args.full:
         r.set_option("pipeline", 0)
         r.reset()
         r.write_accum(np.zeros((sf.local_rows, W, 4), np.float32), args.warmup * args.spp)
@@ -263,7 +276,7 @@ def main():
     # overlap a traversal launch with the other pipe's shade / generate launches, so the kernel's summed launch durations
     # (roofline.frac) measure how the pipes share the GPU as much as the kernel; this is the kernel alone.
     alone = None
-    if rank == 0 and world == 1 and os.environ.get("CRT_BENCH_NOTK") != "1" and not any(o.startswith("wf_pipes=") for o in args.opt):
+    if rank == 0 and world == 1 and time_kernels and not any(o.startswith("wf_pipes=") for o in args.opt):
         r.set_option("wf_pipes", 1).set_option("wf_waves_per_cu", 20)
         r.reset()
         r.frame(args.spp).sync()
@@ -280,42 +293,6 @@ def main():
 
     if rank == 0:
         mrays = rays / elapsed / 1e6
-        # Roofline of the dominant kernel (k_wf_trace, the BVH walk) on THIS rank: algorithmic bytes
-        # (SURVEY.md 8d with this build's record sizes: node bytes per child box tested, 48 B per
-        # primitive tested, 16 B per closest-hit attribute fetch, 36 B per pixel-sample of
-        # framebuffer traffic) over the summed HIP-event durations of its launches in the timed region.
-        st = r.accel_stats()
-        m_rays, m_nodes, m_prims, m_hits, m_paths, _, _ = [float(v) for v in mine.tolist()]
-        alg_bytes = st["bytes_per_box"] * m_nodes + 48.0 * m_prims + 16.0 * m_hits + 36.0 * m_paths
-        per_launch = alg_bytes / max(launches, 1)
-        avg_ms = kernel_ms / max(launches, 1)
-        achieved = alg_bytes / (kernel_ms * 1e-3) / 1e9
-        whole_pass = alg_bytes / (total_ms * 1e-3) / 1e9
-        # HBM bytes per launch from the committed PMC passes of this exact workload (a bench run cannot profile
-        # itself: rocprofv3 --pmc serialises the kernels): reported only while the kernel sources are the ones it was
-        # measured on, null otherwise.
-        traffic, traffic_src, traffic_all = None, None, None
-        trace_form = 2
-        for o in args.opt:
-            if o.startswith("wf_trace_form="):
-                trace_form = int(o.split("=")[1])
-        kernel_name = "k_wf_trace2" if (trace_form == 2 and st["bytes_per_box"] == 16 and st["width"] == 4) else "k_wf_trace"
-        try:
-            with open(os.path.join(ROOT, "profiles", "r03_traffic.json")) as f:
-                entries = json.load(f)
-            key = f"{args.scene} {W}x{H} {args.spp}spp n_gpus={world} accel={args.accel}"
-            for tj in entries:
-                if tj["workload"] == key and tj.get("options", []) == args.opt and tj.get("kernel_sources_sha256") == kernel_sources_sha256():
-                    for kn, kv in tj["kernels"].items():
-                        if kn.startswith(kernel_name + "<false"):
-                            traffic = round(kv["traffic_bytes_per_launch"])
-                            traffic_src = f"profiles/r03_traffic.json ({tj['method']}; {kv['launches']} launches, L2 hit rate {kv['l2_hit_rate']:.3f})"
-                    # every kernel of the pass, per timed step is not known here (launch counts differ between the PMC
-                    # workload and this run): totals of the PMC workload itself
-                    traffic_all = {kn: {"bytes_per_launch": round(kv["traffic_bytes_per_launch"]), "l2_hit_rate": round(kv["l2_hit_rate"], 4)}
-                                   for kn, kv in tj["kernels"].items() if "<true" not in kn}
-        except (OSError, KeyError, ValueError):
-            pass
         out = {
             "metric": "Mrays/sec (+ HBM GB/s vs peak), 1080p 250k-tri scene, 1/2/4/8 MI355X",
             "value": round(mrays, 3), "unit": "Mrays/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -343,36 +320,73 @@ def main():
                      "note": "value counts the reference's intersect() invocations; shadow rays whose NEE term is exactly zero "
                              "(cos_theta == 0) or whose light primitive is missed are decided without a BVH walk"},
             "mrays_walked_per_s": round(walked / elapsed / 1e6, 3),
-            "roofline": {"bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": traffic, "traffic_source": traffic_src,
-                         "traffic_all_kernels": traffic_all,
-                         "measured_hbm_GBs_of_kernel": (round(traffic / (avg_ms * 1e-3) / 1e9, 1) if traffic else None),
-                         "kernel": kernel_name, "launches": launches, "avg_launch_ms": round(avg_ms, 4),
-                         "algorithmic_bytes_per_launch": round(per_launch),
-                         "bytes_per_ray": round(alg_bytes / max(m_rays, 1), 1),
-                         "node_bytes_per_box": st["bytes_per_box"], "node_width": st["width"],
-                         "boxes_per_ray": round(m_nodes / max(m_rays, 1), 2), "prims_per_ray": round(m_prims / max(m_rays, 1), 2),
-                         "kernel_share_of_pass": round(kernel_ms / max(total_ms, 1e-9), 3),
-                         "kernel_alone": (None if not alone else {
-                             "what": "the same kernel with the GPU to itself: one pipe (no shade / generate launch beside it), 20 traversal waves per CU, "
-                                     "two untimed steps after the timed region; algorithmic bytes per step as in the timed steps",
-                             "launches": alone[1], "avg_launch_ms": round(alone[0] / max(alone[1], 1), 4),
-                             "achieved": round(alg_bytes / args.steps * alone[2] / (alone[0] * 1e-3) / 1e9, 2),
-                             "frac": round(alg_bytes / args.steps * alone[2] / (alone[0] * 1e-3) / 1e9 / HBM_PEAK_GBS, 5)}),
-                         "note": "two half-pool pipes run on two streams, so a traversal launch and the other pipe's k_wf_shade / k_wf_gen overlap: "
-                                 "summed launch durations exceed the wall time of the pass; whole_pass_* = bytes / wall time",
-                         "whole_pass_GBs": round(whole_pass, 1), "whole_pass_frac": round(whole_pass / HBM_PEAK_GBS, 5),
-                         "accounting": "this build's records: 16 B per child box of a 64-byte quantised 4-wide node + 48 B per primitive "
-                                       "+ 16 B per hit + 36 B per path (conservative: fewer bytes than the canonical form)",
-                         "canonical": {"what": "SURVEY 8(d) / BASELINE.md: 32 B per BVH2 box tested + 48 B per primitive + 16 B per hit + 36 B per path, "
-                                               "per-ray counts of the BVH2 walk (single-kernel form) on the first timed sample",
-                                       "bytes_per_ray": round(canon, 1), "boxes_per_ray": round(canon_counts[0], 2), "prims_per_ray": round(canon_counts[1], 2),
-                                       "achieved": round(canon * m_rays / (kernel_ms * 1e-3) / 1e9, 2),
-                                       "frac": round(canon * m_rays / (kernel_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5),
-                                       "whole_pass_frac": round(canon * m_rays / (total_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5)}},
         }
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(ps, args)
+        if args.full:
+            # Roofline of the dominant kernel (k_wf_trace, the BVH walk) on THIS rank: algorithmic bytes
+            # (SURVEY.md 8d with this build's record sizes: node bytes per child box tested, 48 B per
+            # primitive tested, 16 B per closest-hit attribute fetch, 36 B per pixel-sample of
+            # framebuffer traffic) over the summed HIP-event durations of its launches in the timed region.
+            st = r.accel_stats()
+            m_rays, m_nodes, m_prims, m_hits, m_paths, _, _ = [float(v) for v in mine.tolist()]
+            alg_bytes = st["bytes_per_box"] * m_nodes + 48.0 * m_prims + 16.0 * m_hits + 36.0 * m_paths
+            per_launch = alg_bytes / max(launches, 1)
+            avg_ms = kernel_ms / max(launches, 1)
+            achieved = alg_bytes / (kernel_ms * 1e-3) / 1e9
+            whole_pass = alg_bytes / (total_ms * 1e-3) / 1e9
+            # HBM bytes per launch from the committed PMC passes of this exact workload (a bench run cannot profile
+            # itself: rocprofv3 --pmc serialises the kernels): reported only while the kernel sources are the ones it was
+            # measured on, null otherwise.
+            traffic, traffic_src, traffic_all = None, None, None
+            trace_form = 2
+            for o in args.opt:
+                if o.startswith("wf_trace_form="):
+                    trace_form = int(o.split("=")[1])
+            kernel_name = "k_wf_trace2" if (trace_form == 2 and st["bytes_per_box"] == 16 and st["width"] == 4) else "k_wf_trace"
+            try:
+                with open(os.path.join(ROOT, "profiles", "r03_traffic.json")) as f:
+                    entries = json.load(f)
+                key = f"{args.scene} {W}x{H} {args.spp}spp n_gpus={world} accel={args.accel}"
+                for tj in entries:
+                    if tj["workload"] == key and tj.get("options", []) == args.opt and tj.get("kernel_sources_sha256") == kernel_sources_sha256():
+                        for kn, kv in tj["kernels"].items():
+                            if kn.startswith(kernel_name + "<false"):
+                                traffic = round(kv["traffic_bytes_per_launch"])
+                                traffic_src = f"profiles/r03_traffic.json ({tj['method']}; {kv['launches']} launches, L2 hit rate {kv['l2_hit_rate']:.3f})"
+                        # every kernel of the pass, per timed step is not known here (launch counts differ between the PMC
+                        # workload and this run): totals of the PMC workload itself
+                        traffic_all = {kn: {"bytes_per_launch": round(kv["traffic_bytes_per_launch"]), "l2_hit_rate": round(kv["l2_hit_rate"], 4)}
+                                       for kn, kv in tj["kernels"].items() if "<true" not in kn}
+            except (OSError, KeyError, ValueError):
+                pass
+            out["roofline"] = {"bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                               "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": traffic, "traffic_source": traffic_src,
+                               "traffic_all_kernels": traffic_all,
+                               "measured_hbm_GBs_of_kernel": (round(traffic / (avg_ms * 1e-3) / 1e9, 1) if traffic else None),
+                               "kernel": kernel_name, "launches": launches, "avg_launch_ms": round(avg_ms, 4),
+                               "algorithmic_bytes_per_launch": round(per_launch),
+                               "bytes_per_ray": round(alg_bytes / max(m_rays, 1), 1),
+                               "node_bytes_per_box": st["bytes_per_box"], "node_width": st["width"],
+                               "boxes_per_ray": round(m_nodes / max(m_rays, 1), 2), "prims_per_ray": round(m_prims / max(m_rays, 1), 2),
+                               "kernel_share_of_pass": round(kernel_ms / max(total_ms, 1e-9), 3),
+                               "kernel_alone": (None if not alone else {
+                                   "what": "the same kernel with the GPU to itself: one pipe (no shade / generate launch beside it), 20 traversal waves per CU, "
+                                           "two untimed steps after the timed region; algorithmic bytes per step as in the timed steps",
+                                   "launches": alone[1], "avg_launch_ms": round(alone[0] / max(alone[1], 1), 4),
+                                   "achieved": round(alg_bytes / args.steps * alone[2] / (alone[0] * 1e-3) / 1e9, 2),
+                                   "frac": round(alg_bytes / args.steps * alone[2] / (alone[0] * 1e-3) / 1e9 / HBM_PEAK_GBS, 5)}),
+                               "note": "two half-pool pipes run on two streams, so a traversal launch and the other pipe's k_wf_shade / k_wf_gen overlap: "
+                                       "summed launch durations exceed the wall time of the pass; whole_pass_* = bytes / wall time",
+                               "whole_pass_GBs": round(whole_pass, 1), "whole_pass_frac": round(whole_pass / HBM_PEAK_GBS, 5),
+                               "accounting": "this build's records: 16 B per child box of a 64-byte quantised 4-wide node + 48 B per primitive "
+                                             "+ 16 B per hit + 36 B per path (conservative: fewer bytes than the canonical form)",
+                               "canonical": {"what": "SURVEY 8(d) / BASELINE.md: 32 B per BVH2 box tested + 48 B per primitive + 16 B per hit + 36 B per path, "
+                                                     "per-ray counts of the BVH2 walk (single-kernel form) on the first timed sample",
+                                             "bytes_per_ray": round(canon, 1), "boxes_per_ray": round(canon_counts[0], 2), "prims_per_ray": round(canon_counts[1], 2),
+                                             "achieved": round(canon * m_rays / (kernel_ms * 1e-3) / 1e9, 2),
+                                             "frac": round(canon * m_rays / (kernel_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5),
+                                             "whole_pass_frac": round(canon * m_rays / (total_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5)}}
+            if world == 1 and not args.no_cpu_baseline:
+                out["cpu_baseline"] = cpu_baseline(ps, args)
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.barrier()
@@ -390,6 +404,26 @@ def kernel_sources_sha256():
             with open(os.path.join(d, name), "rb") as f:
                 h.update(name.encode() + b"\0" + f.read())
     return h.hexdigest()
+
+
+DUMP_LIMIT_BYTES = 64 * 10**6
+
+
+def dump_outputs(path, accum, rgba):
+    """--dump-outputs: the frame the timed steps computed, as float32 .npy files: accum_xyz (the f32 XYZ accumulator;
+    its fourth lane is padding) and rgba8 (the image of the last step).  Frames above DUMP_LIMIT_BYTES keep the same
+    fixed, seeded sample of pixels in both, with their row-major indices in pixel_index (float64)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    acc = accum.cpu().numpy()[..., :3].astype(np.float32)
+    img = rgba.cpu().numpy().astype(np.float32)
+    arrays = {"accum_xyz": acc, "rgba8": img}
+    if sum(a.nbytes for a in arrays.values()) > DUMP_LIMIT_BYTES:
+        n = (DUMP_LIMIT_BYTES - 4096) // (4 * 3 + 4 * 4 + 8)      # (4096: room for the .npy headers)
+        idx = np.sort(np.random.default_rng(0).choice(acc.shape[0] * acc.shape[1], n, replace=False))
+        arrays = {"accum_xyz": acc.reshape(-1, 3)[idx], "rgba8": img.reshape(-1, 4)[idx], "pixel_index": idx.astype(np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
 
 
 def cpu_baseline(ps, args):

@@ -3,7 +3,7 @@
 # (cornell), on mesh10k and on S2: per-kernel launch durations from the middle of a pipelined bench run + the overlap states
 out=$1; export TMPDIR=/tmp; mkdir -p $out
 for sc in cornell mesh10k atrium250k; do
-  timeout -k 10 240 rocprofv3 --kernel-trace --stats --output-format csv -d $out/$sc -o p -- python3 bench.py --scene $sc --steps 5 --warmup 1 --no-cpu-baseline > $out/$sc.json 2> $out/$sc.err || { echo "$sc failed" >> $out/progress.txt; exit 1; }
+  timeout -k 10 240 rocprofv3 --kernel-trace --stats --output-format csv -d $out/$sc -o p -- python3 bench.py --full --scene $sc --steps 5 --warmup 1 --no-cpu-baseline > $out/$sc.json 2> $out/$sc.err || { echo "$sc failed" >> $out/progress.txt; exit 1; }
   echo "$sc done" >> $out/progress.txt
   echo "== $sc" >> $out/summary.txt
   python3 -c "

@@ -5,7 +5,7 @@ out=${1:-gpurun_out/scene_ab.txt}
 : > $out
 for scene in cornell mesh10k atrium250k; do
   for pipes in 1 2; do
-    CRT_LIB=${2:+$PWD/$2} python bench.py --scene $scene --steps 3 --warmup 1 --no-cpu-baseline --opt wf_pipes=$pipes 2>/dev/null | python -c "
+    CRT_LIB=${2:+$PWD/$2} python bench.py --full --scene $scene --steps 3 --warmup 1 --no-cpu-baseline --opt wf_pipes=$pipes 2>/dev/null | python -c "
 import sys, json
 j = json.loads(sys.stdin.readline())
 r = j['roofline']
