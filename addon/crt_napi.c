@@ -461,6 +461,73 @@ static napi_value js_read_sample_rgba8_into(napi_env env, napi_callback_info inf
     return undefined(env);
 }
 
+/* ------------------------------------------------------------------ denoised preview (include/crt.h "Denoised preview")
+ * denoise(h, {iterations, sigmaColor, sigmaNormal, sigmaPlane}) -> Uint8Array (tw*th*4 rgba8); a missing option (or a
+ * missing object) takes the library's default.  readGbuffer(h) -> Float32Array (tw*th*8). */
+static int opt_number(napi_env env, napi_value obj, const char *name, double *out)
+{
+    bool has = false;
+    napi_value v;
+    napi_valuetype t;
+    if (napi_has_named_property(env, obj, name, &has) != napi_ok || !has) return 1;
+    if (napi_get_named_property(env, obj, name, &v) != napi_ok || napi_typeof(env, v, &t) != napi_ok) return 0;
+    if (t == napi_undefined) return 1;
+    return t == napi_number && napi_get_value_double(env, v, out) == napi_ok;
+}
+
+static napi_value js_denoise(napi_env env, napi_callback_info info)
+{
+    size_t argc = 2;
+    napi_value argv[2];
+    NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    if (argc < 1) { napi_throw_type_error(env, NULL, "too few arguments"); return NULL; }
+    crt_ctx *ctx = get_ctx(env, argv[0]);
+    if (!ctx) return NULL;
+    double it = 5.0, sc = 1.0, sn = 0.5, sx = 0.3;
+    napi_valuetype t = napi_undefined;
+    if (argc > 1) NAPI_OK(env, napi_typeof(env, argv[1], &t));
+    if (t == napi_object) {
+        if (!opt_number(env, argv[1], "iterations", &it) || !opt_number(env, argv[1], "sigmaColor", &sc) ||
+            !opt_number(env, argv[1], "sigmaNormal", &sn) || !opt_number(env, argv[1], "sigmaPlane", &sx)) {
+            napi_throw_type_error(env, NULL, "denoise: options must be numbers");
+            return NULL;
+        }
+    } else if (t != napi_undefined && t != napi_null) {
+        napi_throw_type_error(env, NULL, "denoise: options object expected");
+        return NULL;
+    }
+    if (!(it >= 0.0 && it <= 4294967295.0) || it != (double)(uint32_t)it) {
+        napi_throw_range_error(env, NULL, "denoise: iterations must be a non-negative integer");
+        return NULL;
+    }
+    crt_denoise_params p = {(uint32_t)it, (float)sc, (float)sn, (float)sx};
+    uint32_t tl[4];
+    CRT_CHECK(env, ctx, "crt_tile", crt_tile(ctx, tl));
+    size_t px = (size_t)tl[2] * tl[3];
+    void *data = NULL;
+    napi_value ab, ta;
+    NAPI_OK(env, napi_create_arraybuffer(env, px * 4, &data, &ab));
+    CRT_CHECK(env, ctx, "crt_denoise", crt_denoise(ctx, &p, NULL, (uint8_t *)data));
+    NAPI_OK(env, napi_create_typedarray(env, napi_uint8_array, px * 4, ab, 0, &ta));
+    return ta;
+}
+
+static napi_value js_read_gbuffer(napi_env env, napi_callback_info info)
+{
+    ARGS(1)
+    crt_ctx *ctx = get_ctx(env, argv[0]);
+    if (!ctx) return NULL;
+    uint32_t tl[4];
+    CRT_CHECK(env, ctx, "crt_tile", crt_tile(ctx, tl));
+    size_t px = (size_t)tl[2] * tl[3];
+    void *data = NULL;
+    napi_value ab, ta;
+    NAPI_OK(env, napi_create_arraybuffer(env, px * 32, &data, &ab));
+    CRT_CHECK(env, ctx, "crt_read_gbuffer", crt_read_gbuffer(ctx, (float *)data));
+    NAPI_OK(env, napi_create_typedarray(env, napi_float32_array, px * 8, ab, 0, &ta));
+    return ta;
+}
+
 /* ------------------------------------------------------------------ multi-GPU (include/crt.h "Multi-GPU") and composition
  * The reference drives one GPUDevice (src/main.js:8-9); a Node host reaches the tile-partitioned configurations through
  * these: one process (worker) per GPU, the communicator id made by one of them and passed around by the parent
@@ -805,6 +872,7 @@ static napi_value init(napi_env env, napi_value exports)
         {"readFrameRgba8", js_read_frame_rgba8}, {"readFrameAccum", js_read_frame_accum}, {"imageSize", js_image_size},
         {"setRowBands", js_set_row_bands}, {"deviceBuffers", js_device_buffers}, {"frameDeviceBuffers", js_frame_device_buffers},
         {"bindOutput", js_bind_output}, {"setStream", js_set_stream},
+        {"denoise", js_denoise}, {"readGbuffer", js_read_gbuffer},
         {"gatherAsync", js_gather_async}, {"readFrameRgba8Async", js_read_frame_rgba8_async}, {"readFrameAccumAsync", js_read_frame_accum_async},
     };
     for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++) {

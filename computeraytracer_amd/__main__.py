@@ -1,4 +1,4 @@
-"""python -m computeraytracer_amd [--scene file.json] [--width W --height H] [--spp N] [--out image.png]"""
+"""python -m computeraytracer_amd [--scene file.json] [--width W --height H] [--spp N] [--out image.png] [--denoise K]"""
 import argparse
 import json
 import os
@@ -16,6 +16,8 @@ def main():
     ap.add_argument("--accel", default="bvh2", choices=["bvh2", "lbvh", "none"])
     ap.add_argument("--out", default="render.png")
     ap.add_argument("--checkpoint", default=None, help="resume from / save to this .npz")
+    ap.add_argument("--denoise", type=int, default=None, metavar="K",
+                    help="write the image denoised with K a-trous iterations (crt_denoise) instead of the plain average")
     args = ap.parse_args()
     sc = scene.load_scene(args.scene)
     if args.width:
@@ -28,11 +30,14 @@ def main():
         t0 = time.time()
         r.frame(args.spp).sync()
         dt = time.time() - t0
-        rgba = r.read_rgba8()
+        rgba = r.read_rgba8() if args.denoise is None else r.denoise(args.denoise)
         (image.write_ppm if args.out.endswith(".ppm") else image.write_png)(args.out, rgba)
         if args.checkpoint:
             image.save_checkpoint(args.checkpoint, r)
-        print(json.dumps({"width": ps.width, "height": ps.height, "sample": r.sample, "seconds": round(dt, 4), "out": args.out}))
+        info = {"width": ps.width, "height": ps.height, "sample": r.sample, "seconds": round(dt, 4), "out": args.out}
+        if args.denoise is not None:
+            info["denoise"] = args.denoise
+        print(json.dumps(info))
 
 
 if __name__ == "__main__":

@@ -63,10 +63,19 @@ SIGNATURES = {
     "crt_comm_info": (C.c_int, [_P, _P]),
     "crt_comm_destroy": (C.c_int, [_P]),
     "crt_layout_rows": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _P, _P]),
+    "crt_denoise": (C.c_int, [_P, _P, _P, _P]),
+    "crt_read_gbuffer": (C.c_int, [_P, _P]),
     "crt_debug_intersect": (C.c_int, [_P, _P, C.c_size_t, _P]),
     "crt_debug_probes": (C.c_int, [_P, _P]),
     "crt_debug_math": (C.c_int, [_P, C.c_int, _P, _P, _P, C.c_size_t]),
 }
+
+
+
+class DenoiseParams(C.Structure):
+    """crt_denoise_params of include/crt.h."""
+    _fields_ = [("iterations", C.c_uint32), ("sigma_color", C.c_float), ("sigma_normal", C.c_float), ("sigma_plane", C.c_float)]
+
 
 _lib = None
 

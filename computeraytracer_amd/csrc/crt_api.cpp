@@ -37,6 +37,11 @@ hipError_t wf_launch_resolve(const WfParams &P, uint32_t last_sample, hipStream_
 hipError_t build_lbvh(const float *lo, const float *hi, uint32_t n, Bvh &out, hipStream_t stream);
 hipError_t build_lbvh_device(const unsigned char *d_raw, uint32_t n, float hit_pad, float4 *d_prim, float4 *d_primD,
                              uint32_t *d_slot_of_index, float *d_nodes2, uint4 *d_nodes4q, LbvhDeviceResult &res, hipStream_t stream);
+hipError_t dn_launch_gbuffer(const DevScene &S, uint32_t x0, uint32_t y0, uint32_t tw, uint32_t th, float4 *gbuf, uint32_t *key,
+                             int brute, hipStream_t stream);
+hipError_t dn_launch_filter(const float4 *accum, float n, const float4 *gbuf, const uint32_t *key, float4 *c0, float4 *c1,
+                            uchar4 *rgba, uint32_t tw, uint32_t th, uint32_t iterations, float sigma_color, float sigma_normal,
+                            float sigma_plane, float4 **out, hipStream_t stream);
 }  // namespace crt
 
 using namespace crt;
@@ -201,6 +206,14 @@ struct crt_ctx {
     uint32_t last_trace_kernel_launches = 0;
     uint32_t last_iterations = 0;
     unsigned long long probes[8] = {0};   // traversal-efficiency probes of the counting kernels
+
+    // crt_denoise (crt_denoise.hip): the first-hit G-buffer of the tile, built on first use and kept until the scene,
+    // the accel structure or the tile changes; the filter's ping-pong colour buffers and its rgba8 output
+    DevBuf<float4> dn_gbuf;         // 2 per tile pixel: (t, position), (normal, hit index bits)
+    DevBuf<uint32_t> dn_key;        // per tile pixel: material << 24 | reflectance index, 0xFFFFFFFF = miss
+    bool dn_valid = false;
+    DevBuf<float4> dn_c[2];
+    DevBuf<uchar4> dn_rgba;
 };
 
 namespace {
@@ -1606,6 +1619,7 @@ void crt_destroy(crt_ctx *c)
     c->w_ray_o.release(); c->w_ray_d.release(); c->w_sh_d.release(); c->w_beta.release(); c->w_radiance.release();
     c->w_nee.release(); for (uint32_t b = 0; b < kWfRing; b++) c->w_staging[b].release(); c->w_rng.release(); c->w_misc.release(); c->w_hit.release();
     c->w_vis.release(); c->w_dead.release(); c->w_recA.release(); c->w_recB.release(); c->w_recC.release(); c->w_tea.release(); c->w_wq.release();
+    c->dn_gbuf.release(); c->dn_key.release(); c->dn_c[0].release(); c->dn_c[1].release(); c->dn_rgba.release();
     if (c->pub_stream) (void)hipStreamSynchronize(c->pub_stream);
     for (int f = 0; f < crt_ctx::kFinishStreams; f++) {
         if (c->fin_stream[f]) { (void)hipStreamSynchronize(c->fin_stream[f]); (void)hipStreamDestroy(c->fin_stream[f]); }
@@ -1673,6 +1687,7 @@ int crt_upload_scene(crt_ctx *c, const void *primitives, size_t nprim, const voi
     // from here on the old scene is gone: a failure below must not leave a context that can still trace
     c->have_scene = false;
     c->accel_mode = -1;
+    c->dn_valid = false;
     c->prims.swap(prims);
     c->lights.swap(lts);
     std::memcpy(c->camera, camera, sizeof c->camera);
@@ -1730,6 +1745,7 @@ int crt_set_tile(crt_ctx *c, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1)
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->x0 = x0; c->y0 = y0; c->tw = x1 - x0; c->th = y1 - y0;
     c->band = 0x40000000u; c->stride = 1; c->phase = 0;
+    c->dn_valid = false;
     c->accum_bound = nullptr; c->rgba_bound = nullptr;
     int rc = alloc_tile(c);
     if (rc) return rc;
@@ -1750,6 +1766,7 @@ int crt_set_row_bands(crt_ctx *c, uint32_t band_rows, uint32_t parts, uint32_t p
         rows += std::min<uint32_t>(band_rows, c->H - b * band_rows);
     c->x0 = 0; c->y0 = 0; c->tw = c->W; c->th = rows;
     c->band = band_rows; c->stride = parts; c->phase = part;
+    c->dn_valid = false;
     c->accum_bound = nullptr; c->rgba_bound = nullptr;
     int rc = alloc_tile(c);
     if (rc) return rc;
@@ -1769,6 +1786,7 @@ int crt_build_accel(crt_ctx *c, int mode)
     // The build releases the scene's device arrays before it allocates the new ones: until it has succeeded there is
     // no structure to trace against (upload_geometry / build_accel_on_device set accel_mode on success only).
     c->accel_mode = -1;
+    c->dn_valid = false;
     return upload_geometry(c, mode);
 }
 
@@ -2137,6 +2155,72 @@ int crt_set_option(crt_ctx *c, const char *name, int64_t value)
         return CRT_OK;
     }
     return fail(c, CRT_EINVAL, "crt_set_option: unknown option '%s'", name);
+}
+
+// ---------------------------------------------------------------- denoised preview (crt_denoise.hip)
+static int dn_check_state(crt_ctx *c, const char *what)
+{
+    if (!c->have_scene || c->accel_mode < 0) return fail(c, CRT_ESTATE, "%s: scene + accel required", what);
+    if (c->sample == 0) return fail(c, CRT_ESTATE, "%s: no sample traced yet", what);
+    if (c->band != 0x40000000u)
+        return fail(c, CRT_ESTATE, "%s: not under a row-band partition (neighbouring local rows are not neighbouring image rows)", what);
+    if ((size_t)c->tw * c->th != 0 && !accum_ptr(c))
+        return fail(c, CRT_ENOMEM, "%s: the tile's buffers are not allocated (an earlier crt_set_tile failed)", what);
+    return CRT_OK;
+}
+
+// The G-buffer of the tile, built once per scene / accel structure / tile.  Enqueued on the context's stream.
+static int dn_ensure_gbuffer(crt_ctx *c)
+{
+    if (c->dn_valid) return CRT_OK;
+    const size_t n = (size_t)c->tw * c->th;
+    if (c->dn_gbuf.n < 2 * n) HIPCHK(c, c->dn_gbuf.alloc(2 * n));
+    if (c->dn_key.n < n) HIPCHK(c, c->dn_key.alloc(n));
+    HIPCHK(c, dn_launch_gbuffer(c->sc, c->x0, c->y0, c->tw, c->th, c->dn_gbuf.p, c->dn_key.p, c->accel_mode == CRT_ACCEL_NONE, c->stream));
+    c->dn_valid = true;
+    return CRT_OK;
+}
+
+int crt_denoise(crt_ctx *c, const crt_denoise_params *params, float *rgb_out, uint8_t *rgba8_out)
+{
+    if (!c) return CRT_EINVAL;
+    const crt_denoise_params dp = params ? *params : crt_denoise_params{5u, 1.0f, 0.5f, 0.3f};
+    if (dp.iterations > 10u) return fail(c, CRT_EINVAL, "crt_denoise: iterations %u > 10", dp.iterations);
+    const float sig[3] = {dp.sigma_color, dp.sigma_normal, dp.sigma_plane};
+    for (float v : sig)
+        if (!(v > 0.0f && v <= 3.40282347e38f)) return fail(c, CRT_EINVAL, "crt_denoise: every sigma must be positive and finite");
+    { int rc = dn_check_state(c, "crt_denoise"); if (rc) return rc; }
+    HIPCHK(c, hipSetDevice(c->device));
+    { int rc_ = wf_flush(c); if (rc_) return rc_; }
+    const size_t n = (size_t)c->tw * c->th;
+    if (n) {
+        { int rc = dn_ensure_gbuffer(c); if (rc) return rc; }
+        for (int b = 0; b < 2; b++) if (c->dn_c[b].n < n) HIPCHK(c, c->dn_c[b].alloc(n));
+        if (c->dn_rgba.n < n) HIPCHK(c, c->dn_rgba.alloc(n));
+        float4 *res = nullptr;
+        HIPCHK(c, dn_launch_filter(accum_ptr(c), (float)c->sample, c->dn_gbuf.p, c->dn_key.p, c->dn_c[0].p, c->dn_c[1].p,
+                                   rgba8_out ? c->dn_rgba.p : nullptr, c->tw, c->th, dp.iterations, dp.sigma_color,
+                                   dp.sigma_normal, dp.sigma_plane, &res, c->stream));
+        if (rgb_out) HIPCHK(c, hipMemcpyAsync(rgb_out, res, n * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+        if (rgba8_out) HIPCHK(c, hipMemcpyAsync(rgba8_out, c->dn_rgba.p, n * sizeof(uchar4), hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return wf_check_dropped(c);
+}
+
+int crt_read_gbuffer(crt_ctx *c, float *out)
+{
+    if (!c || !out) return CRT_EINVAL;
+    { int rc = dn_check_state(c, "crt_read_gbuffer"); if (rc) return rc; }
+    HIPCHK(c, hipSetDevice(c->device));
+    { int rc_ = wf_flush(c); if (rc_) return rc_; }
+    const size_t n = (size_t)c->tw * c->th;
+    if (n) {
+        { int rc = dn_ensure_gbuffer(c); if (rc) return rc; }
+        HIPCHK(c, hipMemcpyAsync(out, c->dn_gbuf.p, n * 2 * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return wf_check_dropped(c);
 }
 
 int crt_debug_intersect(crt_ctx *c, const float *rays, size_t n, float *out)

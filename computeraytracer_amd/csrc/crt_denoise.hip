@@ -1,0 +1,181 @@
+// crt_denoise.hip -- the denoised preview (include/crt.h, crt_denoise): a first-hit G-buffer and an edge-aware
+// a-trous wavelet filter (Dammertz et al. 2010) over the accumulator's average.  It only READS the accumulator:
+// the bit-exact image and everything that produces it are untouched.  DESIGN.md "Denoised preview" has the
+// definition this follows operation by operation (tests/denoise_ref.py is its numpy restatement).
+#include <algorithm>
+
+#include "crt_shade.h"
+
+namespace crt {
+
+// Per tile pixel: gbuf[2p] = (t, position), gbuf[2p+1] = (normal, hit index bits) -- crt_debug_intersect's record,
+// so the readback is a copy -- and key[p] = material << 24 | reflectance index (kNoHit: the ray left the scene).
+struct DnParams {
+    const float4 *c_in;         // linear rgb (w unused) of the previous iteration
+    float4 *c_out;              // ... of this one (w = 0)
+    const float4 *gbuf;
+    const uint32_t *key;
+    uchar4 *rgba;               // null, or the rgba8 of c_out (last iteration)
+    uint32_t tw, th, step;      // step = 2^i
+    float inv_c;                // 2^i / sigma_color^2
+    float inv_n;                // 1 / sigma_normal^2
+    float inv_x;                // 1 / sigma_plane
+};
+
+// The primary ray of sample kDnSample of each pixel: its stratum (8 + r) / 16 lies within 1/16 pixel of the
+// pixel's centre on both axes, and it is a pure function of (x, y).
+constexpr uint32_t kDnSample = 8;
+
+// grid = tiles_x * tiles_y blocks of 64 threads, block -> 8x8 pixel tile (spatially coherent rays, like k_trace).
+__global__ __launch_bounds__(64) void k_dn_gbuffer(const DevScene S, uint32_t x0, uint32_t y0, uint32_t tw, uint32_t th,
+                                                  uint32_t tiles_x, float4 *__restrict__ gbuf, uint32_t *__restrict__ key, int brute)
+{
+    __shared__ int lds_stack[kStackDepth * 64];
+    const uint32_t lane = threadIdx.x;
+    const uint32_t lx = (blockIdx.x % tiles_x) * 8u + (lane & 7u), ly = (blockIdx.x / tiles_x) * 8u + (lane >> 3);
+    if (lx >= tw || ly >= th) return;
+    int *stk = lds_stack + lane;
+    const uint32_t px = x0 + lx, py = y0 + ly;
+    Rng rng;
+    f3 o, d;
+    primary_ray(S, px, py, kDnSample, tea(px, py * 100u), rng, o, d);
+    // the closest hit as k_debug_intersect finds it
+    float t_max = CRT_INFINITY;
+    uint32_t b_index = kNoHit, b_slot = kNoHit, cn = 0, cp = 0;
+    if (brute || !finite3(o) || !finite3(d)) intersect_all(S, o, d, 0xFFFFFFFFu, t_max, b_index, b_slot, cp);
+    else traverse<false>(S, stk, o, d, 0xFFFFFFFFu, false, t_max, b_index, b_slot, cn, cp);
+    f3 pos = f3{0, 0, 0}, nrm = f3{0, 0, 0};
+    uint32_t meta = 0, k = kNoHit;
+    if (b_slot != kNoHit) {
+        hit_attributes(S, b_slot, o, d, t_max, pos, nrm, meta);
+        k = (((meta >> 2) & 3u) << 24) | ((meta >> 18) & 0x3FFFu);    // material, reflectance index (data4.z, data4.y)
+    }
+    const size_t pix = (size_t)ly * tw + lx;
+    gbuf[2 * pix + 0] = float4{t_max, pos.x, pos.y, pos.z};
+    gbuf[2 * pix + 1] = float4{nrm.x, nrm.y, nrm.z, bits_f(b_slot != kNoHit ? b_index : kNoHit)};
+    key[pix] = k;
+}
+
+// The exposure curve of tonemap_rgba8: colour distances are measured where the image is displayed.
+__device__ __forceinline__ f3 dn_display(float4 c)
+{
+    return f3{1.0f - exp_(-2.2f * max_(c.x, 0.0f)), 1.0f - exp_(-2.2f * max_(c.y, 0.0f)), 1.0f - exp_(-2.2f * max_(c.z, 0.0f))};
+}
+
+// The filter's input: linear rgb of accum / n (the first half of tonemap_rgba8), and its rgba8 when no iteration follows.
+__global__ __launch_bounds__(256) void k_dn_prepare(const float4 *__restrict__ accum, float n, float4 *__restrict__ c,
+                                                    uchar4 *__restrict__ rgba, size_t npix)
+{
+    const size_t i = (size_t)blockIdx.x * 256u + threadIdx.x;
+    if (i >= npix) return;
+    const float4 a = accum[i];
+    const f3 rgb = xyz_to_linear_rgb(f3{a.x, a.y, a.z} / n);
+    c[i] = float4{rgb.x, rgb.y, rgb.z, 0.0f};
+    if (rgba) rgba[i] = linear_rgb_to_rgba8(rgb);
+}
+
+__device__ __forceinline__ bool finite4(float4 c)
+{
+    return abs_(c.x) <= 3.40282347e38f && abs_(c.y) <= 3.40282347e38f && abs_(c.z) <= 3.40282347e38f;
+}
+
+// One a-trous iteration: grid (ceil(tw/16), ceil(th/16)) blocks of 256 threads, block -> 16x16 pixels.  Taps at
+// step * (-2..2)^2 inside the tile; the centre pixel's guides stay in registers, a tap's guides are fetched only when
+// its key matches.
+__global__ __launch_bounds__(256) void k_dn_atrous(const DnParams P)
+{
+    const int x = (int)(blockIdx.x * 16u + (threadIdx.x & 15u)), y = (int)(blockIdx.y * 16u + (threadIdx.x >> 4));
+    const int tw = (int)P.tw, th = (int)P.th, s = (int)P.step;
+    if (x >= tw || y >= th) return;
+    const size_t p = (size_t)y * P.tw + (size_t)x;
+    const uint32_t key_p = P.key[p];
+    const bool hit = key_p != kNoHit;
+    f3 x_p = f3{0, 0, 0}, n_p = f3{0, 0, 0};
+    if (hit) {
+        const float4 g0 = P.gbuf[2 * p], g1 = P.gbuf[2 * p + 1];
+        x_p = f3{g0.y, g0.z, g0.w};
+        n_p = f3{g1.x, g1.y, g1.z};
+    }
+    const float4 cp4 = P.c_in[p];
+    const f3 t_p = dn_display(cp4);
+    const float h[5] = {1.0f / 16.0f, 1.0f / 4.0f, 3.0f / 8.0f, 1.0f / 4.0f, 1.0f / 16.0f};
+    float sw = 0.0f;
+    f3 sc = f3{0, 0, 0};
+#pragma unroll
+    for (int dy = -2; dy <= 2; dy++) {
+        const int qy = y + dy * s;
+        if (qy < 0 || qy >= th) continue;
+#pragma unroll
+        for (int dx = -2; dx <= 2; dx++) {
+            const int qx = x + dx * s;
+            if (qx < 0 || qx >= tw) continue;
+            if (dx == 0 && dy == 0) {                       // the centre: weight h[2]^2, every other factor is 1
+                sw = sw + h[2] * h[2];
+                sc = sc + f3{cp4.x, cp4.y, cp4.z} * (h[2] * h[2]);
+                continue;
+            }
+            const size_t q = (size_t)qy * P.tw + (size_t)qx;
+            if (P.key[q] != key_p) continue;
+            const float4 cq4 = P.c_in[q];
+            if (!finite4(cq4)) continue;
+            // (recomputed per tap: a stored dn_display(c) costs another 16 B per tap, and the pass is bound by tap traffic)
+            const f3 dt = t_p - dn_display(cq4);
+            float e = dot(dt, dt) * P.inv_c;
+            if (hit) {
+                const float4 g0 = P.gbuf[2 * q], g1 = P.gbuf[2 * q + 1];
+                const f3 dn = n_p - f3{g1.x, g1.y, g1.z};
+                e = e + dot(dn, dn) * P.inv_n;
+                const f3 v = f3{g0.y, g0.z, g0.w} - x_p;
+                if (v.x != 0.0f || v.y != 0.0f || v.z != 0.0f) e = e + (abs_(dot(n_p, v)) / length(v)) * P.inv_x;
+            }
+            const float w = (h[dx + 2] * h[dy + 2]) * exp_(-e);
+            sw = sw + w;
+            sc = sc + f3{cq4.x, cq4.y, cq4.z} * w;
+        }
+    }
+    const f3 c = sc / sw;
+    P.c_out[p] = float4{c.x, c.y, c.z, 0.0f};
+    if (P.rgba) P.rgba[p] = linear_rgb_to_rgba8(c);
+}
+
+// ---------------------------------------------------------------- launchers (called from crt_api.cpp)
+hipError_t dn_launch_gbuffer(const DevScene &S, uint32_t x0, uint32_t y0, uint32_t tw, uint32_t th, float4 *gbuf, uint32_t *key,
+                             int brute, hipStream_t stream)
+{
+    const uint32_t tiles_x = (tw + 7u) / 8u, tiles_y = (th + 7u) / 8u;
+    if (tiles_x * tiles_y == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_dn_gbuffer, dim3(tiles_x * tiles_y), dim3(64), 0, stream, S, x0, y0, tw, th, tiles_x, gbuf, key, brute);
+    return hipGetLastError();
+}
+
+// accum -> c[0], then `iterations` filter passes ping-ponging between c[0] and c[1]; the last launch also writes rgba.
+// Returns the buffer that holds the result through *out.
+hipError_t dn_launch_filter(const float4 *accum, float n, const float4 *gbuf, const uint32_t *key, float4 *c0, float4 *c1,
+                            uchar4 *rgba, uint32_t tw, uint32_t th, uint32_t iterations, float sigma_color, float sigma_normal,
+                            float sigma_plane, float4 **out, hipStream_t stream)
+{
+    const size_t npix = (size_t)tw * th;
+    *out = c0;
+    if (npix == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_dn_prepare, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, stream, accum, n, c0,
+                       iterations == 0 ? rgba : nullptr, npix);
+    hipError_t e = hipGetLastError();
+    float4 *buf[2] = {c0, c1};
+    for (uint32_t i = 0; i < iterations && e == hipSuccess; i++) {
+        DnParams P{};
+        P.c_in = buf[i & 1u]; P.c_out = buf[(i + 1u) & 1u];
+        P.gbuf = gbuf; P.key = key;
+        P.rgba = i + 1u == iterations ? rgba : nullptr;
+        P.tw = tw; P.th = th; P.step = 1u << i;
+        // (clamped to finite: 0 * inv must stay 0 for a tiny sigma)
+        P.inv_c = (float)std::min(3.0e38, (double)(1u << i) / ((double)sigma_color * sigma_color));
+        P.inv_n = (float)std::min(3.0e38, 1.0 / ((double)sigma_normal * sigma_normal));
+        P.inv_x = (float)std::min(3.0e38, 1.0 / (double)sigma_plane);
+        hipLaunchKernelGGL(k_dn_atrous, dim3((tw + 15u) / 16u, (th + 15u) / 16u), dim3(256), 0, stream, P);
+        e = hipGetLastError();
+        *out = P.c_out;
+    }
+    return e;
+}
+
+}  // namespace crt

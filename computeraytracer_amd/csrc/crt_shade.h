@@ -436,13 +436,19 @@ __device__ __forceinline__ void wave_add(unsigned long long *dst, uint32_t v)
 }
 
 
-// :110-115  average, XYZ->sRGB, exposure tone map, gamma (G-channel bug kept, Q10), rgba8unorm store
-__device__ __forceinline__ uchar4 tonemap_rgba8(f3 acc, float n_samples_f)
+// :110-115 in two halves: XYZ -> linear sRGB, then exposure tone map, gamma (G-channel bug kept, Q10), rgba8unorm
+// store.  crt_denoise filters between the two.
+__device__ __forceinline__ f3 xyz_to_linear_rgb(f3 avg)
 {
-    f3 avg = acc / n_samples_f;
     float rr = 3.2404542f * avg.x + -1.5371385f * avg.y + -0.4985314f * avg.z;
     float gg = -0.9692660f * avg.x + 1.8760108f * avg.y + 0.0415560f * avg.z;
     float bb = 0.0556434f * avg.x + -0.2040259f * avg.y + 1.0572252f * avg.z;
+    return f3{rr, gg, bb};
+}
+
+__device__ __forceinline__ uchar4 linear_rgb_to_rgba8(f3 rgb)
+{
+    float rr = rgb.x, gg = rgb.y, bb = rgb.z;
     rr = 1.0f - exp_(-rr * 2.2f);
     gg = 1.0f - exp_(-gg * 2.2f);
     bb = 1.0f - exp_(-bb * 2.2f);
@@ -450,6 +456,28 @@ __device__ __forceinline__ uchar4 tonemap_rgba8(f3 acc, float n_samples_f)
     gg = (gg < 0.0031308f) ? gg * (12.92f * gg) : 1.055f * pow_(gg, (float)(1.0 / 2.4)) - 0.055f;
     bb = (bb < 0.0031308f) ? 12.92f * bb : 1.055f * pow_(bb, (float)(1.0 / 2.4)) - 0.055f;
     return uchar4{unorm8(rr), unorm8(gg), unorm8(bb), 255};
+}
+
+// :110-115  average, then the two halves above
+__device__ __forceinline__ uchar4 tonemap_rgba8(f3 acc, float n_samples_f)
+{
+    return linear_rgb_to_rgba8(xyz_to_linear_rgb(acc / n_samples_f));
+}
+
+// The camera ray of (px, py, sample) (camera_ray :477-500 with the seed of :98); rng is left after the film
+// position's two draws.  tea_xy = tea(px, py * 100).
+__device__ __forceinline__ void primary_ray(const DevScene &S, uint32_t px, uint32_t py, uint32_t sample, uint32_t tea_xy,
+                                            Rng &rng, f3 &o, f3 &d)
+{
+    const f3 llc = f3{S.cam[0], S.cam[1], S.cam[2]}, hor = f3{S.cam[3], S.cam[4], S.cam[5]};
+    const f3 ver = f3{S.cam[6], S.cam[7], S.cam[8]}, eye = f3{S.cam[9], S.cam[10], S.cam[11]};
+    rng = Rng{py, px * 100u, sample, tea_xy};
+    float jx = rnd(rng);
+    float fs = ((float)px + ((float)(sample % kGrid) + jx) / (float)kGrid) / (float)S.W;
+    float jy = rnd(rng);
+    float ft = ((float)S.H - (float)py + ((float)(sample % kGrid) + jy) / (float)kGrid) / (float)S.H;
+    o = eye;
+    d = normalize(((llc + hor * fs) + ver * ft) - eye);
 }
 
 // spectral_to_xyz :419-426

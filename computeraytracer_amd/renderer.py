@@ -169,6 +169,26 @@ class Renderer:
         self._chk(self._lib.crt_set_stream(self._h, C.c_void_p(hip_stream or 0)))
         return self
 
+    # -- denoised preview (include/crt.h, "Denoised preview")
+    def denoise(self, iterations: int = 5, sigma_color: float = 1.0, sigma_normal: float = 0.5,
+                sigma_plane: float = 0.3, rgb: bool = False):
+        """The edge-aware a-trous filter of the accumulator's average: rgba8 (H, W, 4), or (rgba8, linear rgb
+        (H, W, 4) float32, channel 3 = pad) with rgb=True.  Reads the accumulator only; finishes what is in flight."""
+        _, _, tw, th = self.tile
+        p = _lib.DenoiseParams(int(iterations), float(sigma_color), float(sigma_normal), float(sigma_plane))
+        rgba = np.empty((th, tw, 4), np.uint8)
+        lin = np.empty((th, tw, 4), np.float32) if rgb else None
+        self._chk(self._lib.crt_denoise(self._h, C.byref(p), lin.ctypes.data if rgb else None, rgba.ctypes.data))
+        return (rgba, lin) if rgb else rgba
+
+    def read_gbuffer(self) -> np.ndarray:
+        """(H, W, 8) float32 per tile pixel: t, position, normal, hit index bits (0xFFFFFFFF = miss) of the primary
+        ray of sample 8 -- the crt_debug_intersect record."""
+        _, _, tw, th = self.tile
+        out = np.empty((th, tw, 8), np.float32)
+        self._chk(self._lib.crt_read_gbuffer(self._h, out.ctypes.data))
+        return out
+
     # -- multi-GPU: the frame across the ranks of a communicator (include/crt.h, "Multi-GPU")
     @staticmethod
     def comm_unique_id(local: bool = False) -> bytes:

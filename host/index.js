@@ -1,7 +1,8 @@
 #!/usr/bin/env node
 'use strict';
 // CLI: node host/index.js [--scene file.json] [--width W --height H] [--spp N] [--accel bvh2|lbvh|none]
-//                         [--out image.ppm] [--dump prefix] [--pack-only prefix]
+//                         [--out image.ppm] [--dump prefix] [--pack-only prefix] [--denoise K]
+// --denoise K: --out gets the image denoised with K a-trous iterations (crt_denoise) instead of the plain average
 const fs = require('fs');
 const { Main, writePPM } = require('./main');
 const sceneLoader = require('./sceneLoader');
@@ -37,7 +38,7 @@ r.run(spp, !args.unfused);
 const dt = Number(process.hrtime.bigint() - t0) / 1e9;
 const c = r.counters();
 const rgba = r.readRgba8();
-if (args.out) writePPM(args.out, rgba, r.width, r.height);
+if (args.out) writePPM(args.out, 'denoise' in args ? r.denoise({ iterations: num('denoise') }) : rgba, r.width, r.height);
 if (args.dump) {
   fs.writeFileSync(`${args.dump}.rgba8.bin`, Buffer.from(rgba.buffer));
   fs.writeFileSync(`${args.dump}.accum.bin`, Buffer.from(r.readAccum().buffer));

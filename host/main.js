@@ -10,6 +10,7 @@
  *   298-311 zero accumulator, sample = 0          (done by uploadScene / reset)
  *   597-611 per frame: dispatch(1); dispatch(W/8,H/8)   frame(): addon.trace(h, 1)
  *   612-617 blit to the canvas                    readRgba8() / writePPM()   (display only)
+ *           (no counterpart)                      denoise(): filtered preview of the same average
  *   620     requestAnimationFrame(frame) forever  run(spp): spp frames, optionally fused
  */
 const fs = require('fs');
@@ -58,6 +59,9 @@ function Main(options = {}) {
     get sample() { return a.sampleCount(device); },
     readAccum: () => a.readAccum(device),
     readRgba8: () => a.readRgba8(device),
+    // denoised preview of the current average (include/crt.h "Denoised preview"): rgba8 of the tile; reads only
+    denoise: (opts = {}) => a.denoise(device, opts),
+    readGbuffer: () => a.readGbuffer(device),
     counters: () => a.counters(device),
     enableCounters: (on) => a.enableCounters(device, !!on),
     lastTraceMs: () => a.lastTraceMs(device),

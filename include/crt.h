@@ -217,6 +217,30 @@ int crt_comm_destroy(crt_ctx *ctx);          /* also done by crt_destroy */
  * n_rows receives their number, global_rows (may be NULL) their indices.  band_rows = 0: contiguous strips. */
 int crt_layout_rows(uint32_t H, uint32_t band_rows, uint32_t parts, uint32_t part, uint32_t *n_rows, uint32_t *global_rows);
 
+/* ------------------------------------------------------------------ Denoised preview
+ * The reference shows one sample per frame (src/main.js:584-621): for the first hundreds of frames that is Monte-Carlo
+ * noise.  crt_denoise filters the accumulator's average with an edge-aware a-trous wavelet filter (Dammertz et al.
+ * 2010; DESIGN.md "Denoised preview" defines it), guided by the first hit of each pixel: the primary ray of sample 8
+ * (within 1/16 pixel of the pixel's centre), its position, normal and material key.  It only READS the accumulator and
+ * the sample count: alt_color_buffer, the rgba8 framebuffer, `sample` and the counters stay as they are.
+ * Both calls are sync points like crt_read_rgba8 (every pipelined batch is finished first).  CRT_ESTATE without a
+ * scene or accel structure, at sample 0, or under a row-band partition (crt_set_row_bands, crt_comm_partition with
+ * band_rows > 0: neighbouring local rows are not neighbouring image rows); a crt_set_tile rectangle is filtered on its
+ * own, its edges taken as image borders.  The G-buffer is built on first use and kept until crt_upload_scene,
+ * crt_build_accel, crt_set_tile or crt_set_row_bands. */
+typedef struct {
+    uint32_t iterations;   /* filter passes, step 2^i in pass i: 0..10 (0 = the plain average, as crt_read_rgba8) */
+    float sigma_color;     /* edge-stopping scales, all > 0 and finite */
+    float sigma_normal;
+    float sigma_plane;
+} crt_denoise_params;
+/* NULL params = defaults {5, 1.0, 0.5, 0.3}.  rgb_out: tw*th*4 floats (linear rgb + pad) or NULL; rgba8_out: tw*th*4
+ * bytes (the reference's colour tail: exposure, gamma, unorm8) or NULL.  CRT_EINVAL for iterations > 10 or a bad sigma. */
+int crt_denoise(crt_ctx *ctx, const crt_denoise_params *params, float *rgb_out, uint8_t *rgba8_out);
+/* The G-buffer: tw*th*8 floats, the crt_debug_intersect record per pixel (t, px,py,pz, nx,ny,nz, index_bits;
+ * index 0xFFFFFFFF = miss). */
+int crt_read_gbuffer(crt_ctx *ctx, float *out);
+
 /* Counters accumulate over crt_trace calls while enabled (off by default: the
  * counting kernel variant is slower). */
 int crt_enable_counters(crt_ctx *ctx, int on);
