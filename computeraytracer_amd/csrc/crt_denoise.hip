@@ -126,7 +126,9 @@ __global__ __launch_bounds__(256) void k_dn_atrous(const DnParams P)
                 const f3 dn = n_p - f3{g1.x, g1.y, g1.z};
                 e = e + dot(dn, dn) * P.inv_n;
                 const f3 v = f3{g0.y, g0.z, g0.w} - x_p;
-                if (v.x != 0.0f || v.y != 0.0f || v.z != 0.0f) e = e + (abs_(dot(n_p, v)) / length(v)) * P.inv_x;
+                // (length > 0, not v != 0: positions ~1e-24 apart give v != 0 with dot(v, v) = 0, and 0 / 0 = NaN)
+                const float len = length(v);
+                if (len > 0.0f) e = e + (abs_(dot(n_p, v)) / len) * P.inv_x;
             }
             const float w = (h[dx + 2] * h[dy + 2]) * exp_(-e);
             sw = sw + w;

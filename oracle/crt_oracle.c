@@ -918,6 +918,144 @@ int orc_intersect(const orc_scene *sc, const float o[3], const float d[3], uint3
     return 0;
 }
 
+/* ---------------------------------------------------------------- denoise */
+/* The denoised preview's f32 contract (DESIGN.md 6a "f32 contract"), restated op by op from the prose with this
+ * file's own dot3 / length3 / exp_ / colour tail.  It is this project's definition, not the reference's. */
+#define FLT_MAX_F 3.40282347e38f
+
+static inline int finite_rgb(const float *c)
+{
+    return abs_(c[0]) <= FLT_MAX_F && abs_(c[1]) <= FLT_MAX_F && abs_(c[2]) <= FLT_MAX_F;
+}
+
+/* T(c) = 1 - exp(-2.2 max(c, 0)) per channel */
+static inline v3 dn_display(const float *c)
+{
+    return V3(1.0f - exp_(-2.2f * max_(c[0], 0.0f)), 1.0f - exp_(-2.2f * max_(c[1], 0.0f)),
+              1.0f - exp_(-2.2f * max_(c[2], 0.0f)));
+}
+
+static inline float dn_inv(double num, double den)
+{
+    double v = num / den;
+    return (float)(v < 3.0e38 ? v : 3.0e38);
+}
+
+/* material << 24 | reflectance index of the hit primitive (data4.z, data4.y), 0xFFFFFFFF on a miss */
+int orc_denoise_keys(const orc_scene *sc, const float *gbuf, size_t npix, uint32_t *key)
+{
+    if (!sc || !sc->primitives || !gbuf || !key) return -1;
+    for (size_t p = 0; p < npix; p++) {
+        uint32_t idx = f_bits(gbuf[p * 8 + 7]);
+        if (idx == MAX_U32) { key[p] = MAX_U32; continue; }
+        if (idx >= sc->nprim) return -1;
+        prim_t pr = load_prim(sc->primitives, idx);
+        key[p] = (pr.material << 24) | pr.reflectance;
+    }
+    return 0;
+}
+
+int orc_denoise(const orc_scene *sc, const float *accum, uint32_t sample, const float *gbuf, uint32_t w,
+                uint32_t h, uint32_t iterations, float sigma_color, float sigma_normal, float sigma_plane,
+                float *rgb_out, uint8_t *rgba8_out, int nthreads)
+{
+    if (!sc || !sc->primitives || !accum || !gbuf || sample == 0 || iterations > 10u) return -1;
+    const size_t npix = (size_t)w * h;
+    if (npix == 0) return 0;
+    static const float hk[5] = {1.0f / 16.0f, 1.0f / 4.0f, 3.0f / 8.0f, 1.0f / 4.0f, 1.0f / 16.0f};
+    uint32_t *key = malloc(npix * sizeof *key);
+    float *buf[2] = {malloc(npix * 4 * sizeof(float)), malloc(npix * 4 * sizeof(float))};
+    int rc = 0;
+    if (!key || !buf[0] || !buf[1]) { rc = -1; goto done; }
+    if (orc_denoise_keys(sc, gbuf, npix, key) != 0) { rc = -1; goto done; }
+#ifdef _OPENMP
+    if (nthreads > 0) omp_set_num_threads(nthreads);
+#else
+    (void)nthreads;
+#endif
+    /* prepare: xyz_to_linear_rgb(accum / n), the division per component */
+    const float n = (float)sample;
+#pragma omp parallel for schedule(static)
+    for (int64_t p = 0; p < (int64_t)npix; p++) {
+        v3 rgb = xyz_to_linear_rgb(V3(accum[p * 4 + 0] / n, accum[p * 4 + 1] / n, accum[p * 4 + 2] / n));
+        float *c = buf[0] + p * 4;
+        c[0] = rgb.x; c[1] = rgb.y; c[2] = rgb.z; c[3] = 0.0f;
+    }
+    for (uint32_t i = 0; i < iterations; i++) {
+        const float *cin = buf[i & 1u];
+        float *cout = buf[(i + 1u) & 1u];
+        const int s = 1 << i;
+        const float inv_c = dn_inv((double)(1u << i), (double)sigma_color * sigma_color);
+        const float inv_n = dn_inv(1.0, (double)sigma_normal * sigma_normal);
+        const float inv_x = dn_inv(1.0, (double)sigma_plane);
+#pragma omp parallel for schedule(dynamic, 1)
+        for (int64_t yy = 0; yy < (int64_t)h; yy++) {
+            const int y = (int)yy;
+            for (int x = 0; x < (int)w; x++) {
+                const size_t p = (size_t)y * w + (size_t)x;
+                const uint32_t kp = key[p];
+                const int hit = kp != MAX_U32;
+                const float *gp = gbuf + p * 8;
+                const v3 xp = hit ? V3(gp[1], gp[2], gp[3]) : V3(0, 0, 0);
+                const v3 np_ = hit ? V3(gp[4], gp[5], gp[6]) : V3(0, 0, 0);
+                const float *cp = cin + p * 4;
+                const v3 tp = dn_display(cp);
+                float sw = 0.0f;
+                v3 acc = V3(0, 0, 0);
+                for (int dy = -2; dy <= 2; dy++) {
+                    const int qy = y + dy * s;
+                    if (qy < 0 || qy >= (int)h) continue;
+                    for (int dx = -2; dx <= 2; dx++) {
+                        const int qx = x + dx * s;
+                        if (qx < 0 || qx >= (int)w) continue;
+                        if (dx == 0 && dy == 0) {
+                            const float w0 = hk[2] * hk[2];
+                            sw = sw + w0;
+                            acc = add3(acc, mul3s(V3(cp[0], cp[1], cp[2]), w0));
+                            continue;
+                        }
+                        const size_t q = (size_t)qy * w + (size_t)qx;
+                        if (key[q] != kp) continue;
+                        const float *cq = cin + q * 4;
+                        if (!finite_rgb(cq)) continue;
+                        const v3 dt = sub3(tp, dn_display(cq));
+                        float e = dot3(dt, dt) * inv_c;
+                        if (hit) {
+                            const float *gq = gbuf + q * 8;
+                            const v3 dn = sub3(np_, V3(gq[4], gq[5], gq[6]));
+                            e = e + dot3(dn, dn) * inv_n;
+                            const v3 v = sub3(V3(gq[1], gq[2], gq[3]), xp);
+                            const float len = length3(v);
+                            if (len > 0.0f) e = e + (abs_(dot3(np_, v)) / len) * inv_x;
+                        }
+                        const float wt = (hk[dx + 2] * hk[dy + 2]) * exp_(-e);
+                        sw = sw + wt;
+                        acc = add3(acc, mul3s(V3(cq[0], cq[1], cq[2]), wt));
+                    }
+                }
+                float *co = cout + p * 4;
+                co[0] = acc.x / sw; co[1] = acc.y / sw; co[2] = acc.z / sw; co[3] = 0.0f;
+            }
+        }
+    }
+    {
+        const float *res = buf[iterations & 1u];
+        if (rgb_out) memcpy(rgb_out, res, npix * 4 * sizeof(float));
+        if (rgba8_out) {
+#pragma omp parallel for schedule(static)
+            for (int64_t p = 0; p < (int64_t)npix; p++) {
+                v3 ldr = tone_map(V3(res[p * 4 + 0], res[p * 4 + 1], res[p * 4 + 2]), 2.2f);
+                gamma_correct(&ldr);
+                rgba8_out[p * 4 + 0] = unorm8(ldr.x); rgba8_out[p * 4 + 1] = unorm8(ldr.y);
+                rgba8_out[p * 4 + 2] = unorm8(ldr.z); rgba8_out[p * 4 + 3] = 255;
+            }
+        }
+    }
+done:
+    free(key); free(buf[0]); free(buf[1]);
+    return rc;
+}
+
 int orc_max_threads(void)
 {
 #ifdef _OPENMP

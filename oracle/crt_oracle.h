@@ -95,6 +95,17 @@ float orc_hit_pad(const orc_scene *sc);
 /* Camera frame as hoisted to the host: 12 floats llc, horizontal, vertical, eye */
 void orc_camera_frame(const float camera[16], float out[12]);
 
+/* The denoised preview's filter (DESIGN.md 6a "f32 contract") on a w x h tile: accum (w*h*4 floats, XYZ sums),
+ * the sample count, and a G-buffer as crt_read_gbuffer returns it (w*h*8 floats: t, position, normal, hit index
+ * bits); keys come from sc's primitive records.  rgb_out: w*h*4 floats (channel 3 = +0), rgba8_out: w*h*4 bytes;
+ * either may be NULL.  Returns -1 on a bad argument or a hit index outside the scene.  nthreads<=0 -> all cores. */
+int orc_denoise(const orc_scene *sc, const float *accum, uint32_t sample, const float *gbuf, uint32_t w,
+                uint32_t h, uint32_t iterations, float sigma_color, float sigma_normal, float sigma_plane,
+                float *rgb_out, uint8_t *rgba8_out, int nthreads);
+
+/* The filter's per-pixel keys for npix G-buffer records (material << 24 | reflectance index, 0xFFFFFFFF = miss). */
+int orc_denoise_keys(const orc_scene *sc, const float *gbuf, size_t npix, uint32_t *key);
+
 /* Threads orc_render uses when nthreads <= 0. */
 int orc_max_threads(void);
 

@@ -78,6 +78,11 @@ def lib():
         L.orc_camera_frame.restype = None
         L.orc_camera_frame.argtypes = [C.c_void_p, C.c_void_p]
         L.orc_max_threads.restype = C.c_int
+        L.orc_denoise_keys.restype = C.c_int
+        L.orc_denoise_keys.argtypes = [C.POINTER(_Scene), C.c_void_p, C.c_size_t, C.c_void_p]
+        L.orc_denoise.restype = C.c_int
+        L.orc_denoise.argtypes = [C.POINTER(_Scene), C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32,
+                                  C.c_uint32, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_int]
         _lib = L
     return _lib
 
@@ -147,6 +152,30 @@ class Scene:
         lib().orc_intersect(C.byref(self.c), o.ctypes.data, d.ctypes.data, exclude, of.ctypes.data,
                             ou.ctypes.data)
         return of, ou
+
+    def denoise(self, accum, n, gbuf, iterations=5, sigma_color=1.0, sigma_normal=0.5, sigma_plane=0.3, nthreads=0):
+        """The denoised preview's filter in the f32 contract on accum (H, W, 4) XYZ sums of n samples,
+        guided by gbuf (H, W, 8) as crt_read_gbuffer returns it, with keys from this scene's primitives.
+        Returns (linear rgb (H, W, 4) f32, channel 3 = +0; rgba8 (H, W, 4) u8)."""
+        accum = np.ascontiguousarray(accum, np.float32)
+        gbuf = np.ascontiguousarray(gbuf, np.float32)
+        hh, ww = accum.shape[:2]
+        assert accum.shape == (hh, ww, 4) and gbuf.shape == (hh, ww, 8)
+        rgb = np.zeros((hh, ww, 4), np.float32)
+        rgba = np.zeros((hh, ww, 4), np.uint8)
+        rc = lib().orc_denoise(C.byref(self.c), accum.ctypes.data, int(n), gbuf.ctypes.data, ww, hh, int(iterations),
+                               sigma_color, sigma_normal, sigma_plane, rgb.ctypes.data, rgba.ctypes.data, nthreads)
+        if rc != 0:
+            raise RuntimeError("orc_denoise failed")
+        return rgb, rgba
+
+    def denoise_keys(self, gbuf):
+        """The filter's key per pixel of gbuf (H, W, 8): (H, W) uint32."""
+        gbuf = np.ascontiguousarray(gbuf, np.float32)
+        key = np.zeros(gbuf.shape[:2], np.uint32)
+        if lib().orc_denoise_keys(C.byref(self.c), gbuf.ctypes.data, key.size, key.ctypes.data) != 0:
+            raise RuntimeError("orc_denoise_keys failed")
+        return key
 
     def hit_pad(self) -> float:
         return float(lib().orc_hit_pad(C.byref(self.c)))

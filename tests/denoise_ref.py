@@ -39,11 +39,15 @@ def keys(gbuf, primitives):
     return k
 
 
-def atrous(c, pos, nrm, key, iterations=5, sigma_color=1.0, sigma_normal=0.5, sigma_plane=0.3, guides=True):
+def atrous(c, pos, nrm, key, iterations=5, sigma_color=1.0, sigma_normal=0.5, sigma_plane=0.3, guides=True,
+           magnitude=False):
     """K iterations of the edge-aware a-trous filter on linear rgb c (H, W, 3) with per-pixel position, normal
     (H, W, 3) and key (H, W).  guides=False: the same filter with colour weights only (no key, normal or plane
-    weights).  Taps outside the image are skipped; so is a tap other than the centre with a non-finite colour."""
+    weights).  Taps outside the image are skipped; so is a tap other than the centre with a non-finite colour.
+    magnitude=True also returns |c| carried through the same weights: the scale of the weighted sums, which bounds
+    what rounding them in float32 can change (the condition of the result)."""
     c = np.asarray(c, np.float64)[..., :3].copy()
+    m = np.abs(c)
     pos = np.asarray(pos, np.float64)
     nrm = np.asarray(nrm, np.float64)
     key = np.asarray(key)
@@ -55,6 +59,7 @@ def atrous(c, pos, nrm, key, iterations=5, sigma_color=1.0, sigma_normal=0.5, si
         fin = np.isfinite(c).all(-1)
         sw = np.zeros((hh, ww))
         sc = np.zeros((hh, ww, 3))
+        sm = np.zeros((hh, ww, 3))
         for dy in range(-2, 3):
             for dx in range(-2, 3):
                 oy, ox = dy * s, dx * s
@@ -66,6 +71,7 @@ def atrous(c, pos, nrm, key, iterations=5, sigma_color=1.0, sigma_normal=0.5, si
                 if dx == 0 and dy == 0:
                     sw[P] += w0
                     sc[P] += w0 * c[P]
+                    sm[P] += w0 * m[P]
                     continue
                 ok = fin[Q]
                 w = w0 * np.exp(-((t[P] - t[Q]) ** 2).sum(-1) / (sigma_color ** 2 * 2.0 ** -i))
@@ -80,8 +86,10 @@ def atrous(c, pos, nrm, key, iterations=5, sigma_color=1.0, sigma_normal=0.5, si
                 w = np.where(ok, w, 0.0)
                 sw[P] += w
                 sc[P] += w[..., None] * np.where(ok[..., None], c[Q], 0.0)
+                sm[P] += w[..., None] * np.where(ok[..., None], m[Q], 0.0)
         c = sc / sw[..., None]
-    return c
+        m = sm / sw[..., None]
+    return (c, m) if magnitude else c
 
 
 def atrous_gbuffer(c, gbuf, primitives, guides=True, **params):
@@ -107,3 +115,28 @@ def to_rgba8(c):
 def mse_display(a, b):
     """Mean squared error in display space T, over every pixel and channel."""
     return float(((display(a) - display(b)) ** 2).mean())
+
+
+def oracle_gbuffer(orc, ps, rect, full_log=True):
+    """The oracle's G-buffer of rect = (x0, y0, tw, th): the first ray of ray_log(x, y, 8), its t, normal and hit index
+    and orc.intersect's position.  full_log=False takes the camera ray from a scene without primitives (the ray depends
+    on the camera only) and everything else from orc.intersect: the same record without tracing whole paths through a
+    large scene on the CPU."""
+    x0, y0, tw, th = rect
+    sc = orc.Scene.from_packed(ps)
+    cam = sc if full_log else orc.Scene(ps.primitives[:0], ps.lights, ps.spectra, ps.cie, ps.camera)
+    out = np.zeros((th, tw, 8), np.float32)
+    hit = np.zeros((th, tw), bool)
+    for y in range(th):
+        for x in range(tw):
+            log = cam.ray_log(x0 + x, y0 + y, 8, cap=1)[0]
+            of, ou = sc.intersect(log[0:3], log[3:6])
+            if full_log:
+                out[y, x, 0], out[y, x, 4:7], out[y, x, 7] = log[8], log[9:12], log[7]
+                hit[y, x] = int(log[7:8].view(np.uint32)[0]) != MISS
+            else:
+                out[y, x, 0], out[y, x, 4:7] = of[0], of[4:7]
+                out[y, x, 7:8] = np.uint32([ou[1] if ou[0] else MISS]).view(np.float32)
+                hit[y, x] = bool(ou[0])
+            out[y, x, 1:4] = of[1:4]
+    return out, hit

@@ -10,40 +10,15 @@ import pytest
 
 import denoise_ref as ref
 from conftest import ROOT, bits
+from denoise_ref import oracle_gbuffer
 
 pytestmark = pytest.mark.gpu
 
-MAXU = 0xFFFFFFFF
 NODE = shutil.which("node")
 
 
 def _u32(a):
     return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-def oracle_gbuffer(orc, ps, rect, full_log=True):
-    """The oracle's G-buffer of rect = (x0, y0, tw, th): the first ray of ray_log(x, y, 8), its t, normal and hit index
-    and orc.intersect's position.  full_log=False takes the camera ray from a scene without primitives (the ray depends
-    on the camera only) and everything else from orc.intersect: the same record without tracing whole paths through a
-    large scene on the CPU."""
-    x0, y0, tw, th = rect
-    sc = orc.Scene.from_packed(ps)
-    cam = sc if full_log else orc.Scene(ps.primitives[:0], ps.lights, ps.spectra, ps.cie, ps.camera)
-    out = np.zeros((th, tw, 8), np.float32)
-    hit = np.zeros((th, tw), bool)
-    for y in range(th):
-        for x in range(tw):
-            log = cam.ray_log(x0 + x, y0 + y, 8, cap=1)[0]
-            of, ou = sc.intersect(log[0:3], log[3:6])
-            if full_log:
-                out[y, x, 0], out[y, x, 4:7], out[y, x, 7] = log[8], log[9:12], log[7]
-                hit[y, x] = int(_u32(log[7:8])[0]) != MAXU
-            else:
-                out[y, x, 0], out[y, x, 4:7] = of[0], of[4:7]
-                out[y, x, 7:8] = np.uint32([ou[1] if ou[0] else MAXU]).view(np.float32)
-                hit[y, x] = bool(ou[0])
-            out[y, x, 1:4] = of[1:4]
-    return out, hit
 
 
 def assert_gbuffer(g, want, hit):
