@@ -528,6 +528,54 @@ static napi_value js_read_gbuffer(napi_env env, napi_callback_info info)
     return ta;
 }
 
+/* ------------------------------------------------------------------ scene edits (include/crt.h "Scene edits")
+ * setCamera(h, camera: 16 floats), updatePrimitives(h, first, records: k*80 B), updateLights(h, first, records),
+ * refitAccel(h) -> true when the tree had to be rebuilt. */
+static napi_value js_set_camera(napi_env env, napi_callback_info info)
+{
+    ARGS(2)
+    crt_ctx *ctx = get_ctx(env, argv[0]);
+    if (!ctx) return NULL;
+    void *p = NULL; size_t n = 0;
+    if (!get_bytes(env, argv[1], &p, &n) || n != 64) {
+        napi_throw_type_error(env, NULL, "setCamera: camera must be 16 floats (64 bytes)");
+        return NULL;
+    }
+    CRT_CHECK(env, ctx, "crt_set_camera", crt_set_camera(ctx, (const float *)p));
+    return undefined(env);
+}
+
+static napi_value update_records(napi_env env, napi_callback_info info, int lights)
+{
+    ARGS(3)
+    crt_ctx *ctx = get_ctx(env, argv[0]);
+    if (!ctx) return NULL;
+    uint32_t first = 0;
+    NAPI_OK(env, napi_get_value_uint32(env, argv[1], &first));
+    void *p = NULL; size_t n = 0;
+    if (!get_bytes(env, argv[2], &p, &n) || n % 80) {
+        napi_throw_type_error(env, NULL, lights ? "updateLights: records must be k*80 bytes" : "updatePrimitives: records must be k*80 bytes");
+        return NULL;
+    }
+    if (lights) CRT_CHECK(env, ctx, "crt_update_lights", crt_update_lights(ctx, first, (uint32_t)(n / 80), p));
+    else CRT_CHECK(env, ctx, "crt_update_primitives", crt_update_primitives(ctx, first, (uint32_t)(n / 80), p));
+    return undefined(env);
+}
+static napi_value js_update_primitives(napi_env env, napi_callback_info info) { return update_records(env, info, 0); }
+static napi_value js_update_lights(napi_env env, napi_callback_info info) { return update_records(env, info, 1); }
+
+static napi_value js_refit_accel(napi_env env, napi_callback_info info)
+{
+    ARGS(1)
+    crt_ctx *ctx = get_ctx(env, argv[0]);
+    if (!ctx) return NULL;
+    int rebuilt = 0;
+    CRT_CHECK(env, ctx, "crt_refit_accel", crt_refit_accel(ctx, &rebuilt));
+    napi_value b;
+    NAPI_OK(env, napi_get_boolean(env, rebuilt != 0, &b));
+    return b;
+}
+
 /* ------------------------------------------------------------------ multi-GPU (include/crt.h "Multi-GPU") and composition
  * The reference drives one GPUDevice (src/main.js:8-9); a Node host reaches the tile-partitioned configurations through
  * these: one process (worker) per GPU, the communicator id made by one of them and passed around by the parent
@@ -873,6 +921,8 @@ static napi_value init(napi_env env, napi_value exports)
         {"setRowBands", js_set_row_bands}, {"deviceBuffers", js_device_buffers}, {"frameDeviceBuffers", js_frame_device_buffers},
         {"bindOutput", js_bind_output}, {"setStream", js_set_stream},
         {"denoise", js_denoise}, {"readGbuffer", js_read_gbuffer},
+        {"setCamera", js_set_camera}, {"updatePrimitives", js_update_primitives}, {"updateLights", js_update_lights},
+        {"refitAccel", js_refit_accel},
         {"gatherAsync", js_gather_async}, {"readFrameRgba8Async", js_read_frame_rgba8_async}, {"readFrameAccumAsync", js_read_frame_accum_async},
     };
     for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++) {

@@ -1,4 +1,4 @@
-"""python -m computeraytracer_amd [--scene file.json] [--width W --height H] [--spp N] [--out image.png] [--denoise K]"""
+"""python -m computeraytracer_amd [--scene file.json] [--width W --height H] [--spp N] [--out image.png] [--denoise K] [--orbit N]"""
 import argparse
 import json
 import os
@@ -18,13 +18,32 @@ def main():
     ap.add_argument("--checkpoint", default=None, help="resume from / save to this .npz")
     ap.add_argument("--denoise", type=int, default=None, metavar="K",
                     help="write the image denoised with K a-trous iterations (crt_denoise) instead of the plain average")
+    ap.add_argument("--orbit", type=int, default=None, metavar="N",
+                    help="N frames of --spp each with the eye turned about the look-at point (one upload and build, then "
+                         "set_camera per frame), written as OUT_000.png, OUT_001.png, ...")
     args = ap.parse_args()
+    if args.orbit is not None and (args.orbit < 1 or args.checkpoint):
+        ap.error("--orbit needs N >= 1 and no --checkpoint")
     sc = scene.load_scene(args.scene)
     if args.width:
         sc["camera"]["width"], sc["camera"]["height"] = args.width, args.height or args.width
     ps = scene.pack_scene(sc, base_dir=os.path.dirname(os.path.abspath(args.scene)) if args.scene else None)
     with Renderer(0) as r:
         r.upload(ps).build_accel(args.accel)
+        if args.orbit is not None:
+            base, ext = os.path.splitext(args.out)
+            outs, t0 = [], time.time()
+            for k, cam in enumerate(scene.orbit_cameras(ps.camera, args.orbit)):
+                r.set_camera(cam).frame(args.spp).sync()
+                rgba = r.read_rgba8() if args.denoise is None else r.denoise(args.denoise)
+                outs.append(f"{base}_{k:03d}{ext}")
+                (image.write_ppm if ext == ".ppm" else image.write_png)(outs[-1], rgba)
+            info = {"width": ps.width, "height": ps.height, "frames": args.orbit, "spp": args.spp,
+                    "seconds": round(time.time() - t0, 4), "out": outs}
+            if args.denoise is not None:
+                info["denoise"] = args.denoise
+            print(json.dumps(info))
+            return
         if args.checkpoint and os.path.exists(args.checkpoint):
             image.load_checkpoint(args.checkpoint, r)
         t0 = time.time()

@@ -68,6 +68,11 @@ SIGNATURES = {
     "crt_debug_intersect": (C.c_int, [_P, _P, C.c_size_t, _P]),
     "crt_debug_probes": (C.c_int, [_P, _P]),
     "crt_debug_math": (C.c_int, [_P, C.c_int, _P, _P, _P, C.c_size_t]),
+    "crt_set_camera": (C.c_int, [_P, _P]),
+    "crt_update_primitives": (C.c_int, [_P, C.c_uint32, C.c_uint32, _P]),
+    "crt_update_lights": (C.c_int, [_P, C.c_uint32, C.c_uint32, _P]),
+    "crt_refit_accel": (C.c_int, [_P, _P]),
+    "crt_debug_hit_pad": (C.c_int, [_P, _P]),
 }
 
 

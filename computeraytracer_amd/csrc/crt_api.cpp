@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cfloat>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -42,6 +43,16 @@ hipError_t dn_launch_gbuffer(const DevScene &S, uint32_t x0, uint32_t y0, uint32
 hipError_t dn_launch_filter(const float4 *accum, float n, const float4 *gbuf, const uint32_t *key, float4 *c0, float4 *c1,
                             uchar4 *rgba, uint32_t tw, uint32_t th, uint32_t iterations, float sigma_color, float sigma_normal,
                             float sigma_plane, float4 **out, hipStream_t stream);
+hipError_t refit_launch_pad(const unsigned char *raw, uint32_t n, uint32_t *out, hipStream_t s);
+hipError_t refit_launch_prims(const unsigned char *raw, uint32_t first, uint32_t count, const uint32_t *slot_of_index, float4 *prim,
+                              float4 *primD, hipStream_t s);
+hipError_t refit_levels(const void *nodes, uint32_t width, bool quantised, int root, uint32_t cap, int *list, uint32_t *counter,
+                        uint32_t *nch, std::vector<uint32_t> &off, hipStream_t s);
+hipError_t refit_launch_bvh2(const float4 *prim, float pad, const int *list, const std::vector<uint32_t> &off, float *nodes, hipStream_t s);
+hipError_t refit_launch_wide(const float4 *prim, float pad, const int *list, const std::vector<uint32_t> &off, const void *refs,
+                             bool quantised, const uint32_t *nch, float *fb, hipStream_t s);
+hipError_t refit_launch_quant4(const float *fb, const uint32_t *nch, uint32_t n4, uint4 *nodes4q, const double base[3], const double scale[3],
+                               hipStream_t s);
 }  // namespace crt
 
 using namespace crt;
@@ -92,6 +103,12 @@ struct DevBuf {
         return hipSuccess;
     }
     void release() { if (p) (void)hipFree(p); p = nullptr; n = 0; }
+};
+
+// A device buffer that goes with its scope.
+template <typename T>
+struct ScopedBuf : DevBuf<T> {
+    ~ScopedBuf() { this->release(); }
 };
 
 }  // namespace
@@ -214,6 +231,16 @@ struct crt_ctx {
     bool dn_valid = false;
     DevBuf<float4> dn_c[2];
     DevBuf<uchar4> dn_rgba;
+
+    // scene edits (crt_refit.hip)
+    float s_prims = 0.0f;           // max |corner coordinate| of the primitives: hit_pad = max(s_prims, |eye|) * 2^-17
+    float tree_pad = 0.0f;          // the hit_pad the tree's boxes were made with (a larger one needs a refit)
+    bool accel_stale = false;       // primitives changed since the tree's boxes were made: crt_refit_accel / crt_build_accel
+    bool rf_ready = false;          // the level lists below belong to the current tree
+    DevBuf<int> rf_lv2, rf_lv4;     // inner nodes of the BVH2 / the 4-wide tree, level by level from the root ...
+    std::vector<uint32_t> rf_off2, rf_off4;   // ... level l = list[off[l] .. off[l+1])
+    DevBuf<uint32_t> rf_nch4, rf_cnt;         // children per 4-wide node; a counter
+    DevBuf<float> rf_fb;            // float boxes of the quantised 4-wide tree (32 floats per node)
 };
 
 namespace {
@@ -286,7 +313,8 @@ int prim_corners(const HostPrim &p, f3 out[4])
     return 3;
 }
 
-float scene_hit_pad(const std::vector<HostPrim> &prims, const float cam[16])
+// scene_hit_pad in two steps: the primitives' part (cached as crt_ctx::s_prims; k_refit_pad on the device) and the eye's.
+float prims_scale(const std::vector<HostPrim> &prims)
 {
     float S = 0.0f;
     f3 c[4];
@@ -296,8 +324,24 @@ float scene_hit_pad(const std::vector<HostPrim> &prims, const float cam[16])
             S = max_(S, abs_(c[k].x)); S = max_(S, abs_(c[k].y)); S = max_(S, abs_(c[k].z));
         }
     }
+    return S;
+}
+
+float pad_of(float S, const float cam[16])
+{
     S = max_(S, abs_(cam[0])); S = max_(S, abs_(cam[1])); S = max_(S, abs_(cam[2]));
     return S * 7.62939453125e-06f;  // 2^-17
+}
+
+float scene_hit_pad(const std::vector<HostPrim> &prims, const float cam[16]) { return pad_of(prims_scale(prims), cam); }
+
+// The device rows of one light record (crt_upload_scene, crt_update_lights).
+void light_rows(const HostPrim &l, float4 out[3])
+{
+    float light_area = length(l.d2) * length(l.d3);              // :363
+    out[0] = float4{l.d1.x, l.d1.y, l.d1.z, bits_f(l.emission)};
+    out[1] = float4{l.d2.x, l.d2.y, l.d2.z, bits_f(l.index)};
+    out[2] = float4{l.d3.x, l.d3.y, l.d3.z, 1.0f / light_area};       // :364
 }
 
 // ComputeShader.wgsl:470-487, everything independent of the pixel.
@@ -509,6 +553,15 @@ int upload_geometry(crt_ctx *c, int mode)
     for (const HostPrim &hp_ : c->prims) c->sc.npatch += hp_.category == 0u ? 1u : 0u;
     c->accel_mode = mode;
     return CRT_OK;
+}
+
+// upload_geometry plus the scene-edit bookkeeping: a new tree is fresh, its boxes made with the current hit_pad.
+int build_tree(crt_ctx *c, int mode)
+{
+    c->rf_ready = false;
+    const int rc = upload_geometry(c, mode);
+    if (rc == CRT_OK) { c->accel_stale = false; c->tree_pad = c->sc.hit_pad; }
+    return rc;
 }
 
 
@@ -1620,6 +1673,7 @@ void crt_destroy(crt_ctx *c)
     c->w_nee.release(); for (uint32_t b = 0; b < kWfRing; b++) c->w_staging[b].release(); c->w_rng.release(); c->w_misc.release(); c->w_hit.release();
     c->w_vis.release(); c->w_dead.release(); c->w_recA.release(); c->w_recB.release(); c->w_recC.release(); c->w_tea.release(); c->w_wq.release();
     c->dn_gbuf.release(); c->dn_key.release(); c->dn_c[0].release(); c->dn_c[1].release(); c->dn_rgba.release();
+    c->rf_lv2.release(); c->rf_lv4.release(); c->rf_nch4.release(); c->rf_cnt.release(); c->rf_fb.release();
     if (c->pub_stream) (void)hipStreamSynchronize(c->pub_stream);
     for (int f = 0; f < crt_ctx::kFinishStreams; f++) {
         if (c->fin_stream[f]) { (void)hipStreamSynchronize(c->fin_stream[f]); (void)hipStreamDestroy(c->fin_stream[f]); }
@@ -1700,7 +1754,10 @@ int crt_upload_scene(crt_ctx *c, const void *primitives, size_t nprim, const voi
     S.nspectra = (uint32_t)nspectra;
     S.nlight = (uint32_t)nlight;
     S.inv_nlight = 1.0f / (float)S.nlight;                       // :372-373
-    S.hit_pad = scene_hit_pad(c->prims, c->camera);
+    c->s_prims = prims_scale(c->prims);
+    S.hit_pad = pad_of(c->s_prims, c->camera);                  // = scene_hit_pad(c->prims, c->camera)
+    c->accel_stale = false;
+    c->rf_ready = false;
     S.nf_last[0] = S.nf_last[1] = kNoHit;
     for (size_t i = c->prims.size(); i-- > 0 && S.nf_last[1] == kNoHit;)
         if (c->prims[i].category != 2u) (S.nf_last[0] == kNoHit ? S.nf_last[0] : S.nf_last[1]) = (uint32_t)i;
@@ -1713,13 +1770,7 @@ int crt_upload_scene(crt_ctx *c, const void *primitives, size_t nprim, const voi
     HIPCHK(c, c->d_cie.alloc(3 * kNCie));
     HIPCHK(c, hipMemcpy(c->d_cie.p, cie, 3 * kNCie * sizeof(float), hipMemcpyHostToDevice));
     std::vector<float4> hl(nlight * 3);
-    for (size_t i = 0; i < nlight; i++) {
-        const HostPrim &l = c->lights[i];
-        float light_area = length(l.d2) * length(l.d3);          // :363
-        hl[3 * i + 0] = float4{l.d1.x, l.d1.y, l.d1.z, bits_f(l.emission)};
-        hl[3 * i + 1] = float4{l.d2.x, l.d2.y, l.d2.z, bits_f(l.index)};
-        hl[3 * i + 2] = float4{l.d3.x, l.d3.y, l.d3.z, 1.0f / light_area};   // :364
-    }
+    for (size_t i = 0; i < nlight; i++) light_rows(c->lights[i], &hl[3 * i]);
     HIPCHK(c, c->d_lights.alloc(hl.size()));
     HIPCHK(c, hipMemcpy(c->d_lights.p, hl.data(), hl.size() * sizeof(float4), hipMemcpyHostToDevice));
     S.spectra = c->d_spectra.p; S.cie = c->d_cie.p; S.lights = c->d_lights.p;
@@ -1787,7 +1838,7 @@ int crt_build_accel(crt_ctx *c, int mode)
     // no structure to trace against (upload_geometry / build_accel_on_device set accel_mode on success only).
     c->accel_mode = -1;
     c->dn_valid = false;
-    return upload_geometry(c, mode);
+    return build_tree(c, mode);
 }
 
 int crt_reset(crt_ctx *c)
@@ -1804,6 +1855,7 @@ int crt_trace(crt_ctx *c, uint32_t n_samples)
     if (!c) return CRT_EINVAL;
     if (!c->have_scene) return fail(c, CRT_ESTATE, "crt_trace: upload a scene first");
     if (c->accel_mode < 0) return fail(c, CRT_ESTATE, "crt_trace: call crt_build_accel first");
+    if (c->accel_stale) return fail(c, CRT_ESTATE, "crt_trace: primitives were updated: call crt_refit_accel or crt_build_accel first");
     HIPCHK(c, hipSetDevice(c->device));
     if ((size_t)c->tw * c->th != 0 && (!accum_ptr(c) || !rgba_ptr(c)))
         return fail(c, CRT_ENOMEM, "crt_trace: the tile's output buffers are not allocated (an earlier crt_set_tile / crt_set_row_bands failed)");
@@ -2161,6 +2213,7 @@ int crt_set_option(crt_ctx *c, const char *name, int64_t value)
 static int dn_check_state(crt_ctx *c, const char *what)
 {
     if (!c->have_scene || c->accel_mode < 0) return fail(c, CRT_ESTATE, "%s: scene + accel required", what);
+    if (c->accel_stale) return fail(c, CRT_ESTATE, "%s: primitives were updated: call crt_refit_accel or crt_build_accel first", what);
     if (c->sample == 0) return fail(c, CRT_ESTATE, "%s: no sample traced yet", what);
     if (c->band != 0x40000000u)
         return fail(c, CRT_ESTATE, "%s: not under a row-band partition (neighbouring local rows are not neighbouring image rows)", what);
@@ -2227,6 +2280,7 @@ int crt_debug_intersect(crt_ctx *c, const float *rays, size_t n, float *out)
 {
     if (!c || (!rays && n) || (!out && n)) return CRT_EINVAL;
     if (!c->have_scene || c->accel_mode < 0) return fail(c, CRT_ESTATE, "crt_debug_intersect: scene + accel required");
+    if (c->accel_stale) return fail(c, CRT_ESTATE, "crt_debug_intersect: primitives were updated: call crt_refit_accel or crt_build_accel first");
     HIPCHK(c, hipSetDevice(c->device));
     DevBuf<float> din, dout;
     HIPCHK(c, din.alloc(n * 8));
@@ -2255,6 +2309,202 @@ int crt_debug_math(crt_ctx *c, int fn, const float *a, const float *b, float *ou
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     da.release(); db.release(); dout.release();
     if (e != hipSuccess) return fail(c, CRT_EDEVICE, "crt_debug_math: %s", hipGetErrorString(e));
+    return CRT_OK;
+}
+
+// ---------------------------------------------------------------- scene edits (crt_refit.hip)
+// Every edit call starts as a sync point (what is in flight finishes against the old scene) ...
+static int edit_begin(crt_ctx *c)
+{
+    HIPCHK(c, hipSetDevice(c->device));
+    { int rc_ = wf_flush(c); if (rc_) return rc_; }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return CRT_OK;
+}
+
+// ... and ends as crt_reset does: accumulator zeroed, sample 0, frame ring emptied; the G-buffer is rebuilt on next use.
+// Tile, row bands, bound outputs, stream, options and a communicator partition stay.
+static int edit_end(crt_ctx *c)
+{
+    c->dn_valid = false;
+    return zero_state(c);
+}
+
+// Recompute every box of the current tree from the current primitives and hit_pad, its topology kept (BVH2, and the
+// 4-wide tree: float boxes, quantised planes on a re-derived grid).  Rebuilt instead, with the builder that made the
+// tree, where a refit cannot serve: an 8-wide tree, or refitted boxes that quantize_bvh4's rule refuses.  The host
+// copies c->bvh / bvh4 / bvh4q keep the boxes of the build; nothing re-derives device nodes from them (every option
+// that changes the tree takes effect at crt_build_accel, which builds from c->prims).
+static int refit_tree(crt_ctx *c, bool *rebuilt)
+{
+    *rebuilt = false;
+    if (c->accel_mode != CRT_ACCEL_BVH2) { c->accel_stale = false; return CRT_OK; }
+    if (c->bvh8q.ok) {
+        *rebuilt = true;
+        c->accel_mode = -1;
+        return build_tree(c, CRT_ACCEL_BVH2);
+    }
+    const float pad = c->sc.hit_pad;
+    const uint32_t n2 = c->bvh.n_inner, n4 = c->bvh4.n_inner;
+    if (n2 == 0 || c->sc.root < 0) { c->accel_stale = false; c->tree_pad = pad; return CRT_OK; }   // one primitive: a leaf, no box
+    const bool quant = c->sc.nodes4q != nullptr && n4 > 0;
+    const bool wide_float = n4 > 0 && c->bvh4.nodes.size() >= (size_t)n4 * kNode4Floats;   // the host build's float 4-wide tree
+    const bool wide = quant || wide_float;
+    const void *refs4 = quant ? (const void *)c->d_nodes4q.p : (const void *)c->d_nodes4.p;
+    if (!c->rf_ready) {                                  // once per tree: the level lists
+        HIPCHK(c, c->rf_cnt.alloc(1));
+        HIPCHK(c, c->rf_lv2.alloc(n2));
+        HIPCHK(c, refit_levels(c->d_nodes.p, 2, false, c->sc.root, n2, c->rf_lv2.p, c->rf_cnt.p, nullptr, c->rf_off2, c->stream));
+        if (c->rf_off2.back() != n2) return fail(c, CRT_EDEVICE, "crt_refit_accel: the BVH2 has %u inner nodes, its levels list %u", n2, c->rf_off2.back());
+        if (wide) {
+            HIPCHK(c, c->rf_lv4.alloc(n4));
+            HIPCHK(c, c->rf_nch4.alloc(n4));
+            HIPCHK(c, refit_levels(refs4, 4, quant, 0, n4, c->rf_lv4.p, c->rf_cnt.p, c->rf_nch4.p, c->rf_off4, c->stream));
+            if (c->rf_off4.back() != n4) return fail(c, CRT_EDEVICE, "crt_refit_accel: the 4-wide tree has %u nodes, its levels list %u", n4, c->rf_off4.back());
+            if (!wide_float) HIPCHK(c, c->rf_fb.alloc((size_t)n4 * kNode4Floats));
+        }
+        c->rf_ready = true;
+    }
+    HIPCHK(c, refit_launch_bvh2(c->d_prim.p, pad, c->rf_lv2.p, c->rf_off2, (float *)c->d_nodes.p, c->stream));
+    if (wide) {
+        float *fb = wide_float ? (float *)c->d_nodes4.p : c->rf_fb.p;
+        HIPCHK(c, refit_launch_wide(c->d_prim.p, pad, c->rf_lv4.p, c->rf_off4, refs4, quant, c->rf_nch4.p, fb, c->stream));
+        if (quant) {
+            // quantize_bvh4's grid: the union of every box = the union of the root's children (each box is its children's union)
+            float root[kNode4Floats];
+            uint32_t k = 0;
+            HIPCHK(c, hipMemcpyAsync(root, fb, sizeof root, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipMemcpyAsync(&k, c->rf_nch4.p, 4, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+            float glo[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, ghi[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX}, base[3], scale[3];
+            bool ok = k > 0 && k <= 4;
+            for (uint32_t i = 0; ok && i < k; i++)
+                for (int a = 0; a < 3; a++) {
+                    const float l = root[4 * a + i], h = root[12 + 4 * a + i];
+                    if (!(l > -1.0e30f) || !(h < 1.0e30f)) ok = false;     // unbounded primitive: not quantisable
+                    glo[a] = std::min(glo[a], l); ghi[a] = std::max(ghi[a], h);
+                }
+            for (int a = 0; ok && a < 3; a++) {
+                const float ext = std::max(ghi[a] - glo[a], 1.0e-3f);
+                const float mag = std::max(std::fabs(glo[a]), std::fabs(ghi[a]));
+                if (mag > 16.0f * ext) ok = false;                          // too far from the origin for the slack
+                base[a] = glo[a]; scale[a] = ext / 65533.0f;
+            }
+            if (!ok) {
+                *rebuilt = true;
+                c->accel_mode = -1;
+                return build_tree(c, CRT_ACCEL_BVH2);
+            }
+            const double bd[3] = {base[0], base[1], base[2]}, sd[3] = {scale[0], scale[1], scale[2]};
+            HIPCHK(c, refit_launch_quant4(fb, c->rf_nch4.p, n4, c->d_nodes4q.p, bd, sd, c->stream));
+            for (int a = 0; a < 3; a++) { c->sc.qbase[a] = c->bvh4q.base[a] = base[a]; c->sc.qscale[a] = c->bvh4q.scale[a] = scale[a]; }
+        }
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->tree_pad = pad;
+    c->accel_stale = false;
+    return CRT_OK;
+}
+
+int crt_set_camera(crt_ctx *c, const float camera[16])
+{
+    if (!c) return CRT_EINVAL;
+    if (!camera) return fail(c, CRT_EINVAL, "crt_set_camera: camera is NULL");
+    if (!c->have_scene) return fail(c, CRT_ESTATE, "crt_set_camera: upload a scene first");
+    if (camera[11] != (float)c->W || camera[12] != (float)c->H)
+        return fail(c, CRT_EINVAL, "crt_set_camera: floats 11, 12 (width, height) must stay %u x %u (a size change is crt_upload_scene's)",
+                    c->W, c->H);
+    { int rc = edit_begin(c); if (rc) return rc; }
+    std::memcpy(c->camera, camera, sizeof c->camera);
+    camera_frame(c->camera, c->sc.cam);
+    c->sc.hit_pad = pad_of(c->s_prims, c->camera);               // = scene_hit_pad(c->prims, c->camera), no primitive scanned
+    if (c->accel_mode == CRT_ACCEL_BVH2 && !c->accel_stale && c->sc.hit_pad > c->tree_pad) {
+        bool rebuilt = false;                                     // a larger pad: the boxes must grow
+        int rc = refit_tree(c, &rebuilt);
+        if (rc) return rc;
+    }
+    return edit_end(c);
+}
+
+int crt_update_primitives(crt_ctx *c, uint32_t first, uint32_t count, const void *records)
+{
+    if (!c) return CRT_EINVAL;
+    if (!records && count) return fail(c, CRT_EINVAL, "crt_update_primitives: records is NULL");
+    if (!c->have_scene) return fail(c, CRT_ESTATE, "crt_update_primitives: upload a scene first");
+    const size_t n = c->prims.size();
+    if ((uint64_t)first + count > n)
+        return fail(c, CRT_EINVAL, "crt_update_primitives: range [%u, %llu) outside the scene's %zu primitives", first,
+                    (unsigned long long)first + count, n);
+    std::vector<HostPrim> np(count);
+    for (uint32_t k = 0; k < count; k++) {
+        const uint32_t i = first + k;
+        const HostPrim p = np[k] = read_prim((const uint8_t *)records, k), &o = c->prims[i];
+        if (p.index != i) return fail(c, CRT_EINVAL, "crt_update_primitives: record %u: index is %u, must equal the array position %u", k, p.index, i);
+        if (p.category != o.category || p.material != o.material)
+            return fail(c, CRT_EINVAL, "crt_update_primitives: primitive %u: category and material cannot change (a topology edit: crt_upload_scene)", i);
+        if (p.emission >= c->sc.nspectra || p.reflectance >= c->sc.nspectra)
+            return fail(c, CRT_EINVAL, "crt_update_primitives: primitive %u: spectrum index out of range", i);
+    }
+    { int rc = edit_begin(c); if (rc) return rc; }
+    std::copy(np.begin(), np.end(), c->prims.begin() + first);   // the host SAH builder reads these
+    if (count) {
+        HIPCHK(c, hipMemcpyAsync(c->d_raw.p + (size_t)first * 80, records, (size_t)count * 80, hipMemcpyHostToDevice, c->stream));   // the LBVH builder's input
+        if (c->accel_mode >= 0)                                  // the leaf-ordered records, in their slots
+            HIPCHK(c, refit_launch_prims(c->d_raw.p, first, count, c->d_slot_of_index.p, c->d_prim.p, c->d_primD.p, c->stream));
+    }
+    ScopedBuf<uint32_t> s;
+    HIPCHK(c, s.alloc(1));
+    HIPCHK(c, refit_launch_pad(c->d_raw.p, (uint32_t)n, s.p, c->stream));
+    uint32_t sb = 0;
+    HIPCHK(c, hipMemcpyAsync(&sb, s.p, 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->s_prims = bits_f(sb);
+    c->sc.hit_pad = pad_of(c->s_prims, c->camera);
+    if (c->accel_mode == CRT_ACCEL_BVH2) c->accel_stale = true;  // (CRT_ACCEL_NONE: no tree to go stale)
+    return edit_end(c);
+}
+
+int crt_update_lights(crt_ctx *c, uint32_t first, uint32_t count, const void *records)
+{
+    if (!c) return CRT_EINVAL;
+    if (!records && count) return fail(c, CRT_EINVAL, "crt_update_lights: records is NULL");
+    if (!c->have_scene) return fail(c, CRT_ESTATE, "crt_update_lights: upload a scene first");
+    if ((uint64_t)first + count > c->lights.size())
+        return fail(c, CRT_EINVAL, "crt_update_lights: range [%u, %llu) outside the scene's %zu lights", first,
+                    (unsigned long long)first + count, c->lights.size());
+    std::vector<HostPrim> nl(count);
+    for (uint32_t k = 0; k < count; k++) {
+        nl[k] = read_prim((const uint8_t *)records, k);
+        if (nl[k].emission >= c->sc.nspectra) return fail(c, CRT_EINVAL, "crt_update_lights: light %u: emission index out of range", first + k);
+    }
+    { int rc = edit_begin(c); if (rc) return rc; }
+    std::copy(nl.begin(), nl.end(), c->lights.begin() + first);
+    std::vector<float4> hl((size_t)count * 3);
+    for (uint32_t k = 0; k < count; k++) light_rows(nl[k], &hl[3 * (size_t)k]);
+    if (count) {
+        HIPCHK(c, hipMemcpyAsync(c->d_lights.p + 3 * (size_t)first, hl.data(), hl.size() * sizeof(float4), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    return edit_end(c);
+}
+
+int crt_refit_accel(crt_ctx *c, int *rebuilt)
+{
+    if (rebuilt) *rebuilt = 0;
+    if (!c) return CRT_EINVAL;
+    if (!c->have_scene) return fail(c, CRT_ESTATE, "crt_refit_accel: upload a scene first");
+    { int rc = edit_begin(c); if (rc) return rc; }
+    bool rb = false;
+    { int rc = refit_tree(c, &rb); if (rc) return rc; }
+    if (rebuilt) *rebuilt = rb ? 1 : 0;
+    return edit_end(c);
+}
+
+int crt_debug_hit_pad(crt_ctx *c, float *out)
+{
+    if (!c || !out) return CRT_EINVAL;
+    if (!c->have_scene) return fail(c, CRT_ESTATE, "crt_debug_hit_pad: no scene");
+    *out = c->sc.hit_pad;
     return CRT_OK;
 }
 

@@ -24,6 +24,7 @@
 
 #include "crt_bvh.h"
 #include "crt_math.h"
+#include "crt_prim.h"
 
 namespace crt {
 namespace {
@@ -228,21 +229,6 @@ hipError_t build_lbvh(const float *lo, const float *hi, uint32_t n, Bvh &out, hi
 // crt_api.cpp upload_geometry), so the kernels and the image are the same.
 namespace {
 
-struct RawPrim { uint32_t category; f3 d1, d2, d3; uint32_t emission, reflectance, material, index; };
-
-__device__ __forceinline__ RawPrim load_raw(const unsigned char *__restrict__ raw, size_t i)
-{
-    const uint4 *r = (const uint4 *)(raw + i * 80);
-    const uint4 a = r[0], b = r[1], c = r[2], d = r[3], e = r[4];
-    RawPrim p;
-    p.category = a.x;
-    p.d1 = f3{bits_f(b.x), bits_f(b.y), bits_f(b.z)};
-    p.d2 = f3{bits_f(c.x), bits_f(c.y), bits_f(c.z)};
-    p.d3 = f3{bits_f(d.x), bits_f(d.y), bits_f(d.z)};
-    p.emission = e.x; p.reflectance = e.y; p.material = e.z; p.index = e.w;
-    return p;
-}
-
 // order-preserving map float -> uint for atomicMin / atomicMax
 __device__ __forceinline__ uint32_t f_ord(float f) { const uint32_t u = f_bits(f); return (u & 0x80000000u) ? ~u : (u | 0x80000000u); }
 __host__ __device__ __forceinline__ float ord_f(uint32_t u) { return bits_f((u & 0x80000000u) ? (u & 0x7FFFFFFFu) : ~u); }
@@ -257,53 +243,12 @@ __global__ __launch_bounds__(256) void k_lbvh_prim_bounds(const unsigned char *_
     bool cvalid = false;
     if (i < n) {
         const RawPrim p = load_raw(raw, i);
-        const float S = pad * 131072.0f;
-        f3 cs[4];
-        int nc;
-        if (p.category == 1u) {
-            const float r = abs_(p.d2.x);
-            cs[0] = f3{p.d1.x - r, p.d1.y - r, p.d1.z - r}; cs[1] = f3{p.d1.x + r, p.d1.y + r, p.d1.z + r}; nc = 2;
-        } else {
-            cs[0] = p.d1; cs[1] = p.d1 + p.d2; cs[2] = p.d1 + p.d3; nc = 3;
-            if (p.category == 0u) { cs[3] = cs[1] + p.d3; nc = 4; }
-        }
-        float l[3] = {cs[0].x, cs[0].y, cs[0].z}, h[3] = {cs[0].x, cs[0].y, cs[0].z};
-        for (int k = 1; k < nc; k++) {
-            l[0] = fminf(l[0], cs[k].x); l[1] = fminf(l[1], cs[k].y); l[2] = fminf(l[2], cs[k].z);
-            h[0] = fmaxf(h[0], cs[k].x); h[1] = fmaxf(h[1], cs[k].y); h[2] = fmaxf(h[2], cs[k].z);
-        }
-        float g = 2.0f * pad;
-        if (p.category == 0u) {
-            const double e1[3] = {p.d2.x, p.d2.y, p.d2.z}, e2[3] = {p.d3.x, p.d3.y, p.d3.z};
-            const double g11 = e1[0] * e1[0] + e1[1] * e1[1] + e1[2] * e1[2];
-            const double g22 = e2[0] * e2[0] + e2[1] * e2[1] + e2[2] * e2[2];
-            const double g12 = e1[0] * e2[0] + e1[1] * e2[1] + e1[2] * e2[2];
-            const double det = g11 * g22 - g12 * g12;
-            if (!(det > 1e-9 * g11 * g22)) {
-                l[0] = l[1] = l[2] = -3.0e38f; h[0] = h[1] = h[2] = 3.0e38f;
-            } else {
-                const double P0[3] = {p.d1.x, p.d1.y, p.d1.z};
-                for (int k = 0; k < 4; k++) {
-                    const double a = (k & 1) ? g11 : 0.0, b = (k & 2) ? g22 : 0.0;
-                    const double al = (a * g22 - b * g12) / det, be = (b * g11 - a * g12) / det;
-                    for (int ax = 0; ax < 3; ax++) {
-                        const double v = P0[ax] + al * e1[ax] + be * e2[ax];
-                        l[ax] = fminf(l[ax], nextafterf((float)v, -INFINITY));
-                        h[ax] = fmaxf(h[ax], nextafterf((float)v, INFINITY));
-                    }
-                }
-            }
-        }
-        if (p.category == 1u) {
-            const float r = fabsf(p.d2.x);
-            g += (r > 0.0f) ? fminf(S * S * 9.5367431640625e-07f / r, S) : S;
-        }
+        float l[3], h[3];
+        prim_bounds(p.category, p.d1, p.d2, p.d3, pad, l, h);
         cvalid = true;
         for (int a = 0; a < 3; a++) {
-            if (!(l[a] == l[a]) || !(h[a] == h[a]) || isinf(l[a]) || isinf(h[a])) { l[a] = -3.0e38f; h[a] = 3.0e38f; }
-            const float lv = l[a] - g, hv = h[a] + g;
-            lo[3 * (size_t)i + a] = lv; hi[3 * (size_t)i + a] = hv;
-            c[a] = 0.5f * lv + 0.5f * hv;
+            lo[3 * (size_t)i + a] = l[a]; hi[3 * (size_t)i + a] = h[a];
+            c[a] = 0.5f * l[a] + 0.5f * h[a];
             if (!(c[a] > -1.0e30f && c[a] < 1.0e30f)) cvalid = false;
         }
     }
@@ -409,19 +354,8 @@ __global__ __launch_bounds__(256) void k_lbvh_gather_prims(const unsigned char *
     const uint32_t slot = blockIdx.x * 256u + threadIdx.x;
     if (slot >= n) return;
     const RawPrim p = load_raw(raw, (size_t)(keys[slot] & 0xFFFFFFFFull));
-    const uint32_t meta = (p.category & 3u) | ((p.material & 3u) << 2) | ((p.emission & 0x3FFFu) << 4) | ((p.reflectance & 0x3FFFu) << 18);
-    float4 A = {p.d1.x, p.d1.y, p.d1.z, bits_f(meta)};
-    float4 B = {p.d2.x, p.d2.y, p.d2.z, bits_f(p.index)};
-    float4 C = {p.d3.x, p.d3.y, p.d3.z, 0.0f};
-    float4 D = {0.0f, 0.0f, 0.0f, 0.0f};
-    if (p.category == 0u) {
-        const f3 nrm = normalize(cross(p.d2, p.d3));             // ComputeShader.wgsl:536
-        D = float4{nrm.x, nrm.y, nrm.z, dot(p.d2, p.d2)};        // :563 denominator
-        C.w = dot(p.d3, p.d3);                                   // :564 denominator
-    } else if (p.category == 1u) {
-        const float r = p.d2.x;                                  // :593-594
-        B = float4{r, r * r, 0.0f, bits_f(p.index)};
-    }
+    float4 A, B, C, D;
+    prim_record(p, A, B, C, D);
     prim[3 * (size_t)slot + 0] = A; prim[3 * (size_t)slot + 1] = B; prim[3 * (size_t)slot + 2] = C;
     primD[slot] = D;
     slot_of_index[p.index] = slot;

@@ -92,6 +92,49 @@ class Renderer:
         self._chk(self._lib.crt_set_option(self._h, name.encode(), int(value)))
         return self
 
+    # -- scene edits (include/crt.h, "Scene edits"): each finishes what is in flight and restarts the accumulation
+    def set_camera(self, camera):
+        """A new camera (16 floats as packed by scene.pack_camera; width and height unchanged)."""
+        cam = np.ascontiguousarray(camera, np.float32)
+        if cam.size != 16:
+            raise ValueError("camera must be 16 floats")
+        self._chk(self._lib.crt_set_camera(self._h, cam.ctypes.data))
+        if self.scene is not None:
+            self.scene = PackedScene(self.scene.primitives, self.scene.lights, cam.copy(), self.scene.spectra, self.scene.cie,
+                                     self.scene.patches, self.scene.spectrum_index)
+        return self
+
+    @staticmethod
+    def _records(records) -> np.ndarray:
+        rec = np.ascontiguousarray(records)
+        if rec.nbytes % 80:
+            raise ValueError("records must be a multiple of 80 bytes")
+        return rec
+
+    def update_primitives(self, first: int, records):
+        """Replace primitive records [first, first + len(records)); the tree goes stale until refit_accel()."""
+        rec = self._records(records)
+        self._chk(self._lib.crt_update_primitives(self._h, int(first), rec.nbytes // 80, rec.ctypes.data))
+        return self
+
+    def update_lights(self, first: int, records):
+        """Replace light records [first, first + len(records)) (e.g. scene.lights_of(edited primitives))."""
+        rec = self._records(records)
+        self._chk(self._lib.crt_update_lights(self._h, int(first), rec.nbytes // 80, rec.ctypes.data))
+        return self
+
+    def refit_accel(self) -> bool:
+        """Recompute the tree's boxes on the GPU; True when it had to be rebuilt instead."""
+        rebuilt = C.c_int()
+        self._chk(self._lib.crt_refit_accel(self._h, C.byref(rebuilt)))
+        return bool(rebuilt.value)
+
+    @property
+    def debug_hit_pad(self) -> float:
+        v = C.c_float()
+        self._chk(self._lib.crt_debug_hit_pad(self._h, C.byref(v)))
+        return v.value
+
     # -- frame()
     def frame(self, n_samples: int = 1):
         """n x { sample++ ; trace }  (asynchronous)."""

@@ -162,6 +162,41 @@ def lights_of(primitives: np.ndarray) -> np.ndarray:
     return sel
 
 
+def transform_records(records: np.ndarray, R, t, scale: float = 1.0) -> np.ndarray:
+    """A copy of 80-byte records moved rigidly: point -> R (s p) + t, vector -> R (s v), in float64, then float32.
+    Patches: origin moves, edges rotate and scale; spheres: centre moves, radius x s; triangles: v0 moves, edges
+    rotate and scale.  Index, category, material and spectra are untouched (crt_update_primitives' rules)."""
+    R = np.asarray(R, np.float64).reshape(3, 3)
+    t = np.asarray(t, np.float64).reshape(3)
+    s = float(scale)
+    src = np.ascontiguousarray(records, PRIM_DTYPE).reshape(-1)
+    out = src.view(np.uint8).copy().view(PRIM_DTYPE)          # (byte copy: the padding words come along as they were)
+    cat = out["category"]
+    d1 = out["data1"].astype(np.float64)
+    d2 = out["data2"].astype(np.float64)
+    d3 = out["data3"].astype(np.float64)
+    out["data1"] = ((s * d1) @ R.T + t).astype(np.float32)
+    sph = cat == CATEGORY["sphere"]
+    out["data2"] = np.where(sph[:, None], d2 * s, (s * d2) @ R.T).astype(np.float32)
+    out["data3"] = np.where(sph[:, None], d3, (s * d3) @ R.T).astype(np.float32)
+    return out
+
+
+def orbit_cameras(camera, n: int) -> np.ndarray:
+    """n cameras (n x 16 float32) whose eye turns about the look-at point around the up axis, k / n of a full turn for
+    k = 0 .. n-1; look-at, up, width, height and focal length kept."""
+    cam = np.asarray(camera, np.float32).reshape(16)
+    eye, look, up = cam[0:3].astype(np.float64), cam[4:7].astype(np.float64), cam[8:11].astype(np.float64)
+    k = up / np.linalg.norm(up)
+    v = eye - look
+    out = np.repeat(cam[None, :], n, axis=0)
+    for i in range(n):
+        a = 2.0 * math.pi * i / n
+        vr = v * math.cos(a) + np.cross(k, v) * math.sin(a) + k * np.dot(k, v) * (1.0 - math.cos(a))   # Rodrigues
+        out[i, 0:3] = (look + vr).astype(np.float32)
+    return out
+
+
 def parse_obj(text: str):
     """Minimal Wavefront OBJ reader: `v x y z` and `f a b c ...` (1-based, negative = relative,
     `a/b/c` forms accepted, polygons fan-triangulated).  Returns (vertices [n][3], triangles [m][3])."""

@@ -1,10 +1,12 @@
 #!/usr/bin/env node
 'use strict';
 // CLI: node host/index.js [--scene file.json] [--width W --height H] [--spp N] [--accel bvh2|lbvh|none]
-//                         [--out image.ppm] [--dump prefix] [--pack-only prefix] [--denoise K]
+//                         [--out image.ppm] [--dump prefix] [--pack-only prefix] [--denoise K] [--orbit N]
 // --denoise K: --out gets the image denoised with K a-trous iterations (crt_denoise) instead of the plain average
+// --orbit N: N frames of --spp each, the eye turned about the look-at point (one upload and build, then setCamera per
+//            frame), written as OUT_000.ppm, OUT_001.ppm, ...
 const fs = require('fs');
-const { Main, writePPM } = require('./main');
+const { Main, writePPM, orbitCameras } = require('./main');
 const sceneLoader = require('./sceneLoader');
 
 const args = {};
@@ -32,6 +34,19 @@ if (args['pack-only']) { // dump the packed host buffers (used by the packer par
 const spp = num('spp', 16);
 const r = Main({ sceneFile: args.scene, width: args.width ? num('width') : undefined, height: args.height ? num('height') : undefined,
   accel: args.accel || 'bvh2', device: num('device', 0) });
+if (args.orbit) {
+  const n = num('orbit'), base = String(args.out || 'orbit.ppm').replace(/\.ppm$/, ''), outs = [];
+  const t1 = process.hrtime.bigint();
+  orbitCameras(r.packed.camera, n).forEach((cam, k) => {
+    r.setCamera(cam);
+    r.run(spp);
+    outs.push(`${base}_${String(k).padStart(3, '0')}.ppm`);
+    writePPM(outs[k], 'denoise' in args ? r.denoise({ iterations: num('denoise') }) : r.readRgba8(), r.width, r.height);
+  });
+  console.log(JSON.stringify({ width: r.width, height: r.height, frames: n, spp, seconds: Number(process.hrtime.bigint() - t1) / 1e9, out: outs }));
+  r.destroy();
+  process.exit(0);
+}
 r.enableCounters(true);
 const t0 = process.hrtime.bigint();
 r.run(spp, !args.unfused);

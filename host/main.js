@@ -11,6 +11,7 @@
  *   597-611 per frame: dispatch(1); dispatch(W/8,H/8)   frame(): addon.trace(h, 1)
  *   612-617 blit to the canvas                    readRgba8() / writePPM()   (display only)
  *           (no counterpart)                      denoise(): filtered preview of the same average
+ *           queue.writeBuffer(camera / primitives / lights)   setCamera / updatePrimitives + refitAccel / updateLights
  *   620     requestAnimationFrame(frame) forever  run(spp): spp frames, optionally fused
  */
 const fs = require('fs');
@@ -62,12 +63,35 @@ function Main(options = {}) {
     // denoised preview of the current average (include/crt.h "Denoised preview"): rgba8 of the tile; reads only
     denoise: (opts = {}) => a.denoise(device, opts),
     readGbuffer: () => a.readGbuffer(device),
+    // scene edits (include/crt.h "Scene edits"): each finishes what is in flight and restarts the accumulation;
+    // the reference's queue.writeBuffer of the camera / primitive / light buffer
+    setCamera: (camera) => a.setCamera(device, camera),
+    updatePrimitives: (first, records) => a.updatePrimitives(device, first, records),
+    updateLights: (first, records) => a.updateLights(device, first, records),
+    refitAccel: () => a.refitAccel(device),
     counters: () => a.counters(device),
     enableCounters: (on) => a.enableCounters(device, !!on),
     lastTraceMs: () => a.lastTraceMs(device),
     accelStats: () => a.accelStats(device),
     destroy: () => a.destroy(device),
   };
+}
+
+// n cameras (Float32Array(16) each) whose eye turns about the look-at point around the up axis, k/n of a full turn for
+// k = 0..n-1 (Rodrigues' rotation in doubles); look-at, up, width, height and focal length kept (scene.orbit_cameras).
+function orbitCameras(camera, n) {
+  const e = [0, 1, 2].map((i) => camera[i]), l = [4, 5, 6].map((i) => camera[i]), u = [8, 9, 10].map((i) => camera[i]);
+  const un = Math.hypot(...u), k = u.map((x) => x / un), v = e.map((x, i) => x - l[i]);
+  const kxv = [k[1] * v[2] - k[2] * v[1], k[2] * v[0] - k[0] * v[2], k[0] * v[1] - k[1] * v[0]];
+  const kv = k[0] * v[0] + k[1] * v[1] + k[2] * v[2];
+  const out = [];
+  for (let j = 0; j < n; j++) {
+    const a = (2 * Math.PI * j) / n, c = Math.cos(a), s = Math.sin(a);
+    const cam = Float32Array.from(camera);
+    for (let i = 0; i < 3; i++) cam[i] = l[i] + (v[i] * c + kxv[i] * s + k[i] * kv * (1 - c));
+    out.push(cam);
+  }
+  return out;
 }
 
 // Binary PPM of the rgba8 framebuffer (row 0 = top, like the reference's blit).
@@ -79,4 +103,4 @@ function writePPM(file, rgba, width, height) {
   fs.writeFileSync(file, Buffer.concat([Buffer.from(`P6\n${width} ${height}\n255\n`), out]));
 }
 
-module.exports = { Main, writePPM, loadAddon };
+module.exports = { Main, writePPM, loadAddon, orbitCameras };

@@ -241,6 +241,38 @@ int crt_denoise(crt_ctx *ctx, const crt_denoise_params *params, float *rgb_out, 
  * index 0xFFFFFFFF = miss). */
 int crt_read_gbuffer(crt_ctx *ctx, float *out);
 
+/* ------------------------------------------------------------------ Scene edits
+ * Move the camera or edit primitives and lights of the uploaded scene in place (DESIGN.md "Scene edits"), instead of
+ * crt_upload_scene + crt_build_accel.  The tree's topology is kept; crt_refit_accel recomputes its boxes on the GPU.
+ * Culling never decides a hit, so the image equals the one a fresh upload and build of the edited buffers gives.
+ * Rules shared by the four edit calls (crt_set_camera, crt_update_primitives, crt_update_lights, crt_refit_accel):
+ *   - each is a sync point (what is in flight finishes first, against the old scene);
+ *   - then the frame state resets as crt_reset does: accumulator zeroed, sample 0, frame ring emptied;
+ *   - tile, row bands, bound outputs, stream, options and a crt_comm_partition stay (W and H never change: every rank
+ *     of a partitioned run makes the same call);
+ *   - the denoise G-buffer is rebuilt on next use;
+ *   - every input is validated before anything changes: on CRT_EINVAL the context is as it was.
+ * Out of scope: adding or removing primitives, changing a category or material, resolution changes (crt_upload_scene). */
+/* camera: 16 floats as for crt_upload_scene; floats 11, 12 must equal the current width and height.  hit_pad is
+ * recomputed as max(primitive scale, |eye|) * 2^-17 without scanning the primitives; a pad larger than the one the
+ * tree's boxes were made with refits the tree here (the caller need not). */
+int crt_set_camera(crt_ctx *ctx, const float camera[16]);
+/* Replace primitive records [first, first+count) (count x 80 bytes).  Each record's index must equal its position,
+ * its category and material must be unchanged, its spectrum indices < nspectra, and the range inside the scene.
+ * With a tree (CRT_ACCEL_BVH2 / LBVH) the tree becomes stale: crt_trace, crt_denoise, crt_read_gbuffer and
+ * crt_debug_intersect return CRT_ESTATE until crt_refit_accel or crt_build_accel.  Several updates may precede one
+ * refit.  Under CRT_ACCEL_NONE nothing goes stale. */
+int crt_update_primitives(crt_ctx *ctx, uint32_t first, uint32_t count, const void *records);
+/* Replace light records [first, first+count) (count x 80 bytes, crt_upload_scene's validation; 1/area recomputed). */
+int crt_update_lights(crt_ctx *ctx, uint32_t first, uint32_t count, const void *records);
+/* Recompute every box of the tree (BVH2 and 4-wide, float and quantised; the quantisation grid re-derived) from the
+ * current primitives, topology kept.  Rebuilds with the builder that made the tree instead, and sets *rebuilt = 1
+ * (rebuilt may be NULL), for an 8-wide tree (option "wf_width" = 8) or when the refitted boxes cannot be quantised.
+ * A no-op on the tree without one.  Clears the stale state, as crt_build_accel does. */
+int crt_refit_accel(crt_ctx *ctx, int *rebuilt);
+/* Test hook: the hit_pad the kernels use. */
+int crt_debug_hit_pad(crt_ctx *ctx, float *out);
+
 /* Counters accumulate over crt_trace calls while enabled (off by default: the
  * counting kernel variant is slower). */
 int crt_enable_counters(crt_ctx *ctx, int on);

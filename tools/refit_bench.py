@@ -1,0 +1,136 @@
+"""Scene edits (include/crt.h "Scene edits") on S2 (atrium250k) at 1920 x 1080 and on the 10 M-triangle soup: host clock
+around synchronous calls, warm, median of --reps.
+
+  build_lbvh_ms        crt_build_accel(CRT_ACCEL_LBVH)
+  refit_ms             crt_refit_accel after a crt_update_primitives (the update itself not timed)
+  update_ms            crt_update_primitives of the moved tenth (records, hit_pad reduction, state reset)
+  set_camera_ms        crt_set_camera with a pad that does not grow (no refit): sync + camera + state reset
+  set_camera_refit_ms  crt_set_camera with an eye farther out each call (the pad grows: inline refit)
+  step_ms_refit / step_ms_fresh   ms per --spp step after a rigid move of a contiguous tenth of the primitives,
+                       refitted tree against a fresh LBVH build of the same buffers (the tree-quality cost)
+
+Per-kernel times come from a separate run under rocprofv3 --kernel-trace --stats.  Prints one JSON line; --out also
+writes it."""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+import numpy as np  # noqa: E402
+
+from computeraytracer_amd import Renderer  # noqa: E402
+from computeraytracer_amd.scene import transform_records  # noqa: E402
+from computeraytracer_amd.scenes_synth import atrium250k, soup  # noqa: E402
+
+
+def timed(fn, reps, warm=3):
+    for _ in range(warm):
+        fn()
+    ts = []
+    for _ in range(reps):
+        t = time.perf_counter()
+        fn()
+        ts.append((time.perf_counter() - t) * 1e3)
+    return round(statistics.median(ts), 4)
+
+
+def run_scene(name, ps, reps, spp, steps):
+    n = len(ps.primitives)
+    first, cnt = n // 3, n // 10
+    th = 0.05
+    R = np.array([[np.cos(th), 0, np.sin(th)], [0, 1, 0], [-np.sin(th), 0, np.cos(th)]])
+    moved = ps.primitives.copy()
+    moved[first:first + cnt] = transform_records(moved[first:first + cnt], R, [6.0, 2.0, -4.0])
+    rec_a, rec_b = ps.primitives[first:first + cnt], moved[first:first + cnt]
+    res = {"scene": name, "primitives": n, "moved": cnt, "width": ps.width, "height": ps.height, "reps": reps}
+    r = Renderer(0)
+    try:
+        r.upload(ps)
+        res["build_lbvh_ms"] = timed(lambda: r.build_accel("lbvh"), reps)
+        flip = [0]
+
+        def update():
+            flip[0] ^= 1
+            r.update_primitives(first, rec_b if flip[0] else rec_a)
+
+        res["update_ms"] = timed(update, reps)
+        ts = []
+        for _ in range(reps + 3):
+            update()
+            t = time.perf_counter()
+            rebuilt = r.refit_accel()
+            ts.append((time.perf_counter() - t) * 1e3)
+            assert not rebuilt
+        res["refit_ms"] = round(statistics.median(ts[3:]), 4)
+        res["refit_speedup"] = round(res["build_lbvh_ms"] / res["refit_ms"], 2)
+        cam0 = ps.camera.copy()
+        look = cam0[4:7].astype(np.float64)
+        v = cam0[0:3].astype(np.float64) - look
+        near = [cam0.copy(), cam0.copy()]
+        near[1][0:3] = (look + 0.9 * v).astype(np.float32)
+        k = [0]
+
+        def cam_near():
+            k[0] ^= 1
+            r.set_camera(near[k[0]])
+
+        r.set_camera(cam0)
+        res["set_camera_ms"] = timed(cam_near, reps)
+        grow = [1.0]
+        far_scale = 1e6 / max(np.linalg.norm(v), 1.0)
+
+        def cam_far():
+            grow[0] *= 1.01
+            c = cam0.copy()
+            c[0:3] = (look + far_scale * grow[0] * v).astype(np.float32)   # |eye| beyond the scene and growing: refit
+            r.set_camera(c)
+
+        res["set_camera_refit_ms"] = timed(cam_far, reps)
+        # tree quality: the moved tenth, refitted, against a fresh build of the same buffers
+        r.set_camera(cam0)
+        r.update_primitives(first, rec_b)
+        r.refit_accel()
+
+        def steps_ms():
+            r.reset()
+            r.frame(spp).sync()
+            t = time.perf_counter()
+            for _ in range(steps):
+                r.frame(spp)
+            r.sync()
+            return round((time.perf_counter() - t) * 1e3 / steps, 3)
+
+        res["step_ms_refit"] = steps_ms()
+        r.build_accel("lbvh")
+        res["step_ms_fresh"] = steps_ms()
+        res["spp_per_step"] = spp
+    finally:
+        r.close()
+    return res
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--spp", type=int, default=8)
+    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--soup-tris", type=int, default=10_000_000)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    out = {"s2": run_scene("S2 atrium250k", atrium250k(1920, 1080), a.reps, a.spp, a.steps)}
+    if a.soup_tris:
+        out["soup"] = run_scene(f"soup {a.soup_tris}", soup(a.soup_tris, 1920, 1080), a.reps, a.spp, a.steps)
+    line = json.dumps(out)
+    print(line)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
