@@ -576,6 +576,72 @@ static napi_value js_refit_accel(napi_env env, napi_callback_info info)
     return b;
 }
 
+/* ------------------------------------------------------------------ adaptive sampling (include/crt.h "Adaptive sampling")
+ * traceAdaptive(h, {samples, threshold, minSamples, maxSamples}) -> active tiles (0: done); a missing option takes the
+ * library's default (crt_adaptive_defaults).  readAdaptive(h) -> {counts: Uint32Array, errors: Float32Array, tilesX, tilesY}. */
+static napi_value js_trace_adaptive(napi_env env, napi_callback_info info)
+{
+    size_t argc = 2;
+    napi_value argv[2];
+    NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    if (argc < 1) { napi_throw_type_error(env, NULL, "too few arguments"); return NULL; }
+    crt_ctx *ctx = get_ctx(env, argv[0]);
+    if (!ctx) return NULL;
+    crt_adaptive_params d;
+    (void)crt_adaptive_defaults(&d);
+    double s = d.samples, thr = d.threshold, mn = d.min_samples, mx = d.max_samples;
+    napi_valuetype t = napi_undefined;
+    if (argc > 1) NAPI_OK(env, napi_typeof(env, argv[1], &t));
+    if (t == napi_object) {
+        if (!opt_number(env, argv[1], "samples", &s) || !opt_number(env, argv[1], "threshold", &thr) ||
+            !opt_number(env, argv[1], "minSamples", &mn) || !opt_number(env, argv[1], "maxSamples", &mx)) {
+            napi_throw_type_error(env, NULL, "traceAdaptive: options must be numbers");
+            return NULL;
+        }
+    } else if (t != napi_undefined && t != napi_null) {
+        napi_throw_type_error(env, NULL, "traceAdaptive: options object expected");
+        return NULL;
+    }
+    const double counts[3] = {s, mn, mx};
+    for (int k = 0; k < 3; k++)
+        if (!(counts[k] >= 0.0 && counts[k] <= 4294967295.0) || counts[k] != (double)(uint32_t)counts[k]) {
+            napi_throw_range_error(env, NULL, "traceAdaptive: samples, minSamples and maxSamples must be non-negative integers");
+            return NULL;
+        }
+    crt_adaptive_params p = {(uint32_t)s, (uint32_t)mn, (uint32_t)mx, (float)thr};
+    uint32_t n = 0;
+    CRT_CHECK(env, ctx, "crt_trace_adaptive", crt_trace_adaptive(ctx, &p, &n));
+    napi_value v;
+    NAPI_OK(env, napi_create_uint32(env, n, &v));
+    return v;
+}
+
+static napi_value js_read_adaptive(napi_env env, napi_callback_info info)
+{
+    ARGS(1)
+    crt_ctx *ctx = get_ctx(env, argv[0]);
+    if (!ctx) return NULL;
+    uint32_t tl[4];
+    CRT_CHECK(env, ctx, "crt_tile", crt_tile(ctx, tl));
+    const uint32_t tx = (tl[2] + 7) / 8, ty = (tl[3] + 7) / 8;
+    const size_t nt = (size_t)tx * ty;
+    void *dc = NULL, *de = NULL;
+    napi_value abc, abe, tc, te, obj, vx, vy;
+    NAPI_OK(env, napi_create_arraybuffer(env, nt * 4, &dc, &abc));
+    NAPI_OK(env, napi_create_arraybuffer(env, nt * 4, &de, &abe));
+    CRT_CHECK(env, ctx, "crt_read_adaptive", crt_read_adaptive(ctx, (uint32_t *)dc, (float *)de));
+    NAPI_OK(env, napi_create_typedarray(env, napi_uint32_array, nt, abc, 0, &tc));
+    NAPI_OK(env, napi_create_typedarray(env, napi_float32_array, nt, abe, 0, &te));
+    NAPI_OK(env, napi_create_object(env, &obj));
+    NAPI_OK(env, napi_create_uint32(env, tx, &vx));
+    NAPI_OK(env, napi_create_uint32(env, ty, &vy));
+    NAPI_OK(env, napi_set_named_property(env, obj, "counts", tc));
+    NAPI_OK(env, napi_set_named_property(env, obj, "errors", te));
+    NAPI_OK(env, napi_set_named_property(env, obj, "tilesX", vx));
+    NAPI_OK(env, napi_set_named_property(env, obj, "tilesY", vy));
+    return obj;
+}
+
 /* ------------------------------------------------------------------ multi-GPU (include/crt.h "Multi-GPU") and composition
  * The reference drives one GPUDevice (src/main.js:8-9); a Node host reaches the tile-partitioned configurations through
  * these: one process (worker) per GPU, the communicator id made by one of them and passed around by the parent
@@ -923,6 +989,7 @@ static napi_value init(napi_env env, napi_value exports)
         {"denoise", js_denoise}, {"readGbuffer", js_read_gbuffer},
         {"setCamera", js_set_camera}, {"updatePrimitives", js_update_primitives}, {"updateLights", js_update_lights},
         {"refitAccel", js_refit_accel},
+        {"traceAdaptive", js_trace_adaptive}, {"readAdaptive", js_read_adaptive},
         {"gatherAsync", js_gather_async}, {"readFrameRgba8Async", js_read_frame_rgba8_async}, {"readFrameAccumAsync", js_read_frame_accum_async},
     };
     for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++) {

@@ -1,4 +1,5 @@
-"""python -m computeraytracer_amd [--scene file.json] [--width W --height H] [--spp N] [--out image.png] [--denoise K] [--orbit N]"""
+"""python -m computeraytracer_amd [--scene file.json] [--width W --height H] [--spp N] [--out image.png] [--denoise K] [--orbit N]
+                                [--adaptive THRESHOLD [--adaptive-step N] [--counts-out counts.png]]"""
 import argparse
 import json
 import os
@@ -21,9 +22,20 @@ def main():
     ap.add_argument("--orbit", type=int, default=None, metavar="N",
                     help="N frames of --spp each with the eye turned about the look-at point (one upload and build, then "
                          "set_camera per frame), written as OUT_000.png, OUT_001.png, ...")
+    ap.add_argument("--adaptive", type=float, default=None, metavar="THRESHOLD",
+                    help="adaptive sampling (crt_trace_adaptive): rounds of --adaptive-step samples for the 8x8 tiles whose "
+                         "error is above THRESHOLD, --spp samples at most, until every tile is done")
+    ap.add_argument("--adaptive-step", type=int, default=16, metavar="N", help="with --adaptive: samples per round (16)")
+    ap.add_argument("--adaptive-min", type=int, default=None, metavar="M",
+                    help="with --adaptive: a tile below M samples is sampled whatever its error (default: min(--spp, 2N))")
+    ap.add_argument("--counts-out", default=None, help="with --adaptive: the per-tile sample counts as a grey PNG")
     args = ap.parse_args()
     if args.orbit is not None and (args.orbit < 1 or args.checkpoint):
         ap.error("--orbit needs N >= 1 and no --checkpoint")
+    if args.adaptive is not None and (args.orbit is not None or args.checkpoint or args.denoise is not None):
+        ap.error("--adaptive goes with neither --orbit, --checkpoint nor --denoise")
+    if (args.counts_out or args.adaptive_min is not None) and args.adaptive is None:
+        ap.error("--counts-out and --adaptive-min need --adaptive")
     sc = scene.load_scene(args.scene)
     if args.width:
         sc["camera"]["width"], sc["camera"]["height"] = args.width, args.height or args.width
@@ -44,6 +56,9 @@ def main():
                 info["denoise"] = args.denoise
             print(json.dumps(info))
             return
+        if args.adaptive is not None:
+            _adaptive(r, ps, args)
+            return
         if args.checkpoint and os.path.exists(args.checkpoint):
             image.load_checkpoint(args.checkpoint, r)
         t0 = time.time()
@@ -57,6 +72,29 @@ def main():
         if args.denoise is not None:
             info["denoise"] = args.denoise
         print(json.dumps(info))
+
+
+def _adaptive(r, ps, args):
+    import numpy as np
+    t0, rounds = time.time(), 0
+    min_samples = min(args.spp, 2 * args.adaptive_step) if args.adaptive_min is None else args.adaptive_min
+    while r.trace_adaptive(samples=args.adaptive_step, threshold=args.adaptive, min_samples=min_samples, max_samples=args.spp):
+        rounds += 1
+    counts, _ = r.read_adaptive()
+    dt = time.time() - t0
+    (image.write_ppm if args.out.endswith(".ppm") else image.write_png)(args.out, r.read_rgba8())
+    pixel_counts = np.repeat(np.repeat(counts, 8, 0), 8, 1)[:ps.height, :ps.width]
+    info = {"width": ps.width, "height": ps.height, "adaptive": args.adaptive, "rounds": rounds,
+            "pixel_samples": int(pixel_counts.sum(dtype=np.uint64)), "seconds": round(dt, 4),
+            "tile_samples": {"min": int(counts.min()), "median": float(np.median(counts)), "max": int(counts.max())},
+            "out": args.out}
+    if args.counts_out:
+        grey = (counts.astype(np.float64) * (255.0 / max(1, args.spp))).clip(0, 255).astype(np.uint8)
+        rgba = np.repeat(np.repeat(grey, 8, 0), 8, 1)[:ps.height, :ps.width, None].repeat(4, 2)
+        rgba[..., 3] = 255
+        image.write_png(args.counts_out, rgba)
+        info["counts_out"] = args.counts_out
+    print(json.dumps(info))
 
 
 if __name__ == "__main__":

@@ -73,8 +73,23 @@ SIGNATURES = {
     "crt_update_lights": (C.c_int, [_P, C.c_uint32, C.c_uint32, _P]),
     "crt_refit_accel": (C.c_int, [_P, _P]),
     "crt_debug_hit_pad": (C.c_int, [_P, _P]),
+    "crt_trace_adaptive": (C.c_int, [_P, _P, _P]),
+    "crt_read_adaptive": (C.c_int, [_P, _P, _P]),
+    "crt_adaptive_defaults": (C.c_int, [_P]),
 }
 
+
+class AdaptiveParams(C.Structure):
+    """crt_adaptive_params of include/crt.h."""
+    _fields_ = [("samples", C.c_uint32), ("min_samples", C.c_uint32), ("max_samples", C.c_uint32), ("threshold", C.c_float)]
+
+
+def adaptive_defaults() -> AdaptiveParams:
+    """The library's defaults for crt_trace_adaptive (crt_adaptive_defaults)."""
+    p = AdaptiveParams()
+    if load().crt_adaptive_defaults(C.byref(p)) != 0:
+        raise RuntimeError("crt_adaptive_defaults failed")
+    return p
 
 
 class DenoiseParams(C.Structure):

@@ -25,13 +25,17 @@
 
 namespace crt {
 hipError_t launch_trace(const TraceParams &P, bool count, bool brute, hipStream_t stream);
+hipError_t launch_trace_adaptive(const TraceParams &P, const AsTiles &A, bool count, bool brute, hipStream_t stream);
+hipError_t wf_launch_resolve_adaptive(const WfParams &P, const AsTiles &A, uint32_t call_end, hipStream_t s);
+hipError_t as_launch_select(const AsParams &A, bool compact, hipStream_t s);
+hipError_t as_launch_commit(uint32_t *counts, const uint32_t *active, uint32_t n_active, uint32_t samples, hipStream_t s);
 hipError_t launch_debug_intersect(const DevScene &S, const float *rays, size_t n, float *out, int brute,
                                   hipStream_t stream);
 hipError_t launch_debug_math(int fn, const float *a, const float *b, float *out, size_t n, hipStream_t stream);
 hipError_t wf_launch_init(const WfParams &P, hipStream_t s);
 hipError_t wf_launch_tea(const WfParams &P, uint32_t *out, hipStream_t s);
 hipError_t wf_launch_shade(const WfParams &P, uint32_t it, hipStream_t s);
-hipError_t wf_launch_gen(const WfParams &P, uint32_t it, hipStream_t s);
+hipError_t wf_launch_gen(const WfParams &P, uint32_t it, hipStream_t s, const AsTiles *A);
 hipError_t wf_launch_trace(const WfParams &P, uint32_t it, uint32_t trace_blocks, hipStream_t s);
 hipError_t wf_launch_finish(const WfParams &P, WfFinishSegs G, uint32_t max_paths, hipStream_t s);
 hipError_t wf_launch_resolve(const WfParams &P, uint32_t last_sample, hipStream_t s);
@@ -241,6 +245,16 @@ struct crt_ctx {
     std::vector<uint32_t> rf_off2, rf_off4;   // ... level l = list[off[l] .. off[l+1])
     DevBuf<uint32_t> rf_nch4, rf_cnt;         // children per 4-wide node; a counter
     DevBuf<float> rf_fb;            // float boxes of the quantised 4-wide tree (32 floats per node)
+
+    // adaptive sampling (crt_adaptive.hip): allocated by the first crt_trace_adaptive, released with the tile
+    bool as_on = false;             // the adaptive state: per-tile counts instead of `sample` (left by everything that zeroes it)
+    bool as_broken = false;         // a crt_trace_adaptive failed part way: the counts lag the accumulator until crt_reset
+    DevBuf<uint32_t> as_counts;     // per 8x8 tile: samples it holds
+    DevBuf<float> as_errors;        // per tile: E as the selection judged it
+    DevBuf<uint32_t> as_flags;      // per tile: active in the last selection
+    DevBuf<uint32_t> as_active;     // the active tiles, ascending (what the sampling kernels run over)
+    DevBuf<uint32_t> as_n;          // their number
+    DevBuf<float> as_q;             // per tile pixel: sum of Y^2 over its samples
 };
 
 namespace {
@@ -269,6 +283,8 @@ uchar4 *rgba_ptr(crt_ctx *c) { return c->rgba_bound ? c->rgba_bound : c->d_rgba.
 
 int alloc_tile(crt_ctx *c)
 {
+    c->as_on = false; c->as_broken = false;                      // (the adaptive buffers are the tile's: next use sizes them)
+    c->as_counts.release(); c->as_errors.release(); c->as_flags.release(); c->as_active.release(); c->as_q.release();
     size_t n = (size_t)c->tw * c->th;
     HIPCHK(c, c->d_accum.alloc(n));
     HIPCHK(c, c->d_rgba.alloc(n));
@@ -296,6 +312,7 @@ int zero_state(crt_ctx *c)
         HIPCHK(c, hipMemsetAsync(rgba_ptr(c), 0, n * sizeof(uchar4), c->stream));
     }
     c->sample = 0; c->published = 0; c->pending = 0; c->resolved_upto = 0; c->ring_from = 1;
+    c->as_on = false; c->as_broken = false;
     return CRT_OK;
 }
 
@@ -703,6 +720,8 @@ struct WfBatch {
     bool evicting = false;          // its last paths are being moved to the side pools (or none are left)
     uint32_t need_mask = 0;         // pipes whose next shade launch evicts ...
     uint32_t launched_mask = 0;     // ... and those that have enqueued it (ev_evict[p][id] recorded)
+    uint32_t as_commit = 0;         // adaptive: the last batch of its crt_trace_adaptive call adds this many samples to the
+                                    // active tiles' counts after its resolve (last_sample is then the call's samples so far)
 };
 
 struct WfRun {
@@ -723,6 +742,7 @@ struct WfRun {
     uint32_t listed_until[kWfRing][crt_ctx::kMaxPipes] = {};   // per id and pipe: launches of iterations < this may look at that queue
     bool resolved_recorded[kWfRing] = {};       // ev_resolved[id] has been recorded since the pool started
     bool all_evicting = false;                  // flush: everything alive was sent to the side pools
+    AsTiles as{};                               // adaptive pool (as.active set): the active tiles its batches sample
     int poll_next = 0;                          // round robin over the pipes for blocking waits
 };
 
@@ -773,11 +793,16 @@ int wf_resolve_batch(crt_ctx *c, const WfBatch &b)
     WfRun &r = *c->run;
     WfParams R = r.pipes[0].W;
     R.batch_id = b.id; R.n_samples = b.n;
-    R.frames = c->d_frames.p; R.frame_ring = c->frame_ring;
-    HIPCHK(c, wf_launch_resolve(R, b.last_sample, c->stream));
-    c->resolved_upto = b.last_sample;
-    if (c->frame_ring && c->frame_batch.size() == c->frame_ring)
-        for (uint32_t k = 0; k < b.n && k < c->frame_ring; k++) c->frame_batch[(b.last_sample - 1u - k) % c->frame_ring] = (uint8_t)b.id;
+    if (r.as.active) {                                           // adaptive: the active tiles only, no frame ring
+        HIPCHK(c, wf_launch_resolve_adaptive(R, r.as, b.last_sample, c->stream));
+        if (b.as_commit) HIPCHK(c, as_launch_commit(c->as_counts.p, r.as.active, r.as.n_active, b.as_commit, c->stream));
+    } else {
+        R.frames = c->d_frames.p; R.frame_ring = c->frame_ring;
+        HIPCHK(c, wf_launch_resolve(R, b.last_sample, c->stream));
+        c->resolved_upto = b.last_sample;
+        if (c->frame_ring && c->frame_batch.size() == c->frame_ring)
+            for (uint32_t k = 0; k < b.n && k < c->frame_ring; k++) c->frame_batch[(b.last_sample - 1u - k) % c->frame_ring] = (uint8_t)b.id;
+    }
     HIPCHK(c, hipEventRecord(c->ev_resolved[b.id], c->stream));    // the id's queue, staging buffer and side pools are free after this
     r.resolved_recorded[b.id] = true;
     c->last_launches++;
@@ -841,7 +866,7 @@ int wf_enqueue(crt_ctx *c, int p, uint32_t iters)
         HIPCHK(c, wf_launch_shade(pp.W, pp.it, pp.stream));
         if (pp.it > pp.it_first) HIPCHK(c, hipEventRecord(c->ev_status[p][(pp.it - 1u) % kStatusRing], pp.stream));   // (blocking waits fall back on it)
         pp.st_counted[pp.it % kStatusRing] = pp.W.count_alive != 0;
-        if (pp.W.rearm) { HIPCHK(c, wf_launch_gen(pp.W, pp.it, pp.stream)); c->last_launches++; }
+        if (pp.W.rearm) { HIPCHK(c, wf_launch_gen(pp.W, pp.it, pp.stream, r.as.active ? &r.as : nullptr)); c->last_launches++; }
         if (pp.evict_next) {                                     // k_wf_finish may start once this launch is through
             for (WfBatch &b : r.open)
                 if ((pp.evict_next >> b.id) & 1u) {
@@ -1360,7 +1385,14 @@ int wf_check_dropped(crt_ctx *c)
     return CRT_OK;
 }
 
-int wf_trace_batch(crt_ctx *c, uint32_t n);
+// One batch of a crt_trace_adaptive call: its samples off + 1 .. off + n of every active tile.
+struct AsBatch {
+    uint32_t off;                   // samples of the call before this batch
+    uint32_t n_active;              // tiles in the active list
+    uint32_t commit;                // last batch of the call: the call's samples (committed to the counts after its resolve)
+};
+
+int wf_trace_batch(crt_ctx *c, uint32_t n, const AsBatch *as = nullptr);
 
 // Samples per batch at most: the staging buffer stays below ~6 GB and work ids fit 32 bits.
 uint32_t wf_batch_cap(crt_ctx *c)
@@ -1427,13 +1459,23 @@ int wf_flush(crt_ctx *c)
     return rc;
 }
 
-// One batch of n samples through the wavefront pipeline.
-int wf_trace_batch(crt_ctx *c, uint32_t n)
+// One batch of n samples through the wavefront pipeline.  as: a batch of the active tiles of an adaptive call -- its queue
+// holds n * n_active * 64 work ids; the pool is sized as for the uniform batch of n samples, so that rounds with fewer
+// active tiles neither shrink nor reallocate it.
+int wf_trace_batch(crt_ctx *c, uint32_t n, const AsBatch *as)
 {
     if (!c->run) c->run = new WfRun();
     WfRun &r = *c->run;
     const WfConfig g = wf_config(c, n);
-    if (g.npix == 0 || n == 0) { int rc = wf_flush(c); c->published += n; return rc; }
+    if (g.npix == 0 || n == 0) { int rc = wf_flush(c); if (!as) c->published += n; return rc; }
+    unsigned long long work_total = g.work_total;
+    uint32_t work_per_shard = g.work_per_shard;
+    if (as) {
+        work_total = (unsigned long long)n * as->n_active * 64u;
+        work_per_shard = (uint32_t)(((work_total + kWfShards - 1) / kWfShards + 63u) & ~63ull);
+    }
+    const uint32_t first_sample = as ? as->off + 1u : c->published + 1u;    // (adaptive: + the tile's count, in k_wf_gen)
+    const uint32_t last_sample = as ? as->off + n : c->published + n;
     // counting folds counters on the host after every batch; otherwise batches are pipelined across calls
     const bool defer = c->wf_defer && !c->counting;
     const size_t staging_elems = (size_t)n * g.npix;
@@ -1447,6 +1489,7 @@ int wf_trace_batch(crt_ctx *c, uint32_t n)
         bool regrow = false;
         for (uint32_t b = 0; b < r.ring; b++) regrow = regrow || c->w_staging[b].n < staging_elems;
         if (r.ring > 4u && (double)r.ring * (double)staging_elems * 16.0 > 32.0e9) regrow = true;
+        if ((r.as.active != nullptr) != (as != nullptr) || (as && r.as.n_active != as->n_active)) regrow = true;   // (one kind of work per pool)
         if ((unsigned long long)g.P > 2ull * r.P || 2ull * g.P < (unsigned long long)r.P || regrow) {
             int rc = wf_flush(c);
             if (rc) return rc;
@@ -1467,9 +1510,9 @@ int wf_trace_batch(crt_ctx *c, uint32_t n)
         r.trace_blocks = (uint32_t)c->num_cu * wf_waves(c);
         r.open.clear();
         WfBatch nb;
-        nb.n = n; nb.last_sample = c->published + n; nb.id = 0;
+        nb.n = n; nb.last_sample = last_sample; nb.id = 0; nb.as_commit = as ? as->commit : 0u;
         r.open.push_back(nb);
-        r.seg_total[0] = g.work_total; r.seg_wps[0] = g.work_per_shard;
+        r.seg_total[0] = work_total; r.seg_wps[0] = work_per_shard;
         for (uint32_t b = 0; b < kWfRing; b++) {
             r.queue_left[b] = false; r.consumed[b] = 0; r.resolved_recorded[b] = false;
             for (int p = 0; p < crt_ctx::kMaxPipes; p++) r.listed_until[b][p] = 0;
@@ -1478,6 +1521,7 @@ int wf_trace_batch(crt_ctx *c, uint32_t n)
         r.consumed_total = 0; r.rate_consumed = 0; r.rate_its = 0;                // (rate_its: set below, once the pipes' iteration numbers are)
         r.per_it = (double)g.Pp;                                 // an empty pool takes a slot's worth per slot
         r.all_evicting = false; r.poll_next = 0;
+        r.as = as ? AsTiles{c->as_active.p, c->as_counts.p, c->as_q.p, as->n_active} : AsTiles{};
         for (int p = 0; p < r.K; p++) {
             const uint32_t it0 = r.pipes[p].it + 2u * (uint32_t)kStatusRing;
             r.pipes[p] = WfPipe();
@@ -1507,7 +1551,7 @@ int wf_trace_batch(crt_ctx *c, uint32_t n)
             W.band = c->band; W.stride = c->stride; W.phase = c->phase;
             W.tiles_x = g.tiles_x; W.tiles_y = g.tiles_y; W.npix_padded = g.npix_padded;
             W.list_cap = g.list_cap;
-            W.seg[0] = WfSeg{g.work_total, g.work_per_shard, c->published + 1};
+            W.seg[0] = WfSeg{work_total, work_per_shard, first_sample};
             W.seg_n = 1;
             W.n_samples = n;
             W.accum = accum_ptr(c); W.rgba = rgba_ptr(c);
@@ -1552,15 +1596,15 @@ int wf_trace_batch(crt_ctx *c, uint32_t n)
         // The batches in flight keep their slots, queues and staging buffers; this one takes the next id and its
         // work flows into the slots that are free once the older queues are dry.
         WfBatch nb;
-        nb.n = n; nb.last_sample = c->published + n; nb.id = (r.open.back().id + 1u) % r.ring;
+        nb.n = n; nb.last_sample = last_sample; nb.id = (r.open.back().id + 1u) % r.ring; nb.as_commit = as ? as->commit : 0u;
         const uint32_t id = nb.id;
-        r.seg_total[id] = g.work_total; r.seg_wps[id] = g.work_per_shard;
+        r.seg_total[id] = work_total; r.seg_wps[id] = work_per_shard;
         r.queue_left[id] = r.work_left = true;
         r.consumed[id] = 0;
         for (int p = 0; p < r.K; p++) {
             WfPipe &pp = r.pipes[p];
             nb.from_it[p] = 0xFFFFFFFFu;                         // (set when the host sees the queue reset complete: wf_check_ready)
-            pp.W.seg[id] = WfSeg{g.work_total, g.work_per_shard, c->published + 1};
+            pp.W.seg[id] = WfSeg{work_total, work_per_shard, first_sample};
             pp.W.n_samples = n;
             pp.W.batch_id = id; pp.W.keep_pool = 1;
             pp.tail_bound = 0; pp.blocks_now = r.trace_blocks;
@@ -1583,7 +1627,7 @@ int wf_trace_batch(crt_ctx *c, uint32_t n)
         nb.ready = false;                                        // listed by the launches enqueued once the host has seen that event complete
         r.open.push_back(nb);
     }
-    c->published += n;
+    if (!as) c->published += n;
     rc = wf_pump(c, false);
     if (rc == CRT_OK && !defer) rc = wf_flush(c);
     if (rc != CRT_OK && r.live) {
@@ -1674,6 +1718,7 @@ void crt_destroy(crt_ctx *c)
     c->w_vis.release(); c->w_dead.release(); c->w_recA.release(); c->w_recB.release(); c->w_recC.release(); c->w_tea.release(); c->w_wq.release();
     c->dn_gbuf.release(); c->dn_key.release(); c->dn_c[0].release(); c->dn_c[1].release(); c->dn_rgba.release();
     c->rf_lv2.release(); c->rf_lv4.release(); c->rf_nch4.release(); c->rf_cnt.release(); c->rf_fb.release();
+    c->as_counts.release(); c->as_errors.release(); c->as_flags.release(); c->as_active.release(); c->as_n.release(); c->as_q.release();
     if (c->pub_stream) (void)hipStreamSynchronize(c->pub_stream);
     for (int f = 0; f < crt_ctx::kFinishStreams; f++) {
         if (c->fin_stream[f]) { (void)hipStreamSynchronize(c->fin_stream[f]); (void)hipStreamDestroy(c->fin_stream[f]); }
@@ -1850,9 +1895,17 @@ int crt_reset(crt_ctx *c)
     return zero_state(c);
 }
 
+// The calls that assume one sample count for the whole tile refuse the adaptive state.
+static int as_refuse(crt_ctx *c, const char *what)
+{
+    return fail(c, CRT_ESTATE, "%s: the context is in the adaptive state (per-tile sample counts: crt_read_adaptive; crt_reset "
+                               "returns to uniform sampling)", what);
+}
+
 int crt_trace(crt_ctx *c, uint32_t n_samples)
 {
     if (!c) return CRT_EINVAL;
+    if (c->as_on) return as_refuse(c, "crt_trace");
     if (!c->have_scene) return fail(c, CRT_ESTATE, "crt_trace: upload a scene first");
     if (c->accel_mode < 0) return fail(c, CRT_ESTATE, "crt_trace: call crt_build_accel first");
     if (c->accel_stale) return fail(c, CRT_ESTATE, "crt_trace: primitives were updated: call crt_refit_accel or crt_build_accel first");
@@ -1902,9 +1955,146 @@ int crt_sync(crt_ctx *c)
     return wf_check_dropped(c);
 }
 
+// ---------------------------------------------------------------- adaptive sampling (crt_adaptive.hip)
+extern "C" int crt_internal_comm_partitioned(crt_ctx *c);     // crt_comm.cpp
+
+static AsParams as_params(crt_ctx *c, const crt_adaptive_params &p)
+{
+    AsParams A{};
+    A.accum = accum_ptr(c); A.q = c->as_q.p; A.counts = c->as_counts.p; A.errors = c->as_errors.p; A.flags = c->as_flags.p;
+    A.active = c->as_active.p; A.n_active = c->as_n.p;
+    A.tw = c->tw; A.th = c->th; A.tiles_x = (c->tw + 7) / 8; A.tiles_y = (c->th + 7) / 8;
+    A.min_samples = p.min_samples; A.max_samples = p.max_samples; A.threshold = p.threshold;
+    return A;
+}
+
+// Enter the adaptive state: every tile at 0 samples, Q = 0 (the accumulator is at sample 0 already).
+static int as_begin(crt_ctx *c)
+{
+    const size_t ntiles = std::max<size_t>((size_t)((c->tw + 7) / 8) * ((c->th + 7) / 8), 1);
+    const size_t npix = std::max<size_t>((size_t)c->tw * c->th, 1);
+    if (c->as_counts.n < ntiles) HIPCHK(c, c->as_counts.alloc(ntiles));
+    if (c->as_errors.n < ntiles) HIPCHK(c, c->as_errors.alloc(ntiles));
+    if (c->as_flags.n < ntiles) HIPCHK(c, c->as_flags.alloc(ntiles));
+    if (c->as_active.n < ntiles) HIPCHK(c, c->as_active.alloc(ntiles));
+    if (c->as_n.n < 1) HIPCHK(c, c->as_n.alloc(1));
+    if (c->as_q.n < npix) HIPCHK(c, c->as_q.alloc(npix));
+    HIPCHK(c, hipMemsetAsync(c->as_counts.p, 0, ntiles * sizeof(uint32_t), c->stream));
+    HIPCHK(c, hipMemsetAsync(c->as_q.p, 0, npix * sizeof(float), c->stream));
+    c->as_on = true;
+    return CRT_OK;
+}
+
+// The defaults (tools/adaptive_bench.py): rounds of 64 samples reach tau in 0.60 / 0.62 of the wall time of
+// rounds of 16 on S2 / the Cornell box at 1080p for 1.07 / 1.03 times the pixel-samples (each round flushes, selects and
+// reads back); min_samples guards tiles whose first samples miss a rare path; max_samples bounds the tiles that do not
+// reach tau = 0.01 (0.9 % of S2's tiles at 4096 samples).
+static const crt_adaptive_params kAsDefaults = {64u, 32u, 4096u, 0.01f};
+
+int crt_adaptive_defaults(crt_adaptive_params *out)
+{
+    if (!out) return CRT_EINVAL;
+    *out = kAsDefaults;
+    return CRT_OK;
+}
+
+static int as_refuse_broken(crt_ctx *c, const char *what)
+{
+    return fail(c, CRT_ESTATE, "%s: an earlier crt_trace_adaptive failed part way (the tile counts lag the accumulator): "
+                               "crt_reset first", what);
+}
+
+int crt_trace_adaptive(crt_ctx *c, const crt_adaptive_params *params, uint32_t *active_tiles)
+{
+    if (!c) return CRT_EINVAL;
+    const crt_adaptive_params p = params ? *params : kAsDefaults;
+    if (p.samples == 0) return fail(c, CRT_EINVAL, "crt_trace_adaptive: samples must be >= 1");
+    if (!(p.threshold >= 0.0f && p.threshold <= FLT_MAX)) return fail(c, CRT_EINVAL, "crt_trace_adaptive: threshold must be finite and >= 0");
+    if (p.max_samples != 0 && p.max_samples < p.min_samples)
+        return fail(c, CRT_EINVAL, "crt_trace_adaptive: max_samples %u < min_samples %u", p.max_samples, p.min_samples);
+    if (!c->have_scene) return fail(c, CRT_ESTATE, "crt_trace: upload a scene first");
+    if (c->accel_mode < 0) return fail(c, CRT_ESTATE, "crt_trace: call crt_build_accel first");
+    if (c->accel_stale) return fail(c, CRT_ESTATE, "crt_trace: primitives were updated: call crt_refit_accel or crt_build_accel first");
+    if (crt_internal_comm_partitioned(c)) return fail(c, CRT_ESTATE, "crt_trace_adaptive: not under a crt_comm_partition (multi-GPU adaptivity is not supported)");
+    if (c->as_broken) return as_refuse_broken(c, "crt_trace_adaptive");
+    if (!c->as_on && c->sample > 0)
+        return fail(c, CRT_ESTATE, "crt_trace_adaptive: the context holds %u uniform samples whose second moment was not kept: crt_reset first", c->sample);
+    HIPCHK(c, hipSetDevice(c->device));
+    if ((size_t)c->tw * c->th != 0 && (!accum_ptr(c) || !rgba_ptr(c)))
+        return fail(c, CRT_ENOMEM, "crt_trace_adaptive: the tile's output buffers are not allocated (an earlier crt_set_tile / crt_set_row_bands failed)");
+    { int rc = wf_flush(c); if (rc) return rc; }                 // (the selection reads the accumulator)
+    if (!c->as_on) { int rc = as_begin(c); if (rc) return rc; }
+    const uint32_t tiles_x = (c->tw + 7) / 8, tiles_y = (c->th + 7) / 8;
+    uint32_t n_active = 0;
+    if (tiles_x * tiles_y) {
+        HIPCHK(c, as_launch_select(as_params(c, p), true, c->stream));
+        HIPCHK(c, hipMemcpyAsync(&n_active, c->as_n.p, sizeof n_active, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        { int rc = wf_check_dropped(c); if (rc) return rc; }
+    }
+    if (active_tiles) *active_tiles = n_active;
+    if (n_active == 0) return CRT_OK;
+    c->last_launches = 0;
+    c->last_timed = true;
+    c->last_iterations = 0;
+    HIPCHK(c, hipEventRecord(c->ev0, c->stream));
+    if (c->pipeline == 1 && c->accel_mode == CRT_ACCEL_BVH2) {
+        const uint32_t cap = wf_batch_cap(c);
+        for (uint32_t off = 0; off < p.samples;) {
+            const uint32_t take = std::min(p.samples - off, cap);
+            const AsBatch ab{off, n_active, off + take == p.samples ? p.samples : 0u};
+            int rc = wf_trace_batch(c, take, &ab);
+            if (rc) { c->as_broken = true; return rc; }              // (samples of this call may be in the accumulator already)
+            off += take;
+        }
+    } else {
+        TraceParams P{};
+        P.sc = c->sc;
+        P.x0 = c->x0; P.y0 = c->y0; P.tw = c->tw; P.th = c->th;
+        P.band = c->band; P.stride = c->stride; P.phase = c->phase;
+        P.accum = accum_ptr(c); P.rgba = rgba_ptr(c);
+        P.counters = c->counting ? c->d_counters.p : nullptr;
+        P.tiles_x = tiles_x; P.tiles_y = tiles_y;
+        const AsTiles A{c->as_active.p, c->as_counts.p, c->as_q.p, n_active};
+        const uint32_t chunk = c->spp_per_launch ? c->spp_per_launch : 8u;
+        for (uint32_t off = 0; off < p.samples;) {
+            const uint32_t n = std::min(p.samples - off, chunk);
+            P.first_sample = off + 1u;                           // + the tile's count (k_trace)
+            P.n_samples = n;
+            const hipError_t e = launch_trace_adaptive(P, A, c->counting, c->accel_mode == CRT_ACCEL_NONE, c->stream);
+            if (e != hipSuccess) { c->as_broken = true; HIPCHK(c, e); }
+            c->last_launches++;
+            off += n;
+        }
+        const hipError_t e = as_launch_commit(c->as_counts.p, c->as_active.p, n_active, p.samples, c->stream);
+        if (e != hipSuccess) { c->as_broken = true; HIPCHK(c, e); }
+    }
+    HIPCHK(c, hipEventRecord(c->ev1, c->stream));
+    return CRT_OK;
+}
+
+int crt_read_adaptive(crt_ctx *c, uint32_t *counts, float *errors)
+{
+    if (!c) return CRT_EINVAL;
+    if (!c->as_on) return fail(c, CRT_ESTATE, "crt_read_adaptive: the context is in the uniform state (crt_trace_adaptive first)");
+    if (c->as_broken) return as_refuse_broken(c, "crt_read_adaptive");
+    HIPCHK(c, hipSetDevice(c->device));
+    { int rc = wf_flush(c); if (rc) return rc; }
+    const size_t ntiles = (size_t)((c->tw + 7) / 8) * ((c->th + 7) / 8);
+    if (ntiles) {
+        // (the selection's thresholds do not enter E: any will do; the active list is left alone)
+        HIPCHK(c, as_launch_select(as_params(c, crt_adaptive_params{1u, 0u, 0u, 0.0f}), false, c->stream));
+        if (counts) HIPCHK(c, hipMemcpyAsync(counts, c->as_counts.p, ntiles * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        if (errors) HIPCHK(c, hipMemcpyAsync(errors, c->as_errors.p, ntiles * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return wf_check_dropped(c);
+}
+
 int crt_sample_count(crt_ctx *c, uint32_t *out)
 {
     if (!c || !out) return CRT_EINVAL;
+    if (c->as_on) return as_refuse(c, "crt_sample_count");
     *out = c->sample;
     return CRT_OK;
 }
@@ -1983,6 +2173,7 @@ int crt_unpin_host(void *ptr)
 int crt_latest_sample(crt_ctx *c, uint32_t *out)
 {
     if (!c || !out) return CRT_EINVAL;
+    if (c->as_on) return as_refuse(c, "crt_latest_sample");
     if (c->run && c->run->live) { HIPCHK(c, hipSetDevice(c->device)); int rc = wf_tick(c); if (rc) return rc; }   // (retire what has finished meanwhile)
     *out = c->resolved_upto;
     return CRT_OK;
@@ -1992,6 +2183,7 @@ int crt_read_latest_rgba8(crt_ctx *c, uint8_t *out, uint32_t *sample)
 {
     if (!c || !out) return CRT_EINVAL;
     if (!c->have_scene) return fail(c, CRT_ESTATE, "crt_read_latest_rgba8: no scene");
+    if (c->as_on) return as_refuse(c, "crt_read_latest_rgba8");
     HIPCHK(c, hipSetDevice(c->device));
     if (c->run && c->run->live) { int rc = wf_tick(c); if (rc) return rc; }
     // No flush: in stream order the framebuffer holds the complete frame of the newest batch whose resolve pass has been
@@ -2008,6 +2200,7 @@ int crt_read_sample_rgba8(crt_ctx *c, uint32_t sample, uint8_t *out)
 {
     if (!c || !out) return CRT_EINVAL;
     if (!c->have_scene) return fail(c, CRT_ESTATE, "crt_read_sample_rgba8: no scene");
+    if (c->as_on) return as_refuse(c, "crt_read_sample_rgba8");
     if (!c->frame_ring || !c->d_frames.p) return fail(c, CRT_ESTATE, "crt_read_sample_rgba8: set option frame_ring first (frames kept per sample)");
     if (sample == 0 || sample > c->sample) return fail(c, CRT_EINVAL, "crt_read_sample_rgba8: sample %u has not been requested (1..%u)", sample, c->sample);
     if (sample < c->ring_from) return fail(c, CRT_EINVAL, "crt_read_sample_rgba8: sample %u was not traced by this context since its last reset / crt_write_accum (frames from %u on)", sample, c->ring_from);
@@ -2036,6 +2229,7 @@ int crt_write_accum(crt_ctx *c, const float *in, uint32_t sample)
     if (n) HIPCHK(c, hipMemcpyAsync(accum_ptr(c), in, n * sizeof(float4), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->sample = sample; c->published = sample; c->pending = 0; c->resolved_upto = sample; c->ring_from = sample + 1u;
+    c->as_on = false; c->as_broken = false;                      // (the restored accumulator is a uniform one)
     return CRT_OK;
 }
 
@@ -2242,6 +2436,7 @@ int crt_denoise(crt_ctx *c, const crt_denoise_params *params, float *rgb_out, ui
     const float sig[3] = {dp.sigma_color, dp.sigma_normal, dp.sigma_plane};
     for (float v : sig)
         if (!(v > 0.0f && v <= 3.40282347e38f)) return fail(c, CRT_EINVAL, "crt_denoise: every sigma must be positive and finite");
+    if (c->as_on) return as_refuse(c, "crt_denoise");
     { int rc = dn_check_state(c, "crt_denoise"); if (rc) return rc; }
     HIPCHK(c, hipSetDevice(c->device));
     { int rc_ = wf_flush(c); if (rc_) return rc_; }

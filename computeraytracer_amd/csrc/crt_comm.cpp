@@ -405,4 +405,11 @@ int crt_comm_info(crt_ctx *c, int out[4])
     return CRT_OK;
 }
 
+// (crt_api.cpp: crt_trace_adaptive refuses a partitioned context)
+int crt_internal_comm_partitioned(crt_ctx *c)
+{
+    Comm *m = find(c);
+    return m && m->partitioned ? 1 : 0;
+}
+
 }  // extern "C"

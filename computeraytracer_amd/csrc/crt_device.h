@@ -66,6 +66,29 @@ struct TraceParams {
     uint32_t tiles_x, tiles_y;
 };
 
+// The active tiles of an adaptive call (crt_adaptive.hip), a kernel argument of its own for the adaptive
+// instantiations of k_trace, k_wf_gen and k_wf_resolve (so that the uniform ones keep their parameter blocks).
+struct AsTiles {
+    const uint32_t *active;         // the active tiles, ascending
+    const uint32_t *base;           // per tile: samples it held when the call began (its first sample is base + 1 + offset)
+    float *q;                       // per tile pixel: sum of Y^2 over its samples
+    uint32_t n_active;
+};
+
+// Adaptive sampling (crt_adaptive.hip): the tile selection's inputs and outputs.
+struct AsParams {
+    const float4 *accum;
+    const float *q;                 // per tile pixel: sum of Y^2 over the pixel's samples
+    const uint32_t *counts;         // per tile: samples it holds
+    float *errors;                  // per tile: E
+    uint32_t *flags;                // per tile: 1 = active
+    uint32_t *active;               // the active tiles, ascending
+    uint32_t *n_active;
+    uint32_t tw, th, tiles_x, tiles_y;
+    uint32_t min_samples, max_samples;
+    float threshold;
+};
+
 
 // ---------------------------------------------------------------------------------------------
 // Wavefront pipeline state (crt_wavefront.hip).  A pool of P path slots lives in HBM (SoA,

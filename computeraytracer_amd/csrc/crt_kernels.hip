@@ -23,8 +23,10 @@ namespace crt {
 // ---------------------------------------------------------------- the kernel
 // grid = tiles_x*tiles_y blocks of 64 threads; block -> 8x8 pixel tile of the
 // context's rectangle.  BRUTE: no BVH, the reference loop for every ray.
-template <bool COUNT, bool BRUTE>
-__global__ __launch_bounds__(64) void k_trace(const TraceParams P)
+// ADAPT: grid = the active tiles, block -> A.active[i]; the tile's first sample is
+// A.base[tile] + first_sample, and the second moment of Y is kept in A.q.
+template <bool COUNT, bool BRUTE, bool ADAPT>
+__global__ __launch_bounds__(64) void k_trace(const TraceParams P, const AsTiles A)
 {
     __shared__ int lds_stack[kStackDepth * 64];
     const DevScene &S = P.sc;
@@ -33,10 +35,12 @@ __global__ __launch_bounds__(64) void k_trace(const TraceParams P)
 
     // XCD-aware tile order: blocks b, b+8, b+16.. share an XCD (round-robin
     // dispatch), so give each XCD a contiguous band of tiles (bijective form).
-    const uint32_t ntiles = P.tiles_x * P.tiles_y;
+    // (adaptive: of the active list, which is in ascending tile order)
+    const uint32_t ntiles = ADAPT ? A.n_active : P.tiles_x * P.tiles_y;
     const uint32_t b = blockIdx.x;
     const uint32_t q = ntiles >> 3, r = ntiles & 7u, xcd = b & 7u;
-    const uint32_t tile = (xcd < r ? xcd * (q + 1u) : r * (q + 1u) + (xcd - r) * q) + (b >> 3);
+    const uint32_t idx = (xcd < r ? xcd * (q + 1u) : r * (q + 1u) + (xcd - r) * q) + (b >> 3);
+    const uint32_t tile = ADAPT ? A.active[idx] : idx;
     const uint32_t tx = tile % P.tiles_x, ty = tile / P.tiles_x;
     const uint32_t lx = tx * 8u + (lane & 7u), ly = ty * 8u + (lane >> 3);
     const bool in_tile = lx < P.tw && ly < P.th;
@@ -52,7 +56,8 @@ __global__ __launch_bounds__(64) void k_trace(const TraceParams P)
         const uint32_t tea_xy = tea(px, py * 100u);
         const f3 llc = f3{S.cam[0], S.cam[1], S.cam[2]}, hor = f3{S.cam[3], S.cam[4], S.cam[5]};
         const f3 ver = f3{S.cam[6], S.cam[7], S.cam[8]}, eye = f3{S.cam[9], S.cam[10], S.cam[11]};
-        uint32_t sample = P.first_sample;
+        uint32_t sample = ADAPT ? A.base[tile] + P.first_sample : P.first_sample;
+        float qy = ADAPT ? A.q[pix] : 0.0f;
 
         for (uint32_t si = 0; si < P.n_samples; si++, sample++) {
             Rng rng = {py, px * 100u, sample, tea_xy};                              // :98
@@ -237,8 +242,10 @@ __global__ __launch_bounds__(64) void k_trace(const TraceParams P)
 
             f3 xyzc = spectral_to_xyz(S, radiance, wl);
             acc = acc + xyzc;                                                        // :108
+            if (ADAPT) qy = qy + xyzc.y * xyzc.y;
         }
 
+        if (ADAPT) A.q[pix] = qy;
         P.accum[pix] = float4{acc.x, acc.y, acc.z, acc4.w};
         if (P.n_samples > 0) {
             P.rgba[pix] = tonemap_rgba8(acc, (float)(sample - 1u));
@@ -304,11 +311,26 @@ hipError_t launch_trace(const TraceParams &P, bool count, bool brute, hipStream_
     dim3 grid(P.tiles_x * P.tiles_y), block(64);
     if (grid.x == 0) return hipSuccess;
     if (count) {
-        if (brute) hipLaunchKernelGGL((k_trace<true, true>), grid, block, 0, stream, P);
-        else hipLaunchKernelGGL((k_trace<true, false>), grid, block, 0, stream, P);
+        if (brute) hipLaunchKernelGGL((k_trace<true, true, false>), grid, block, 0, stream, P, AsTiles{});
+        else hipLaunchKernelGGL((k_trace<true, false, false>), grid, block, 0, stream, P, AsTiles{});
     } else {
-        if (brute) hipLaunchKernelGGL((k_trace<false, true>), grid, block, 0, stream, P);
-        else hipLaunchKernelGGL((k_trace<false, false>), grid, block, 0, stream, P);
+        if (brute) hipLaunchKernelGGL((k_trace<false, true, false>), grid, block, 0, stream, P, AsTiles{});
+        else hipLaunchKernelGGL((k_trace<false, false, false>), grid, block, 0, stream, P, AsTiles{});
+    }
+    return hipGetLastError();
+}
+
+// The adaptive instantiation: one block per active tile (A.n_active of them, listed in A.active).
+hipError_t launch_trace_adaptive(const TraceParams &P, const AsTiles &A, bool count, bool brute, hipStream_t stream)
+{
+    dim3 grid(A.n_active), block(64);
+    if (grid.x == 0) return hipSuccess;
+    if (count) {
+        if (brute) hipLaunchKernelGGL((k_trace<true, true, true>), grid, block, 0, stream, P, A);
+        else hipLaunchKernelGGL((k_trace<true, false, true>), grid, block, 0, stream, P, A);
+    } else {
+        if (brute) hipLaunchKernelGGL((k_trace<false, true, true>), grid, block, 0, stream, P, A);
+        else hipLaunchKernelGGL((k_trace<false, false, true>), grid, block, 0, stream, P, A);
     }
     return hipGetLastError();
 }

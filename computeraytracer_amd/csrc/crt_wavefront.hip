@@ -712,8 +712,16 @@ __global__ __launch_bounds__(CRT_WF_SHADE_BLOCK, CRT_WF_SHADE_MIN_WAVES) void k_
 // batch's queue), and looks at the other shards' cursors with one wave-wide load only when all of its own are dry.
 // Fewer than 64 dead slots at the end of a shard's list stay dead until the next launch lists them again.  The camera
 // rays are ray class 0 of the iteration's lists.
-template <bool COUNT>
-__global__ __launch_bounds__(64) void k_wf_gen(const WfParams P, uint32_t it)
+// ADAPT: a queue's work ids cover the active tiles only (AsTiles): id w is sample offset
+// w / (n_active*64) of tile active[(w / 64) % n_active]; the slot stores the FULL-FRAME id of that (sample, pixel), so
+// shade, finish and resolve see no difference, and the sample index is the tile's count + the batch's first sample.
+__device__ __forceinline__ uint32_t wf_as_tile(const AsTiles &A, uint32_t w)
+{
+    return A.active[(w % (A.n_active * 64u)) >> 6];
+}
+
+template <bool COUNT, bool ADAPT>
+__global__ __launch_bounds__(64) void k_wf_gen(const WfParams P, uint32_t it, const AsTiles A)
 {
     const DevScene &S = P.sc;
     const uint32_t ring = it & 3u, lbuf = it & 1u;
@@ -783,7 +791,7 @@ __global__ __launch_bounds__(64) void k_wf_gen(const WfParams P, uint32_t it)
         for (uint32_t g = 0; g < 2u; g++) {
             n_valid[g] = 0;
             for (uint32_t k = 0; k < seg_n[g]; k++) {
-                const uint32_t tile = ((seg_w[g] + 64u * k) % P.npix_padded) >> 6;
+                const uint32_t tile = ADAPT ? wf_as_tile(A, seg_w[g] + 64u * k) : ((seg_w[g] + 64u * k) % P.npix_padded) >> 6;
                 const uint32_t lx = (tile % P.tiles_x) * 8u + (lane & 7u), ly = (tile / P.tiles_x) * 8u + (lane >> 3);
                 n_valid[g] += (uint32_t)__popcll(__ballot(lx < P.tw && ly < P.th));
             }
@@ -803,7 +811,11 @@ __global__ __launch_bounds__(64) void k_wf_gen(const WfParams P, uint32_t it)
         const uint32_t g = k < seg_n[0] ? 0u : 1u, kk = g ? k - seg_n[0] : k;
         const uint32_t sg = seg_q[g];
         const uint32_t w0 = seg_w[g] + 64u * kk;
-        const uint32_t sample_off = w0 / P.npix_padded, pp0 = w0 % P.npix_padded;
+        uint32_t sample_off = w0 / P.npix_padded, pp0 = w0 % P.npix_padded;
+        if (ADAPT) {                                                     // the full-frame position of the active tile's chunk
+            sample_off = w0 / (A.n_active * 64u);
+            pp0 = wf_as_tile(A, w0) * 64u;
+        }
         const uint32_t tile = pp0 >> 6;
         const uint32_t lx = (tile % P.tiles_x) * 8u + (lane & 7u), ly = (tile / P.tiles_x) * 8u + (lane >> 3);
         const bool valid = lx < P.tw && ly < P.th;
@@ -812,7 +824,7 @@ __global__ __launch_bounds__(64) void k_wf_gen(const WfParams P, uint32_t it)
         f3 eye = f3{0.0f, 0.0f, 0.0f}, d = eye;
         uint32_t resolved = 0u;
         if (valid) {
-            const uint32_t px = P.x0 + lx, sample = P.seg[sg].first_sample + sample_off;
+            const uint32_t px = P.x0 + lx, sample = ADAPT ? A.base[tile] + P.seg[sg].first_sample + sample_off : P.seg[sg].first_sample + sample_off;
             const uint32_t py = P.y0 + (ly / P.band) * P.band * P.stride + P.phase * P.band + ly % P.band;
             Rng rng = Rng{py, px * 100u, sample, P.tea[(size_t)ly * P.tw + lx]};             // :98 (tea(px, py*100) from k_wf_tea)
             const float jx = rnd(rng);
@@ -831,7 +843,7 @@ __global__ __launch_bounds__(64) void k_wf_gen(const WfParams P, uint32_t it)
             // every dead slot with its coalesced streams)
             stnt(&P.ray_d[slot], float4{d.x, d.y, d.z, bits_f(0u)});
             stnt(&P.rng[slot], uint4{rng.x, rng.y, rng.z, rng.w});
-            stnt((uint2 *)&P.misc[slot], uint2{w0 + lane, flags});                   // work, flags
+            stnt((uint2 *)&P.misc[slot], uint2{(ADAPT ? sample_off * P.npix_padded + pp0 : w0) + lane, flags});   // work (full-frame id), flags
             // (a camera ray is finite unless the camera itself is not.  Such a ray is decided by the reference loop in its own
             // order like any other non-finite ray -- by the NEXT shade step (kWfNanRay): a call to that loop in this kernel would
             // cost it half its occupancy in registers, and the kernel sits between the shade and the traversal launch of its pipe)
@@ -1760,6 +1772,30 @@ __global__ __launch_bounds__(64) void k_wf_resolve(const WfParams P, uint32_t la
     if (P.n_samples > 0) P.rgba[pix] = tonemap_rgba8(acc, (float)last_sample);
 }
 
+// The adaptive instantiation: one block per ACTIVE tile, lane = the tile's pixel (the staging buffer of a
+// retired tile holds stale data); sums in sample order as above, keeps the second moment of Y and tone-maps with the
+// tile's own count, A.base[tile] + call_end (the samples of the call up to this batch's last).  No frame ring.
+__global__ __launch_bounds__(64) void k_wf_resolve_as(const WfParams P, uint32_t call_end, const AsTiles A)
+{
+    const uint32_t tile = A.active[blockIdx.x], lane = threadIdx.x;
+    const uint32_t lx = (tile % P.tiles_x) * 8u + (lane & 7u), ly = (tile / P.tiles_x) * 8u + (lane >> 3);
+    if (lx >= P.tw || ly >= P.th) return;
+    const size_t npix = (size_t)P.tw * P.th;
+    const size_t pix = (size_t)ly * P.tw + lx;
+    const float4 a4 = P.accum[pix];
+    f3 acc = f3{a4.x, a4.y, a4.z};
+    float qy = A.q[pix];
+    const float4 *__restrict__ staging = P.staging[P.batch_id];
+    for (uint32_t s = 0; s < P.n_samples; s++) {
+        const float4 v = ldnt(&staging[(size_t)s * npix + pix]);
+        acc = acc + f3{v.x, v.y, v.z};                           // :108, in sample order
+        qy = qy + v.y * v.y;
+    }
+    A.q[pix] = qy;
+    P.accum[pix] = float4{acc.x, acc.y, acc.z, a4.w};
+    if (P.n_samples > 0) P.rgba[pix] = tonemap_rgba8(acc, (float)(A.base[tile] + call_end));
+}
+
 // The pixel's RNG seed word tea(px, py*100) (:98) depends on the pixel only: 16 rounds computed once per run
 // instead of at every re-arm (where every wave paid for them with a third of its lanes on).
 __global__ __launch_bounds__(256) void k_wf_tea(const WfParams P, uint32_t *out)
@@ -1820,12 +1856,17 @@ hipError_t wf_launch_shade(const WfParams &P, uint32_t it, hipStream_t s)
     return hipGetLastError();
 }
 
-hipError_t wf_launch_gen(const WfParams &P, uint32_t it, hipStream_t s)
+hipError_t wf_launch_gen(const WfParams &P, uint32_t it, hipStream_t s, const AsTiles *A)
 {
     if (P.gen_blocks == 0u) return hipErrorInvalidValue;
     const dim3 gs(kWfShards * P.gen_blocks), bs(64);
-    if (P.count) hipLaunchKernelGGL((k_wf_gen<true>), gs, bs, 0, s, P, it);
-    else hipLaunchKernelGGL((k_wf_gen<false>), gs, bs, 0, s, P, it);
+    if (A) {                                                     // adaptive batches
+        if (P.count) hipLaunchKernelGGL((k_wf_gen<true, true>), gs, bs, 0, s, P, it, *A);
+        else hipLaunchKernelGGL((k_wf_gen<false, true>), gs, bs, 0, s, P, it, *A);
+        return hipGetLastError();
+    }
+    if (P.count) hipLaunchKernelGGL((k_wf_gen<true, false>), gs, bs, 0, s, P, it, AsTiles{});
+    else hipLaunchKernelGGL((k_wf_gen<false, false>), gs, bs, 0, s, P, it, AsTiles{});
     return hipGetLastError();
 }
 
@@ -1867,6 +1908,13 @@ hipError_t wf_launch_resolve(const WfParams &P, uint32_t last_sample, hipStream_
     const size_t npix = (size_t)P.tw * P.th;
     if (npix == 0) return hipSuccess;
     hipLaunchKernelGGL(k_wf_resolve, dim3((unsigned)((npix + 63) / 64)), dim3(64), 0, s, P, last_sample);
+    return hipGetLastError();
+}
+
+hipError_t wf_launch_resolve_adaptive(const WfParams &P, const AsTiles &A, uint32_t call_end, hipStream_t s)
+{
+    if (A.n_active == 0 || !A.active) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_wf_resolve_as, dim3(A.n_active), dim3(64), 0, s, P, call_end, A);
     return hipGetLastError();
 }
 

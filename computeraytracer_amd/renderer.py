@@ -145,6 +145,32 @@ class Renderer:
         self._chk(self._lib.crt_sync(self._h))
         return self
 
+    # -- adaptive sampling (include/crt.h, "Adaptive sampling")
+    def trace_adaptive(self, samples: int | None = None, threshold: float | None = None, min_samples: int | None = None,
+                       max_samples: int | None = None) -> int:
+        """`samples` more samples for every 8x8 tile that is still active (asynchronous); returns how many tiles that
+        was -- 0 when every tile has converged or reached max_samples (0 = no limit).  The first call needs sample 0.
+        A parameter left out takes the library's default (crt_adaptive_defaults)."""
+        p = _lib.adaptive_defaults()
+        for k, v in (("samples", samples), ("min_samples", min_samples), ("max_samples", max_samples)):
+            if v is not None:
+                setattr(p, k, int(v))
+        if threshold is not None:
+            p.threshold = float(threshold)
+        n = C.c_uint32()
+        self._chk(self._lib.crt_trace_adaptive(self._h, C.byref(p), C.byref(n)))
+        return int(n.value)
+
+    def read_adaptive(self):
+        """(counts (tiles_y, tiles_x) uint32, errors (tiles_y, tiles_x) float32): the samples each tile holds and its
+        error E as the next trace_adaptive judges it."""
+        _, _, tw, th = self.tile
+        tx, ty = (tw + 7) // 8, (th + 7) // 8
+        counts = np.zeros((ty, tx), np.uint32)
+        errors = np.zeros((ty, tx), np.float32)
+        self._chk(self._lib.crt_read_adaptive(self._h, counts.ctypes.data, errors.ctypes.data))
+        return counts, errors
+
     @property
     def sample(self) -> int:
         v = C.c_uint32()

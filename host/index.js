@@ -5,6 +5,9 @@
 // --denoise K: --out gets the image denoised with K a-trous iterations (crt_denoise) instead of the plain average
 // --orbit N: N frames of --spp each, the eye turned about the look-at point (one upload and build, then setCamera per
 //            frame), written as OUT_000.ppm, OUT_001.ppm, ...
+// --adaptive T [--adaptive-step N] [--adaptive-min M]: adaptive sampling (traceAdaptive), rounds of N (16) samples until
+//            every 8x8 tile has an error <= T or holds --spp samples; a tile below M (default min(--spp, 2N)) samples is
+//            sampled whatever its error; prints rounds, pixel-samples, seconds and the min / median / max tile count
 const fs = require('fs');
 const { Main, writePPM, orbitCameras } = require('./main');
 const sceneLoader = require('./sceneLoader');
@@ -34,6 +37,7 @@ if (args['pack-only']) { // dump the packed host buffers (used by the packer par
 const spp = num('spp', 16);
 const r = Main({ sceneFile: args.scene, width: args.width ? num('width') : undefined, height: args.height ? num('height') : undefined,
   accel: args.accel || 'bvh2', device: num('device', 0) });
+if ('adaptive' in args && (args.orbit || 'denoise' in args)) { console.error('--adaptive goes with neither --orbit nor --denoise'); process.exit(2); }
 if (args.orbit) {
   const n = num('orbit'), base = String(args.out || 'orbit.ppm').replace(/\.ppm$/, ''), outs = [];
   const t1 = process.hrtime.bigint();
@@ -44,6 +48,23 @@ if (args.orbit) {
     writePPM(outs[k], 'denoise' in args ? r.denoise({ iterations: num('denoise') }) : r.readRgba8(), r.width, r.height);
   });
   console.log(JSON.stringify({ width: r.width, height: r.height, frames: n, spp, seconds: Number(process.hrtime.bigint() - t1) / 1e9, out: outs }));
+  r.destroy();
+  process.exit(0);
+}
+if ('adaptive' in args) {
+  const step = num('adaptive-step', 16), minS = num('adaptive-min', Math.min(spp, 2 * step)), t1 = process.hrtime.bigint();
+  let rounds = 0;
+  while (r.traceAdaptive({ samples: step, threshold: num('adaptive'), minSamples: minS, maxSamples: spp })) rounds++;
+  const ad = r.readAdaptive(), counts = Array.from(ad.counts).sort((a, b) => a - b);
+  let pixelSamples = 0;
+  for (let ty = 0; ty < ad.tilesY; ty++)
+    for (let tx = 0; tx < ad.tilesX; tx++)
+      pixelSamples += ad.counts[ty * ad.tilesX + tx] * Math.min(8, r.width - 8 * tx) * Math.min(8, r.height - 8 * ty);
+  const seconds = Number(process.hrtime.bigint() - t1) / 1e9;
+  if (args.out) writePPM(args.out, r.readRgba8(), r.width, r.height);
+  const mid = counts.length >> 1, median = counts.length % 2 ? counts[mid] : (counts[mid - 1] + counts[mid]) / 2;
+  console.log(JSON.stringify({ width: r.width, height: r.height, adaptive: num('adaptive'), rounds, pixel_samples: pixelSamples, seconds,
+    tile_samples: { min: counts[0], median, max: counts[counts.length - 1] } }));
   r.destroy();
   process.exit(0);
 }

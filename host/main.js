@@ -69,6 +69,10 @@ function Main(options = {}) {
     updatePrimitives: (first, records) => a.updatePrimitives(device, first, records),
     updateLights: (first, records) => a.updateLights(device, first, records),
     refitAccel: () => a.refitAccel(device),
+    // adaptive sampling (include/crt.h "Adaptive sampling"): more samples for the 8x8 tiles that have not converged;
+    // returns how many tiles that was (0: done).  readAdaptive: {counts, errors, tilesX, tilesY}
+    traceAdaptive: (opts = {}) => a.traceAdaptive(device, opts),
+    readAdaptive: () => a.readAdaptive(device),
     counters: () => a.counters(device),
     enableCounters: (on) => a.enableCounters(device, !!on),
     lastTraceMs: () => a.lastTraceMs(device),

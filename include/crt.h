@@ -273,6 +273,41 @@ int crt_refit_accel(crt_ctx *ctx, int *rebuilt);
 /* Test hook: the hit_pad the kernels use. */
 int crt_debug_hit_pad(crt_ctx *ctx, float *out);
 
+/* ------------------------------------------------------------------ Adaptive sampling
+ * Per 8x8 tile of the context's rectangle: stop sampling the tiles that have converged.  Sample s of pixel
+ * (x, y) depends on (x, y, s) only, so a pixel of a tile that holds n samples holds exactly the accumulator of a uniform
+ * render of n samples, whatever the other tiles hold; its rgba8 is tone-mapped with its tile's count.
+ * A tile's error E is the largest, over its pixels, of the standard error of the mean luminance Y, times the slope of the
+ * exposure curve 1 - exp(-2.2 Y) at that mean (NaN counts as +inf; E = +inf below 2 samples).  Tile t holding n_t
+ * samples is ACTIVE iff (max_samples == 0 || n_t < max_samples) && (n_t < min_samples || !(E_t <= threshold)).
+ * crt_trace_adaptive finishes what is in flight, selects the active tiles on the GPU (reading back their number, 4 bytes),
+ * enqueues `samples` more samples for each of them (samples n_t + 1 .. n_t + samples) and returns without waiting for them,
+ * like crt_trace.  Tiles that are not active are not touched.
+ * State: the first successful call puts the context into the ADAPTIVE state; it needs sample 0 (after crt_reset, an upload
+ * or an edit; else CRT_ESTATE).  Every call that zeroes or replaces the accumulator (crt_reset, crt_write_accum,
+ * crt_upload_scene, crt_set_tile, crt_set_row_bands, the scene edits) returns to the uniform state; crt_build_accel keeps it.
+ * In the adaptive state crt_trace, crt_sample_count, crt_read_latest_rgba8, crt_latest_sample, crt_read_sample_rgba8 and
+ * crt_denoise return CRT_ESTATE; crt_read_accum / crt_read_rgba8 / crt_bind_output / counters keep working.
+ * CRT_ESTATE also under a crt_comm_partition, and without a scene / accel structure or with a stale tree.  CRT_EINVAL (the
+ * context unchanged) for samples == 0, a negative or non-finite threshold, or max_samples != 0 && max_samples < min_samples. */
+typedef struct {
+    uint32_t samples;      /* samples added to every ACTIVE tile by this call, >= 1                    */
+    uint32_t min_samples;  /* a tile below this count is active whatever its error                      */
+    uint32_t max_samples;  /* a tile at or above this count is never active; 0 = no limit               */
+    float threshold;       /* converged when the tile's error <= threshold; finite and >= 0              */
+} crt_adaptive_params;
+/* NULL = the defaults (crt_adaptive_defaults).  *active_tiles (may be NULL) = tiles sampled by this call; 0 = nothing
+ * enqueued.  A call that fails after some of its samples were enqueued leaves the counts behind the accumulator: the
+ * context then refuses crt_trace_adaptive / crt_read_adaptive (CRT_ESTATE) until crt_reset. */
+int crt_trace_adaptive(crt_ctx *ctx, const crt_adaptive_params *params, uint32_t *active_tiles);
+/* The defaults {samples 64, min_samples 32, max_samples 4096, threshold 0.01}: the bindings start from what this returns
+ * (DESIGN.md 6c has the measurements they were chosen by).  No context needed. */
+int crt_adaptive_defaults(crt_adaptive_params *out);
+/* Per 8x8 tile of the context's rectangle, row-major, tiles_x = ceil(tw/8), tiles_y = ceil(th/8):
+ * counts = samples the tile holds, errors = the tile's error E as the NEXT crt_trace_adaptive will judge it.
+ * Either pointer may be NULL.  A sync point.  CRT_ESTATE in the uniform state. */
+int crt_read_adaptive(crt_ctx *ctx, uint32_t *counts, float *errors);
+
 /* Counters accumulate over crt_trace calls while enabled (off by default: the
  * counting kernel variant is slower). */
 int crt_enable_counters(crt_ctx *ctx, int on);
