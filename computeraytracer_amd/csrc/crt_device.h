@@ -98,12 +98,15 @@ struct AsParams {
 //   sh_d    (light dir.xyz, t of the light's own primitive)   pending shadow ray
 //   beta, radiance, nee                   path throughput, radiance, NEE term waiting for visibility
 //   rng     uvec4 PCG state               (ComputeShader.wgsl:899)
-//   misc    (work id, flags, last_bounce_pdf bits, etaScale bits)
+//   misc    (work id, flags, last_bounce_pdf bits, etaScale bits); a fresh slot (kWfFresh): (work id, flags, sample, tea seed)
 //   hit     (t, hit slot bits)            written by the trace kernel for extension rays
 //   vis     in: light primitive index, out: 1 = light visible    (shadow rays)
 //   list[parity][class]                   slots with an active ray this iteration (ballot/popc compacted)
 //   staging[b] (xyz, -) per (sample, pixel)  finished samples of the batch with id b, summed in sample order by k_wf_resolve
 constexpr uint32_t kWfAlive = 1u, kWfDying = 2u, kWfShadow = 4u, kWfSpecular = 8u, kWfInTrans = 16u;
+// The slot holds a camera ray k_wf_gen has started and nobody has shaded yet: misc = (work id, flags, sample, tea seed)
+// and ray_o / ray_d / beta / rng hold nothing -- the shade step rebuilds the ray from those (camera_ray)
+constexpr uint32_t kWfFresh = 32u;
 constexpr uint32_t kWfNanRay = 1u << 31;   // the slot's (camera) ray is non-finite and has not been traced: the next shade step resolves it with the reference loop
 constexpr uint32_t kWfHasRad = 1u << 30;   // radiance[slot] holds the path's radiance (else it is still zero: nothing was ever stored)
 // ray-list entries: the slot, and on shadow-list entries a mark "this slot also listed an extension ray"

@@ -113,6 +113,38 @@ __device__ __noinline__ float2 resolve_nonfinite(const float4 *prim, const float
     return float2{tm, bits_f(bs)};
 }
 
+// The camera ray of (px, py, sample) and the path's RNG state after its three draws (:98-103, :317-319).  k_wf_gen lists
+// it for the traversal kernel, and the shade step of a fresh slot (kWfFresh) rebuilds it from the same four inputs: the
+// same operations in the same order (no contraction, csrc/Makefile), so the direction it shades is the one that was traced.
+struct CamRay { f3 eye, d; Rng rng; uint32_t lambda; bool nan_ray; };
+__device__ __forceinline__ CamRay camera_ray(const DevScene &S, uint32_t px, uint32_t py, uint32_t sample, uint32_t seed)
+{
+    CamRay c;
+    c.rng = Rng{py, px * 100u, sample, seed};                                       // :98 (tea(px, py*100) from k_wf_tea)
+    const float jx = rnd(c.rng);
+    const float fs = ((float)px + ((float)(sample % kGrid) + jx) / (float)kGrid) / (float)S.W;
+    const float jy = rnd(c.rng);
+    const float ft = ((float)S.H - (float)py + ((float)(sample % kGrid) + jy) / (float)kGrid) / (float)S.H;
+    const f3 llc = f3{S.cam[0], S.cam[1], S.cam[2]}, hor = f3{S.cam[3], S.cam[4], S.cam[5]};
+    const f3 ver = f3{S.cam[6], S.cam[7], S.cam[8]};
+    c.eye = f3{S.cam[9], S.cam[10], S.cam[11]};
+    c.d = normalize(((llc + hor * fs) + ver * ft) - c.eye);
+    const float ul = rnd(c.rng);
+    c.lambda = (uint32_t)(301.0f * ul);                                               // :317-319
+    c.nan_ray = !finite3(c.eye) || !finite3(c.d);
+    return c;
+}
+
+// The full-frame pixel of a slot's work id (k_wf_gen's mapping: 8x8 tiles of the tile rectangle, row bands).
+__device__ __forceinline__ void work_pixel(const WfParams &P, uint32_t work, uint32_t &px, uint32_t &py)
+{
+    const uint32_t pp = work % P.npix_padded;
+    const uint32_t tile = pp >> 6, l = pp & 63u;
+    const uint32_t lx = (tile % P.tiles_x) * 8u + (l & 7u), ly = (tile / P.tiles_x) * 8u + (l >> 3);
+    px = P.x0 + lx;
+    py = P.y0 + (ly / P.band) * P.band * P.stride + P.phase * P.band + ly % P.band;
+}
+
 // ------------------------------------------------------------------ shade
 struct PathRegs {
     f3 ray_o, ray_d;
@@ -306,13 +338,26 @@ __device__ __forceinline__ ShadeOut shade_body(const WfParams &P, uint32_t slot,
     CRT_PROBE(tp, 2)
 
     if (alive) {
+        if (R.flags & kWfFresh) {
+            // a path k_wf_gen started: nothing of it is in the slot streams but (work, flags, sample, seed) -- its camera
+            // ray again, and what every path starts with (:98-103): the eye, no exclusion, throughput 1, pdfs 1
+            uint32_t px, py;
+            work_pixel(P, R.work, px, py);
+            const CamRay c = camera_ray(S, px, py, misc.z, misc.w);
+            v_ro = float4{c.eye.x, c.eye.y, c.eye.z, bits_f(0xFFFFFFFFu)};
+            v_rd = float4{c.d.x, c.d.y, c.d.z, 0.0f};
+            v_beta = float4{1.0f, 1.0f, 1.0f, 1.0f};
+            rs = uint4{c.rng.x, c.rng.y, c.rng.z, c.rng.w};
+            R.last_pdf = 1.0f; R.etaScale = 1.0f;
+            R.flags &= ~kWfFresh;
+        }
         R.ray_o = xyz(v_ro); R.exclude = f_bits(v_ro.w);
         R.ray_d = xyz(v_rd);
         R.beta = f4{v_beta.x, v_beta.y, v_beta.z, v_beta.w};
+        R.rng = Rng{rs.x, rs.y, rs.z, rs.w};
         // (a path's radiance is stored only once something has been added to it: until then the array holds what the
         // slot's previous path left there)
         R.radiance = (R.flags & kWfHasRad) ? f4{v_rad.x, v_rad.y, v_rad.z, v_rad.w} : f4{0.0f, 0.0f, 0.0f, 0.0f};
-        R.rng = Rng{rs.x, rs.y, rs.z, rs.w};
         uint32_t wl[4];
         wavelengths_of((R.flags >> kWfLambdaShift) & 0x1FFu, wl);
         uint32_t depth = (R.flags >> kWfDepthShift) & 0xFFu;
@@ -470,12 +515,10 @@ __device__ __forceinline__ uint32_t shade_store(const WfParams &P, uint32_t slot
     PathRegs &R = so.R;
     uint32_t resolved = 0u;
     if (in_pool) {
-        // ray_o, beta and misc are written for EVERY slot: a dead slot gets what a fresh path starts with (the eye, no exclusion,
-        // throughput 1, last_bounce_pdf = etaScale = 1) here, in the launch's coalesced streams, so that k_wf_gen -- whose
-        // stores go to scattered slots, 16 bytes at a time: 2.5 x their size in HBM writes -- only writes what depends on the pixel.
-        const float4 vo = so.alive ? float4{R.ray_o.x, R.ray_o.y, R.ray_o.z, bits_f(R.exclude)} : float4{S.cam[9], S.cam[10], S.cam[11], bits_f(0xFFFFFFFFu)};
-        stnt(&P.ray_o[slot], vo);
+        // A dead slot gets its misc only (that is what marks it dead): k_wf_gen re-arms it with one 16-byte store of misc
+        // (kWfFresh), and the next shade step rebuilds everything else a fresh path starts with.
         if (so.alive) {
+            stnt(&P.ray_o[slot], float4{R.ray_o.x, R.ray_o.y, R.ray_o.z, bits_f(R.exclude)});
             // A non-finite ray (e.g. refract at the numerical edge of total reflection) is decided
             // by the reference loop in its own order; do that here and flag the ray as resolved
             // so the traversal kernel stays free of the fallback.
@@ -494,9 +537,9 @@ __device__ __forceinline__ uint32_t shade_store(const WfParams &P, uint32_t slot
 #ifdef CRT_WHATIF_EXTRA_STREAM          /* sensitivity probe: 16 B more read and written per live slot (an array the pool does not use) */
             if (!FINISH) { const float4 x = ldnt(&P.sh_d[slot]); stnt(&P.sh_d[slot], float4{x.y, x.x, x.w, x.z}); }
 #endif
+            stnt(&P.beta[slot], float4{R.beta.x, R.beta.y, R.beta.z, R.beta.w});
         }
-        stnt(&P.beta[slot], so.alive ? float4{R.beta.x, R.beta.y, R.beta.z, R.beta.w} : float4{1.0f, 1.0f, 1.0f, 1.0f});
-        stnt(&P.misc[slot], so.alive ? uint4{R.work, R.flags, f_bits(R.last_pdf), f_bits(R.etaScale)} : uint4{0u, 0u, f_bits(1.0f), f_bits(1.0f)});
+        stnt(&P.misc[slot], so.alive ? uint4{R.work, R.flags, f_bits(R.last_pdf), f_bits(R.etaScale)} : uint4{0u, 0u, 0u, 0u});
     }
     return resolved;
 }
@@ -594,7 +637,8 @@ __global__ __launch_bounds__(CRT_WF_SHADE_BLOCK, CRT_WF_SHADE_MIN_WAVES) void k_
     if (P.evict_mask) {
         // Move the (few) paths of the batches named by evict_mask out of the pool: their rays of the last
         // iteration are traced, so the slot state is complete; k_wf_finish continues them from the side pool.
-        // The slot is then dead and is listed for k_wf_gen below like any other.
+        // The slot is then dead and is listed for k_wf_gen below like any other.  (A fresh slot's state is all in its misc:
+        // k_wf_finish starts with a shade step, which rebuilds the rest.)
         uint4 misc = uint4{0, 0, 0, 0};
         if (in_pool) misc = P.misc[slot];
         const uint32_t par = (misc.y >> kWfBatchShift) & (kWfRing - 1u);
@@ -826,28 +870,17 @@ __global__ __launch_bounds__(64) void k_wf_gen(const WfParams P, uint32_t it, co
         if (valid) {
             const uint32_t px = P.x0 + lx, sample = ADAPT ? A.base[tile] + P.seg[sg].first_sample + sample_off : P.seg[sg].first_sample + sample_off;
             const uint32_t py = P.y0 + (ly / P.band) * P.band * P.stride + P.phase * P.band + ly % P.band;
-            Rng rng = Rng{py, px * 100u, sample, P.tea[(size_t)ly * P.tw + lx]};             // :98 (tea(px, py*100) from k_wf_tea)
-            const float jx = rnd(rng);
-            const float fs = ((float)px + ((float)(sample % kGrid) + jx) / (float)kGrid) / (float)S.W;
-            const float jy = rnd(rng);
-            const float ft = ((float)S.H - (float)py + ((float)(sample % kGrid) + jy) / (float)kGrid) / (float)S.H;
-            const f3 llc = f3{S.cam[0], S.cam[1], S.cam[2]}, hor = f3{S.cam[3], S.cam[4], S.cam[5]};
-            const f3 ver = f3{S.cam[6], S.cam[7], S.cam[8]};
-            eye = f3{S.cam[9], S.cam[10], S.cam[11]};
-            d = normalize(((llc + hor * fs) + ver * ft) - eye);
-            const float ul = rnd(rng);
-            const uint32_t lambda = (uint32_t)(301.0f * ul);                                  // :317-319
-            const bool nan_ray = !finite3(eye) || !finite3(d);
-            const uint32_t flags = kWfAlive | (lambda << kWfLambdaShift) | (sg << kWfBatchShift) | (nan_ray ? kWfNanRay : 0u);
-            // (ray_o = the eye, beta = 1, last_bounce_pdf = etaScale = 1 are in the slot already: k_wf_shade writes them into
-            // every dead slot with its coalesced streams)
-            stnt(&P.ray_d[slot], float4{d.x, d.y, d.z, bits_f(0u)});
-            stnt(&P.rng[slot], uint4{rng.x, rng.y, rng.z, rng.w});
-            stnt((uint2 *)&P.misc[slot], uint2{(ADAPT ? sample_off * P.npix_padded + pp0 : w0) + lane, flags});   // work (full-frame id), flags
+            const uint32_t seed = P.tea[(size_t)ly * P.tw + lx];
+            const CamRay c = camera_ray(S, px, py, sample, seed);
+            eye = c.eye; d = c.d;
+            const uint32_t flags = kWfAlive | kWfFresh | (c.lambda << kWfLambdaShift) | (sg << kWfBatchShift) | (c.nan_ray ? kWfNanRay : 0u);
+            // The slot gets ONE 16-byte store (its stores go to scattered slots: 2.5 x their size in HBM writes): work
+            // (full-frame id), flags, and what the next shade step needs to rebuild the ray and the RNG state (kWfFresh).
+            stnt(&P.misc[slot], uint4{(ADAPT ? sample_off * P.npix_padded + pp0 : w0) + lane, flags, sample, seed});
             // (a camera ray is finite unless the camera itself is not.  Such a ray is decided by the reference loop in its own
             // order like any other non-finite ray -- by the NEXT shade step (kWfNanRay): a call to that loop in this kernel would
             // cost it half its occupancy in registers, and the kernel sits between the shade and the traversal launch of its pipe)
-            if (!finite3(eye) || !finite3(d)) resolved = 1u;
+            if (c.nan_ray) resolved = 1u;
         }
         if (!have_b0) { b0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)b0); have_b0 = true; }   // (its round trip ran under the first set-up)
         if (valid) {
