@@ -512,6 +512,69 @@ static napi_value js_denoise(napi_env env, napi_callback_info info)
     return ta;
 }
 
+/* denoiseAdaptive(h, {iterations, sigmaVariance, sigmaNormal, sigmaPlane, variance}) -> Uint8Array (tw*th*4 rgba8), or
+ * with variance: true -> {rgba8, variance: Float32Array(tw*th)}: the variance-guided filter of an adaptive render
+ * (include/crt.h "Denoised preview of an adaptive render").  A missing option takes the library's default
+ * (crt_denoise_adaptive_defaults).  denoiseAdaptiveAsync(h, {...}) -> Promise of the Uint8Array (below). */
+static int denoise_adaptive_options(napi_env env, napi_value opts, int have_opts, crt_denoise_adaptive_params *p, bool *variance)
+{
+    double it, sv, sn, sx;
+    napi_valuetype t = napi_undefined;
+    if (crt_denoise_adaptive_defaults(p) != CRT_OK) { napi_throw_error(env, NULL, "crt_denoise_adaptive_defaults failed"); return 0; }
+    it = p->iterations; sv = p->sigma_variance; sn = p->sigma_normal; sx = p->sigma_plane;
+    if (variance) *variance = false;
+    if (have_opts && napi_typeof(env, opts, &t) != napi_ok) { napi_throw_type_error(env, NULL, "denoiseAdaptive: options object expected"); return 0; }
+    if (t == napi_object) {
+        if (!opt_number(env, opts, "iterations", &it) || !opt_number(env, opts, "sigmaVariance", &sv) ||
+            !opt_number(env, opts, "sigmaNormal", &sn) || !opt_number(env, opts, "sigmaPlane", &sx)) {
+            napi_throw_type_error(env, NULL, "denoiseAdaptive: options must be numbers");
+            return 0;
+        }
+        bool has = false;
+        napi_value v;
+        if (variance && napi_has_named_property(env, opts, "variance", &has) == napi_ok && has &&
+            napi_get_named_property(env, opts, "variance", &v) == napi_ok)
+            napi_coerce_to_bool(env, v, &v), napi_get_value_bool(env, v, variance);
+    } else if (t != napi_undefined && t != napi_null) {
+        napi_throw_type_error(env, NULL, "denoiseAdaptive: options object expected");
+        return 0;
+    }
+    if (!(it >= 0.0 && it <= 4294967295.0) || it != (double)(uint32_t)it) {
+        napi_throw_range_error(env, NULL, "denoiseAdaptive: iterations must be a non-negative integer");
+        return 0;
+    }
+    p->iterations = (uint32_t)it; p->sigma_variance = (float)sv; p->sigma_normal = (float)sn; p->sigma_plane = (float)sx;
+    return 1;
+}
+
+static napi_value js_denoise_adaptive(napi_env env, napi_callback_info info)
+{
+    size_t argc = 2;
+    napi_value argv[2];
+    NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    if (argc < 1) { napi_throw_type_error(env, NULL, "too few arguments"); return NULL; }
+    crt_ctx *ctx = get_ctx(env, argv[0]);
+    if (!ctx) return NULL;
+    crt_denoise_adaptive_params p;
+    bool variance = false;
+    if (!denoise_adaptive_options(env, argc > 1 ? argv[1] : NULL, argc > 1, &p, &variance)) return NULL;
+    uint32_t tl[4];
+    CRT_CHECK(env, ctx, "crt_tile", crt_tile(ctx, tl));
+    size_t px = (size_t)tl[2] * tl[3];
+    void *data = NULL, *vdata = NULL;
+    napi_value ab, ta, vab, vta, obj;
+    NAPI_OK(env, napi_create_arraybuffer(env, px * 4, &data, &ab));
+    if (variance) NAPI_OK(env, napi_create_arraybuffer(env, px * 4, &vdata, &vab));
+    CRT_CHECK(env, ctx, "crt_denoise_adaptive", crt_denoise_adaptive(ctx, &p, NULL, (uint8_t *)data, (float *)vdata));
+    NAPI_OK(env, napi_create_typedarray(env, napi_uint8_array, px * 4, ab, 0, &ta));
+    if (!variance) return ta;
+    NAPI_OK(env, napi_create_typedarray(env, napi_float32_array, px, vab, 0, &vta));
+    NAPI_OK(env, napi_create_object(env, &obj));
+    NAPI_OK(env, napi_set_named_property(env, obj, "rgba8", ta));
+    NAPI_OK(env, napi_set_named_property(env, obj, "variance", vta));
+    return obj;
+}
+
 static napi_value js_read_gbuffer(napi_env env, napi_callback_info info)
 {
     ARGS(1)
@@ -836,13 +899,15 @@ static napi_value js_set_stream(napi_env env, napi_callback_info info)
  * traceAsync(h, n), syncAsync(h), readRgba8Async(h), readAccumAsync(h) -> Promise.  The reference's frame() is
  * fire-and-forget (queue.submit, src/main.js:618-620): a Node display loop must not block its event loop on the
  * GPU either.  Jobs of one context run in call order. */
-enum { JOB_TRACE, JOB_SYNC, JOB_READ_RGBA8, JOB_READ_ACCUM, JOB_GATHER, JOB_READ_FRAME_RGBA8, JOB_READ_FRAME_ACCUM, JOB_READ_SAMPLE_RGBA8 };
+enum { JOB_TRACE, JOB_SYNC, JOB_READ_RGBA8, JOB_READ_ACCUM, JOB_GATHER, JOB_READ_FRAME_RGBA8, JOB_READ_FRAME_ACCUM, JOB_READ_SAMPLE_RGBA8,
+       JOB_DENOISE_ADAPTIVE };
 typedef struct job {
     napi_async_work work;
     napi_deferred deferred;
     slot *sl;
     int op, rc;
     uint32_t n, px;
+    crt_denoise_adaptive_params dn;     /* JOB_DENOISE_ADAPTIVE */
     void *data;              /* ArrayBuffer memory of a read job (kept alive by ab_ref) */
     napi_ref ab_ref;
     char err[640];
@@ -862,6 +927,7 @@ static void job_execute(napi_env env, void *data)
     case JOB_GATHER: j->rc = crt_gather(ctx, (int)j->n); break;
     case JOB_READ_FRAME_RGBA8: j->rc = crt_read_frame_rgba8(ctx, (uint8_t *)j->data); break;
     case JOB_READ_SAMPLE_RGBA8: j->rc = crt_read_sample_rgba8(ctx, j->n, (uint8_t *)j->data); break;
+    case JOB_DENOISE_ADAPTIVE: j->rc = crt_denoise_adaptive(ctx, &j->dn, NULL, (uint8_t *)j->data, NULL); break;
     default: j->rc = crt_read_frame_accum(ctx, (float *)j->data); break;
     }
     if (j->rc != CRT_OK) {
@@ -879,7 +945,8 @@ static void job_complete(napi_env env, napi_status status, void *data)
     if (j->rc == CRT_OK) {
         if (j->ab_ref) {
             napi_value ab;
-            const int bytes8 = j->op == JOB_READ_RGBA8 || j->op == JOB_READ_FRAME_RGBA8 || j->op == JOB_READ_SAMPLE_RGBA8;
+            const int bytes8 = j->op == JOB_READ_RGBA8 || j->op == JOB_READ_FRAME_RGBA8 || j->op == JOB_READ_SAMPLE_RGBA8 ||
+                               j->op == JOB_DENOISE_ADAPTIVE;
             if (napi_get_reference_value(env, j->ab_ref, &ab) == napi_ok)
                 napi_create_typedarray(env, bytes8 ? napi_uint8_array : napi_float32_array, (size_t)j->px * 4, ab, 0, &result);
         }
@@ -913,11 +980,14 @@ static napi_value start_job(napi_env env, napi_callback_info info, int op)
     if (!sl) return NULL;
     job *j = (job *)calloc(1, sizeof *j);
     j->sl = sl; j->op = op;
+    if (op == JOB_DENOISE_ADAPTIVE && !denoise_adaptive_options(env, argc > 1 ? argv[1] : NULL, argc > 1, &j->dn, NULL)) { free(j); return NULL; }
     if (op == JOB_TRACE || op == JOB_GATHER || op == JOB_READ_SAMPLE_RGBA8) {
         if (napi_get_value_uint32(env, argv[1], &j->n) != napi_ok) { free(j); napi_throw_type_error(env, NULL, "traceAsync / gatherAsync: a number expected"); return NULL; }
     }
-    if (op == JOB_READ_RGBA8 || op == JOB_READ_ACCUM || op == JOB_READ_FRAME_RGBA8 || op == JOB_READ_FRAME_ACCUM || op == JOB_READ_SAMPLE_RGBA8) {
-        const int frame = op == JOB_READ_FRAME_RGBA8 || op == JOB_READ_FRAME_ACCUM, bytes8 = op == JOB_READ_RGBA8 || op == JOB_READ_FRAME_RGBA8 || op == JOB_READ_SAMPLE_RGBA8;
+    if (op == JOB_READ_RGBA8 || op == JOB_READ_ACCUM || op == JOB_READ_FRAME_RGBA8 || op == JOB_READ_FRAME_ACCUM || op == JOB_READ_SAMPLE_RGBA8 ||
+        op == JOB_DENOISE_ADAPTIVE) {
+        const int frame = op == JOB_READ_FRAME_RGBA8 || op == JOB_READ_FRAME_ACCUM;
+        const int bytes8 = op == JOB_READ_RGBA8 || op == JOB_READ_FRAME_RGBA8 || op == JOB_READ_SAMPLE_RGBA8 || op == JOB_DENOISE_ADAPTIVE;
         uint32_t t[4];
         if (frame) { if (crt_image_size(sl->ctx, t + 2) != CRT_OK) { free(j); return throw_crt(env, sl->ctx, CRT_ESTATE, "crt_image_size"); } }
         else if (crt_tile(sl->ctx, t) != CRT_OK) { free(j); return throw_crt(env, sl->ctx, CRT_ESTATE, "crt_tile"); }
@@ -957,6 +1027,7 @@ static napi_value js_gather_async(napi_env env, napi_callback_info info) { retur
 static napi_value js_read_sample_rgba8_async(napi_env env, napi_callback_info info) { return start_job(env, info, JOB_READ_SAMPLE_RGBA8); }
 static napi_value js_read_frame_rgba8_async(napi_env env, napi_callback_info info) { return start_job(env, info, JOB_READ_FRAME_RGBA8); }
 static napi_value js_read_frame_accum_async(napi_env env, napi_callback_info info) { return start_job(env, info, JOB_READ_FRAME_ACCUM); }
+static napi_value js_denoise_adaptive_async(napi_env env, napi_callback_info info) { return start_job(env, info, JOB_DENOISE_ADAPTIVE); }
 
 static napi_value js_abi_version(napi_env env, napi_callback_info info)
 {
@@ -990,6 +1061,7 @@ static napi_value init(napi_env env, napi_value exports)
         {"setCamera", js_set_camera}, {"updatePrimitives", js_update_primitives}, {"updateLights", js_update_lights},
         {"refitAccel", js_refit_accel},
         {"traceAdaptive", js_trace_adaptive}, {"readAdaptive", js_read_adaptive},
+        {"denoiseAdaptive", js_denoise_adaptive}, {"denoiseAdaptiveAsync", js_denoise_adaptive_async},
         {"gatherAsync", js_gather_async}, {"readFrameRgba8Async", js_read_frame_rgba8_async}, {"readFrameAccumAsync", js_read_frame_accum_async},
     };
     for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++) {

@@ -18,7 +18,8 @@ def main():
     ap.add_argument("--out", default="render.png")
     ap.add_argument("--checkpoint", default=None, help="resume from / save to this .npz")
     ap.add_argument("--denoise", type=int, default=None, metavar="K",
-                    help="write the image denoised with K a-trous iterations (crt_denoise) instead of the plain average")
+                    help="write the image denoised with K a-trous iterations instead of the plain average (crt_denoise; with "
+                         "--adaptive the variance-guided crt_denoise_adaptive)")
     ap.add_argument("--orbit", type=int, default=None, metavar="N",
                     help="N frames of --spp each with the eye turned about the look-at point (one upload and build, then "
                          "set_camera per frame), written as OUT_000.png, OUT_001.png, ...")
@@ -32,8 +33,8 @@ def main():
     args = ap.parse_args()
     if args.orbit is not None and (args.orbit < 1 or args.checkpoint):
         ap.error("--orbit needs N >= 1 and no --checkpoint")
-    if args.adaptive is not None and (args.orbit is not None or args.checkpoint or args.denoise is not None):
-        ap.error("--adaptive goes with neither --orbit, --checkpoint nor --denoise")
+    if args.adaptive is not None and (args.orbit is not None or args.checkpoint):
+        ap.error("--adaptive goes with neither --orbit nor --checkpoint")
     if (args.counts_out or args.adaptive_min is not None) and args.adaptive is None:
         ap.error("--counts-out and --adaptive-min need --adaptive")
     sc = scene.load_scene(args.scene)
@@ -82,12 +83,15 @@ def _adaptive(r, ps, args):
         rounds += 1
     counts, _ = r.read_adaptive()
     dt = time.time() - t0
-    (image.write_ppm if args.out.endswith(".ppm") else image.write_png)(args.out, r.read_rgba8())
+    rgba = r.read_rgba8() if args.denoise is None else r.denoise_adaptive(args.denoise)
+    (image.write_ppm if args.out.endswith(".ppm") else image.write_png)(args.out, rgba)
     pixel_counts = np.repeat(np.repeat(counts, 8, 0), 8, 1)[:ps.height, :ps.width]
     info = {"width": ps.width, "height": ps.height, "adaptive": args.adaptive, "rounds": rounds,
             "pixel_samples": int(pixel_counts.sum(dtype=np.uint64)), "seconds": round(dt, 4),
             "tile_samples": {"min": int(counts.min()), "median": float(np.median(counts)), "max": int(counts.max())},
             "out": args.out}
+    if args.denoise is not None:
+        info["denoise"] = args.denoise
     if args.counts_out:
         grey = (counts.astype(np.float64) * (255.0 / max(1, args.spp))).clip(0, 255).astype(np.uint8)
         rgba = np.repeat(np.repeat(grey, 8, 0), 8, 1)[:ps.height, :ps.width, None].repeat(4, 2)

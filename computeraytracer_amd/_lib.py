@@ -76,6 +76,8 @@ SIGNATURES = {
     "crt_trace_adaptive": (C.c_int, [_P, _P, _P]),
     "crt_read_adaptive": (C.c_int, [_P, _P, _P]),
     "crt_adaptive_defaults": (C.c_int, [_P]),
+    "crt_denoise_adaptive": (C.c_int, [_P, _P, _P, _P, _P]),
+    "crt_denoise_adaptive_defaults": (C.c_int, [_P]),
 }
 
 
@@ -95,6 +97,19 @@ def adaptive_defaults() -> AdaptiveParams:
 class DenoiseParams(C.Structure):
     """crt_denoise_params of include/crt.h."""
     _fields_ = [("iterations", C.c_uint32), ("sigma_color", C.c_float), ("sigma_normal", C.c_float), ("sigma_plane", C.c_float)]
+
+
+class DenoiseAdaptiveParams(C.Structure):
+    """crt_denoise_adaptive_params of include/crt.h."""
+    _fields_ = [("iterations", C.c_uint32), ("sigma_variance", C.c_float), ("sigma_normal", C.c_float), ("sigma_plane", C.c_float)]
+
+
+def denoise_adaptive_defaults() -> DenoiseAdaptiveParams:
+    """The library's defaults for crt_denoise_adaptive (crt_denoise_adaptive_defaults)."""
+    p = DenoiseAdaptiveParams()
+    if load().crt_denoise_adaptive_defaults(C.byref(p)) != 0:
+        raise RuntimeError("crt_denoise_adaptive_defaults failed")
+    return p
 
 
 _lib = None

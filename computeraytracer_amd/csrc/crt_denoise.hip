@@ -2,8 +2,12 @@
 // a-trous wavelet filter (Dammertz et al. 2010) over the accumulator's average.  It only READS the accumulator:
 // the bit-exact image and everything that produces it are untouched.  DESIGN.md "Denoised preview" has the
 // definition this follows operation by operation (tests/denoise_ref.py is its numpy restatement).
+//
+// crt_denoise_adaptive is the same filter for the adaptive state: per-tile counts, and a colour weight
+// scaled by the pixels' own variance (k_dn_prepare_as, k_dn_vblur, k_dn_atrous_as below).
 #include <algorithm>
 
+#include "crt_adaptive.h"
 #include "crt_shade.h"
 
 namespace crt {
@@ -140,6 +144,146 @@ __global__ __launch_bounds__(256) void k_dn_atrous(const DnParams P)
     if (P.rgba) P.rgba[p] = linear_rgb_to_rgba8(c);
 }
 
+// ---------------------------------------------------------------- the variance-guided filter (crt_denoise_adaptive)
+// DESIGN.md 6d defines it operation by operation (tests/denoise_adaptive_ref.py is its numpy restatement).  The colour
+// buffers carry the pixel's variance v in their w lane, so v_q rides along with c_q; the blurred variance rides along
+// with the key in one 8-byte word, so a matching tap costs the four requests of the plain filter.
+struct DnAsParams {
+    const float4 *c_in;         // linear rgb, w = variance v of the previous iteration
+    float4 *c_out;
+    const float4 *gbuf;
+    const uint2 *kv;            // per pixel: (key, bits of the 3x3 blur of v)
+    uchar4 *rgba;               // null, or the rgba8 of c_out (last iteration)
+    float *var;                 // null, or v of c_out (last iteration)
+    uint32_t tw, th, step;
+    float sv2;                  // sigma_variance^2
+    float inv_n, inv_x;
+};
+
+constexpr float kDnEps = (0.5f / 255.0f) * (0.5f / 255.0f);      // half an 8-bit step, squared
+
+// The filter's input in the adaptive state: c = M (accum / n) and v = e * e with the count n of the pixel's 8x8 tile.
+// v = 1 ("nothing known") below 2 samples or where e * e is not finite (e NaN or infinite, or its square overflows).
+__global__ __launch_bounds__(256) void k_dn_prepare_as(const float4 *__restrict__ accum, const float *__restrict__ q,
+                                                       const uint32_t *__restrict__ counts, uint32_t tw, uint32_t th,
+                                                       uint32_t tiles_x, float4 *__restrict__ c, uchar4 *__restrict__ rgba,
+                                                       float *__restrict__ var)
+{
+    const uint32_t x = blockIdx.x * 64u + (threadIdx.x & 63u), y = blockIdx.y * 4u + (threadIdx.x >> 6);
+    if (x >= tw || y >= th) return;
+    const size_t i = (size_t)y * tw + x;
+    const uint32_t n_t = counts[(y >> 3) * tiles_x + (x >> 3)];
+    const float4 a = accum[i];
+    const f3 rgb = xyz_to_linear_rgb(f3{a.x, a.y, a.z} / (float)n_t);
+    float v = 1.0f;
+    if (n_t >= 2u) {
+        const float e = pixel_error(a.y, q[i], n_t);
+        const float ee = e * e;
+        if (ee <= 3.40282347e38f) v = ee;
+    }
+    c[i] = float4{rgb.x, rgb.y, rgb.z, v};
+    if (rgba) rgba[i] = linear_rgb_to_rgba8(rgb);
+    if (var) var[i] = v;
+}
+
+// (1,2,1) x (1,2,1) / 16 of v at unit step over the taps inside the tile whose key equals the centre's, renormalised;
+// written next to the key.  grid as k_dn_atrous.
+__global__ __launch_bounds__(256) void k_dn_vblur(const float4 *__restrict__ c, const uint32_t *__restrict__ key,
+                                                  uint2 *__restrict__ kv, uint32_t utw, uint32_t uth)
+{
+    const int x = (int)(blockIdx.x * 16u + (threadIdx.x & 15u)), y = (int)(blockIdx.y * 16u + (threadIdx.x >> 4));
+    const int tw = (int)utw, th = (int)uth;
+    if (x >= tw || y >= th) return;
+    const size_t p = (size_t)y * utw + (size_t)x;
+    const uint32_t key_p = key[p];
+    const float g[3] = {0.25f, 0.5f, 0.25f};
+    float sv = 0.0f, sw = 0.0f;
+#pragma unroll
+    for (int dy = -1; dy <= 1; dy++) {
+        const int qy = y + dy;
+        if (qy < 0 || qy >= th) continue;
+#pragma unroll
+        for (int dx = -1; dx <= 1; dx++) {
+            const int qx = x + dx;
+            if (qx < 0 || qx >= tw) continue;
+            const size_t q = (size_t)qy * utw + (size_t)qx;
+            if (key[q] != key_p) continue;                      // (the centre always passes)
+            const float w = g[dx + 1] * g[dy + 1];
+            sv = sv + w * c[q].w;
+            sw = sw + w;
+        }
+    }
+    kv[p] = uint2{key_p, f_bits(sv / sw)};
+}
+
+// One iteration: k_dn_atrous with the colour term scaled by the two pixels' blurred variances, and the variance carried
+// through the same weights.
+__global__ __launch_bounds__(256) void k_dn_atrous_as(const DnAsParams P)
+{
+    const int x = (int)(blockIdx.x * 16u + (threadIdx.x & 15u)), y = (int)(blockIdx.y * 16u + (threadIdx.x >> 4));
+    const int tw = (int)P.tw, th = (int)P.th, s = (int)P.step;
+    if (x >= tw || y >= th) return;
+    const size_t p = (size_t)y * P.tw + (size_t)x;
+    const uint2 kv_p = P.kv[p];
+    const uint32_t key_p = kv_p.x;
+    const float vt_p = bits_f(kv_p.y);
+    const bool hit = key_p != kNoHit;
+    f3 x_p = f3{0, 0, 0}, n_p = f3{0, 0, 0};
+    if (hit) {
+        const float4 g0 = P.gbuf[2 * p], g1 = P.gbuf[2 * p + 1];
+        x_p = f3{g0.y, g0.z, g0.w};
+        n_p = f3{g1.x, g1.y, g1.z};
+    }
+    const float4 cp4 = P.c_in[p];
+    const f3 t_p = dn_display(cp4);
+    const float h[5] = {1.0f / 16.0f, 1.0f / 4.0f, 3.0f / 8.0f, 1.0f / 4.0f, 1.0f / 16.0f};
+    float sw = 0.0f, sv = 0.0f;
+    f3 sc = f3{0, 0, 0};
+#pragma unroll
+    for (int dy = -2; dy <= 2; dy++) {
+        const int qy = y + dy * s;
+        if (qy < 0 || qy >= th) continue;
+#pragma unroll
+        for (int dx = -2; dx <= 2; dx++) {
+            const int qx = x + dx * s;
+            if (qx < 0 || qx >= tw) continue;
+            if (dx == 0 && dy == 0) {
+                const float w = h[2] * h[2];
+                sw = sw + w;
+                sc = sc + f3{cp4.x, cp4.y, cp4.z} * w;
+                sv = sv + (w * w) * cp4.w;
+                continue;
+            }
+            const size_t q = (size_t)qy * P.tw + (size_t)qx;
+            const uint2 kv_q = P.kv[q];
+            if (kv_q.x != key_p) continue;
+            const float4 cq4 = P.c_in[q];
+            if (!finite4(cq4)) continue;
+            const f3 dt = t_p - dn_display(cq4);
+            float e = dot(dt, dt) / (P.sv2 * (vt_p + bits_f(kv_q.y)) + kDnEps);
+            if (hit) {
+                const float4 g0 = P.gbuf[2 * q], g1 = P.gbuf[2 * q + 1];
+                const f3 dn = n_p - f3{g1.x, g1.y, g1.z};
+                e = e + dot(dn, dn) * P.inv_n;
+                const f3 v = f3{g0.y, g0.z, g0.w} - x_p;
+                const float len = length(v);
+                if (len > 0.0f) e = e + (abs_(dot(n_p, v)) / len) * P.inv_x;
+            }
+            const float w = (h[dx + 2] * h[dy + 2]) * exp_(-e);
+            sw = sw + w;
+            sc = sc + f3{cq4.x, cq4.y, cq4.z} * w;
+            sv = sv + (w * w) * cq4.w;
+        }
+    }
+    const f3 c = sc / sw;
+    // (a centre whose colour is not finite has NaN weights: it keeps its v, so that v stays finite and the NaN reaches
+    // no neighbour through the blurred variance either)
+    const float v = finite4(cp4) ? sv / (sw * sw) : cp4.w;
+    P.c_out[p] = float4{c.x, c.y, c.z, v};
+    if (P.rgba) P.rgba[p] = linear_rgb_to_rgba8(c);
+    if (P.var) P.var[p] = v;
+}
+
 // ---------------------------------------------------------------- launchers (called from crt_api.cpp)
 hipError_t dn_launch_gbuffer(const DevScene &S, uint32_t x0, uint32_t y0, uint32_t tw, uint32_t th, float4 *gbuf, uint32_t *key,
                              int brute, hipStream_t stream)
@@ -174,6 +318,42 @@ hipError_t dn_launch_filter(const float4 *accum, float n, const float4 *gbuf, co
         P.inv_n = (float)std::min(3.0e38, 1.0 / ((double)sigma_normal * sigma_normal));
         P.inv_x = (float)std::min(3.0e38, 1.0 / (double)sigma_plane);
         hipLaunchKernelGGL(k_dn_atrous, dim3((tw + 15u) / 16u, (th + 15u) / 16u), dim3(256), 0, stream, P);
+        e = hipGetLastError();
+        *out = P.c_out;
+    }
+    return e;
+}
+
+// The adaptive state's filter: (accum, q, counts) -> c[0] with v in w, then per iteration the variance blur into kv and
+// the filter pass between c[0] and c[1]; the last launch also writes rgba and var (either may be null).
+hipError_t dn_launch_filter_adaptive(const float4 *accum, const float *q, const uint32_t *counts, const float4 *gbuf,
+                                     const uint32_t *key, uint2 *kv, float4 *c0, float4 *c1, uchar4 *rgba, float *var,
+                                     uint32_t tw, uint32_t th, uint32_t iterations, float sigma_variance, float sigma_normal,
+                                     float sigma_plane, float4 **out, hipStream_t stream)
+{
+    *out = c0;
+    if ((size_t)tw * th == 0) return hipSuccess;
+    const bool last0 = iterations == 0;
+    hipLaunchKernelGGL(k_dn_prepare_as, dim3((tw + 63u) / 64u, (th + 3u) / 4u), dim3(256), 0, stream, accum, q, counts, tw, th,
+                       (tw + 7u) / 8u, c0, last0 ? rgba : nullptr, last0 ? var : nullptr);
+    hipError_t e = hipGetLastError();
+    float4 *buf[2] = {c0, c1};
+    const dim3 grid((tw + 15u) / 16u, (th + 15u) / 16u);
+    for (uint32_t i = 0; i < iterations && e == hipSuccess; i++) {
+        DnAsParams P{};
+        P.c_in = buf[i & 1u]; P.c_out = buf[(i + 1u) & 1u];
+        P.gbuf = gbuf; P.kv = kv;
+        const bool last = i + 1u == iterations;
+        P.rgba = last ? rgba : nullptr;
+        P.var = last ? var : nullptr;
+        P.tw = tw; P.th = th; P.step = 1u << i;
+        P.sv2 = (float)std::min(3.0e38, (double)sigma_variance * sigma_variance);
+        P.inv_n = (float)std::min(3.0e38, 1.0 / ((double)sigma_normal * sigma_normal));
+        P.inv_x = (float)std::min(3.0e38, 1.0 / (double)sigma_plane);
+        hipLaunchKernelGGL(k_dn_vblur, grid, dim3(256), 0, stream, P.c_in, key, kv, tw, th);
+        e = hipGetLastError();
+        if (e != hipSuccess) break;
+        hipLaunchKernelGGL(k_dn_atrous_as, grid, dim3(256), 0, stream, P);
         e = hipGetLastError();
         *out = P.c_out;
     }

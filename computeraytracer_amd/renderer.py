@@ -250,6 +250,28 @@ class Renderer:
         self._chk(self._lib.crt_denoise(self._h, C.byref(p), lin.ctypes.data if rgb else None, rgba.ctypes.data))
         return (rgba, lin) if rgb else rgba
 
+    def denoise_adaptive(self, iterations: int | None = None, sigma_variance: float | None = None,
+                         sigma_normal: float | None = None, sigma_plane: float | None = None, rgb: bool = False,
+                         var: bool = False):
+        """The variance-guided a-trous filter of an adaptive render (include/crt.h "Denoised preview of an adaptive
+        render"): rgba8 (H, W, 4); with rgb=True also linear rgb (H, W, 4) float32 (channel 3 = the variance), with
+        var=True also the variance left after filtering (H, W) float32 -- a tuple in that order.  A parameter left out
+        takes the library's default (crt_denoise_adaptive_defaults).  Reads only; finishes what is in flight."""
+        _, _, tw, th = self.tile
+        p = _lib.denoise_adaptive_defaults()
+        if iterations is not None:
+            p.iterations = int(iterations)
+        for k, v in (("sigma_variance", sigma_variance), ("sigma_normal", sigma_normal), ("sigma_plane", sigma_plane)):
+            if v is not None:
+                setattr(p, k, float(v))
+        rgba = np.empty((th, tw, 4), np.uint8)
+        lin = np.empty((th, tw, 4), np.float32) if rgb else None
+        vout = np.empty((th, tw), np.float32) if var else None
+        self._chk(self._lib.crt_denoise_adaptive(self._h, C.byref(p), lin.ctypes.data if rgb else None, rgba.ctypes.data,
+                                                 vout.ctypes.data if var else None))
+        out = (rgba,) + ((lin,) if rgb else ()) + ((vout,) if var else ())
+        return out if len(out) > 1 else rgba
+
     def read_gbuffer(self) -> np.ndarray:
         """(H, W, 8) float32 per tile pixel: t, position, normal, hit index bits (0xFFFFFFFF = miss) of the primary
         ray of sample 8 -- the crt_debug_intersect record."""

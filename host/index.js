@@ -2,7 +2,8 @@
 'use strict';
 // CLI: node host/index.js [--scene file.json] [--width W --height H] [--spp N] [--accel bvh2|lbvh|none]
 //                         [--out image.ppm] [--dump prefix] [--pack-only prefix] [--denoise K] [--orbit N]
-// --denoise K: --out gets the image denoised with K a-trous iterations (crt_denoise) instead of the plain average
+// --denoise K: --out gets the image denoised with K a-trous iterations (crt_denoise; with --adaptive the variance-guided
+//            crt_denoise_adaptive) instead of the plain average
 // --orbit N: N frames of --spp each, the eye turned about the look-at point (one upload and build, then setCamera per
 //            frame), written as OUT_000.ppm, OUT_001.ppm, ...
 // --adaptive T [--adaptive-step N] [--adaptive-min M]: adaptive sampling (traceAdaptive), rounds of N (16) samples until
@@ -37,7 +38,7 @@ if (args['pack-only']) { // dump the packed host buffers (used by the packer par
 const spp = num('spp', 16);
 const r = Main({ sceneFile: args.scene, width: args.width ? num('width') : undefined, height: args.height ? num('height') : undefined,
   accel: args.accel || 'bvh2', device: num('device', 0) });
-if ('adaptive' in args && (args.orbit || 'denoise' in args)) { console.error('--adaptive goes with neither --orbit nor --denoise'); process.exit(2); }
+if ('adaptive' in args && args.orbit) { console.error('--adaptive does not go with --orbit'); process.exit(2); }
 if (args.orbit) {
   const n = num('orbit'), base = String(args.out || 'orbit.ppm').replace(/\.ppm$/, ''), outs = [];
   const t1 = process.hrtime.bigint();
@@ -61,10 +62,10 @@ if ('adaptive' in args) {
     for (let tx = 0; tx < ad.tilesX; tx++)
       pixelSamples += ad.counts[ty * ad.tilesX + tx] * Math.min(8, r.width - 8 * tx) * Math.min(8, r.height - 8 * ty);
   const seconds = Number(process.hrtime.bigint() - t1) / 1e9;
-  if (args.out) writePPM(args.out, r.readRgba8(), r.width, r.height);
+  if (args.out) writePPM(args.out, 'denoise' in args ? r.denoiseAdaptive({ iterations: num('denoise') }) : r.readRgba8(), r.width, r.height);
   const mid = counts.length >> 1, median = counts.length % 2 ? counts[mid] : (counts[mid - 1] + counts[mid]) / 2;
   console.log(JSON.stringify({ width: r.width, height: r.height, adaptive: num('adaptive'), rounds, pixel_samples: pixelSamples, seconds,
-    tile_samples: { min: counts[0], median, max: counts[counts.length - 1] } }));
+    tile_samples: { min: counts[0], median, max: counts[counts.length - 1] }, ...('denoise' in args ? { denoise: num('denoise') } : {}) }));
   r.destroy();
   process.exit(0);
 }

@@ -73,6 +73,10 @@ function Main(options = {}) {
     // returns how many tiles that was (0: done).  readAdaptive: {counts, errors, tilesX, tilesY}
     traceAdaptive: (opts = {}) => a.traceAdaptive(device, opts),
     readAdaptive: () => a.readAdaptive(device),
+    // the variance-guided preview filter of an adaptive render (include/crt.h "Denoised preview of an adaptive render"):
+    // rgba8 of the tile, or {rgba8, variance} with opts.variance; reads only.  The Promise form resolves to the rgba8.
+    denoiseAdaptive: (opts = {}) => a.denoiseAdaptive(device, opts),
+    denoiseAdaptiveAsync: (opts = {}) => a.denoiseAdaptiveAsync(device, opts),
     counters: () => a.counters(device),
     enableCounters: (on) => a.enableCounters(device, !!on),
     lastTraceMs: () => a.lastTraceMs(device),

@@ -287,7 +287,8 @@ int crt_debug_hit_pad(crt_ctx *ctx, float *out);
  * or an edit; else CRT_ESTATE).  Every call that zeroes or replaces the accumulator (crt_reset, crt_write_accum,
  * crt_upload_scene, crt_set_tile, crt_set_row_bands, the scene edits) returns to the uniform state; crt_build_accel keeps it.
  * In the adaptive state crt_trace, crt_sample_count, crt_read_latest_rgba8, crt_latest_sample, crt_read_sample_rgba8 and
- * crt_denoise return CRT_ESTATE; crt_read_accum / crt_read_rgba8 / crt_bind_output / counters keep working.
+ * crt_denoise return CRT_ESTATE; crt_read_accum / crt_read_rgba8 / crt_bind_output / counters keep working, and
+ * crt_denoise_adaptive (below) is the preview filter of this state.
  * CRT_ESTATE also under a crt_comm_partition, and without a scene / accel structure or with a stale tree.  CRT_EINVAL (the
  * context unchanged) for samples == 0, a negative or non-finite threshold, or max_samples != 0 && max_samples < min_samples. */
 typedef struct {
@@ -307,6 +308,36 @@ int crt_adaptive_defaults(crt_adaptive_params *out);
  * counts = samples the tile holds, errors = the tile's error E as the NEXT crt_trace_adaptive will judge it.
  * Either pointer may be NULL.  A sync point.  CRT_ESTATE in the uniform state. */
 int crt_read_adaptive(crt_ctx *ctx, uint32_t *counts, float *errors);
+
+/* ------------------------------------------------------------------ Denoised preview of an adaptive render
+ * crt_denoise_adaptive is crt_denoise for the ADAPTIVE state (DESIGN.md 6d defines it): the same a-trous filter, guides
+ * and G-buffer, with each pixel averaged by its tile's count, and with the colour edge-stopping weight scaled by the
+ * pixels' own noise instead of a fixed sigma_color.  The variance v of a pixel is the square of the pixel error of
+ * "Adaptive sampling" (the standard error of its mean luminance times the slope of the exposure curve; v = 1 below 2
+ * samples or where that square is not finite); the colour term of a tap q of pixel p is
+ * |T(c_p) - T(c_q)|^2 / (sigma_variance^2 (v~_p + v~_q) + (0.5/255)^2), v~ a 3x3 blur of v, and v is carried through
+ * the filter (v' = sum w^2 v / (sum w)^2), so a pixel that has converged is left alone and later passes narrow by
+ * themselves.  Below about 8 samples per pixel the variance estimate is itself too noisy and crt_denoise on a uniform
+ * render is a little better (DESIGN.md 6d has the numbers): crt_denoise stays the preview of the first frames.
+ * A sync point like crt_read_rgba8.  It only READS the accumulator, the second moments and the counts: accumulator,
+ * rgba8 framebuffer, counts, errors, counters and the adaptive state stay as they are, and the next crt_trace_adaptive
+ * continues bit for bit.  CRT_ESTATE in the uniform state (crt_denoise filters a uniform render; crt_trace_adaptive with
+ * min_samples == max_samples gives this filter a uniform one), after a crt_trace_adaptive that failed part way, without
+ * a scene or accel structure, with a stale tree, or under a row-band partition.  A crt_set_tile rectangle is filtered
+ * on its own. */
+typedef struct {
+    uint32_t iterations;    /* 0..10, step 2^i in pass i; 0 = the plain per-tile average, as crt_read_rgba8 */
+    float sigma_variance;   /* colour edge-stopping scale in standard errors; > 0 and finite */
+    float sigma_normal;     /* as crt_denoise_params */
+    float sigma_plane;
+} crt_denoise_adaptive_params;
+/* The defaults {5, 8.0, 0.5, 0.3}.  No context and no GPU needed. */
+int crt_denoise_adaptive_defaults(crt_denoise_adaptive_params *out);
+/* NULL params = the defaults.  rgb_out: tw*th*4 floats (linear rgb; channel 3 = the pixel's var_out) or NULL;
+ * rgba8_out: tw*th*4 bytes or NULL; var_out: tw*th floats, the variance left after filtering (display units squared),
+ * or NULL.  CRT_EINVAL (the context unchanged) for iterations > 10 or a sigma that is not positive and finite. */
+int crt_denoise_adaptive(crt_ctx *ctx, const crt_denoise_adaptive_params *params, float *rgb_out, uint8_t *rgba8_out,
+                         float *var_out);
 
 /* Counters accumulate over crt_trace calls while enabled (off by default: the
  * counting kernel variant is slower). */
