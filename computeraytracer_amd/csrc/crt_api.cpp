@@ -37,6 +37,7 @@ hipError_t wf_launch_tea(const WfParams &P, uint32_t *out, hipStream_t s);
 hipError_t wf_launch_shade(const WfParams &P, uint32_t it, hipStream_t s);
 hipError_t wf_launch_gen(const WfParams &P, uint32_t it, hipStream_t s, const AsTiles *A);
 hipError_t wf_launch_trace(const WfParams &P, uint32_t it, uint32_t trace_blocks, hipStream_t s);
+int wf_trace_kernel(const WfParams &P);
 hipError_t wf_launch_finish(const WfParams &P, WfFinishSegs G, uint32_t max_paths, hipStream_t s);
 hipError_t wf_launch_resolve(const WfParams &P, uint32_t last_sample, hipStream_t s);
 hipError_t build_lbvh(const float *lo, const float *hi, uint32_t n, Bvh &out, hipStream_t stream);
@@ -143,6 +144,7 @@ struct crt_ctx {
     Bvh8Q bvh8q;
     int quantize = 1;
     int wf_width = 4;               // node width of the wavefront traversal: 4 (64-byte quantised nodes), or 8 (128-byte; measured slower)
+    uint32_t wf_depth = 0;          // inner levels of the tree the wavefront kernels walk (sizes their stacks' overflow area)
 
     // device scene
     DevBuf<unsigned char> d_raw;    // the scene's 80-byte records as uploaded (input of the all-device LBVH build)
@@ -408,7 +410,7 @@ int build_accel_on_device(crt_ctx *c, bool *done)
     // the host keeps the tree's statistics only
     c->bvh = Bvh(); c->bvh4 = Bvh4(); c->bvh4q = Bvh4Q(); c->bvh8q = Bvh8Q();
     c->bvh.root = 0; c->bvh.n_inner = n - 1; c->bvh.n_leaves = n; c->bvh.max_depth = res.max_depth;
-    c->bvh4.root = 0; c->bvh4.n_inner = res.n_nodes4;
+    c->bvh4.root = 0; c->bvh4.n_inner = res.n_nodes4; c->bvh4.max_depth = res.depth4;
     c->bvh4q.ok = true;
     for (int a = 0; a < 3; a++) { c->bvh4q.base[a] = res.qbase[a]; c->bvh4q.scale[a] = res.qscale[a]; c->sc.qbase[a] = res.qbase[a]; c->sc.qscale[a] = res.qscale[a]; }
     c->accel_builder = 1;
@@ -578,11 +580,43 @@ int upload_geometry(crt_ctx *c, int mode)
     return CRT_OK;
 }
 
+// The stacks of the wavefront walks ("Stack capacity"): a nearest-first walk holds at most
+// (node width - 1) entries per inner level of the walked tree.
+uint32_t wf_stack_need(const crt_ctx *c) { return (c->bvh8q.ok ? 7u : 3u) * c->wf_depth; }
+// LDS stack entries per lane of the kernel wf_launch_trace picks (wf_trace_kernel: k_wf_trace2 for the quantised 4-wide tree under form 2)
+uint32_t wf_stack_lds(const crt_ctx *c) { return (c->wf_trace_form == 2 && c->bvh4q.ok && !c->bvh8q.ok) ? (uint32_t)kWfStackLds2 : (uint32_t)kWfStackLds; }
+uint32_t wf_overflow_levels(const crt_ctx *c)
+{
+    const uint32_t need = wf_stack_need(c), lds = wf_stack_lds(c);
+    return std::max(kWfOverflowLevels, need > lds ? need - lds : 0u);
+}
+
 // upload_geometry plus the scene-edit bookkeeping: a new tree is fresh, its boxes made with the current hit_pad.
+// Also records the depth of the tree the wavefront kernels walk, and builds the SAH tree instead of an LBVH too deep for
+// a reasonable stack overflow area.
 int build_tree(crt_ctx *c, int mode)
 {
     c->rf_ready = false;
-    const int rc = upload_geometry(c, mode);
+    c->wf_depth = 0;
+    int rc = upload_geometry(c, mode);
+    if (rc == CRT_OK && mode == CRT_ACCEL_BVH2) {
+        c->wf_depth = c->bvh8q.ok ? c->bvh8q.max_depth : c->bvh4.max_depth;
+        // ("wf_trace_form" may change after the build: judged with the fewest LDS entries a kernel for this tree has)
+        const uint32_t lds_min = c->bvh4q.ok && !c->bvh8q.ok ? (uint32_t)kWfStackLds2 : (uint32_t)kWfStackLds;
+        if (c->accel_builder == 1 && wf_stack_need(c) > lds_min + kWfOverflowMaxLevels) {
+            // an LBVH this deep would need an unreasonable overflow area: the SAH builder's tree is at most 30 levels deep
+            const uint32_t depth = c->wf_depth, width = c->bvh8q.ok ? 8u : 4u;
+            c->want_lbvh = false; c->accel_mode = -1;
+            rc = upload_geometry(c, mode);
+            c->want_lbvh = true;                                 // (a rebuild by crt_refit_accel tries the LBVH again)
+            if (rc == CRT_OK) {
+                c->wf_depth = c->bvh8q.ok ? c->bvh8q.max_depth : c->bvh4.max_depth;
+                (void)fail(c, CRT_OK, "crt_build_accel: the %u-wide LBVH is %u levels deep (its walk would need %u stack entries per lane, "
+                                      "more than %u + %u); built with the host SAH builder instead (%u levels)",
+                           width, depth, (width - 1u) * depth, lds_min, kWfOverflowMaxLevels, c->wf_depth);
+            }
+        }
+    }
     if (rc == CRT_OK) { c->accel_stale = false; c->tree_pad = c->sc.hit_pad; }
     return rc;
 }
@@ -616,6 +650,20 @@ int build_tree(crt_ctx *c, int mode)
 constexpr int kStatusRing = crt_ctx::kStatusSlots;
 
 uint32_t wf_waves(const crt_ctx *c) { return c->wf_waves_per_cu ? c->wf_waves_per_cu : (c->wf_trace_form == 2 && c->bvh4q.ok && !c->bvh8q.ok) ? 13u : 16u; }
+
+// The deep-stack overflow area: wf_overflow_levels levels beyond the LDS part for every resident traversal lane of every
+// pipe ([pipe][level][lane]; pipe p's part starts at p * lanes per pipe * levels).
+int wf_ensure_overflow(crt_ctx *c)
+{
+    if (c->num_cu == 0) {
+        hipDeviceProp_t prop;
+        HIPCHK(c, hipGetDeviceProperties(&prop, c->device));
+        c->num_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+    }
+    const size_t lanes = (size_t)c->num_cu * wf_waves(c) * 64u * (size_t)std::max(1, c->wf_pipes);
+    if (c->w_overflow.n < lanes * wf_overflow_levels(c)) HIPCHK(c, c->w_overflow.alloc(lanes * wf_overflow_levels(c)));
+    return CRT_OK;
+}
 
 int wf_ensure(crt_ctx *c, size_t P, size_t staging_elems, size_t list_elems, uint32_t ring)
 {
@@ -682,16 +730,7 @@ int wf_ensure(crt_ctx *c, size_t P, size_t staging_elems, size_t list_elems, uin
         }
         c->wf_host_ready = true;
     }
-    if (c->num_cu == 0) {
-        hipDeviceProp_t prop;
-        HIPCHK(c, hipGetDeviceProperties(&prop, c->device));
-        c->num_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    }
-    {   // deep-stack overflow area: kWfOverflowLevels levels beyond the LDS part for every resident traversal lane
-        const size_t lanes = (size_t)c->num_cu * wf_waves(c) * 64u * (size_t)std::max(1, c->wf_pipes);
-        if (c->w_overflow.n < lanes * kWfOverflowLevels) HIPCHK(c, c->w_overflow.alloc(lanes * kWfOverflowLevels));
-    }
-    return CRT_OK;
+    return wf_ensure_overflow(c);
 }
 
 // One shade->trace chain over its share of the pool.
@@ -1564,7 +1603,7 @@ int wf_trace_batch(crt_ctx *c, uint32_t n, const AsBatch *as)
             W.tea = c->w_tea.p;
             W.count = c->counting ? 1u : 0u;
             W.overflow_lanes = (uint32_t)c->num_cu * wf_waves(c) * 64u;
-            W.stack_overflow = c->w_overflow.p + (size_t)p * W.overflow_lanes * kWfOverflowLevels;
+            W.stack_overflow = c->w_overflow.p + (size_t)p * W.overflow_lanes * wf_overflow_levels(c);
             W.trace_form = (uint32_t)c->wf_trace_form;
             if (!c->pipe_stream[p]) {
                 // Streams beyond the hardware queues (4 by default) share one, and two pipes sharing a queue do not
@@ -2539,6 +2578,127 @@ int crt_debug_intersect(crt_ctx *c, const float *rays, size_t n, float *out)
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     din.release(); dout.release();
     if (e != hipSuccess) return fail(c, CRT_EDEVICE, "crt_debug_intersect: %s", hipGetErrorString(e));
+    return CRT_OK;
+}
+
+// Caller-chosen rays through the traversal kernel crt_trace launches: one iteration's ray lists filled by hand (as
+// k_wf_shade / k_wf_gen leave them), one wf_launch_trace with the context's scene, form, waves per CU and overflow
+// area, and P.hit / P.vis read back.  The lists, the control block and the result arrays are the call's own.
+int crt_debug_trace_rays(crt_ctx *c, const float *rays, size_t n, uint32_t *out, uint64_t report[8])
+{
+    if (!c || (!rays && n) || (!out && n)) return CRT_EINVAL;
+    if (!c->have_scene || c->accel_mode < 0) return fail(c, CRT_ESTATE, "crt_debug_trace_rays: scene + accel required");
+    if (c->accel_stale) return fail(c, CRT_ESTATE, "crt_debug_trace_rays: primitives were updated: call crt_refit_accel or crt_build_accel first");
+    if (c->accel_mode != CRT_ACCEL_BVH2 || c->pipeline != 1)
+        return fail(c, CRT_ESTATE, "crt_debug_trace_rays: no wavefront tree (CRT_ACCEL_NONE or option pipeline = 0)");
+    if (n > (size_t)kWfListSlot) return fail(c, CRT_EINVAL, "crt_debug_trace_rays: too many rays");
+    const uint32_t nprim = (uint32_t)c->prims.size();
+    // ray i goes to shard kShardOf[i % 16] (a quarter of the shards: the waves that start on an empty one scan, the
+    // listed ones hold several chunks) and, by (i / 16) & 1, to the first or the second list of its kind
+    static const uint8_t kShardOf[16] = {0, 1, 2, 3, 5, 8, 13, 21, 34, 55, 63, 62, 31, 32, 33, 7};
+    std::vector<uint32_t> cnt((size_t)kWfShards * 4, 0u), pos(n);
+    for (size_t i = 0; i < n; i++) {
+        const float *r = rays + 12 * i;
+        uint32_t u[4];
+        std::memcpy(u, r + 6, 16);                               // exclude, kind, t_light, light index
+        for (int k = 0; k < 6; k++)
+            if (!std::isfinite(r[k])) return fail(c, CRT_EINVAL, "crt_debug_trace_rays: ray %zu is not finite (crt_trace resolves such rays without a walk)", i);
+        if (u[1] > 1u) return fail(c, CRT_EINVAL, "crt_debug_trace_rays: ray %zu: kind must be 0 (extension) or 1 (shadow)", i);
+        if (u[1] == 1u && (!std::isfinite(r[8]) || u[3] >= nprim))
+            return fail(c, CRT_EINVAL, "crt_debug_trace_rays: shadow ray %zu: t_light must be finite and the light index below %u", i, nprim);
+        const uint32_t cls = (u[1] ? 2u : 0u) + (uint32_t)((i / 16) & 1u);
+        pos[i] = cnt[(size_t)kShardOf[i % 16] * 4 + cls]++;
+    }
+    uint32_t list_cap = 64;
+    for (uint32_t v : cnt) list_cap = std::max(list_cap, (v + 63u) & ~63u);
+    HIPCHK(c, hipSetDevice(c->device));
+    { int rc_ = wf_flush(c); if (rc_) return rc_; }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    { int rc_ = wf_ensure_overflow(c); if (rc_) return rc_; }
+
+    WfParams W{};
+    W.sc = c->sc;
+    W.list_cap = list_cap;
+    W.count = c->counting ? 1u : 0u;
+    W.trace_form = (uint32_t)c->wf_trace_form;
+    W.overflow_lanes = (uint32_t)c->num_cu * wf_waves(c) * 64u;
+    W.stack_overflow = c->w_overflow.p;                          // pipe 0's part
+    const int kernel = wf_trace_kernel(W);
+    if (report) {
+        report[0] = kernel == 2 ? 8 : 4;                          // node width of the walked tree
+        report[1] = c->wf_depth;                                 // its inner levels
+        report[2] = wf_stack_lds(c);                             // stack entries per lane in LDS
+        report[3] = wf_overflow_levels(c);                       // ... and in the overflow area
+        report[4] = report[2] + report[3];                       // capacity per lane
+        report[5] = 0;                                           // deepest stack a lane reached (counting variant)
+        report[6] = (uint64_t)kernel;
+        report[7] = W.count;
+    }
+    if (n == 0) return CRT_OK;
+
+    const size_t cls_stride = (size_t)list_cap * kWfShards;
+    std::vector<float4> hA(4 * cls_stride, float4{0, 0, 0, 0}), hB(4 * cls_stride, float4{0, 0, 0, 0});
+    std::vector<uint4> hC(4 * cls_stride, uint4{0, 0, 0, 0});
+    std::vector<uint32_t> slot_of(std::max<uint32_t>(nprim, 1u)), index_of(std::max<uint32_t>(nprim, 1u));
+    if (nprim) HIPCHK(c, hipMemcpy(slot_of.data(), c->d_slot_of_index.p, (size_t)nprim * 4, hipMemcpyDeviceToHost));
+    for (uint32_t i = 0; i < nprim; i++) {
+        if (slot_of[i] >= nprim) return fail(c, CRT_EDEVICE, "crt_debug_trace_rays: slot_of_index[%u] = %u", i, slot_of[i]);
+        index_of[slot_of[i]] = i;
+    }
+    for (size_t i = 0; i < n; i++) {
+        const float *r = rays + 12 * i;
+        uint32_t u[4];
+        std::memcpy(u, r + 6, 16);
+        const uint32_t cls = (u[1] ? 2u : 0u) + (uint32_t)((i / 16) & 1u);
+        const size_t g = (size_t)cls * cls_stride + (size_t)kShardOf[i % 16] * list_cap + pos[i];
+        hA[g] = float4{r[0], r[1], r[2], bits_f(u[0])};
+        if (u[1]) {
+            hB[g] = float4{r[3], r[4], r[5], r[8]};
+            hC[g] = uint4{(uint32_t)i, u[3], slot_of[u[3]], 0u};
+        } else {
+            hB[g] = float4{r[3], r[4], r[5], bits_f((uint32_t)i)};
+        }
+    }
+    std::vector<WfCtl> hctl(1);
+    std::memset(hctl.data(), 0, sizeof(WfCtl));
+    for (uint32_t sh = 0; sh < kWfShards; sh++)
+        for (int k = 0; k < 4; k++) hctl[0].shard[0][sh].n[k] = cnt[(size_t)sh * 4 + k];
+
+    ScopedBuf<float4> dA, dB;
+    ScopedBuf<uint4> dC;
+    ScopedBuf<WfCtl> dctl;
+    ScopedBuf<float2> dhit;
+    ScopedBuf<uint32_t> dvis;
+    HIPCHK(c, dA.alloc(hA.size())); HIPCHK(c, dB.alloc(hB.size())); HIPCHK(c, dC.alloc(hC.size()));
+    HIPCHK(c, dctl.alloc(1)); HIPCHK(c, dhit.alloc(n)); HIPCHK(c, dvis.alloc(n));
+    HIPCHK(c, hipMemcpyAsync(dA.p, hA.data(), hA.size() * sizeof(float4), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(dB.p, hB.data(), hB.size() * sizeof(float4), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(dC.p, hC.data(), hC.size() * sizeof(uint4), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(dctl.p, hctl.data(), sizeof(WfCtl), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemsetAsync(dhit.p, 0xEE, n * sizeof(float2), c->stream));     // "never written": no slot, no visibility bit
+    HIPCHK(c, hipMemsetAsync(dvis.p, 0xEE, n * sizeof(uint32_t), c->stream));
+    W.recA = dA.p; W.recB = dB.p; W.recC = dC.p; W.ctl = dctl.p; W.hit = dhit.p; W.vis = dvis.p;
+    HIPCHK(c, wf_launch_trace(W, 0u, (uint32_t)c->num_cu * wf_waves(c), c->stream));   // iteration 0: list parity 0, shard ring 0
+    std::vector<float2> hhit(n);
+    std::vector<uint32_t> hvis(n);
+    HIPCHK(c, hipMemcpyAsync(hhit.data(), dhit.p, n * sizeof(float2), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(hvis.data(), dvis.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    if (W.count) HIPCHK(c, hipMemcpyAsync(hctl[0].max_sp, dctl.p->max_sp, sizeof hctl[0].max_sp, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (report && W.count)
+        for (uint32_t sh = 0; sh < kWfShards; sh++) report[5] = std::max<uint64_t>(report[5], hctl[0].max_sp[sh]);
+    for (size_t i = 0; i < n; i++) {
+        uint32_t kind;
+        std::memcpy(&kind, rays + 12 * i + 7, 4);
+        if (kind) {
+            if (hvis[i] > 1u) return fail(c, CRT_EDEVICE, "crt_debug_trace_rays: shadow ray %zu was not resolved (vis = 0x%08x)", i, hvis[i]);
+            out[2 * i] = hvis[i]; out[2 * i + 1] = 0u;
+        } else {
+            const uint32_t slot = f_bits(hhit[i].y);
+            if (slot != kNoHit && slot >= nprim) return fail(c, CRT_EDEVICE, "crt_debug_trace_rays: ray %zu was not resolved (slot = 0x%08x)", i, slot);
+            out[2 * i] = f_bits(hhit[i].x); out[2 * i + 1] = slot == kNoHit ? kNoHit : index_of[slot];
+        }
+    }
     return CRT_OK;
 }
 

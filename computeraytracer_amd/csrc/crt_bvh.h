@@ -72,6 +72,7 @@ void build_bvh8q(const Bvh &b2, Bvh8Q &out);
 struct LbvhDeviceResult {
     uint32_t n_nodes4 = 0;         // 4-wide nodes written (breadth-first numbering, root = 0)
     uint32_t max_depth = 0;        // of the BVH2
+    uint32_t depth4 = 0;           // inner levels of the 4-wide tree (the levels of the collapse loop)
     float qbase[3] = {0, 0, 0}, qscale[3] = {1, 1, 1};
     bool quantised = false;        // false: the scene cannot be quantised (quantize_bvh4's rules); use the host path
 };

@@ -119,7 +119,12 @@ constexpr uint32_t kWfRing = 32;                                // batch ids cyc
 // their end on another stream.  Side-pool slots precede the pool in the same arrays:
 // [(id*pipes + pipe)*kWfSideCap, +kWfSideCap).
 constexpr uint32_t kWfSideCap = 65536;
-constexpr uint32_t kWfOverflowLevels = 96;                   // global stack levels per traversal lane beyond the LDS entries
+// Traversal stacks: kWfStackLds (k_wf_trace) / kWfStackLds2 (k_wf_trace2) entries per lane in LDS, the rest in a global
+// overflow area of at least kWfOverflowLevels levels.  A nearest-first walk holds at most (node width - 1) entries per
+// inner level of the walked tree; crt_api.cpp sizes the area from that depth (wf_overflow_levels) and, where that would
+// take more than kWfOverflowMaxLevels, builds the shallower tree instead.  The pushes themselves are unchecked.
+constexpr int kWfStackLds = 32, kWfStackLds2 = 16;
+constexpr uint32_t kWfOverflowLevels = 96, kWfOverflowMaxLevels = 384;
 
 // Every queue counter is sharded kWfShards ways, one 128-byte line per shard: same-address
 // returning atomics serialize at ~11 ns each on gfx950, which at one atomic per wave would
@@ -138,6 +143,7 @@ struct WfCtl {                       // device control block, one per context
     uint32_t side_count[kWfRing];    // paths moved to the side pool, per batch id
     uint32_t dropped;                // paths a capacity guard had to leave behind (side pool full, bounce guard of
                                      // k_wf_finish): must stay 0 -- the host turns anything else into CRT_EDEVICE
+    uint32_t max_sp[kWfShards];      // counting traversal kernels only: the deepest stack (entries) a lane of the shard's waves reached
 };
 // The work queue is shared by the pipes of a context (two half-pools run on two streams so that
 // one half's streaming shade pass overlaps the other half's latency-bound traversal).  There are kWfRing
@@ -227,7 +233,7 @@ struct WfParams {
     const uint32_t *tea;             // per tile pixel: tea(px, py*100), the 16-round seed of the pixel's RNG (:98), computed once
     uint32_t count;                  // 1: maintain ctl->counters
     uint32_t trace_form;             // 2: k_wf_trace2 (ray ring + primitive tasks) where the tree is the quantised 4-wide one; else k_wf_trace
-    int *stack_overflow;             // [level - LDS entries][global lane], for stacks deeper than the LDS part (kWfOverflowLevels levels)
+    int *stack_overflow;             // [level - LDS entries][global lane], for stacks deeper than the LDS part (wf_overflow_levels levels)
     uint32_t overflow_lanes;
 };
 

@@ -439,6 +439,7 @@ hipError_t build_lbvh_device(const unsigned char *d_raw, uint32_t n, float hit_p
         level_base += count;
         count = next;
         cur ^= 1;
+        res.depth4 = (uint32_t)level + 1u;
     }
 #undef LB
     res.n_nodes4 = level_base;

@@ -62,7 +62,8 @@ namespace crt {
 #ifndef CRT_WF_MIN_WAVES
 #define CRT_WF_MIN_WAVES 1
 #endif
-constexpr int kWfStack = CRT_WF_STACK;      // LDS stack entries per lane (BVH depth is capped by the builder)
+constexpr int kWfStack = CRT_WF_STACK;      // LDS stack entries per lane; deeper stacks go on in P.stack_overflow (crt_device.h)
+static_assert(kWfStack == kWfStackLds, "crt_api.cpp sizes the overflow area from kWfStackLds");
 constexpr int kNoNode = 0x7FFFFFFF;          // "no node left to walk" (inner ids are smaller, leaf references negative)
 constexpr int kTraceChunk = 128;            // list entries a wave reserves per atomic
 constexpr int kRefillAt = CRT_WF_REFILL;    // refill when at least this many lanes are idle
@@ -996,6 +997,7 @@ __global__ __launch_bounds__(64, CRT_WF_MIN_WAVES) void k_wf_trace(const WfParam
     int nx = 0, ny = 0, nz = 0;                      // 0: lo plane is the near one on that axis, 3: hi plane
     uint32_t c_nodes = 0, c_prims = 0;
     uint32_t d_inner_it = 0, d_inner_act = 0, d_leaf_it = 0, d_leaf_act = 0, d_prim_it = 0, d_refill = 0, d_refill_lanes = 0, d_scans = 0;   // lane 0 only
+    uint32_t d_max_sp = 0;                           // COUNT: the deepest stack this lane reached
 
     for (;;) {
         // ---- refill idle lanes from the wave's chunk
@@ -1165,6 +1167,7 @@ __global__ __launch_bounds__(64, CRT_WF_MIN_WAVES) void k_wf_trace(const WfParam
                     if (k0 < 3.0e38f) {
                         // descend into the nearest; the others wait on the stack, farthest pushed first
                         CRT_PUSH(k7, r7) CRT_PUSH(k6, r6) CRT_PUSH(k5, r5) CRT_PUSH(k4, r4) CRT_PUSH(k3, r3) CRT_PUSH(k2, r2) CRT_PUSH(k1, r1)
+                        if (COUNT) d_max_sp = max(d_max_sp, (uint32_t)sp);
                         node = r0;
                     } else if (sp > 0) {
                         sp--; node = stack_pop(stk, ovf, ovl, sp);
@@ -1236,6 +1239,7 @@ __global__ __launch_bounds__(64, CRT_WF_MIN_WAVES) void k_wf_trace(const WfParam
                         if (k3 < 3.0e38f) { if (sp < kWfStack) stk[sp * 64] = r3; else ovf[(size_t)(sp - kWfStack) * ovl] = r3; sp++; }
                         if (k2 < 3.0e38f) { if (sp < kWfStack) stk[sp * 64] = r2; else ovf[(size_t)(sp - kWfStack) * ovl] = r2; sp++; }
                         if (k1 < 3.0e38f) { if (sp < kWfStack) stk[sp * 64] = r1; else ovf[(size_t)(sp - kWfStack) * ovl] = r1; sp++; }
+                        if (COUNT) d_max_sp = max(d_max_sp, (uint32_t)sp);
                         node = r0;
                     } else if (sp > 0) {
                         sp--; node = stack_pop(stk, ovf, ovl, sp);
@@ -1299,6 +1303,8 @@ __global__ __launch_bounds__(64, CRT_WF_MIN_WAVES) void k_wf_trace(const WfParam
             atomicAdd(ctl->counters[blockIdx.x % kWfShards] + 12, (unsigned long long)d_prim_it); atomicAdd(ctl->counters[blockIdx.x % kWfShards] + 13, (unsigned long long)d_scans); atomicAdd(ctl->counters[blockIdx.x % kWfShards] + 14, (unsigned long long)d_refill);
             atomicAdd(ctl->counters[blockIdx.x % kWfShards] + 15, (unsigned long long)d_refill_lanes);
         }
+        for (int off = 32; off > 0; off >>= 1) d_max_sp = max(d_max_sp, (uint32_t)__shfl_xor((int)d_max_sp, off, 64));
+        if (lane == 0) atomicMax(&ctl->max_sp[blockIdx.x % kWfShards], d_max_sp);
     }
 }
 
@@ -1328,7 +1334,7 @@ __global__ __launch_bounds__(64, CRT_WF_MIN_WAVES) void k_wf_trace(const WfParam
 #ifndef CRT_WF_STALL_AT
 #define CRT_WF_STALL_AT 16
 #endif
-constexpr int kStk2 = 16;
+constexpr int kStk2 = kWfStackLds2;
 #ifndef CRT_WF_RING
 #define CRT_WF_RING 32
 #endif
@@ -1408,6 +1414,7 @@ __global__ __launch_bounds__(64, CRT_WF_T2_WAVES) void k_wf_trace2(const WfParam
     bool gx = false, gy = false, gz = false;         // the hi plane is the near one on that axis
     uint32_t c_nodes = 0, c_prims = 0;
     uint32_t d_inner_it = 0, d_inner_act = 0, d_leaf_it = 0, d_leaf_act = 0, d_prim_it = 0, d_refill = 0, d_refill_lanes = 0, d_scans = 0;   // lane 0 only
+    uint32_t d_max_sp = 0;                           // COUNT: the deepest stack this lane reached
 
     for (;;) {
         // ---- idle lanes pick ready rays up from the ring; an empty ring is refilled with the next chunk first
@@ -1673,6 +1680,7 @@ __global__ __launch_bounds__(64, CRT_WF_T2_WAVES) void k_wf_trace2(const WfParam
                         if (k3 < 3.0e38f) { if (sp < kStk2) stk[sp * 64] = r3; else ovf[(size_t)(sp - kStk2) * ovl] = r3; sp++; }
                         if (k2 < 3.0e38f) { if (sp < kStk2) stk[sp * 64] = r2; else ovf[(size_t)(sp - kStk2) * ovl] = r2; sp++; }
                         if (k1 < 3.0e38f) { if (sp < kStk2) stk[sp * 64] = r1; else ovf[(size_t)(sp - kStk2) * ovl] = r1; sp++; }
+                        if (COUNT) d_max_sp = max(d_max_sp, (uint32_t)sp);
                         node = r0;
                     } else if (sp > 0) {
                         sp--; node = stack_pop2(stk, ovf, ovl, sp);
@@ -1697,6 +1705,8 @@ __global__ __launch_bounds__(64, CRT_WF_T2_WAVES) void k_wf_trace2(const WfParam
             atomicAdd(ctl->counters[blockIdx.x % kWfShards] + 12, (unsigned long long)d_prim_it); atomicAdd(ctl->counters[blockIdx.x % kWfShards] + 13, (unsigned long long)d_scans); atomicAdd(ctl->counters[blockIdx.x % kWfShards] + 14, (unsigned long long)d_refill);
             atomicAdd(ctl->counters[blockIdx.x % kWfShards] + 15, (unsigned long long)d_refill_lanes);
         }
+        for (int off = 32; off > 0; off >>= 1) d_max_sp = max(d_max_sp, (uint32_t)__shfl_xor((int)d_max_sp, off, 64));
+        if (lane == 0) atomicMax(&ctl->max_sp[blockIdx.x % kWfShards], d_max_sp);
     }
 }
 
@@ -1903,11 +1913,19 @@ hipError_t wf_launch_gen(const WfParams &P, uint32_t it, hipStream_t s, const As
     return hipGetLastError();
 }
 
+// Which traversal kernel wf_launch_trace launches for these parameters: 0, 1, 2 = k_wf_trace<*, QUANT> (plain 4-wide,
+// quantised 4-wide, quantised 8-wide), 3 = k_wf_trace2 (the regrouped form: quantised 4-wide tree only).
+int wf_trace_kernel(const WfParams &P)
+{
+    const int q = !CRT_WF_BVH4 ? 0 : P.sc.nodes8q != nullptr ? 2 : P.sc.nodes4q != nullptr ? 1 : 0;
+    return q == 1 && P.trace_form == 2u ? 3 : q;
+}
+
 hipError_t wf_launch_trace(const WfParams &P, uint32_t it, uint32_t trace_blocks, hipStream_t s)
 {
     const dim3 g(trace_blocks), b(64);
-    const int q = !CRT_WF_BVH4 ? 0 : P.sc.nodes8q != nullptr ? 2 : P.sc.nodes4q != nullptr ? 1 : 0;
-    if (q == 1 && P.trace_form == 2u) {                          // the regrouped form (quantised 4-wide tree only)
+    const int kernel = wf_trace_kernel(P), q = kernel == 3 ? 1 : kernel;
+    if (kernel == 3) {
         if (P.count) hipLaunchKernelGGL((k_wf_trace2<true>), g, b, 0, s, P, it);
         else hipLaunchKernelGGL((k_wf_trace2<false>), g, b, 0, s, P, it);
         return hipGetLastError();

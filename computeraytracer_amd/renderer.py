@@ -382,6 +382,34 @@ class Renderer:
         self._chk(self._lib.crt_debug_intersect(self._h, rays.ctypes.data, n, out.ctypes.data))
         return out
 
+    TRACE_KERNELS = ("k_wf_trace<,0>", "k_wf_trace<,1>", "k_wf_trace<,2>", "k_wf_trace2")
+
+    def debug_trace_rays(self, origins, directions, exclude=None, shadow=None, t_light=None, light=None):
+        """Rays through the traversal kernel frame() launches for the current tree and options (crt_debug_trace_rays).
+        shadow: bool mask of the shadow rays, which take t_light / light (the light primitive's own t and index).
+        Returns (t float32 (n,), index uint32 (n,) -- 0xFFFFFFFF = miss --, visible uint32 (n,), report dict); t and
+        index hold zeros / the visibility bit at shadow rays, visible is 0 at extension rays."""
+        o = np.asarray(origins, np.float32).reshape(-1, 3)
+        d = np.asarray(directions, np.float32).reshape(-1, 3)
+        n = o.shape[0]
+        rays = np.zeros((n, 12), np.float32)
+        rays[:, 0:3] = o
+        rays[:, 3:6] = d
+        ru = rays.view(np.uint32)
+        ru[:, 6] = 0xFFFFFFFF if exclude is None else np.asarray(exclude, np.uint32)
+        sh = np.zeros(n, bool) if shadow is None else np.asarray(shadow, bool)
+        if sh.any():
+            ru[:, 7] = sh
+            rays[sh, 8] = np.asarray(t_light, np.float32)[sh]
+            ru[sh, 9] = np.asarray(light, np.uint32)[sh]
+        out = np.zeros((n, 2), np.uint32)
+        rep = np.zeros(8, np.uint64)
+        self._chk(self._lib.crt_debug_trace_rays(self._h, rays.ctypes.data, n, out.ctypes.data, rep.ctypes.data))
+        report = dict(width=int(rep[0]), depth=int(rep[1]), lds_entries=int(rep[2]), overflow_levels=int(rep[3]),
+                      capacity=int(rep[4]), deepest=int(rep[5]), kernel=self.TRACE_KERNELS[int(rep[6])], counting=bool(rep[7]))
+        t = np.where(sh, np.uint32(0), out[:, 0]).astype(np.uint32).view(np.float32)
+        return t, np.where(sh, np.uint32(0), out[:, 1]).astype(np.uint32), np.where(sh, out[:, 0], np.uint32(0)).astype(np.uint32), report
+
     def debug_probes(self) -> list:
         out = np.zeros(8, np.uint64)
         self._chk(self._lib.crt_debug_probes(self._h, out.ctypes.data))

@@ -377,12 +377,30 @@ int crt_set_option(crt_ctx *ctx, const char *name, int64_t value);
  * [7]=builder (0: host binned SAH, 1: GPU LBVH). */
 int crt_accel_stats(crt_ctx *ctx, uint64_t out[8]);
 
-/* Test hooks: one closest-hit query per ray through the product's traversal
- * (rays: n x 8 floats ox,oy,oz,dx,dy,dz,exclude_as_u32_bits,_;  out: n x 8:
- * t, px,py,pz, nx,ny,nz, index_bits (0xFFFFFFFF = miss)); and elementwise
- * evaluation of the device math (fn codes: 0 sin 1 cos 2 exp 3 log2 4 exp2
+/* Test hooks: one closest-hit query per ray (rays: n x 8 floats ox,oy,oz,dx,dy,dz,exclude_as_u32_bits,_;  out: n x 8:
+ * t, px,py,pz, nx,ny,nz, index_bits (0xFFFFFFFF = miss)) through the SINGLE-RAY walk: of the BVH2 under
+ * CRT_ACCEL_BVH2 / LBVH (the walk of the "pipeline" = 0 form, of k_wf_finish and of the denoise G-buffer -- not the
+ * wide tree the wavefront kernels of crt_trace walk: crt_debug_trace_rays), the reference's loop over every primitive
+ * under CRT_ACCEL_NONE; and elementwise evaluation of the device math (fn codes: 0 sin 1 cos 2 exp 3 log2 4 exp2
  * 5 pow 6 sqrt 7 div 8 tan). */
 int crt_debug_intersect(crt_ctx *ctx, const float *rays, size_t n, float *out);
+/* Test hook: n rays through the traversal kernel crt_trace launches for the context's current tree and options (the
+ * same instantiation: node width, quantisation, "wf_trace_form", the counting variant under crt_enable_counters; the
+ * context's waves per CU and stack overflow area).  The rays are laid out as one iteration's ray lists -- spread over
+ * several shards and all four list classes -- so chunking, the shard scan and the refill run as in production.
+ *   rays: n x 12 floats  ox,oy,oz, dx,dy,dz, exclude_as_u32_bits, kind_as_u32_bits (0 extension ray, 1 shadow ray),
+ *                        t_light, light_index_as_u32_bits, _, _      (the last four: shadow rays only -- the t of the
+ *                        light's own primitive along the ray and that primitive's index, as the shade kernel primes them)
+ *   out:  n x 2 uint32   extension ray: t bits, primitive index (0xFFFFFFFF = miss);  shadow ray: 1 = light visible / 0, 0
+ *   report (may be NULL): [0] node width of the walked tree (4 | 8), [1] its inner levels, [2] stack entries per lane in
+ *                        LDS, [3] levels of the overflow area, [4] capacity per lane = [2] + [3], [5] deepest stack a
+ *                        lane reached (counting variant, else 0), [6] kernel: 0, 1, 2 = k_wf_trace on the plain 4-wide /
+ *                        quantised 4-wide / quantised 8-wide tree, 3 = k_wf_trace2, [7] 1 = counting variant
+ * A walk holds at most (width - 1) x levels entries; crt_build_accel sizes the overflow area so that [4] covers it.
+ * A sync point.  CRT_EINVAL for a non-finite ray (crt_trace never lets one walk) or a bad kind / light; CRT_ESTATE
+ * without a scene or tree, with a stale tree, and where there is no wavefront tree (CRT_ACCEL_NONE, "pipeline" = 0).
+ * The counters of crt_counters are not touched. */
+int crt_debug_trace_rays(crt_ctx *ctx, const float *rays, size_t n, uint32_t *out, uint64_t report[8]);
 int crt_debug_math(crt_ctx *ctx, int fn, const float *a, const float *b, float *out, size_t n);
 /* Traversal-efficiency probes of the counting kernel variant (wave-level): inner iterations,
  * lanes active in them, leaf passes, lanes active in them, leaf loop trips, -, refills, lanes refilled. */

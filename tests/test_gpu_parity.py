@@ -553,7 +553,9 @@ def test_gpu_lbvh_build_gives_the_same_image(renderer, orc):
     """crt_build_accel(CRT_ACCEL_LBVH): the BVH2 is built on the GPU (Morton order, Karras hierarchy).  The
     closest hit does not depend on the tree, so the image is the SAH build's bit for bit: on the mixed scene
     (patches, spheres, glass, triangles), on the 250k-triangle frame (crops), in every
-    pipeline form and ray by ray; and the tree is a proper BVH over all primitives."""
+    pipeline form and ray by ray -- through the single-ray walk of the BVH2 (debug_intersect) and through the
+    wavefront kernel's walk of the 4-wide tree (debug_trace_rays); the tree has a leaf per primitive and n - 1 inner
+    nodes (its boxes are judged by the rays only: test_traversal_rays_gpu.py)."""
     from computeraytracer_amd.scenes_synth import atrium250k
     ps = _mixed_scene(640, 360)
     a_sah, r_sah = render(renderer, ps, 4, "bvh2")
@@ -587,9 +589,13 @@ def test_gpu_lbvh_build_gives_the_same_image(renderer, orc):
     d = rng.normal(size=(20000, 3)).astype(np.float32)
     renderer.upload(big).build_accel("lbvh")
     h_lb = renderer.debug_intersect(o, d)
+    t_wf, i_wf, _, rep = renderer.debug_trace_rays(o, d)
     renderer.build_accel("none")
     h_ref = renderer.debug_intersect(o, d)
     assert np.array_equal(bits(h_lb), bits(h_ref))
+    i_ref = h_ref[:, 7].view(np.uint32)
+    assert rep["kernel"] == "k_wf_trace2" and 3 * rep["depth"] <= rep["capacity"]
+    assert np.array_equal(i_wf, i_ref) and np.array_equal(bits(t_wf), bits(h_ref[:, 0]))
 
 
 def test_one_sample_per_pixel_and_tiny_tiles(renderer, orc):
