@@ -575,6 +575,105 @@ static napi_value js_denoise_adaptive(napi_env env, napi_callback_info info)
     return obj;
 }
 
+/* setSampleOffset(h, offset), sampleOffset(h) -> number, temporalReset(h): include/crt.h "Sample offset" and "Temporal
+ * reuse across camera moves".
+ * denoiseTemporal(h, {iterations, sigmaColor, sigmaNormal, sigmaPlane, maxHistory, normalTol, planeTol, history}) ->
+ * Uint8Array (tw*th*4 rgba8), or with history: true -> {rgba8, history: Float32Array(tw*th)} (the weight Hw in samples).
+ * A missing option takes the library's default (crt_denoise_temporal_defaults).  denoiseTemporalAsync(h, {...}) ->
+ * Promise of the Uint8Array (below). */
+static napi_value js_set_sample_offset(napi_env env, napi_callback_info info)
+{
+    ARGS(2)
+    crt_ctx *ctx = get_ctx(env, argv[0]);
+    if (!ctx) return NULL;
+    uint32_t n;
+    NAPI_OK(env, napi_get_value_uint32(env, argv[1], &n));
+    CRT_CHECK(env, ctx, "crt_set_sample_offset", crt_set_sample_offset(ctx, n));
+    return undefined(env);
+}
+
+static napi_value js_sample_offset(napi_env env, napi_callback_info info)
+{
+    ARGS(1)
+    crt_ctx *ctx = get_ctx(env, argv[0]);
+    if (!ctx) return NULL;
+    uint32_t s = 0;
+    CRT_CHECK(env, ctx, "crt_sample_offset", crt_sample_offset(ctx, &s));
+    napi_value out;
+    NAPI_OK(env, napi_create_uint32(env, s, &out));
+    return out;
+}
+
+static napi_value js_temporal_reset(napi_env env, napi_callback_info info)
+{
+    ARGS(1)
+    crt_ctx *ctx = get_ctx(env, argv[0]);
+    if (!ctx) return NULL;
+    CRT_CHECK(env, ctx, "crt_denoise_temporal_reset", crt_denoise_temporal_reset(ctx));
+    return undefined(env);
+}
+
+static int denoise_temporal_options(napi_env env, napi_value opts, int have_opts, crt_denoise_temporal_params *p, bool *history)
+{
+    double it, v[6];
+    static const char *names[6] = {"sigmaColor", "sigmaNormal", "sigmaPlane", "maxHistory", "normalTol", "planeTol"};
+    napi_valuetype t = napi_undefined;
+    if (crt_denoise_temporal_defaults(p) != CRT_OK) { napi_throw_error(env, NULL, "crt_denoise_temporal_defaults failed"); return 0; }
+    it = p->iterations;
+    v[0] = p->sigma_color; v[1] = p->sigma_normal; v[2] = p->sigma_plane; v[3] = p->max_history; v[4] = p->normal_tol; v[5] = p->plane_tol;
+    if (history) *history = false;
+    if (have_opts && napi_typeof(env, opts, &t) != napi_ok) { napi_throw_type_error(env, NULL, "denoiseTemporal: options object expected"); return 0; }
+    if (t == napi_object) {
+        int ok = opt_number(env, opts, "iterations", &it);
+        for (int k = 0; k < 6 && ok; k++) ok = opt_number(env, opts, names[k], &v[k]);
+        if (!ok) { napi_throw_type_error(env, NULL, "denoiseTemporal: options must be numbers"); return 0; }
+        bool has = false;
+        napi_value hv;
+        if (history && napi_has_named_property(env, opts, "history", &has) == napi_ok && has &&
+            napi_get_named_property(env, opts, "history", &hv) == napi_ok)
+            napi_coerce_to_bool(env, hv, &hv), napi_get_value_bool(env, hv, history);
+    } else if (t != napi_undefined && t != napi_null) {
+        napi_throw_type_error(env, NULL, "denoiseTemporal: options object expected");
+        return 0;
+    }
+    if (!(it >= 0.0 && it <= 4294967295.0) || it != (double)(uint32_t)it) {
+        napi_throw_range_error(env, NULL, "denoiseTemporal: iterations must be a non-negative integer");
+        return 0;
+    }
+    p->iterations = (uint32_t)it;
+    p->sigma_color = (float)v[0]; p->sigma_normal = (float)v[1]; p->sigma_plane = (float)v[2];
+    p->max_history = (float)v[3]; p->normal_tol = (float)v[4]; p->plane_tol = (float)v[5];
+    return 1;
+}
+
+static napi_value js_denoise_temporal(napi_env env, napi_callback_info info)
+{
+    size_t argc = 2;
+    napi_value argv[2];
+    NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    if (argc < 1) { napi_throw_type_error(env, NULL, "too few arguments"); return NULL; }
+    crt_ctx *ctx = get_ctx(env, argv[0]);
+    if (!ctx) return NULL;
+    crt_denoise_temporal_params p;
+    bool history = false;
+    if (!denoise_temporal_options(env, argc > 1 ? argv[1] : NULL, argc > 1, &p, &history)) return NULL;
+    uint32_t tl[4];
+    CRT_CHECK(env, ctx, "crt_tile", crt_tile(ctx, tl));
+    size_t px = (size_t)tl[2] * tl[3];
+    void *data = NULL, *hdata = NULL;
+    napi_value ab, ta, hab, hta, obj;
+    NAPI_OK(env, napi_create_arraybuffer(env, px * 4, &data, &ab));
+    if (history) NAPI_OK(env, napi_create_arraybuffer(env, px * 4, &hdata, &hab));
+    CRT_CHECK(env, ctx, "crt_denoise_temporal", crt_denoise_temporal(ctx, &p, NULL, (uint8_t *)data, (float *)hdata));
+    NAPI_OK(env, napi_create_typedarray(env, napi_uint8_array, px * 4, ab, 0, &ta));
+    if (!history) return ta;
+    NAPI_OK(env, napi_create_typedarray(env, napi_float32_array, px, hab, 0, &hta));
+    NAPI_OK(env, napi_create_object(env, &obj));
+    NAPI_OK(env, napi_set_named_property(env, obj, "rgba8", ta));
+    NAPI_OK(env, napi_set_named_property(env, obj, "history", hta));
+    return obj;
+}
+
 static napi_value js_read_gbuffer(napi_env env, napi_callback_info info)
 {
     ARGS(1)
@@ -900,7 +999,7 @@ static napi_value js_set_stream(napi_env env, napi_callback_info info)
  * fire-and-forget (queue.submit, src/main.js:618-620): a Node display loop must not block its event loop on the
  * GPU either.  Jobs of one context run in call order. */
 enum { JOB_TRACE, JOB_SYNC, JOB_READ_RGBA8, JOB_READ_ACCUM, JOB_GATHER, JOB_READ_FRAME_RGBA8, JOB_READ_FRAME_ACCUM, JOB_READ_SAMPLE_RGBA8,
-       JOB_DENOISE_ADAPTIVE };
+       JOB_DENOISE_ADAPTIVE, JOB_DENOISE_TEMPORAL };
 typedef struct job {
     napi_async_work work;
     napi_deferred deferred;
@@ -908,6 +1007,7 @@ typedef struct job {
     int op, rc;
     uint32_t n, px;
     crt_denoise_adaptive_params dn;     /* JOB_DENOISE_ADAPTIVE */
+    crt_denoise_temporal_params dt;     /* JOB_DENOISE_TEMPORAL */
     void *data;              /* ArrayBuffer memory of a read job (kept alive by ab_ref) */
     napi_ref ab_ref;
     char err[640];
@@ -928,6 +1028,7 @@ static void job_execute(napi_env env, void *data)
     case JOB_READ_FRAME_RGBA8: j->rc = crt_read_frame_rgba8(ctx, (uint8_t *)j->data); break;
     case JOB_READ_SAMPLE_RGBA8: j->rc = crt_read_sample_rgba8(ctx, j->n, (uint8_t *)j->data); break;
     case JOB_DENOISE_ADAPTIVE: j->rc = crt_denoise_adaptive(ctx, &j->dn, NULL, (uint8_t *)j->data, NULL); break;
+    case JOB_DENOISE_TEMPORAL: j->rc = crt_denoise_temporal(ctx, &j->dt, NULL, (uint8_t *)j->data, NULL); break;
     default: j->rc = crt_read_frame_accum(ctx, (float *)j->data); break;
     }
     if (j->rc != CRT_OK) {
@@ -946,7 +1047,7 @@ static void job_complete(napi_env env, napi_status status, void *data)
         if (j->ab_ref) {
             napi_value ab;
             const int bytes8 = j->op == JOB_READ_RGBA8 || j->op == JOB_READ_FRAME_RGBA8 || j->op == JOB_READ_SAMPLE_RGBA8 ||
-                               j->op == JOB_DENOISE_ADAPTIVE;
+                               j->op == JOB_DENOISE_ADAPTIVE || j->op == JOB_DENOISE_TEMPORAL;
             if (napi_get_reference_value(env, j->ab_ref, &ab) == napi_ok)
                 napi_create_typedarray(env, bytes8 ? napi_uint8_array : napi_float32_array, (size_t)j->px * 4, ab, 0, &result);
         }
@@ -981,13 +1082,15 @@ static napi_value start_job(napi_env env, napi_callback_info info, int op)
     job *j = (job *)calloc(1, sizeof *j);
     j->sl = sl; j->op = op;
     if (op == JOB_DENOISE_ADAPTIVE && !denoise_adaptive_options(env, argc > 1 ? argv[1] : NULL, argc > 1, &j->dn, NULL)) { free(j); return NULL; }
+    if (op == JOB_DENOISE_TEMPORAL && !denoise_temporal_options(env, argc > 1 ? argv[1] : NULL, argc > 1, &j->dt, NULL)) { free(j); return NULL; }
     if (op == JOB_TRACE || op == JOB_GATHER || op == JOB_READ_SAMPLE_RGBA8) {
         if (napi_get_value_uint32(env, argv[1], &j->n) != napi_ok) { free(j); napi_throw_type_error(env, NULL, "traceAsync / gatherAsync: a number expected"); return NULL; }
     }
     if (op == JOB_READ_RGBA8 || op == JOB_READ_ACCUM || op == JOB_READ_FRAME_RGBA8 || op == JOB_READ_FRAME_ACCUM || op == JOB_READ_SAMPLE_RGBA8 ||
-        op == JOB_DENOISE_ADAPTIVE) {
+        op == JOB_DENOISE_ADAPTIVE || op == JOB_DENOISE_TEMPORAL) {
         const int frame = op == JOB_READ_FRAME_RGBA8 || op == JOB_READ_FRAME_ACCUM;
-        const int bytes8 = op == JOB_READ_RGBA8 || op == JOB_READ_FRAME_RGBA8 || op == JOB_READ_SAMPLE_RGBA8 || op == JOB_DENOISE_ADAPTIVE;
+        const int bytes8 = op == JOB_READ_RGBA8 || op == JOB_READ_FRAME_RGBA8 || op == JOB_READ_SAMPLE_RGBA8 || op == JOB_DENOISE_ADAPTIVE ||
+                           op == JOB_DENOISE_TEMPORAL;
         uint32_t t[4];
         if (frame) { if (crt_image_size(sl->ctx, t + 2) != CRT_OK) { free(j); return throw_crt(env, sl->ctx, CRT_ESTATE, "crt_image_size"); } }
         else if (crt_tile(sl->ctx, t) != CRT_OK) { free(j); return throw_crt(env, sl->ctx, CRT_ESTATE, "crt_tile"); }
@@ -1028,6 +1131,7 @@ static napi_value js_read_sample_rgba8_async(napi_env env, napi_callback_info in
 static napi_value js_read_frame_rgba8_async(napi_env env, napi_callback_info info) { return start_job(env, info, JOB_READ_FRAME_RGBA8); }
 static napi_value js_read_frame_accum_async(napi_env env, napi_callback_info info) { return start_job(env, info, JOB_READ_FRAME_ACCUM); }
 static napi_value js_denoise_adaptive_async(napi_env env, napi_callback_info info) { return start_job(env, info, JOB_DENOISE_ADAPTIVE); }
+static napi_value js_denoise_temporal_async(napi_env env, napi_callback_info info) { return start_job(env, info, JOB_DENOISE_TEMPORAL); }
 
 static napi_value js_abi_version(napi_env env, napi_callback_info info)
 {
@@ -1062,6 +1166,8 @@ static napi_value init(napi_env env, napi_value exports)
         {"refitAccel", js_refit_accel},
         {"traceAdaptive", js_trace_adaptive}, {"readAdaptive", js_read_adaptive},
         {"denoiseAdaptive", js_denoise_adaptive}, {"denoiseAdaptiveAsync", js_denoise_adaptive_async},
+        {"setSampleOffset", js_set_sample_offset}, {"sampleOffset", js_sample_offset}, {"temporalReset", js_temporal_reset},
+        {"denoiseTemporal", js_denoise_temporal}, {"denoiseTemporalAsync", js_denoise_temporal_async},
         {"gatherAsync", js_gather_async}, {"readFrameRgba8Async", js_read_frame_rgba8_async}, {"readFrameAccumAsync", js_read_frame_accum_async},
     };
     for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++) {

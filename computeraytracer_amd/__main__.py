@@ -1,4 +1,4 @@
-"""python -m computeraytracer_amd [--scene file.json] [--width W --height H] [--spp N] [--out image.png] [--denoise K] [--orbit N]
+"""python -m computeraytracer_amd [--scene file.json] [--width W --height H] [--spp N] [--out image.png] [--denoise K] [--orbit N [--temporal]]
                                 [--adaptive THRESHOLD [--adaptive-step N] [--counts-out counts.png]]"""
 import argparse
 import json
@@ -23,6 +23,9 @@ def main():
     ap.add_argument("--orbit", type=int, default=None, metavar="N",
                     help="N frames of --spp each with the eye turned about the look-at point (one upload and build, then "
                          "set_camera per frame), written as OUT_000.png, OUT_001.png, ...")
+    ap.add_argument("--temporal", action="store_true",
+                    help="with --orbit and --denoise K: frame k draws samples k * spp + 1 .. (set_sample_offset) and is blended "
+                         "with the reprojected result of frame k - 1 before the filter (crt_denoise_temporal)")
     ap.add_argument("--adaptive", type=float, default=None, metavar="THRESHOLD",
                     help="adaptive sampling (crt_trace_adaptive): rounds of --adaptive-step samples for the 8x8 tiles whose "
                          "error is above THRESHOLD, --spp samples at most, until every tile is done")
@@ -33,6 +36,8 @@ def main():
     args = ap.parse_args()
     if args.orbit is not None and (args.orbit < 1 or args.checkpoint):
         ap.error("--orbit needs N >= 1 and no --checkpoint")
+    if args.temporal and (args.orbit is None or args.denoise is None):
+        ap.error("--temporal goes with --orbit N --denoise K")
     if args.adaptive is not None and (args.orbit is not None or args.checkpoint):
         ap.error("--adaptive goes with neither --orbit nor --checkpoint")
     if (args.counts_out or args.adaptive_min is not None) and args.adaptive is None:
@@ -47,14 +52,22 @@ def main():
             base, ext = os.path.splitext(args.out)
             outs, t0 = [], time.time()
             for k, cam in enumerate(scene.orbit_cameras(ps.camera, args.orbit)):
-                r.set_camera(cam).frame(args.spp).sync()
-                rgba = r.read_rgba8() if args.denoise is None else r.denoise(args.denoise)
+                r.set_camera(cam)
+                if args.temporal:
+                    r.set_sample_offset(k * args.spp)
+                r.frame(args.spp).sync()
+                if args.temporal:
+                    rgba = r.denoise_temporal(args.denoise)
+                else:
+                    rgba = r.read_rgba8() if args.denoise is None else r.denoise(args.denoise)
                 outs.append(f"{base}_{k:03d}{ext}")
                 (image.write_ppm if ext == ".ppm" else image.write_png)(outs[-1], rgba)
             info = {"width": ps.width, "height": ps.height, "frames": args.orbit, "spp": args.spp,
                     "seconds": round(time.time() - t0, 4), "out": outs}
             if args.denoise is not None:
                 info["denoise"] = args.denoise
+            if args.temporal:
+                info["temporal"] = True
             print(json.dumps(info))
             return
         if args.adaptive is not None:

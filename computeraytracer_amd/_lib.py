@@ -79,6 +79,11 @@ SIGNATURES = {
     "crt_adaptive_defaults": (C.c_int, [_P]),
     "crt_denoise_adaptive": (C.c_int, [_P, _P, _P, _P, _P]),
     "crt_denoise_adaptive_defaults": (C.c_int, [_P]),
+    "crt_set_sample_offset": (C.c_int, [_P, C.c_uint32]),
+    "crt_sample_offset": (C.c_int, [_P, _P]),
+    "crt_denoise_temporal": (C.c_int, [_P, _P, _P, _P, _P]),
+    "crt_denoise_temporal_defaults": (C.c_int, [_P]),
+    "crt_denoise_temporal_reset": (C.c_int, [_P]),
 }
 
 
@@ -110,6 +115,20 @@ def denoise_adaptive_defaults() -> DenoiseAdaptiveParams:
     p = DenoiseAdaptiveParams()
     if load().crt_denoise_adaptive_defaults(C.byref(p)) != 0:
         raise RuntimeError("crt_denoise_adaptive_defaults failed")
+    return p
+
+
+class DenoiseTemporalParams(C.Structure):
+    """crt_denoise_temporal_params of include/crt.h."""
+    _fields_ = [("iterations", C.c_uint32), ("sigma_color", C.c_float), ("sigma_normal", C.c_float), ("sigma_plane", C.c_float),
+                ("max_history", C.c_float), ("normal_tol", C.c_float), ("plane_tol", C.c_float)]
+
+
+def denoise_temporal_defaults() -> DenoiseTemporalParams:
+    """The library's defaults for crt_denoise_temporal (crt_denoise_temporal_defaults)."""
+    p = DenoiseTemporalParams()
+    if load().crt_denoise_temporal_defaults(C.byref(p)) != 0:
+        raise RuntimeError("crt_denoise_temporal_defaults failed")
     return p
 
 

@@ -52,6 +52,9 @@ hipError_t dn_launch_filter_adaptive(const float4 *accum, const float *q, const 
                                      const uint32_t *key, uint2 *kv, float4 *c0, float4 *c1, uchar4 *rgba, float *var,
                                      uint32_t tw, uint32_t th, uint32_t iterations, float sigma_variance, float sigma_normal,
                                      float sigma_plane, float4 **out, hipStream_t stream);
+hipError_t dn_launch_temporal(DnReprojParams P, const float4 *gbuf, const uint32_t *key, float4 *c0, float4 *c1, uchar4 *rgba,
+                              uint32_t iterations, float sigma_color, float sigma_normal, float sigma_plane, float4 **out,
+                              hipStream_t stream);
 hipError_t refit_launch_pad(const unsigned char *raw, uint32_t n, uint32_t *out, hipStream_t s);
 hipError_t refit_launch_prims(const unsigned char *raw, uint32_t first, uint32_t count, const uint32_t *slot_of_index, float4 *prim,
                               float4 *primD, hipStream_t s);
@@ -172,6 +175,8 @@ struct crt_ctx {
     uint32_t published = 0;         // ... of which this many have been turned into batches (or run by the single-kernel form)
     uint32_t pending = 0;           // ... and this many wait to be merged with the next calls' (sample == published + pending)
     bool in_publish = false;
+    uint32_t sample_offset = 0;     // crt_set_sample_offset: sample j since the reset is drawn with the reference's index offset + j
+    uint32_t frame_id = 0;          // events that zeroed the accumulator so far (zero_state): a frame of crt_denoise_temporal
     int wf_cohort = 16;             // small calls are merged into batches of at least this many samples (1 = every call its own batch)
 
     DevBuf<unsigned long long> d_counters;
@@ -243,6 +248,25 @@ struct crt_ctx {
     DevBuf<uchar4> dn_rgba;
     DevBuf<uint2> dn_kv;            // crt_denoise_adaptive: per tile pixel (key, blurred variance bits) of the current pass
     DevBuf<float> dn_var;           // ... and the variance left after the last pass
+    // crt_denoise_temporal: the history slots.  Buffers move between the slots and dn_gbuf / dn_key by
+    // swapping pointers.  The CURRENT slot's G-buffer is dn_gbuf / dn_key themselves while dn_gen == th_gen; a rebuild of
+    // the G-buffer before the slot is promoted (a plain crt_denoise of a later frame) parks them in th_park_* first.
+    struct DnHistory {
+        DevBuf<float4> c;           // blended linear rgb before any spatial filter, w = its weight Hw in samples
+        DevBuf<float4> gbuf;
+        DevBuf<uint32_t> key;
+        float cam[12] = {0};        // that frame's camera_frame
+        bool valid = false;
+    } th_prev;
+    DevBuf<float4> th_cur_c;        // CURRENT: (c, Hw)
+    float th_cur_cam[12] = {0};
+    bool th_cur_valid = false;
+    uint32_t th_cur_frame = 0;      // frame_id it was made in
+    uint32_t th_gen = 0, dn_gen = 0;    // dn_gen: builds of dn_gbuf so far; th_gen: the build CURRENT was made with
+    bool th_parked = false;
+    DevBuf<float4> th_park_gbuf;
+    DevBuf<uint32_t> th_park_key;
+    DevBuf<float> th_hist;          // Hw alone, for history_out
 
     // scene edits (crt_refit.hip)
     float s_prims = 0.0f;           // max |corner coordinate| of the primitives: hit_pad = max(s_prims, |eye|) * 2^-17
@@ -312,6 +336,12 @@ int alloc_frames(crt_ctx *c)
     return CRT_OK;
 }
 
+// Drop the history of crt_denoise_temporal (the buffers stay for the next use).
+void th_drop(crt_ctx *c)
+{
+    c->th_prev.valid = false; c->th_cur_valid = false; c->th_parked = false;
+}
+
 int zero_state(crt_ctx *c)
 {
     size_t n = (size_t)c->tw * c->th;
@@ -321,6 +351,7 @@ int zero_state(crt_ctx *c)
     }
     c->sample = 0; c->published = 0; c->pending = 0; c->resolved_upto = 0; c->ring_from = 1;
     c->as_on = false; c->as_broken = false;
+    c->frame_id++;
     return CRT_OK;
 }
 
@@ -1519,7 +1550,9 @@ int wf_trace_batch(crt_ctx *c, uint32_t n, const AsBatch *as)
         work_total = (unsigned long long)n * as->n_active * 64u;
         work_per_shard = (uint32_t)(((work_total + kWfShards - 1) / kWfShards + 63u) & ~63ull);
     }
-    const uint32_t first_sample = as ? as->off + 1u : c->published + 1u;    // (adaptive: + the tile's count, in k_wf_gen)
+    // (adaptive: + the tile's count, in k_wf_gen.  The sample offset moves the RNG / stratum index alone: work ids, the
+    // staging layout and last_sample, which the resolve pass tone-maps with and indexes the frame ring by, count from the reset)
+    const uint32_t first_sample = as ? as->off + 1u : c->sample_offset + c->published + 1u;
     const uint32_t last_sample = as ? as->off + n : c->published + n;
     // counting folds counters on the host after every batch; otherwise batches are pipelined across calls
     const bool defer = c->wf_defer && !c->counting;
@@ -1763,6 +1796,8 @@ void crt_destroy(crt_ctx *c)
     c->w_vis.release(); c->w_dead.release(); c->w_recA.release(); c->w_recB.release(); c->w_recC.release(); c->w_tea.release(); c->w_wq.release();
     c->dn_gbuf.release(); c->dn_key.release(); c->dn_c[0].release(); c->dn_c[1].release(); c->dn_rgba.release();
     c->dn_kv.release(); c->dn_var.release();
+    c->th_prev.c.release(); c->th_prev.gbuf.release(); c->th_prev.key.release(); c->th_cur_c.release();
+    c->th_park_gbuf.release(); c->th_park_key.release(); c->th_hist.release();
     c->rf_lv2.release(); c->rf_lv4.release(); c->rf_nch4.release(); c->rf_cnt.release(); c->rf_fb.release();
     c->as_counts.release(); c->as_errors.release(); c->as_flags.release(); c->as_active.release(); c->as_n.release(); c->as_q.release();
     if (c->pub_stream) (void)hipStreamSynchronize(c->pub_stream);
@@ -1833,6 +1868,8 @@ int crt_upload_scene(crt_ctx *c, const void *primitives, size_t nprim, const voi
     c->have_scene = false;
     c->accel_mode = -1;
     c->dn_valid = false;
+    c->sample_offset = 0;
+    th_drop(c);
     c->prims.swap(prims);
     c->lights.swap(lts);
     std::memcpy(c->camera, camera, sizeof c->camera);
@@ -1888,6 +1925,7 @@ int crt_set_tile(crt_ctx *c, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1)
     c->x0 = x0; c->y0 = y0; c->tw = x1 - x0; c->th = y1 - y0;
     c->band = 0x40000000u; c->stride = 1; c->phase = 0;
     c->dn_valid = false;
+    th_drop(c);
     c->accum_bound = nullptr; c->rgba_bound = nullptr;
     int rc = alloc_tile(c);
     if (rc) return rc;
@@ -1909,6 +1947,7 @@ int crt_set_row_bands(crt_ctx *c, uint32_t band_rows, uint32_t parts, uint32_t p
     c->x0 = 0; c->y0 = 0; c->tw = c->W; c->th = rows;
     c->band = band_rows; c->stride = parts; c->phase = part;
     c->dn_valid = false;
+    th_drop(c);
     c->accum_bound = nullptr; c->rgba_bound = nullptr;
     int rc = alloc_tile(c);
     if (rc) return rc;
@@ -1955,6 +1994,13 @@ int crt_trace(crt_ctx *c, uint32_t n_samples)
     if (!c->have_scene) return fail(c, CRT_ESTATE, "crt_trace: upload a scene first");
     if (c->accel_mode < 0) return fail(c, CRT_ESTATE, "crt_trace: call crt_build_accel first");
     if (c->accel_stale) return fail(c, CRT_ESTATE, "crt_trace: primitives were updated: call crt_refit_accel or crt_build_accel first");
+    if (c->sample_offset) {
+        if (!(c->pipeline == 1 && c->accel_mode == CRT_ACCEL_BVH2))
+            return fail(c, CRT_ESTATE, "crt_trace: a sample offset needs the wavefront pipeline (\"pipeline\" = 1 and a tree): "
+                                       "crt_set_sample_offset(ctx, 0) first");
+        if ((unsigned long long)c->sample_offset + c->sample + n_samples > 0xFFFFFFFFull)
+            return fail(c, CRT_EINVAL, "crt_trace: sample offset %u + %u samples so far + %u pass 2^32 - 1", c->sample_offset, c->sample, n_samples);
+    }
     HIPCHK(c, hipSetDevice(c->device));
     if ((size_t)c->tw * c->th != 0 && (!accum_ptr(c) || !rgba_ptr(c)))
         return fail(c, CRT_ENOMEM, "crt_trace: the tile's output buffers are not allocated (an earlier crt_set_tile / crt_set_row_bands failed)");
@@ -2063,6 +2109,8 @@ int crt_trace_adaptive(crt_ctx *c, const crt_adaptive_params *params, uint32_t *
     if (c->accel_stale) return fail(c, CRT_ESTATE, "crt_trace: primitives were updated: call crt_refit_accel or crt_build_accel first");
     if (crt_internal_comm_partitioned(c)) return fail(c, CRT_ESTATE, "crt_trace_adaptive: not under a crt_comm_partition (multi-GPU adaptivity is not supported)");
     if (c->as_broken) return as_refuse_broken(c, "crt_trace_adaptive");
+    if (c->sample_offset)
+        return fail(c, CRT_ESTATE, "crt_trace_adaptive: not with a sample offset (%u): crt_set_sample_offset(ctx, 0) first", c->sample_offset);
     if (!c->as_on && c->sample > 0)
         return fail(c, CRT_ESTATE, "crt_trace_adaptive: the context holds %u uniform samples whose second moment was not kept: crt_reset first", c->sample);
     HIPCHK(c, hipSetDevice(c->device));
@@ -2276,6 +2324,8 @@ int crt_write_accum(crt_ctx *c, const float *in, uint32_t sample)
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->sample = sample; c->published = sample; c->pending = 0; c->resolved_upto = sample; c->ring_from = sample + 1u;
     c->as_on = false; c->as_broken = false;                      // (the restored accumulator is a uniform one)
+    c->frame_id++;
+    th_drop(c);
     return CRT_OK;
 }
 
@@ -2467,10 +2517,15 @@ static int dn_ensure_gbuffer(crt_ctx *c)
 {
     if (c->dn_valid) return CRT_OK;
     const size_t n = (size_t)c->tw * c->th;
+    if (c->th_cur_valid && c->th_gen == c->dn_gen && !c->th_parked) {     // the history's CURRENT slot owns this content
+        std::swap(c->dn_gbuf, c->th_park_gbuf); std::swap(c->dn_key, c->th_park_key);
+        c->th_parked = true;
+    }
     if (c->dn_gbuf.n < 2 * n) HIPCHK(c, c->dn_gbuf.alloc(2 * n));
     if (c->dn_key.n < n) HIPCHK(c, c->dn_key.alloc(n));
     HIPCHK(c, dn_launch_gbuffer(c->sc, c->x0, c->y0, c->tw, c->th, c->dn_gbuf.p, c->dn_key.p, c->accel_mode == CRT_ACCEL_NONE, c->stream));
     c->dn_valid = true;
+    c->dn_gen++;
     return CRT_OK;
 }
 
@@ -2543,6 +2598,137 @@ int crt_denoise_adaptive(crt_ctx *c, const crt_denoise_adaptive_params *params, 
         if (rgb_out) HIPCHK(c, hipMemcpyAsync(rgb_out, res, n * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
         if (rgba8_out) HIPCHK(c, hipMemcpyAsync(rgba8_out, c->dn_rgba.p, n * sizeof(uchar4), hipMemcpyDeviceToHost, c->stream));
         if (var_out) HIPCHK(c, hipMemcpyAsync(var_out, c->dn_var.p, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return wf_check_dropped(c);
+}
+
+// ---------------------------------------------------------------- temporal reuse
+int crt_set_sample_offset(crt_ctx *c, uint32_t offset)
+{
+    if (!c) return CRT_EINVAL;
+    if (c->as_on) return as_refuse(c, "crt_set_sample_offset");
+    if (c->sample != 0)
+        return fail(c, CRT_ESTATE, "crt_set_sample_offset: the context holds %u samples: the offset is set at sample 0 (crt_reset first)", c->sample);
+    c->sample_offset = offset;
+    return CRT_OK;
+}
+
+int crt_sample_offset(crt_ctx *c, uint32_t *out)
+{
+    if (!c || !out) return CRT_EINVAL;
+    *out = c->sample_offset;
+    return CRT_OK;
+}
+
+// max_history 64, normal_tol 0.5, plane_tol 2: DESIGN.md 6e has the sweep they were chosen by.
+static const crt_denoise_temporal_params kDnTpDefaults = {5u, 1.0f, 0.5f, 0.3f, 64.0f, 0.5f, 2.0f};
+
+int crt_denoise_temporal_defaults(crt_denoise_temporal_params *out)
+{
+    if (!out) return CRT_EINVAL;
+    *out = kDnTpDefaults;
+    return CRT_OK;
+}
+
+int crt_denoise_temporal_reset(crt_ctx *c)
+{
+    if (!c) return CRT_EINVAL;
+    th_drop(c);
+    return CRT_OK;
+}
+
+// kappa of a camera frame: the pixel's footprint per unit distance, (|hor| / W) / |llc + hor/2 + ver/2 - eye|, in double.
+static double th_kappa(const float cam[12], uint32_t W)
+{
+    double hor = 0.0, ax = 0.0;
+    for (int k = 0; k < 3; k++) {
+        hor += (double)cam[3 + k] * cam[3 + k];
+        const double a = (double)cam[k] + 0.5 * cam[3 + k] + 0.5 * cam[6 + k] - cam[9 + k];
+        ax += a * a;
+    }
+    return (std::sqrt(hor) / (double)W) / std::sqrt(ax);
+}
+
+int crt_denoise_temporal(crt_ctx *c, const crt_denoise_temporal_params *params, float *rgb_out, uint8_t *rgba8_out, float *history_out)
+{
+    if (!c) return CRT_EINVAL;
+    const crt_denoise_temporal_params dp = params ? *params : kDnTpDefaults;
+    if (dp.iterations > 10u) return fail(c, CRT_EINVAL, "crt_denoise_temporal: iterations %u > 10", dp.iterations);
+    const float pos[6] = {dp.sigma_color, dp.sigma_normal, dp.sigma_plane, dp.max_history, dp.normal_tol, dp.plane_tol};
+    for (float v : pos)
+        if (!(v > 0.0f && v <= 3.40282347e38f))
+            return fail(c, CRT_EINVAL, "crt_denoise_temporal: every sigma, tolerance and max_history must be positive and finite");
+    if (c->as_on) return as_refuse(c, "crt_denoise_temporal");
+    { int rc = dn_check_state(c, "crt_denoise_temporal"); if (rc) return rc; }
+    HIPCHK(c, hipSetDevice(c->device));
+    { int rc_ = wf_flush(c); if (rc_) return rc_; }
+    const size_t n = (size_t)c->tw * c->th;
+    if (n) {
+        // every buffer first: a failed allocation leaves the slots as they were
+        if (c->th_cur_c.n < n) HIPCHK(c, c->th_cur_c.alloc(n));
+        if (c->th_prev.c.n < n) HIPCHK(c, c->th_prev.c.alloc(n));
+        for (int b = 0; b < 2; b++) if (c->dn_c[b].n < n) HIPCHK(c, c->dn_c[b].alloc(n));
+        if (c->dn_rgba.n < n) HIPCHK(c, c->dn_rgba.alloc(n));
+        if (c->th_hist.n < n) HIPCHK(c, c->th_hist.alloc(n));
+        // the first call of a new frame: CURRENT becomes PREVIOUS, by pointer
+        if (c->th_cur_valid && c->th_cur_frame != c->frame_id) {
+            if (c->th_parked) {
+                std::swap(c->th_prev.gbuf, c->th_park_gbuf); std::swap(c->th_prev.key, c->th_park_key);
+            } else {
+                std::swap(c->th_prev.gbuf, c->dn_gbuf); std::swap(c->th_prev.key, c->dn_key);
+                c->dn_valid = false;                             // (what came back is an older frame's: rebuilt below)
+            }
+            std::swap(c->th_prev.c, c->th_cur_c);
+            std::memcpy(c->th_prev.cam, c->th_cur_cam, sizeof c->th_prev.cam);
+            c->th_prev.valid = true;
+            c->th_cur_valid = false; c->th_parked = false;
+        }
+        c->th_cur_valid = false;                                 // (rewritten below: a rebuild of the G-buffer has nothing to park)
+        { int rc = dn_ensure_gbuffer(c); if (rc) return rc; }
+        DnReprojParams P{};
+        P.accum = accum_ptr(c); P.gbuf = c->dn_gbuf.p; P.key = c->dn_key.p;
+        P.h_cur = c->th_cur_c.p;
+        P.hist = history_out || rgb_out ? c->th_hist.p : nullptr;
+        P.tw = c->tw; P.th = c->th; P.n = (float)c->sample;
+        if (c->th_prev.valid) {
+            // M' = [hor' ver' (llc' - eye')]^-1 by cofactors, in double
+            const float *q = c->th_prev.cam;
+            double A[3][3], inv[3][3];
+            for (int k = 0; k < 3; k++) { A[k][0] = q[3 + k]; A[k][1] = q[6 + k]; A[k][2] = (double)q[k] - (double)q[9 + k]; }
+            const double det = A[0][0] * (A[1][1] * A[2][2] - A[1][2] * A[2][1]) - A[0][1] * (A[1][0] * A[2][2] - A[1][2] * A[2][0]) +
+                               A[0][2] * (A[1][0] * A[2][1] - A[1][1] * A[2][0]);
+            for (int i = 0; i < 3; i++)
+                for (int j = 0; j < 3; j++) {
+                    const int r0 = (j + 1) % 3, r1 = (j + 2) % 3, c0 = (i + 1) % 3, c1 = (i + 2) % 3;
+                    inv[i][j] = (A[r0][c0] * A[r1][c1] - A[r0][c1] * A[r1][c0]) / det;
+                }
+            bool ok = std::isfinite(det) && det != 0.0;
+            for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) { P.m[3 * i + j] = inv[i][j]; ok = ok && std::isfinite(inv[i][j]); }
+            if (ok) {                                            // (a degenerate previous camera: nothing is reused)
+                P.h_prev = c->th_prev.c.p; P.gbuf_prev = c->th_prev.gbuf.p; P.key_prev = c->th_prev.key.p;
+            }
+            for (int k = 0; k < 3; k++) { P.eye_prev[k] = q[9 + k]; P.eye[k] = c->sc.cam[9 + k]; }
+            P.kappa_prev = (float)th_kappa(q, c->W); P.kappa = (float)th_kappa(c->sc.cam, c->W);
+        }
+        P.W = (double)c->W; P.H = (double)c->H; P.x0 = (double)c->x0; P.y0 = (double)c->y0;
+        P.max_history = dp.max_history;
+        P.normal_tol2 = (float)std::min(3.0e38, (double)dp.normal_tol * dp.normal_tol);
+        P.plane_tol = dp.plane_tol;
+        float4 *res = nullptr;
+        HIPCHK(c, dn_launch_temporal(P, c->dn_gbuf.p, c->dn_key.p, c->dn_c[0].p, c->dn_c[1].p, rgba8_out ? c->dn_rgba.p : nullptr,
+                                     dp.iterations, dp.sigma_color, dp.sigma_normal, dp.sigma_plane, &res, c->stream));
+        std::memcpy(c->th_cur_cam, c->sc.cam, sizeof c->th_cur_cam);
+        c->th_cur_valid = true; c->th_cur_frame = c->frame_id; c->th_gen = c->dn_gen; c->th_parked = false;
+        std::vector<float> hw;                                   // (rgb_out's channel 3 is Hw: the filter passes leave it 0)
+        if (rgb_out && dp.iterations > 0 && !history_out) hw.resize(n);
+        float *hw_host = history_out ? history_out : hw.empty() ? nullptr : hw.data();
+        if (rgb_out) HIPCHK(c, hipMemcpyAsync(rgb_out, res, n * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+        if (rgba8_out) HIPCHK(c, hipMemcpyAsync(rgba8_out, c->dn_rgba.p, n * sizeof(uchar4), hipMemcpyDeviceToHost, c->stream));
+        if (hw_host) HIPCHK(c, hipMemcpyAsync(hw_host, c->th_hist.p, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (rgb_out && dp.iterations > 0)
+            for (size_t i = 0; i < n; i++) rgb_out[4 * i + 3] = hw_host[i];
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return wf_check_dropped(c);
@@ -2855,6 +3041,7 @@ int crt_update_primitives(crt_ctx *c, uint32_t first, uint32_t count, const void
     }
     { int rc = edit_begin(c); if (rc) return rc; }
     std::copy(np.begin(), np.end(), c->prims.begin() + first);   // the host SAH builder reads these
+    th_drop(c);                                                  // (reusing history across moved geometry needs motion vectors)
     if (count) {
         HIPCHK(c, hipMemcpyAsync(c->d_raw.p + (size_t)first * 80, records, (size_t)count * 80, hipMemcpyHostToDevice, c->stream));   // the LBVH builder's input
         if (c->accel_mode >= 0)                                  // the leaf-ordered records, in their slots
@@ -2887,6 +3074,7 @@ int crt_update_lights(crt_ctx *c, uint32_t first, uint32_t count, const void *re
     }
     { int rc = edit_begin(c); if (rc) return rc; }
     std::copy(nl.begin(), nl.end(), c->lights.begin() + first);
+    th_drop(c);
     std::vector<float4> hl((size_t)count * 3);
     for (uint32_t k = 0; k < count; k++) light_rows(nl[k], &hl[3 * (size_t)k]);
     if (count) {

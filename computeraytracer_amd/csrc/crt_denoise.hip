@@ -284,7 +284,110 @@ __global__ __launch_bounds__(256) void k_dn_atrous_as(const DnAsParams P)
     if (P.var) P.var[p] = v;
 }
 
+// ---------------------------------------------------------------- temporal reuse (crt_denoise_temporal)
+// DESIGN.md 6e defines it operation by operation (tests/denoise_temporal_ref.py is its numpy restatement).
+// k_dn_prepare's work, the reprojection into the previous frame and the blend in one pass: grid as k_dn_atrous.  The
+// pixel's own guides stay in registers; a tap's history and G-buffer are fetched only when its key matches.
+__global__ __launch_bounds__(256) void k_dn_reproject(const DnReprojParams P)
+{
+    const int x = (int)(blockIdx.x * 16u + (threadIdx.x & 15u)), y = (int)(blockIdx.y * 16u + (threadIdx.x >> 4));
+    const int tw = (int)P.tw, th = (int)P.th;
+    if (x >= tw || y >= th) return;
+    const size_t p = (size_t)y * P.tw + (size_t)x;
+    const float4 a = P.accum[p];
+    const f3 c_new = xyz_to_linear_rgb(f3{a.x, a.y, a.z} / P.n);
+    f3 c = c_new;
+    float Hw = P.n;
+    const uint32_t key_p = P.key[p];
+    if (P.h_prev && key_p != kNoHit && (key_p >> 24) != kGlass && finite4(float4{c_new.x, c_new.y, c_new.z, 0.0f})) {
+        const float4 g0 = P.gbuf[2 * p], g1 = P.gbuf[2 * p + 1];
+        const f3 x_p = f3{g0.y, g0.z, g0.w}, n_p = f3{g1.x, g1.y, g1.z};
+        // the film position in the previous camera, in binary64 (products and sums as written, nothing contracted)
+        const double dx_ = (double)x_p.x - P.eye_prev[0], dy_ = (double)x_p.y - P.eye_prev[1], dz_ = (double)x_p.z - P.eye_prev[2];
+        const double pa = (P.m[0] * dx_ + P.m[1] * dy_) + P.m[2] * dz_;
+        const double pb = (P.m[3] * dx_ + P.m[4] * dy_) + P.m[5] * dz_;
+        const double pc = (P.m[6] * dx_ + P.m[7] * dy_) + P.m[8] * dz_;
+        if (pc > 0.0 && pc <= 1.7976931348623157e308) {
+            const double u = ((pa / pc) * P.W - 0.53125) - P.x0;
+            const double v = ((P.H + 0.53125) - (pb / pc) * P.H) - P.y0;
+            // (a NaN fails both comparisons; the bounds also keep the conversions to int defined)
+            if (u >= -1.0 && u < (double)tw && v >= -1.0 && v < (double)th) {
+                const double fu = floor(u), fv = floor(v);
+                const int ix = (int)fu, iy = (int)fv;
+                const float fx = (float)(u - fu), fy = (float)(v - fv);
+                const float wx[2] = {1.0f - fx, fx}, wy[2] = {1.0f - fy, fy};
+                const f3 d = x_p - f3{(float)P.eye_prev[0], (float)P.eye_prev[1], (float)P.eye_prev[2]};
+                const float r_p = max_(P.kappa * length(x_p - f3{P.eye[0], P.eye[1], P.eye[2]}), P.kappa_prev * length(d));
+                const float plane_max = P.plane_tol * r_p;
+                float sw = 0.0f, sh = 0.0f;
+                f3 sc = f3{0, 0, 0};
+#pragma unroll
+                for (int dy = 0; dy < 2; dy++) {
+                    const int qy = iy + dy;
+                    if (qy < 0 || qy >= th) continue;
+#pragma unroll
+                    for (int dx = 0; dx < 2; dx++) {
+                        const int qx = ix + dx;
+                        if (qx < 0 || qx >= tw) continue;
+                        const size_t q = (size_t)qy * P.tw + (size_t)qx;
+                        if (P.key_prev[q] != key_p) continue;
+                        const float4 hq = P.h_prev[q];
+                        if (!(hq.w > 0.0f) || !finite4(hq)) continue;
+                        const float4 q0 = P.gbuf_prev[2 * q], q1 = P.gbuf_prev[2 * q + 1];
+                        const f3 dn = n_p - f3{q1.x, q1.y, q1.z};
+                        if (!(dot(dn, dn) <= P.normal_tol2)) continue;
+                        if (!(abs_(dot(n_p, f3{q0.y, q0.z, q0.w} - x_p)) <= plane_max)) continue;
+                        const float w = wx[dx] * wy[dy];
+                        sw = sw + w;
+                        sc = sc + f3{hq.x, hq.y, hq.z} * w;
+                        sh = sh + w * hq.w;
+                    }
+                }
+                if (sw > 0.0f) {
+                    const f3 h = sc / sw;
+                    const float Hp = min_(sh / sw, P.max_history);
+                    Hw = P.n + Hp;
+                    c = (c_new * P.n + h * Hp) / Hw;
+                }
+            }
+        }
+    }
+    P.h_cur[p] = float4{c.x, c.y, c.z, Hw};
+    if (P.rgba) P.rgba[p] = linear_rgb_to_rgba8(c);
+    if (P.hist) P.hist[p] = Hw;
+}
+
 // ---------------------------------------------------------------- launchers (called from crt_api.cpp)
+// The blend into P.h_cur, then `iterations` passes of k_dn_atrous reading h_cur first and ping-ponging between c0 and
+// c1 (h_cur itself stays unfiltered: it is the next frame's history).  The last launch writes rgba.
+hipError_t dn_launch_temporal(DnReprojParams P, const float4 *gbuf, const uint32_t *key, float4 *c0, float4 *c1, uchar4 *rgba,
+                              uint32_t iterations, float sigma_color, float sigma_normal, float sigma_plane, float4 **out,
+                              hipStream_t stream)
+{
+    const uint32_t tw = P.tw, th = P.th;
+    *out = P.h_cur;
+    if ((size_t)tw * th == 0) return hipSuccess;
+    const dim3 grid((tw + 15u) / 16u, (th + 15u) / 16u);
+    P.rgba = iterations == 0 ? rgba : nullptr;
+    hipLaunchKernelGGL(k_dn_reproject, grid, dim3(256), 0, stream, P);
+    hipError_t e = hipGetLastError();
+    float4 *buf[2] = {c0, c1};
+    for (uint32_t i = 0; i < iterations && e == hipSuccess; i++) {
+        DnParams A{};
+        A.c_in = i == 0 ? P.h_cur : buf[(i + 1u) & 1u]; A.c_out = buf[i & 1u];
+        A.gbuf = gbuf; A.key = key;
+        A.rgba = i + 1u == iterations ? rgba : nullptr;
+        A.tw = tw; A.th = th; A.step = 1u << i;
+        A.inv_c = (float)std::min(3.0e38, (double)(1u << i) / ((double)sigma_color * sigma_color));
+        A.inv_n = (float)std::min(3.0e38, 1.0 / ((double)sigma_normal * sigma_normal));
+        A.inv_x = (float)std::min(3.0e38, 1.0 / (double)sigma_plane);
+        hipLaunchKernelGGL(k_dn_atrous, grid, dim3(256), 0, stream, A);
+        e = hipGetLastError();
+        *out = A.c_out;
+    }
+    return e;
+}
+
 hipError_t dn_launch_gbuffer(const DevScene &S, uint32_t x0, uint32_t y0, uint32_t tw, uint32_t th, float4 *gbuf, uint32_t *key,
                              int brute, hipStream_t stream)
 {

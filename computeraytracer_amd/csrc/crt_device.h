@@ -237,4 +237,27 @@ struct WfParams {
     uint32_t overflow_lanes;
 };
 
+// k_dn_reproject (crt_denoise.hip): the blend of a frame with the reprojected history of the previous one.
+// The projection into the previous film plane is binary64 (binary32 places a tap no better than 5e-5 pixel at 480 pixels,
+// and the history of neighbouring pixels differs by whole units); everything else is binary32.
+struct DnReprojParams {
+    double m[9];                    // rows of [hor' ver' (llc' - eye')]^-1 of the previous camera
+    double eye_prev[3];
+    double W, H, x0, y0;            // the full image's size and the rectangle's origin
+    const float4 *accum;            // this frame: XYZ sums of n samples,
+    const float4 *gbuf;             //   its G-buffer and keys
+    const uint32_t *key;
+    const float4 *h_prev;           // previous frame: blended linear rgb, w = its weight Hw in samples; null = no history
+    const float4 *gbuf_prev;
+    const uint32_t *key_prev;
+    float4 *h_cur;                  // out: (c, Hw) of this frame
+    uchar4 *rgba;                   // null, or the rgba8 of c (no filter pass follows)
+    float *hist;                    // null, or Hw alone
+    uint32_t tw, th;
+    float n;
+    float eye[3];
+    float kappa_prev, kappa;        // pixel footprint per unit distance: (|hor| / W) / |llc + hor/2 + ver/2 - eye|
+    float max_history, normal_tol2, plane_tol;
+};
+
 }  // namespace crt

@@ -272,6 +272,47 @@ class Renderer:
         out = (rgba,) + ((lin,) if rgb else ()) + ((vout,) if var else ())
         return out if len(out) > 1 else rgba
 
+    # -- temporal reuse (include/crt.h, "Sample offset" and "Temporal reuse across camera moves")
+    def set_sample_offset(self, offset: int):
+        """Sample j since the reset is drawn with the reference's index offset + j (set at sample 0; wavefront only)."""
+        self._chk(self._lib.crt_set_sample_offset(self._h, int(offset)))
+        return self
+
+    @property
+    def sample_offset(self) -> int:
+        v = C.c_uint32()
+        self._chk(self._lib.crt_sample_offset(self._h, C.byref(v)))
+        return v.value
+
+    def denoise_temporal(self, iterations: int | None = None, sigma_color: float | None = None,
+                         sigma_normal: float | None = None, sigma_plane: float | None = None,
+                         max_history: float | None = None, normal_tol: float | None = None, plane_tol: float | None = None,
+                         rgb: bool = False, history: bool = False):
+        """The frame blended with the previous frame's reprojected result, then the a-trous filter: rgba8 (H, W, 4); with
+        rgb=True also linear rgb (H, W, 4) float32 (channel 3 = the history weight Hw in samples), with history=True
+        also Hw (H, W) float32 -- a tuple in that order.  A parameter left out takes the library's default
+        (crt_denoise_temporal_defaults).  Reads the accumulator only; finishes what is in flight."""
+        _, _, tw, th = self.tile
+        p = _lib.denoise_temporal_defaults()
+        if iterations is not None:
+            p.iterations = int(iterations)
+        for k, v in (("sigma_color", sigma_color), ("sigma_normal", sigma_normal), ("sigma_plane", sigma_plane),
+                     ("max_history", max_history), ("normal_tol", normal_tol), ("plane_tol", plane_tol)):
+            if v is not None:
+                setattr(p, k, float(v))
+        rgba = np.empty((th, tw, 4), np.uint8)
+        lin = np.empty((th, tw, 4), np.float32) if rgb else None
+        hw = np.empty((th, tw), np.float32) if history else None
+        self._chk(self._lib.crt_denoise_temporal(self._h, C.byref(p), lin.ctypes.data if rgb else None, rgba.ctypes.data,
+                                                 hw.ctypes.data if history else None))
+        out = (rgba,) + ((lin,) if rgb else ()) + ((hw,) if history else ())
+        return out if len(out) > 1 else rgba
+
+    def temporal_reset(self):
+        """Drop the history: the next denoise_temporal equals denoise."""
+        self._chk(self._lib.crt_denoise_temporal_reset(self._h))
+        return self
+
     def read_gbuffer(self) -> np.ndarray:
         """(H, W, 8) float32 per tile pixel: t, position, normal, hit index bits (0xFFFFFFFF = miss) of the primary
         ray of sample 8 -- the crt_debug_intersect record."""

@@ -1,11 +1,13 @@
 #!/usr/bin/env node
 'use strict';
 // CLI: node host/index.js [--scene file.json] [--width W --height H] [--spp N] [--accel bvh2|lbvh|none]
-//                         [--out image.ppm] [--dump prefix] [--pack-only prefix] [--denoise K] [--orbit N]
+//                         [--out image.ppm] [--dump prefix] [--pack-only prefix] [--denoise K] [--orbit N [--temporal]]
 // --denoise K: --out gets the image denoised with K a-trous iterations (crt_denoise; with --adaptive the variance-guided
 //            crt_denoise_adaptive) instead of the plain average
 // --orbit N: N frames of --spp each, the eye turned about the look-at point (one upload and build, then setCamera per
 //            frame), written as OUT_000.ppm, OUT_001.ppm, ...
+// --temporal: with --orbit N --denoise K, frame k draws samples k * spp + 1 .. (setSampleOffset) and is blended with the
+//            reprojected result of frame k - 1 before the filter (denoiseTemporal)
 // --adaptive T [--adaptive-step N] [--adaptive-min M]: adaptive sampling (traceAdaptive), rounds of N (16) samples until
 //            every 8x8 tile has an error <= T or holds --spp samples; a tile below M (default min(--spp, 2N)) samples is
 //            sampled whatever its error; prints rounds, pixel-samples, seconds and the min / median / max tile count
@@ -39,14 +41,18 @@ const spp = num('spp', 16);
 const r = Main({ sceneFile: args.scene, width: args.width ? num('width') : undefined, height: args.height ? num('height') : undefined,
   accel: args.accel || 'bvh2', device: num('device', 0) });
 if ('adaptive' in args && args.orbit) { console.error('--adaptive does not go with --orbit'); process.exit(2); }
+if (args.temporal && !(args.orbit && 'denoise' in args)) { console.error('--temporal goes with --orbit N --denoise K'); process.exit(2); }
 if (args.orbit) {
   const n = num('orbit'), base = String(args.out || 'orbit.ppm').replace(/\.ppm$/, ''), outs = [];
   const t1 = process.hrtime.bigint();
   orbitCameras(r.packed.camera, n).forEach((cam, k) => {
     r.setCamera(cam);
+    if (args.temporal) r.setSampleOffset(k * spp);
     r.run(spp);
     outs.push(`${base}_${String(k).padStart(3, '0')}.ppm`);
-    writePPM(outs[k], 'denoise' in args ? r.denoise({ iterations: num('denoise') }) : r.readRgba8(), r.width, r.height);
+    const rgba = args.temporal ? r.denoiseTemporal({ iterations: num('denoise') })
+      : 'denoise' in args ? r.denoise({ iterations: num('denoise') }) : r.readRgba8();
+    writePPM(outs[k], rgba, r.width, r.height);
   });
   console.log(JSON.stringify({ width: r.width, height: r.height, frames: n, spp, seconds: Number(process.hrtime.bigint() - t1) / 1e9, out: outs }));
   r.destroy();

@@ -77,6 +77,14 @@ function Main(options = {}) {
     // rgba8 of the tile, or {rgba8, variance} with opts.variance; reads only.  The Promise form resolves to the rgba8.
     denoiseAdaptive: (opts = {}) => a.denoiseAdaptive(device, opts),
     denoiseAdaptiveAsync: (opts = {}) => a.denoiseAdaptiveAsync(device, opts),
+    // temporal reuse (include/crt.h "Sample offset", "Temporal reuse across camera moves"): distinct samples per frame,
+    // and the frame blended with the previous frame's reprojected result before the filter; rgba8 of the tile, or
+    // {rgba8, history} with opts.history; reads only.  The Promise form resolves to the rgba8.
+    setSampleOffset: (offset) => a.setSampleOffset(device, offset),
+    get sampleOffset() { return a.sampleOffset(device); },
+    denoiseTemporal: (opts = {}) => a.denoiseTemporal(device, opts),
+    denoiseTemporalAsync: (opts = {}) => a.denoiseTemporalAsync(device, opts),
+    temporalReset: () => a.temporalReset(device),
     counters: () => a.counters(device),
     enableCounters: (on) => a.enableCounters(device, !!on),
     lastTraceMs: () => a.lastTraceMs(device),

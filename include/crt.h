@@ -339,6 +339,64 @@ int crt_denoise_adaptive_defaults(crt_denoise_adaptive_params *out);
 int crt_denoise_adaptive(crt_ctx *ctx, const crt_denoise_adaptive_params *params, float *rgb_out, uint8_t *rgba8_out,
                          float *var_out);
 
+/* ------------------------------------------------------------------ Sample offset
+ * Sample s of pixel (x, y) is seeded by (x, y, s) only, and every frame after a reset draws samples 1..n again: the
+ * noise of consecutive frames of a moving camera is the same pattern in screen space, and averaging them over time
+ * gains almost nothing.  With offset B the j-th sample of the frame (j = 1, 2, ...) is drawn with the reference's
+ * sample index B + j (its seed and its stratum (B + j) % 16); everything that COUNTS samples keeps counting from the
+ * reset: crt_sample_count, the tone map's divisor, the indices of the frame ring, the n of crt_denoise.  A frame of n
+ * samples is bit for bit the reference's samples B+1 .. B+n summed into a zero accumulator.
+ * The offset may be set only at sample 0 in the uniform state (else CRT_ESTATE); it persists over crt_reset and the
+ * scene edits, crt_upload_scene returns it to 0, and crt_write_accum(in, s) continues at index B + s + 1.  crt_trace
+ * returns CRT_EINVAL if B plus the samples requested since the reset would pass 2^32 - 1.  Wavefront pipeline only: with
+ * a non-zero offset crt_trace under "pipeline" = 0 or CRT_ACCEL_NONE, and crt_trace_adaptive, return CRT_ESTATE.
+ * Offset 0 (the default) is the behaviour without this call. */
+int crt_set_sample_offset(crt_ctx *ctx, uint32_t offset);
+int crt_sample_offset(crt_ctx *ctx, uint32_t *out);
+
+/* ------------------------------------------------------------------ Temporal reuse across camera moves
+ * Every camera move zeroes the accumulator, so crt_denoise filters each frame of an orbit from that frame's few samples
+ * alone.  crt_denoise_temporal first blends the frame with the previous frame's result, reprojected through the first-hit
+ * G-buffer -- the temporal half of SVGF (Schied et al. 2017; DESIGN.md 6e defines it operation by operation) -- and then
+ * runs crt_denoise's a-trous passes on the blend.  Give consecutive frames distinct samples (crt_set_sample_offset):
+ * with the same samples every frame there is nothing to gain.
+ * The context keeps two history slots over its rectangle, PREVIOUS and CURRENT: the blended linear rgb before any
+ * spatial filter with its weight Hw in samples, that frame's G-buffer and keys, and its camera.  A FRAME is the span
+ * between two events that zero the accumulator.  The first crt_denoise_temporal of a new frame promotes CURRENT to
+ * PREVIOUS; further calls in the same frame (after more samples, say) blend against the same PREVIOUS and overwrite
+ * CURRENT, so calling twice is idempotent.  History survives crt_set_camera, crt_reset, crt_build_accel and a
+ * crt_refit_accel with no primitive update before it; it is dropped by crt_upload_scene, crt_set_tile,
+ * crt_set_row_bands, crt_comm_partition, crt_update_primitives, crt_update_lights, crt_write_accum and
+ * crt_denoise_temporal_reset (moving geometry would need motion vectors).
+ * Per pixel p with first hit x_p, normal n_p and key: no history is taken where there is no PREVIOUS, at a miss, on
+ * glass (view-dependent) or where the pixel's own colour is not finite.  Otherwise x_p is projected into the previous
+ * camera; each of the four bilinear taps q there is reused iff it lies inside the rectangle, has the same key, holds
+ * finite history, |n_p - n_q|^2 <= normal_tol^2 and |n_p . (x_q - x_p)| <= plane_tol * r_p, r_p the larger of the
+ * pixel's footprints at x_p in the two cameras.  With h and Hp the weighted means of the taps' colour and weight,
+ * Hp capped at max_history: c = (n c_new + Hp h) / (n + Hp), Hw = n + Hp; without an accepted tap c = c_new, Hw = n.
+ * A sync point like crt_denoise, and it only READS the accumulator and the sample count: accumulator, rgba8
+ * framebuffer, counters and frame ring stay as they are and the next crt_trace continues bit for bit.  CRT_ESTATE where
+ * crt_denoise returns it (no scene or tree, a stale tree, sample 0, row bands, the adaptive state).  A crt_set_tile
+ * rectangle is filtered on its own. */
+typedef struct {
+    uint32_t iterations;    /* a-trous passes after the blend, 0..10 */
+    float sigma_color;      /* as crt_denoise_params */
+    float sigma_normal;
+    float sigma_plane;
+    float max_history;      /* cap, in samples, on the weight of reused history; > 0 and finite */
+    float normal_tol;       /* a tap is reused if |n_p - n_q|^2 <= normal_tol^2 ... */
+    float plane_tol;        /* ... and |n_p . (x_q - x_p)| <= plane_tol * pixel footprint at x_p */
+} crt_denoise_temporal_params;
+/* The defaults {5, 1.0, 0.5, 0.3, 64, 0.5, 2.0}.  No context and no GPU needed. */
+int crt_denoise_temporal_defaults(crt_denoise_temporal_params *out);
+/* NULL params = the defaults.  rgb_out: tw*th*4 floats (linear rgb; channel 3 = Hw) or NULL; rgba8_out: tw*th*4 bytes
+ * or NULL; history_out: tw*th floats of Hw (n where nothing was reused) or NULL.  CRT_EINVAL (context and history
+ * unchanged) for iterations > 10 or a sigma, tolerance or max_history that is not positive and finite. */
+int crt_denoise_temporal(crt_ctx *ctx, const crt_denoise_temporal_params *params, float *rgb_out, uint8_t *rgba8_out,
+                         float *history_out);
+/* Drop the history: the next crt_denoise_temporal equals crt_denoise. */
+int crt_denoise_temporal_reset(crt_ctx *ctx);
+
 /* Counters accumulate over crt_trace calls while enabled (off by default: the
  * counting kernel variant is slower). */
 int crt_enable_counters(crt_ctx *ctx, int on);

@@ -1,0 +1,112 @@
+"""GPU: temporal reuse from JS (host/main.js setSampleOffset / denoiseTemporal through the N-API addon, blocking and
+Promise form) returns the bytes the Python path returns, and the command lines write it with --orbit --denoise --temporal."""
+import json
+import os
+import shutil
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+from conftest import ROOT, bits
+
+pytestmark = pytest.mark.gpu
+NODE = shutil.which("node")
+
+SCRIPT = r"""
+const fs = require('fs');
+const { Main, orbitCameras } = require(process.argv[1] + '/host/main.js');
+const dir = process.argv[2];
+const r = Main({ width: 64, height: 64, accel: 'bvh2' });
+const cams = orbitCameras(r.packed.camera, 64);
+r.setCamera(cams[0]); r.run(4);
+fs.writeFileSync(`${dir}/f0.bin`, Buffer.from(r.denoiseTemporal().buffer));
+r.setCamera(cams[1]); r.setSampleOffset(4); r.run(4);
+const offset = r.sampleOffset;
+fs.writeFileSync(`${dir}/f1.bin`, Buffer.from(r.denoiseTemporal().buffer));
+const both = r.denoiseTemporal({ iterations: 3, sigmaColor: 0.5, sigmaNormal: 0.25, sigmaPlane: 0.2, maxHistory: 2, normalTol: 0.25, planeTol: 1, history: true });
+fs.writeFileSync(`${dir}/k3.bin`, Buffer.from(both.rgba8.buffer));
+fs.writeFileSync(`${dir}/k3_hw.bin`, Buffer.from(both.history.buffer));
+let threw = '';
+try { r.denoiseTemporal({ iterations: 11 }); } catch (e) { threw = String(e.message); }
+r.denoiseTemporalAsync({ iterations: 3, sigmaColor: 0.5, sigmaNormal: 0.25, sigmaPlane: 0.2, maxHistory: 2, normalTol: 0.25, planeTol: 1 }).then((rgba) => {
+  fs.writeFileSync(`${dir}/k3_async.bin`, Buffer.from(rgba.buffer));
+  r.temporalReset();
+  fs.writeFileSync(`${dir}/reset.bin`, Buffer.from(r.denoiseTemporal().buffer));
+  fs.writeFileSync(`${dir}/plain.bin`, Buffer.from(r.denoise().buffer));
+  console.log(JSON.stringify({ threw, offset }));
+  r.destroy();
+});
+"""
+
+
+@pytest.mark.skipif(NODE is None, reason="node not installed")
+def test_node_denoise_temporal_equals_the_python_path(tmp_path, renderer):
+    from computeraytracer_amd import cornell
+    from computeraytracer_amd.scene import orbit_cameras
+    out = subprocess.run([NODE, "-e", SCRIPT, ROOT, str(tmp_path)], capture_output=True, text=True, check=True, cwd=ROOT)
+    info = json.loads(out.stdout.strip().splitlines()[-1])
+    assert "iterations" in info["threw"] and info["offset"] == 4
+    ps = cornell(64, 64)
+    cams = orbit_cameras(ps.camera, 64)
+    read = lambda name, dt, shape: np.frombuffer((tmp_path / name).read_bytes(), dt).reshape(shape)    # noqa: E731
+    renderer.upload(ps).build_accel("bvh2")
+    try:
+        renderer.set_camera(cams[0]).frame(4).sync()
+        assert np.array_equal(read("f0.bin", np.uint8, (64, 64, 4)), renderer.denoise_temporal())
+        renderer.set_camera(cams[1]).set_sample_offset(4).frame(4).sync()
+        assert np.array_equal(read("f1.bin", np.uint8, (64, 64, 4)), renderer.denoise_temporal())
+        rgba, hw = renderer.denoise_temporal(3, 0.5, 0.25, 0.2, 2.0, 0.25, 1.0, history=True)
+        assert np.array_equal(read("k3.bin", np.uint8, (64, 64, 4)), rgba)
+        assert np.array_equal(read("k3_async.bin", np.uint8, (64, 64, 4)), rgba)
+        assert np.array_equal(bits(read("k3_hw.bin", np.float32, (64, 64))), bits(hw)) and hw.max() == 6.0
+        assert np.array_equal(read("reset.bin", np.uint8, (64, 64, 4)), read("plain.bin", np.uint8, (64, 64, 4)))
+        assert np.array_equal(read("plain.bin", np.uint8, (64, 64, 4)), renderer.denoise())
+    finally:
+        renderer.temporal_reset().reset().set_sample_offset(0)
+
+
+def _python_orbit(renderer, ps, frames, spp, k_iter):
+    from computeraytracer_amd.scene import orbit_cameras
+    renderer.upload(ps).build_accel("bvh2")
+    out = []
+    for k, cam in enumerate(orbit_cameras(ps.camera, frames)):
+        renderer.set_camera(cam).set_sample_offset(k * spp).frame(spp).sync()
+        out.append(renderer.denoise_temporal(k_iter))
+    return out
+
+
+def test_command_line_writes_the_temporal_orbit(tmp_path, renderer):
+    from computeraytracer_amd import cornell, image
+    out = tmp_path / "orb.png"
+    run = subprocess.run([sys.executable, "-m", "computeraytracer_amd", "--width", "64", "--height", "48", "--spp", "4",
+                          "--orbit", "3", "--denoise", "4", "--temporal", "--out", str(out)],
+                         capture_output=True, text=True, check=True, cwd=ROOT)
+    info = json.loads(run.stdout.strip().splitlines()[-1])
+    assert info["temporal"] is True and info["denoise"] == 4 and len(info["out"]) == 3
+    try:
+        for k, rgba in enumerate(_python_orbit(renderer, cornell(64, 48), 3, 4, 4)):
+            want = tmp_path / f"want_{k}.png"
+            image.write_png(str(want), rgba)
+            assert (tmp_path / f"orb_{k:03d}.png").read_bytes() == want.read_bytes()
+    finally:
+        renderer.temporal_reset().reset().set_sample_offset(0)
+    bad = subprocess.run([sys.executable, "-m", "computeraytracer_amd", "--temporal"], capture_output=True, text=True, cwd=ROOT)
+    assert bad.returncode == 2 and "--temporal" in bad.stderr
+
+
+@pytest.mark.skipif(NODE is None, reason="node not installed")
+def test_node_command_line_writes_the_temporal_orbit(tmp_path, renderer):
+    from computeraytracer_amd import cornell
+    out = tmp_path / "orb.ppm"
+    run = subprocess.run([NODE, os.path.join(ROOT, "host", "index.js"), "--width", "64", "--height", "48", "--spp", "4",
+                          "--orbit", "3", "--denoise", "4", "--temporal", "--out", str(out)], capture_output=True, text=True, check=True)
+    info = json.loads(run.stdout.strip().splitlines()[-1])
+    assert info["frames"] == 3
+    try:
+        for k, rgba in enumerate(_python_orbit(renderer, cornell(64, 48), 3, 4, 4)):
+            got = (tmp_path / f"orb_{k:03d}.ppm").read_bytes()
+            assert got == b"P6\n64 48\n255\n" + np.ascontiguousarray(rgba[..., :3]).tobytes()
+    finally:
+        renderer.temporal_reset().reset().set_sample_offset(0)
