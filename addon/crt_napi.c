@@ -475,41 +475,95 @@ static int opt_number(napi_env env, napi_value obj, const char *name, double *ou
     return t == napi_number && napi_get_value_double(env, v, out) == napi_ok;
 }
 
+/* One options object for the three filters.  `opts` lists (JS name, value): a property that is present and not undefined
+ * must be a number and replaces *value; opts[0] is the iteration count, a non-negative integer.  `flag`, where one is
+ * wanted, names a property whose truthiness goes to *flag_out.  Throws as `fn` and returns 0 on a refusal. */
+typedef struct { const char *name; double *value; } dn_opt;
+
+static int denoise_options(napi_env env, const char *fn, napi_value obj, int have_obj, const dn_opt *opts, size_t n_opts,
+                           const char *flag, bool *flag_out)
+{
+    char msg[96];
+    napi_valuetype t = napi_undefined;
+    if (flag_out) *flag_out = false;
+    if (have_obj && napi_typeof(env, obj, &t) != napi_ok) t = napi_boolean;
+    if (t == napi_object) {
+        for (size_t k = 0; k < n_opts; k++)
+            if (!opt_number(env, obj, opts[k].name, opts[k].value)) {
+                snprintf(msg, sizeof msg, "%s: options must be numbers", fn);
+                napi_throw_type_error(env, NULL, msg);
+                return 0;
+            }
+        bool has = false;
+        napi_value v;
+        if (flag_out && napi_has_named_property(env, obj, flag, &has) == napi_ok && has &&
+            napi_get_named_property(env, obj, flag, &v) == napi_ok)
+            napi_coerce_to_bool(env, v, &v), napi_get_value_bool(env, v, flag_out);
+    } else if (t != napi_undefined && t != napi_null) {
+        snprintf(msg, sizeof msg, "%s: options object expected", fn);
+        napi_throw_type_error(env, NULL, msg);
+        return 0;
+    }
+    const double it = *opts[0].value;
+    if (!(it >= 0.0 && it <= 4294967295.0) || it != (double)(uint32_t)it) {
+        snprintf(msg, sizeof msg, "%s: iterations must be a non-negative integer", fn);
+        napi_throw_range_error(env, NULL, msg);
+        return 0;
+    }
+    return 1;
+}
+
+/* The outputs of a filter call on the tile: rgba8 (tw*th*4 bytes) and, where wanted, one float per pixel. */
+typedef struct { size_t px; void *rgba8, *plane; napi_value rgba8_ab, plane_ab; } dn_out;
+
+static int denoise_outputs(napi_env env, crt_ctx *ctx, bool plane, dn_out *o)
+{
+    uint32_t tl[4];
+    memset(o, 0, sizeof *o);
+    const int rc = crt_tile(ctx, tl);
+    if (rc != CRT_OK) { throw_crt(env, ctx, rc, "crt_tile"); return 0; }
+    o->px = (size_t)tl[2] * tl[3];
+    if (napi_create_arraybuffer(env, o->px * 4, &o->rgba8, &o->rgba8_ab) != napi_ok ||
+        (plane && napi_create_arraybuffer(env, o->px * 4, &o->plane, &o->plane_ab) != napi_ok)) {
+        napi_throw_error(env, NULL, "out of memory");
+        return 0;
+    }
+    return 1;
+}
+
+/* ... as the call's result: the Uint8Array, or {rgba8, <name>: Float32Array(tw*th)} where the plane was wanted. */
+static napi_value denoise_result(napi_env env, const dn_out *o, const char *name)
+{
+    napi_value ta, pta, obj;
+    NAPI_OK(env, napi_create_typedarray(env, napi_uint8_array, o->px * 4, o->rgba8_ab, 0, &ta));
+    if (!o->plane) return ta;
+    NAPI_OK(env, napi_create_typedarray(env, napi_float32_array, o->px, o->plane_ab, 0, &pta));
+    NAPI_OK(env, napi_create_object(env, &obj));
+    NAPI_OK(env, napi_set_named_property(env, obj, "rgba8", ta));
+    NAPI_OK(env, napi_set_named_property(env, obj, name, pta));
+    return obj;
+}
+
+/* (handle, options?) of the three filters */
+#define DENOISE_ARGS                                                                                \
+    size_t argc = 2;                                                                                \
+    napi_value argv[2];                                                                             \
+    NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));                             \
+    if (argc < 1) { napi_throw_type_error(env, NULL, "too few arguments"); return NULL; }           \
+    crt_ctx *ctx = get_ctx(env, argv[0]);                                                           \
+    if (!ctx) return NULL;
+
 static napi_value js_denoise(napi_env env, napi_callback_info info)
 {
-    size_t argc = 2;
-    napi_value argv[2];
-    NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
-    if (argc < 1) { napi_throw_type_error(env, NULL, "too few arguments"); return NULL; }
-    crt_ctx *ctx = get_ctx(env, argv[0]);
-    if (!ctx) return NULL;
+    DENOISE_ARGS
     double it = 5.0, sc = 1.0, sn = 0.5, sx = 0.3;
-    napi_valuetype t = napi_undefined;
-    if (argc > 1) NAPI_OK(env, napi_typeof(env, argv[1], &t));
-    if (t == napi_object) {
-        if (!opt_number(env, argv[1], "iterations", &it) || !opt_number(env, argv[1], "sigmaColor", &sc) ||
-            !opt_number(env, argv[1], "sigmaNormal", &sn) || !opt_number(env, argv[1], "sigmaPlane", &sx)) {
-            napi_throw_type_error(env, NULL, "denoise: options must be numbers");
-            return NULL;
-        }
-    } else if (t != napi_undefined && t != napi_null) {
-        napi_throw_type_error(env, NULL, "denoise: options object expected");
-        return NULL;
-    }
-    if (!(it >= 0.0 && it <= 4294967295.0) || it != (double)(uint32_t)it) {
-        napi_throw_range_error(env, NULL, "denoise: iterations must be a non-negative integer");
-        return NULL;
-    }
+    const dn_opt o[] = {{"iterations", &it}, {"sigmaColor", &sc}, {"sigmaNormal", &sn}, {"sigmaPlane", &sx}};
+    if (!denoise_options(env, "denoise", argc > 1 ? argv[1] : NULL, argc > 1, o, 4, NULL, NULL)) return NULL;
     crt_denoise_params p = {(uint32_t)it, (float)sc, (float)sn, (float)sx};
-    uint32_t tl[4];
-    CRT_CHECK(env, ctx, "crt_tile", crt_tile(ctx, tl));
-    size_t px = (size_t)tl[2] * tl[3];
-    void *data = NULL;
-    napi_value ab, ta;
-    NAPI_OK(env, napi_create_arraybuffer(env, px * 4, &data, &ab));
-    CRT_CHECK(env, ctx, "crt_denoise", crt_denoise(ctx, &p, NULL, (uint8_t *)data));
-    NAPI_OK(env, napi_create_typedarray(env, napi_uint8_array, px * 4, ab, 0, &ta));
-    return ta;
+    dn_out out;
+    if (!denoise_outputs(env, ctx, false, &out)) return NULL;
+    CRT_CHECK(env, ctx, "crt_denoise", crt_denoise(ctx, &p, NULL, (uint8_t *)out.rgba8));
+    return denoise_result(env, &out, NULL);
 }
 
 /* denoiseAdaptive(h, {iterations, sigmaVariance, sigmaNormal, sigmaPlane, variance}) -> Uint8Array (tw*th*4 rgba8), or
@@ -518,61 +572,24 @@ static napi_value js_denoise(napi_env env, napi_callback_info info)
  * (crt_denoise_adaptive_defaults).  denoiseAdaptiveAsync(h, {...}) -> Promise of the Uint8Array (below). */
 static int denoise_adaptive_options(napi_env env, napi_value opts, int have_opts, crt_denoise_adaptive_params *p, bool *variance)
 {
-    double it, sv, sn, sx;
-    napi_valuetype t = napi_undefined;
     if (crt_denoise_adaptive_defaults(p) != CRT_OK) { napi_throw_error(env, NULL, "crt_denoise_adaptive_defaults failed"); return 0; }
-    it = p->iterations; sv = p->sigma_variance; sn = p->sigma_normal; sx = p->sigma_plane;
-    if (variance) *variance = false;
-    if (have_opts && napi_typeof(env, opts, &t) != napi_ok) { napi_throw_type_error(env, NULL, "denoiseAdaptive: options object expected"); return 0; }
-    if (t == napi_object) {
-        if (!opt_number(env, opts, "iterations", &it) || !opt_number(env, opts, "sigmaVariance", &sv) ||
-            !opt_number(env, opts, "sigmaNormal", &sn) || !opt_number(env, opts, "sigmaPlane", &sx)) {
-            napi_throw_type_error(env, NULL, "denoiseAdaptive: options must be numbers");
-            return 0;
-        }
-        bool has = false;
-        napi_value v;
-        if (variance && napi_has_named_property(env, opts, "variance", &has) == napi_ok && has &&
-            napi_get_named_property(env, opts, "variance", &v) == napi_ok)
-            napi_coerce_to_bool(env, v, &v), napi_get_value_bool(env, v, variance);
-    } else if (t != napi_undefined && t != napi_null) {
-        napi_throw_type_error(env, NULL, "denoiseAdaptive: options object expected");
-        return 0;
-    }
-    if (!(it >= 0.0 && it <= 4294967295.0) || it != (double)(uint32_t)it) {
-        napi_throw_range_error(env, NULL, "denoiseAdaptive: iterations must be a non-negative integer");
-        return 0;
-    }
+    double it = p->iterations, sv = p->sigma_variance, sn = p->sigma_normal, sx = p->sigma_plane;
+    const dn_opt o[] = {{"iterations", &it}, {"sigmaVariance", &sv}, {"sigmaNormal", &sn}, {"sigmaPlane", &sx}};
+    if (!denoise_options(env, "denoiseAdaptive", opts, have_opts, o, 4, "variance", variance)) return 0;
     p->iterations = (uint32_t)it; p->sigma_variance = (float)sv; p->sigma_normal = (float)sn; p->sigma_plane = (float)sx;
     return 1;
 }
 
 static napi_value js_denoise_adaptive(napi_env env, napi_callback_info info)
 {
-    size_t argc = 2;
-    napi_value argv[2];
-    NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
-    if (argc < 1) { napi_throw_type_error(env, NULL, "too few arguments"); return NULL; }
-    crt_ctx *ctx = get_ctx(env, argv[0]);
-    if (!ctx) return NULL;
+    DENOISE_ARGS
     crt_denoise_adaptive_params p;
     bool variance = false;
     if (!denoise_adaptive_options(env, argc > 1 ? argv[1] : NULL, argc > 1, &p, &variance)) return NULL;
-    uint32_t tl[4];
-    CRT_CHECK(env, ctx, "crt_tile", crt_tile(ctx, tl));
-    size_t px = (size_t)tl[2] * tl[3];
-    void *data = NULL, *vdata = NULL;
-    napi_value ab, ta, vab, vta, obj;
-    NAPI_OK(env, napi_create_arraybuffer(env, px * 4, &data, &ab));
-    if (variance) NAPI_OK(env, napi_create_arraybuffer(env, px * 4, &vdata, &vab));
-    CRT_CHECK(env, ctx, "crt_denoise_adaptive", crt_denoise_adaptive(ctx, &p, NULL, (uint8_t *)data, (float *)vdata));
-    NAPI_OK(env, napi_create_typedarray(env, napi_uint8_array, px * 4, ab, 0, &ta));
-    if (!variance) return ta;
-    NAPI_OK(env, napi_create_typedarray(env, napi_float32_array, px, vab, 0, &vta));
-    NAPI_OK(env, napi_create_object(env, &obj));
-    NAPI_OK(env, napi_set_named_property(env, obj, "rgba8", ta));
-    NAPI_OK(env, napi_set_named_property(env, obj, "variance", vta));
-    return obj;
+    dn_out out;
+    if (!denoise_outputs(env, ctx, variance, &out)) return NULL;
+    CRT_CHECK(env, ctx, "crt_denoise_adaptive", crt_denoise_adaptive(ctx, &p, NULL, (uint8_t *)out.rgba8, (float *)out.plane));
+    return denoise_result(env, &out, "variance");
 }
 
 /* setSampleOffset(h, offset), sampleOffset(h) -> number, temporalReset(h): include/crt.h "Sample offset" and "Temporal
@@ -615,63 +632,28 @@ static napi_value js_temporal_reset(napi_env env, napi_callback_info info)
 
 static int denoise_temporal_options(napi_env env, napi_value opts, int have_opts, crt_denoise_temporal_params *p, bool *history)
 {
-    double it, v[6];
-    static const char *names[6] = {"sigmaColor", "sigmaNormal", "sigmaPlane", "maxHistory", "normalTol", "planeTol"};
-    napi_valuetype t = napi_undefined;
     if (crt_denoise_temporal_defaults(p) != CRT_OK) { napi_throw_error(env, NULL, "crt_denoise_temporal_defaults failed"); return 0; }
-    it = p->iterations;
-    v[0] = p->sigma_color; v[1] = p->sigma_normal; v[2] = p->sigma_plane; v[3] = p->max_history; v[4] = p->normal_tol; v[5] = p->plane_tol;
-    if (history) *history = false;
-    if (have_opts && napi_typeof(env, opts, &t) != napi_ok) { napi_throw_type_error(env, NULL, "denoiseTemporal: options object expected"); return 0; }
-    if (t == napi_object) {
-        int ok = opt_number(env, opts, "iterations", &it);
-        for (int k = 0; k < 6 && ok; k++) ok = opt_number(env, opts, names[k], &v[k]);
-        if (!ok) { napi_throw_type_error(env, NULL, "denoiseTemporal: options must be numbers"); return 0; }
-        bool has = false;
-        napi_value hv;
-        if (history && napi_has_named_property(env, opts, "history", &has) == napi_ok && has &&
-            napi_get_named_property(env, opts, "history", &hv) == napi_ok)
-            napi_coerce_to_bool(env, hv, &hv), napi_get_value_bool(env, hv, history);
-    } else if (t != napi_undefined && t != napi_null) {
-        napi_throw_type_error(env, NULL, "denoiseTemporal: options object expected");
-        return 0;
-    }
-    if (!(it >= 0.0 && it <= 4294967295.0) || it != (double)(uint32_t)it) {
-        napi_throw_range_error(env, NULL, "denoiseTemporal: iterations must be a non-negative integer");
-        return 0;
-    }
+    double it = p->iterations, sc = p->sigma_color, sn = p->sigma_normal, sx = p->sigma_plane, mh = p->max_history, nt = p->normal_tol,
+           pt = p->plane_tol;
+    const dn_opt o[] = {{"iterations", &it}, {"sigmaColor", &sc}, {"sigmaNormal", &sn}, {"sigmaPlane", &sx}, {"maxHistory", &mh},
+                        {"normalTol", &nt}, {"planeTol", &pt}};
+    if (!denoise_options(env, "denoiseTemporal", opts, have_opts, o, 7, "history", history)) return 0;
     p->iterations = (uint32_t)it;
-    p->sigma_color = (float)v[0]; p->sigma_normal = (float)v[1]; p->sigma_plane = (float)v[2];
-    p->max_history = (float)v[3]; p->normal_tol = (float)v[4]; p->plane_tol = (float)v[5];
+    p->sigma_color = (float)sc; p->sigma_normal = (float)sn; p->sigma_plane = (float)sx;
+    p->max_history = (float)mh; p->normal_tol = (float)nt; p->plane_tol = (float)pt;
     return 1;
 }
 
 static napi_value js_denoise_temporal(napi_env env, napi_callback_info info)
 {
-    size_t argc = 2;
-    napi_value argv[2];
-    NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
-    if (argc < 1) { napi_throw_type_error(env, NULL, "too few arguments"); return NULL; }
-    crt_ctx *ctx = get_ctx(env, argv[0]);
-    if (!ctx) return NULL;
+    DENOISE_ARGS
     crt_denoise_temporal_params p;
     bool history = false;
     if (!denoise_temporal_options(env, argc > 1 ? argv[1] : NULL, argc > 1, &p, &history)) return NULL;
-    uint32_t tl[4];
-    CRT_CHECK(env, ctx, "crt_tile", crt_tile(ctx, tl));
-    size_t px = (size_t)tl[2] * tl[3];
-    void *data = NULL, *hdata = NULL;
-    napi_value ab, ta, hab, hta, obj;
-    NAPI_OK(env, napi_create_arraybuffer(env, px * 4, &data, &ab));
-    if (history) NAPI_OK(env, napi_create_arraybuffer(env, px * 4, &hdata, &hab));
-    CRT_CHECK(env, ctx, "crt_denoise_temporal", crt_denoise_temporal(ctx, &p, NULL, (uint8_t *)data, (float *)hdata));
-    NAPI_OK(env, napi_create_typedarray(env, napi_uint8_array, px * 4, ab, 0, &ta));
-    if (!history) return ta;
-    NAPI_OK(env, napi_create_typedarray(env, napi_float32_array, px, hab, 0, &hta));
-    NAPI_OK(env, napi_create_object(env, &obj));
-    NAPI_OK(env, napi_set_named_property(env, obj, "rgba8", ta));
-    NAPI_OK(env, napi_set_named_property(env, obj, "history", hta));
-    return obj;
+    dn_out out;
+    if (!denoise_outputs(env, ctx, history, &out)) return NULL;
+    CRT_CHECK(env, ctx, "crt_denoise_temporal", crt_denoise_temporal(ctx, &p, NULL, (uint8_t *)out.rgba8, (float *)out.plane));
+    return denoise_result(env, &out, "history");
 }
 
 static napi_value js_read_gbuffer(napi_env env, napi_callback_info info)

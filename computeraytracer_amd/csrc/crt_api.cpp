@@ -43,18 +43,6 @@ hipError_t wf_launch_resolve(const WfParams &P, uint32_t last_sample, hipStream_
 hipError_t build_lbvh(const float *lo, const float *hi, uint32_t n, Bvh &out, hipStream_t stream);
 hipError_t build_lbvh_device(const unsigned char *d_raw, uint32_t n, float hit_pad, float4 *d_prim, float4 *d_primD,
                              uint32_t *d_slot_of_index, float *d_nodes2, uint4 *d_nodes4q, LbvhDeviceResult &res, hipStream_t stream);
-hipError_t dn_launch_gbuffer(const DevScene &S, uint32_t x0, uint32_t y0, uint32_t tw, uint32_t th, float4 *gbuf, uint32_t *key,
-                             int brute, hipStream_t stream);
-hipError_t dn_launch_filter(const float4 *accum, float n, const float4 *gbuf, const uint32_t *key, float4 *c0, float4 *c1,
-                            uchar4 *rgba, uint32_t tw, uint32_t th, uint32_t iterations, float sigma_color, float sigma_normal,
-                            float sigma_plane, float4 **out, hipStream_t stream);
-hipError_t dn_launch_filter_adaptive(const float4 *accum, const float *q, const uint32_t *counts, const float4 *gbuf,
-                                     const uint32_t *key, uint2 *kv, float4 *c0, float4 *c1, uchar4 *rgba, float *var,
-                                     uint32_t tw, uint32_t th, uint32_t iterations, float sigma_variance, float sigma_normal,
-                                     float sigma_plane, float4 **out, hipStream_t stream);
-hipError_t dn_launch_temporal(DnReprojParams P, const float4 *gbuf, const uint32_t *key, float4 *c0, float4 *c1, uchar4 *rgba,
-                              uint32_t iterations, float sigma_color, float sigma_normal, float sigma_plane, float4 **out,
-                              hipStream_t stream);
 hipError_t refit_launch_pad(const unsigned char *raw, uint32_t n, uint32_t *out, hipStream_t s);
 hipError_t refit_launch_prims(const unsigned char *raw, uint32_t first, uint32_t count, const uint32_t *slot_of_index, float4 *prim,
                               float4 *primD, hipStream_t s);
@@ -2512,6 +2500,12 @@ static int dn_check_state(crt_ctx *c, const char *what, bool adaptive = false)  
     return CRT_OK;
 }
 
+// Grow a DevBuf of the context to `count` elements (the refusal names the buffer).
+#define DN_ENSURE(c, buf, count)                                   \
+    do {                                                           \
+        if (c->buf.n < (count)) HIPCHK(c, c->buf.alloc(count));    \
+    } while (0)
+
 // The G-buffer of the tile, built once per scene / accel structure / tile.  Enqueued on the context's stream.
 static int dn_ensure_gbuffer(crt_ctx *c)
 {
@@ -2521,40 +2515,76 @@ static int dn_ensure_gbuffer(crt_ctx *c)
         std::swap(c->dn_gbuf, c->th_park_gbuf); std::swap(c->dn_key, c->th_park_key);
         c->th_parked = true;
     }
-    if (c->dn_gbuf.n < 2 * n) HIPCHK(c, c->dn_gbuf.alloc(2 * n));
-    if (c->dn_key.n < n) HIPCHK(c, c->dn_key.alloc(n));
+    DN_ENSURE(c, dn_gbuf, 2 * n);
+    DN_ENSURE(c, dn_key, n);
     HIPCHK(c, dn_launch_gbuffer(c->sc, c->x0, c->y0, c->tw, c->th, c->dn_gbuf.p, c->dn_key.p, c->accel_mode == CRT_ACCEL_NONE, c->stream));
     c->dn_valid = true;
     c->dn_gen++;
     return CRT_OK;
 }
 
-int crt_denoise(crt_ctx *c, const crt_denoise_params *params, float *rgb_out, uint8_t *rgba8_out)
+// What the four entry points below do first: the checks, then the context's device and everything in flight finished.
+// `values` must be positive and finite; `which` names them in the refusal.
+enum DnState { DN_UNIFORM, DN_ADAPTIVE, DN_EITHER };
+
+static int dn_begin(crt_ctx *c, const char *what, uint32_t iterations, const float *values, int count, const char *which, DnState state)
 {
     if (!c) return CRT_EINVAL;
-    const crt_denoise_params dp = params ? *params : crt_denoise_params{5u, 1.0f, 0.5f, 0.3f};
-    if (dp.iterations > 10u) return fail(c, CRT_EINVAL, "crt_denoise: iterations %u > 10", dp.iterations);
-    const float sig[3] = {dp.sigma_color, dp.sigma_normal, dp.sigma_plane};
-    for (float v : sig)
-        if (!(v > 0.0f && v <= 3.40282347e38f)) return fail(c, CRT_EINVAL, "crt_denoise: every sigma must be positive and finite");
-    if (c->as_on) return as_refuse(c, "crt_denoise");
-    { int rc = dn_check_state(c, "crt_denoise"); if (rc) return rc; }
+    if (iterations > 10u) return fail(c, CRT_EINVAL, "%s: iterations %u > 10", what, iterations);
+    for (int k = 0; k < count; k++)
+        if (!(values[k] > 0.0f && values[k] <= 3.40282347e38f)) return fail(c, CRT_EINVAL, "%s: %s must be positive and finite", what, which);
+    if (state == DN_UNIFORM && c->as_on) return as_refuse(c, what);
+    if (state == DN_ADAPTIVE && !c->as_on)
+        return fail(c, CRT_ESTATE, "%s: the context is in the uniform state (crt_denoise filters a uniform render; "
+                                   "crt_trace_adaptive with min_samples == max_samples gives this filter one)", what);
+    if (state == DN_ADAPTIVE && c->as_broken) return as_refuse_broken(c, what);
+    { int rc = dn_check_state(c, what, state == DN_ADAPTIVE); if (rc) return rc; }
     HIPCHK(c, hipSetDevice(c->device));
-    { int rc_ = wf_flush(c); if (rc_) return rc_; }
-    const size_t n = (size_t)c->tw * c->th;
-    if (n) {
-        { int rc = dn_ensure_gbuffer(c); if (rc) return rc; }
-        for (int b = 0; b < 2; b++) if (c->dn_c[b].n < n) HIPCHK(c, c->dn_c[b].alloc(n));
-        if (c->dn_rgba.n < n) HIPCHK(c, c->dn_rgba.alloc(n));
-        float4 *res = nullptr;
-        HIPCHK(c, dn_launch_filter(accum_ptr(c), (float)c->sample, c->dn_gbuf.p, c->dn_key.p, c->dn_c[0].p, c->dn_c[1].p,
-                                   rgba8_out ? c->dn_rgba.p : nullptr, c->tw, c->th, dp.iterations, dp.sigma_color,
-                                   dp.sigma_normal, dp.sigma_plane, &res, c->stream));
-        if (rgb_out) HIPCHK(c, hipMemcpyAsync(rgb_out, res, n * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
-        if (rgba8_out) HIPCHK(c, hipMemcpyAsync(rgba8_out, c->dn_rgba.p, n * sizeof(uchar4), hipMemcpyDeviceToHost, c->stream));
-    }
+    return wf_flush(c);
+}
+
+// The colour buffers and the rgba8 of every filter, and what its launchers share (once the G-buffer is there).
+static int dn_ensure_buffers(crt_ctx *c, size_t n)
+{
+    DN_ENSURE(c, dn_c[0], n);
+    DN_ENSURE(c, dn_c[1], n);
+    DN_ENSURE(c, dn_rgba, n);
+    return CRT_OK;
+}
+
+static DnFilter dn_filter(crt_ctx *c, uint32_t iterations, float sigma_normal, float sigma_plane, bool rgba)
+{
+    return DnFilter{c->dn_gbuf.p, c->dn_key.p, {c->dn_c[0].p, c->dn_c[1].p}, rgba ? c->dn_rgba.p : nullptr, c->tw, c->th, iterations,
+                    sigma_normal, sigma_plane, c->stream};
+}
+
+// ... and last: the readbacks (plane: the filter's own float per pixel), the one synchronise, the dropped-path check.
+static int dn_finish(crt_ctx *c, size_t n, const float4 *res, float *rgb_out, uint8_t *rgba8_out, const float *plane = nullptr,
+                     float *plane_out = nullptr)
+{
+    if (n && rgb_out) HIPCHK(c, hipMemcpyAsync(rgb_out, res, n * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+    if (n && rgba8_out) HIPCHK(c, hipMemcpyAsync(rgba8_out, c->dn_rgba.p, n * sizeof(uchar4), hipMemcpyDeviceToHost, c->stream));
+    if (n && plane_out) HIPCHK(c, hipMemcpyAsync(plane_out, plane, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return wf_check_dropped(c);
+}
+
+static const crt_denoise_params kDnDefaults = {5u, 1.0f, 0.5f, 0.3f};
+
+int crt_denoise(crt_ctx *c, const crt_denoise_params *params, float *rgb_out, uint8_t *rgba8_out)
+{
+    const crt_denoise_params dp = params ? *params : kDnDefaults;
+    const float sig[3] = {dp.sigma_color, dp.sigma_normal, dp.sigma_plane};
+    { int rc = dn_begin(c, "crt_denoise", dp.iterations, sig, 3, "every sigma", DN_UNIFORM); if (rc) return rc; }
+    const size_t n = (size_t)c->tw * c->th;
+    float4 *res = nullptr;
+    if (n) {
+        { int rc = dn_ensure_gbuffer(c); if (rc) return rc; }
+        { int rc = dn_ensure_buffers(c, n); if (rc) return rc; }
+        const DnFilter F = dn_filter(c, dp.iterations, dp.sigma_normal, dp.sigma_plane, rgba8_out != nullptr);
+        HIPCHK(c, dn_launch_filter(F, accum_ptr(c), (float)c->sample, dp.sigma_color, &res));
+    }
+    return dn_finish(c, n, res, rgb_out, rgba8_out);
 }
 
 // The variance-guided filter of the adaptive state.  sigma_variance 8: the best of 1..24 at 16 and 32
@@ -2570,37 +2600,21 @@ int crt_denoise_adaptive_defaults(crt_denoise_adaptive_params *out)
 
 int crt_denoise_adaptive(crt_ctx *c, const crt_denoise_adaptive_params *params, float *rgb_out, uint8_t *rgba8_out, float *var_out)
 {
-    if (!c) return CRT_EINVAL;
     const crt_denoise_adaptive_params dp = params ? *params : kDnAsDefaults;
-    if (dp.iterations > 10u) return fail(c, CRT_EINVAL, "crt_denoise_adaptive: iterations %u > 10", dp.iterations);
     const float sig[3] = {dp.sigma_variance, dp.sigma_normal, dp.sigma_plane};
-    for (float v : sig)
-        if (!(v > 0.0f && v <= 3.40282347e38f)) return fail(c, CRT_EINVAL, "crt_denoise_adaptive: every sigma must be positive and finite");
-    if (!c->as_on)
-        return fail(c, CRT_ESTATE, "crt_denoise_adaptive: the context is in the uniform state (crt_denoise filters a uniform render; "
-                                   "crt_trace_adaptive with min_samples == max_samples gives this filter one)");
-    if (c->as_broken) return as_refuse_broken(c, "crt_denoise_adaptive");
-    { int rc = dn_check_state(c, "crt_denoise_adaptive", true); if (rc) return rc; }
-    HIPCHK(c, hipSetDevice(c->device));
-    { int rc_ = wf_flush(c); if (rc_) return rc_; }
+    { int rc = dn_begin(c, "crt_denoise_adaptive", dp.iterations, sig, 3, "every sigma", DN_ADAPTIVE); if (rc) return rc; }
     const size_t n = (size_t)c->tw * c->th;
+    float4 *res = nullptr;
     if (n) {
         { int rc = dn_ensure_gbuffer(c); if (rc) return rc; }
-        for (int b = 0; b < 2; b++) if (c->dn_c[b].n < n) HIPCHK(c, c->dn_c[b].alloc(n));
-        if (c->dn_rgba.n < n) HIPCHK(c, c->dn_rgba.alloc(n));
-        if (c->dn_kv.n < n) HIPCHK(c, c->dn_kv.alloc(n));
-        if (c->dn_var.n < n) HIPCHK(c, c->dn_var.alloc(n));
-        float4 *res = nullptr;
-        HIPCHK(c, dn_launch_filter_adaptive(accum_ptr(c), c->as_q.p, c->as_counts.p, c->dn_gbuf.p, c->dn_key.p, c->dn_kv.p,
-                                            c->dn_c[0].p, c->dn_c[1].p, rgba8_out ? c->dn_rgba.p : nullptr,
-                                            var_out ? c->dn_var.p : nullptr, c->tw, c->th, dp.iterations, dp.sigma_variance,
-                                            dp.sigma_normal, dp.sigma_plane, &res, c->stream));
-        if (rgb_out) HIPCHK(c, hipMemcpyAsync(rgb_out, res, n * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
-        if (rgba8_out) HIPCHK(c, hipMemcpyAsync(rgba8_out, c->dn_rgba.p, n * sizeof(uchar4), hipMemcpyDeviceToHost, c->stream));
-        if (var_out) HIPCHK(c, hipMemcpyAsync(var_out, c->dn_var.p, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+        { int rc = dn_ensure_buffers(c, n); if (rc) return rc; }
+        DN_ENSURE(c, dn_kv, n);
+        DN_ENSURE(c, dn_var, n);
+        const DnFilter F = dn_filter(c, dp.iterations, dp.sigma_normal, dp.sigma_plane, rgba8_out != nullptr);
+        HIPCHK(c, dn_launch_filter_adaptive(F, accum_ptr(c), c->as_q.p, c->as_counts.p, c->dn_kv.p, var_out ? c->dn_var.p : nullptr,
+                                            dp.sigma_variance, &res));
     }
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return wf_check_dropped(c);
+    return dn_finish(c, n, res, rgb_out, rgba8_out, c->dn_var.p, var_out);
 }
 
 // ---------------------------------------------------------------- temporal reuse
@@ -2652,25 +2666,21 @@ static double th_kappa(const float cam[12], uint32_t W)
 
 int crt_denoise_temporal(crt_ctx *c, const crt_denoise_temporal_params *params, float *rgb_out, uint8_t *rgba8_out, float *history_out)
 {
-    if (!c) return CRT_EINVAL;
     const crt_denoise_temporal_params dp = params ? *params : kDnTpDefaults;
-    if (dp.iterations > 10u) return fail(c, CRT_EINVAL, "crt_denoise_temporal: iterations %u > 10", dp.iterations);
     const float pos[6] = {dp.sigma_color, dp.sigma_normal, dp.sigma_plane, dp.max_history, dp.normal_tol, dp.plane_tol};
-    for (float v : pos)
-        if (!(v > 0.0f && v <= 3.40282347e38f))
-            return fail(c, CRT_EINVAL, "crt_denoise_temporal: every sigma, tolerance and max_history must be positive and finite");
-    if (c->as_on) return as_refuse(c, "crt_denoise_temporal");
-    { int rc = dn_check_state(c, "crt_denoise_temporal"); if (rc) return rc; }
-    HIPCHK(c, hipSetDevice(c->device));
-    { int rc_ = wf_flush(c); if (rc_) return rc_; }
+    { int rc = dn_begin(c, "crt_denoise_temporal", dp.iterations, pos, 6, "every sigma, tolerance and max_history", DN_UNIFORM);
+      if (rc) return rc; }
     const size_t n = (size_t)c->tw * c->th;
+    float4 *res = nullptr;
+    std::vector<float> hw;                                       // (rgb_out's channel 3 is Hw: the filter passes leave it 0)
+    if (rgb_out && dp.iterations > 0 && !history_out) hw.resize(n);
+    float *hw_host = history_out ? history_out : hw.empty() ? nullptr : hw.data();
     if (n) {
         // every buffer first: a failed allocation leaves the slots as they were
-        if (c->th_cur_c.n < n) HIPCHK(c, c->th_cur_c.alloc(n));
-        if (c->th_prev.c.n < n) HIPCHK(c, c->th_prev.c.alloc(n));
-        for (int b = 0; b < 2; b++) if (c->dn_c[b].n < n) HIPCHK(c, c->dn_c[b].alloc(n));
-        if (c->dn_rgba.n < n) HIPCHK(c, c->dn_rgba.alloc(n));
-        if (c->th_hist.n < n) HIPCHK(c, c->th_hist.alloc(n));
+        DN_ENSURE(c, th_cur_c, n);
+        DN_ENSURE(c, th_prev.c, n);
+        { int rc = dn_ensure_buffers(c, n); if (rc) return rc; }
+        DN_ENSURE(c, th_hist, n);
         // the first call of a new frame: CURRENT becomes PREVIOUS, by pointer
         if (c->th_cur_valid && c->th_cur_frame != c->frame_id) {
             if (c->th_parked) {
@@ -2715,38 +2725,27 @@ int crt_denoise_temporal(crt_ctx *c, const crt_denoise_temporal_params *params, 
         P.max_history = dp.max_history;
         P.normal_tol2 = (float)std::min(3.0e38, (double)dp.normal_tol * dp.normal_tol);
         P.plane_tol = dp.plane_tol;
-        float4 *res = nullptr;
-        HIPCHK(c, dn_launch_temporal(P, c->dn_gbuf.p, c->dn_key.p, c->dn_c[0].p, c->dn_c[1].p, rgba8_out ? c->dn_rgba.p : nullptr,
-                                     dp.iterations, dp.sigma_color, dp.sigma_normal, dp.sigma_plane, &res, c->stream));
+        const DnFilter F = dn_filter(c, dp.iterations, dp.sigma_normal, dp.sigma_plane, rgba8_out != nullptr);
+        HIPCHK(c, dn_launch_temporal(F, P, dp.sigma_color, &res));
         std::memcpy(c->th_cur_cam, c->sc.cam, sizeof c->th_cur_cam);
         c->th_cur_valid = true; c->th_cur_frame = c->frame_id; c->th_gen = c->dn_gen; c->th_parked = false;
-        std::vector<float> hw;                                   // (rgb_out's channel 3 is Hw: the filter passes leave it 0)
-        if (rgb_out && dp.iterations > 0 && !history_out) hw.resize(n);
-        float *hw_host = history_out ? history_out : hw.empty() ? nullptr : hw.data();
-        if (rgb_out) HIPCHK(c, hipMemcpyAsync(rgb_out, res, n * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
-        if (rgba8_out) HIPCHK(c, hipMemcpyAsync(rgba8_out, c->dn_rgba.p, n * sizeof(uchar4), hipMemcpyDeviceToHost, c->stream));
-        if (hw_host) HIPCHK(c, hipMemcpyAsync(hw_host, c->th_hist.p, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        if (rgb_out && dp.iterations > 0)
-            for (size_t i = 0; i < n; i++) rgb_out[4 * i + 3] = hw_host[i];
     }
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return wf_check_dropped(c);
+    const int rc = dn_finish(c, n, res, rgb_out, rgba8_out, c->th_hist.p, hw_host);
+    if (rgb_out && dp.iterations > 0)
+        for (size_t i = 0; i < n; i++) rgb_out[4 * i + 3] = hw_host[i];
+    return rc;
 }
 
 int crt_read_gbuffer(crt_ctx *c, float *out)
 {
     if (!c || !out) return CRT_EINVAL;
-    { int rc = dn_check_state(c, "crt_read_gbuffer"); if (rc) return rc; }
-    HIPCHK(c, hipSetDevice(c->device));
-    { int rc_ = wf_flush(c); if (rc_) return rc_; }
+    { int rc = dn_begin(c, "crt_read_gbuffer", 0, nullptr, 0, "", DN_EITHER); if (rc) return rc; }
     const size_t n = (size_t)c->tw * c->th;
     if (n) {
         { int rc = dn_ensure_gbuffer(c); if (rc) return rc; }
         HIPCHK(c, hipMemcpyAsync(out, c->dn_gbuf.p, n * 2 * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
     }
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return wf_check_dropped(c);
+    return dn_finish(c, n, nullptr, nullptr, nullptr);
 }
 
 int crt_debug_intersect(crt_ctx *c, const float *rays, size_t n, float *out)

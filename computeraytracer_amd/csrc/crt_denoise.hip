@@ -78,31 +78,62 @@ __global__ __launch_bounds__(256) void k_dn_prepare(const float4 *__restrict__ a
     if (rgba) rgba[i] = linear_rgb_to_rgba8(rgb);
 }
 
-__device__ __forceinline__ bool finite4(float4 c)
+constexpr float kDnMaxFinite = 3.40282347e38f;                  // v is finite where |v| <= this (false for a NaN)
+__device__ __forceinline__ bool dn_finite(float v) { return abs_(v) <= kDnMaxFinite; }
+__device__ __forceinline__ bool finite4(float4 c) { return dn_finite(c.x) && dn_finite(c.y) && dn_finite(c.z); }
+
+// ---------------------------------------------------------------- what the a-trous kernels share
+// The pixel of a thread where block -> 16x16 pixels: grid (ceil(tw/16), ceil(th/16)) blocks of 256 threads.
+__device__ __forceinline__ int dn_x16() { return (int)(blockIdx.x * 16u + (threadIdx.x & 15u)); }
+__device__ __forceinline__ int dn_y16() { return (int)(blockIdx.y * 16u + (threadIdx.x >> 4)); }
+
+// The B3 spline (1, 4, 6, 4, 1) / 16 at tap i + 2.
+__device__ __forceinline__ float dn_h(int i)
 {
-    return abs_(c.x) <= 3.40282347e38f && abs_(c.y) <= 3.40282347e38f && abs_(c.z) <= 3.40282347e38f;
+    const float h[5] = {1.0f / 16.0f, 1.0f / 4.0f, 3.0f / 8.0f, 1.0f / 4.0f, 1.0f / 16.0f};
+    return h[i];
 }
 
-// One a-trous iteration: grid (ceil(tw/16), ceil(th/16)) blocks of 256 threads, block -> 16x16 pixels.  Taps at
-// step * (-2..2)^2 inside the tile; the centre pixel's guides stay in registers, a tap's guides are fetched only when
-// its key matches.
+// The centre pixel's guides: position and normal (zeros at a miss, where no tap reads them).
+struct DnGuides { f3 x, n; };
+__device__ __forceinline__ DnGuides dn_centre_guides(const float4 *gbuf, size_t p, bool hit)
+{
+    f3 x_p = f3{0, 0, 0}, n_p = f3{0, 0, 0};
+    if (hit) {
+        const float4 g0 = gbuf[2 * p], g1 = gbuf[2 * p + 1];
+        x_p = f3{g0.y, g0.z, g0.w};
+        n_p = f3{g1.x, g1.y, g1.z};
+    }
+    return DnGuides{x_p, n_p};
+}
+
+// e plus the normal and plane terms of tap q against the centre's guides.
+__device__ __forceinline__ float dn_guide_term(float e, const float4 *gbuf, size_t q, f3 n_p, f3 x_p, float inv_n, float inv_x)
+{
+    const float4 g0 = gbuf[2 * q], g1 = gbuf[2 * q + 1];
+    const f3 dn = n_p - f3{g1.x, g1.y, g1.z};
+    e = e + dot(dn, dn) * inv_n;
+    const f3 v = f3{g0.y, g0.z, g0.w} - x_p;
+    // (length > 0, not v != 0: positions ~1e-24 apart give v != 0 with dot(v, v) = 0, and 0 / 0 = NaN)
+    const float len = length(v);
+    if (len > 0.0f) e = e + (abs_(dot(n_p, v)) / len) * inv_x;
+    return e;
+}
+
+// One a-trous iteration (grid: dn_x16).  Taps at step * (-2..2)^2 inside the tile; the centre pixel's guides stay in
+// registers, a tap's guides are fetched only when its key matches.
 __global__ __launch_bounds__(256) void k_dn_atrous(const DnParams P)
 {
-    const int x = (int)(blockIdx.x * 16u + (threadIdx.x & 15u)), y = (int)(blockIdx.y * 16u + (threadIdx.x >> 4));
+    const int x = dn_x16(), y = dn_y16();
     const int tw = (int)P.tw, th = (int)P.th, s = (int)P.step;
     if (x >= tw || y >= th) return;
     const size_t p = (size_t)y * P.tw + (size_t)x;
     const uint32_t key_p = P.key[p];
     const bool hit = key_p != kNoHit;
-    f3 x_p = f3{0, 0, 0}, n_p = f3{0, 0, 0};
-    if (hit) {
-        const float4 g0 = P.gbuf[2 * p], g1 = P.gbuf[2 * p + 1];
-        x_p = f3{g0.y, g0.z, g0.w};
-        n_p = f3{g1.x, g1.y, g1.z};
-    }
+    const DnGuides g_p = dn_centre_guides(P.gbuf, p, hit);
+    const f3 x_p = g_p.x, n_p = g_p.n;
     const float4 cp4 = P.c_in[p];
     const f3 t_p = dn_display(cp4);
-    const float h[5] = {1.0f / 16.0f, 1.0f / 4.0f, 3.0f / 8.0f, 1.0f / 4.0f, 1.0f / 16.0f};
     float sw = 0.0f;
     f3 sc = f3{0, 0, 0};
 #pragma unroll
@@ -114,8 +145,8 @@ __global__ __launch_bounds__(256) void k_dn_atrous(const DnParams P)
             const int qx = x + dx * s;
             if (qx < 0 || qx >= tw) continue;
             if (dx == 0 && dy == 0) {                       // the centre: weight h[2]^2, every other factor is 1
-                sw = sw + h[2] * h[2];
-                sc = sc + f3{cp4.x, cp4.y, cp4.z} * (h[2] * h[2]);
+                sw = sw + dn_h(2) * dn_h(2);
+                sc = sc + f3{cp4.x, cp4.y, cp4.z} * (dn_h(2) * dn_h(2));
                 continue;
             }
             const size_t q = (size_t)qy * P.tw + (size_t)qx;
@@ -125,16 +156,8 @@ __global__ __launch_bounds__(256) void k_dn_atrous(const DnParams P)
             // (recomputed per tap: a stored dn_display(c) costs another 16 B per tap, and the pass is bound by tap traffic)
             const f3 dt = t_p - dn_display(cq4);
             float e = dot(dt, dt) * P.inv_c;
-            if (hit) {
-                const float4 g0 = P.gbuf[2 * q], g1 = P.gbuf[2 * q + 1];
-                const f3 dn = n_p - f3{g1.x, g1.y, g1.z};
-                e = e + dot(dn, dn) * P.inv_n;
-                const f3 v = f3{g0.y, g0.z, g0.w} - x_p;
-                // (length > 0, not v != 0: positions ~1e-24 apart give v != 0 with dot(v, v) = 0, and 0 / 0 = NaN)
-                const float len = length(v);
-                if (len > 0.0f) e = e + (abs_(dot(n_p, v)) / len) * P.inv_x;
-            }
-            const float w = (h[dx + 2] * h[dy + 2]) * exp_(-e);
+            if (hit) e = dn_guide_term(e, P.gbuf, q, n_p, x_p, P.inv_n, P.inv_x);
+            const float w = (dn_h(dx + 2) * dn_h(dy + 2)) * exp_(-e);
             sw = sw + w;
             sc = sc + f3{cq4.x, cq4.y, cq4.z} * w;
         }
@@ -179,7 +202,7 @@ __global__ __launch_bounds__(256) void k_dn_prepare_as(const float4 *__restrict_
     if (n_t >= 2u) {
         const float e = pixel_error(a.y, q[i], n_t);
         const float ee = e * e;
-        if (ee <= 3.40282347e38f) v = ee;
+        if (ee <= kDnMaxFinite) v = ee;
     }
     c[i] = float4{rgb.x, rgb.y, rgb.z, v};
     if (rgba) rgba[i] = linear_rgb_to_rgba8(rgb);
@@ -191,7 +214,7 @@ __global__ __launch_bounds__(256) void k_dn_prepare_as(const float4 *__restrict_
 __global__ __launch_bounds__(256) void k_dn_vblur(const float4 *__restrict__ c, const uint32_t *__restrict__ key,
                                                   uint2 *__restrict__ kv, uint32_t utw, uint32_t uth)
 {
-    const int x = (int)(blockIdx.x * 16u + (threadIdx.x & 15u)), y = (int)(blockIdx.y * 16u + (threadIdx.x >> 4));
+    const int x = dn_x16(), y = dn_y16();
     const int tw = (int)utw, th = (int)uth;
     if (x >= tw || y >= th) return;
     const size_t p = (size_t)y * utw + (size_t)x;
@@ -220,7 +243,7 @@ __global__ __launch_bounds__(256) void k_dn_vblur(const float4 *__restrict__ c, 
 // through the same weights.
 __global__ __launch_bounds__(256) void k_dn_atrous_as(const DnAsParams P)
 {
-    const int x = (int)(blockIdx.x * 16u + (threadIdx.x & 15u)), y = (int)(blockIdx.y * 16u + (threadIdx.x >> 4));
+    const int x = dn_x16(), y = dn_y16();
     const int tw = (int)P.tw, th = (int)P.th, s = (int)P.step;
     if (x >= tw || y >= th) return;
     const size_t p = (size_t)y * P.tw + (size_t)x;
@@ -228,15 +251,10 @@ __global__ __launch_bounds__(256) void k_dn_atrous_as(const DnAsParams P)
     const uint32_t key_p = kv_p.x;
     const float vt_p = bits_f(kv_p.y);
     const bool hit = key_p != kNoHit;
-    f3 x_p = f3{0, 0, 0}, n_p = f3{0, 0, 0};
-    if (hit) {
-        const float4 g0 = P.gbuf[2 * p], g1 = P.gbuf[2 * p + 1];
-        x_p = f3{g0.y, g0.z, g0.w};
-        n_p = f3{g1.x, g1.y, g1.z};
-    }
+    const DnGuides g_p = dn_centre_guides(P.gbuf, p, hit);
+    const f3 x_p = g_p.x, n_p = g_p.n;
     const float4 cp4 = P.c_in[p];
     const f3 t_p = dn_display(cp4);
-    const float h[5] = {1.0f / 16.0f, 1.0f / 4.0f, 3.0f / 8.0f, 1.0f / 4.0f, 1.0f / 16.0f};
     float sw = 0.0f, sv = 0.0f;
     f3 sc = f3{0, 0, 0};
 #pragma unroll
@@ -248,7 +266,7 @@ __global__ __launch_bounds__(256) void k_dn_atrous_as(const DnAsParams P)
             const int qx = x + dx * s;
             if (qx < 0 || qx >= tw) continue;
             if (dx == 0 && dy == 0) {
-                const float w = h[2] * h[2];
+                const float w = dn_h(2) * dn_h(2);
                 sw = sw + w;
                 sc = sc + f3{cp4.x, cp4.y, cp4.z} * w;
                 sv = sv + (w * w) * cp4.w;
@@ -261,15 +279,8 @@ __global__ __launch_bounds__(256) void k_dn_atrous_as(const DnAsParams P)
             if (!finite4(cq4)) continue;
             const f3 dt = t_p - dn_display(cq4);
             float e = dot(dt, dt) / (P.sv2 * (vt_p + bits_f(kv_q.y)) + kDnEps);
-            if (hit) {
-                const float4 g0 = P.gbuf[2 * q], g1 = P.gbuf[2 * q + 1];
-                const f3 dn = n_p - f3{g1.x, g1.y, g1.z};
-                e = e + dot(dn, dn) * P.inv_n;
-                const f3 v = f3{g0.y, g0.z, g0.w} - x_p;
-                const float len = length(v);
-                if (len > 0.0f) e = e + (abs_(dot(n_p, v)) / len) * P.inv_x;
-            }
-            const float w = (h[dx + 2] * h[dy + 2]) * exp_(-e);
+            if (hit) e = dn_guide_term(e, P.gbuf, q, n_p, x_p, P.inv_n, P.inv_x);
+            const float w = (dn_h(dx + 2) * dn_h(dy + 2)) * exp_(-e);
             sw = sw + w;
             sc = sc + f3{cq4.x, cq4.y, cq4.z} * w;
             sv = sv + (w * w) * cq4.w;
@@ -290,7 +301,7 @@ __global__ __launch_bounds__(256) void k_dn_atrous_as(const DnAsParams P)
 // pixel's own guides stay in registers; a tap's history and G-buffer are fetched only when its key matches.
 __global__ __launch_bounds__(256) void k_dn_reproject(const DnReprojParams P)
 {
-    const int x = (int)(blockIdx.x * 16u + (threadIdx.x & 15u)), y = (int)(blockIdx.y * 16u + (threadIdx.x >> 4));
+    const int x = dn_x16(), y = dn_y16();
     const int tw = (int)P.tw, th = (int)P.th;
     if (x >= tw || y >= th) return;
     const size_t p = (size_t)y * P.tw + (size_t)x;
@@ -357,37 +368,7 @@ __global__ __launch_bounds__(256) void k_dn_reproject(const DnReprojParams P)
     if (P.hist) P.hist[p] = Hw;
 }
 
-// ---------------------------------------------------------------- launchers (called from crt_api.cpp)
-// The blend into P.h_cur, then `iterations` passes of k_dn_atrous reading h_cur first and ping-ponging between c0 and
-// c1 (h_cur itself stays unfiltered: it is the next frame's history).  The last launch writes rgba.
-hipError_t dn_launch_temporal(DnReprojParams P, const float4 *gbuf, const uint32_t *key, float4 *c0, float4 *c1, uchar4 *rgba,
-                              uint32_t iterations, float sigma_color, float sigma_normal, float sigma_plane, float4 **out,
-                              hipStream_t stream)
-{
-    const uint32_t tw = P.tw, th = P.th;
-    *out = P.h_cur;
-    if ((size_t)tw * th == 0) return hipSuccess;
-    const dim3 grid((tw + 15u) / 16u, (th + 15u) / 16u);
-    P.rgba = iterations == 0 ? rgba : nullptr;
-    hipLaunchKernelGGL(k_dn_reproject, grid, dim3(256), 0, stream, P);
-    hipError_t e = hipGetLastError();
-    float4 *buf[2] = {c0, c1};
-    for (uint32_t i = 0; i < iterations && e == hipSuccess; i++) {
-        DnParams A{};
-        A.c_in = i == 0 ? P.h_cur : buf[(i + 1u) & 1u]; A.c_out = buf[i & 1u];
-        A.gbuf = gbuf; A.key = key;
-        A.rgba = i + 1u == iterations ? rgba : nullptr;
-        A.tw = tw; A.th = th; A.step = 1u << i;
-        A.inv_c = (float)std::min(3.0e38, (double)(1u << i) / ((double)sigma_color * sigma_color));
-        A.inv_n = (float)std::min(3.0e38, 1.0 / ((double)sigma_normal * sigma_normal));
-        A.inv_x = (float)std::min(3.0e38, 1.0 / (double)sigma_plane);
-        hipLaunchKernelGGL(k_dn_atrous, grid, dim3(256), 0, stream, A);
-        e = hipGetLastError();
-        *out = A.c_out;
-    }
-    return e;
-}
-
+// ---------------------------------------------------------------- launchers (called from crt_api.cpp; DnFilter: crt_device.h)
 hipError_t dn_launch_gbuffer(const DevScene &S, uint32_t x0, uint32_t y0, uint32_t tw, uint32_t th, float4 *gbuf, uint32_t *key,
                              int brute, hipStream_t stream)
 {
@@ -397,66 +378,88 @@ hipError_t dn_launch_gbuffer(const DevScene &S, uint32_t x0, uint32_t y0, uint32
     return hipGetLastError();
 }
 
-// accum -> c[0], then `iterations` filter passes ping-ponging between c[0] and c[1]; the last launch also writes rgba.
-// Returns the buffer that holds the result through *out.
-hipError_t dn_launch_filter(const float4 *accum, float n, const float4 *gbuf, const uint32_t *key, float4 *c0, float4 *c1,
-                            uchar4 *rgba, uint32_t tw, uint32_t th, uint32_t iterations, float sigma_color, float sigma_normal,
-                            float sigma_plane, float4 **out, hipStream_t stream)
+static dim3 dn_grid16(const DnFilter &F) { return dim3((F.tw + 15u) / 16u, (F.th + 15u) / 16u); }
+
+// (clamped to finite: 0 * inv must stay 0 for a tiny sigma)
+static float dn_clamped(double v) { return (float)std::min(3.0e38, v); }
+
+static void dn_guide_sigmas(const DnFilter &F, float &inv_n, float &inv_x)
 {
-    const size_t npix = (size_t)tw * th;
-    *out = c0;
-    if (npix == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_dn_prepare, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, stream, accum, n, c0,
-                       iterations == 0 ? rgba : nullptr, npix);
-    hipError_t e = hipGetLastError();
-    float4 *buf[2] = {c0, c1};
-    for (uint32_t i = 0; i < iterations && e == hipSuccess; i++) {
+    inv_n = dn_clamped(1.0 / ((double)F.sigma_normal * F.sigma_normal));
+    inv_x = dn_clamped(1.0 / (double)F.sigma_plane);
+}
+
+// F.iterations passes of k_dn_atrous: the first reads `first`, each writes the buffer of F.c that it does not read
+// (F.c[0] where `first` is neither), and the last also writes rgba.  Leaves the buffer that holds the result in *out.
+static hipError_t dn_run_atrous(const DnFilter &F, float4 *first, float sigma_color, float4 **out)
+{
+    hipError_t e = hipSuccess;
+    *out = first;
+    for (uint32_t i = 0; i < F.iterations && e == hipSuccess; i++) {
         DnParams P{};
-        P.c_in = buf[i & 1u]; P.c_out = buf[(i + 1u) & 1u];
-        P.gbuf = gbuf; P.key = key;
-        P.rgba = i + 1u == iterations ? rgba : nullptr;
-        P.tw = tw; P.th = th; P.step = 1u << i;
-        // (clamped to finite: 0 * inv must stay 0 for a tiny sigma)
-        P.inv_c = (float)std::min(3.0e38, (double)(1u << i) / ((double)sigma_color * sigma_color));
-        P.inv_n = (float)std::min(3.0e38, 1.0 / ((double)sigma_normal * sigma_normal));
-        P.inv_x = (float)std::min(3.0e38, 1.0 / (double)sigma_plane);
-        hipLaunchKernelGGL(k_dn_atrous, dim3((tw + 15u) / 16u, (th + 15u) / 16u), dim3(256), 0, stream, P);
+        P.c_in = *out; P.c_out = F.c[*out == F.c[0] ? 1 : 0];
+        P.gbuf = F.gbuf; P.key = F.key;
+        P.rgba = i + 1u == F.iterations ? F.rgba : nullptr;
+        P.tw = F.tw; P.th = F.th; P.step = 1u << i;
+        P.inv_c = dn_clamped((double)(1u << i) / ((double)sigma_color * sigma_color));
+        dn_guide_sigmas(F, P.inv_n, P.inv_x);
+        hipLaunchKernelGGL(k_dn_atrous, dn_grid16(F), dim3(256), 0, F.stream, P);
         e = hipGetLastError();
         *out = P.c_out;
     }
     return e;
 }
 
+// accum -> c[0], then the passes between c[0] and c[1].
+hipError_t dn_launch_filter(const DnFilter &F, const float4 *accum, float n, float sigma_color, float4 **out)
+{
+    const size_t npix = (size_t)F.tw * F.th;
+    *out = F.c[0];
+    if (npix == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_dn_prepare, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, F.stream, accum, n, F.c[0],
+                       F.iterations == 0 ? F.rgba : nullptr, npix);
+    const hipError_t e = hipGetLastError();
+    return e != hipSuccess ? e : dn_run_atrous(F, F.c[0], sigma_color, out);
+}
+
+// The blend into P.h_cur, then the passes reading h_cur first and writing c[0], c[1], ... (h_cur itself stays
+// unfiltered: it is the next frame's history).
+hipError_t dn_launch_temporal(const DnFilter &F, DnReprojParams P, float sigma_color, float4 **out)
+{
+    *out = P.h_cur;
+    if ((size_t)F.tw * F.th == 0) return hipSuccess;
+    P.rgba = F.iterations == 0 ? F.rgba : nullptr;
+    hipLaunchKernelGGL(k_dn_reproject, dn_grid16(F), dim3(256), 0, F.stream, P);
+    const hipError_t e = hipGetLastError();
+    return e != hipSuccess ? e : dn_run_atrous(F, P.h_cur, sigma_color, out);
+}
+
 // The adaptive state's filter: (accum, q, counts) -> c[0] with v in w, then per iteration the variance blur into kv and
 // the filter pass between c[0] and c[1]; the last launch also writes rgba and var (either may be null).
-hipError_t dn_launch_filter_adaptive(const float4 *accum, const float *q, const uint32_t *counts, const float4 *gbuf,
-                                     const uint32_t *key, uint2 *kv, float4 *c0, float4 *c1, uchar4 *rgba, float *var,
-                                     uint32_t tw, uint32_t th, uint32_t iterations, float sigma_variance, float sigma_normal,
-                                     float sigma_plane, float4 **out, hipStream_t stream)
+hipError_t dn_launch_filter_adaptive(const DnFilter &F, const float4 *accum, const float *q, const uint32_t *counts, uint2 *kv,
+                                     float *var, float sigma_variance, float4 **out)
 {
-    *out = c0;
+    const uint32_t tw = F.tw, th = F.th;
+    *out = F.c[0];
     if ((size_t)tw * th == 0) return hipSuccess;
-    const bool last0 = iterations == 0;
-    hipLaunchKernelGGL(k_dn_prepare_as, dim3((tw + 63u) / 64u, (th + 3u) / 4u), dim3(256), 0, stream, accum, q, counts, tw, th,
-                       (tw + 7u) / 8u, c0, last0 ? rgba : nullptr, last0 ? var : nullptr);
+    const bool last0 = F.iterations == 0;
+    hipLaunchKernelGGL(k_dn_prepare_as, dim3((tw + 63u) / 64u, (th + 3u) / 4u), dim3(256), 0, F.stream, accum, q, counts, tw, th,
+                       (tw + 7u) / 8u, F.c[0], last0 ? F.rgba : nullptr, last0 ? var : nullptr);
     hipError_t e = hipGetLastError();
-    float4 *buf[2] = {c0, c1};
-    const dim3 grid((tw + 15u) / 16u, (th + 15u) / 16u);
-    for (uint32_t i = 0; i < iterations && e == hipSuccess; i++) {
+    for (uint32_t i = 0; i < F.iterations && e == hipSuccess; i++) {
         DnAsParams P{};
-        P.c_in = buf[i & 1u]; P.c_out = buf[(i + 1u) & 1u];
-        P.gbuf = gbuf; P.kv = kv;
-        const bool last = i + 1u == iterations;
-        P.rgba = last ? rgba : nullptr;
+        P.c_in = F.c[i & 1u]; P.c_out = F.c[(i + 1u) & 1u];
+        P.gbuf = F.gbuf; P.kv = kv;
+        const bool last = i + 1u == F.iterations;
+        P.rgba = last ? F.rgba : nullptr;
         P.var = last ? var : nullptr;
         P.tw = tw; P.th = th; P.step = 1u << i;
-        P.sv2 = (float)std::min(3.0e38, (double)sigma_variance * sigma_variance);
-        P.inv_n = (float)std::min(3.0e38, 1.0 / ((double)sigma_normal * sigma_normal));
-        P.inv_x = (float)std::min(3.0e38, 1.0 / (double)sigma_plane);
-        hipLaunchKernelGGL(k_dn_vblur, grid, dim3(256), 0, stream, P.c_in, key, kv, tw, th);
+        P.sv2 = dn_clamped((double)sigma_variance * sigma_variance);
+        dn_guide_sigmas(F, P.inv_n, P.inv_x);
+        hipLaunchKernelGGL(k_dn_vblur, dn_grid16(F), dim3(256), 0, F.stream, P.c_in, F.key, kv, tw, th);
         e = hipGetLastError();
         if (e != hipSuccess) break;
-        hipLaunchKernelGGL(k_dn_atrous_as, grid, dim3(256), 0, stream, P);
+        hipLaunchKernelGGL(k_dn_atrous_as, dn_grid16(F), dim3(256), 0, F.stream, P);
         e = hipGetLastError();
         *out = P.c_out;
     }

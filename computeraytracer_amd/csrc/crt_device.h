@@ -260,4 +260,23 @@ struct DnReprojParams {
     float max_history, normal_tol2, plane_tol;
 };
 
+// What the launchers of the three preview filters share (crt_denoise.hip).
+struct DnFilter {
+    const float4 *gbuf;             // the guides: G-buffer and keys of the tile
+    const uint32_t *key;
+    float4 *c[2];                   // the colour buffers the passes alternate between
+    uchar4 *rgba;                   // null, or where the last launch writes the result's rgba8
+    uint32_t tw, th, iterations;
+    float sigma_normal, sigma_plane;
+    hipStream_t stream;
+};
+
+hipError_t dn_launch_gbuffer(const DevScene &S, uint32_t x0, uint32_t y0, uint32_t tw, uint32_t th, float4 *gbuf, uint32_t *key,
+                             int brute, hipStream_t stream);
+// (each leaves the buffer that holds the result in *out)
+hipError_t dn_launch_filter(const DnFilter &F, const float4 *accum, float n, float sigma_color, float4 **out);
+hipError_t dn_launch_filter_adaptive(const DnFilter &F, const float4 *accum, const float *q, const uint32_t *counts, uint2 *kv,
+                                     float *var, float sigma_variance, float4 **out);
+hipError_t dn_launch_temporal(const DnFilter &F, DnReprojParams P, float sigma_color, float4 **out);
+
 }  // namespace crt

@@ -239,16 +239,30 @@ class Renderer:
         return self
 
     # -- denoised preview (include/crt.h, "Denoised preview")
+    def _denoise(self, call, p, overrides: dict, rgb: bool, plane: bool | None = None):
+        """One filter call.  The overrides that are not None replace fields of the parameter struct p, as the field's
+        type.  Returns rgba8, or a tuple of it, the linear rgb (rgb) and the filter's own float plane (plane; None: the
+        call has none)."""
+        _, _, tw, th = self.tile
+        for k, v in overrides.items():
+            if v is not None:
+                setattr(p, k, type(getattr(p, k))(v))
+        rgba = np.empty((th, tw, 4), np.uint8)
+        lin = np.empty((th, tw, 4), np.float32) if rgb else None
+        extra = np.empty((th, tw), np.float32) if plane else None
+        args = [lin.ctypes.data if rgb else None, rgba.ctypes.data]
+        if plane is not None:
+            args.append(extra.ctypes.data if plane else None)
+        self._chk(call(self._h, C.byref(p), *args))
+        out = tuple(a for a in (rgba, lin, extra) if a is not None)
+        return out if len(out) > 1 else rgba
+
     def denoise(self, iterations: int = 5, sigma_color: float = 1.0, sigma_normal: float = 0.5,
                 sigma_plane: float = 0.3, rgb: bool = False):
         """The edge-aware a-trous filter of the accumulator's average: rgba8 (H, W, 4), or (rgba8, linear rgb
         (H, W, 4) float32, channel 3 = pad) with rgb=True.  Reads the accumulator only; finishes what is in flight."""
-        _, _, tw, th = self.tile
-        p = _lib.DenoiseParams(int(iterations), float(sigma_color), float(sigma_normal), float(sigma_plane))
-        rgba = np.empty((th, tw, 4), np.uint8)
-        lin = np.empty((th, tw, 4), np.float32) if rgb else None
-        self._chk(self._lib.crt_denoise(self._h, C.byref(p), lin.ctypes.data if rgb else None, rgba.ctypes.data))
-        return (rgba, lin) if rgb else rgba
+        return self._denoise(self._lib.crt_denoise, _lib.DenoiseParams(), dict(
+            iterations=iterations, sigma_color=sigma_color, sigma_normal=sigma_normal, sigma_plane=sigma_plane), rgb)
 
     def denoise_adaptive(self, iterations: int | None = None, sigma_variance: float | None = None,
                          sigma_normal: float | None = None, sigma_plane: float | None = None, rgb: bool = False,
@@ -257,20 +271,8 @@ class Renderer:
         render"): rgba8 (H, W, 4); with rgb=True also linear rgb (H, W, 4) float32 (channel 3 = the variance), with
         var=True also the variance left after filtering (H, W) float32 -- a tuple in that order.  A parameter left out
         takes the library's default (crt_denoise_adaptive_defaults).  Reads only; finishes what is in flight."""
-        _, _, tw, th = self.tile
-        p = _lib.denoise_adaptive_defaults()
-        if iterations is not None:
-            p.iterations = int(iterations)
-        for k, v in (("sigma_variance", sigma_variance), ("sigma_normal", sigma_normal), ("sigma_plane", sigma_plane)):
-            if v is not None:
-                setattr(p, k, float(v))
-        rgba = np.empty((th, tw, 4), np.uint8)
-        lin = np.empty((th, tw, 4), np.float32) if rgb else None
-        vout = np.empty((th, tw), np.float32) if var else None
-        self._chk(self._lib.crt_denoise_adaptive(self._h, C.byref(p), lin.ctypes.data if rgb else None, rgba.ctypes.data,
-                                                 vout.ctypes.data if var else None))
-        out = (rgba,) + ((lin,) if rgb else ()) + ((vout,) if var else ())
-        return out if len(out) > 1 else rgba
+        return self._denoise(self._lib.crt_denoise_adaptive, _lib.denoise_adaptive_defaults(), dict(
+            iterations=iterations, sigma_variance=sigma_variance, sigma_normal=sigma_normal, sigma_plane=sigma_plane), rgb, bool(var))
 
     # -- temporal reuse (include/crt.h, "Sample offset" and "Temporal reuse across camera moves")
     def set_sample_offset(self, offset: int):
@@ -292,21 +294,9 @@ class Renderer:
         rgb=True also linear rgb (H, W, 4) float32 (channel 3 = the history weight Hw in samples), with history=True
         also Hw (H, W) float32 -- a tuple in that order.  A parameter left out takes the library's default
         (crt_denoise_temporal_defaults).  Reads the accumulator only; finishes what is in flight."""
-        _, _, tw, th = self.tile
-        p = _lib.denoise_temporal_defaults()
-        if iterations is not None:
-            p.iterations = int(iterations)
-        for k, v in (("sigma_color", sigma_color), ("sigma_normal", sigma_normal), ("sigma_plane", sigma_plane),
-                     ("max_history", max_history), ("normal_tol", normal_tol), ("plane_tol", plane_tol)):
-            if v is not None:
-                setattr(p, k, float(v))
-        rgba = np.empty((th, tw, 4), np.uint8)
-        lin = np.empty((th, tw, 4), np.float32) if rgb else None
-        hw = np.empty((th, tw), np.float32) if history else None
-        self._chk(self._lib.crt_denoise_temporal(self._h, C.byref(p), lin.ctypes.data if rgb else None, rgba.ctypes.data,
-                                                 hw.ctypes.data if history else None))
-        out = (rgba,) + ((lin,) if rgb else ()) + ((hw,) if history else ())
-        return out if len(out) > 1 else rgba
+        return self._denoise(self._lib.crt_denoise_temporal, _lib.denoise_temporal_defaults(), dict(
+            iterations=iterations, sigma_color=sigma_color, sigma_normal=sigma_normal, sigma_plane=sigma_plane,
+            max_history=max_history, normal_tol=normal_tol, plane_tol=plane_tol), rgb, bool(history))
 
     def temporal_reset(self):
         """Drop the history: the next denoise_temporal equals denoise."""
