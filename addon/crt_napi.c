@@ -672,6 +672,24 @@ static napi_value js_read_gbuffer(napi_env env, napi_callback_info info)
     return ta;
 }
 
+/* readMotion(h) -> Float32Array (tw*th*2): per pixel the film position (u, v) where the last denoiseTemporal looked for
+ * it in the previous frame, NaN where there is none (include/crt.h crt_read_motion). */
+static napi_value js_read_motion(napi_env env, napi_callback_info info)
+{
+    ARGS(1)
+    crt_ctx *ctx = get_ctx(env, argv[0]);
+    if (!ctx) return NULL;
+    uint32_t tl[4];
+    CRT_CHECK(env, ctx, "crt_tile", crt_tile(ctx, tl));
+    size_t px = (size_t)tl[2] * tl[3];
+    void *data = NULL;
+    napi_value ab, ta;
+    NAPI_OK(env, napi_create_arraybuffer(env, px * 8, &data, &ab));
+    CRT_CHECK(env, ctx, "crt_read_motion", crt_read_motion(ctx, (float *)data));
+    NAPI_OK(env, napi_create_typedarray(env, napi_float32_array, px * 2, ab, 0, &ta));
+    return ta;
+}
+
 /* ------------------------------------------------------------------ scene edits (include/crt.h "Scene edits")
  * setCamera(h, camera: 16 floats), updatePrimitives(h, first, records: k*80 B), updateLights(h, first, records),
  * refitAccel(h) -> true when the tree had to be rebuilt. */
@@ -1143,7 +1161,7 @@ static napi_value init(napi_env env, napi_value exports)
         {"readFrameRgba8", js_read_frame_rgba8}, {"readFrameAccum", js_read_frame_accum}, {"imageSize", js_image_size},
         {"setRowBands", js_set_row_bands}, {"deviceBuffers", js_device_buffers}, {"frameDeviceBuffers", js_frame_device_buffers},
         {"bindOutput", js_bind_output}, {"setStream", js_set_stream},
-        {"denoise", js_denoise}, {"readGbuffer", js_read_gbuffer},
+        {"denoise", js_denoise}, {"readGbuffer", js_read_gbuffer}, {"readMotion", js_read_motion},
         {"setCamera", js_set_camera}, {"updatePrimitives", js_update_primitives}, {"updateLights", js_update_lights},
         {"refitAccel", js_refit_accel},
         {"traceAdaptive", js_trace_adaptive}, {"readAdaptive", js_read_adaptive},

@@ -1,4 +1,4 @@
-"""python -m computeraytracer_amd [--scene file.json] [--width W --height H] [--spp N] [--out image.png] [--denoise K] [--orbit N [--temporal]]
+"""python -m computeraytracer_amd [--scene file.json] [--width W --height H] [--spp N] [--out image.png] [--denoise K] [--orbit N [--temporal [--animate]]]
                                 [--adaptive THRESHOLD [--adaptive-step N] [--counts-out counts.png]]"""
 import argparse
 import json
@@ -26,6 +26,10 @@ def main():
     ap.add_argument("--temporal", action="store_true",
                     help="with --orbit and --denoise K: frame k draws samples k * spp + 1 .. (set_sample_offset) and is blended "
                          "with the reprojected result of frame k - 1 before the filter (crt_denoise_temporal)")
+    ap.add_argument("--animate", action="store_true",
+                    help="with --orbit N --denoise K --temporal: before frame k every sphere is moved to its frame-0 centre plus "
+                         "(0, 0.5 radius sin(2 pi k / 16), 0) (update_primitives + refit_accel), and option temporal_motion keeps "
+                         "the history across those edits")
     ap.add_argument("--adaptive", type=float, default=None, metavar="THRESHOLD",
                     help="adaptive sampling (crt_trace_adaptive): rounds of --adaptive-step samples for the 8x8 tiles whose "
                          "error is above THRESHOLD, --spp samples at most, until every tile is done")
@@ -38,6 +42,8 @@ def main():
         ap.error("--orbit needs N >= 1 and no --checkpoint")
     if args.temporal and (args.orbit is None or args.denoise is None):
         ap.error("--temporal goes with --orbit N --denoise K")
+    if args.animate and not args.temporal:
+        ap.error("--animate goes with --orbit N --denoise K --temporal")
     if args.adaptive is not None and (args.orbit is not None or args.checkpoint):
         ap.error("--adaptive goes with neither --orbit nor --checkpoint")
     if (args.counts_out or args.adaptive_min is not None) and args.adaptive is None:
@@ -51,7 +57,17 @@ def main():
         if args.orbit is not None:
             base, ext = os.path.splitext(args.out)
             outs, t0 = [], time.time()
+            if args.animate:
+                import math
+                r.set_option("temporal_motion", 1)
+                spheres = [int(i) for i in (ps.primitives["category"] == scene.CATEGORY["sphere"]).nonzero()[0]]
             for k, cam in enumerate(scene.orbit_cameras(ps.camera, args.orbit)):
+                if args.animate:
+                    for i in spheres:
+                        rec = ps.primitives[i:i + 1]
+                        up = 0.5 * float(rec["data2"][0, 0]) * math.sin(2.0 * math.pi * k / 16.0)
+                        r.update_primitives(i, scene.transform_records(rec, [[1, 0, 0], [0, 1, 0], [0, 0, 1]], (0.0, up, 0.0)))
+                    r.refit_accel()
                 r.set_camera(cam)
                 if args.temporal:
                     r.set_sample_offset(k * args.spp)
@@ -68,6 +84,8 @@ def main():
                 info["denoise"] = args.denoise
             if args.temporal:
                 info["temporal"] = True
+            if args.animate:
+                info["animate"] = True
             print(json.dumps(info))
             return
         if args.adaptive is not None:

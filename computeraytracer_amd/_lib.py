@@ -65,6 +65,7 @@ SIGNATURES = {
     "crt_layout_rows": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _P, _P]),
     "crt_denoise": (C.c_int, [_P, _P, _P, _P]),
     "crt_read_gbuffer": (C.c_int, [_P, _P]),
+    "crt_read_motion": (C.c_int, [_P, _P]),
     "crt_debug_intersect": (C.c_int, [_P, _P, C.c_size_t, _P]),
     "crt_debug_trace_rays": (C.c_int, [_P, _P, C.c_size_t, _P, _P]),
     "crt_debug_probes": (C.c_int, [_P, _P]),

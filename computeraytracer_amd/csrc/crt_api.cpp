@@ -255,6 +255,12 @@ struct crt_ctx {
     DevBuf<float4> th_park_gbuf;
     DevBuf<uint32_t> th_park_key;
     DevBuf<float> th_hist;          // Hw alone, for history_out
+    // option "temporal_motion" (DESIGN.md 6f): the history outlives crt_update_primitives.  th_snap is a copy of d_raw, the
+    // scene as the newest valid slot saw it, taken by the first update after that slot was written.
+    bool th_motion = false;
+    DevBuf<unsigned char> th_snap;
+    enum { TH_SNAP_NONE, TH_SNAP_CURRENT, TH_SNAP_PREVIOUS } th_snap_of = TH_SNAP_NONE;   // the slot whose geometry it is
+    DevBuf<float2> th_uv;           // crt_read_motion's output
 
     // scene edits (crt_refit.hip)
     float s_prims = 0.0f;           // max |corner coordinate| of the primitives: hit_pad = max(s_prims, |eye|) * 2^-17
@@ -324,10 +330,11 @@ int alloc_frames(crt_ctx *c)
     return CRT_OK;
 }
 
-// Drop the history of crt_denoise_temporal (the buffers stay for the next use).
+// Drop the history of crt_denoise_temporal (the slots' buffers stay for the next use; the geometry snapshot goes).
 void th_drop(crt_ctx *c)
 {
     c->th_prev.valid = false; c->th_cur_valid = false; c->th_parked = false;
+    c->th_snap.release(); c->th_snap_of = crt_ctx::TH_SNAP_NONE;
 }
 
 int zero_state(crt_ctx *c)
@@ -1785,7 +1792,7 @@ void crt_destroy(crt_ctx *c)
     c->dn_gbuf.release(); c->dn_key.release(); c->dn_c[0].release(); c->dn_c[1].release(); c->dn_rgba.release();
     c->dn_kv.release(); c->dn_var.release();
     c->th_prev.c.release(); c->th_prev.gbuf.release(); c->th_prev.key.release(); c->th_cur_c.release();
-    c->th_park_gbuf.release(); c->th_park_key.release(); c->th_hist.release();
+    c->th_park_gbuf.release(); c->th_park_key.release(); c->th_hist.release(); c->th_snap.release(); c->th_uv.release();
     c->rf_lv2.release(); c->rf_lv4.release(); c->rf_nch4.release(); c->rf_cnt.release(); c->rf_fb.release();
     c->as_counts.release(); c->as_errors.release(); c->as_flags.release(); c->as_active.release(); c->as_n.release(); c->as_q.release();
     if (c->pub_stream) (void)hipStreamSynchronize(c->pub_stream);
@@ -2461,6 +2468,13 @@ int crt_set_option(crt_ctx *c, const char *name, int64_t value)
     if (!std::strcmp(name, "wf_pool_spp")) { c->wf_pool_spp = (int)std::min<int64_t>(64, std::max<int64_t>(1, value)); return CRT_OK; }
     if (!std::strcmp(name, "wf_feed_pct")) { c->wf_feed = (double)std::min<int64_t>(400, std::max<int64_t>(10, value)) / 100.0; return CRT_OK; }
     if (!std::strcmp(name, "wf_tail_walk")) { c->wf_tail_walk = value != 0; return CRT_OK; }
+    if (!std::strcmp(name, "temporal_motion")) {
+        if (value != 0 && value != 1) return fail(c, CRT_EINVAL, "crt_set_option: temporal_motion is 0 or 1");
+        if (!value && c->th_snap_of != crt_ctx::TH_SNAP_NONE) th_drop(c);   // (history across an edit is this option's)
+        if (!value) c->th_snap.release();
+        c->th_motion = value != 0;
+        return CRT_OK;
+    }
     if (!std::strcmp(name, "frame_ring")) {
         c->frame_ring = (uint32_t)std::min<int64_t>(256, std::max<int64_t>(0, value));
         c->ring_from = c->sample + 1u;                          // (a new ring starts empty)
@@ -2664,6 +2678,40 @@ static double th_kappa(const float cam[12], uint32_t W)
     return (std::sqrt(hor) / (double)W) / std::sqrt(ax);
 }
 
+// What the blend and crt_read_motion share: the frame's guides (gbuf, key), the PREVIOUS slot and its camera, and the
+// records the map of 6f reads.  h_prev stays null without a usable PREVIOUS.
+static DnReprojParams th_reproj_params(crt_ctx *c, const float4 *gbuf, const uint32_t *key)
+{
+    DnReprojParams P{};
+    P.gbuf = gbuf; P.key = key;
+    P.tw = c->tw; P.th = c->th;
+    if (c->th_prev.valid) {
+        // M' = [hor' ver' (llc' - eye')]^-1 by cofactors, in double
+        const float *q = c->th_prev.cam;
+        double A[3][3], inv[3][3];
+        for (int k = 0; k < 3; k++) { A[k][0] = q[3 + k]; A[k][1] = q[6 + k]; A[k][2] = (double)q[k] - (double)q[9 + k]; }
+        const double det = A[0][0] * (A[1][1] * A[2][2] - A[1][2] * A[2][1]) - A[0][1] * (A[1][0] * A[2][2] - A[1][2] * A[2][0]) +
+                           A[0][2] * (A[1][0] * A[2][1] - A[1][1] * A[2][0]);
+        for (int i = 0; i < 3; i++)
+            for (int j = 0; j < 3; j++) {
+                const int r0 = (j + 1) % 3, r1 = (j + 2) % 3, c0 = (i + 1) % 3, c1 = (i + 2) % 3;
+                inv[i][j] = (A[r0][c0] * A[r1][c1] - A[r0][c1] * A[r1][c0]) / det;
+            }
+        bool ok = std::isfinite(det) && det != 0.0;
+        for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) { P.m[3 * i + j] = inv[i][j]; ok = ok && std::isfinite(inv[i][j]); }
+        if (ok) {                                                // (a degenerate previous camera: nothing is reused)
+            P.h_prev = c->th_prev.c.p; P.gbuf_prev = c->th_prev.gbuf.p; P.key_prev = c->th_prev.key.p;
+        }
+        for (int k = 0; k < 3; k++) { P.eye_prev[k] = q[9 + k]; P.eye[k] = c->sc.cam[9 + k]; }
+        P.kappa_prev = (float)th_kappa(q, c->W); P.kappa = (float)th_kappa(c->sc.cam, c->W);
+        if (c->th_snap_of == crt_ctx::TH_SNAP_PREVIOUS) {        // PREVIOUS saw another pose of the scene: k_dn_reproject<true>
+            P.raw = c->d_raw.p; P.raw_prev = c->th_snap.p; P.nprim = (uint32_t)c->prims.size();
+        }
+    }
+    P.W = (double)c->W; P.H = (double)c->H; P.x0 = (double)c->x0; P.y0 = (double)c->y0;
+    return P;
+}
+
 int crt_denoise_temporal(crt_ctx *c, const crt_denoise_temporal_params *params, float *rgb_out, uint8_t *rgba8_out, float *history_out)
 {
     const crt_denoise_temporal_params dp = params ? *params : kDnTpDefaults;
@@ -2693,35 +2741,16 @@ int crt_denoise_temporal(crt_ctx *c, const crt_denoise_temporal_params *params, 
             std::memcpy(c->th_prev.cam, c->th_cur_cam, sizeof c->th_prev.cam);
             c->th_prev.valid = true;
             c->th_cur_valid = false; c->th_parked = false;
+            // a snapshot taken for that slot is now PREVIOUS's geometry; an older one went with the slot it belonged to
+            c->th_snap_of = c->th_snap_of == crt_ctx::TH_SNAP_CURRENT ? crt_ctx::TH_SNAP_PREVIOUS : crt_ctx::TH_SNAP_NONE;
         }
         c->th_cur_valid = false;                                 // (rewritten below: a rebuild of the G-buffer has nothing to park)
         { int rc = dn_ensure_gbuffer(c); if (rc) return rc; }
-        DnReprojParams P{};
-        P.accum = accum_ptr(c); P.gbuf = c->dn_gbuf.p; P.key = c->dn_key.p;
+        DnReprojParams P = th_reproj_params(c, c->dn_gbuf.p, c->dn_key.p);
+        P.accum = accum_ptr(c);
         P.h_cur = c->th_cur_c.p;
         P.hist = history_out || rgb_out ? c->th_hist.p : nullptr;
-        P.tw = c->tw; P.th = c->th; P.n = (float)c->sample;
-        if (c->th_prev.valid) {
-            // M' = [hor' ver' (llc' - eye')]^-1 by cofactors, in double
-            const float *q = c->th_prev.cam;
-            double A[3][3], inv[3][3];
-            for (int k = 0; k < 3; k++) { A[k][0] = q[3 + k]; A[k][1] = q[6 + k]; A[k][2] = (double)q[k] - (double)q[9 + k]; }
-            const double det = A[0][0] * (A[1][1] * A[2][2] - A[1][2] * A[2][1]) - A[0][1] * (A[1][0] * A[2][2] - A[1][2] * A[2][0]) +
-                               A[0][2] * (A[1][0] * A[2][1] - A[1][1] * A[2][0]);
-            for (int i = 0; i < 3; i++)
-                for (int j = 0; j < 3; j++) {
-                    const int r0 = (j + 1) % 3, r1 = (j + 2) % 3, c0 = (i + 1) % 3, c1 = (i + 2) % 3;
-                    inv[i][j] = (A[r0][c0] * A[r1][c1] - A[r0][c1] * A[r1][c0]) / det;
-                }
-            bool ok = std::isfinite(det) && det != 0.0;
-            for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) { P.m[3 * i + j] = inv[i][j]; ok = ok && std::isfinite(inv[i][j]); }
-            if (ok) {                                            // (a degenerate previous camera: nothing is reused)
-                P.h_prev = c->th_prev.c.p; P.gbuf_prev = c->th_prev.gbuf.p; P.key_prev = c->th_prev.key.p;
-            }
-            for (int k = 0; k < 3; k++) { P.eye_prev[k] = q[9 + k]; P.eye[k] = c->sc.cam[9 + k]; }
-            P.kappa_prev = (float)th_kappa(q, c->W); P.kappa = (float)th_kappa(c->sc.cam, c->W);
-        }
-        P.W = (double)c->W; P.H = (double)c->H; P.x0 = (double)c->x0; P.y0 = (double)c->y0;
+        P.n = (float)c->sample;
         P.max_history = dp.max_history;
         P.normal_tol2 = (float)std::min(3.0e38, (double)dp.normal_tol * dp.normal_tol);
         P.plane_tol = dp.plane_tol;
@@ -2734,6 +2763,24 @@ int crt_denoise_temporal(crt_ctx *c, const crt_denoise_temporal_params *params, 
     if (rgb_out && dp.iterations > 0)
         for (size_t i = 0; i < n; i++) rgb_out[4 * i + 3] = hw_host[i];
     return rc;
+}
+
+int crt_read_motion(crt_ctx *c, float *out)
+{
+    if (!c || !out) return CRT_EINVAL;
+    { int rc = dn_begin(c, "crt_read_motion", 0, nullptr, 0, "", DN_UNIFORM); if (rc) return rc; }
+    if (!c->th_cur_valid || c->th_cur_frame != c->frame_id)
+        return fail(c, CRT_ESTATE, "crt_read_motion: no crt_denoise_temporal in this frame yet (it reports where that call's blend looked)");
+    const size_t n = (size_t)c->tw * c->th;
+    if (n) {
+        DN_ENSURE(c, th_uv, n);
+        // CURRENT's guides: dn_gbuf itself unless a later rebuild parked them
+        const DnReprojParams P = c->th_parked ? th_reproj_params(c, c->th_park_gbuf.p, c->th_park_key.p)
+                                              : th_reproj_params(c, c->dn_gbuf.p, c->dn_key.p);
+        HIPCHK(c, dn_launch_motion(P, c->th_uv.p, c->stream));
+        HIPCHK(c, hipMemcpyAsync(out, c->th_uv.p, n * sizeof(float2), hipMemcpyDeviceToHost, c->stream));
+    }
+    return dn_finish(c, n, nullptr, nullptr, nullptr);
 }
 
 int crt_read_gbuffer(crt_ctx *c, float *out)
@@ -3039,8 +3086,23 @@ int crt_update_primitives(crt_ctx *c, uint32_t first, uint32_t count, const void
             return fail(c, CRT_EINVAL, "crt_update_primitives: primitive %u: spectrum index out of range", i);
     }
     { int rc = edit_begin(c); if (rc) return rc; }
+    // option "temporal_motion": the history stays, with the scene as its newest slot saw it.  Not retaken
+    // until a newer slot exists: several updates may precede one refit, and a frame that is never filtered temporally
+    // must not cost the older slot its geometry.
+    const int snap_for = !c->th_motion ? crt_ctx::TH_SNAP_NONE : c->th_cur_valid ? crt_ctx::TH_SNAP_CURRENT
+                         : c->th_prev.valid ? crt_ctx::TH_SNAP_PREVIOUS : crt_ctx::TH_SNAP_NONE;
+    const bool take = snap_for != crt_ctx::TH_SNAP_NONE && c->th_snap_of != snap_for;
+    if (take && c->th_snap.n < c->d_raw.n) {                      // before anything changes: CRT_ENOMEM leaves all as it was
+        ScopedBuf<unsigned char> fresh;
+        HIPCHK(c, fresh.alloc(c->d_raw.n));
+        std::swap(c->th_snap.p, fresh.p); std::swap(c->th_snap.n, fresh.n);
+    }
+    if (take) {
+        HIPCHK(c, hipMemcpyAsync(c->th_snap.p, c->d_raw.p, c->d_raw.n, hipMemcpyDeviceToDevice, c->stream));
+        c->th_snap_of = (decltype(c->th_snap_of))snap_for;
+    }
+    if (snap_for == crt_ctx::TH_SNAP_NONE) th_drop(c);           // (nothing to keep, or the option is off)
     std::copy(np.begin(), np.end(), c->prims.begin() + first);   // the host SAH builder reads these
-    th_drop(c);                                                  // (reusing history across moved geometry needs motion vectors)
     if (count) {
         HIPCHK(c, hipMemcpyAsync(c->d_raw.p + (size_t)first * 80, records, (size_t)count * 80, hipMemcpyHostToDevice, c->stream));   // the LBVH builder's input
         if (c->accel_mode >= 0)                                  // the leaf-ordered records, in their slots

@@ -297,8 +297,67 @@ __global__ __launch_bounds__(256) void k_dn_atrous_as(const DnAsParams P)
 
 // ---------------------------------------------------------------- temporal reuse (crt_denoise_temporal)
 // DESIGN.md 6e defines it operation by operation (tests/denoise_temporal_ref.py is its numpy restatement).
+// What k_dn_reproject and k_dn_motion share, so that the motion output cannot drift from the blend: steps 1-2 of 6e (the
+// film position of the pixel's first hit in the previous camera, binary64, nothing contracted), and with MOTION the map
+// of 6f before them -- the hit carried through its primitive's record as the PREVIOUS slot saw it (P.raw_prev).
+struct DnMapped {
+    double u, v;                    // rectangle-local film position in the previous camera
+    f3 x, n;                        // x~ rounded to float and n~: what the taps' plane and normal tests compare against
+};
+
+__device__ __forceinline__ double dn_dot64(const double a[3], const double b[3]) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
+__device__ __forceinline__ f3 dn_xyz(uint4 w) { return f3{bits_f(w.x), bits_f(w.y), bits_f(w.z)}; }
+__device__ __forceinline__ bool dn_same_xyz(uint4 a, uint4 b) { return a.x == b.x && a.y == b.y && a.z == b.z; }
+
+// false: the pixel takes no history (a changed spectrum, a map that refuses, depth <= 0 or not finite).
+template <bool MOTION>
+__device__ __forceinline__ bool dn_film_position(const DnReprojParams &P, f3 x_p, f3 n_p, uint32_t index, DnMapped &o)
+{
+    double X[3] = {(double)x_p.x, (double)x_p.y, (double)x_p.z};
+    o.x = x_p; o.n = n_p;
+    if constexpr (MOTION) {
+        if (index >= P.nprim) return false;                     // (no hit names one: the loads below stay inside the buffers)
+        const uint4 *rc = (const uint4 *)(P.raw + (size_t)index * 80), *rp = (const uint4 *)(P.raw_prev + (size_t)index * 80);
+        const uint4 c1 = rc[1], c2 = rc[2], c3 = rc[3], c4 = rc[4], p1 = rp[1], p2 = rp[2], p3 = rp[3], p4 = rp[4];
+        // compared before anything is computed: a pixel on a record that did not change pays the loads alone
+        if (!(dn_same_xyz(c1, p1) && dn_same_xyz(c2, p2) && dn_same_xyz(c3, p3) && c4.x == p4.x && c4.y == p4.y)) {
+            if (c4.x != p4.x || c4.y != p4.y) return false;     // emission or reflectance changed: what the history holds is stale
+            const f3 d1 = dn_xyz(c1), d2 = dn_xyz(c2), d3 = dn_xyz(c3), q1 = dn_xyz(p1), q2 = dn_xyz(p2), q3 = dn_xyz(p3);
+            const double D1[3] = {(double)d1.x, (double)d1.y, (double)d1.z}, Q1[3] = {(double)q1.x, (double)q1.y, (double)q1.z};
+            if (rc[0].x == 1u) {                                // sphere: same direction from the centre, radius scaled
+                const double rho = (double)q2.x / (double)d2.x;
+                if (!(d2.x != 0.0f) || !(fabs(rho) <= 1.7976931348623157e308)) return false;
+                for (int k = 0; k < 3; k++) X[k] = Q1[k] + (X[k] - D1[k]) * rho;
+            } else {                                            // patch, triangle: same coordinates in the edges' frame
+                const double D2[3] = {(double)d2.x, (double)d2.y, (double)d2.z}, D3[3] = {(double)d3.x, (double)d3.y, (double)d3.z};
+                const double E[3] = {X[0] - D1[0], X[1] - D1[1], X[2] - D1[2]};
+                const double g11 = dn_dot64(D2, D2), g22 = dn_dot64(D3, D3), g12 = dn_dot64(D2, D3);
+                const double det = g11 * g22 - g12 * g12;
+                if (!(det > 0.0 && det <= 1.7976931348623157e308)) return false;
+                const double b1 = dn_dot64(E, D2), b2 = dn_dot64(E, D3);
+                const double beta = (b1 * g22 - b2 * g12) / det, gamma = (b2 * g11 - b1 * g12) / det;
+                const double Q2[3] = {(double)q2.x, (double)q2.y, (double)q2.z}, Q3[3] = {(double)q3.x, (double)q3.y, (double)q3.z};
+                for (int k = 0; k < 3; k++) X[k] = (Q1[k] + beta * Q2[k]) + gamma * Q3[k];
+                const f3 m = normalize(cross(q2, q3));          // hit_attributes_rec's normal of the old pose, on n_p's side
+                o.n = dot(n_p, normalize(cross(d2, d3))) < 0.0f ? f3{-m.x, -m.y, -m.z} : m;
+            }
+            o.x = f3{(float)X[0], (float)X[1], (float)X[2]};
+        }
+    }
+    const double dx_ = X[0] - P.eye_prev[0], dy_ = X[1] - P.eye_prev[1], dz_ = X[2] - P.eye_prev[2];
+    const double pa = (P.m[0] * dx_ + P.m[1] * dy_) + P.m[2] * dz_;
+    const double pb = (P.m[3] * dx_ + P.m[4] * dy_) + P.m[5] * dz_;
+    const double pc = (P.m[6] * dx_ + P.m[7] * dy_) + P.m[8] * dz_;
+    if (!(pc > 0.0 && pc <= 1.7976931348623157e308)) return false;
+    o.u = ((pa / pc) * P.W - 0.53125) - P.x0;
+    o.v = ((P.H + 0.53125) - (pb / pc) * P.H) - P.y0;
+    return true;
+}
+
 // k_dn_prepare's work, the reprojection into the previous frame and the blend in one pass: grid as k_dn_atrous.  The
 // pixel's own guides stay in registers; a tap's history and G-buffer are fetched only when its key matches.
+// <false>: PREVIOUS saw the scene as it is (6e alone); <true>: PREVIOUS has a geometry snapshot (6f).
+template <bool MOTION>
 __global__ __launch_bounds__(256) void k_dn_reproject(const DnReprojParams P)
 {
     const int x = dn_x16(), y = dn_y16();
@@ -313,21 +372,17 @@ __global__ __launch_bounds__(256) void k_dn_reproject(const DnReprojParams P)
     if (P.h_prev && key_p != kNoHit && (key_p >> 24) != kGlass && finite4(float4{c_new.x, c_new.y, c_new.z, 0.0f})) {
         const float4 g0 = P.gbuf[2 * p], g1 = P.gbuf[2 * p + 1];
         const f3 x_p = f3{g0.y, g0.z, g0.w}, n_p = f3{g1.x, g1.y, g1.z};
-        // the film position in the previous camera, in binary64 (products and sums as written, nothing contracted)
-        const double dx_ = (double)x_p.x - P.eye_prev[0], dy_ = (double)x_p.y - P.eye_prev[1], dz_ = (double)x_p.z - P.eye_prev[2];
-        const double pa = (P.m[0] * dx_ + P.m[1] * dy_) + P.m[2] * dz_;
-        const double pb = (P.m[3] * dx_ + P.m[4] * dy_) + P.m[5] * dz_;
-        const double pc = (P.m[6] * dx_ + P.m[7] * dy_) + P.m[8] * dz_;
-        if (pc > 0.0 && pc <= 1.7976931348623157e308) {
-            const double u = ((pa / pc) * P.W - 0.53125) - P.x0;
-            const double v = ((P.H + 0.53125) - (pb / pc) * P.H) - P.y0;
+        DnMapped mp;
+        if (dn_film_position<MOTION>(P, x_p, n_p, f_bits(g1.w), mp)) {
+            const double u = mp.u, v = mp.v;
+            const f3 x_m = mp.x, n_m = mp.n;
             // (a NaN fails both comparisons; the bounds also keep the conversions to int defined)
             if (u >= -1.0 && u < (double)tw && v >= -1.0 && v < (double)th) {
                 const double fu = floor(u), fv = floor(v);
                 const int ix = (int)fu, iy = (int)fv;
                 const float fx = (float)(u - fu), fy = (float)(v - fv);
                 const float wx[2] = {1.0f - fx, fx}, wy[2] = {1.0f - fy, fy};
-                const f3 d = x_p - f3{(float)P.eye_prev[0], (float)P.eye_prev[1], (float)P.eye_prev[2]};
+                const f3 d = x_m - f3{(float)P.eye_prev[0], (float)P.eye_prev[1], (float)P.eye_prev[2]};
                 const float r_p = max_(P.kappa * length(x_p - f3{P.eye[0], P.eye[1], P.eye[2]}), P.kappa_prev * length(d));
                 const float plane_max = P.plane_tol * r_p;
                 float sw = 0.0f, sh = 0.0f;
@@ -345,9 +400,9 @@ __global__ __launch_bounds__(256) void k_dn_reproject(const DnReprojParams P)
                         const float4 hq = P.h_prev[q];
                         if (!(hq.w > 0.0f) || !finite4(hq)) continue;
                         const float4 q0 = P.gbuf_prev[2 * q], q1 = P.gbuf_prev[2 * q + 1];
-                        const f3 dn = n_p - f3{q1.x, q1.y, q1.z};
+                        const f3 dn = n_m - f3{q1.x, q1.y, q1.z};
                         if (!(dot(dn, dn) <= P.normal_tol2)) continue;
-                        if (!(abs_(dot(n_p, f3{q0.y, q0.z, q0.w} - x_p)) <= plane_max)) continue;
+                        if (!(abs_(dot(n_m, f3{q0.y, q0.z, q0.w} - x_m)) <= plane_max)) continue;
                         const float w = wx[dx] * wy[dy];
                         sw = sw + w;
                         sc = sc + f3{hq.x, hq.y, hq.z} * w;
@@ -366,6 +421,25 @@ __global__ __launch_bounds__(256) void k_dn_reproject(const DnReprojParams P)
     P.h_cur[p] = float4{c.x, c.y, c.z, Hw};
     if (P.rgba) P.rgba[p] = linear_rgb_to_rgba8(c);
     if (P.hist) P.hist[p] = Hw;
+}
+
+// crt_read_motion: where the blend above looks for each pixel in the PREVIOUS slot -- (u, v) rounded to float, NaN where
+// no position exists.  grid as k_dn_atrous.
+template <bool MOTION>
+__global__ __launch_bounds__(256) void k_dn_motion(const DnReprojParams P, float2 *__restrict__ out)
+{
+    const int x = dn_x16(), y = dn_y16();
+    if (x >= (int)P.tw || y >= (int)P.th) return;
+    const size_t p = (size_t)y * P.tw + (size_t)x;
+    const float nan = bits_f(0x7FC00000u);
+    float2 uv = float2{nan, nan};
+    const uint32_t key_p = P.key[p];
+    if (P.h_prev && key_p != kNoHit && (key_p >> 24) != kGlass) {
+        const float4 g0 = P.gbuf[2 * p], g1 = P.gbuf[2 * p + 1];
+        DnMapped mp;
+        if (dn_film_position<MOTION>(P, f3{g0.y, g0.z, g0.w}, f3{g1.x, g1.y, g1.z}, f_bits(g1.w), mp)) uv = float2{(float)mp.u, (float)mp.v};
+    }
+    out[p] = uv;
 }
 
 // ---------------------------------------------------------------- launchers (called from crt_api.cpp; DnFilter: crt_device.h)
@@ -429,9 +503,20 @@ hipError_t dn_launch_temporal(const DnFilter &F, DnReprojParams P, float sigma_c
     *out = P.h_cur;
     if ((size_t)F.tw * F.th == 0) return hipSuccess;
     P.rgba = F.iterations == 0 ? F.rgba : nullptr;
-    hipLaunchKernelGGL(k_dn_reproject, dn_grid16(F), dim3(256), 0, F.stream, P);
+    if (P.raw_prev) hipLaunchKernelGGL(k_dn_reproject<true>, dn_grid16(F), dim3(256), 0, F.stream, P);
+    else hipLaunchKernelGGL(k_dn_reproject<false>, dn_grid16(F), dim3(256), 0, F.stream, P);
     const hipError_t e = hipGetLastError();
     return e != hipSuccess ? e : dn_run_atrous(F, P.h_cur, sigma_color, out);
+}
+
+// The film positions of P's pixels in its previous slot (P.gbuf / P.key: the slot they are asked for), tw * th float2.
+hipError_t dn_launch_motion(const DnReprojParams &P, float2 *out, hipStream_t stream)
+{
+    if ((size_t)P.tw * P.th == 0) return hipSuccess;
+    const dim3 grid((P.tw + 15u) / 16u, (P.th + 15u) / 16u);
+    if (P.raw_prev) hipLaunchKernelGGL(k_dn_motion<true>, grid, dim3(256), 0, stream, P, out);
+    else hipLaunchKernelGGL(k_dn_motion<false>, grid, dim3(256), 0, stream, P, out);
+    return hipGetLastError();
 }
 
 // The adaptive state's filter: (accum, q, counts) -> c[0] with v in w, then per iteration the variance blur into kv and

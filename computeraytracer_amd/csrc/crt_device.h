@@ -258,6 +258,9 @@ struct DnReprojParams {
     float eye[3];
     float kappa_prev, kappa;        // pixel footprint per unit distance: (|hor| / W) / |llc + hor/2 + ver/2 - eye|
     float max_history, normal_tol2, plane_tol;
+    // the 80-byte records as they are and as the previous slot saw them; raw_prev null = the same scene
+    const unsigned char *raw, *raw_prev;
+    uint32_t nprim;
 };
 
 // What the launchers of the three preview filters share (crt_denoise.hip).
@@ -278,5 +281,6 @@ hipError_t dn_launch_filter(const DnFilter &F, const float4 *accum, float n, flo
 hipError_t dn_launch_filter_adaptive(const DnFilter &F, const float4 *accum, const float *q, const uint32_t *counts, uint2 *kv,
                                      float *var, float sigma_variance, float4 **out);
 hipError_t dn_launch_temporal(const DnFilter &F, DnReprojParams P, float sigma_color, float4 **out);
+hipError_t dn_launch_motion(const DnReprojParams &P, float2 *out, hipStream_t stream);
 
 }  // namespace crt

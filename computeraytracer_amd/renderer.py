@@ -303,6 +303,16 @@ class Renderer:
         self._chk(self._lib.crt_denoise_temporal_reset(self._h))
         return self
 
+    def read_motion(self) -> np.ndarray:
+        """(H, W, 2) float32 per tile pixel: the film position (u, v), in the tile's own pixel coordinates, where the
+        last denoise_temporal looked for the pixel in the previous frame; NaN where there is none (no previous frame, a
+        miss, glass, behind the previous camera, a primitive edit the map refuses).  Option "temporal_motion" = 1 makes
+        it follow update_primitives."""
+        _, _, tw, th = self.tile
+        out = np.empty((th, tw, 2), np.float32)
+        self._chk(self._lib.crt_read_motion(self._h, out.ctypes.data))
+        return out
+
     def read_gbuffer(self) -> np.ndarray:
         """(H, W, 8) float32 per tile pixel: t, position, normal, hit index bits (0xFFFFFFFF = miss) of the primary
         ray of sample 8 -- the crt_debug_intersect record."""

@@ -85,6 +85,11 @@ function Main(options = {}) {
     denoiseTemporal: (opts = {}) => a.denoiseTemporal(device, opts),
     denoiseTemporalAsync: (opts = {}) => a.denoiseTemporalAsync(device, opts),
     temporalReset: () => a.temporalReset(device),
+    // motion vectors (include/crt.h crt_read_motion): Float32Array(tw*th*2), per pixel the film position where the last
+    // denoiseTemporal looked for it in the previous frame, NaN where there is none.  setOption('temporal_motion', 1)
+    // keeps the history across updatePrimitives and makes the positions follow the edited primitives.
+    readMotion: () => a.readMotion(device),
+    setOption: (name, value) => a.setOption(device, name, value),
     counters: () => a.counters(device),
     enableCounters: (on) => a.enableCounters(device, !!on),
     lastTraceMs: () => a.lastTraceMs(device),

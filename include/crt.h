@@ -261,7 +261,11 @@ int crt_set_camera(crt_ctx *ctx, const float camera[16]);
  * its category and material must be unchanged, its spectrum indices < nspectra, and the range inside the scene.
  * With a tree (CRT_ACCEL_BVH2 / LBVH) the tree becomes stale: crt_trace, crt_denoise, crt_read_gbuffer and
  * crt_debug_intersect return CRT_ESTATE until crt_refit_accel or crt_build_accel.  Several updates may precede one
- * refit.  Under CRT_ACCEL_NONE nothing goes stale. */
+ * refit.  Under CRT_ACCEL_NONE nothing goes stale.
+ * The history of crt_denoise_temporal is dropped, unless option "temporal_motion" is 1: then it is kept, and the first
+ * update after a history slot was written first copies the records as they were (nprim x 80 bytes on the device) so that
+ * the next crt_denoise_temporal can look every edited primitive's pixels up where they were ("Temporal reuse" below).
+ * If that copy cannot be allocated the call returns CRT_ENOMEM with the context, the scene and the history as they were. */
 int crt_update_primitives(crt_ctx *ctx, uint32_t first, uint32_t count, const void *records);
 /* Replace light records [first, first+count) (count x 80 bytes, crt_upload_scene's validation; 1/area recomputed). */
 int crt_update_lights(crt_ctx *ctx, uint32_t first, uint32_t count, const void *records);
@@ -367,7 +371,16 @@ int crt_sample_offset(crt_ctx *ctx, uint32_t *out);
  * CURRENT, so calling twice is idempotent.  History survives crt_set_camera, crt_reset, crt_build_accel and a
  * crt_refit_accel with no primitive update before it; it is dropped by crt_upload_scene, crt_set_tile,
  * crt_set_row_bands, crt_comm_partition, crt_update_primitives, crt_update_lights, crt_write_accum and
- * crt_denoise_temporal_reset (moving geometry would need motion vectors).
+ * crt_denoise_temporal_reset.
+ * Moving geometry: with option "temporal_motion" = 1 (default 0) crt_update_primitives keeps the history, and the next
+ * crt_denoise_temporal reprojects every pixel whose primitive's record changed through that primitive's previous record
+ * (DESIGN.md 6f): the hit keeps its coordinates in the primitive (a patch's or triangle's edge coordinates, a sphere's
+ * direction from the centre), x_p and n_p become the position x~ and normal n~ they had in the old pose, and x~, n~ take
+ * x_p's, n_p's place in the projection and in the taps' tests.  A pixel whose record is bitwise unchanged takes the path
+ * below exactly; one whose emission or reflectance index changed, or whose old record is degenerate, takes no history.
+ * crt_update_lights drops the history in both modes (it changes what every surface receives), and lighting that changed
+ * because something else moved (a shadow sliding over a static floor) is stale history until the blend outweighs it.
+ * Setting the option back to 0 after such an edit drops the history.
  * Per pixel p with first hit x_p, normal n_p and key: no history is taken where there is no PREVIOUS, at a miss, on
  * glass (view-dependent) or where the pixel's own colour is not finite.  Otherwise x_p is projected into the previous
  * camera; each of the four bilinear taps q there is reused iff it lies inside the rectangle, has the same key, holds
@@ -396,6 +409,14 @@ int crt_denoise_temporal(crt_ctx *ctx, const crt_denoise_temporal_params *params
                          float *history_out);
 /* Drop the history: the next crt_denoise_temporal equals crt_denoise. */
 int crt_denoise_temporal_reset(crt_ctx *ctx);
+/* Motion vectors: per pixel of the rectangle the film position (u, v), in the rectangle's own pixel coordinates, where
+ * the blend of the last crt_denoise_temporal looked for that pixel in the PREVIOUS slot (the binary64 value rounded to
+ * float; out: tw*th*2 floats) -- what an external denoiser or encoder asks for.  (NaN, NaN) where no position exists:
+ * no PREVIOUS slot, a miss, glass, a depth in the previous camera that is <= 0 or not finite, or a map of
+ * "temporal_motion" that refuses.  Positions outside the rectangle are reported as they are.  With "temporal_motion" off
+ * it is the camera-only reprojection.  A sync point like crt_read_gbuffer, and it only reads.  CRT_ESTATE where
+ * crt_denoise_temporal returns it, and when no crt_denoise_temporal has run since the accumulator was last zeroed. */
+int crt_read_motion(crt_ctx *ctx, float *out);
 
 /* Counters accumulate over crt_trace calls while enabled (off by default: the
  * counting kernel variant is slower). */
@@ -425,6 +446,8 @@ int crt_last_kernel_ms(crt_ctx *ctx, float *ms, uint32_t *launches);
  * "quantize", "wf_width" (4 | 8: node width of the wavefront traversal; at crt_build_accel);
  * "wf_trace_form" (2: ray ring + primitive tasks, default; 1: the first traversal kernel); "frame_ring" = F (keep the
  * rgba8 frame of each of the last F samples for crt_read_sample_rgba8; 0 = off);
+ * "temporal_motion" (0 | 1, anything else is CRT_EINVAL: 1 keeps the history of crt_denoise_temporal across
+ * crt_update_primitives, see "Temporal reuse"; costs 80 bytes per primitive on the device once an edit has happened);
  * "time_kernels"; "debug_fail_alloc" = k (test hook: the k-th device allocation from now on reports
  * out of memory).  Setting an option first finishes what is in flight. */
 int crt_set_option(crt_ctx *ctx, const char *name, int64_t value);
