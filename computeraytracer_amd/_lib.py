@@ -68,6 +68,7 @@ SIGNATURES = {
     "crt_read_motion": (C.c_int, [_P, _P]),
     "crt_debug_intersect": (C.c_int, [_P, _P, C.c_size_t, _P]),
     "crt_debug_trace_rays": (C.c_int, [_P, _P, C.c_size_t, _P, _P]),
+    "crt_debug_read_accel": (C.c_int, [_P, C.c_int, _P, C.c_size_t, _P]),
     "crt_debug_probes": (C.c_int, [_P, _P]),
     "crt_debug_math": (C.c_int, [_P, C.c_int, _P, _P, _P, C.c_size_t]),
     "crt_set_camera": (C.c_int, [_P, _P]),

@@ -2934,6 +2934,55 @@ int crt_debug_trace_rays(crt_ctx *c, const float *rays, size_t n, uint32_t *out,
     return CRT_OK;
 }
 
+// The current structure as it lies on the device, part by part (include/crt.h): device-to-host copies only.
+int crt_debug_read_accel(crt_ctx *c, int what, void *out, size_t capacity, size_t *bytes)
+{
+    if (!c) return CRT_EINVAL;
+    if (bytes) *bytes = 0;
+    if (!c->have_scene || c->accel_mode < 0) return fail(c, CRT_ESTATE, "crt_debug_read_accel: scene + accel required");
+    if (what < CRT_ACCEL_PART_HEADER || what > CRT_ACCEL_PART_SLOT_OF_INDEX) return fail(c, CRT_EINVAL, "crt_debug_read_accel: unknown part %d", what);
+    HIPCHK(c, hipSetDevice(c->device));
+    { int rc_ = wf_flush(c); if (rc_) return rc_; }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const bool tree = c->accel_mode == CRT_ACCEL_BVH2;
+    const size_t n = c->prims.size(), n2 = tree ? c->bvh.n_inner : 0, n4 = tree ? c->bvh4.n_inner : 0, n8 = tree && c->bvh8q.ok ? c->bvh8q.n_inner : 0;
+    const bool device_route = tree && n4 > 0 && c->bvh4.nodes.size() < n4 * (size_t)kNode4Floats;
+    const bool live4 = tree && n4 > 0 && !device_route, live4q = tree && n4 > 0 && c->sc.nodes4q != nullptr, live8q = n8 > 0 && c->sc.nodes8q != nullptr;
+    double hdr[CRT_ACCEL_HEADER_N] = {0};
+    const void *src = nullptr;
+    size_t need = 0;
+    switch (what) {
+    case CRT_ACCEL_PART_HEADER: {
+        const size_t lanes = (size_t)c->num_cu * wf_waves(c) * 64u * (size_t)std::max(1, c->wf_pipes);
+        hdr[0] = c->accel_mode; hdr[1] = c->accel_builder; hdr[2] = (double)n;
+        hdr[3] = tree ? c->sc.root : -1; hdr[4] = tree ? c->sc.root4 : -1; hdr[5] = live8q ? c->sc.root8 : -1;
+        hdr[6] = (double)n2; hdr[7] = (double)n4; hdr[8] = (double)n8;
+        hdr[9] = live4; hdr[10] = live4q; hdr[11] = live8q;
+        for (int a = 0; a < 3; a++) { hdr[12 + a] = c->sc.qbase[a]; hdr[15 + a] = c->sc.qscale[a]; }
+        hdr[18] = c->sc.hit_pad; hdr[19] = c->tree_pad;
+        hdr[20] = c->bvh.max_depth; hdr[21] = c->bvh4.max_depth; hdr[22] = c->bvh8q.max_depth; hdr[23] = c->wf_depth;
+        hdr[24] = wf_stack_need(c); hdr[25] = wf_stack_lds(c); hdr[26] = wf_overflow_levels(c);
+        hdr[27] = lanes ? (double)(c->w_overflow.n / lanes) : 0.0;
+        hdr[28] = c->accel_stale; hdr[29] = device_route;
+        need = sizeof hdr;
+        break;
+    }
+    case CRT_ACCEL_PART_NODES2: src = c->d_nodes.p; need = n2 * kNodeFloats * sizeof(float); break;
+    case CRT_ACCEL_PART_NODES4: src = c->d_nodes4.p; need = live4 ? n4 * kNode4Floats * sizeof(float) : 0; break;
+    case CRT_ACCEL_PART_NODES4Q: src = c->d_nodes4q.p; need = live4q ? n4 * 16 * sizeof(uint32_t) : 0; break;
+    case CRT_ACCEL_PART_NODES8Q: src = c->d_nodes8q.p; need = live8q ? n8 * 32 * sizeof(uint32_t) : 0; break;
+    case CRT_ACCEL_PART_PRIM: src = c->d_prim.p; need = n * 3 * sizeof(float4); break;
+    case CRT_ACCEL_PART_PRIMD: src = c->d_primD.p; need = tree ? n * sizeof(float4) : 0; break;
+    default: src = c->d_slot_of_index.p; need = n * sizeof(uint32_t); break;
+    }
+    if (bytes) *bytes = need;
+    if (!out) return CRT_OK;
+    if (capacity < need) return fail(c, CRT_EINVAL, "crt_debug_read_accel: part %d holds %zu bytes, the buffer %zu", what, need, capacity);
+    if (what == CRT_ACCEL_PART_HEADER) std::memcpy(out, hdr, need);
+    else if (need) HIPCHK(c, hipMemcpy(out, src, need, hipMemcpyDeviceToHost));
+    return CRT_OK;
+}
+
 int crt_debug_math(crt_ctx *c, int fn, const float *a, const float *b, float *out, size_t n)
 {
     if (!c || !a || !b || !out) return CRT_EINVAL;

@@ -451,6 +451,34 @@ class Renderer:
         t = np.where(sh, np.uint32(0), out[:, 0]).astype(np.uint32).view(np.float32)
         return t, np.where(sh, np.uint32(0), out[:, 1]).astype(np.uint32), np.where(sh, out[:, 0], np.uint32(0)).astype(np.uint32), report
 
+    ACCEL_HEADER = ("accel_mode", "builder", "nprim", "root", "root4", "root8", "n2", "n4", "n8", "live4", "live4q", "live8q",
+                    "qbase_x", "qbase_y", "qbase_z", "qscale_x", "qscale_y", "qscale_z", "hit_pad", "tree_pad", "depth2", "depth4",
+                    "depth8", "wf_depth", "wf_stack_need", "wf_stack_lds", "wf_overflow_levels", "overflow_allocated", "stale",
+                    "device_route")
+    ACCEL_PARTS = (("nodes2", np.float32, 16), ("nodes4", np.float32, 32), ("nodes4q", np.uint32, 16), ("nodes8q", np.uint32, 32),
+                   ("prim", np.float32, 12), ("primD", np.float32, 4), ("slot_of_index", np.uint32, 1))
+
+    def debug_read_accel(self) -> dict:
+        """The current acceleration structure as it lies on the device (crt_debug_read_accel): the header's scalars by
+        name (ints; qbase / qscale / hit_pad / tree_pad as float32) and the arrays, one row per node / slot (empty where
+        the part is not live).  Works on a stale tree; reads only."""
+        def part(what, dtype):
+            nbytes = C.c_size_t()
+            self._chk(self._lib.crt_debug_read_accel(self._h, what, None, 0, C.byref(nbytes)))
+            out = np.zeros(nbytes.value // np.dtype(dtype).itemsize, dtype)
+            if nbytes.value:
+                self._chk(self._lib.crt_debug_read_accel(self._h, what, out.ctypes.data, out.nbytes, None))
+            return out
+        h = part(0, np.float64)
+        floats = ("qbase_x", "qbase_y", "qbase_z", "qscale_x", "qscale_y", "qscale_z", "hit_pad", "tree_pad")   # (a pad may be inf)
+        out = {k: int(v) for k, v in zip(self.ACCEL_HEADER, h) if k not in floats}
+        out["qbase"], out["qscale"] = h[12:15].astype(np.float32), h[15:18].astype(np.float32)
+        out["hit_pad"], out["tree_pad"] = np.float32(h[18]), np.float32(h[19])
+        for what, (name, dtype, cols) in enumerate(self.ACCEL_PARTS, 1):
+            a = part(what, dtype)
+            out[name] = a.reshape(-1, cols) if cols > 1 else a
+        return out
+
     def debug_probes(self) -> list:
         out = np.zeros(8, np.uint64)
         self._chk(self._lib.crt_debug_probes(self._h, out.ctypes.data))

@@ -483,6 +483,35 @@ int crt_debug_intersect(crt_ctx *ctx, const float *rays, size_t n, float *out);
  * The counters of crt_counters are not touched. */
 int crt_debug_trace_rays(crt_ctx *ctx, const float *rays, size_t n, uint32_t *out, uint64_t report[8]);
 int crt_debug_math(crt_ctx *ctx, int fn, const float *a, const float *b, float *out, size_t n);
+/* Test hook: the context's current acceleration structure, copied to the caller with plain device-to-host copies (no
+ * kernel runs).  `what` selects one part; *bytes (may be NULL) receives the part's size; out == NULL only reports it.
+ *   CRT_ACCEL_PART_HEADER        CRT_ACCEL_HEADER_N doubles (every value is an integer or a float, exact in a double):
+ *       [0] accel mode (CRT_ACCEL_NONE | CRT_ACCEL_BVH2: both builders make that structure), [1] builder (0 host SAH, 1 GPU
+ *       LBVH), [2] nprim, [3] root, [4] root4, [5] root8 (child references; -1: none), [6] [7] [8] inner nodes of the BVH2 /
+ *       the 4-wide / the 8-wide tree, [9] [10] [11] 1 = the float 4-wide / quantised 4-wide / quantised 8-wide nodes are
+ *       live on the device, [12..14] qbase, [15..17] qscale, [18] hit_pad, [19] tree_pad (the pad the boxes were made with),
+ *       [20] recorded depth of the BVH2, [21] of the 4-wide tree (the host collapse's, or the level count of the device
+ *       collapse), [22] of the 8-wide tree, [23] wf_depth (inner levels of the tree the wavefront kernels walk),
+ *       [24] stack entries a walk can need = (width - 1) x [23], [25] stack entries per lane in LDS, [26] overflow levels
+ *       the context asks for, [27] overflow levels allocated now (0 before the first trace call), [28] 1 = the tree is
+ *       stale (primitives updated, not refitted), [29] 1 = the all-device LBVH route built the tree (the host holds
+ *       statistics only)
+ *   CRT_ACCEL_PART_NODES2        [6] x 16 floats (crt_bvh.h: c0.lo c0.hi c1.lo c1.hi ref0 ref1 - -)
+ *   CRT_ACCEL_PART_NODES4        [7] x 32 floats where [9], else empty
+ *   CRT_ACCEL_PART_NODES4Q       [7] x 16 dwords where [10], else empty
+ *   CRT_ACCEL_PART_NODES8Q       [8] x 32 dwords where [11], else empty
+ *   CRT_ACCEL_PART_PRIM          nprim x 12 floats, the leaf-ordered records
+ *   CRT_ACCEL_PART_PRIMD         nprim x 4 floats
+ *   CRT_ACCEL_PART_SLOT_OF_INDEX nprim uint32
+ * Under CRT_ACCEL_NONE only the header, PRIM and SLOT_OF_INDEX are not empty.  Works on a stale tree (it shows the boxes
+ * as they are).  A sync point; it only reads: accumulator, sample count, counters and the tree stay as they are.
+ * CRT_ESTATE without a scene or accel structure, CRT_EINVAL for an unknown part or capacity below the part's size. */
+enum {
+    CRT_ACCEL_PART_HEADER = 0, CRT_ACCEL_PART_NODES2 = 1, CRT_ACCEL_PART_NODES4 = 2, CRT_ACCEL_PART_NODES4Q = 3,
+    CRT_ACCEL_PART_NODES8Q = 4, CRT_ACCEL_PART_PRIM = 5, CRT_ACCEL_PART_PRIMD = 6, CRT_ACCEL_PART_SLOT_OF_INDEX = 7
+};
+#define CRT_ACCEL_HEADER_N 32
+int crt_debug_read_accel(crt_ctx *ctx, int what, void *out, size_t capacity, size_t *bytes);
 /* Traversal-efficiency probes of the counting kernel variant (wave-level): inner iterations,
  * lanes active in them, leaf passes, lanes active in them, leaf loop trips, -, refills, lanes refilled. */
 int crt_debug_probes(crt_ctx *ctx, uint64_t out[8]);

@@ -278,3 +278,65 @@ def test_hook_refusals(renderer):
     renderer.refit_accel()
     t, i, vis, rep = renderer.debug_trace_rays(o, d)
     assert len(t) == 3 and rep["kernel"] == "k_wf_trace2" and not rep["counting"] and rep["deepest"] == 0
+
+
+def test_read_accel_refusals():
+    """crt_debug_read_accel: CRT_ESTATE without a scene or tree, CRT_EINVAL for an unknown part or a buffer that is too
+    small; a size query writes nothing; under CRT_ACCEL_NONE only the records and slot_of_index come back."""
+    import ctypes as C
+    from computeraytracer_amd import Renderer
+    from computeraytracer_amd._lib import CrtError
+    case = CASES["tiny5"]
+    with Renderer(0) as r:
+        for _ in range(2):                                      # no scene; a scene without a tree
+            with pytest.raises(CrtError, match="scene \\+ accel required") as e:
+                r.debug_read_accel()
+            assert e.value.code == -3
+            r.upload(TC.packed(case))
+        r.build_accel("none")
+        a = r.debug_read_accel()
+        assert (a["accel_mode"], a["nprim"], a["root"], a["root4"], a["root8"], a["n2"], a["n4"], a["n8"]) == (0, 5, -1, -1, -1, 0, 0, 0)
+        assert a["prim"].shape == (5, 12) and a["slot_of_index"].tolist() == [0, 1, 2, 3, 4]
+        assert all(len(a[k]) == 0 for k in ("nodes2", "nodes4", "nodes4q", "nodes8q", "primD"))
+        r.build_accel("bvh2")
+        lib, h = r._lib, r._h
+        nbytes = C.c_size_t(77)
+        assert lib.crt_debug_read_accel(h, 1, None, 0, C.byref(nbytes)) == 0 and nbytes.value == r.accel_stats()["nodes"] * 64 > 0
+        buf = np.full(nbytes.value // 4 + 1, 7.0, np.float32)
+        assert lib.crt_debug_read_accel(h, 1, buf.ctypes.data, nbytes.value - 1, None) == -1          # too small: nothing is written
+        assert b"the buffer" in lib.crt_last_error(h) and (buf == 7.0).all()
+        assert lib.crt_debug_read_accel(h, 1, buf.ctypes.data, nbytes.value, None) == 0 and buf[-1] == 7.0 and not (buf[:-1] == 7.0).all()
+        for part in (-1, 8, 99):
+            assert lib.crt_debug_read_accel(h, part, None, 0, C.byref(nbytes)) == -1 and nbytes.value == 0
+        assert lib.crt_debug_read_accel(h, 0, buf.ctypes.data, 8, None) == -1                         # the header too
+        assert lib.crt_debug_read_accel(None, 0, None, 0, None) == -1
+
+
+def test_read_accel_only_reads(renderer):
+    """Counters, accumulator, sample count and the tree itself are the same before and after crt_debug_read_accel, and
+    the render goes on from there bit for bit as it does without the call."""
+    from computeraytracer_amd import cornell
+    ps = cornell(32, 32)
+
+    def run(hook):
+        renderer.upload(ps).build_accel("lbvh")
+        renderer.enable_counters(True)
+        renderer.reset_counters()
+        renderer.frame(3).sync()
+        before = (renderer.counters(), renderer.sample, renderer.read_accum().copy(), renderer.accel_stats())
+        a = renderer.debug_read_accel() if hook else None
+        after = (renderer.counters(), renderer.sample, renderer.read_accum().copy(), renderer.accel_stats())
+        assert before[0] == after[0] and before[1] == after[1] == 3 and before[3] == after[3]
+        assert np.array_equal(bits(before[2]), bits(after[2]))
+        if hook:
+            b = renderer.debug_read_accel()
+            for k, v in a.items():
+                assert np.array_equal(np.atleast_1d(v).view(np.uint8), np.atleast_1d(b[k]).view(np.uint8)), k
+            assert a["n2"] == after[3]["nodes"] and a["n4"] == after[3]["wide_nodes"] and a["depth2"] == after[3]["max_depth"]
+        renderer.frame(2).sync()
+        assert renderer.sample == 5
+        return renderer.read_accum().copy()
+    try:
+        assert np.array_equal(bits(run(True)), bits(run(False)))
+    finally:
+        renderer.enable_counters(False)

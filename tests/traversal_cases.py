@@ -35,6 +35,7 @@ class Case:
     plane_y: float | None = None            # case 4: the triangles of the quad lie in y = plane_y
     flat: bool = False                      # every primitive in one plane: nothing can occlude, in-plane rays hit nothing
     shadow_close: float = 0.4               # share of the shadow rays that start between an occluder and the light, at any distance from it
+    shadow_near: float = 4e-3               # ... and the least such distance (a few float32 steps of the coordinates at the very least)
     shadow_exclude: int | None = None       # the plain shadow class excludes this primitive on every second ray (else a random one):
                                             # where only a copy of the light can hide it, the copy is "the surface the ray leaves"
     eye: np.ndarray | None = None           # camera eye (sets the scene scale the origins stay inside)
@@ -331,6 +332,54 @@ def case_deep(n=4096):
     return _finish(Case("deep_lbvh", tris(v0, v1, v2), lights=[rest[40]], shadow_close=0.9))
 
 
+CHAIN_J = 8                           # case_chain: index bits of its chain below the 30 code bits
+
+
+def chain_levels(J=CHAIN_J):
+    """(cell (n, 3), chain level (n,)) of case_chain's primitives; level -1: the filler in the last cell."""
+    n = (1 << J) + 3
+    cell = np.full((n, 3), 1023, np.int64)
+    level = np.full(n, -1, np.int64)
+    zero = {0: 29 + J, 1: 29 + J, 2: 29 + J, 3: 29 + J}           # cell 0: the index -> its chain level
+    for j in range(2, J + 1):
+        for m in range(3):
+            zero[(1 << j) + m] = 30 + (J - j)
+    for i, lv in zero.items():
+        cell[i], level[i] = 0, lv
+    rest = [i for i in range(n) if i not in zero]
+    for k in range(30):
+        j, axis = (29 - k) // 3, 2 - (29 - k) % 3                 # bit 2 of a triplet is x, bit 0 is z
+        for i in rest[3 * k:3 * k + 3]:
+            cell[i] = 0
+            cell[i, axis] = 1 << j
+            level[i] = k
+    return cell, level
+
+
+def case_chain(J=CHAIN_J, shadow_close=0.5):
+    """An LBVH that is a chain like case_deep's -- 30 splits on the code bits, then J - 1 on the index bits (cell 0 holds
+    the primitives 2^j, 2^j + 1, 2^j + 2 for j = J .. 2 and 0 .. 3) -- whose WIDE tree is as deep as the chain: at
+    every chain level the sibling subtree holds three triangles with one and the same box, a cube of half edge
+    60 000 - 1 000 x level around its cell, larger than the box of the whole rest of the chain (the cells lie within
+    [0, 1024), the next level's cubes are 2 000 narrower).  The collapse opens the larger child first, so a 4-wide node
+    takes the three triangles and the rest of the chain: one wide level per BVH2 level, 30 + J levels, and 3 x depth
+    passes the 16 + 96 stack entries the default overflow area gives k_wf_trace2.  The primitives left over (all of
+    level-0 size) fill the last cell, which also pins the box of the centres to [0.5, 1023.5]."""
+    cell, level = chain_levels(J)
+    n = len(cell)
+    rng = np.random.default_rng(9)
+    c = cell.astype(np.float64) + 0.5
+    h = np.repeat((60000.0 - 1000.0 * np.maximum(level, 0))[:, None], 3, 1)   # whole numbers: the box centre is exact
+    sx, sz = rng.choice([-1.0, 1.0], (2, n))
+    v0 = c + np.stack([-h[:, 0], -h[:, 1], -sz * h[:, 2]], 1)
+    v1 = c + np.stack([h[:, 0], -h[:, 1], sz * h[:, 2]], 1)
+    v2 = c + np.stack([sx * 0.0, h[:, 1], 0.0 * sz], 1)
+    # (the triangles lie in two families of parallel planes, z - x = const and z + x = const; a filler triangle of the
+    # second family is its outermost plane and can be seen from beyond it -- any other is hidden from nearly everywhere)
+    light = int(np.flatnonzero((level == -1) & (sz < 0))[-1])      # (its copies tie with it exactly: the last one wins)
+    return _finish(Case("chain_lbvh", tris(v0, v1, v2), lights=[light], shadow_close=shadow_close, shadow_near=16.0))
+
+
 def all_cases():
     return ([case_baseline()] + cases_tiny() + cases_coincident() + [case_grid()] + cases_degenerate() + cases_flat()
             + cases_unbounded() + [case_deep()])
@@ -528,7 +577,7 @@ class Rays:
             out.append(("box_plane", *self.box_plane(n), "none"))
         if self.case.plane_y is not None:
             out.append(("inside_many", *self.inside_many(n), "none"))
-        if self.case.name == "deep_lbvh":                         # from the region every box holds
+        if self.case.name in ("deep_lbvh", "chain_lbvh"):         # from the region every box holds
             o = self.rng.uniform(-40, 40, (n, 3)).astype(np.float32)
             out.append(("deep_centre", o, _unit(self.rng.normal(size=(n, 3))), "none"))
         return out
@@ -556,8 +605,9 @@ class Rays:
         q = self.diag[other[self.rng.integers(0, len(other), n)]].astype(np.float64) if len(other) else tgt
         s = self.rng.uniform(0.15, 0.9, (n, 1))
         # (close to the light too, from 0.004 units up: a dense scene blocks every long ray)
-        far = np.maximum(0.9 * np.linalg.norm(q - tgt, axis=1, keepdims=True), 8e-3)
-        s2 = np.exp(self.rng.uniform(np.log(4e-3), np.log(far))) / np.maximum(np.linalg.norm(q - tgt, axis=1, keepdims=True), 1e-30)
+        near = self.case.shadow_near
+        far = np.maximum(0.9 * np.linalg.norm(q - tgt, axis=1, keepdims=True), 2 * near)
+        s2 = np.exp(self.rng.uniform(np.log(near), np.log(far))) / np.maximum(np.linalg.norm(q - tgt, axis=1, keepdims=True), 1e-30)
         o = np.where(m == 0, self.origins(n, 1.0), np.where(m == 1, q + (q - tgt) * s, tgt + (q - tgt) * s2))
         h = ((o - tgt) * nrm).sum(1)
         graze = np.abs(h) < 0.2 * np.linalg.norm(o - tgt, axis=1)               # (nearly) in the light's plane, e.g. a coplanar q: lift it
