@@ -656,6 +656,94 @@ static napi_value js_denoise_temporal(napi_env env, napi_callback_info info)
     return denoise_result(env, &out, "history");
 }
 
+/* denoiseSvgfDefaults() -> {iterations, sigmaVariance, sigmaNormal, sigmaPlane, maxHistory, normalTol, planeTol, minFrames}.
+ * denoiseSvgf(h, {those, history, variance}) -> Uint8Array (tw*th*4 rgba8), or with history: true and / or variance: true
+ * -> {rgba8, history?, variance?: Float32Array(tw*th)}: denoiseTemporal's blend followed by the variance-guided passes, the
+ * variance taken from the temporal moments (include/crt.h "Variance-guided temporal filter").  A missing option takes the
+ * library's default.  denoiseSvgfAsync(h, {...}) -> Promise of the Uint8Array (below).
+ * readMoments(h) -> Float32Array (tw*th*4): (m1, s, Mw, 0) of the slot the last denoiseSvgf of this frame left. */
+static napi_value js_denoise_svgf_defaults(napi_env env, napi_callback_info info)
+{
+    (void)info;
+    crt_denoise_svgf_params p;
+    if (crt_denoise_svgf_defaults(&p) != CRT_OK) { napi_throw_error(env, NULL, "crt_denoise_svgf_defaults failed"); return NULL; }
+    const char *names[8] = {"iterations", "sigmaVariance", "sigmaNormal", "sigmaPlane", "maxHistory", "normalTol", "planeTol", "minFrames"};
+    const double values[8] = {p.iterations, p.sigma_variance, p.sigma_normal, p.sigma_plane, p.max_history, p.normal_tol, p.plane_tol,
+                              p.min_frames};
+    napi_value obj, v;
+    NAPI_OK(env, napi_create_object(env, &obj));
+    for (int k = 0; k < 8; k++) {
+        NAPI_OK(env, napi_create_double(env, values[k], &v));
+        NAPI_OK(env, napi_set_named_property(env, obj, names[k], v));
+    }
+    return obj;
+}
+
+static int denoise_svgf_options(napi_env env, napi_value opts, int have_opts, crt_denoise_svgf_params *p, bool *history, bool *variance)
+{
+    if (crt_denoise_svgf_defaults(p) != CRT_OK) { napi_throw_error(env, NULL, "crt_denoise_svgf_defaults failed"); return 0; }
+    double it = p->iterations, sv = p->sigma_variance, sn = p->sigma_normal, sx = p->sigma_plane, mh = p->max_history, nt = p->normal_tol,
+           pt = p->plane_tol, mf = p->min_frames;
+    const dn_opt o[] = {{"iterations", &it}, {"sigmaVariance", &sv}, {"sigmaNormal", &sn}, {"sigmaPlane", &sx}, {"maxHistory", &mh},
+                        {"normalTol", &nt}, {"planeTol", &pt}, {"minFrames", &mf}};
+    if (!denoise_options(env, "denoiseSvgf", opts, have_opts, o, 8, "history", history)) return 0;
+    if (variance) {                                             /* (the options object has passed denoise_options' checks) */
+        napi_valuetype t = napi_undefined;
+        napi_value v;
+        bool has = false;
+        *variance = false;
+        if (have_opts && napi_typeof(env, opts, &t) == napi_ok && t == napi_object &&
+            napi_has_named_property(env, opts, "variance", &has) == napi_ok && has &&
+            napi_get_named_property(env, opts, "variance", &v) == napi_ok)
+            napi_coerce_to_bool(env, v, &v), napi_get_value_bool(env, v, variance);
+    }
+    p->iterations = (uint32_t)it;
+    p->sigma_variance = (float)sv; p->sigma_normal = (float)sn; p->sigma_plane = (float)sx;
+    p->max_history = (float)mh; p->normal_tol = (float)nt; p->plane_tol = (float)pt; p->min_frames = (float)mf;
+    return 1;
+}
+
+static napi_value js_denoise_svgf(napi_env env, napi_callback_info info)
+{
+    DENOISE_ARGS
+    crt_denoise_svgf_params p;
+    bool history = false, variance = false;
+    if (!denoise_svgf_options(env, argc > 1 ? argv[1] : NULL, argc > 1, &p, &history, &variance)) return NULL;
+    dn_out out;
+    if (!denoise_outputs(env, ctx, history, &out)) return NULL;
+    void *var = NULL;
+    napi_value var_ab, ta, pta, obj;
+    if (variance) NAPI_OK(env, napi_create_arraybuffer(env, out.px * 4, &var, &var_ab));
+    CRT_CHECK(env, ctx, "crt_denoise_svgf", crt_denoise_svgf(ctx, &p, NULL, (uint8_t *)out.rgba8, (float *)out.plane, (float *)var));
+    if (!variance) return denoise_result(env, &out, "history");
+    NAPI_OK(env, napi_create_typedarray(env, napi_uint8_array, out.px * 4, out.rgba8_ab, 0, &ta));
+    NAPI_OK(env, napi_create_object(env, &obj));
+    NAPI_OK(env, napi_set_named_property(env, obj, "rgba8", ta));
+    if (history) {
+        NAPI_OK(env, napi_create_typedarray(env, napi_float32_array, out.px, out.plane_ab, 0, &pta));
+        NAPI_OK(env, napi_set_named_property(env, obj, "history", pta));
+    }
+    NAPI_OK(env, napi_create_typedarray(env, napi_float32_array, out.px, var_ab, 0, &pta));
+    NAPI_OK(env, napi_set_named_property(env, obj, "variance", pta));
+    return obj;
+}
+
+static napi_value js_read_moments(napi_env env, napi_callback_info info)
+{
+    ARGS(1)
+    crt_ctx *ctx = get_ctx(env, argv[0]);
+    if (!ctx) return NULL;
+    uint32_t tl[4];
+    CRT_CHECK(env, ctx, "crt_tile", crt_tile(ctx, tl));
+    size_t px = (size_t)tl[2] * tl[3];
+    void *data = NULL;
+    napi_value ab, ta;
+    NAPI_OK(env, napi_create_arraybuffer(env, px * 16, &data, &ab));
+    CRT_CHECK(env, ctx, "crt_debug_read_moments", crt_debug_read_moments(ctx, (float *)data));
+    NAPI_OK(env, napi_create_typedarray(env, napi_float32_array, px * 4, ab, 0, &ta));
+    return ta;
+}
+
 static napi_value js_read_gbuffer(napi_env env, napi_callback_info info)
 {
     ARGS(1)
@@ -999,7 +1087,7 @@ static napi_value js_set_stream(napi_env env, napi_callback_info info)
  * fire-and-forget (queue.submit, src/main.js:618-620): a Node display loop must not block its event loop on the
  * GPU either.  Jobs of one context run in call order. */
 enum { JOB_TRACE, JOB_SYNC, JOB_READ_RGBA8, JOB_READ_ACCUM, JOB_GATHER, JOB_READ_FRAME_RGBA8, JOB_READ_FRAME_ACCUM, JOB_READ_SAMPLE_RGBA8,
-       JOB_DENOISE_ADAPTIVE, JOB_DENOISE_TEMPORAL };
+       JOB_DENOISE_ADAPTIVE, JOB_DENOISE_TEMPORAL, JOB_DENOISE_SVGF };
 typedef struct job {
     napi_async_work work;
     napi_deferred deferred;
@@ -1008,6 +1096,7 @@ typedef struct job {
     uint32_t n, px;
     crt_denoise_adaptive_params dn;     /* JOB_DENOISE_ADAPTIVE */
     crt_denoise_temporal_params dt;     /* JOB_DENOISE_TEMPORAL */
+    crt_denoise_svgf_params ds;         /* JOB_DENOISE_SVGF */
     void *data;              /* ArrayBuffer memory of a read job (kept alive by ab_ref) */
     napi_ref ab_ref;
     char err[640];
@@ -1029,6 +1118,7 @@ static void job_execute(napi_env env, void *data)
     case JOB_READ_SAMPLE_RGBA8: j->rc = crt_read_sample_rgba8(ctx, j->n, (uint8_t *)j->data); break;
     case JOB_DENOISE_ADAPTIVE: j->rc = crt_denoise_adaptive(ctx, &j->dn, NULL, (uint8_t *)j->data, NULL); break;
     case JOB_DENOISE_TEMPORAL: j->rc = crt_denoise_temporal(ctx, &j->dt, NULL, (uint8_t *)j->data, NULL); break;
+    case JOB_DENOISE_SVGF: j->rc = crt_denoise_svgf(ctx, &j->ds, NULL, (uint8_t *)j->data, NULL, NULL); break;
     default: j->rc = crt_read_frame_accum(ctx, (float *)j->data); break;
     }
     if (j->rc != CRT_OK) {
@@ -1047,7 +1137,7 @@ static void job_complete(napi_env env, napi_status status, void *data)
         if (j->ab_ref) {
             napi_value ab;
             const int bytes8 = j->op == JOB_READ_RGBA8 || j->op == JOB_READ_FRAME_RGBA8 || j->op == JOB_READ_SAMPLE_RGBA8 ||
-                               j->op == JOB_DENOISE_ADAPTIVE || j->op == JOB_DENOISE_TEMPORAL;
+                               j->op == JOB_DENOISE_ADAPTIVE || j->op == JOB_DENOISE_TEMPORAL || j->op == JOB_DENOISE_SVGF;
             if (napi_get_reference_value(env, j->ab_ref, &ab) == napi_ok)
                 napi_create_typedarray(env, bytes8 ? napi_uint8_array : napi_float32_array, (size_t)j->px * 4, ab, 0, &result);
         }
@@ -1083,14 +1173,15 @@ static napi_value start_job(napi_env env, napi_callback_info info, int op)
     j->sl = sl; j->op = op;
     if (op == JOB_DENOISE_ADAPTIVE && !denoise_adaptive_options(env, argc > 1 ? argv[1] : NULL, argc > 1, &j->dn, NULL)) { free(j); return NULL; }
     if (op == JOB_DENOISE_TEMPORAL && !denoise_temporal_options(env, argc > 1 ? argv[1] : NULL, argc > 1, &j->dt, NULL)) { free(j); return NULL; }
+    if (op == JOB_DENOISE_SVGF && !denoise_svgf_options(env, argc > 1 ? argv[1] : NULL, argc > 1, &j->ds, NULL, NULL)) { free(j); return NULL; }
     if (op == JOB_TRACE || op == JOB_GATHER || op == JOB_READ_SAMPLE_RGBA8) {
         if (napi_get_value_uint32(env, argv[1], &j->n) != napi_ok) { free(j); napi_throw_type_error(env, NULL, "traceAsync / gatherAsync: a number expected"); return NULL; }
     }
     if (op == JOB_READ_RGBA8 || op == JOB_READ_ACCUM || op == JOB_READ_FRAME_RGBA8 || op == JOB_READ_FRAME_ACCUM || op == JOB_READ_SAMPLE_RGBA8 ||
-        op == JOB_DENOISE_ADAPTIVE || op == JOB_DENOISE_TEMPORAL) {
+        op == JOB_DENOISE_ADAPTIVE || op == JOB_DENOISE_TEMPORAL || op == JOB_DENOISE_SVGF) {
         const int frame = op == JOB_READ_FRAME_RGBA8 || op == JOB_READ_FRAME_ACCUM;
         const int bytes8 = op == JOB_READ_RGBA8 || op == JOB_READ_FRAME_RGBA8 || op == JOB_READ_SAMPLE_RGBA8 || op == JOB_DENOISE_ADAPTIVE ||
-                           op == JOB_DENOISE_TEMPORAL;
+                           op == JOB_DENOISE_TEMPORAL || op == JOB_DENOISE_SVGF;
         uint32_t t[4];
         if (frame) { if (crt_image_size(sl->ctx, t + 2) != CRT_OK) { free(j); return throw_crt(env, sl->ctx, CRT_ESTATE, "crt_image_size"); } }
         else if (crt_tile(sl->ctx, t) != CRT_OK) { free(j); return throw_crt(env, sl->ctx, CRT_ESTATE, "crt_tile"); }
@@ -1132,6 +1223,7 @@ static napi_value js_read_frame_rgba8_async(napi_env env, napi_callback_info inf
 static napi_value js_read_frame_accum_async(napi_env env, napi_callback_info info) { return start_job(env, info, JOB_READ_FRAME_ACCUM); }
 static napi_value js_denoise_adaptive_async(napi_env env, napi_callback_info info) { return start_job(env, info, JOB_DENOISE_ADAPTIVE); }
 static napi_value js_denoise_temporal_async(napi_env env, napi_callback_info info) { return start_job(env, info, JOB_DENOISE_TEMPORAL); }
+static napi_value js_denoise_svgf_async(napi_env env, napi_callback_info info) { return start_job(env, info, JOB_DENOISE_SVGF); }
 
 static napi_value js_abi_version(napi_env env, napi_callback_info info)
 {
@@ -1168,6 +1260,8 @@ static napi_value init(napi_env env, napi_value exports)
         {"denoiseAdaptive", js_denoise_adaptive}, {"denoiseAdaptiveAsync", js_denoise_adaptive_async},
         {"setSampleOffset", js_set_sample_offset}, {"sampleOffset", js_sample_offset}, {"temporalReset", js_temporal_reset},
         {"denoiseTemporal", js_denoise_temporal}, {"denoiseTemporalAsync", js_denoise_temporal_async},
+        {"denoiseSvgfDefaults", js_denoise_svgf_defaults}, {"denoiseSvgf", js_denoise_svgf}, {"denoiseSvgfAsync", js_denoise_svgf_async},
+        {"readMoments", js_read_moments},
         {"gatherAsync", js_gather_async}, {"readFrameRgba8Async", js_read_frame_rgba8_async}, {"readFrameAccumAsync", js_read_frame_accum_async},
     };
     for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++) {

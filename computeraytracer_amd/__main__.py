@@ -1,4 +1,4 @@
-"""python -m computeraytracer_amd [--scene file.json] [--width W --height H] [--spp N] [--out image.png] [--denoise K] [--orbit N [--temporal [--animate]]]
+"""python -m computeraytracer_amd [--scene file.json] [--width W --height H] [--spp N] [--out image.png] [--denoise K] [--orbit N [--temporal [--variance] [--animate]]]
                                 [--adaptive THRESHOLD [--adaptive-step N] [--counts-out counts.png]]"""
 import argparse
 import json
@@ -26,6 +26,9 @@ def main():
     ap.add_argument("--temporal", action="store_true",
                     help="with --orbit and --denoise K: frame k draws samples k * spp + 1 .. (set_sample_offset) and is blended "
                          "with the reprojected result of frame k - 1 before the filter (crt_denoise_temporal)")
+    ap.add_argument("--variance", action="store_true",
+                    help="with --orbit N --denoise K --temporal: the passes after the blend are variance-guided, the variance "
+                         "taken from the spread of the frame means (crt_denoise_svgf)")
     ap.add_argument("--animate", action="store_true",
                     help="with --orbit N --denoise K --temporal: before frame k every sphere is moved to its frame-0 centre plus "
                          "(0, 0.5 radius sin(2 pi k / 16), 0) (update_primitives + refit_accel), and option temporal_motion keeps "
@@ -42,6 +45,8 @@ def main():
         ap.error("--orbit needs N >= 1 and no --checkpoint")
     if args.temporal and (args.orbit is None or args.denoise is None):
         ap.error("--temporal goes with --orbit N --denoise K")
+    if args.variance and not args.temporal:
+        ap.error("--variance goes with --orbit N --denoise K --temporal")
     if args.animate and not args.temporal:
         ap.error("--animate goes with --orbit N --denoise K --temporal")
     if args.adaptive is not None and (args.orbit is not None or args.checkpoint):
@@ -73,7 +78,7 @@ def main():
                     r.set_sample_offset(k * args.spp)
                 r.frame(args.spp).sync()
                 if args.temporal:
-                    rgba = r.denoise_temporal(args.denoise)
+                    rgba = r.denoise_svgf(args.denoise) if args.variance else r.denoise_temporal(args.denoise)
                 else:
                     rgba = r.read_rgba8() if args.denoise is None else r.denoise(args.denoise)
                 outs.append(f"{base}_{k:03d}{ext}")
@@ -84,6 +89,8 @@ def main():
                 info["denoise"] = args.denoise
             if args.temporal:
                 info["temporal"] = True
+            if args.variance:
+                info["variance"] = True
             if args.animate:
                 info["animate"] = True
             print(json.dumps(info))

@@ -86,6 +86,9 @@ SIGNATURES = {
     "crt_denoise_temporal": (C.c_int, [_P, _P, _P, _P, _P]),
     "crt_denoise_temporal_defaults": (C.c_int, [_P]),
     "crt_denoise_temporal_reset": (C.c_int, [_P]),
+    "crt_denoise_svgf": (C.c_int, [_P, _P, _P, _P, _P, _P]),
+    "crt_denoise_svgf_defaults": (C.c_int, [_P]),
+    "crt_debug_read_moments": (C.c_int, [_P, _P]),
 }
 
 
@@ -131,6 +134,20 @@ def denoise_temporal_defaults() -> DenoiseTemporalParams:
     p = DenoiseTemporalParams()
     if load().crt_denoise_temporal_defaults(C.byref(p)) != 0:
         raise RuntimeError("crt_denoise_temporal_defaults failed")
+    return p
+
+
+class DenoiseSvgfParams(C.Structure):
+    """crt_denoise_svgf_params of include/crt.h."""
+    _fields_ = [("iterations", C.c_uint32), ("sigma_variance", C.c_float), ("sigma_normal", C.c_float), ("sigma_plane", C.c_float),
+                ("max_history", C.c_float), ("normal_tol", C.c_float), ("plane_tol", C.c_float), ("min_frames", C.c_float)]
+
+
+def denoise_svgf_defaults() -> DenoiseSvgfParams:
+    """The library's defaults for crt_denoise_svgf (crt_denoise_svgf_defaults)."""
+    p = DenoiseSvgfParams()
+    if load().crt_denoise_svgf_defaults(C.byref(p)) != 0:
+        raise RuntimeError("crt_denoise_svgf_defaults failed")
     return p
 
 

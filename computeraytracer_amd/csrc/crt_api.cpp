@@ -243,10 +243,14 @@ struct crt_ctx {
         DevBuf<float4> c;           // blended linear rgb before any spatial filter, w = its weight Hw in samples
         DevBuf<float4> gbuf;
         DevBuf<uint32_t> key;
+        DevBuf<float4> m;           // crt_denoise_svgf: (m1, s, Mw, 0), the temporal moments of the luminance
         float cam[12] = {0};        // that frame's camera_frame
         bool valid = false;
+        bool has_m = false;         // m belongs to this slot (a crt_denoise_svgf wrote it)
     } th_prev;
     DevBuf<float4> th_cur_c;        // CURRENT: (c, Hw)
+    DevBuf<float4> th_cur_m;        // ... and its moments, while th_cur_has_m
+    bool th_cur_has_m = false;
     float th_cur_cam[12] = {0};
     bool th_cur_valid = false;
     uint32_t th_cur_frame = 0;      // frame_id it was made in
@@ -334,6 +338,7 @@ int alloc_frames(crt_ctx *c)
 void th_drop(crt_ctx *c)
 {
     c->th_prev.valid = false; c->th_cur_valid = false; c->th_parked = false;
+    c->th_prev.has_m = false; c->th_cur_has_m = false;
     c->th_snap.release(); c->th_snap_of = crt_ctx::TH_SNAP_NONE;
 }
 
@@ -1793,6 +1798,7 @@ void crt_destroy(crt_ctx *c)
     c->dn_kv.release(); c->dn_var.release();
     c->th_prev.c.release(); c->th_prev.gbuf.release(); c->th_prev.key.release(); c->th_cur_c.release();
     c->th_park_gbuf.release(); c->th_park_key.release(); c->th_hist.release(); c->th_snap.release(); c->th_uv.release();
+    c->th_prev.m.release(); c->th_cur_m.release();
     c->rf_lv2.release(); c->rf_lv4.release(); c->rf_nch4.release(); c->rf_cnt.release(); c->rf_fb.release();
     c->as_counts.release(); c->as_errors.release(); c->as_flags.release(); c->as_active.release(); c->as_n.release(); c->as_q.release();
     if (c->pub_stream) (void)hipStreamSynchronize(c->pub_stream);
@@ -2712,6 +2718,74 @@ static DnReprojParams th_reproj_params(crt_ctx *c, const float4 *gbuf, const uin
     return P;
 }
 
+// What crt_denoise_temporal and crt_denoise_svgf share once dn_begin has passed: the buffers, the promotion of CURRENT, the
+// G-buffer, the blend and the passes after it.  svgf: also the moments and the variance-guided passes.
+struct ThCall {
+    uint32_t iterations;
+    float sigma_normal, sigma_plane, max_history, normal_tol, plane_tol;
+    bool svgf;
+    float sigma_color;                  // !svgf
+    float sigma_variance, min_frames;   // svgf
+};
+
+static int th_blend_and_filter(crt_ctx *c, const ThCall &t, bool rgba, bool hist, bool var, float4 **res)
+{
+    const size_t n = (size_t)c->tw * c->th;
+    // every buffer first: a failed allocation leaves the slots as they were
+    DN_ENSURE(c, th_cur_c, n);
+    DN_ENSURE(c, th_prev.c, n);
+    { int rc = dn_ensure_buffers(c, n); if (rc) return rc; }
+    DN_ENSURE(c, th_hist, n);
+    if (t.svgf) {
+        DN_ENSURE(c, th_cur_m, n);
+        DN_ENSURE(c, th_prev.m, n);
+        DN_ENSURE(c, dn_kv, n);
+        DN_ENSURE(c, dn_var, n);
+    }
+    // the first call of a new frame: CURRENT becomes PREVIOUS, by pointer
+    if (c->th_cur_valid && c->th_cur_frame != c->frame_id) {
+        if (c->th_parked) {
+            std::swap(c->th_prev.gbuf, c->th_park_gbuf); std::swap(c->th_prev.key, c->th_park_key);
+        } else {
+            std::swap(c->th_prev.gbuf, c->dn_gbuf); std::swap(c->th_prev.key, c->dn_key);
+            c->dn_valid = false;                             // (what came back is an older frame's: rebuilt below)
+        }
+        std::swap(c->th_prev.c, c->th_cur_c);
+        std::swap(c->th_prev.m, c->th_cur_m);
+        c->th_prev.has_m = c->th_cur_has_m;
+        std::memcpy(c->th_prev.cam, c->th_cur_cam, sizeof c->th_prev.cam);
+        c->th_prev.valid = true;
+        c->th_cur_valid = false; c->th_parked = false;
+        // a snapshot taken for that slot is now PREVIOUS's geometry; an older one went with the slot it belonged to
+        c->th_snap_of = c->th_snap_of == crt_ctx::TH_SNAP_CURRENT ? crt_ctx::TH_SNAP_PREVIOUS : crt_ctx::TH_SNAP_NONE;
+    }
+    c->th_cur_valid = false;                                 // (rewritten below: a rebuild of the G-buffer has nothing to park)
+    c->th_cur_has_m = false;
+    { int rc = dn_ensure_gbuffer(c); if (rc) return rc; }
+    DnSvgfParams P{};
+    static_cast<DnReprojParams &>(P) = th_reproj_params(c, c->dn_gbuf.p, c->dn_key.p);
+    P.accum = accum_ptr(c);
+    P.h_cur = c->th_cur_c.p;
+    P.hist = hist ? c->th_hist.p : nullptr;
+    P.n = (float)c->sample;
+    P.max_history = t.max_history;
+    P.normal_tol2 = (float)std::min(3.0e38, (double)t.normal_tol * t.normal_tol);
+    P.plane_tol = t.plane_tol;
+    const DnFilter F = dn_filter(c, t.iterations, t.sigma_normal, t.sigma_plane, rgba);
+    if (t.svgf) {
+        P.m_prev = P.h_prev && c->th_prev.has_m ? c->th_prev.m.p : nullptr;
+        P.m_cur = c->th_cur_m.p;
+        P.min_frames = t.min_frames;
+        HIPCHK(c, dn_launch_svgf(F, P, c->dn_kv.p, var ? c->dn_var.p : nullptr, t.sigma_variance, res));
+    } else {
+        HIPCHK(c, dn_launch_temporal(F, P, t.sigma_color, res));
+    }
+    std::memcpy(c->th_cur_cam, c->sc.cam, sizeof c->th_cur_cam);
+    c->th_cur_valid = true; c->th_cur_frame = c->frame_id; c->th_gen = c->dn_gen; c->th_parked = false;
+    c->th_cur_has_m = t.svgf;
+    return CRT_OK;
+}
+
 int crt_denoise_temporal(crt_ctx *c, const crt_denoise_temporal_params *params, float *rgb_out, uint8_t *rgba8_out, float *history_out)
 {
     const crt_denoise_temporal_params dp = params ? *params : kDnTpDefaults;
@@ -2724,45 +2798,58 @@ int crt_denoise_temporal(crt_ctx *c, const crt_denoise_temporal_params *params, 
     if (rgb_out && dp.iterations > 0 && !history_out) hw.resize(n);
     float *hw_host = history_out ? history_out : hw.empty() ? nullptr : hw.data();
     if (n) {
-        // every buffer first: a failed allocation leaves the slots as they were
-        DN_ENSURE(c, th_cur_c, n);
-        DN_ENSURE(c, th_prev.c, n);
-        { int rc = dn_ensure_buffers(c, n); if (rc) return rc; }
-        DN_ENSURE(c, th_hist, n);
-        // the first call of a new frame: CURRENT becomes PREVIOUS, by pointer
-        if (c->th_cur_valid && c->th_cur_frame != c->frame_id) {
-            if (c->th_parked) {
-                std::swap(c->th_prev.gbuf, c->th_park_gbuf); std::swap(c->th_prev.key, c->th_park_key);
-            } else {
-                std::swap(c->th_prev.gbuf, c->dn_gbuf); std::swap(c->th_prev.key, c->dn_key);
-                c->dn_valid = false;                             // (what came back is an older frame's: rebuilt below)
-            }
-            std::swap(c->th_prev.c, c->th_cur_c);
-            std::memcpy(c->th_prev.cam, c->th_cur_cam, sizeof c->th_prev.cam);
-            c->th_prev.valid = true;
-            c->th_cur_valid = false; c->th_parked = false;
-            // a snapshot taken for that slot is now PREVIOUS's geometry; an older one went with the slot it belonged to
-            c->th_snap_of = c->th_snap_of == crt_ctx::TH_SNAP_CURRENT ? crt_ctx::TH_SNAP_PREVIOUS : crt_ctx::TH_SNAP_NONE;
-        }
-        c->th_cur_valid = false;                                 // (rewritten below: a rebuild of the G-buffer has nothing to park)
-        { int rc = dn_ensure_gbuffer(c); if (rc) return rc; }
-        DnReprojParams P = th_reproj_params(c, c->dn_gbuf.p, c->dn_key.p);
-        P.accum = accum_ptr(c);
-        P.h_cur = c->th_cur_c.p;
-        P.hist = history_out || rgb_out ? c->th_hist.p : nullptr;
-        P.n = (float)c->sample;
-        P.max_history = dp.max_history;
-        P.normal_tol2 = (float)std::min(3.0e38, (double)dp.normal_tol * dp.normal_tol);
-        P.plane_tol = dp.plane_tol;
-        const DnFilter F = dn_filter(c, dp.iterations, dp.sigma_normal, dp.sigma_plane, rgba8_out != nullptr);
-        HIPCHK(c, dn_launch_temporal(F, P, dp.sigma_color, &res));
-        std::memcpy(c->th_cur_cam, c->sc.cam, sizeof c->th_cur_cam);
-        c->th_cur_valid = true; c->th_cur_frame = c->frame_id; c->th_gen = c->dn_gen; c->th_parked = false;
+        const ThCall t{dp.iterations, dp.sigma_normal, dp.sigma_plane, dp.max_history, dp.normal_tol, dp.plane_tol, false,
+                       dp.sigma_color, 0.0f, 0.0f};
+        const int rc = th_blend_and_filter(c, t, rgba8_out != nullptr, history_out || rgb_out, false, &res);
+        if (rc) return rc;
     }
     const int rc = dn_finish(c, n, res, rgb_out, rgba8_out, c->th_hist.p, hw_host);
     if (rgb_out && dp.iterations > 0)
         for (size_t i = 0; i < n; i++) rgb_out[4 * i + 3] = hw_host[i];
     return rc;
+}
+
+// sigma_variance 4, min_frames 4: DESIGN.md 6g has the sweep they were chosen by.
+static const crt_denoise_svgf_params kDnSvgfDefaults = {5u, 4.0f, 0.5f, 0.3f, 64.0f, 0.5f, 2.0f, 4.0f};
+
+int crt_denoise_svgf_defaults(crt_denoise_svgf_params *out)
+{
+    if (!out) return CRT_EINVAL;
+    *out = kDnSvgfDefaults;
+    return CRT_OK;
+}
+
+int crt_denoise_svgf(crt_ctx *c, const crt_denoise_svgf_params *params, float *rgb_out, uint8_t *rgba8_out, float *history_out,
+                     float *var_out)
+{
+    const crt_denoise_svgf_params dp = params ? *params : kDnSvgfDefaults;
+    const float pos[6] = {dp.sigma_variance, dp.sigma_normal, dp.sigma_plane, dp.max_history, dp.normal_tol, dp.plane_tol};
+    if (c && !(dp.min_frames >= 2.0f && dp.min_frames <= 3.40282347e38f))
+        return fail(c, CRT_EINVAL, "crt_denoise_svgf: min_frames must be >= 2 and finite");
+    { int rc = dn_begin(c, "crt_denoise_svgf", dp.iterations, pos, 6, "every sigma, tolerance and max_history", DN_UNIFORM);
+      if (rc) return rc; }
+    const size_t n = (size_t)c->tw * c->th;
+    float4 *res = nullptr;
+    if (n) {
+        const ThCall t{dp.iterations, dp.sigma_normal, dp.sigma_plane, dp.max_history, dp.normal_tol, dp.plane_tol, true,
+                       0.0f, dp.sigma_variance, dp.min_frames};
+        const int rc = th_blend_and_filter(c, t, rgba8_out != nullptr, history_out != nullptr, var_out != nullptr, &res);
+        if (rc) return rc;
+        if (var_out) HIPCHK(c, hipMemcpyAsync(var_out, c->dn_var.p, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    }
+    return dn_finish(c, n, res, rgb_out, rgba8_out, c->th_hist.p, history_out);
+}
+
+int crt_debug_read_moments(crt_ctx *c, float *out)
+{
+    if (!c || !out) return CRT_EINVAL;
+    { int rc = dn_begin(c, "crt_debug_read_moments", 0, nullptr, 0, "", DN_UNIFORM); if (rc) return rc; }
+    if (!c->th_cur_valid || c->th_cur_frame != c->frame_id || !c->th_cur_has_m)
+        return fail(c, CRT_ESTATE, "crt_debug_read_moments: no crt_denoise_svgf in this frame yet, or a crt_denoise_temporal after it "
+                                   "(the CURRENT slot carries no moments)");
+    const size_t n = (size_t)c->tw * c->th;
+    if (n) HIPCHK(c, hipMemcpyAsync(out, c->th_cur_m.p, n * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+    return dn_finish(c, n, nullptr, nullptr, nullptr);
 }
 
 int crt_read_motion(crt_ctx *c, float *out)

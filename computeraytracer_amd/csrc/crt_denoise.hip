@@ -6,6 +6,7 @@
 // crt_denoise_adaptive is the same filter for the adaptive state: per-tile counts, and a colour weight
 // scaled by the pixels' own variance (k_dn_prepare_as, k_dn_vblur, k_dn_atrous_as below).
 #include <algorithm>
+#include <type_traits>
 
 #include "crt_adaptive.h"
 #include "crt_shade.h"
@@ -356,9 +357,12 @@ __device__ __forceinline__ bool dn_film_position(const DnReprojParams &P, f3 x_p
 
 // k_dn_prepare's work, the reprojection into the previous frame and the blend in one pass: grid as k_dn_atrous.  The
 // pixel's own guides stay in registers; a tap's history and G-buffer are fetched only when its key matches.
-// <false>: PREVIOUS saw the scene as it is (6e alone); <true>: PREVIOUS has a geometry snapshot (6f).
-template <bool MOTION>
-__global__ __launch_bounds__(256) void k_dn_reproject(const DnReprojParams P)
+// <false, *>: PREVIOUS saw the scene as it is (6e alone); <true, *>: PREVIOUS has a geometry snapshot (6f).
+// <*, true> (crt_denoise_svgf; tests/denoise_svgf_ref.py): the accepted taps also carry the temporal moments
+// of the luminance -- one more float4 per tap that passed every test -- and the variance they give goes out as the w of
+// the filter's input P.cv.  What reaches P.h_cur is <*, false>'s bit for bit.
+template <bool MOTION, bool MOMENTS>
+__global__ __launch_bounds__(256) void k_dn_reproject(const std::conditional_t<MOMENTS, DnSvgfParams, DnReprojParams> P)
 {
     const int x = dn_x16(), y = dn_y16();
     const int tw = (int)P.tw, th = (int)P.th;
@@ -368,6 +372,8 @@ __global__ __launch_bounds__(256) void k_dn_reproject(const DnReprojParams P)
     const f3 c_new = xyz_to_linear_rgb(f3{a.x, a.y, a.z} / P.n);
     f3 c = c_new;
     float Hw = P.n;
+    const float lum = a.y / P.n;                                // y of 6g: the frame's mean luminance
+    float m1 = lum, ms = 0.0f, Mw = P.n;                          // (MOMENTS only)
     const uint32_t key_p = P.key[p];
     if (P.h_prev && key_p != kNoHit && (key_p >> 24) != kGlass && finite4(float4{c_new.x, c_new.y, c_new.z, 0.0f})) {
         const float4 g0 = P.gbuf[2 * p], g1 = P.gbuf[2 * p + 1];
@@ -387,6 +393,7 @@ __global__ __launch_bounds__(256) void k_dn_reproject(const DnReprojParams P)
                 const float plane_max = P.plane_tol * r_p;
                 float sw = 0.0f, sh = 0.0f;
                 f3 sc = f3{0, 0, 0};
+                f3 sm = f3{0, 0, 0};                            // (MOMENTS only) sums of w m1', w s', w Mw'
 #pragma unroll
                 for (int dy = 0; dy < 2; dy++) {
                     const int qy = iy + dy;
@@ -407,6 +414,12 @@ __global__ __launch_bounds__(256) void k_dn_reproject(const DnReprojParams P)
                         sw = sw + w;
                         sc = sc + f3{hq.x, hq.y, hq.z} * w;
                         sh = sh + w * hq.w;
+                        if constexpr (MOMENTS) {
+                            if (P.m_prev) {
+                                const float4 mq = P.m_prev[q];
+                                sm = sm + f3{mq.x, mq.y, mq.z} * w;
+                            }
+                        }
                     }
                 }
                 if (sw > 0.0f) {
@@ -414,6 +427,16 @@ __global__ __launch_bounds__(256) void k_dn_reproject(const DnReprojParams P)
                     const float Hp = min_(sh / sw, P.max_history);
                     Hw = P.n + Hp;
                     c = (c_new * P.n + h * Hp) / Hw;
+                    if constexpr (MOMENTS) {
+                        if (P.m_prev) {                         // the pairwise merge of (lum, 0, n) with the taps' (h1, hs, Mp)
+                            const float h1 = sm.x / sw, hs = sm.y / sw;
+                            const float Mp = min_(sm.z / sw, P.max_history);
+                            const float d = lum - h1;
+                            Mw = P.n + Mp;
+                            m1 = (lum * P.n + h1 * Mp) / Mw;
+                            ms = (Mp / Mw) * hs + ((P.n * Mp) * (d * d)) / (Mw * Mw);
+                        }
+                    }
                 }
             }
         }
@@ -421,6 +444,20 @@ __global__ __launch_bounds__(256) void k_dn_reproject(const DnReprojParams P)
     P.h_cur[p] = float4{c.x, c.y, c.z, Hw};
     if (P.rgba) P.rgba[p] = linear_rgb_to_rgba8(c);
     if (P.hist) P.hist[p] = Hw;
+    if constexpr (MOMENTS) {
+        // the variance of the blend in display units: s / (F - 1) over F = Mw / n frames, through the exposure curve's slope
+        // at m1 (as pixel_error); 1 ("nothing known", as k_dn_prepare_as) below min_frames or where it is not finite
+        float v = 1.0f;
+        const float F = Mw / P.n;
+        if (F >= P.min_frames) {
+            const float g = 2.2f * exp_(-2.2f * max_(m1, 0.0f));
+            const float t = (g * g) * (ms / (F - 1.0f));
+            if (dn_finite(t)) v = t;
+        }
+        P.m_cur[p] = float4{m1, ms, Mw, 0.0f};
+        P.cv[p] = float4{c.x, c.y, c.z, v};
+        if (P.var) P.var[p] = v;
+    }
 }
 
 // crt_read_motion: where the blend above looks for each pixel in the PREVIOUS slot -- (u, v) rounded to float, NaN where
@@ -503,8 +540,8 @@ hipError_t dn_launch_temporal(const DnFilter &F, DnReprojParams P, float sigma_c
     *out = P.h_cur;
     if ((size_t)F.tw * F.th == 0) return hipSuccess;
     P.rgba = F.iterations == 0 ? F.rgba : nullptr;
-    if (P.raw_prev) hipLaunchKernelGGL(k_dn_reproject<true>, dn_grid16(F), dim3(256), 0, F.stream, P);
-    else hipLaunchKernelGGL(k_dn_reproject<false>, dn_grid16(F), dim3(256), 0, F.stream, P);
+    if (P.raw_prev) hipLaunchKernelGGL((k_dn_reproject<true, false>), dn_grid16(F), dim3(256), 0, F.stream, P);
+    else hipLaunchKernelGGL((k_dn_reproject<false, false>), dn_grid16(F), dim3(256), 0, F.stream, P);
     const hipError_t e = hipGetLastError();
     return e != hipSuccess ? e : dn_run_atrous(F, P.h_cur, sigma_color, out);
 }
@@ -519,18 +556,13 @@ hipError_t dn_launch_motion(const DnReprojParams &P, float2 *out, hipStream_t st
     return hipGetLastError();
 }
 
-// The adaptive state's filter: (accum, q, counts) -> c[0] with v in w, then per iteration the variance blur into kv and
-// the filter pass between c[0] and c[1]; the last launch also writes rgba and var (either may be null).
-hipError_t dn_launch_filter_adaptive(const DnFilter &F, const float4 *accum, const float *q, const uint32_t *counts, uint2 *kv,
-                                     float *var, float sigma_variance, float4 **out)
+// F.iterations times (k_dn_vblur into kv, k_dn_atrous_as) on the (c, v) in F.c[0], between F.c[0] and F.c[1]; the last
+// launch also writes rgba and var (either may be null).  Leaves the buffer that holds the result in *out.
+static hipError_t dn_run_atrous_as(const DnFilter &F, uint2 *kv, float *var, float sigma_variance, float4 **out)
 {
     const uint32_t tw = F.tw, th = F.th;
+    hipError_t e = hipSuccess;
     *out = F.c[0];
-    if ((size_t)tw * th == 0) return hipSuccess;
-    const bool last0 = F.iterations == 0;
-    hipLaunchKernelGGL(k_dn_prepare_as, dim3((tw + 63u) / 64u, (th + 3u) / 4u), dim3(256), 0, F.stream, accum, q, counts, tw, th,
-                       (tw + 7u) / 8u, F.c[0], last0 ? F.rgba : nullptr, last0 ? var : nullptr);
-    hipError_t e = hipGetLastError();
     for (uint32_t i = 0; i < F.iterations && e == hipSuccess; i++) {
         DnAsParams P{};
         P.c_in = F.c[i & 1u]; P.c_out = F.c[(i + 1u) & 1u];
@@ -549,6 +581,36 @@ hipError_t dn_launch_filter_adaptive(const DnFilter &F, const float4 *accum, con
         *out = P.c_out;
     }
     return e;
+}
+
+// The adaptive state's filter: (accum, q, counts) -> c[0] with v in w, then the variance-guided passes.
+hipError_t dn_launch_filter_adaptive(const DnFilter &F, const float4 *accum, const float *q, const uint32_t *counts, uint2 *kv,
+                                     float *var, float sigma_variance, float4 **out)
+{
+    const uint32_t tw = F.tw, th = F.th;
+    *out = F.c[0];
+    if ((size_t)tw * th == 0) return hipSuccess;
+    const bool last0 = F.iterations == 0;
+    hipLaunchKernelGGL(k_dn_prepare_as, dim3((tw + 63u) / 64u, (th + 3u) / 4u), dim3(256), 0, F.stream, accum, q, counts, tw, th,
+                       (tw + 7u) / 8u, F.c[0], last0 ? F.rgba : nullptr, last0 ? var : nullptr);
+    const hipError_t e = hipGetLastError();
+    return e != hipSuccess ? e : dn_run_atrous_as(F, kv, var, sigma_variance, out);
+}
+
+// crt_denoise_svgf: the blend into P.h_cur and the moments into P.m_cur, (c, v) into c[0], then the variance-guided passes
+// (h_cur and m_cur stay unfiltered: they are the next frame's history).
+hipError_t dn_launch_svgf(const DnFilter &F, DnSvgfParams P, uint2 *kv, float *var, float sigma_variance, float4 **out)
+{
+    *out = F.c[0];
+    if ((size_t)F.tw * F.th == 0) return hipSuccess;
+    const bool last0 = F.iterations == 0;
+    P.rgba = last0 ? F.rgba : nullptr;
+    P.var = last0 ? var : nullptr;
+    P.cv = F.c[0];
+    if (P.raw_prev) hipLaunchKernelGGL((k_dn_reproject<true, true>), dn_grid16(F), dim3(256), 0, F.stream, P);
+    else hipLaunchKernelGGL((k_dn_reproject<false, true>), dn_grid16(F), dim3(256), 0, F.stream, P);
+    const hipError_t e = hipGetLastError();
+    return e != hipSuccess ? e : dn_run_atrous_as(F, kv, var, sigma_variance, out);
 }
 
 }  // namespace crt

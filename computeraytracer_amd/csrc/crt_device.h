@@ -263,7 +263,17 @@ struct DnReprojParams {
     uint32_t nprim;
 };
 
-// What the launchers of the three preview filters share (crt_denoise.hip).
+// k_dn_reproject<*, true>: the blend above plus the temporal moments of the pixel's luminance, and the
+// variance they give as the w of the filter's input.  A struct of its own, so that the <*, false> kernels keep theirs.
+struct DnSvgfParams : DnReprojParams {
+    const float4 *m_prev;           // previous frame: (m1, s, Mw, 0) per pixel; null = the slot has no moments
+    float4 *m_cur;                  // out: the moments of this frame
+    float4 *cv;                     // out: (c, v), the input of the variance-guided passes
+    float *var;                     // null, or v alone (no filter pass follows)
+    float min_frames;               // v is trusted from Mw / n >= this on
+};
+
+// What the launchers of the four preview filters share (crt_denoise.hip).
 struct DnFilter {
     const float4 *gbuf;             // the guides: G-buffer and keys of the tile
     const uint32_t *key;
@@ -281,6 +291,7 @@ hipError_t dn_launch_filter(const DnFilter &F, const float4 *accum, float n, flo
 hipError_t dn_launch_filter_adaptive(const DnFilter &F, const float4 *accum, const float *q, const uint32_t *counts, uint2 *kv,
                                      float *var, float sigma_variance, float4 **out);
 hipError_t dn_launch_temporal(const DnFilter &F, DnReprojParams P, float sigma_color, float4 **out);
+hipError_t dn_launch_svgf(const DnFilter &F, DnSvgfParams P, uint2 *kv, float *var, float sigma_variance, float4 **out);
 hipError_t dn_launch_motion(const DnReprojParams &P, float2 *out, hipStream_t stream);
 
 }  // namespace crt

@@ -303,6 +303,39 @@ class Renderer:
         self._chk(self._lib.crt_denoise_temporal_reset(self._h))
         return self
 
+    def denoise_svgf(self, iterations: int | None = None, sigma_variance: float | None = None,
+                     sigma_normal: float | None = None, sigma_plane: float | None = None,
+                     max_history: float | None = None, normal_tol: float | None = None, plane_tol: float | None = None,
+                     min_frames: float | None = None, rgb: bool = False, history: bool = False, var: bool = False):
+        """denoise_temporal's blend followed by the variance-guided filter, the variance taken from the temporal moments
+        of the pixel's luminance (include/crt.h "Variance-guided temporal filter"): rgba8 (H, W, 4); with rgb=True also
+        linear rgb (H, W, 4) float32 (channel 3 = the variance), with history=True also Hw, with var=True also the
+        variance left after filtering, both (H, W) float32 -- a tuple in that order.  A parameter left out takes the
+        library's default (crt_denoise_svgf_defaults).  Reads the accumulator only; finishes what is in flight."""
+        _, _, tw, th = self.tile
+        p = _lib.denoise_svgf_defaults()
+        for k, v in dict(iterations=iterations, sigma_variance=sigma_variance, sigma_normal=sigma_normal, sigma_plane=sigma_plane,
+                         max_history=max_history, normal_tol=normal_tol, plane_tol=plane_tol, min_frames=min_frames).items():
+            if v is not None:
+                setattr(p, k, type(getattr(p, k))(v))
+        rgba = np.empty((th, tw, 4), np.uint8)
+        lin = np.empty((th, tw, 4), np.float32) if rgb else None
+        hw = np.empty((th, tw), np.float32) if history else None
+        vv = np.empty((th, tw), np.float32) if var else None
+        self._chk(self._lib.crt_denoise_svgf(self._h, C.byref(p), lin.ctypes.data if rgb else None, rgba.ctypes.data,
+                                             hw.ctypes.data if history else None, vv.ctypes.data if var else None))
+        out = tuple(a for a in (rgba, lin, hw, vv) if a is not None)
+        return out if len(out) > 1 else rgba
+
+    def read_moments(self) -> np.ndarray:
+        """(H, W, 4) float32 per tile pixel: (m1, s, Mw, 0) of the slot the last denoise_svgf of this frame left -- mean
+        luminance, variance of the frame means, the weight in samples behind both (crt_debug_read_moments, a test
+        hook)."""
+        _, _, tw, th = self.tile
+        out = np.empty((th, tw, 4), np.float32)
+        self._chk(self._lib.crt_debug_read_moments(self._h, out.ctypes.data))
+        return out
+
     def read_motion(self) -> np.ndarray:
         """(H, W, 2) float32 per tile pixel: the film position (u, v), in the tile's own pixel coordinates, where the
         last denoise_temporal looked for the pixel in the previous frame; NaN where there is none (no previous frame, a

@@ -1,13 +1,15 @@
 #!/usr/bin/env node
 'use strict';
 // CLI: node host/index.js [--scene file.json] [--width W --height H] [--spp N] [--accel bvh2|lbvh|none]
-//                         [--out image.ppm] [--dump prefix] [--pack-only prefix] [--denoise K] [--orbit N [--temporal]]
+//                         [--out image.ppm] [--dump prefix] [--pack-only prefix] [--denoise K] [--orbit N [--temporal [--variance]]]
 // --denoise K: --out gets the image denoised with K a-trous iterations (crt_denoise; with --adaptive the variance-guided
 //            crt_denoise_adaptive) instead of the plain average
 // --orbit N: N frames of --spp each, the eye turned about the look-at point (one upload and build, then setCamera per
 //            frame), written as OUT_000.ppm, OUT_001.ppm, ...
 // --temporal: with --orbit N --denoise K, frame k draws samples k * spp + 1 .. (setSampleOffset) and is blended with the
 //            reprojected result of frame k - 1 before the filter (denoiseTemporal)
+// --variance: with --temporal, the passes after the blend are variance-guided, the variance taken from the spread of the
+//            frame means (denoiseSvgf)
 // --adaptive T [--adaptive-step N] [--adaptive-min M]: adaptive sampling (traceAdaptive), rounds of N (16) samples until
 //            every 8x8 tile has an error <= T or holds --spp samples; a tile below M (default min(--spp, 2N)) samples is
 //            sampled whatever its error; prints rounds, pixel-samples, seconds and the min / median / max tile count
@@ -42,6 +44,7 @@ const r = Main({ sceneFile: args.scene, width: args.width ? num('width') : undef
   accel: args.accel || 'bvh2', device: num('device', 0) });
 if ('adaptive' in args && args.orbit) { console.error('--adaptive does not go with --orbit'); process.exit(2); }
 if (args.temporal && !(args.orbit && 'denoise' in args)) { console.error('--temporal goes with --orbit N --denoise K'); process.exit(2); }
+if (args.variance && !args.temporal) { console.error('--variance goes with --orbit N --denoise K --temporal'); process.exit(2); }
 if (args.orbit) {
   const n = num('orbit'), base = String(args.out || 'orbit.ppm').replace(/\.ppm$/, ''), outs = [];
   const t1 = process.hrtime.bigint();
@@ -50,7 +53,8 @@ if (args.orbit) {
     if (args.temporal) r.setSampleOffset(k * spp);
     r.run(spp);
     outs.push(`${base}_${String(k).padStart(3, '0')}.ppm`);
-    const rgba = args.temporal ? r.denoiseTemporal({ iterations: num('denoise') })
+    const rgba = args.variance ? r.denoiseSvgf({ iterations: num('denoise') })
+      : args.temporal ? r.denoiseTemporal({ iterations: num('denoise') })
       : 'denoise' in args ? r.denoise({ iterations: num('denoise') }) : r.readRgba8();
     writePPM(outs[k], rgba, r.width, r.height);
   });

@@ -89,6 +89,13 @@ function Main(options = {}) {
     // denoiseTemporal looked for it in the previous frame, NaN where there is none.  setOption('temporal_motion', 1)
     // keeps the history across updatePrimitives and makes the positions follow the edited primitives.
     readMotion: () => a.readMotion(device),
+    // the variance-guided temporal filter (include/crt.h "Variance-guided temporal filter"): denoiseTemporal's blend, then
+    // the passes of denoiseAdaptive with the variance taken from the spread of the frame means; rgba8 of the tile, or
+    // {rgba8, history?, variance?} with opts.history / opts.variance; reads only.  The Promise form resolves to the rgba8.
+    denoiseSvgfDefaults: () => a.denoiseSvgfDefaults(),
+    denoiseSvgf: (opts = {}) => a.denoiseSvgf(device, opts),
+    denoiseSvgfAsync: (opts = {}) => a.denoiseSvgfAsync(device, opts),
+    readMoments: () => a.readMoments(device),
     setOption: (name, value) => a.setOption(device, name, value),
     counters: () => a.counters(device),
     enableCounters: (on) => a.enableCounters(device, !!on),

@@ -418,6 +418,45 @@ int crt_denoise_temporal_reset(crt_ctx *ctx);
  * crt_denoise_temporal returns it, and when no crt_denoise_temporal has run since the accumulator was last zeroed. */
 int crt_read_motion(crt_ctx *ctx, float *out);
 
+/* ------------------------------------------------------------------ Variance-guided temporal filter
+ * crt_denoise_temporal's filter does not know how far its input has converged: a pixel holding 64 samples of history is
+ * blurred as hard as one holding 4.  crt_denoise_svgf is the same blend followed by crt_denoise_adaptive's variance-guided
+ * passes, with the variance taken from the spread of the frame means over time -- SVGF's temporal moments (DESIGN.md 6g
+ * defines it operation by operation).  Each history slot gains a second plane (m1, s, Mw, 0) per pixel: the mean
+ * luminance, the weighted population variance of the frame means, and the weight in samples behind both.  With
+ * y = accum.y / n: a pixel that takes no history, or whose PREVIOUS slot has no moments, starts at m1 = y, s = 0, Mw = n;
+ * otherwise, over the accepted taps and weights of the colour blend, h1, hs and Mp (capped at max_history) are the means
+ * of the taps' m1, s and Mw, and Mw = n + Mp, m1 = (n y + Mp h1) / Mw, s = (Mp / Mw) hs + n Mp (y - h1)^2 / Mw^2.
+ * With F = Mw / n frames behind the pixel its variance in display units is v = g^2 s / (F - 1), g = 2.2 exp(-2.2 max(m1, 0))
+ * the exposure curve's slope, where F >= min_frames and v is finite, and v = 1 ("nothing known", as crt_denoise_adaptive
+ * below 2 samples) elsewhere: misses, glass and pixels without history.  The passes are crt_denoise_adaptive's on (c, v).
+ * The slots, the promotion, the events that keep or drop the history, the frame notion, "temporal_motion" and the
+ * contract (a sync point, reads only, CRT_ESTATE in the same places) are crt_denoise_temporal's, and what it leaves in
+ * CURRENT's colour plane is bit for bit what crt_denoise_temporal leaves there.  The two calls mix: a
+ * crt_denoise_temporal writes CURRENT without moments, and a later crt_denoise_svgf reuses its colour history and starts
+ * the moments again (Mw = n).  A failed allocation (CRT_ENOMEM) leaves the slots as they were. */
+typedef struct {
+    uint32_t iterations;    /* variance-guided passes after the blend, 0..10 */
+    float sigma_variance;   /* as crt_denoise_adaptive_params */
+    float sigma_normal;
+    float sigma_plane;
+    float max_history;      /* as crt_denoise_temporal_params */
+    float normal_tol;
+    float plane_tol;
+    float min_frames;       /* the variance is trusted from this many frames of history on; >= 2 and finite */
+} crt_denoise_svgf_params;
+/* The defaults {5, 4.0, 0.5, 0.3, 64, 0.5, 2.0, 4.0}.  No context and no GPU needed. */
+int crt_denoise_svgf_defaults(crt_denoise_svgf_params *out);
+/* NULL params = the defaults.  rgb_out: tw*th*4 floats (linear rgb; channel 3 = the pixel's var_out) or NULL; rgba8_out:
+ * tw*th*4 bytes or NULL; history_out: tw*th floats of Hw or NULL; var_out: tw*th floats, the variance left after
+ * filtering (v itself at iterations = 0), or NULL.  CRT_EINVAL (context, history and moments unchanged) for
+ * iterations > 10, a sigma, tolerance or max_history that is not positive and finite, or min_frames < 2 or not finite. */
+int crt_denoise_svgf(crt_ctx *ctx, const crt_denoise_svgf_params *params, float *rgb_out, uint8_t *rgba8_out,
+                     float *history_out, float *var_out);
+/* Test hook: the moments (m1, s, Mw, 0) of the CURRENT slot, tw*th*4 floats.  CRT_ESTATE unless CURRENT belongs to this
+ * frame and carries moments (no crt_denoise_svgf in this frame yet, or a crt_denoise_temporal after it). */
+int crt_debug_read_moments(crt_ctx *ctx, float *out);
+
 /* Counters accumulate over crt_trace calls while enabled (off by default: the
  * counting kernel variant is slower). */
 int crt_enable_counters(crt_ctx *ctx, int on);
