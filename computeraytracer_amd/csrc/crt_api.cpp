@@ -227,44 +227,52 @@ struct crt_ctx {
     uint32_t last_iterations = 0;
     unsigned long long probes[8] = {0};   // traversal-efficiency probes of the counting kernels
 
-    // crt_denoise (crt_denoise.hip): the first-hit G-buffer of the tile, built on first use and kept until the scene,
-    // the accel structure or the tile changes; the filter's ping-pong colour buffers and its rgba8 output
-    DevBuf<float4> dn_gbuf;         // 2 per tile pixel: (t, position), (normal, hit index bits)
-    DevBuf<uint32_t> dn_key;        // per tile pixel: material << 24 | reflectance index, 0xFFFFFFFF = miss
-    bool dn_valid = false;
-    DevBuf<float4> dn_c[2];
-    DevBuf<uchar4> dn_rgba;
-    DevBuf<uint2> dn_kv;            // crt_denoise_adaptive: per tile pixel (key, blurred variance bits) of the current pass
-    DevBuf<float> dn_var;           // ... and the variance left after the last pass
-    // crt_denoise_temporal: the history slots.  Buffers move between the slots and dn_gbuf / dn_key by
-    // swapping pointers.  The CURRENT slot's G-buffer is dn_gbuf / dn_key themselves while dn_gen == th_gen; a rebuild of
-    // the G-buffer before the slot is promoted (a plain crt_denoise of a later frame) parks them in th_park_* first.
-    struct DnHistory {
+    // The preview filters (crt_denoise.hip).  DESIGN.md 6e has the model: guide sets in a pool, history slots that name
+    // the set they were blended with.
+    struct DnGuideSet {             // a first-hit G-buffer of the tile and its keys
+        DevBuf<float4> gbuf;        // 2 per tile pixel: (t, position), (normal, hit index bits)
+        DevBuf<uint32_t> key;       // per tile pixel: material << 24 | reflectance index, 0xFFFFFFFF = miss
+    };
+    struct DnSlot {                 // one frame of history (crt_denoise_temporal, crt_denoise_svgf)
         DevBuf<float4> c;           // blended linear rgb before any spatial filter, w = its weight Hw in samples
-        DevBuf<float4> gbuf;
-        DevBuf<uint32_t> key;
         DevBuf<float4> m;           // crt_denoise_svgf: (m1, s, Mw, 0), the temporal moments of the luminance
+        int guides = -1;            // the set of `sets` this frame was blended with (-1: none, the slot is not valid)
         float cam[12] = {0};        // that frame's camera_frame
+        uint32_t frame = 0;         // frame_id it was made in
         bool valid = false;
         bool has_m = false;         // m belongs to this slot (a crt_denoise_svgf wrote it)
-    } th_prev;
-    DevBuf<float4> th_cur_c;        // CURRENT: (c, Hw)
-    DevBuf<float4> th_cur_m;        // ... and its moments, while th_cur_has_m
-    bool th_cur_has_m = false;
-    float th_cur_cam[12] = {0};
-    bool th_cur_valid = false;
-    uint32_t th_cur_frame = 0;      // frame_id it was made in
-    uint32_t th_gen = 0, dn_gen = 0;    // dn_gen: builds of dn_gbuf so far; th_gen: the build CURRENT was made with
-    bool th_parked = false;
-    DevBuf<float4> th_park_gbuf;
-    DevBuf<uint32_t> th_park_key;
-    DevBuf<float> th_hist;          // Hw alone, for history_out
-    // option "temporal_motion" (DESIGN.md 6f): the history outlives crt_update_primitives.  th_snap is a copy of d_raw, the
-    // scene as the newest valid slot saw it, taken by the first update after that slot was written.
-    bool th_motion = false;
-    DevBuf<unsigned char> th_snap;
-    enum { TH_SNAP_NONE, TH_SNAP_CURRENT, TH_SNAP_PREVIOUS } th_snap_of = TH_SNAP_NONE;   // the slot whose geometry it is
-    DevBuf<float2> th_uv;           // crt_read_motion's output
+        bool snap = false;          // `snap` below is the scene as THIS slot saw it (at most one slot says so)
+        void clear() { guides = -1; valid = has_m = snap = false; }     // (the buffers stay for the next use)
+    };
+    struct Denoise {
+        // the G-buffer of the tile is sets[set] while `valid`: built on first use, kept until the scene, the accel structure
+        // or the tile changes.  A rebuild writes a set that no slot names, so a third one exists only once both slots hold
+        // one of their own and a plain crt_denoise needs another.
+        DnGuideSet sets[3];
+        int set = 0;
+        bool valid = false;
+        DevBuf<float4> c[2];        // the filter's ping-pong colour buffers ...
+        DevBuf<uchar4> rgba;        // ... and its rgba8 output
+        DevBuf<uint2> kv;           // crt_denoise_adaptive: per tile pixel (key, blurred variance bits) of the current pass
+        DevBuf<float> var;          // ... and the variance left after the last pass
+        DnSlot cur, prev;           // CURRENT: the last temporal call of this frame; PREVIOUS: what it was blended with
+        DevBuf<float> hist;         // Hw alone, for history_out
+        // option "temporal_motion" (DESIGN.md 6f): the history outlives crt_update_primitives.  snap is a copy of d_raw, the
+        // scene as the newest valid slot saw it, taken by the first update after that slot was written.
+        bool motion = false;
+        DevBuf<unsigned char> snap;
+        DevBuf<float2> uv;          // crt_read_motion's output
+
+        // Drop the history (the geometry snapshot goes with it).
+        void drop() { cur.clear(); prev.clear(); snap.release(); }
+        void release()
+        {
+            drop();
+            for (DnGuideSet &g : sets) { g.gbuf.release(); g.key.release(); }
+            for (DnSlot *s : {&cur, &prev}) { s->c.release(); s->m.release(); }
+            c[0].release(); c[1].release(); rgba.release(); kv.release(); var.release(); hist.release(); uv.release();
+        }
+    } dn;
 
     // scene edits (crt_refit.hip)
     float s_prims = 0.0f;           // max |corner coordinate| of the primitives: hit_pad = max(s_prims, |eye|) * 2^-17
@@ -332,14 +340,6 @@ int alloc_frames(crt_ctx *c)
     c->frame_batch.assign(c->frame_ring, 0);
     if (c->frame_ring && !c->read_stream) HIPCHK(c, hipStreamCreateWithFlags(&c->read_stream, hipStreamNonBlocking));
     return CRT_OK;
-}
-
-// Drop the history of crt_denoise_temporal (the slots' buffers stay for the next use; the geometry snapshot goes).
-void th_drop(crt_ctx *c)
-{
-    c->th_prev.valid = false; c->th_cur_valid = false; c->th_parked = false;
-    c->th_prev.has_m = false; c->th_cur_has_m = false;
-    c->th_snap.release(); c->th_snap_of = crt_ctx::TH_SNAP_NONE;
 }
 
 int zero_state(crt_ctx *c)
@@ -1794,11 +1794,7 @@ void crt_destroy(crt_ctx *c)
     c->w_ray_o.release(); c->w_ray_d.release(); c->w_sh_d.release(); c->w_beta.release(); c->w_radiance.release();
     c->w_nee.release(); for (uint32_t b = 0; b < kWfRing; b++) c->w_staging[b].release(); c->w_rng.release(); c->w_misc.release(); c->w_hit.release();
     c->w_vis.release(); c->w_dead.release(); c->w_recA.release(); c->w_recB.release(); c->w_recC.release(); c->w_tea.release(); c->w_wq.release();
-    c->dn_gbuf.release(); c->dn_key.release(); c->dn_c[0].release(); c->dn_c[1].release(); c->dn_rgba.release();
-    c->dn_kv.release(); c->dn_var.release();
-    c->th_prev.c.release(); c->th_prev.gbuf.release(); c->th_prev.key.release(); c->th_cur_c.release();
-    c->th_park_gbuf.release(); c->th_park_key.release(); c->th_hist.release(); c->th_snap.release(); c->th_uv.release();
-    c->th_prev.m.release(); c->th_cur_m.release();
+    c->dn.release();
     c->rf_lv2.release(); c->rf_lv4.release(); c->rf_nch4.release(); c->rf_cnt.release(); c->rf_fb.release();
     c->as_counts.release(); c->as_errors.release(); c->as_flags.release(); c->as_active.release(); c->as_n.release(); c->as_q.release();
     if (c->pub_stream) (void)hipStreamSynchronize(c->pub_stream);
@@ -1868,9 +1864,9 @@ int crt_upload_scene(crt_ctx *c, const void *primitives, size_t nprim, const voi
     // from here on the old scene is gone: a failure below must not leave a context that can still trace
     c->have_scene = false;
     c->accel_mode = -1;
-    c->dn_valid = false;
+    c->dn.valid = false;
     c->sample_offset = 0;
-    th_drop(c);
+    c->dn.drop();
     c->prims.swap(prims);
     c->lights.swap(lts);
     std::memcpy(c->camera, camera, sizeof c->camera);
@@ -1925,8 +1921,8 @@ int crt_set_tile(crt_ctx *c, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1)
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->x0 = x0; c->y0 = y0; c->tw = x1 - x0; c->th = y1 - y0;
     c->band = 0x40000000u; c->stride = 1; c->phase = 0;
-    c->dn_valid = false;
-    th_drop(c);
+    c->dn.valid = false;
+    c->dn.drop();
     c->accum_bound = nullptr; c->rgba_bound = nullptr;
     int rc = alloc_tile(c);
     if (rc) return rc;
@@ -1947,8 +1943,8 @@ int crt_set_row_bands(crt_ctx *c, uint32_t band_rows, uint32_t parts, uint32_t p
         rows += std::min<uint32_t>(band_rows, c->H - b * band_rows);
     c->x0 = 0; c->y0 = 0; c->tw = c->W; c->th = rows;
     c->band = band_rows; c->stride = parts; c->phase = part;
-    c->dn_valid = false;
-    th_drop(c);
+    c->dn.valid = false;
+    c->dn.drop();
     c->accum_bound = nullptr; c->rgba_bound = nullptr;
     int rc = alloc_tile(c);
     if (rc) return rc;
@@ -1968,7 +1964,7 @@ int crt_build_accel(crt_ctx *c, int mode)
     // The build releases the scene's device arrays before it allocates the new ones: until it has succeeded there is
     // no structure to trace against (upload_geometry / build_accel_on_device set accel_mode on success only).
     c->accel_mode = -1;
-    c->dn_valid = false;
+    c->dn.valid = false;
     return build_tree(c, mode);
 }
 
@@ -2326,7 +2322,7 @@ int crt_write_accum(crt_ctx *c, const float *in, uint32_t sample)
     c->sample = sample; c->published = sample; c->pending = 0; c->resolved_upto = sample; c->ring_from = sample + 1u;
     c->as_on = false; c->as_broken = false;                      // (the restored accumulator is a uniform one)
     c->frame_id++;
-    th_drop(c);
+    c->dn.drop();
     return CRT_OK;
 }
 
@@ -2476,9 +2472,9 @@ int crt_set_option(crt_ctx *c, const char *name, int64_t value)
     if (!std::strcmp(name, "wf_tail_walk")) { c->wf_tail_walk = value != 0; return CRT_OK; }
     if (!std::strcmp(name, "temporal_motion")) {
         if (value != 0 && value != 1) return fail(c, CRT_EINVAL, "crt_set_option: temporal_motion is 0 or 1");
-        if (!value && c->th_snap_of != crt_ctx::TH_SNAP_NONE) th_drop(c);   // (history across an edit is this option's)
-        if (!value) c->th_snap.release();
-        c->th_motion = value != 0;
+        if (!value && (c->dn.cur.snap || c->dn.prev.snap)) c->dn.drop();    // (history across an edit is this option's)
+        if (!value) c->dn.snap.release();
+        c->dn.motion = value != 0;
         return CRT_OK;
     }
     if (!std::strcmp(name, "frame_ring")) {
@@ -2526,20 +2522,28 @@ static int dn_check_state(crt_ctx *c, const char *what, bool adaptive = false)  
         if (c->buf.n < (count)) HIPCHK(c, c->buf.alloc(count));    \
     } while (0)
 
-// The G-buffer of the tile, built once per scene / accel structure / tile.  Enqueued on the context's stream.
-static int dn_ensure_gbuffer(crt_ctx *c)
+// The G-buffer of the tile, built once per scene / accel structure / tile.  Enqueued on the context's stream.  A rebuild
+// goes into a set that no history slot names, the first such from the current one on (so in place if it can), but an
+// allocated one before an unallocated one: nothing is allocated while a free set has buffers, and with three sets and
+// two slots there always is a free one.  `dying` is a slot the caller is about to overwrite or let go: its set counts
+// as free, and the slot is cleared once the allocations have succeeded, before its guides are overwritten.
+static int dn_ensure_gbuffer(crt_ctx *c, crt_ctx::DnSlot *dying = nullptr)
 {
-    if (c->dn_valid) return CRT_OK;
-    const size_t n = (size_t)c->tw * c->th;
-    if (c->th_cur_valid && c->th_gen == c->dn_gen && !c->th_parked) {     // the history's CURRENT slot owns this content
-        std::swap(c->dn_gbuf, c->th_park_gbuf); std::swap(c->dn_key, c->th_park_key);
-        c->th_parked = true;
+    crt_ctx::Denoise &d = c->dn;
+    if (d.valid) return CRT_OK;
+    int set = -1;
+    for (int k = 0; k < 3; k++) {
+        const int s = (d.set + k) % 3;
+        if ((&d.cur != dying && d.cur.guides == s) || (&d.prev != dying && d.prev.guides == s)) continue;
+        if (set < 0 || (!d.sets[set].gbuf.p && d.sets[s].gbuf.p)) set = s;
     }
-    DN_ENSURE(c, dn_gbuf, 2 * n);
-    DN_ENSURE(c, dn_key, n);
-    HIPCHK(c, dn_launch_gbuffer(c->sc, c->x0, c->y0, c->tw, c->th, c->dn_gbuf.p, c->dn_key.p, c->accel_mode == CRT_ACCEL_NONE, c->stream));
-    c->dn_valid = true;
-    c->dn_gen++;
+    const size_t n = (size_t)c->tw * c->th;
+    DN_ENSURE(c, dn.sets[set].gbuf, 2 * n);
+    DN_ENSURE(c, dn.sets[set].key, n);
+    if (dying) dying->clear();
+    HIPCHK(c, dn_launch_gbuffer(c->sc, c->x0, c->y0, c->tw, c->th, d.sets[set].gbuf.p, d.sets[set].key.p, c->accel_mode == CRT_ACCEL_NONE, c->stream));
+    d.set = set;
+    d.valid = true;
     return CRT_OK;
 }
 
@@ -2566,15 +2570,16 @@ static int dn_begin(crt_ctx *c, const char *what, uint32_t iterations, const flo
 // The colour buffers and the rgba8 of every filter, and what its launchers share (once the G-buffer is there).
 static int dn_ensure_buffers(crt_ctx *c, size_t n)
 {
-    DN_ENSURE(c, dn_c[0], n);
-    DN_ENSURE(c, dn_c[1], n);
-    DN_ENSURE(c, dn_rgba, n);
+    DN_ENSURE(c, dn.c[0], n);
+    DN_ENSURE(c, dn.c[1], n);
+    DN_ENSURE(c, dn.rgba, n);
     return CRT_OK;
 }
 
 static DnFilter dn_filter(crt_ctx *c, uint32_t iterations, float sigma_normal, float sigma_plane, bool rgba)
 {
-    return DnFilter{c->dn_gbuf.p, c->dn_key.p, {c->dn_c[0].p, c->dn_c[1].p}, rgba ? c->dn_rgba.p : nullptr, c->tw, c->th, iterations,
+    const crt_ctx::DnGuideSet &g = c->dn.sets[c->dn.set];
+    return DnFilter{g.gbuf.p, g.key.p, {c->dn.c[0].p, c->dn.c[1].p}, rgba ? c->dn.rgba.p : nullptr, c->tw, c->th, iterations,
                     sigma_normal, sigma_plane, c->stream};
 }
 
@@ -2583,7 +2588,7 @@ static int dn_finish(crt_ctx *c, size_t n, const float4 *res, float *rgb_out, ui
                      float *plane_out = nullptr)
 {
     if (n && rgb_out) HIPCHK(c, hipMemcpyAsync(rgb_out, res, n * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
-    if (n && rgba8_out) HIPCHK(c, hipMemcpyAsync(rgba8_out, c->dn_rgba.p, n * sizeof(uchar4), hipMemcpyDeviceToHost, c->stream));
+    if (n && rgba8_out) HIPCHK(c, hipMemcpyAsync(rgba8_out, c->dn.rgba.p, n * sizeof(uchar4), hipMemcpyDeviceToHost, c->stream));
     if (n && plane_out) HIPCHK(c, hipMemcpyAsync(plane_out, plane, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return wf_check_dropped(c);
@@ -2628,13 +2633,13 @@ int crt_denoise_adaptive(crt_ctx *c, const crt_denoise_adaptive_params *params, 
     if (n) {
         { int rc = dn_ensure_gbuffer(c); if (rc) return rc; }
         { int rc = dn_ensure_buffers(c, n); if (rc) return rc; }
-        DN_ENSURE(c, dn_kv, n);
-        DN_ENSURE(c, dn_var, n);
+        DN_ENSURE(c, dn.kv, n);
+        DN_ENSURE(c, dn.var, n);
         const DnFilter F = dn_filter(c, dp.iterations, dp.sigma_normal, dp.sigma_plane, rgba8_out != nullptr);
-        HIPCHK(c, dn_launch_filter_adaptive(F, accum_ptr(c), c->as_q.p, c->as_counts.p, c->dn_kv.p, var_out ? c->dn_var.p : nullptr,
+        HIPCHK(c, dn_launch_filter_adaptive(F, accum_ptr(c), c->as_q.p, c->as_counts.p, c->dn.kv.p, var_out ? c->dn.var.p : nullptr,
                                             dp.sigma_variance, &res));
     }
-    return dn_finish(c, n, res, rgb_out, rgba8_out, c->dn_var.p, var_out);
+    return dn_finish(c, n, res, rgb_out, rgba8_out, c->dn.var.p, var_out);
 }
 
 // ---------------------------------------------------------------- temporal reuse
@@ -2668,7 +2673,7 @@ int crt_denoise_temporal_defaults(crt_denoise_temporal_params *out)
 int crt_denoise_temporal_reset(crt_ctx *c)
 {
     if (!c) return CRT_EINVAL;
-    th_drop(c);
+    c->dn.drop();
     return CRT_OK;
 }
 
@@ -2684,16 +2689,17 @@ static double th_kappa(const float cam[12], uint32_t W)
     return (std::sqrt(hor) / (double)W) / std::sqrt(ax);
 }
 
-// What the blend and crt_read_motion share: the frame's guides (gbuf, key), the PREVIOUS slot and its camera, and the
+// What the blend and crt_read_motion share: the frame's guides, the PREVIOUS slot with its own and its camera, and the
 // records the map of 6f reads.  h_prev stays null without a usable PREVIOUS.
-static DnReprojParams th_reproj_params(crt_ctx *c, const float4 *gbuf, const uint32_t *key)
+static DnReprojParams th_reproj_params(crt_ctx *c, const crt_ctx::DnGuideSet &guides)
 {
+    const crt_ctx::DnSlot &prev = c->dn.prev;
     DnReprojParams P{};
-    P.gbuf = gbuf; P.key = key;
+    P.gbuf = guides.gbuf.p; P.key = guides.key.p;
     P.tw = c->tw; P.th = c->th;
-    if (c->th_prev.valid) {
+    if (prev.valid) {
         // M' = [hor' ver' (llc' - eye')]^-1 by cofactors, in double
-        const float *q = c->th_prev.cam;
+        const float *q = prev.cam;
         double A[3][3], inv[3][3];
         for (int k = 0; k < 3; k++) { A[k][0] = q[3 + k]; A[k][1] = q[6 + k]; A[k][2] = (double)q[k] - (double)q[9 + k]; }
         const double det = A[0][0] * (A[1][1] * A[2][2] - A[1][2] * A[2][1]) - A[0][1] * (A[1][0] * A[2][2] - A[1][2] * A[2][0]) +
@@ -2706,12 +2712,12 @@ static DnReprojParams th_reproj_params(crt_ctx *c, const float4 *gbuf, const uin
         bool ok = std::isfinite(det) && det != 0.0;
         for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) { P.m[3 * i + j] = inv[i][j]; ok = ok && std::isfinite(inv[i][j]); }
         if (ok) {                                                // (a degenerate previous camera: nothing is reused)
-            P.h_prev = c->th_prev.c.p; P.gbuf_prev = c->th_prev.gbuf.p; P.key_prev = c->th_prev.key.p;
+            P.h_prev = prev.c.p; P.gbuf_prev = c->dn.sets[prev.guides].gbuf.p; P.key_prev = c->dn.sets[prev.guides].key.p;
         }
         for (int k = 0; k < 3; k++) { P.eye_prev[k] = q[9 + k]; P.eye[k] = c->sc.cam[9 + k]; }
         P.kappa_prev = (float)th_kappa(q, c->W); P.kappa = (float)th_kappa(c->sc.cam, c->W);
-        if (c->th_snap_of == crt_ctx::TH_SNAP_PREVIOUS) {        // PREVIOUS saw another pose of the scene: k_dn_reproject<true>
-            P.raw = c->d_raw.p; P.raw_prev = c->th_snap.p; P.nprim = (uint32_t)c->prims.size();
+        if (prev.snap) {                                         // PREVIOUS saw another pose of the scene: k_dn_reproject<true>
+            P.raw = c->d_raw.p; P.raw_prev = c->dn.snap.p; P.nprim = (uint32_t)c->prims.size();
         }
     }
     P.W = (double)c->W; P.H = (double)c->H; P.x0 = (double)c->x0; P.y0 = (double)c->y0;
@@ -2731,58 +2737,46 @@ struct ThCall {
 static int th_blend_and_filter(crt_ctx *c, const ThCall &t, bool rgba, bool hist, bool var, float4 **res)
 {
     const size_t n = (size_t)c->tw * c->th;
-    // every buffer first: a failed allocation leaves the slots as they were
-    DN_ENSURE(c, th_cur_c, n);
-    DN_ENSURE(c, th_prev.c, n);
+    crt_ctx::DnSlot &cur = c->dn.cur, &prev = c->dn.prev;
+    const bool promote = cur.valid && cur.frame != c->frame_id;  // the first call of a new frame
+    // Every buffer first: a failed allocation leaves the slots as they were.  dn_ensure_gbuffer comes last because it also
+    // clears a slot and moves dn.set once its own two allocations are through: no allocation may follow it.
+    DN_ENSURE(c, dn.cur.c, n);
+    DN_ENSURE(c, dn.prev.c, n);
     { int rc = dn_ensure_buffers(c, n); if (rc) return rc; }
-    DN_ENSURE(c, th_hist, n);
+    DN_ENSURE(c, dn.hist, n);
     if (t.svgf) {
-        DN_ENSURE(c, th_cur_m, n);
-        DN_ENSURE(c, th_prev.m, n);
-        DN_ENSURE(c, dn_kv, n);
-        DN_ENSURE(c, dn_var, n);
+        DN_ENSURE(c, dn.cur.m, n);
+        DN_ENSURE(c, dn.prev.m, n);
+        DN_ENSURE(c, dn.kv, n);
+        DN_ENSURE(c, dn.var, n);
     }
-    // the first call of a new frame: CURRENT becomes PREVIOUS, by pointer
-    if (c->th_cur_valid && c->th_cur_frame != c->frame_id) {
-        if (c->th_parked) {
-            std::swap(c->th_prev.gbuf, c->th_park_gbuf); std::swap(c->th_prev.key, c->th_park_key);
-        } else {
-            std::swap(c->th_prev.gbuf, c->dn_gbuf); std::swap(c->th_prev.key, c->dn_key);
-            c->dn_valid = false;                             // (what came back is an older frame's: rebuilt below)
-        }
-        std::swap(c->th_prev.c, c->th_cur_c);
-        std::swap(c->th_prev.m, c->th_cur_m);
-        c->th_prev.has_m = c->th_cur_has_m;
-        std::memcpy(c->th_prev.cam, c->th_cur_cam, sizeof c->th_prev.cam);
-        c->th_prev.valid = true;
-        c->th_cur_valid = false; c->th_parked = false;
-        // a snapshot taken for that slot is now PREVIOUS's geometry; an older one went with the slot it belonged to
-        c->th_snap_of = c->th_snap_of == crt_ctx::TH_SNAP_CURRENT ? crt_ctx::TH_SNAP_PREVIOUS : crt_ctx::TH_SNAP_NONE;
-    }
-    c->th_cur_valid = false;                                 // (rewritten below: a rebuild of the G-buffer has nothing to park)
-    c->th_cur_has_m = false;
-    { int rc = dn_ensure_gbuffer(c); if (rc) return rc; }
+    { int rc = dn_ensure_gbuffer(c, promote ? &prev : &cur); if (rc) return rc; }
+    // CURRENT becomes PREVIOUS, with its guides and its snapshot flag; the slot that was PREVIOUS ends here, as CURRENT
+    // does when this frame is filtered again
+    if (promote) std::swap(prev, cur);
+    cur.clear();
     DnSvgfParams P{};
-    static_cast<DnReprojParams &>(P) = th_reproj_params(c, c->dn_gbuf.p, c->dn_key.p);
+    static_cast<DnReprojParams &>(P) = th_reproj_params(c, c->dn.sets[c->dn.set]);
     P.accum = accum_ptr(c);
-    P.h_cur = c->th_cur_c.p;
-    P.hist = hist ? c->th_hist.p : nullptr;
+    P.h_cur = cur.c.p;
+    P.hist = hist ? c->dn.hist.p : nullptr;
     P.n = (float)c->sample;
     P.max_history = t.max_history;
     P.normal_tol2 = (float)std::min(3.0e38, (double)t.normal_tol * t.normal_tol);
     P.plane_tol = t.plane_tol;
     const DnFilter F = dn_filter(c, t.iterations, t.sigma_normal, t.sigma_plane, rgba);
     if (t.svgf) {
-        P.m_prev = P.h_prev && c->th_prev.has_m ? c->th_prev.m.p : nullptr;
-        P.m_cur = c->th_cur_m.p;
+        P.m_prev = P.h_prev && prev.has_m ? prev.m.p : nullptr;
+        P.m_cur = cur.m.p;
         P.min_frames = t.min_frames;
-        HIPCHK(c, dn_launch_svgf(F, P, c->dn_kv.p, var ? c->dn_var.p : nullptr, t.sigma_variance, res));
+        HIPCHK(c, dn_launch_svgf(F, P, c->dn.kv.p, var ? c->dn.var.p : nullptr, t.sigma_variance, res));
     } else {
         HIPCHK(c, dn_launch_temporal(F, P, t.sigma_color, res));
     }
-    std::memcpy(c->th_cur_cam, c->sc.cam, sizeof c->th_cur_cam);
-    c->th_cur_valid = true; c->th_cur_frame = c->frame_id; c->th_gen = c->dn_gen; c->th_parked = false;
-    c->th_cur_has_m = t.svgf;
+    std::memcpy(cur.cam, c->sc.cam, sizeof cur.cam);
+    cur.guides = c->dn.set; cur.frame = c->frame_id;
+    cur.valid = true; cur.has_m = t.svgf;
     return CRT_OK;
 }
 
@@ -2803,7 +2797,7 @@ int crt_denoise_temporal(crt_ctx *c, const crt_denoise_temporal_params *params, 
         const int rc = th_blend_and_filter(c, t, rgba8_out != nullptr, history_out || rgb_out, false, &res);
         if (rc) return rc;
     }
-    const int rc = dn_finish(c, n, res, rgb_out, rgba8_out, c->th_hist.p, hw_host);
+    const int rc = dn_finish(c, n, res, rgb_out, rgba8_out, c->dn.hist.p, hw_host);
     if (rgb_out && dp.iterations > 0)
         for (size_t i = 0; i < n; i++) rgb_out[4 * i + 3] = hw_host[i];
     return rc;
@@ -2835,20 +2829,20 @@ int crt_denoise_svgf(crt_ctx *c, const crt_denoise_svgf_params *params, float *r
                        0.0f, dp.sigma_variance, dp.min_frames};
         const int rc = th_blend_and_filter(c, t, rgba8_out != nullptr, history_out != nullptr, var_out != nullptr, &res);
         if (rc) return rc;
-        if (var_out) HIPCHK(c, hipMemcpyAsync(var_out, c->dn_var.p, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+        if (var_out) HIPCHK(c, hipMemcpyAsync(var_out, c->dn.var.p, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     }
-    return dn_finish(c, n, res, rgb_out, rgba8_out, c->th_hist.p, history_out);
+    return dn_finish(c, n, res, rgb_out, rgba8_out, c->dn.hist.p, history_out);
 }
 
 int crt_debug_read_moments(crt_ctx *c, float *out)
 {
     if (!c || !out) return CRT_EINVAL;
     { int rc = dn_begin(c, "crt_debug_read_moments", 0, nullptr, 0, "", DN_UNIFORM); if (rc) return rc; }
-    if (!c->th_cur_valid || c->th_cur_frame != c->frame_id || !c->th_cur_has_m)
+    if (!c->dn.cur.valid || c->dn.cur.frame != c->frame_id || !c->dn.cur.has_m)
         return fail(c, CRT_ESTATE, "crt_debug_read_moments: no crt_denoise_svgf in this frame yet, or a crt_denoise_temporal after it "
                                    "(the CURRENT slot carries no moments)");
     const size_t n = (size_t)c->tw * c->th;
-    if (n) HIPCHK(c, hipMemcpyAsync(out, c->th_cur_m.p, n * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+    if (n) HIPCHK(c, hipMemcpyAsync(out, c->dn.cur.m.p, n * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
     return dn_finish(c, n, nullptr, nullptr, nullptr);
 }
 
@@ -2856,16 +2850,14 @@ int crt_read_motion(crt_ctx *c, float *out)
 {
     if (!c || !out) return CRT_EINVAL;
     { int rc = dn_begin(c, "crt_read_motion", 0, nullptr, 0, "", DN_UNIFORM); if (rc) return rc; }
-    if (!c->th_cur_valid || c->th_cur_frame != c->frame_id)
+    if (!c->dn.cur.valid || c->dn.cur.frame != c->frame_id)
         return fail(c, CRT_ESTATE, "crt_read_motion: no crt_denoise_temporal in this frame yet (it reports where that call's blend looked)");
     const size_t n = (size_t)c->tw * c->th;
     if (n) {
-        DN_ENSURE(c, th_uv, n);
-        // CURRENT's guides: dn_gbuf itself unless a later rebuild parked them
-        const DnReprojParams P = c->th_parked ? th_reproj_params(c, c->th_park_gbuf.p, c->th_park_key.p)
-                                              : th_reproj_params(c, c->dn_gbuf.p, c->dn_key.p);
-        HIPCHK(c, dn_launch_motion(P, c->th_uv.p, c->stream));
-        HIPCHK(c, hipMemcpyAsync(out, c->th_uv.p, n * sizeof(float2), hipMemcpyDeviceToHost, c->stream));
+        DN_ENSURE(c, dn.uv, n);
+        const DnReprojParams P = th_reproj_params(c, c->dn.sets[c->dn.cur.guides]);      // CURRENT's own guides
+        HIPCHK(c, dn_launch_motion(P, c->dn.uv.p, c->stream));
+        HIPCHK(c, hipMemcpyAsync(out, c->dn.uv.p, n * sizeof(float2), hipMemcpyDeviceToHost, c->stream));
     }
     return dn_finish(c, n, nullptr, nullptr, nullptr);
 }
@@ -2877,7 +2869,7 @@ int crt_read_gbuffer(crt_ctx *c, float *out)
     const size_t n = (size_t)c->tw * c->th;
     if (n) {
         { int rc = dn_ensure_gbuffer(c); if (rc) return rc; }
-        HIPCHK(c, hipMemcpyAsync(out, c->dn_gbuf.p, n * 2 * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(out, c->dn.sets[c->dn.set].gbuf.p, n * 2 * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
     }
     return dn_finish(c, n, nullptr, nullptr, nullptr);
 }
@@ -3102,7 +3094,7 @@ static int edit_begin(crt_ctx *c)
 // Tile, row bands, bound outputs, stream, options and a communicator partition stay.
 static int edit_end(crt_ctx *c)
 {
-    c->dn_valid = false;
+    c->dn.valid = false;
     return zero_state(c);
 }
 
@@ -3225,19 +3217,20 @@ int crt_update_primitives(crt_ctx *c, uint32_t first, uint32_t count, const void
     // option "temporal_motion": the history stays, with the scene as its newest slot saw it.  Not retaken
     // until a newer slot exists: several updates may precede one refit, and a frame that is never filtered temporally
     // must not cost the older slot its geometry.
-    const int snap_for = !c->th_motion ? crt_ctx::TH_SNAP_NONE : c->th_cur_valid ? crt_ctx::TH_SNAP_CURRENT
-                         : c->th_prev.valid ? crt_ctx::TH_SNAP_PREVIOUS : crt_ctx::TH_SNAP_NONE;
-    const bool take = snap_for != crt_ctx::TH_SNAP_NONE && c->th_snap_of != snap_for;
-    if (take && c->th_snap.n < c->d_raw.n) {                      // before anything changes: CRT_ENOMEM leaves all as it was
+    crt_ctx::Denoise &d = c->dn;
+    crt_ctx::DnSlot *const newest = !d.motion ? nullptr : d.cur.valid ? &d.cur : d.prev.valid ? &d.prev : nullptr;
+    const bool take = newest && !newest->snap;
+    if (take && d.snap.n < c->d_raw.n) {                         // before anything changes: CRT_ENOMEM leaves all as it was
         ScopedBuf<unsigned char> fresh;
         HIPCHK(c, fresh.alloc(c->d_raw.n));
-        std::swap(c->th_snap.p, fresh.p); std::swap(c->th_snap.n, fresh.n);
+        std::swap(d.snap.p, fresh.p); std::swap(d.snap.n, fresh.n);
     }
     if (take) {
-        HIPCHK(c, hipMemcpyAsync(c->th_snap.p, c->d_raw.p, c->d_raw.n, hipMemcpyDeviceToDevice, c->stream));
-        c->th_snap_of = (decltype(c->th_snap_of))snap_for;
+        HIPCHK(c, hipMemcpyAsync(d.snap.p, c->d_raw.p, c->d_raw.n, hipMemcpyDeviceToDevice, c->stream));
+        d.cur.snap = d.prev.snap = false;
+        newest->snap = true;
     }
-    if (snap_for == crt_ctx::TH_SNAP_NONE) th_drop(c);           // (nothing to keep, or the option is off)
+    if (!newest) d.drop();                                       // (nothing to keep, or the option is off)
     std::copy(np.begin(), np.end(), c->prims.begin() + first);   // the host SAH builder reads these
     if (count) {
         HIPCHK(c, hipMemcpyAsync(c->d_raw.p + (size_t)first * 80, records, (size_t)count * 80, hipMemcpyHostToDevice, c->stream));   // the LBVH builder's input
@@ -3271,7 +3264,7 @@ int crt_update_lights(crt_ctx *c, uint32_t first, uint32_t count, const void *re
     }
     { int rc = edit_begin(c); if (rc) return rc; }
     std::copy(nl.begin(), nl.end(), c->lights.begin() + first);
-    th_drop(c);
+    c->dn.drop();
     std::vector<float4> hl((size_t)count * 3);
     for (uint32_t k = 0; k < count; k++) light_rows(nl[k], &hl[3 * (size_t)k]);
     if (count) {

@@ -344,37 +344,58 @@ def test_denoise_svgf_refuses_what_it_cannot_do():
         assert r.denoise_svgf().shape == (48, 64, 4)
 
 
-@pytest.mark.parametrize("k", [1, 2, 4])
-def test_a_failed_allocation_leaves_the_slots_as_they_were(k):
-    """A context that has only called crt_denoise_temporal: crt_denoise_svgf needs four more buffers (both slots' moment
-    planes, the blurred variance, the variance).  The k-th of them fails: CRT_ENOMEM before any slot changes, and the
-    next call finds PREVIOUS and CURRENT where they were."""
+def _failed_allocation(k, before, call, after):
+    """Frame 0 under `before`, then on frame 1 the k-th device allocation of `call` fails: CRT_ENOMEM.  Returns what
+    `after` gives on frame 1 and on frame 2 (k = 0: nothing is injected)."""
     from computeraytracer_amd import Renderer, cornell
     from computeraytracer_amd._lib import CrtError
     from computeraytracer_amd.scene import orbit_cameras
     ps = cornell(64, 48)
     cams = orbit_cameras(ps.camera, 64)
-
-    def run(inject):
-        with Renderer(0) as r:
-            r.upload(ps).build_accel("bvh2")
-            try:
-                _frame(r, cams, 0)
-                r.denoise_temporal()
-                _frame(r, cams, 1)
-                if inject:
-                    r.set_option("debug_fail_alloc", inject)
-                    with pytest.raises(CrtError) as e:
-                        r.denoise_svgf()
-                    r.set_option("debug_fail_alloc", 0)
-                    assert e.value.code == -4                   # CRT_ENOMEM
-                out = svgf_all(r)
-                _frame(r, cams, 2)
-                return out + svgf_all(r)
-            finally:
+    with Renderer(0) as r:
+        r.upload(ps).build_accel("bvh2")
+        try:
+            _frame(r, cams, 0)
+            before(r)
+            _frame(r, cams, 1)
+            if k:
+                r.set_option("debug_fail_alloc", k)
+                with pytest.raises(CrtError) as e:
+                    call(r)
                 r.set_option("debug_fail_alloc", 0)
-    a, b = run(k), run(0)
+                assert e.value.code == -4                       # CRT_ENOMEM
+            out = after(r)
+            _frame(r, cams, 2)
+            return out + after(r)
+        finally:
+            r.set_option("debug_fail_alloc", 0)
+
+
+@pytest.fixture(scope="module")
+def uninjected():
+    """The runs without a failure, once for every k."""
+    return {"svgf": _failed_allocation(0, lambda r: r.denoise_temporal(), None, svgf_all),
+            "temporal": _failed_allocation(0, lambda r: r.denoise(), None, lambda r: r.denoise_temporal(rgb=True, history=True))}
+
+
+@pytest.mark.parametrize("k", [1, 2, 3, 4, 5, 6])
+def test_a_failed_allocation_leaves_the_slots_as_they_were(k, uninjected):
+    """A context that has only called crt_denoise_temporal: crt_denoise_svgf makes six allocations (both slots' moment
+    planes, the blurred variance, the variance, and the G-buffer and keys of the guide set the new frame is built into).
+    The k-th of them fails: CRT_ENOMEM before any slot changes, and the next call finds PREVIOUS and CURRENT where they
+    were."""
+    a, b = _failed_allocation(k, lambda r: r.denoise_temporal(), lambda r: r.denoise_svgf(), svgf_all), uninjected["svgf"]
     assert same(a, b) and (a[2] > SPP).mean() > 0.5 and (a[9][..., 2] > SPP).mean() > 0.5
+
+
+@pytest.mark.parametrize("k", [1, 2, 3])
+def test_a_failed_allocation_of_the_first_temporal_call_leaves_the_context_as_it_was(k, uninjected):
+    """A context that has only called crt_denoise: crt_denoise_temporal makes three allocations (both slots' colour
+    planes and the history weights; the guide set is crt_denoise's, rebuilt in place).  The k-th of them fails:
+    CRT_ENOMEM, and the next call is the one an uninjected run makes."""
+    a = _failed_allocation(k, lambda r: r.denoise(), lambda r: r.denoise_temporal(), lambda r: r.denoise_temporal(rgb=True, history=True))
+    b = uninjected["temporal"]
+    assert same(a, b) and (a[2] == SPP).all() and (a[5] > SPP).mean() > 0.5
 
 
 # ------------------------------------------------------------------ 7. read-only
