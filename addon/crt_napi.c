@@ -814,6 +814,39 @@ static napi_value update_records(napi_env env, napi_callback_info info, int ligh
 static napi_value js_update_primitives(napi_env env, napi_callback_info info) { return update_records(env, info, 0); }
 static napi_value js_update_lights(napi_env env, napi_callback_info info) { return update_records(env, info, 1); }
 
+/* transformPrimitives(h, ops: k*60 B, packed crt_prim_transform records {u32 first, u32 count, f32 m[12], f32
+ * radius_scale}) moves the ranges on the device; readPrimitives(h, first, count) -> Uint8Array (count*80 B), the records
+ * as the device holds them.  transformPrimitivesAsync / readPrimitivesAsync: the Promise forms (below). */
+static napi_value js_transform_primitives(napi_env env, napi_callback_info info)
+{
+    ARGS(2)
+    crt_ctx *ctx = get_ctx(env, argv[0]);
+    if (!ctx) return NULL;
+    void *p = NULL; size_t n = 0;
+    if (!get_bytes(env, argv[1], &p, &n) || n % sizeof(crt_prim_transform)) {
+        napi_throw_type_error(env, NULL, "transformPrimitives: ops must be k*60 bytes");
+        return NULL;
+    }
+    CRT_CHECK(env, ctx, "crt_transform_primitives", crt_transform_primitives(ctx, (const crt_prim_transform *)p, (uint32_t)(n / sizeof(crt_prim_transform))));
+    return undefined(env);
+}
+
+static napi_value js_read_primitives(napi_env env, napi_callback_info info)
+{
+    ARGS(3)
+    crt_ctx *ctx = get_ctx(env, argv[0]);
+    if (!ctx) return NULL;
+    uint32_t first = 0, count = 0;
+    NAPI_OK(env, napi_get_value_uint32(env, argv[1], &first));
+    NAPI_OK(env, napi_get_value_uint32(env, argv[2], &count));
+    void *data = NULL;
+    napi_value ab, ta;
+    NAPI_OK(env, napi_create_arraybuffer(env, (size_t)count * 80, &data, &ab));
+    CRT_CHECK(env, ctx, "crt_read_primitives", crt_read_primitives(ctx, first, count, count ? data : NULL));
+    NAPI_OK(env, napi_create_typedarray(env, napi_uint8_array, (size_t)count * 80, ab, 0, &ta));
+    return ta;
+}
+
 static napi_value js_refit_accel(napi_env env, napi_callback_info info)
 {
     ARGS(1)
@@ -1087,7 +1120,7 @@ static napi_value js_set_stream(napi_env env, napi_callback_info info)
  * fire-and-forget (queue.submit, src/main.js:618-620): a Node display loop must not block its event loop on the
  * GPU either.  Jobs of one context run in call order. */
 enum { JOB_TRACE, JOB_SYNC, JOB_READ_RGBA8, JOB_READ_ACCUM, JOB_GATHER, JOB_READ_FRAME_RGBA8, JOB_READ_FRAME_ACCUM, JOB_READ_SAMPLE_RGBA8,
-       JOB_DENOISE_ADAPTIVE, JOB_DENOISE_TEMPORAL, JOB_DENOISE_SVGF };
+       JOB_DENOISE_ADAPTIVE, JOB_DENOISE_TEMPORAL, JOB_DENOISE_SVGF, JOB_TRANSFORM_PRIMITIVES, JOB_READ_PRIMITIVES };
 typedef struct job {
     napi_async_work work;
     napi_deferred deferred;
@@ -1097,6 +1130,8 @@ typedef struct job {
     crt_denoise_adaptive_params dn;     /* JOB_DENOISE_ADAPTIVE */
     crt_denoise_temporal_params dt;     /* JOB_DENOISE_TEMPORAL */
     crt_denoise_svgf_params ds;         /* JOB_DENOISE_SVGF */
+    crt_prim_transform *ops;            /* JOB_TRANSFORM_PRIMITIVES: the job's own copy of the n ops */
+    uint32_t first;                     /* JOB_READ_PRIMITIVES: records [first, first + n) */
     void *data;              /* ArrayBuffer memory of a read job (kept alive by ab_ref) */
     napi_ref ab_ref;
     char err[640];
@@ -1119,6 +1154,8 @@ static void job_execute(napi_env env, void *data)
     case JOB_DENOISE_ADAPTIVE: j->rc = crt_denoise_adaptive(ctx, &j->dn, NULL, (uint8_t *)j->data, NULL); break;
     case JOB_DENOISE_TEMPORAL: j->rc = crt_denoise_temporal(ctx, &j->dt, NULL, (uint8_t *)j->data, NULL); break;
     case JOB_DENOISE_SVGF: j->rc = crt_denoise_svgf(ctx, &j->ds, NULL, (uint8_t *)j->data, NULL, NULL); break;
+    case JOB_TRANSFORM_PRIMITIVES: j->rc = crt_transform_primitives(ctx, j->ops, j->n); break;
+    case JOB_READ_PRIMITIVES: j->rc = crt_read_primitives(ctx, j->first, j->n, j->n ? j->data : NULL); break;
     default: j->rc = crt_read_frame_accum(ctx, (float *)j->data); break;
     }
     if (j->rc != CRT_OK) {
@@ -1138,8 +1175,10 @@ static void job_complete(napi_env env, napi_status status, void *data)
             napi_value ab;
             const int bytes8 = j->op == JOB_READ_RGBA8 || j->op == JOB_READ_FRAME_RGBA8 || j->op == JOB_READ_SAMPLE_RGBA8 ||
                                j->op == JOB_DENOISE_ADAPTIVE || j->op == JOB_DENOISE_TEMPORAL || j->op == JOB_DENOISE_SVGF;
-            if (napi_get_reference_value(env, j->ab_ref, &ab) == napi_ok)
-                napi_create_typedarray(env, bytes8 ? napi_uint8_array : napi_float32_array, (size_t)j->px * 4, ab, 0, &result);
+            if (napi_get_reference_value(env, j->ab_ref, &ab) == napi_ok) {
+                if (j->op == JOB_READ_PRIMITIVES) napi_create_typedarray(env, napi_uint8_array, (size_t)j->n * 80, ab, 0, &result);
+                else napi_create_typedarray(env, bytes8 ? napi_uint8_array : napi_float32_array, (size_t)j->px * 4, ab, 0, &result);
+            }
         }
         if (!result) napi_get_undefined(env, &result);
         napi_resolve_deferred(env, j->deferred, result);
@@ -1152,6 +1191,7 @@ static void job_complete(napi_env env, napi_status status, void *data)
     }
     if (j->ab_ref) napi_delete_reference(env, j->ab_ref);
     napi_delete_async_work(env, j->work);
+    free(j->ops);
     /* the next job of this context */
     sl->head = j->next;
     if (!sl->head) {
@@ -1163,10 +1203,10 @@ static void job_complete(napi_env env, napi_status status, void *data)
 
 static napi_value start_job(napi_env env, napi_callback_info info, int op)
 {
-    size_t argc = 2;
-    napi_value argv[2];
+    size_t argc = 3;
+    napi_value argv[3];
     NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
-    if (argc < ((op == JOB_TRACE || op == JOB_GATHER || op == JOB_READ_SAMPLE_RGBA8) ? 2u : 1u)) { napi_throw_type_error(env, NULL, "too few arguments"); return NULL; }
+    if (argc < (op == JOB_READ_PRIMITIVES ? 3u : (op == JOB_TRACE || op == JOB_GATHER || op == JOB_READ_SAMPLE_RGBA8 || op == JOB_TRANSFORM_PRIMITIVES) ? 2u : 1u)) { napi_throw_type_error(env, NULL, "too few arguments"); return NULL; }
     slot *sl = get_slot(env, argv[0]);
     if (!sl) return NULL;
     job *j = (job *)calloc(1, sizeof *j);
@@ -1176,6 +1216,20 @@ static napi_value start_job(napi_env env, napi_callback_info info, int op)
     if (op == JOB_DENOISE_SVGF && !denoise_svgf_options(env, argc > 1 ? argv[1] : NULL, argc > 1, &j->ds, NULL, NULL)) { free(j); return NULL; }
     if (op == JOB_TRACE || op == JOB_GATHER || op == JOB_READ_SAMPLE_RGBA8) {
         if (napi_get_value_uint32(env, argv[1], &j->n) != napi_ok) { free(j); napi_throw_type_error(env, NULL, "traceAsync / gatherAsync: a number expected"); return NULL; }
+    }
+    if (op == JOB_TRANSFORM_PRIMITIVES) {                        /* the caller may change its buffer before the job runs */
+        void *p = NULL; size_t n = 0;
+        if (!get_bytes(env, argv[1], &p, &n) || n % sizeof(crt_prim_transform)) { free(j); napi_throw_type_error(env, NULL, "transformPrimitivesAsync: ops must be k*60 bytes"); return NULL; }
+        j->n = (uint32_t)(n / sizeof(crt_prim_transform));
+        j->ops = (crt_prim_transform *)malloc(n ? n : 1);
+        if (!j->ops) { free(j); napi_throw_error(env, NULL, "out of memory"); return NULL; }
+        memcpy(j->ops, p, n);
+    }
+    if (op == JOB_READ_PRIMITIVES) {
+        napi_value ab;
+        if (napi_get_value_uint32(env, argv[1], &j->first) != napi_ok || napi_get_value_uint32(env, argv[2], &j->n) != napi_ok) { free(j); napi_throw_type_error(env, NULL, "readPrimitivesAsync: first and count are numbers"); return NULL; }
+        if (napi_create_arraybuffer(env, (size_t)j->n * 80, &j->data, &ab) != napi_ok ||
+            napi_create_reference(env, ab, 1, &j->ab_ref) != napi_ok) { free(j); napi_throw_error(env, NULL, "out of memory"); return NULL; }
     }
     if (op == JOB_READ_RGBA8 || op == JOB_READ_ACCUM || op == JOB_READ_FRAME_RGBA8 || op == JOB_READ_FRAME_ACCUM || op == JOB_READ_SAMPLE_RGBA8 ||
         op == JOB_DENOISE_ADAPTIVE || op == JOB_DENOISE_TEMPORAL || op == JOB_DENOISE_SVGF) {
@@ -1194,6 +1248,7 @@ static napi_value start_job(napi_env env, napi_callback_info info, int op)
     if (napi_create_promise(env, &j->deferred, &promise) != napi_ok ||
         napi_create_string_utf8(env, "crt_async", NAPI_AUTO_LENGTH, &name) != napi_ok ||
         napi_create_async_work(env, NULL, name, job_execute, job_complete, j, &j->work) != napi_ok) {
+        free(j->ops);
         free(j);
         napi_throw_error(env, NULL, "crt_napi: could not create the asynchronous job");
         return NULL;
@@ -1204,6 +1259,7 @@ static napi_value start_job(napi_env env, napi_callback_info info, int op)
             sl->self = NULL;
             napi_delete_async_work(env, j->work);
             if (j->ab_ref) napi_delete_reference(env, j->ab_ref);
+            free(j->ops);
             free(j);
             napi_throw_error(env, NULL, "crt_napi: could not pin the context handle");
             return NULL;
@@ -1224,6 +1280,8 @@ static napi_value js_read_frame_accum_async(napi_env env, napi_callback_info inf
 static napi_value js_denoise_adaptive_async(napi_env env, napi_callback_info info) { return start_job(env, info, JOB_DENOISE_ADAPTIVE); }
 static napi_value js_denoise_temporal_async(napi_env env, napi_callback_info info) { return start_job(env, info, JOB_DENOISE_TEMPORAL); }
 static napi_value js_denoise_svgf_async(napi_env env, napi_callback_info info) { return start_job(env, info, JOB_DENOISE_SVGF); }
+static napi_value js_transform_primitives_async(napi_env env, napi_callback_info info) { return start_job(env, info, JOB_TRANSFORM_PRIMITIVES); }
+static napi_value js_read_primitives_async(napi_env env, napi_callback_info info) { return start_job(env, info, JOB_READ_PRIMITIVES); }
 
 static napi_value js_abi_version(napi_env env, napi_callback_info info)
 {
@@ -1256,6 +1314,8 @@ static napi_value init(napi_env env, napi_value exports)
         {"denoise", js_denoise}, {"readGbuffer", js_read_gbuffer}, {"readMotion", js_read_motion},
         {"setCamera", js_set_camera}, {"updatePrimitives", js_update_primitives}, {"updateLights", js_update_lights},
         {"refitAccel", js_refit_accel},
+        {"transformPrimitives", js_transform_primitives}, {"transformPrimitivesAsync", js_transform_primitives_async},
+        {"readPrimitives", js_read_primitives}, {"readPrimitivesAsync", js_read_primitives_async},
         {"traceAdaptive", js_trace_adaptive}, {"readAdaptive", js_read_adaptive},
         {"denoiseAdaptive", js_denoise_adaptive}, {"denoiseAdaptiveAsync", js_denoise_adaptive_async},
         {"setSampleOffset", js_set_sample_offset}, {"sampleOffset", js_sample_offset}, {"temporalReset", js_temporal_reset},

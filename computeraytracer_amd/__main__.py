@@ -1,4 +1,4 @@
-"""python -m computeraytracer_amd [--scene file.json] [--width W --height H] [--spp N] [--out image.png] [--denoise K] [--orbit N [--temporal [--variance] [--animate]]]
+"""python -m computeraytracer_amd [--scene file.json] [--width W --height H] [--spp N] [--out image.png] [--denoise K] [--orbit N [--temporal [--variance] [--animate | --animate-device]]]
                                 [--adaptive THRESHOLD [--adaptive-step N] [--counts-out counts.png]]"""
 import argparse
 import json
@@ -33,6 +33,10 @@ def main():
                     help="with --orbit N --denoise K --temporal: before frame k every sphere is moved to its frame-0 centre plus "
                          "(0, 0.5 radius sin(2 pi k / 16), 0) (update_primitives + refit_accel), and option temporal_motion keeps "
                          "the history across those edits")
+    ap.add_argument("--animate-device", action="store_true",
+                    help="with --orbit N --denoise K --temporal: --animate's motion without uploading records: before frame "
+                         "k > 0 one transform_primitives call translates every sphere by (0, up(k) - up(k - 1), 0) on the device, "
+                         "up(k) = 0.5 radius sin(2 pi k / 16) in float32 with the radius of frame 0 (then refit_accel)")
     ap.add_argument("--adaptive", type=float, default=None, metavar="THRESHOLD",
                     help="adaptive sampling (crt_trace_adaptive): rounds of --adaptive-step samples for the 8x8 tiles whose "
                          "error is above THRESHOLD, --spp samples at most, until every tile is done")
@@ -49,6 +53,8 @@ def main():
         ap.error("--variance goes with --orbit N --denoise K --temporal")
     if args.animate and not args.temporal:
         ap.error("--animate goes with --orbit N --denoise K --temporal")
+    if args.animate_device and (not args.temporal or args.animate):
+        ap.error("--animate-device goes with --orbit N --denoise K --temporal, and not with --animate")
     if args.adaptive is not None and (args.orbit is not None or args.checkpoint):
         ap.error("--adaptive goes with neither --orbit nor --checkpoint")
     if (args.counts_out or args.adaptive_min is not None) and args.adaptive is None:
@@ -62,8 +68,9 @@ def main():
         if args.orbit is not None:
             base, ext = os.path.splitext(args.out)
             outs, t0 = [], time.time()
-            if args.animate:
+            if args.animate or args.animate_device:
                 import math
+                import numpy as np
                 r.set_option("temporal_motion", 1)
                 spheres = [int(i) for i in (ps.primitives["category"] == scene.CATEGORY["sphere"]).nonzero()[0]]
             for k, cam in enumerate(scene.orbit_cameras(ps.camera, args.orbit)):
@@ -73,6 +80,13 @@ def main():
                         up = 0.5 * float(rec["data2"][0, 0]) * math.sin(2.0 * math.pi * k / 16.0)
                         r.update_primitives(i, scene.transform_records(rec, [[1, 0, 0], [0, 1, 0], [0, 0, 1]], (0.0, up, 0.0)))
                     r.refit_accel()
+                if args.animate_device and k:
+                    ops = []
+                    for i in spheres:
+                        rad = float(ps.primitives["data2"][i, 0])
+                        up0, up1 = (np.float32(0.5 * rad * math.sin(2.0 * math.pi * j / 16.0)) for j in (k - 1, k))
+                        ops.append((i, 1, [1, 0, 0, 0, 0, 1, 0, np.float32(up1 - up0), 0, 0, 1, 0]))
+                    r.transform_primitives(ops).refit_accel()
                 r.set_camera(cam)
                 if args.temporal:
                     r.set_sample_offset(k * args.spp)
@@ -93,6 +107,8 @@ def main():
                 info["variance"] = True
             if args.animate:
                 info["animate"] = True
+            if args.animate_device:
+                info["animate_device"] = True
             print(json.dumps(info))
             return
         if args.adaptive is not None:

@@ -73,6 +73,8 @@ SIGNATURES = {
     "crt_debug_math": (C.c_int, [_P, C.c_int, _P, _P, _P, C.c_size_t]),
     "crt_set_camera": (C.c_int, [_P, _P]),
     "crt_update_primitives": (C.c_int, [_P, C.c_uint32, C.c_uint32, _P]),
+    "crt_transform_primitives": (C.c_int, [_P, _P, C.c_uint32]),
+    "crt_read_primitives": (C.c_int, [_P, C.c_uint32, C.c_uint32, _P]),
     "crt_update_lights": (C.c_int, [_P, C.c_uint32, C.c_uint32, _P]),
     "crt_refit_accel": (C.c_int, [_P, _P]),
     "crt_debug_hit_pad": (C.c_int, [_P, _P]),
@@ -103,6 +105,11 @@ def adaptive_defaults() -> AdaptiveParams:
     if load().crt_adaptive_defaults(C.byref(p)) != 0:
         raise RuntimeError("crt_adaptive_defaults failed")
     return p
+
+
+class PrimTransform(C.Structure):
+    """crt_prim_transform of include/crt.h (60 bytes; scene.TRANSFORM_DTYPE is the numpy form)."""
+    _fields_ = [("first", C.c_uint32), ("count", C.c_uint32), ("m", C.c_float * 12), ("radius_scale", C.c_float)]
 
 
 class DenoiseParams(C.Structure):

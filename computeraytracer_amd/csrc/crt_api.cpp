@@ -46,6 +46,8 @@ hipError_t build_lbvh_device(const unsigned char *d_raw, uint32_t n, float hit_p
 hipError_t refit_launch_pad(const unsigned char *raw, uint32_t n, uint32_t *out, hipStream_t s);
 hipError_t refit_launch_prims(const unsigned char *raw, uint32_t first, uint32_t count, const uint32_t *slot_of_index, float4 *prim,
                               float4 *primD, hipStream_t s);
+hipError_t refit_launch_transform(unsigned char *raw, const uint32_t *start, const crt_prim_transform *ops, uint32_t n_ops, uint32_t total,
+                                  const uint32_t *slot_of_index, float4 *prim, float4 *primD, hipStream_t s);
 hipError_t refit_levels(const void *nodes, uint32_t width, bool quantised, int root, uint32_t cap, int *list, uint32_t *counter,
                         uint32_t *nch, std::vector<uint32_t> &off, hipStream_t s);
 hipError_t refit_launch_bvh2(const float4 *prim, float pad, const int *list, const std::vector<uint32_t> &off, float *nodes, hipStream_t s);
@@ -283,6 +285,9 @@ struct crt_ctx {
     std::vector<uint32_t> rf_off2, rf_off4;   // ... level l = list[off[l] .. off[l+1])
     DevBuf<uint32_t> rf_nch4, rf_cnt;         // children per 4-wide node; a counter
     DevBuf<float> rf_fb;            // float boxes of the quantised 4-wide tree (32 floats per node)
+    bool prims_moved = false;       // crt_transform_primitives moved records on the device: the geometry of `prims` is out of date
+                                    // (refresh_prims before anything reads it; category, material, spectra and index never are)
+    DevBuf<uint32_t> xf_tab;        // one call's ops table: prefix sums of the counts, then the ops (kept between calls)
 
     // adaptive sampling (crt_adaptive.hip): allocated by the first crt_trace_adaptive, released with the tile
     bool as_on = false;             // the adaptive state: per-tile counts instead of `sample` (left by everything that zeroes it)
@@ -391,6 +396,23 @@ float pad_of(float S, const float cam[16])
 
 float scene_hit_pad(const std::vector<HostPrim> &prims, const float cam[16]) { return pad_of(prims_scale(prims), cam); }
 
+// The host copy of the primitives again as the device holds them, after crt_transform_primitives moved records there.
+// Called before anything reads geometry from c->prims: the host builders and record packing of upload_geometry (and
+// prims_scale, should a caller of it appear that runs after an edit).
+int refresh_prims(crt_ctx *c)
+{
+    if (!c->prims_moved) return CRT_OK;
+    const size_t n = c->prims.size();
+    std::vector<uint8_t> raw(n * 80);
+    if (n) {
+        HIPCHK(c, hipMemcpyAsync(raw.data(), c->d_raw.p, n * 80, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    for (size_t i = 0; i < n; i++) c->prims[i] = read_prim(raw.data(), i);
+    c->prims_moved = false;
+    return CRT_OK;
+}
+
 // The device rows of one light record (crt_upload_scene, crt_update_lights).
 void light_rows(const HostPrim &l, float4 out[3])
 {
@@ -468,6 +490,7 @@ int upload_geometry(crt_ctx *c, int mode)
         int rc = build_accel_on_device(c, &done);
         if (rc || done) return rc;
     }
+    { int rc = refresh_prims(c); if (rc) return rc; }            // (the device build above reads d_raw itself)
     std::vector<uint32_t> order;
     c->bvh = Bvh();
     if (mode == CRT_ACCEL_BVH2 && n > 0) {
@@ -1795,7 +1818,7 @@ void crt_destroy(crt_ctx *c)
     c->w_nee.release(); for (uint32_t b = 0; b < kWfRing; b++) c->w_staging[b].release(); c->w_rng.release(); c->w_misc.release(); c->w_hit.release();
     c->w_vis.release(); c->w_dead.release(); c->w_recA.release(); c->w_recB.release(); c->w_recC.release(); c->w_tea.release(); c->w_wq.release();
     c->dn.release();
-    c->rf_lv2.release(); c->rf_lv4.release(); c->rf_nch4.release(); c->rf_cnt.release(); c->rf_fb.release();
+    c->rf_lv2.release(); c->rf_lv4.release(); c->rf_nch4.release(); c->rf_cnt.release(); c->rf_fb.release(); c->xf_tab.release();
     c->as_counts.release(); c->as_errors.release(); c->as_flags.release(); c->as_active.release(); c->as_n.release(); c->as_q.release();
     if (c->pub_stream) (void)hipStreamSynchronize(c->pub_stream);
     for (int f = 0; f < crt_ctx::kFinishStreams; f++) {
@@ -1868,6 +1891,7 @@ int crt_upload_scene(crt_ctx *c, const void *primitives, size_t nprim, const voi
     c->sample_offset = 0;
     c->dn.drop();
     c->prims.swap(prims);
+    c->prims_moved = false;
     c->lights.swap(lts);
     std::memcpy(c->camera, camera, sizeof c->camera);
     c->W = (uint32_t)camera[11];                                 // ComputeShader.wgsl:85
@@ -3194,6 +3218,45 @@ int crt_set_camera(crt_ctx *c, const float camera[16])
     return edit_end(c);
 }
 
+// The two halves every primitive edit shares (crt_update_primitives, crt_transform_primitives).  Before anything changes:
+// option "temporal_motion": the history stays, with the scene as its newest slot saw it.  Not retaken
+// until a newer slot exists: several edits may precede one refit, and a frame that is never filtered temporally
+// must not cost the older slot its geometry.
+static int prims_edit_history(crt_ctx *c)
+{
+    crt_ctx::Denoise &d = c->dn;
+    crt_ctx::DnSlot *const newest = !d.motion ? nullptr : d.cur.valid ? &d.cur : d.prev.valid ? &d.prev : nullptr;
+    const bool take = newest && !newest->snap;
+    if (take && d.snap.n < c->d_raw.n) {                         // before anything changes: CRT_ENOMEM leaves all as it was
+        ScopedBuf<unsigned char> fresh;
+        HIPCHK(c, fresh.alloc(c->d_raw.n));
+        std::swap(d.snap.p, fresh.p); std::swap(d.snap.n, fresh.n);
+    }
+    if (take) {
+        HIPCHK(c, hipMemcpyAsync(d.snap.p, c->d_raw.p, c->d_raw.n, hipMemcpyDeviceToDevice, c->stream));
+        d.cur.snap = d.prev.snap = false;
+        newest->snap = true;
+    }
+    if (!newest) d.drop();                                       // (nothing to keep, or the option is off)
+    return CRT_OK;
+}
+
+// After d_raw (and the leaf-ordered records) changed: hit_pad exactly as a fresh upload computes it (the full scan: the
+// value enters the kernels), the tree stale, the frame state reset.
+static int prims_edit_end(crt_ctx *c)
+{
+    ScopedBuf<uint32_t> s;
+    HIPCHK(c, s.alloc(1));
+    HIPCHK(c, refit_launch_pad(c->d_raw.p, (uint32_t)c->prims.size(), s.p, c->stream));
+    uint32_t sb = 0;
+    HIPCHK(c, hipMemcpyAsync(&sb, s.p, 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->s_prims = bits_f(sb);
+    c->sc.hit_pad = pad_of(c->s_prims, c->camera);
+    if (c->accel_mode == CRT_ACCEL_BVH2) c->accel_stale = true;  // (CRT_ACCEL_NONE: no tree to go stale)
+    return edit_end(c);
+}
+
 int crt_update_primitives(crt_ctx *c, uint32_t first, uint32_t count, const void *records)
 {
     if (!c) return CRT_EINVAL;
@@ -3214,39 +3277,78 @@ int crt_update_primitives(crt_ctx *c, uint32_t first, uint32_t count, const void
             return fail(c, CRT_EINVAL, "crt_update_primitives: primitive %u: spectrum index out of range", i);
     }
     { int rc = edit_begin(c); if (rc) return rc; }
-    // option "temporal_motion": the history stays, with the scene as its newest slot saw it.  Not retaken
-    // until a newer slot exists: several updates may precede one refit, and a frame that is never filtered temporally
-    // must not cost the older slot its geometry.
-    crt_ctx::Denoise &d = c->dn;
-    crt_ctx::DnSlot *const newest = !d.motion ? nullptr : d.cur.valid ? &d.cur : d.prev.valid ? &d.prev : nullptr;
-    const bool take = newest && !newest->snap;
-    if (take && d.snap.n < c->d_raw.n) {                         // before anything changes: CRT_ENOMEM leaves all as it was
-        ScopedBuf<unsigned char> fresh;
-        HIPCHK(c, fresh.alloc(c->d_raw.n));
-        std::swap(d.snap.p, fresh.p); std::swap(d.snap.n, fresh.n);
-    }
-    if (take) {
-        HIPCHK(c, hipMemcpyAsync(d.snap.p, c->d_raw.p, c->d_raw.n, hipMemcpyDeviceToDevice, c->stream));
-        d.cur.snap = d.prev.snap = false;
-        newest->snap = true;
-    }
-    if (!newest) d.drop();                                       // (nothing to keep, or the option is off)
+    { int rc = prims_edit_history(c); if (rc) return rc; }
     std::copy(np.begin(), np.end(), c->prims.begin() + first);   // the host SAH builder reads these
     if (count) {
         HIPCHK(c, hipMemcpyAsync(c->d_raw.p + (size_t)first * 80, records, (size_t)count * 80, hipMemcpyHostToDevice, c->stream));   // the LBVH builder's input
         if (c->accel_mode >= 0)                                  // the leaf-ordered records, in their slots
             HIPCHK(c, refit_launch_prims(c->d_raw.p, first, count, c->d_slot_of_index.p, c->d_prim.p, c->d_primD.p, c->stream));
     }
-    ScopedBuf<uint32_t> s;
-    HIPCHK(c, s.alloc(1));
-    HIPCHK(c, refit_launch_pad(c->d_raw.p, (uint32_t)n, s.p, c->stream));
-    uint32_t sb = 0;
-    HIPCHK(c, hipMemcpyAsync(&sb, s.p, 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->s_prims = bits_f(sb);
-    c->sc.hit_pad = pad_of(c->s_prims, c->camera);
-    if (c->accel_mode == CRT_ACCEL_BVH2) c->accel_stale = true;  // (CRT_ACCEL_NONE: no tree to go stale)
-    return edit_end(c);
+    return prims_edit_end(c);
+}
+
+int crt_transform_primitives(crt_ctx *c, const crt_prim_transform *ops, uint32_t n_ops)
+{
+    if (!c) return CRT_EINVAL;
+    if (!ops && n_ops) return fail(c, CRT_EINVAL, "crt_transform_primitives: ops is NULL");
+    if (!c->have_scene) return fail(c, CRT_ESTATE, "crt_transform_primitives: upload a scene first");
+    const size_t n = c->prims.size();
+    std::vector<uint32_t> live;                                  // the ops that move something, in the caller's order
+    for (uint32_t k = 0; k < n_ops; k++) {
+        const crt_prim_transform &o = ops[k];
+        if ((uint64_t)o.first + o.count > n)
+            return fail(c, CRT_EINVAL, "crt_transform_primitives: op %u: range [%u, %llu) outside the scene's %zu primitives", k, o.first,
+                        (unsigned long long)o.first + o.count, n);
+        bool finite = std::isfinite(o.radius_scale);
+        for (int a = 0; a < 12; a++) finite = finite && std::isfinite(o.m[a]);
+        if (!finite) return fail(c, CRT_EINVAL, "crt_transform_primitives: op %u: a non-finite matrix entry or radius_scale", k);
+        if (o.count) live.push_back(k);
+    }
+    std::vector<uint32_t> by_first(live);
+    std::sort(by_first.begin(), by_first.end(), [&](uint32_t a, uint32_t b) { return ops[a].first < ops[b].first; });
+    for (size_t j = 1; j < by_first.size(); j++) {
+        const crt_prim_transform &a = ops[by_first[j - 1]], &b = ops[by_first[j]];
+        if (a.first + a.count > b.first)
+            return fail(c, CRT_EINVAL, "crt_transform_primitives: ops %u and %u overlap: both move primitive %u", by_first[j - 1], by_first[j], b.first);
+    }
+    // the device table: live.size() + 1 prefix sums (padded to whole records), then the ops
+    const size_t op_dw = sizeof(crt_prim_transform) / 4, head = (live.size() + 1 + op_dw - 1) / op_dw * op_dw;
+    std::vector<uint32_t> tab(head + live.size() * op_dw, 0u);
+    uint32_t total = 0;                                          // <= n: the ranges are disjoint
+    for (size_t j = 0; j < live.size(); j++) {
+        tab[j] = total;
+        total += ops[live[j]].count;
+        std::memcpy(&tab[head + j * op_dw], &ops[live[j]], sizeof(crt_prim_transform));
+    }
+    tab[live.size()] = total;
+    { int rc = edit_begin(c); if (rc) return rc; }
+    // the table and the snapshot are allocated before anything changes, the history included: CRT_ENOMEM leaves all as it was
+    if (total && c->xf_tab.n < tab.size()) HIPCHK(c, c->xf_tab.alloc(std::max(tab.size(), 2 * c->xf_tab.n)));
+    { int rc = prims_edit_history(c); if (rc) return rc; }
+    if (total) {
+        HIPCHK(c, hipMemcpyAsync(c->xf_tab.p, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, c->stream));
+        const bool built = c->accel_mode >= 0;                   // the leaf-ordered records exist: moved in the same thread
+        HIPCHK(c, refit_launch_transform(c->d_raw.p, c->xf_tab.p, (const crt_prim_transform *)(c->xf_tab.p + head), (uint32_t)live.size(), total,
+                                         c->d_slot_of_index.p, built ? c->d_prim.p : nullptr, built ? c->d_primD.p : nullptr, c->stream));
+        c->prims_moved = true;
+    }
+    return prims_edit_end(c);                                    // (its sync covers the table's upload from `tab`)
+}
+
+int crt_read_primitives(crt_ctx *c, uint32_t first, uint32_t count, void *out)
+{
+    if (!c) return CRT_EINVAL;
+    if (!out && count) return fail(c, CRT_EINVAL, "crt_read_primitives: out is NULL");
+    if (!c->have_scene) return fail(c, CRT_ESTATE, "crt_read_primitives: upload a scene first");
+    if ((uint64_t)first + count > c->prims.size())
+        return fail(c, CRT_EINVAL, "crt_read_primitives: range [%u, %llu) outside the scene's %zu primitives", first,
+                    (unsigned long long)first + count, c->prims.size());
+    { int rc = edit_begin(c); if (rc) return rc; }               // (a sync point; nothing is edited)
+    if (count) {
+        HIPCHK(c, hipMemcpyAsync(out, c->d_raw.p + (size_t)first * 80, (size_t)count * 80, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    return CRT_OK;
 }
 
 int crt_update_lights(crt_ctx *c, uint32_t first, uint32_t count, const void *records)

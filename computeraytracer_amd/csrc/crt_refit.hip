@@ -4,6 +4,8 @@
 //
 //   k_refit_pad       max |corner coordinate| over the primitives, as scene_hit_pad computes it (NaN ignored, inf kept)
 //   k_refit_prims     48-byte records + D of primitives [first, first+count) into their slots (slot_of_index)
+//   k_refit_transform every op of one crt_transform_primitives call: the 80-byte records moved where they lie, and their
+//                     48-byte records + D in the same thread
 //   k_refit_expand    once per tree: the inner nodes level by level from the root (one launch per level), so that a
 //                     refit can walk the levels bottom-up
 //   k_refit_bvh2      one launch per BVH2 level, deepest first: each node's two child boxes, from the leaf's primitives
@@ -19,6 +21,7 @@
 
 #include <vector>
 
+#include "../../include/crt.h"
 #include "crt_bvh.h"
 #include "crt_math.h"
 #include "crt_prim.h"
@@ -73,6 +76,56 @@ __global__ __launch_bounds__(256) void k_refit_prims(const unsigned char *__rest
     float4 A, B, C, D;
     prim_record(p, A, B, C, D);
     const uint32_t slot = slot_of_index[first + k];
+    prim[3 * (size_t)slot + 0] = A; prim[3 * (size_t)slot + 1] = B; prim[3 * (size_t)slot + 2] = C;
+    primD[slot] = D;
+}
+
+// crt_transform_primitives (include/crt.h pins the arithmetic: every product and sum rounded, in this order).
+__device__ __forceinline__ f3 xf_vector(const float *__restrict__ m, f3 v)
+{
+    return f3{__fadd_rn(__fadd_rn(__fmul_rn(m[0], v.x), __fmul_rn(m[1], v.y)), __fmul_rn(m[2], v.z)),
+              __fadd_rn(__fadd_rn(__fmul_rn(m[4], v.x), __fmul_rn(m[5], v.y)), __fmul_rn(m[6], v.z)),
+              __fadd_rn(__fadd_rn(__fmul_rn(m[8], v.x), __fmul_rn(m[9], v.y)), __fmul_rn(m[10], v.z))};
+}
+__device__ __forceinline__ f3 xf_point(const float *__restrict__ m, f3 p)
+{
+    const f3 v = xf_vector(m, p);
+    return f3{__fadd_rn(v.x, m[3]), __fadd_rn(v.y, m[7]), __fadd_rn(v.z, m[11])};
+}
+
+// Thread t of the concatenated ranges: its op is the last one whose start (prefix sum of the counts; start[n_ops] =
+// total, no op empty) is <= t.  Only the nine (spheres: four) geometry floats of the 80-byte record are stored, so every
+// other byte stays as it was; prim / primD may be null (no structure built yet: the build makes them).
+__global__ __launch_bounds__(256) void k_refit_transform(unsigned char *raw, const uint32_t *__restrict__ start, const crt_prim_transform *__restrict__ ops,
+                                                         uint32_t n_ops, uint32_t total, const uint32_t *__restrict__ slot_of_index,
+                                                         float4 *__restrict__ prim, float4 *__restrict__ primD)
+{
+    const uint32_t t = blockIdx.x * 256u + threadIdx.x;
+    if (t >= total) return;
+    uint32_t lo = 0, hi = n_ops;                                 // start[lo] <= t < start[hi]
+    while (hi - lo > 1u) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (start[mid] <= t) lo = mid; else hi = mid;
+    }
+    const crt_prim_transform &op = ops[lo];                     // (include/crt.h: first, count, m[12], radius_scale)
+    const size_t i = (size_t)op.first + (t - start[lo]);
+    RawPrim p = load_raw(raw, i);
+    float *rec = (float *)(raw + i * 80);
+    p.d1 = xf_point(op.m, p.d1);
+    rec[4] = p.d1.x; rec[5] = p.d1.y; rec[6] = p.d1.z;
+    if (p.category == 1u) {
+        p.d2.x = __fmul_rn(p.d2.x, op.radius_scale);
+        rec[8] = p.d2.x;
+    } else {
+        p.d2 = xf_vector(op.m, p.d2);
+        p.d3 = xf_vector(op.m, p.d3);
+        rec[8] = p.d2.x; rec[9] = p.d2.y; rec[10] = p.d2.z;
+        rec[12] = p.d3.x; rec[13] = p.d3.y; rec[14] = p.d3.z;
+    }
+    if (!prim) return;
+    float4 A, B, C, D;
+    prim_record(p, A, B, C, D);
+    const uint32_t slot = slot_of_index[i];
     prim[3 * (size_t)slot + 0] = A; prim[3 * (size_t)slot + 1] = B; prim[3 * (size_t)slot + 2] = C;
     primD[slot] = D;
 }
@@ -193,6 +246,15 @@ hipError_t refit_launch_prims(const unsigned char *raw, uint32_t first, uint32_t
 {
     if (count == 0) return hipSuccess;
     hipLaunchKernelGGL(k_refit_prims, dim3(blocks_of(count)), dim3(256), 0, s, raw, first, count, slot_of_index, prim, primD);
+    return hipGetLastError();
+}
+
+// start: n_ops + 1 prefix sums (start[n_ops] = total), ops: n_ops records, both on the device; no op is empty.
+hipError_t refit_launch_transform(unsigned char *raw, const uint32_t *start, const crt_prim_transform *ops, uint32_t n_ops, uint32_t total,
+                                  const uint32_t *slot_of_index, float4 *prim, float4 *primD, hipStream_t s)
+{
+    if (total == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_refit_transform, dim3(blocks_of(total)), dim3(256), 0, s, raw, start, ops, n_ops, total, slot_of_index, prim, primD);
     return hipGetLastError();
 }
 

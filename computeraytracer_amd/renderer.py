@@ -117,6 +117,24 @@ class Renderer:
         self._chk(self._lib.crt_update_primitives(self._h, int(first), rec.nbytes // 80, rec.ctypes.data))
         return self
 
+    def transform_primitives(self, ops):
+        """Move primitive ranges on the device (crt_transform_primitives): ops as scene.transform_ops takes them, e.g.
+        [(first, count, m)] with m the 3 x 4 matrix (R | t), or (first, count, m, radius_scale) where spheres scale.
+        The tree goes stale until refit_accel(); read_primitives shows the moved records."""
+        from .scene import transform_ops
+        t = transform_ops(ops)
+        self._chk(self._lib.crt_transform_primitives(self._h, t.ctypes.data if len(t) else None, len(t)))
+        return self
+
+    def read_primitives(self, first: int = 0, count: int | None = None) -> np.ndarray:
+        """Primitive records [first, first + count) as they lie on the device (PRIM_DTYPE; count None: to the end)."""
+        from .scene import PRIM_DTYPE
+        if count is None:
+            count = len(self.scene.primitives) - int(first)
+        out = np.zeros(int(count), PRIM_DTYPE)
+        self._chk(self._lib.crt_read_primitives(self._h, int(first), int(count), out.ctypes.data if count else None))
+        return out
+
     def update_lights(self, first: int, records):
         """Replace light records [first, first + len(records)) (e.g. scene.lights_of(edited primitives))."""
         rec = self._records(records)

@@ -50,6 +50,9 @@ PATCH_DTYPE = np.dtype({
     "itemsize": 64,
 })
 
+# crt_prim_transform of include/crt.h: one op of Renderer.transform_primitives (m: row-major 3x4, rows (R | t))
+TRANSFORM_DTYPE = np.dtype([("first", "<u4"), ("count", "<u4"), ("m", "<f4", (12,)), ("radius_scale", "<f4")])
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SCENES_DIR = os.path.normpath(os.path.join(_HERE, "..", "scenes"))
 
@@ -179,6 +182,19 @@ def transform_records(records: np.ndarray, R, t, scale: float = 1.0) -> np.ndarr
     sph = cat == CATEGORY["sphere"]
     out["data2"] = np.where(sph[:, None], d2 * s, (s * d2) @ R.T).astype(np.float32)
     out["data3"] = np.where(sph[:, None], d3, (s * d3) @ R.T).astype(np.float32)
+    return out
+
+
+def transform_ops(ops) -> np.ndarray:
+    """Ops for Renderer.transform_primitives as a TRANSFORM_DTYPE array.  Takes such an array, or a sequence of
+    (first, count, m) / (first, count, m, radius_scale) with m 12 numbers or 3 x 4 (rows (R | t)); radius_scale 1."""
+    if isinstance(ops, np.ndarray) and ops.dtype == TRANSFORM_DTYPE:
+        return np.ascontiguousarray(ops).reshape(-1)
+    out = np.zeros(len(ops), TRANSFORM_DTYPE)
+    for k, op in enumerate(ops):
+        out[k]["first"], out[k]["count"] = int(op[0]), int(op[1])
+        out[k]["m"] = np.asarray(op[2], np.float32).reshape(12)
+        out[k]["radius_scale"] = np.float32(op[3]) if len(op) > 3 else np.float32(1.0)
     return out
 
 

@@ -12,6 +12,7 @@
  *   612-617 blit to the canvas                    readRgba8() / writePPM()   (display only)
  *           (no counterpart)                      denoise(): filtered preview of the same average
  *           queue.writeBuffer(camera / primitives / lights)   setCamera / updatePrimitives + refitAccel / updateLights
+ *           (no counterpart)                      transformPrimitives: ranges moved on the device, nothing uploaded
  *   620     requestAnimationFrame(frame) forever  run(spp): spp frames, optionally fused
  */
 const fs = require('fs');
@@ -69,6 +70,13 @@ function Main(options = {}) {
     updatePrimitives: (first, records) => a.updatePrimitives(device, first, records),
     updateLights: (first, records) => a.updateLights(device, first, records),
     refitAccel: () => a.refitAccel(device),
+    // move primitive ranges on the device instead of uploading moved records (include/crt.h crt_transform_primitives):
+    // ops = [{first, count, m: 12 numbers (row-major 3x4, rows (R | t)), radiusScale = 1}]; the tree goes stale until
+    // refitAccel().  readPrimitives: Uint8Array(count * 80), the records as the device holds them.
+    transformPrimitives: (ops) => a.transformPrimitives(device, packTransforms(ops)),
+    transformPrimitivesAsync: (ops) => a.transformPrimitivesAsync(device, packTransforms(ops)),
+    readPrimitives: (first, count) => a.readPrimitives(device, first, count),
+    readPrimitivesAsync: (first, count) => a.readPrimitivesAsync(device, first, count),
     // adaptive sampling (include/crt.h "Adaptive sampling"): more samples for the 8x8 tiles that have not converged;
     // returns how many tiles that was (0: done).  readAdaptive: {counts, errors, tilesX, tilesY}
     traceAdaptive: (opts = {}) => a.traceAdaptive(device, opts),
@@ -105,6 +113,20 @@ function Main(options = {}) {
   };
 }
 
+// The ops of transformPrimitives as packed crt_prim_transform records (60 bytes each: u32 first, u32 count, f32 m[12],
+// f32 radius_scale); numbers become float32 by Math.fround's rule, as a Float32Array store rounds them.
+function packTransforms(ops) {
+  const buf = new ArrayBuffer(60 * ops.length), v = new DataView(buf);
+  ops.forEach((op, k) => {
+    if (!op.m || op.m.length !== 12) throw new TypeError('transformPrimitives: m must hold 12 numbers');
+    v.setUint32(60 * k, op.first, true);
+    v.setUint32(60 * k + 4, op.count, true);
+    for (let i = 0; i < 12; i++) v.setFloat32(60 * k + 8 + 4 * i, op.m[i], true);
+    v.setFloat32(60 * k + 56, op.radiusScale === undefined ? 1 : op.radiusScale, true);
+  });
+  return new Uint8Array(buf);
+}
+
 // n cameras (Float32Array(16) each) whose eye turns about the look-at point around the up axis, k/n of a full turn for
 // k = 0..n-1 (Rodrigues' rotation in doubles); look-at, up, width, height and focal length kept (scene.orbit_cameras).
 function orbitCameras(camera, n) {
@@ -131,4 +153,4 @@ function writePPM(file, rgba, width, height) {
   fs.writeFileSync(file, Buffer.concat([Buffer.from(`P6\n${width} ${height}\n255\n`), out]));
 }
 
-module.exports = { Main, writePPM, loadAddon, orbitCameras };
+module.exports = { Main, writePPM, loadAddon, orbitCameras, packTransforms };

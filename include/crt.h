@@ -245,7 +245,8 @@ int crt_read_gbuffer(crt_ctx *ctx, float *out);
  * Move the camera or edit primitives and lights of the uploaded scene in place (DESIGN.md "Scene edits"), instead of
  * crt_upload_scene + crt_build_accel.  The tree's topology is kept; crt_refit_accel recomputes its boxes on the GPU.
  * Culling never decides a hit, so the image equals the one a fresh upload and build of the edited buffers gives.
- * Rules shared by the four edit calls (crt_set_camera, crt_update_primitives, crt_update_lights, crt_refit_accel):
+ * Rules shared by the five edit calls (crt_set_camera, crt_update_primitives, crt_transform_primitives, crt_update_lights,
+ * crt_refit_accel):
  *   - each is a sync point (what is in flight finishes first, against the old scene);
  *   - then the frame state resets as crt_reset does: accumulator zeroed, sample 0, frame ring emptied;
  *   - tile, row bands, bound outputs, stream, options and a crt_comm_partition stay (W and H never change: every rank
@@ -267,6 +268,34 @@ int crt_set_camera(crt_ctx *ctx, const float camera[16]);
  * the next crt_denoise_temporal can look every edited primitive's pixels up where they were ("Temporal reuse" below).
  * If that copy cannot be allocated the call returns CRT_ENOMEM with the context, the scene and the history as they were. */
 int crt_update_primitives(crt_ctx *ctx, uint32_t first, uint32_t count, const void *records);
+/* Move primitive ranges where they lie on the device, instead of transforming them on the host and uploading them
+ * through crt_update_primitives.  One call takes any number of ops; each moves primitives
+ * [first, first+count) by the row-major 3x4 matrix m.  The arithmetic is binary32, every product and sum rounded, in
+ * this order:
+ *   point  (x, y, z): x' = ((m0*x + m1*y) + m2*z) + m3,  y' from m4..m7,  z' from m8..m11
+ *   vector (x, y, z): the same without the last addition
+ *   patches and triangles: data1.xyz is a point, data2.xyz and data3.xyz are vectors
+ *   spheres: data1.xyz is a point, data2.x (the radius) is multiplied by radius_scale
+ * Every other byte of a record stays as it was (category, the w lanes, a sphere's unused lanes, data4).  With spheres in
+ * a range the caller makes m a similarity of scale radius_scale.
+ * The contract is crt_update_primitives': a sync point; the frame state resets; with a tree the tree goes stale until
+ * crt_refit_accel or crt_build_accel (several calls may precede one refit); hit_pad is recomputed and equals a fresh
+ * upload's; the history of crt_denoise_temporal is dropped unless option "temporal_motion" is 1, and then the records
+ * are first copied as they were (CRT_ENOMEM leaves the context, the scene and the history as they were), so that the
+ * temporal filters and crt_read_motion follow a transformed mesh as they follow an uploaded edit.  Light records are
+ * not touched: an emitter is moved with crt_update_lights.
+ * CRT_EINVAL, with the context as it was: ops NULL with n_ops > 0, a range outside the scene, two ranges that share a
+ * primitive (the ops may come in any order; count 0 is allowed), a non-finite m entry or radius_scale. */
+typedef struct {
+    uint32_t first, count;   /* primitives [first, first+count) */
+    float m[12];             /* row-major 3x4: rows (m0 m1 m2 | m3), (m4 m5 m6 | m7), (m8 m9 m10 | m11) */
+    float radius_scale;      /* spheres: radius' = radius * radius_scale */
+} crt_prim_transform;
+int crt_transform_primitives(crt_ctx *ctx, const crt_prim_transform *ops, uint32_t n_ops);
+/* Primitive records [first, first+count) as they lie on the device (count x 80 bytes): after crt_transform_primitives the
+ * only place where the caller sees the geometry.  A sync point like crt_read_gbuffer; it only reads, and it works on a
+ * stale tree.  CRT_EINVAL for a range outside the scene or out NULL with count > 0. */
+int crt_read_primitives(crt_ctx *ctx, uint32_t first, uint32_t count, void *out);
 /* Replace light records [first, first+count) (count x 80 bytes, crt_upload_scene's validation; 1/area recomputed). */
 int crt_update_lights(crt_ctx *ctx, uint32_t first, uint32_t count, const void *records);
 /* Recompute every box of the tree (BVH2 and 4-wide, float and quantised; the quantisation grid re-derived) from the
@@ -370,9 +399,10 @@ int crt_sample_offset(crt_ctx *ctx, uint32_t *out);
  * PREVIOUS; further calls in the same frame (after more samples, say) blend against the same PREVIOUS and overwrite
  * CURRENT, so calling twice is idempotent.  History survives crt_set_camera, crt_reset, crt_build_accel and a
  * crt_refit_accel with no primitive update before it; it is dropped by crt_upload_scene, crt_set_tile,
- * crt_set_row_bands, crt_comm_partition, crt_update_primitives, crt_update_lights, crt_write_accum and
- * crt_denoise_temporal_reset.
- * Moving geometry: with option "temporal_motion" = 1 (default 0) crt_update_primitives keeps the history, and the next
+ * crt_set_row_bands, crt_comm_partition, crt_update_primitives, crt_transform_primitives, crt_update_lights,
+ * crt_write_accum and crt_denoise_temporal_reset.
+ * Moving geometry: with option "temporal_motion" = 1 (default 0) crt_update_primitives and crt_transform_primitives keep
+ * the history, and the next
  * crt_denoise_temporal reprojects every pixel whose primitive's record changed through that primitive's previous record
  * (DESIGN.md 6f): the hit keeps its coordinates in the primitive (a patch's or triangle's edge coordinates, a sphere's
  * direction from the centre), x_p and n_p become the position x~ and normal n~ they had in the old pose, and x~, n~ take

@@ -4,10 +4,18 @@ around synchronous calls, warm, median of --reps.
   build_lbvh_ms        crt_build_accel(CRT_ACCEL_LBVH)
   refit_ms             crt_refit_accel after a crt_update_primitives (the update itself not timed)
   update_ms            crt_update_primitives of the moved tenth (records, hit_pad reduction, state reset)
+  transform_ms         crt_transform_primitives of the same tenth by the same rigid move, one op (the records never leave
+                       the device; forward and inverse alternate so that the geometry stays where it is)
+  transform_1000_ms    the same tenth as 1000 ops of one call
+  refit_after_transform_ms   crt_refit_accel after such a call
   set_camera_ms        crt_set_camera with a pad that does not grow (no refit): sync + camera + state reset
   set_camera_refit_ms  crt_set_camera with an eye farther out each call (the pad grows: inline refit)
   step_ms_refit / step_ms_fresh   ms per --spp step after a rigid move of a contiguous tenth of the primitives,
                        refitted tree against a fresh LBVH build of the same buffers (the tree-quality cost)
+
+--parent DIR: a checkout of the parent commit with its library built.  Its crt_update_primitives of the same tenth is
+measured in child processes (this tool with --update-only --tree DIR) before and after this build's run, in one session:
+parent_update_ms holds both medians, their difference is the run-to-run spread the comparison allows for.
 
 Per-kernel times come from a separate run under rocprofv3 --kernel-trace --stats.  Prints one JSON line; --out also
 writes it."""
@@ -18,7 +26,8 @@ import statistics
 import sys
 import time
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+TREE = sys.argv[sys.argv.index("--tree") + 1] if "--tree" in sys.argv else os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.abspath(TREE))
 
 import numpy as np  # noqa: E402
 
@@ -38,7 +47,7 @@ def timed(fn, reps, warm=3):
     return round(statistics.median(ts), 4)
 
 
-def run_scene(name, ps, reps, spp, steps):
+def run_scene(name, ps, reps, spp, steps, update_only=False):
     n = len(ps.primitives)
     first, cnt = n // 3, n // 10
     th = 0.05
@@ -58,6 +67,36 @@ def run_scene(name, ps, reps, spp, steps):
             r.update_primitives(first, rec_b if flip[0] else rec_a)
 
         res["update_ms"] = timed(update, reps)
+        if update_only:
+            return res
+        from computeraytracer_amd.scene import transform_ops            # (a parent tree has none: imported past --update-only)
+        t3 = np.float64([6.0, 2.0, -4.0])
+        fwd = np.concatenate([R, t3[:, None]], 1).astype(np.float32).reshape(12)
+        inv = np.concatenate([R.T, -(R.T @ t3)[:, None]], 1).astype(np.float32).reshape(12)
+        bounds = np.linspace(first, first + cnt, 1001).astype(np.int64)
+        # packed once, outside the timed region (transform_ops passes such an array through)
+        many = [transform_ops([(int(a), int(b - a), m) for a, b in zip(bounds[:-1], bounds[1:])]) for m in (inv, fwd)]
+        one = [transform_ops([(first, cnt, m)]) for m in (inv, fwd)]
+
+        def transform(ops):
+            def call():
+                flip[0] ^= 1
+                r.transform_primitives(ops[flip[0]])
+            return call
+
+        flip[0] = 0
+        res["transform_ms"] = timed(transform(one), reps, warm=4)        # (an even number of calls: back where it began)
+        res["transform_1000_ms"] = timed(transform(many), reps, warm=4)
+        ts = []
+        for _ in range(reps + 4):
+            transform(one)()
+            t = time.perf_counter()
+            rebuilt = r.refit_accel()
+            ts.append((time.perf_counter() - t) * 1e3)
+            assert not rebuilt
+        res["refit_after_transform_ms"] = round(statistics.median(ts[4:]), 4)
+        r.update_primitives(first, rec_a)                                # the uploaded records again, for what follows
+        flip[0] = 0
         ts = []
         for _ in range(reps + 3):
             update()
@@ -120,10 +159,24 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--soup-tris", type=int, default=10_000_000)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--parent", default=None, metavar="DIR", help="a built checkout of the parent commit: its update_ms, before and after")
+    ap.add_argument("--update-only", action="store_true", help="build_lbvh_ms and update_ms only")
+    ap.add_argument("--tree", default=None, metavar="DIR", help="import the package from this checkout instead of the tool's own")
     a = ap.parse_args()
-    out = {"s2": run_scene("S2 atrium250k", atrium250k(1920, 1080), a.reps, a.spp, a.steps)}
+
+    def parent_update():
+        import subprocess
+        cmd = [sys.executable, os.path.abspath(__file__), "--update-only", "--tree", a.parent, "--reps", str(a.reps), "--soup-tris", str(a.soup_tris)]
+        return json.loads(subprocess.run(cmd, check=True, capture_output=True, text=True).stdout.strip().splitlines()[-1])
+
+    before = parent_update() if a.parent else None
+    out = {"s2": run_scene("S2 atrium250k", atrium250k(1920, 1080), a.reps, a.spp, a.steps, a.update_only)}
     if a.soup_tris:
-        out["soup"] = run_scene(f"soup {a.soup_tris}", soup(a.soup_tris, 1920, 1080), a.reps, a.spp, a.steps)
+        out["soup"] = run_scene(f"soup {a.soup_tris}", soup(a.soup_tris, 1920, 1080), a.reps, a.spp, a.steps, a.update_only)
+    if a.parent:
+        after = parent_update()
+        for k in out:
+            out[k]["parent_update_ms"] = [before[k]["update_ms"], after[k]["update_ms"]]
     line = json.dumps(out)
     print(line)
     if a.out:
