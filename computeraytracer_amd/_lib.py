@@ -70,6 +70,7 @@ SIGNATURES = {
     "crt_debug_trace_rays": (C.c_int, [_P, _P, C.c_size_t, _P, _P]),
     "crt_debug_read_accel": (C.c_int, [_P, C.c_int, _P, C.c_size_t, _P]),
     "crt_debug_probes": (C.c_int, [_P, _P]),
+    "crt_debug_gen_culled": (C.c_int, [_P, _P]),
     "crt_debug_math": (C.c_int, [_P, C.c_int, _P, _P, _P, C.c_size_t]),
     "crt_set_camera": (C.c_int, [_P, _P]),
     "crt_update_primitives": (C.c_int, [_P, C.c_uint32, C.c_uint32, _P]),

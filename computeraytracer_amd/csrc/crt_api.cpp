@@ -194,6 +194,7 @@ struct crt_ctx {
     int wf_tail_walk = 1;           // shade walks the ray lists once few paths are left
     int wf_gen_blocks = 128;        // k_wf_gen: waves per shard (64 shards)
     int wf_trace_form = 2;          // traversal kernel: 2 = k_wf_trace2 (ray ring + primitive tasks), 1 = k_wf_trace
+    int wf_cull_miss = 1;           // k_wf_gen decides whole work chunks whose camera rays all miss the tree's root boxes
     int wf_chunk = 1;               // iterations per status record at most
     int wf_ahead = 3;               // iterations in flight per pipe before the pump waits for a status
     int wf_ring = 32;               // batches in flight at most (2..kWfRing): bounds how many calls a bound output can lag
@@ -1244,6 +1245,21 @@ bool wf_has_room(crt_ctx *c)
 //      starts afresh -- so without the fork wait the reset of the new run's second batch could zero the side counters
 //      under the previous run's k_wf_finish: round 3's lost-paths defect, test_flush_without_host_sync_then_quick_batches.)
 //      WfCtl::dropped is never reset by a set-up, only once the host has reported it.
+//  I10 Consumed work is not paths: k_wf_gen's CULL form decides whole work chunks itself -- it stores their
+//      samples into the batch's staging buffer and starts nothing.  Nothing here assumes otherwise: `consumed` and `per_it`
+//      only pace the feeding (a gen launch that culls takes MORE work per iteration; the estimate follows it), `alive`
+//      counts what k_wf_gen started and k_wf_shade kept, and a pipe is drained when its queues are dry and it lists no rays
+//      -- true from the first status on for a frame that is culled whole, whose queues drain inside gen launches alone
+//      (while work is left every iteration re-lists the dead slots and launches k_wf_gen: rearm).  A batch is not resolved
+//      before a culled sample's staging store has landed: the gen launch G that stored it took the work from the batch's
+//      queue, so the queue was not dry before G; G belongs to some pipe p, and p's first status that says "dry" for the batch
+//      is written by a shade launch BEHIND G in p's stream (a status written before G would have seen the work G took).  The
+//      host resolves only after it has READ such a status from every pipe -- so G has completed, its stores with it, before
+//      the resolve pass is even enqueued.  wf_retire asks every pipe that is not `done` for dry[b]; it skips a `done` pipe,
+//      so wf_finish_all marks a pipe done only when that pipe's OWN records say dry for every open batch (r.work_left alone
+//      may come from the other pipe's status, and a frame that is culled whole or nearly so lists no rays while its work
+//      is still being taken, which without the cull practically never happened).  The batches still open when the flush
+//      loop ends are resolved behind ev_join of every pipe.
 //
 // Feed the pool: enqueue the iterations the published work needs (see the head of this section).  for_room = false:
 // return once they are enqueued (the call does not wait for its work); for_room = true: keep feeding and reading
@@ -1371,7 +1387,12 @@ int wf_finish_all(crt_ctx *c)
         if (!r.work_left) pp.chunk = 1;
         // every alive slot lists a ray: no rays and no work means this pipe is drained (another pipe's view of the
         // queues can lag; a pipe with no rays while work may be left simply keeps going)
-        if (!r.work_left && pp.any && pp.rays == 0) { pp.done = true; active--; continue; }
+        // -- but only on its OWN word that every queue is dry (I10): r.work_left may have turned false through another
+        // pipe's status, and a gen launch of this pipe behind the record just read may have been the one that took, and
+        // culled, the last chunks.  wf_retire asks nothing of a drained pipe, so its own record has to say it here.
+        bool own_dry = true;
+        for (const WfBatch &b : r.open) own_dry = own_dry && pp.dry[b.id];
+        if (!r.work_left && pp.any && pp.rays == 0 && own_dry) { pp.done = true; active--; continue; }
         if (!r.work_left && pp.any && c->wf_tail_walk && pp.rays < std::min<unsigned long long>((unsigned long long)r.Pp / 4u, 65536ull)) {
             // The tail: no path can start any more, so ray counts only shrink from here.  Shade walks
             // the ray lists instead of the whole pool and the grids shrink.  Per-shard bound for later iterations:
@@ -1637,6 +1658,7 @@ int wf_trace_batch(crt_ctx *c, uint32_t n, const AsBatch *as)
             W.rearm = 0;
             // k_wf_gen: waves per shard (each takes every gen_blocks-th chunk of 64 dead slots of its shard's list)
             W.gen_blocks = std::max(1u, std::min((uint32_t)c->wf_gen_blocks, g.list_cap / 64u));
+            W.cull_miss = c->wf_cull_miss ? 1u : 0u;
             W.recA = c->w_recA.p + g.list_per_pipe * (size_t)p; W.recB = c->w_recB.p + g.list_per_pipe * (size_t)p;
             W.recC = c->w_recC.p + g.list_per_pipe * (size_t)p;
             for (uint32_t b = 0; b < kWfRing; b++) {
@@ -2403,6 +2425,26 @@ int crt_reset_counters(crt_ctx *c)
     for (int k = 0; k < 8; k++) c->probes[k] = 0;
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipMemsetAsync(c->d_counters.p, 0, CRT_NCOUNTERS * sizeof(unsigned long long), c->stream));
+    // (k_wf_gen's own count lives in the pipes' control blocks; every run's pipes start behind the context's stream)
+    for (int p = 0; p < crt_ctx::kMaxPipes; p++)
+        if (c->w_ctl[p].p) HIPCHK(c, hipMemsetAsync(&c->w_ctl[p].p->gen_culled[0], 0, sizeof(unsigned long long) * kWfShards, c->stream));
+    return CRT_OK;
+}
+
+int crt_debug_gen_culled(crt_ctx *c, uint64_t *out)
+{
+    if (!c || !out) return CRT_EINVAL;
+    HIPCHK(c, hipSetDevice(c->device));
+    { int rc_ = wf_flush(c); if (rc_) return rc_; }
+    HIPCHK(c, hipStreamSynchronize(c->stream));                  // (a flush joins the pipes' streams into this one)
+    uint64_t n = 0;
+    for (int p = 0; p < crt_ctx::kMaxPipes; p++) {
+        if (!c->w_ctl[p].p) continue;
+        unsigned long long sh[kWfShards];
+        HIPCHK(c, hipMemcpy(sh, &c->w_ctl[p].p->gen_culled[0], sizeof sh, hipMemcpyDeviceToHost));
+        for (uint32_t s_ = 0; s_ < kWfShards; s_++) n += sh[s_];
+    }
+    *out = n;
     return CRT_OK;
 }
 
@@ -2509,6 +2551,7 @@ int crt_set_option(crt_ctx *c, const char *name, int64_t value)
     }
     if (!std::strcmp(name, "wf_gen_blocks")) { c->wf_gen_blocks = (int)std::min<int64_t>(4096, std::max<int64_t>(1, value)); return CRT_OK; }
     if (!std::strcmp(name, "wf_trace_form")) { c->wf_trace_form = value == 1 ? 1 : 2; return CRT_OK; }
+    if (!std::strcmp(name, "wf_cull_miss")) { c->wf_cull_miss = value != 0; return CRT_OK; }
     if (!std::strcmp(name, "wf_pipes")) { c->wf_pipes = (int)std::min<int64_t>(crt_ctx::kMaxPipes, std::max<int64_t>(1, value)); return CRT_OK; }
     if (!std::strcmp(name, "wf_pool")) { c->wf_pool = (uint32_t)std::max<int64_t>(0, value); return CRT_OK; }
     if (!std::strcmp(name, "wf_waves_per_cu")) { c->wf_waves_per_cu = (uint32_t)std::min<int64_t>(32, std::max<int64_t>(0, value)); return CRT_OK; }

@@ -144,6 +144,7 @@ struct WfCtl {                       // device control block, one per context
     uint32_t dropped;                // paths a capacity guard had to leave behind (side pool full, bounce guard of
                                      // k_wf_finish): must stay 0 -- the host turns anything else into CRT_EDEVICE
     uint32_t max_sp[kWfShards];      // counting traversal kernels only: the deepest stack (entries) a lane of the shard's waves reached
+    unsigned long long gen_culled[kWfShards];   // (pixel, sample) k_wf_gen decided without a slot (its CULL form), always counted: crt_debug_gen_culled
 };
 // The work queue is shared by the pipes of a context (two half-pools run on two streams so that
 // one half's streaming shade pass overlaps the other half's latency-bound traversal).  There are kWfRing
@@ -203,6 +204,7 @@ struct WfParams {
     uint32_t *dead;                  // [shard * list_cap + i]: slots that are dead after this iteration's shade launch (k_wf_gen's input)
     uint32_t rearm;                  // k_wf_shade: list the dead slots (a k_wf_gen launch follows: some queue may hold work)
     uint32_t gen_blocks;             // k_wf_gen: blocks per shard (block j of a shard takes chunks j, j + gen_blocks, ... of its dead list)
+    uint32_t cull_miss;              // k_wf_gen: option "wf_cull_miss" (wf_gen_culls: whether the launch takes the CULL form)
     float4 *staging[kWfRing];        // finished samples, per batch id (several batches can be in flight)
     uint32_t batch_id;           // id of the newest batch (k_wf_init: the batch being set up; k_wf_resolve / k_wf_finish: the batch to resolve / finish)
     WfStatus *status_out;            // k_wf_shade: where its first wave writes the PREVIOUS iteration's status record (pinned host memory), or null

@@ -765,26 +765,15 @@ __device__ __forceinline__ uint32_t wf_as_tile(const AsTiles &A, uint32_t w)
     return A.active[(w % (A.n_active * 64u)) >> 6];
 }
 
-template <bool COUNT, bool ADAPT>
-__global__ __launch_bounds__(64) void k_wf_gen(const WfParams P, uint32_t it, const AsTiles A)
+// The work for `want` chunks of 64 slots in as few round trips as possible (the kernel sits between the shade and the
+// traversal launch of its pipe and is bound by dependent round trips, not by arithmetic): up to two segments of
+// consecutive work items -- the wave's own shard of the listed queues, oldest first, or one other shard when all of its
+// own are dry.  (Ranges, totals and steps are multiples of 64.)  Returns the chunks found.
+struct GenWork { uint32_t q[2], w[2], n[2]; };              // per segment: queue (batch id), first work id (fits 32 bits: wf_batch_cap), chunks
+__device__ __forceinline__ uint32_t gen_reserve(const WfParams &P, uint32_t my_shard, uint32_t lane, uint32_t want, GenWork &G)
 {
-    const DevScene &S = P.sc;
-    const uint32_t ring = it & 3u, lbuf = it & 1u;
-    WfCtl *ctl = P.ctl;
-    const uint32_t lane = lane_id();
-    const uint32_t my_shard = blockIdx.x % kWfShards, j = blockIdx.x / kWfShards;
-    WfShard &sh = ctl->shard[ring][my_shard];
-    const uint32_t n_chunks = min(sh.n_dead, P.list_cap) / 64u;          // (final: the shade launch is through)
-    if (j >= n_chunks) return;
-    const uint32_t mine = (n_chunks - j + P.gen_blocks - 1u) / P.gen_blocks;     // this wave's chunks: j, j + gen_blocks, ...
-    const size_t region = (size_t)my_shard * P.list_cap;
-    const size_t cls_stride = (size_t)P.list_cap * kWfShards;
-    // ---- the work for ALL of this wave's chunks in as few round trips as possible (the kernel sits between the shade
-    //      and the traversal launch of its pipe and is bound by dependent round trips, not by arithmetic): up to two
-    //      segments of consecutive work items -- the wave's own shard of the listed queues, oldest first, or one other
-    //      shard when all of its own are dry.  (Ranges, totals and steps are multiples of 64.)  What finds no work stays dead.
-    uint32_t seg_q[2] = {0, 0}, seg_n[2] = {0, 0}, nseg = 0, want = mine;
-    uint32_t seg_w[2] = {0, 0};                                          // (work ids fit 32 bits: wf_batch_cap)
+    G.q[0] = G.q[1] = 0; G.w[0] = G.w[1] = 0; G.n[0] = G.n[1] = 0;
+    uint32_t nseg = 0;
     for (uint32_t si = 0; si < P.seg_n && want > 0u && nseg < 2u; si++) {
         const uint32_t sg = P.seg_order[si];
         WfWorkQ *wq = P.wq + sg;
@@ -798,7 +787,7 @@ __global__ __launch_bounds__(64) void k_wf_gen(const WfParams P, uint32_t it, co
         base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
         if (base >= size) continue;
         const uint32_t got = min(want, (size - base) / 64u);
-        seg_q[nseg] = sg; seg_w[nseg] = (uint32_t)lo + base; seg_n[nseg] = got; nseg++;
+        G.q[nseg] = sg; G.w[nseg] = (uint32_t)lo + base; G.n[nseg] = got; nseg++;
         want -= got;
     }
     for (uint32_t si = 0; si < P.seg_n && nseg == 0u; si++) {            // every shard of every listed queue, one try each
@@ -823,20 +812,183 @@ __global__ __launch_bounds__(64) void k_wf_gen(const WfParams P, uint32_t it, co
         const uint32_t size_s = (uint32_t)__shfl((int)size_l, (int)s_pick, 64);
         if (base >= size_s) continue;
         const uint32_t got = min(want, (size_s - base) / 64u);
-        seg_q[0] = sg; seg_w[0] = s_pick * wps + base; seg_n[0] = got; nseg = 1;
+        G.q[0] = sg; G.w[0] = s_pick * wps + base; G.n[0] = got; nseg = 1;
         want -= got;
     }
-    const uint32_t total = seg_n[0] + seg_n[1];
+    return G.n[0] + G.n[1];
+}
+
+// The root step of the traversal kernels on the quantised 4-wide tree (k_wf_trace2 and k_wf_trace<, 1>: the same set-up
+// and box test, RESTATED here operation for operation -- shared through a function, the traversal kernel's instruction
+// stream would be at the compiler's mercy) for a camera ray (t_min 0.001, t_max infinite): true when none of the root's
+// four child boxes is entered, which is exactly the case in which the traversal kernel stores (infinity, no hit) for the
+// ray after this one node step.  Q0..Q2: the root node's plane words, wave-uniform.
+typedef const __attribute__((address_space(4))) v4u *cptr4u;
+__device__ __forceinline__ bool root_step_misses(const v4u Q0, const v4u Q1, const v4u Q2, f3 qscale, f3 qbase, f3 ro, f3 rd)
+{
+    const float tiny = 1.0e-20f, t_min = 0.001f, t_max = CRT_INFINITY;
+    f3 i3;
+    i3.x = 1.0f / (abs_(rd.x) > tiny ? rd.x : __builtin_copysignf(tiny, rd.x));
+    i3.y = 1.0f / (abs_(rd.y) > tiny ? rd.y : __builtin_copysignf(tiny, rd.y));
+    i3.z = 1.0f / (abs_(rd.z) > tiny ? rd.z : __builtin_copysignf(tiny, rd.z));
+    const f3 oid = f3{fma_(qbase.x, i3.x, -(ro.x * i3.x)), fma_(qbase.y, i3.y, -(ro.y * i3.y)), fma_(qbase.z, i3.z, -(ro.z * i3.z))};
+    const f3 id = f3{qscale.x * i3.x, qscale.y * i3.y, qscale.z * i3.z};
+    const bool gx = i3.x < 0.0f, gy = i3.y < 0.0f, gz = i3.z < 0.0f;     // the hi plane is the near one on that axis
+    const uint32_t nxa = gx ? Q1.z : Q0.x, nxb = gx ? Q1.w : Q0.y, fxa = gx ? Q0.x : Q1.z, fxb = gx ? Q0.y : Q1.w;
+    const uint32_t nya = gy ? Q2.x : Q0.z, nyb = gy ? Q2.y : Q0.w, fya = gy ? Q0.z : Q2.x, fyb = gy ? Q0.w : Q2.y;
+    const uint32_t nza = gz ? Q2.z : Q1.x, nzb = gz ? Q2.w : Q1.y, fza = gz ? Q1.x : Q2.z, fzb = gz ? Q1.y : Q2.w;
+    float k0, k1, k2, k3;
+#define CRT_QBOX(K, NXQ, NYQ, NZQ, FXQ, FYQ, FZQ) { \
+        const float tn_ = __builtin_fmaxf(__builtin_fmaxf(fma_((float)(NXQ), id.x, oid.x), fma_((float)(NYQ), id.y, oid.y)), \
+                                          __builtin_fmaxf(fma_((float)(NZQ), id.z, oid.z), t_min)); \
+        const float tf_ = __builtin_fminf(__builtin_fminf(fma_((float)(FXQ), id.x, oid.x), fma_((float)(FYQ), id.y, oid.y)), \
+                                          __builtin_fminf(fma_((float)(FZQ), id.z, oid.z), t_max)); \
+        K = (tn_ <= tf_ * 1.0000005f) ? tn_ : 3.0e38f; }
+    CRT_QBOX(k0, nxa & 0xFFFFu, nya & 0xFFFFu, nza & 0xFFFFu, fxa & 0xFFFFu, fya & 0xFFFFu, fza & 0xFFFFu)
+    CRT_QBOX(k1, nxa >> 16, nya >> 16, nza >> 16, fxa >> 16, fya >> 16, fza >> 16)
+    CRT_QBOX(k2, nxb & 0xFFFFu, nyb & 0xFFFFu, nzb & 0xFFFFu, fxb & 0xFFFFu, fyb & 0xFFFFu, fzb & 0xFFFFu)
+    CRT_QBOX(k3, nxb >> 16, nyb >> 16, nzb >> 16, fxb >> 16, fyb >> 16, fzb >> 16)
+#undef CRT_QBOX
+    // (the kernel sorts the keys and descends iff the smallest is < 3.0e38f)
+    return !(k0 < 3.0e38f) && !(k1 < 3.0e38f) && !(k2 < 3.0e38f) && !(k3 < 3.0e38f);
+}
+
+#ifndef CRT_WF_GEN_ROUNDS
+#define CRT_WF_GEN_ROUNDS 8          /* k_wf_gen<, , true>: work reservations per wave at most */
+#endif
+
+// CULL (quantised 4-wide tree with an inner root, option "wf_cull_miss"): a work chunk ALL of whose camera
+// rays are finite and miss the root's four child boxes is decided here -- each of its paths is the one ray, "no hit", zero
+// radiance: the staging store of the shade step that would have found that out, made now -- and takes no slot: the
+// wave's chunk of dead slots stays with it for its next work chunk, and a wave that runs out of reserved work with slot
+// chunks still empty reserves again (CRT_WF_GEN_ROUNDS times at most; what is empty then stays dead as before).  Any
+// other chunk goes the way it goes without the cull, lanes that miss included: 64 dead slots <-> 64 consecutive work
+// items.  List positions are reserved per started chunk (how many start is not known up front), so every position below
+// n[0] holds a ray; the atomic's round trip runs under the next chunk's set-up, the chunk's records wait in registers.
+// The two forms below state the chunk set-up twice (tile decode, camera_ray, the slot's misc word, the record pair, the
+// counters): they differ in when list positions are known, and the form without the cull keeps its one atomic per wave and
+// its 45 VGPRs.  A change to the slot word or the record layout is made in BOTH loops; tests/test_gen_cull_gpu.py compares
+// their images and counters.
+template <bool COUNT, bool ADAPT, bool CULL>
+__global__ __launch_bounds__(64) void k_wf_gen(const WfParams P, uint32_t it, const AsTiles A)
+{
+    static_assert(!(ADAPT && CULL), "the adaptive instantiation does not cull");
+    const DevScene &S = P.sc;
+    const uint32_t ring = it & 3u, lbuf = it & 1u;
+    WfCtl *ctl = P.ctl;
+    const uint32_t lane = lane_id();
+    const uint32_t my_shard = blockIdx.x % kWfShards, j = blockIdx.x / kWfShards;
+    WfShard &sh = ctl->shard[ring][my_shard];
+    const uint32_t n_chunks = min(sh.n_dead, P.list_cap) / 64u;          // (final: the shade launch is through)
+    if (j >= n_chunks) return;
+    const uint32_t mine = (n_chunks - j + P.gen_blocks - 1u) / P.gen_blocks;     // this wave's chunks: j, j + gen_blocks, ...
+    const size_t region = (size_t)my_shard * P.list_cap;
+    const size_t cls_stride = (size_t)P.list_cap * kWfShards;
+    if (CULL) {
+        // the root node: wave-uniform, fetched with scalar loads from the constant address space (the tree is read-only
+        // during a trace; refits and edits between traces change it on the device, so it is read here in every launch)
+        const cptr4u rq = (cptr4u)S.nodes4q + 4 * (size_t)S.root4;
+        const v4u Q0 = rq[0], Q1 = rq[1], Q2 = rq[2];
+        const f3 qscale = f3{S.qscale[0], S.qscale[1], S.qscale[2]}, qbase = f3{S.qbase[0], S.qbase[1], S.qbase[2]};
+        const f3 eye = f3{S.cam[9], S.cam[10], S.cam[11]};               // (camera_ray's eye: the same for every ray)
+        uint32_t filled = 0;                                             // slot chunks of this wave re-armed so far
+        uint32_t slot = 0, slot_of = 0xFFFFFFFFu;                        // the dead slots of chunk j + slot_of * gen_blocks
+        uint32_t started = 0, started_q = 0;                             // paths started and not yet added to alive[started_q]
+        uint32_t c_rays = 0, c_cull = 0;
+        // the started chunk whose list positions are on their way
+        bool pend = false, p_valid = false;
+        uint32_t p_base = 0, p_entry = 0, p_rank = 0;
+        f3 p_d = f3{0.0f, 0.0f, 0.0f};
+        auto list_pending = [&]() {
+            const uint32_t b0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)p_base);
+            if (p_valid) {
+                const size_t e = (size_t)(lbuf * 4u) * cls_stride + region + b0 + p_rank;
+                stnt(&P.recA[e], float4{eye.x, eye.y, eye.z, bits_f(0xFFFFFFFFu)});
+                stnt(&P.recB[e], float4{p_d.x, p_d.y, p_d.z, bits_f(p_entry)});
+            }
+        };
+        for (uint32_t round = 0; round < (uint32_t)CRT_WF_GEN_ROUNDS && filled < mine; round++) {
+            GenWork G;
+            const uint32_t total = gen_reserve(P, my_shard, lane, mine - filled, G);
+            if (total == 0u) break;                                      // no work anywhere: the slots stay dead
+            for (uint32_t k = 0; k < total; k++) {
+                const uint32_t g = k < G.n[0] ? 0u : 1u, kk = g ? k - G.n[0] : k;
+                const uint32_t sg = G.q[g];
+                const uint32_t w0 = G.w[g] + 64u * kk;
+                const uint32_t sample_off = w0 / P.npix_padded, pp0 = w0 % P.npix_padded;
+                const uint32_t tile = pp0 >> 6;
+                const uint32_t lx = (tile % P.tiles_x) * 8u + (lane & 7u), ly = (tile / P.tiles_x) * 8u + (lane >> 3);
+                const bool valid = lx < P.tw && ly < P.th;               // (an item outside a ragged tile is consumed without a path)
+                const unsigned long long mv = __ballot(valid);
+                if (slot_of != filled) { slot = ldnt(&P.dead[region + (size_t)(j + filled * P.gen_blocks) * 64u + lane]); slot_of = filled; }
+                f3 d = f3{0.0f, 0.0f, 0.0f};
+                uint32_t sample = 0, seed = 0, lambda = 0;
+                bool nan_ray = false, miss = true;
+                if (valid) {
+                    const uint32_t px = P.x0 + lx;
+                    const uint32_t py = P.y0 + (ly / P.band) * P.band * P.stride + P.phase * P.band + ly % P.band;
+                    sample = P.seg[sg].first_sample + sample_off;
+                    seed = P.tea[(size_t)ly * P.tw + lx];
+                    const CamRay c = camera_ray(S, px, py, sample, seed);
+                    d = c.d; lambda = c.lambda; nan_ray = c.nan_ray;
+                    miss = !c.nan_ray && root_step_misses(Q0, Q1, Q2, qscale, qbase, c.eye, c.d);
+                }
+                if (__ballot(!miss) == 0ull) {
+                    // every path of the chunk ends at its camera ray: what its shade step would store (same function, same bits)
+                    if (valid) {
+                        uint32_t wl[4];
+                        wavelengths_of(lambda, wl);
+                        const f3 c = spectral_to_xyz(S, f4{0.0f, 0.0f, 0.0f, 0.0f}, wl);
+                        stnt(&P.staging[sg][(size_t)sample_off * ((size_t)P.tw * P.th) + (size_t)ly * P.tw + lx], float4{c.x, c.y, c.z, 0.0f});
+                        c_cull++;
+                    }
+                    continue;
+                }
+                if (valid) {
+                    const uint32_t flags = kWfAlive | kWfFresh | (lambda << kWfLambdaShift) | (sg << kWfBatchShift) | (nan_ray ? kWfNanRay : 0u);
+                    stnt(&P.misc[slot], uint4{w0 + lane, flags, sample, seed});   // (see the other form below)
+                    c_rays++;
+                }
+                if (pend) list_pending();                                // (its positions came in under this chunk's set-up)
+                if (lane == 0) p_base = atomicAdd(&sh.n[0], (uint32_t)__popcll(mv));
+                pend = true; p_valid = valid; p_d = d; p_rank = prefix_popc(mv, lane);
+                p_entry = slot | (nan_ray ? kWfListAlsoExt : 0u);        // (a non-finite ray is the next shade step's: kWfNanRay)
+                if (P.count_alive) {
+                    if (started != 0u && started_q != sg) { if (lane == 0) atomicAdd(&sh.alive[started_q], started); started = 0; }
+                    started_q = sg; started += (uint32_t)__popcll(mv);
+                }
+                filled++;
+            }
+        }
+        if (pend) list_pending();
+        if (started != 0u && lane == 0) atomicAdd(&sh.alive[started_q], started);
+        {
+            uint32_t n = c_cull;                                         // pixel-samples decided here (crt_debug_gen_culled): always counted
+            for (int off = 32; off > 0; off >>= 1) n += (uint32_t)__shfl_xor((int)n, off, 64);
+            if (lane == 0 && n) atomicAdd(&ctl->gen_culled[my_shard], (unsigned long long)n);
+        }
+        if (COUNT) {
+            // a culled path is still one intersect() call of the reference, and its walk's only node step was taken here
+            wave_add(ctl->counters[blockIdx.x % kWfShards] + CRT_CNT_RAYS, c_rays + c_cull);
+            wave_add(ctl->counters[blockIdx.x % kWfShards] + CRT_CNT_WALKED, c_rays + c_cull);
+            wave_add(ctl->counters[blockIdx.x % kWfShards] + CRT_CNT_BOUNCES, c_cull);
+            wave_add(ctl->counters[blockIdx.x % kWfShards] + CRT_CNT_PATHS, c_cull);
+            wave_add(ctl->counters[blockIdx.x % kWfShards] + CRT_CNT_NODES, 4u * c_cull);
+        }
+        return;
+    }
+    GenWork G;
+    const uint32_t total = gen_reserve(P, my_shard, lane, mine, G);
     if (total == 0u) return;                                             // no work anywhere: the slots stay dead
     // ---- list positions of the whole wave's camera rays: one atomic.  Every item of an 8x8 tile inside the frame
     //      yields a path; an item outside a ragged tile is consumed without one (its slot stays dead).
     const bool ragged = ((P.tw | P.th) & 7u) != 0u;
-    uint32_t n_valid[2] = {seg_n[0] * 64u, seg_n[1] * 64u};
+    uint32_t n_valid[2] = {G.n[0] * 64u, G.n[1] * 64u};
     if (ragged) {
         for (uint32_t g = 0; g < 2u; g++) {
             n_valid[g] = 0;
-            for (uint32_t k = 0; k < seg_n[g]; k++) {
-                const uint32_t tile = ADAPT ? wf_as_tile(A, seg_w[g] + 64u * k) : ((seg_w[g] + 64u * k) % P.npix_padded) >> 6;
+            for (uint32_t k = 0; k < G.n[g]; k++) {
+                const uint32_t tile = ADAPT ? wf_as_tile(A, G.w[g] + 64u * k) : ((G.w[g] + 64u * k) % P.npix_padded) >> 6;
                 const uint32_t lx = (tile % P.tiles_x) * 8u + (lane & 7u), ly = (tile / P.tiles_x) * 8u + (lane >> 3);
                 n_valid[g] += (uint32_t)__popcll(__ballot(lx < P.tw && ly < P.th));
             }
@@ -846,16 +998,16 @@ __global__ __launch_bounds__(64) void k_wf_gen(const WfParams P, uint32_t it, co
     if (lane == 0) {
         b0 = atomicAdd(&sh.n[0], n_valid[0] + n_valid[1]);
         if (P.count_alive) {
-            if (n_valid[0]) atomicAdd(&sh.alive[seg_q[0]], n_valid[0]);
-            if (n_valid[1]) atomicAdd(&sh.alive[seg_q[1]], n_valid[1]);
+            if (n_valid[0]) atomicAdd(&sh.alive[G.q[0]], n_valid[0]);
+            if (n_valid[1]) atomicAdd(&sh.alive[G.q[1]], n_valid[1]);
         }
     }
     uint32_t c_rays = 0, pos = 0;                                        // pos: camera rays of this wave listed so far
     bool have_b0 = false;
     for (uint32_t k = 0; k < total; k++) {
-        const uint32_t g = k < seg_n[0] ? 0u : 1u, kk = g ? k - seg_n[0] : k;
-        const uint32_t sg = seg_q[g];
-        const uint32_t w0 = seg_w[g] + 64u * kk;
+        const uint32_t g = k < G.n[0] ? 0u : 1u, kk = g ? k - G.n[0] : k;
+        const uint32_t sg = G.q[g];
+        const uint32_t w0 = G.w[g] + 64u * kk;
         uint32_t sample_off = w0 / P.npix_padded, pp0 = w0 % P.npix_padded;
         if (ADAPT) {                                                     // the full-frame position of the active tile's chunk
             sample_off = w0 / (A.n_active * 64u);
@@ -1899,17 +2051,33 @@ hipError_t wf_launch_shade(const WfParams &P, uint32_t it, hipStream_t s)
     return hipGetLastError();
 }
 
+int wf_trace_kernel(const WfParams &P);
+
+// Does k_wf_gen decide camera rays that miss the scene (its CULL form)?  Only where the pool's traversal kernel walks the
+// quantised 4-wide tree (both forms take the root step k_wf_gen restates) from an inner root, the scene holds more than the
+// four primitives of a one-node tree (a walk that short leaves nothing to save), and option "wf_cull_miss" is on.
+bool wf_gen_culls(const WfParams &P)
+{
+    const int k = wf_trace_kernel(P);
+    return P.cull_miss != 0u && (k == 1 || k == 3) && P.sc.nprim > 4u && P.sc.root4 >= 0 && P.sc.root4 != kNoNode;
+}
+
 hipError_t wf_launch_gen(const WfParams &P, uint32_t it, hipStream_t s, const AsTiles *A)
 {
     if (P.gen_blocks == 0u) return hipErrorInvalidValue;
     const dim3 gs(kWfShards * P.gen_blocks), bs(64);
     if (A) {                                                     // adaptive batches
-        if (P.count) hipLaunchKernelGGL((k_wf_gen<true, true>), gs, bs, 0, s, P, it, *A);
-        else hipLaunchKernelGGL((k_wf_gen<false, true>), gs, bs, 0, s, P, it, *A);
+        if (P.count) hipLaunchKernelGGL((k_wf_gen<true, true, false>), gs, bs, 0, s, P, it, *A);
+        else hipLaunchKernelGGL((k_wf_gen<false, true, false>), gs, bs, 0, s, P, it, *A);
         return hipGetLastError();
     }
-    if (P.count) hipLaunchKernelGGL((k_wf_gen<true, false>), gs, bs, 0, s, P, it, AsTiles{});
-    else hipLaunchKernelGGL((k_wf_gen<false, false>), gs, bs, 0, s, P, it, AsTiles{});
+    if (wf_gen_culls(P)) {
+        if (P.count) hipLaunchKernelGGL((k_wf_gen<true, false, true>), gs, bs, 0, s, P, it, AsTiles{});
+        else hipLaunchKernelGGL((k_wf_gen<false, false, true>), gs, bs, 0, s, P, it, AsTiles{});
+        return hipGetLastError();
+    }
+    if (P.count) hipLaunchKernelGGL((k_wf_gen<true, false, false>), gs, bs, 0, s, P, it, AsTiles{});
+    else hipLaunchKernelGGL((k_wf_gen<false, false, false>), gs, bs, 0, s, P, it, AsTiles{});
     return hipGetLastError();
 }
 

@@ -535,6 +535,13 @@ class Renderer:
         self._chk(self._lib.crt_debug_probes(self._h, out.ctypes.data))
         return [int(v) for v in out]
 
+    def gen_culled(self) -> int:
+        """(pixel, sample) pairs the generate kernel decided itself since reset_counters() (crt_debug_gen_culled):
+        camera rays that miss the tree's root boxes, by whole 8x8 tiles of one sample.  A sync point."""
+        n = C.c_uint64()
+        self._chk(self._lib.crt_debug_gen_culled(self._h, C.byref(n)))
+        return int(n.value)
+
     def debug_math(self, fn: int, a, b=None) -> np.ndarray:
         a = np.ascontiguousarray(a, np.float32)
         b = np.ascontiguousarray(b if b is not None else np.zeros_like(a), np.float32)

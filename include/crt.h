@@ -513,7 +513,9 @@ int crt_last_kernel_ms(crt_ctx *ctx, float *ms, uint32_t *launches);
  * a time), "wf_ahead" (iterations in flight per pipe before the call waits), "wf_feed_pct", "wf_finish_at",
  * "wf_flush_at", "wf_side_ppw", "wf_flush_ppw", "wf_tail_walk": pipeline tuning;
  * "quantize", "wf_width" (4 | 8: node width of the wavefront traversal; at crt_build_accel);
- * "wf_trace_form" (2: ray ring + primitive tasks, default; 1: the first traversal kernel); "frame_ring" = F (keep the
+ * "wf_trace_form" (2: ray ring + primitive tasks, default; 1: the first traversal kernel); "wf_cull_miss" (1, default:
+ * work chunks whose camera rays all miss the tree's root boxes are finished where they are generated and take no path
+ * slot; 0: every camera ray goes through the pool; same image and counters either way); "frame_ring" = F (keep the
  * rgba8 frame of each of the last F samples for crt_read_sample_rgba8; 0 = off);
  * "temporal_motion" (0 | 1, anything else is CRT_EINVAL: 1 keeps the history of crt_denoise_temporal across
  * crt_update_primitives, see "Temporal reuse"; costs 80 bytes per primitive on the device once an edit has happened);
@@ -584,6 +586,10 @@ int crt_debug_read_accel(crt_ctx *ctx, int what, void *out, size_t capacity, siz
 /* Traversal-efficiency probes of the counting kernel variant (wave-level): inner iterations,
  * lanes active in them, leaf passes, lanes active in them, leaf loop trips, -, refills, lanes refilled. */
 int crt_debug_probes(crt_ctx *ctx, uint64_t out[8]);
+/* Test hook: (pixel, sample) pairs that k_wf_gen decided itself since the last crt_reset_counters -- camera rays that miss
+ * the tree's root boxes, by whole 8x8 tiles of one sample (option "wf_cull_miss").  Counted with and without
+ * crt_enable_counters.  A sync point; work in flight at a crt_reset_counters may count on either side of it. */
+int crt_debug_gen_culled(crt_ctx *ctx, uint64_t *out);
 
 #ifdef __cplusplus
 }
