@@ -13,6 +13,7 @@
 
 #include "crt_adaptive.h"
 #include "crt_device.h"
+#include "crt_launch.h"
 #include "crt_math.h"
 
 namespace crt {

@@ -9,6 +9,7 @@
 #include <type_traits>
 
 #include "crt_adaptive.h"
+#include "crt_launch.h"
 #include "crt_shade.h"
 
 namespace crt {
@@ -479,7 +480,7 @@ __global__ __launch_bounds__(256) void k_dn_motion(const DnReprojParams P, float
     out[p] = uv;
 }
 
-// ---------------------------------------------------------------- launchers (called from crt_api.cpp; DnFilter: crt_device.h)
+// ---------------------------------------------------------------- launchers (declared in crt_launch.h; DnFilter: crt_device.h)
 hipError_t dn_launch_gbuffer(const DevScene &S, uint32_t x0, uint32_t y0, uint32_t tw, uint32_t th, float4 *gbuf, uint32_t *key,
                              int brute, hipStream_t stream)
 {

@@ -121,7 +121,7 @@ constexpr uint32_t kWfRing = 32;                                // batch ids cyc
 constexpr uint32_t kWfSideCap = 65536;
 // Traversal stacks: kWfStackLds (k_wf_trace) / kWfStackLds2 (k_wf_trace2) entries per lane in LDS, the rest in a global
 // overflow area of at least kWfOverflowLevels levels.  A nearest-first walk holds at most (node width - 1) entries per
-// inner level of the walked tree; crt_api.cpp sizes the area from that depth (wf_overflow_levels) and, where that would
+// inner level of the walked tree; crt_scene.cpp sizes the area from that depth (wf_overflow_levels) and, where that would
 // take more than kWfOverflowMaxLevels, builds the shallower tree instead.  The pushes themselves are unchecked.
 constexpr int kWfStackLds = 32, kWfStackLds2 = 16;
 constexpr uint32_t kWfOverflowLevels = 96, kWfOverflowMaxLevels = 384;
@@ -275,7 +275,7 @@ struct DnSvgfParams : DnReprojParams {
     float min_frames;               // v is trusted from Mw / n >= this on
 };
 
-// What the launchers of the four preview filters share (crt_denoise.hip).
+// What the launchers of the four preview filters share (crt_denoise.hip; declared in crt_launch.h).
 struct DnFilter {
     const float4 *gbuf;             // the guides: G-buffer and keys of the tile
     const uint32_t *key;
@@ -285,15 +285,5 @@ struct DnFilter {
     float sigma_normal, sigma_plane;
     hipStream_t stream;
 };
-
-hipError_t dn_launch_gbuffer(const DevScene &S, uint32_t x0, uint32_t y0, uint32_t tw, uint32_t th, float4 *gbuf, uint32_t *key,
-                             int brute, hipStream_t stream);
-// (each leaves the buffer that holds the result in *out)
-hipError_t dn_launch_filter(const DnFilter &F, const float4 *accum, float n, float sigma_color, float4 **out);
-hipError_t dn_launch_filter_adaptive(const DnFilter &F, const float4 *accum, const float *q, const uint32_t *counts, uint2 *kv,
-                                     float *var, float sigma_variance, float4 **out);
-hipError_t dn_launch_temporal(const DnFilter &F, DnReprojParams P, float sigma_color, float4 **out);
-hipError_t dn_launch_svgf(const DnFilter &F, DnSvgfParams P, uint2 *kv, float *var, float sigma_variance, float4 **out);
-hipError_t dn_launch_motion(const DnReprojParams &P, float2 *out, hipStream_t stream);
 
 }  // namespace crt

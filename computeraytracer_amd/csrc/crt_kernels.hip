@@ -17,6 +17,7 @@
 // Arithmetic follows crt_math.h to the operation so results are bit-identical
 // to the CPU restatement used by the tests.
 #include "crt_shade.h"
+#include "crt_launch.h"
 
 namespace crt {
 
@@ -305,7 +306,7 @@ __global__ void k_debug_math(int fn, const float *a, const float *b, float *out,
     out[i] = r;
 }
 
-// ---------------------------------------------------------------- launchers (called from crt_api.cpp)
+// ---------------------------------------------------------------- launchers (declared in crt_launch.h)
 hipError_t launch_trace(const TraceParams &P, bool count, bool brute, hipStream_t stream)
 {
     dim3 grid(P.tiles_x * P.tiles_y), block(64);

@@ -1,0 +1,68 @@
+// crt_launch.h -- every host entry into the device code, declared once: the launchers of the six .hip files, the GPU tree
+// builders and the level lists of the refit.  The .hip file that defines one and every host unit that calls one include
+// this header.  (Parameter structs: crt_device.h.)
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <vector>
+
+#include "../../include/crt.h"
+#include "crt_bvh.h"
+#include "crt_device.h"
+
+namespace crt {
+
+// crt_kernels.hip
+hipError_t launch_trace(const TraceParams &P, bool count, bool brute, hipStream_t stream);
+hipError_t launch_trace_adaptive(const TraceParams &P, const AsTiles &A, bool count, bool brute, hipStream_t stream);
+hipError_t launch_debug_intersect(const DevScene &S, const float *rays, size_t n, float *out, int brute, hipStream_t stream);
+hipError_t launch_debug_math(int fn, const float *a, const float *b, float *out, size_t n, hipStream_t stream);
+hipError_t launch_assemble(const void *full, void *frame, uint32_t elem_bytes, uint32_t W, uint32_t H, uint32_t world, uint32_t rows_max,
+                           uint32_t band, hipStream_t stream);
+
+// crt_wavefront.hip
+hipError_t wf_launch_init(const WfParams &P, hipStream_t s);
+hipError_t wf_launch_tea(const WfParams &P, uint32_t *out, hipStream_t s);
+hipError_t wf_launch_shade(const WfParams &P, uint32_t it, hipStream_t s);
+hipError_t wf_launch_gen(const WfParams &P, uint32_t it, hipStream_t s, const AsTiles *A);
+hipError_t wf_launch_trace(const WfParams &P, uint32_t it, uint32_t trace_blocks, hipStream_t s);
+int wf_trace_kernel(const WfParams &P);
+hipError_t wf_launch_finish(const WfParams &P, WfFinishSegs G, uint32_t max_paths, hipStream_t s);
+hipError_t wf_launch_resolve(const WfParams &P, uint32_t last_sample, hipStream_t s);
+hipError_t wf_launch_resolve_adaptive(const WfParams &P, const AsTiles &A, uint32_t call_end, hipStream_t s);
+
+// crt_adaptive.hip
+hipError_t as_launch_select(const AsParams &A, bool compact, hipStream_t s);
+hipError_t as_launch_commit(uint32_t *counts, const uint32_t *active, uint32_t n_active, uint32_t samples, hipStream_t s);
+
+// crt_lbvh.hip
+hipError_t build_lbvh(const float *lo, const float *hi, uint32_t n, Bvh &out, hipStream_t stream);
+hipError_t build_lbvh_device(const unsigned char *d_raw, uint32_t n, float hit_pad, float4 *d_prim, float4 *d_primD,
+                             uint32_t *d_slot_of_index, float *d_nodes2, uint4 *d_nodes4q, LbvhDeviceResult &res, hipStream_t stream);
+
+// crt_refit.hip
+hipError_t refit_launch_pad(const unsigned char *raw, uint32_t n, uint32_t *out, hipStream_t s);
+hipError_t refit_launch_prims(const unsigned char *raw, uint32_t first, uint32_t count, const uint32_t *slot_of_index, float4 *prim,
+                              float4 *primD, hipStream_t s);
+hipError_t refit_launch_transform(unsigned char *raw, const uint32_t *start, const crt_prim_transform *ops, uint32_t n_ops, uint32_t total,
+                                  const uint32_t *slot_of_index, float4 *prim, float4 *primD, hipStream_t s);
+hipError_t refit_levels(const void *nodes, uint32_t width, bool quantised, int root, uint32_t cap, int *list, uint32_t *counter,
+                        uint32_t *nch, std::vector<uint32_t> &off, hipStream_t s);
+hipError_t refit_launch_bvh2(const float4 *prim, float pad, const int *list, const std::vector<uint32_t> &off, float *nodes, hipStream_t s);
+hipError_t refit_launch_wide(const float4 *prim, float pad, const int *list, const std::vector<uint32_t> &off, const void *refs,
+                             bool quantised, const uint32_t *nch, float *fb, hipStream_t s);
+hipError_t refit_launch_quant4(const float *fb, const uint32_t *nch, uint32_t n4, uint4 *nodes4q, const double base[3], const double scale[3],
+                               hipStream_t s);
+
+// crt_denoise.hip
+hipError_t dn_launch_gbuffer(const DevScene &S, uint32_t x0, uint32_t y0, uint32_t tw, uint32_t th, float4 *gbuf, uint32_t *key,
+                             int brute, hipStream_t stream);
+// (each leaves the buffer that holds the result in *out)
+hipError_t dn_launch_filter(const DnFilter &F, const float4 *accum, float n, float sigma_color, float4 **out);
+hipError_t dn_launch_filter_adaptive(const DnFilter &F, const float4 *accum, const float *q, const uint32_t *counts, uint2 *kv,
+                                     float *var, float sigma_variance, float4 **out);
+hipError_t dn_launch_temporal(const DnFilter &F, DnReprojParams P, float sigma_color, float4 **out);
+hipError_t dn_launch_svgf(const DnFilter &F, DnSvgfParams P, uint2 *kv, float *var, float sigma_variance, float4 **out);
+hipError_t dn_launch_motion(const DnReprojParams &P, float2 *out, hipStream_t stream);
+
+}  // namespace crt

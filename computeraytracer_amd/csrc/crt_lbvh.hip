@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "crt_bvh.h"
+#include "crt_launch.h"
 #include "crt_math.h"
 #include "crt_prim.h"
 
@@ -226,7 +227,7 @@ hipError_t build_lbvh(const float *lo, const float *hi, uint32_t n, Bvh &out, hi
 // from their 80-byte records, Morton keys, radix sort, hierarchy, bottom-up bounds as above; then the collapse to the
 // 4-wide tree, its 16-bit quantisation and the leaf-ordered primitive records, without a copy of the tree ever
 // visiting the host.  Same structures and rules as the host path (crt_bvh.cpp collapse_bvh4 / quantize_bvh4,
-// crt_api.cpp upload_geometry), so the kernels and the image are the same.
+// crt_scene.cpp upload_geometry), so the kernels and the image are the same.
 namespace {
 
 // order-preserving map float -> uint for atomicMin / atomicMax

@@ -23,6 +23,7 @@
 
 #include "../../include/crt.h"
 #include "crt_bvh.h"
+#include "crt_launch.h"
 #include "crt_math.h"
 #include "crt_prim.h"
 

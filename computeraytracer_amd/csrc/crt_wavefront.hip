@@ -25,6 +25,7 @@
 // consumes no random numbers, so a diffuse bounce can draw its light, hemisphere
 // and roulette numbers in one go.
 #include "crt_shade.h"
+#include "crt_launch.h"
 #include <algorithm>
 
 namespace crt {
@@ -63,7 +64,7 @@ namespace crt {
 #define CRT_WF_MIN_WAVES 1
 #endif
 constexpr int kWfStack = CRT_WF_STACK;      // LDS stack entries per lane; deeper stacks go on in P.stack_overflow (crt_device.h)
-static_assert(kWfStack == kWfStackLds, "crt_api.cpp sizes the overflow area from kWfStackLds");
+static_assert(kWfStack == kWfStackLds, "crt_scene.cpp sizes the overflow area from kWfStackLds");
 constexpr int kNoNode = 0x7FFFFFFF;          // "no node left to walk" (inner ids are smaller, leaf references negative)
 constexpr int kTraceChunk = 128;            // list entries a wave reserves per atomic
 constexpr int kRefillAt = CRT_WF_REFILL;    // refill when at least this many lanes are idle
@@ -2050,8 +2051,6 @@ hipError_t wf_launch_shade(const WfParams &P, uint32_t it, hipStream_t s)
     else hipLaunchKernelGGL((k_wf_shade<false>), gs, bs, 0, s, P, it);
     return hipGetLastError();
 }
-
-int wf_trace_kernel(const WfParams &P);
 
 // Does k_wf_gen decide camera rays that miss the scene (its CULL form)?  Only where the pool's traversal kernel walks the
 // quantised 4-wide tree (both forms take the root step k_wf_gen restates) from an inner root, the scene holds more than the

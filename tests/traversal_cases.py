@@ -107,7 +107,7 @@ def box_patches(lo, hi):
 
 def corners(prims):
     """Corner points (n, 4, 3) float32 (a triangle repeats its first corner, a sphere gives its box) -- the corners of
-    crt_api.cpp prim_corners."""
+    crt_scene.cpp prim_corners."""
     d1, d2, d3 = prims["data1"], prims["data2"], prims["data3"]
     cat = prims["category"]
     c = np.stack([d1, d1 + d2, d1 + d3, np.where((cat == 0)[:, None], (d1 + d2) + d3, d1)], 1).astype(np.float32)
@@ -530,7 +530,7 @@ class Rays:
 
     def box_plane(self, n):
         """Origins exactly in a plane of a primitive's box as the builders make it (corner box -/+ 2 hit_pad, in float32:
-        crt_api.cpp upload_geometry) -- a quarter of them in a plane of the scene box, the extreme primitive's -- running
+        crt_scene.cpp upload_geometry) -- a quarter of them in a plane of the scene box, the extreme primitive's -- running
         along that plane: the direction component on the plane's axis comes from TINY (both signs, both sides of the
         1e-20 clamp), the other two aim past the primitive at the rest of the scene."""
         p = self.prims
