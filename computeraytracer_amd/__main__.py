@@ -14,7 +14,7 @@ def main():
     ap.add_argument("--width", type=int)
     ap.add_argument("--height", type=int)
     ap.add_argument("--spp", type=int, default=64)
-    ap.add_argument("--accel", default="bvh2", choices=["bvh2", "lbvh", "none"])
+    ap.add_argument("--accel", default="bvh2", choices=["bvh2", "lbvh", "ploc", "none"])
     ap.add_argument("--out", default="render.png")
     ap.add_argument("--checkpoint", default=None, help="resume from / save to this .npz")
     ap.add_argument("--denoise", type=int, default=None, metavar="K",

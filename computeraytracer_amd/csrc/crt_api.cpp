@@ -307,9 +307,10 @@ int crt_build_accel(crt_ctx *c, int mode)
 {
     if (!c) return CRT_EINVAL;
     if (!c->have_scene) return fail(c, CRT_ESTATE, "crt_build_accel: upload a scene first");
-    if (mode != CRT_ACCEL_NONE && mode != CRT_ACCEL_BVH2 && mode != CRT_ACCEL_LBVH) return fail(c, CRT_EINVAL, "crt_build_accel: unknown mode %d", mode);
-    c->want_lbvh = mode == CRT_ACCEL_LBVH;
-    if (mode == CRT_ACCEL_LBVH) mode = CRT_ACCEL_BVH2;          // same structure, same kernels
+    if (mode != CRT_ACCEL_NONE && mode != CRT_ACCEL_BVH2 && mode != CRT_ACCEL_LBVH && mode != CRT_ACCEL_PLOC)
+        return fail(c, CRT_EINVAL, "crt_build_accel: unknown mode %d", mode);
+    c->want_builder = mode == CRT_ACCEL_LBVH ? 1 : mode == CRT_ACCEL_PLOC ? 2 : 0;
+    if (c->want_builder) mode = CRT_ACCEL_BVH2;                 // same structure, same kernels
     CRT_TRY(quiesce(c, true));
     // The build releases the scene's device arrays before it allocates the new ones: until it has succeeded there is
     // no structure to trace against (upload_geometry / build_accel_on_device set accel_mode on success only).
@@ -743,7 +744,7 @@ int crt_accel_stats(crt_ctx *c, uint64_t out[8])
     out[4] = wide ? (c->bvh4q.ok ? 16 : 32) : 32;      // bytes of node data per child box tested
     out[5] = wide8 ? 8 : wide ? 4 : 2;                  // node width used by crt_trace
     out[6] = wide8 ? c->bvh8q.n_inner : wide ? c->bvh4.n_inner : c->bvh.n_inner;   // inner nodes of that tree
-    out[7] = (uint64_t)c->accel_builder;               // 0: host binned SAH, 1: GPU LBVH
+    out[7] = (uint64_t)c->accel_builder;               // 0: host binned SAH, 1: GPU LBVH, 2: GPU PLOC
     out[0] = c->bvh.n_inner; out[1] = c->bvh.n_leaves; out[2] = c->bvh.max_depth;
     out[3] = (uint64_t)c->bvh.n_inner * 64u + (uint64_t)c->bvh4.n_inner * 128u + (uint64_t)c->prims.size() * 48u;
     return CRT_OK;
@@ -754,6 +755,21 @@ int crt_set_option(crt_ctx *c, const char *name, int64_t value)
     if (!c || !name) return CRT_EINVAL;
     CRT_TRY(wf_flush(c));
     if (!std::strcmp(name, "debug_fail_alloc")) { g_fail_alloc_in = value; return CRT_OK; }
+    if (!std::strcmp(name, "ploc_radius")) {                 // takes effect at crt_build_accel
+        if (value < 1 || value > 32) return fail(c, CRT_EINVAL, "crt_set_option: ploc_radius is 1..32");
+        c->ploc.radius = (uint32_t)value;
+        return CRT_OK;
+    }
+    if (!std::strcmp(name, "debug_ploc_max_depth")) {        // test hooks: a PLOC build past these is abandoned for the LBVH
+        if (value < 1 || value > 62) return fail(c, CRT_EINVAL, "crt_set_option: debug_ploc_max_depth is 1..62");
+        c->ploc.max_depth = (uint32_t)value;
+        return CRT_OK;
+    }
+    if (!std::strcmp(name, "debug_ploc_max_rounds")) {
+        if (value < 1) return fail(c, CRT_EINVAL, "crt_set_option: debug_ploc_max_rounds is >= 1");
+        c->ploc.max_rounds = (uint32_t)std::min<int64_t>(value, 1 << 30);
+        return CRT_OK;
+    }
     if (!std::strcmp(name, "wf_defer")) { c->wf_defer = value != 0; return CRT_OK; }
     if (!std::strcmp(name, "spp_per_launch")) { c->spp_per_launch = (uint32_t)std::max<int64_t>(0, value); return CRT_OK; }
     if (!std::strcmp(name, "pipeline")) { c->pipeline = value ? 1 : 0; return CRT_OK; }

@@ -77,4 +77,15 @@ struct LbvhDeviceResult {
     bool quantised = false;        // false: the scene cannot be quantised (quantize_bvh4's rules); use the host path
 };
 
+// The clustered GPU build (crt_ploc.hip; DESIGN.md 3 "GPU build, clustered").
+struct PlocOptions {
+    uint32_t radius = 8;           // clusters searched to either side for the nearest neighbour (1..32)
+    uint32_t max_depth = 62;       // a deeper hierarchy does not fit the 64-entry single-ray stacks: abandoned
+    uint32_t max_rounds = 256;     // a build that has not finished within this many rounds is abandoned
+};
+struct PlocInfo {
+    uint32_t rounds = 0, depth = 0;
+    int abandoned = 0;             // 0: built; 1: deeper than max_depth; 2: not finished within max_rounds (the caller builds an LBVH)
+};
+
 }  // namespace crt

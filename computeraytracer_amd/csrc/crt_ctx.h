@@ -130,8 +130,9 @@ struct crt_ctx {
     uint32_t W = 0, H = 0;
     bool have_scene = false;
     int accel_mode = -1;            // -1: not built
-    bool want_lbvh = false;         // crt_build_accel(CRT_ACCEL_LBVH): build the BVH2 on the GPU
-    int accel_builder = 0;          // 0: host binned SAH, 1: GPU LBVH
+    int want_builder = 0;           // the builder crt_build_accel asked for: 0 host binned SAH, 1 GPU LBVH (CRT_ACCEL_LBVH), 2 GPU PLOC (CRT_ACCEL_PLOC)
+    int accel_builder = 0;          // the builder that made the current tree (same numbers)
+    crt::PlocOptions ploc;          // options "ploc_radius", "debug_ploc_max_depth", "debug_ploc_max_rounds"
     crt::Bvh bvh;
     crt::Bvh4 bvh4;
     crt::Bvh4Q bvh4q;

@@ -1,4 +1,4 @@
-// crt_launch.h -- every host entry into the device code, declared once: the launchers of the six .hip files, the GPU tree
+// crt_launch.h -- every host entry into the device code, declared once: the launchers of the seven .hip files, the GPU tree
 // builders and the level lists of the refit.  The .hip file that defines one and every host unit that calls one include
 // this header.  (Parameter structs: crt_device.h.)
 #pragma once
@@ -39,6 +39,21 @@ hipError_t as_launch_commit(uint32_t *counts, const uint32_t *active, uint32_t n
 hipError_t build_lbvh(const float *lo, const float *hi, uint32_t n, Bvh &out, hipStream_t stream);
 hipError_t build_lbvh_device(const unsigned char *d_raw, uint32_t n, float hit_pad, float4 *d_prim, float4 *d_primD,
                              uint32_t *d_slot_of_index, float *d_nodes2, uint4 *d_nodes4q, LbvhDeviceResult &res, hipStream_t stream);
+// (its stages, which the clustered build of crt_ploc.hip shares: sorted Morton keys, the record gather, the collapse)
+template <typename T> struct DevBuf;        // crt_ctx.h: the sort's temporary is the caller's, freed with its scope
+hipError_t lbvh_sorted_keys_host(const float *lo, const float *hi, uint32_t n, float *d_lo, float *d_hi, unsigned long long *d_keys,
+                                 unsigned long long *d_sorted, DevBuf<char> &sort_tmp, hipStream_t stream);
+hipError_t lbvh_sorted_keys_device(const unsigned char *d_raw, uint32_t n, float hit_pad, float *d_lo, float *d_hi, uint32_t *d_cbox,
+                                   unsigned long long *d_keys, unsigned long long *d_sorted, DevBuf<char> &sort_tmp, hipStream_t stream);
+hipError_t lbvh_launch_gather(const unsigned char *d_raw, const unsigned long long *d_keys, uint32_t n, float4 *d_prim, float4 *d_primD,
+                              uint32_t *d_slot_of_index, hipStream_t stream);
+hipError_t lbvh_collapse_device(const float *d_nodes2, uint32_t n, uint4 *d_nodes4q, LbvhDeviceResult &res, hipStream_t stream);
+
+// crt_ploc.hip
+hipError_t build_ploc(const float *lo, const float *hi, uint32_t n, const PlocOptions &opt, Bvh &out, PlocInfo &info, hipStream_t stream);
+hipError_t build_ploc_device(const unsigned char *d_raw, uint32_t n, float hit_pad, const PlocOptions &opt, float4 *d_prim, float4 *d_primD,
+                             uint32_t *d_slot_of_index, float *d_nodes2, uint4 *d_nodes4q, LbvhDeviceResult &res, PlocInfo &info,
+                             hipStream_t stream);
 
 // crt_refit.hip
 hipError_t refit_launch_pad(const unsigned char *raw, uint32_t n, uint32_t *out, hipStream_t s);

@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "crt_bvh.h"
+#include "crt_ctx.h"
 #include "crt_launch.h"
 #include "crt_math.h"
 #include "crt_prim.h"
@@ -149,12 +150,14 @@ struct Tmp {
 
 }  // namespace
 
-// lo/hi: n x 3 floats on the host (padded conservatively by the caller, finite: unbounded
-// primitives come in as +-3e38).  Needs n >= 2.
-hipError_t build_lbvh(const float *lo, const float *hi, uint32_t n, Bvh &out, hipStream_t stream)
+#define LB(call) do { e = (call); if (e != hipSuccess) return e; } while (0)
+
+// The front both GPU builders share (crt_ploc.hip clusters the same sorted keys): Morton keys of boxes that came from the
+// host, sorted.  d_lo / d_hi / d_keys / d_sorted: n x 3 floats and n keys each, the caller's; sort_tmp is allocated here and
+// lives as long as the caller keeps it.
+hipError_t lbvh_sorted_keys_host(const float *lo, const float *hi, uint32_t n, float *d_lo, float *d_hi, unsigned long long *d_keys,
+                                 unsigned long long *d_sorted, DevBuf<char> &sort_tmp, hipStream_t stream)
 {
-    out = Bvh();
-    if (n < 2) return hipErrorInvalidValue;
     // scene box of the centroids (host: one pass over data that is in cache from the bounds computation)
     float clo[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, chi[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
     for (size_t i = 0; i < n; i++)
@@ -167,27 +170,37 @@ hipError_t build_lbvh(const float *lo, const float *hi, uint32_t n, Bvh &out, hi
         if (!(clo[a] <= chi[a])) { clo[a] = 0.0f; chi[a] = 1.0f; }
         sc[a] = 1024.0f / std::max(chi[a] - clo[a], 1.0e-20f);
     }
+    hipError_t e;
+    LB(hipMemcpyAsync(d_lo, lo, (size_t)n * 12, hipMemcpyHostToDevice, stream));
+    LB(hipMemcpyAsync(d_hi, hi, (size_t)n * 12, hipMemcpyHostToDevice, stream));
+    hipLaunchKernelGGL(k_lbvh_keys, dim3((n + 255u) / 256u), dim3(256), 0, stream, d_lo, d_hi, n, clo[0], clo[1], clo[2], sc[0], sc[1], sc[2], d_keys);
+    LB(hipGetLastError());
+    size_t tmp_bytes = 0;
+    LB(hipcub::DeviceRadixSort::SortKeys(nullptr, tmp_bytes, d_keys, d_sorted, (int)n, 0, 62, stream));
+    LB(sort_tmp.alloc(std::max<size_t>(tmp_bytes, 1)));
+    LB(hipcub::DeviceRadixSort::SortKeys(sort_tmp.p, tmp_bytes, d_keys, d_sorted, (int)n, 0, 62, stream));
+    return hipSuccess;
+}
+
+// lo/hi: n x 3 floats on the host (padded conservatively by the caller, finite: unbounded
+// primitives come in as +-3e38).  Needs n >= 2.
+hipError_t build_lbvh(const float *lo, const float *hi, uint32_t n, Bvh &out, hipStream_t stream)
+{
+    out = Bvh();
+    if (n < 2) return hipErrorInvalidValue;
     Tmp<float> d_lo, d_hi, d_nb, d_nodes;
     Tmp<unsigned long long> d_keys, d_sorted;
     Tmp<int> d_child, d_pi, d_pl;
     Tmp<unsigned int> d_flag;
-    Tmp<char> d_tmp;
+    DevBuf<char> d_tmp;
     hipError_t e;
-#define LB(call) do { e = (call); if (e != hipSuccess) return e; } while (0)
     LB(d_lo.alloc((size_t)n * 3)); LB(d_hi.alloc((size_t)n * 3));
     LB(d_keys.alloc(n)); LB(d_sorted.alloc(n));
     LB(d_child.alloc((size_t)2 * (n - 1))); LB(d_pi.alloc(n - 1)); LB(d_pl.alloc(n));
     LB(d_flag.alloc(n - 1)); LB(d_nb.alloc((size_t)6 * (n - 1))); LB(d_nodes.alloc((size_t)(n - 1) * kNodeFloats));
-    LB(hipMemcpyAsync(d_lo.p, lo, (size_t)n * 12, hipMemcpyHostToDevice, stream));
-    LB(hipMemcpyAsync(d_hi.p, hi, (size_t)n * 12, hipMemcpyHostToDevice, stream));
     LB(hipMemsetAsync(d_flag.p, 0, (size_t)(n - 1) * 4, stream));
+    LB(lbvh_sorted_keys_host(lo, hi, n, d_lo.p, d_hi.p, d_keys.p, d_sorted.p, d_tmp, stream));
     const unsigned blocks = (n + 255u) / 256u;
-    hipLaunchKernelGGL(k_lbvh_keys, dim3(blocks), dim3(256), 0, stream, d_lo.p, d_hi.p, n, clo[0], clo[1], clo[2], sc[0], sc[1], sc[2], d_keys.p);
-    LB(hipGetLastError());
-    size_t tmp_bytes = 0;
-    LB(hipcub::DeviceRadixSort::SortKeys(nullptr, tmp_bytes, d_keys.p, d_sorted.p, (int)n, 0, 62, stream));
-    LB(d_tmp.alloc(tmp_bytes));
-    LB(hipcub::DeviceRadixSort::SortKeys(d_tmp.p, tmp_bytes, d_keys.p, d_sorted.p, (int)n, 0, 62, stream));
     hipLaunchKernelGGL(k_lbvh_hierarchy, dim3(blocks), dim3(256), 0, stream, d_sorted.p, (int)n, d_child.p, d_pi.p, d_pl.p);
     LB(hipGetLastError());
     hipLaunchKernelGGL(k_lbvh_bounds, dim3(blocks), dim3(256), 0, stream, d_sorted.p, (int)n, d_lo.p, d_hi.p, d_child.p, d_pi.p, d_pl.p,
@@ -198,7 +211,6 @@ hipError_t build_lbvh(const float *lo, const float *hi, uint32_t n, Bvh &out, hi
     LB(hipMemcpyAsync(out.nodes.data(), d_nodes.p, out.nodes.size() * sizeof(float), hipMemcpyDeviceToHost, stream));
     LB(hipMemcpyAsync(keys.data(), d_sorted.p, (size_t)n * 8, hipMemcpyDeviceToHost, stream));
     LB(hipStreamSynchronize(stream));
-#undef LB
     out.order.resize(n);
     for (size_t s = 0; s < n; s++) out.order[s] = (uint32_t)(keys[s] & 0xFFFFFFFFull);
     out.root = 0;
@@ -364,54 +376,45 @@ __global__ __launch_bounds__(256) void k_lbvh_gather_prims(const unsigned char *
 
 }  // namespace
 
-// d_raw: the scene's 80-byte records on the device.  Outputs (device, caller-allocated): prim 3n float4, primD n,
-// slot_of_index n, nodes2 (n-1) x 16 floats (the BVH2 of crt_bvh.h), nodes4q (n-1) x 4 uint4 at most.
-// res.quantised == false: the scene cannot be quantised (same rules as quantize_bvh4); nothing usable was produced
-// beyond nodes2 and the caller takes the host path.
-hipError_t build_lbvh_device(const unsigned char *d_raw, uint32_t n, float hit_pad, float4 *d_prim, float4 *d_primD,
-                             uint32_t *d_slot_of_index, float *d_nodes2, uint4 *d_nodes4q, LbvhDeviceResult &res, hipStream_t stream)
+// The same front from the scene's 80-byte records on the device: bounds at hit_pad, the box of the centroids (d_cbox: six
+// dwords of the caller's), keys, sort.
+hipError_t lbvh_sorted_keys_device(const unsigned char *d_raw, uint32_t n, float hit_pad, float *d_lo, float *d_hi, uint32_t *d_cbox,
+                                   unsigned long long *d_keys, unsigned long long *d_sorted, DevBuf<char> &sort_tmp, hipStream_t stream)
 {
-    res = LbvhDeviceResult();
-    if (n < 2) return hipErrorInvalidValue;
-    Tmp<float> d_lo, d_hi, d_nb;
-    Tmp<unsigned long long> d_keys, d_sorted;
-    Tmp<int> d_child, d_pi, d_pl, d_height, d_front[2];
-    Tmp<unsigned int> d_flag, d_small;
-    Tmp<char> d_tmp;
     hipError_t e;
-#define LB(call) do { e = (call); if (e != hipSuccess) return e; } while (0)
-    LB(d_lo.alloc((size_t)n * 3)); LB(d_hi.alloc((size_t)n * 3));
-    LB(d_keys.alloc(n)); LB(d_sorted.alloc(n));
-    LB(d_child.alloc((size_t)2 * (n - 1))); LB(d_pi.alloc(n - 1)); LB(d_pl.alloc(n));
-    LB(d_flag.alloc(n - 1)); LB(d_nb.alloc((size_t)6 * (n - 1))); LB(d_height.alloc(n - 1));
-    LB(d_small.alloc(16));
     const uint32_t cinit[6] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u, 0u};
-    LB(hipMemcpyAsync(d_small.p, cinit, sizeof cinit, hipMemcpyHostToDevice, stream));
-    LB(hipMemsetAsync(d_flag.p, 0, (size_t)(n - 1) * 4, stream));
+    LB(hipMemcpyAsync(d_cbox, cinit, sizeof cinit, hipMemcpyHostToDevice, stream));
     const unsigned blocks = (n + 255u) / 256u;
-    hipLaunchKernelGGL(k_lbvh_prim_bounds, dim3(blocks), dim3(256), 0, stream, d_raw, n, hit_pad, d_lo.p, d_hi.p, d_small.p);
+    hipLaunchKernelGGL(k_lbvh_prim_bounds, dim3(blocks), dim3(256), 0, stream, d_raw, n, hit_pad, d_lo, d_hi, d_cbox);
     LB(hipGetLastError());
-    hipLaunchKernelGGL(k_lbvh_keys_dev, dim3(blocks), dim3(256), 0, stream, d_lo.p, d_hi.p, n, d_small.p, d_keys.p);
+    hipLaunchKernelGGL(k_lbvh_keys_dev, dim3(blocks), dim3(256), 0, stream, d_lo, d_hi, n, d_cbox, d_keys);
     LB(hipGetLastError());
     size_t tmp_bytes = 0;
-    LB(hipcub::DeviceRadixSort::SortKeys(nullptr, tmp_bytes, d_keys.p, d_sorted.p, (int)n, 0, 62, stream));
-    LB(d_tmp.alloc(tmp_bytes));
-    LB(hipcub::DeviceRadixSort::SortKeys(d_tmp.p, tmp_bytes, d_keys.p, d_sorted.p, (int)n, 0, 62, stream));
-    hipLaunchKernelGGL(k_lbvh_hierarchy, dim3(blocks), dim3(256), 0, stream, d_sorted.p, (int)n, d_child.p, d_pi.p, d_pl.p);
-    LB(hipGetLastError());
-    hipLaunchKernelGGL(k_lbvh_bounds, dim3(blocks), dim3(256), 0, stream, d_sorted.p, (int)n, d_lo.p, d_hi.p, d_child.p, d_pi.p, d_pl.p,
-                       d_flag.p, d_nb.p, d_nodes2, d_height.p);
-    LB(hipGetLastError());
-    // the leaf-ordered primitive records do not depend on the tree's shape: enqueue them now
-    hipLaunchKernelGGL(k_lbvh_gather_prims, dim3(blocks), dim3(256), 0, stream, d_raw, d_sorted.p, n, d_prim, d_primD, d_slot_of_index);
-    LB(hipGetLastError());
-    // the scene box = the union of the root's two child boxes; the tree's depth = the root's height
+    LB(hipcub::DeviceRadixSort::SortKeys(nullptr, tmp_bytes, d_keys, d_sorted, (int)n, 0, 62, stream));
+    LB(sort_tmp.alloc(std::max<size_t>(tmp_bytes, 1)));
+    LB(hipcub::DeviceRadixSort::SortKeys(sort_tmp.p, tmp_bytes, d_keys, d_sorted, (int)n, 0, 62, stream));
+    return hipSuccess;
+}
+
+// Leaf-ordered records through `keys`: slot s holds the primitive whose index is the low half of keys[s].
+hipError_t lbvh_launch_gather(const unsigned char *d_raw, const unsigned long long *d_keys, uint32_t n, float4 *d_prim, float4 *d_primD,
+                              uint32_t *d_slot_of_index, hipStream_t stream)
+{
+    hipLaunchKernelGGL(k_lbvh_gather_prims, dim3((n + 255u) / 256u), dim3(256), 0, stream, d_raw, d_keys, n, d_prim, d_primD, d_slot_of_index);
+    return hipGetLastError();
+}
+
+// A finished BVH2 on the device (root = node 0; res.max_depth set by the caller) -> the quantised 4-wide tree, level by
+// level.  res.quantised stays false where quantize_bvh4's rules refuse the scene.
+hipError_t lbvh_collapse_device(const float *d_nodes2, uint32_t n, uint4 *d_nodes4q, LbvhDeviceResult &res, hipStream_t stream)
+{
+    hipError_t e;
+    DevBuf<int> d_front[2];
+    DevBuf<unsigned int> d_count;
+    // the scene box = the union of the root's two child boxes
     float rootrec[kNodeFloats];
-    int depth = 0;
     LB(hipMemcpyAsync(rootrec, d_nodes2, sizeof rootrec, hipMemcpyDeviceToHost, stream));
-    LB(hipMemcpyAsync(&depth, d_height.p, sizeof depth, hipMemcpyDeviceToHost, stream));
     LB(hipStreamSynchronize(stream));
-    res.max_depth = (uint32_t)depth;
     double base[3], scale[3];
     for (int a = 0; a < 3; a++) {
         const float glo = std::min(rootrec[a], rootrec[6 + a]), ghi = std::max(rootrec[3 + a], rootrec[9 + a]);
@@ -423,29 +426,67 @@ hipError_t build_lbvh_device(const unsigned char *d_raw, uint32_t n, float hit_p
         base[a] = res.qbase[a]; scale[a] = res.qscale[a];
     }
     // collapse level by level (breadth-first numbering: the top of the tree sits together, like the host's renumbering)
-    LB(d_front[0].alloc(n / 2 + 2)); LB(d_front[1].alloc(n / 2 + 2));
+    LB(d_front[0].alloc(n / 2 + 2)); LB(d_front[1].alloc(n / 2 + 2)); LB(d_count.alloc(1));
     const int root = 0;
     LB(hipMemcpyAsync(d_front[0].p, &root, sizeof root, hipMemcpyHostToDevice, stream));
     uint32_t count = 1, level_base = 0;
     int cur = 0;
     for (int level = 0; count > 0; level++) {
         if (level > 64) return hipErrorUnknown;
-        LB(hipMemsetAsync(d_small.p + 8, 0, 4, stream));
-        hipLaunchKernelGGL(k_lbvh_collapse_level, dim3((count + 255u) / 256u), dim3(256), 0, stream, (const float *)d_nodes2, (const int *)d_front[cur].p, count,
-                           level_base, d_front[cur ^ 1].p, d_small.p + 8, level_base + count, d_nodes4q, base[0], base[1], base[2], scale[0], scale[1], scale[2]);
+        LB(hipMemsetAsync(d_count.p, 0, 4, stream));
+        hipLaunchKernelGGL(k_lbvh_collapse_level, dim3((count + 255u) / 256u), dim3(256), 0, stream, d_nodes2, (const int *)d_front[cur].p, count,
+                           level_base, d_front[cur ^ 1].p, d_count.p, level_base + count, d_nodes4q, base[0], base[1], base[2], scale[0], scale[1], scale[2]);
         LB(hipGetLastError());
         uint32_t next = 0;
-        LB(hipMemcpyAsync(&next, d_small.p + 8, 4, hipMemcpyDeviceToHost, stream));
+        LB(hipMemcpyAsync(&next, d_count.p, 4, hipMemcpyDeviceToHost, stream));
         LB(hipStreamSynchronize(stream));
         level_base += count;
         count = next;
         cur ^= 1;
         res.depth4 = (uint32_t)level + 1u;
     }
-#undef LB
     res.n_nodes4 = level_base;
     res.quantised = true;
     return hipSuccess;
 }
+
+// d_raw: the scene's 80-byte records on the device.  Outputs (device, caller-allocated): prim 3n float4, primD n,
+// slot_of_index n, nodes2 (n-1) x 16 floats (the BVH2 of crt_bvh.h), nodes4q (n-1) x 4 uint4 at most.
+// res.quantised == false: the scene cannot be quantised (same rules as quantize_bvh4); nothing usable was produced
+// beyond nodes2 and the caller takes the host path.
+hipError_t build_lbvh_device(const unsigned char *d_raw, uint32_t n, float hit_pad, float4 *d_prim, float4 *d_primD,
+                             uint32_t *d_slot_of_index, float *d_nodes2, uint4 *d_nodes4q, LbvhDeviceResult &res, hipStream_t stream)
+{
+    res = LbvhDeviceResult();
+    if (n < 2) return hipErrorInvalidValue;
+    Tmp<float> d_lo, d_hi, d_nb;
+    Tmp<unsigned long long> d_keys, d_sorted;
+    Tmp<int> d_child, d_pi, d_pl, d_height;
+    Tmp<unsigned int> d_flag, d_small;
+    DevBuf<char> d_tmp;
+    hipError_t e;
+    LB(d_lo.alloc((size_t)n * 3)); LB(d_hi.alloc((size_t)n * 3));
+    LB(d_keys.alloc(n)); LB(d_sorted.alloc(n));
+    LB(d_child.alloc((size_t)2 * (n - 1))); LB(d_pi.alloc(n - 1)); LB(d_pl.alloc(n));
+    LB(d_flag.alloc(n - 1)); LB(d_nb.alloc((size_t)6 * (n - 1))); LB(d_height.alloc(n - 1));
+    LB(d_small.alloc(16));
+    LB(hipMemsetAsync(d_flag.p, 0, (size_t)(n - 1) * 4, stream));
+    LB(lbvh_sorted_keys_device(d_raw, n, hit_pad, d_lo.p, d_hi.p, d_small.p, d_keys.p, d_sorted.p, d_tmp, stream));
+    const unsigned blocks = (n + 255u) / 256u;
+    hipLaunchKernelGGL(k_lbvh_hierarchy, dim3(blocks), dim3(256), 0, stream, d_sorted.p, (int)n, d_child.p, d_pi.p, d_pl.p);
+    LB(hipGetLastError());
+    hipLaunchKernelGGL(k_lbvh_bounds, dim3(blocks), dim3(256), 0, stream, d_sorted.p, (int)n, d_lo.p, d_hi.p, d_child.p, d_pi.p, d_pl.p,
+                       d_flag.p, d_nb.p, d_nodes2, d_height.p);
+    LB(hipGetLastError());
+    // the leaf-ordered primitive records do not depend on the tree's shape: enqueue them now
+    LB(lbvh_launch_gather(d_raw, d_sorted.p, n, d_prim, d_primD, d_slot_of_index, stream));
+    // the tree's depth = the root's height
+    int depth = 0;
+    LB(hipMemcpyAsync(&depth, d_height.p, sizeof depth, hipMemcpyDeviceToHost, stream));
+    LB(hipStreamSynchronize(stream));
+    res.max_depth = (uint32_t)depth;
+    return lbvh_collapse_device(d_nodes2, n, d_nodes4q, res, stream);
+}
+#undef LB
 
 }  // namespace crt

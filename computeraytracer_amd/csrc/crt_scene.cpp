@@ -102,6 +102,19 @@ void camera_frame(const float cam[16], float out[12])
 // crt_build_accel(CRT_ACCEL_LBVH), all on the device (crt_lbvh.hip): bounds, Morton order, hierarchy, collapse to the
 // 4-wide tree, quantisation and the leaf-ordered primitive records; nothing of the tree visits the host.  Returns
 // CRT_OK with *done = false when the scene cannot take this path (not quantisable): the caller builds the host way.
+//
+// CRT_ACCEL_PLOC takes the same route with the clustered hierarchy (crt_ploc.hip).  A PLOC build that is abandoned (deeper
+// than the single-ray stacks allow, or not finished within the rounds limit) leaves a note in crt_last_error and the
+// same call builds the Karras LBVH instead.
+static void ploc_abandoned_note(crt_ctx *c, const PlocInfo &info)
+{
+    if (info.abandoned == 1)
+        (void)fail(c, CRT_OK, "crt_build_accel: the PLOC hierarchy is %u levels deep, more than the %u the walk's stacks allow; built the LBVH instead",
+                   info.depth, c->ploc.max_depth);
+    else
+        (void)fail(c, CRT_OK, "crt_build_accel: the PLOC build had not finished after %u rounds (the limit); built the LBVH instead", info.rounds);
+}
+
 static int build_accel_on_device(crt_ctx *c, bool *done)
 {
     *done = false;
@@ -114,9 +127,20 @@ static int build_accel_on_device(crt_ctx *c, bool *done)
     HIPCHK(c, c->d_nodes4q.alloc((size_t)(n - 1) * 4));
     HIPCHK(c, c->d_nodes4.alloc(8));
     LbvhDeviceResult res;
-    const hipError_t e = build_lbvh_device(c->d_raw.p, n, c->sc.hit_pad, c->d_prim.p, c->d_primD.p, c->d_slot_of_index.p,
-                                           (float *)c->d_nodes.p, c->d_nodes4q.p, res, c->stream);
-    if (e != hipSuccess) return fail(c, e == hipErrorOutOfMemory ? CRT_ENOMEM : CRT_EDEVICE, "crt_build_accel: GPU LBVH build: %s", hipGetErrorString(e));
+    int builder = 1;
+    if (c->want_builder == 2) {
+        PlocInfo info;
+        const hipError_t e = build_ploc_device(c->d_raw.p, n, c->sc.hit_pad, c->ploc, c->d_prim.p, c->d_primD.p, c->d_slot_of_index.p,
+                                               (float *)c->d_nodes.p, c->d_nodes4q.p, res, info, c->stream);
+        if (e != hipSuccess) return fail(c, e == hipErrorOutOfMemory ? CRT_ENOMEM : CRT_EDEVICE, "crt_build_accel: GPU PLOC build: %s", hipGetErrorString(e));
+        if (info.abandoned) ploc_abandoned_note(c, info);
+        else builder = 2;
+    }
+    if (builder == 1) {
+        const hipError_t e = build_lbvh_device(c->d_raw.p, n, c->sc.hit_pad, c->d_prim.p, c->d_primD.p, c->d_slot_of_index.p,
+                                               (float *)c->d_nodes.p, c->d_nodes4q.p, res, c->stream);
+        if (e != hipSuccess) return fail(c, e == hipErrorOutOfMemory ? CRT_ENOMEM : CRT_EDEVICE, "crt_build_accel: GPU LBVH build: %s", hipGetErrorString(e));
+    }
     if (!res.quantised) return CRT_OK;
     // the host keeps the tree's statistics only
     c->bvh = Bvh(); c->bvh4 = Bvh4(); c->bvh4q = Bvh4Q(); c->bvh8q = Bvh8Q();
@@ -124,7 +148,7 @@ static int build_accel_on_device(crt_ctx *c, bool *done)
     c->bvh4.root = 0; c->bvh4.n_inner = res.n_nodes4; c->bvh4.max_depth = res.depth4;
     c->bvh4q.ok = true;
     for (int a = 0; a < 3; a++) { c->bvh4q.base[a] = res.qbase[a]; c->bvh4q.scale[a] = res.qscale[a]; c->sc.qbase[a] = res.qbase[a]; c->sc.qscale[a] = res.qscale[a]; }
-    c->accel_builder = 1;
+    c->accel_builder = builder;
     c->sc.prim = c->d_prim.p; c->sc.primD = c->d_primD.p; c->sc.slot_of_index = c->d_slot_of_index.p;
     c->sc.nodes = c->d_nodes.p; c->sc.root = 0;
     c->sc.nodes4 = c->d_nodes4.p; c->sc.root4 = 0; c->sc.n_nodes4 = res.n_nodes4;
@@ -143,7 +167,7 @@ static int upload_geometry(crt_ctx *c, int mode)
 {
     const uint32_t n = (uint32_t)c->prims.size();
     const float pad = c->sc.hit_pad;
-    if (mode == CRT_ACCEL_BVH2 && c->want_lbvh) {
+    if (mode == CRT_ACCEL_BVH2 && c->want_builder != 0) {
         bool done = false;
         int rc = build_accel_on_device(c, &done);
         if (rc || done) return rc;
@@ -202,11 +226,21 @@ static int upload_geometry(crt_ctx *c, int mode)
             }
         }
         c->accel_builder = 0;
-        if (c->want_lbvh && n >= 2) {
-            // GPU build (crt_lbvh.hip): same structure, so everything below is shared
-            hipError_t e = build_lbvh(lo.data(), hi.data(), n, c->bvh, c->stream);
-            if (e != hipSuccess) return fail(c, e == hipErrorOutOfMemory ? CRT_ENOMEM : CRT_EDEVICE, "crt_build_accel: GPU LBVH build: %s", hipGetErrorString(e));
-            c->accel_builder = 1;
+        if (c->want_builder != 0 && n >= 2) {
+            // GPU build (crt_lbvh.hip, crt_ploc.hip): same structure, so everything below is shared
+            int builder = 1;
+            if (c->want_builder == 2) {
+                PlocInfo info;
+                hipError_t e = build_ploc(lo.data(), hi.data(), n, c->ploc, c->bvh, info, c->stream);
+                if (e != hipSuccess) return fail(c, e == hipErrorOutOfMemory ? CRT_ENOMEM : CRT_EDEVICE, "crt_build_accel: GPU PLOC build: %s", hipGetErrorString(e));
+                if (info.abandoned) ploc_abandoned_note(c, info);
+                else builder = 2;
+            }
+            if (builder == 1) {
+                hipError_t e = build_lbvh(lo.data(), hi.data(), n, c->bvh, c->stream);
+                if (e != hipSuccess) return fail(c, e == hipErrorOutOfMemory ? CRT_ENOMEM : CRT_EDEVICE, "crt_build_accel: GPU LBVH build: %s", hipGetErrorString(e));
+            }
+            c->accel_builder = builder;
         } else {
             build_bvh2(lo.data(), hi.data(), n, c->bvh);
         }
@@ -315,17 +349,19 @@ int build_tree(crt_ctx *c, int mode)
         c->wf_depth = c->bvh8q.ok ? c->bvh8q.max_depth : c->bvh4.max_depth;
         // ("wf_trace_form" may change after the build: judged with the fewest LDS entries a kernel for this tree has)
         const uint32_t lds_min = c->bvh4q.ok && !c->bvh8q.ok ? (uint32_t)kWfStackLds2 : (uint32_t)kWfStackLds;
-        if (c->accel_builder == 1 && wf_stack_need(c) > lds_min + kWfOverflowMaxLevels) {
-            // an LBVH this deep would need an unreasonable overflow area: the SAH builder's tree is at most 30 levels deep
+        if (c->accel_builder != 0 && wf_stack_need(c) > lds_min + kWfOverflowMaxLevels) {
+            // a GPU-built tree this deep would need an unreasonable overflow area: the SAH builder's tree is at most 30 levels deep
             const uint32_t depth = c->wf_depth, width = c->bvh8q.ok ? 8u : 4u;
-            c->want_lbvh = false; c->accel_mode = -1;
+            const int wanted = c->want_builder;
+            const char *made = c->accel_builder == 2 ? "PLOC tree" : "LBVH";
+            c->want_builder = 0; c->accel_mode = -1;
             rc = upload_geometry(c, mode);
-            c->want_lbvh = true;                                 // (a rebuild by crt_refit_accel tries the LBVH again)
+            c->want_builder = wanted;                            // (a rebuild by crt_refit_accel tries the GPU builder again)
             if (rc == CRT_OK) {
                 c->wf_depth = c->bvh8q.ok ? c->bvh8q.max_depth : c->bvh4.max_depth;
-                (void)fail(c, CRT_OK, "crt_build_accel: the %u-wide LBVH is %u levels deep (its walk would need %u stack entries per lane, "
+                (void)fail(c, CRT_OK, "crt_build_accel: the %u-wide %s is %u levels deep (its walk would need %u stack entries per lane, "
                                       "more than %u + %u); built with the host SAH builder instead (%u levels)",
-                           width, depth, (width - 1u) * depth, lds_min, kWfOverflowMaxLevels, c->wf_depth);
+                           width, made, depth, (width - 1u) * depth, lds_min, kWfOverflowMaxLevels, c->wf_depth);
             }
         }
     }

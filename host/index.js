@@ -1,6 +1,6 @@
 #!/usr/bin/env node
 'use strict';
-// CLI: node host/index.js [--scene file.json] [--width W --height H] [--spp N] [--accel bvh2|lbvh|none]
+// CLI: node host/index.js [--scene file.json] [--width W --height H] [--spp N] [--accel bvh2|lbvh|ploc|none]
 //                         [--out image.ppm] [--dump prefix] [--pack-only prefix] [--denoise K] [--orbit N [--temporal [--variance]]]
 // --denoise K: --out gets the image denoised with K a-trous iterations (crt_denoise; with --adaptive the variance-guided
 //            crt_denoise_adaptive) instead of the plain average

@@ -25,7 +25,7 @@ function loadAddon() {
   return addon;
 }
 
-const ACCEL = { none: 0, brute: 0, bvh2: 1, bvh: 1, lbvh: 2 };
+const ACCEL = { none: 0, brute: 0, bvh2: 1, bvh: 1, lbvh: 2, ploc: 3 };
 
 function Main(options = {}) {
   const a = loadAddon();

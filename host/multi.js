@@ -14,7 +14,7 @@
  *            -> { trace(spp); gather(rgba8) } x frames -> sync -> gather(rgba8 | accum); rank 0 writes the image
  *
  *   node host/multi.js --gpus 8 [--scene file.json] [--width W --height H] [--spp 64] [--frames 4] [--band 8]
- *                      [--accel bvh2|lbvh] [--out frame.ppm] [--local]
+ *                      [--accel bvh2|lbvh|ploc] [--out frame.ppm] [--local]
  *   --local: all ranks in THIS process on device 0, joined by the in-process transport (CRT_COMM_LOCAL: device-to-device
  *            copies stand where the RCCL all-gather does) -- how the path is exercised on a one-GPU box.
  */
@@ -23,7 +23,7 @@ const { fork } = require('child_process');
 const { writePPM, loadAddon } = require('./main');
 const sceneLoader = require('./sceneLoader');
 
-const ACCEL = { none: 0, brute: 0, bvh2: 1, bvh: 1, lbvh: 2 };
+const ACCEL = { none: 0, brute: 0, bvh2: 1, bvh: 1, lbvh: 2, ploc: 3 };
 const GATHER_RGBA8 = 1, GATHER_ACCUM = 2;
 
 function parseArgs(argv) {

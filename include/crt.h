@@ -46,10 +46,17 @@ enum {
     CRT_ACCEL_BVH2 = 1, /* binned-SAH BVH2 built on the host; returns exactly
                            what the loop returns (closest t; equal t -> later
                            primitive) */
-    CRT_ACCEL_LBVH = 2  /* the same structure built on the GPU, end to end (Morton order,
+    CRT_ACCEL_LBVH = 2, /* the same structure built on the GPU, end to end (Morton order,
                            Karras hierarchy, collapse to 4-wide, quantisation, leaf-ordered
                            records): milliseconds instead of seconds to build (10 M
                            triangles: 0.11 s), same image, more nodes visited per ray  */
+    CRT_ACCEL_PLOC = 3  /* the same BVH2 and wide-tree structures, built on the GPU by parallel
+                           locally-ordered clustering over the LBVH's Morton order (option
+                           "ploc_radius"): same image, a build of milliseconds, and a tree
+                           closer to the SAH builder's than the LBVH's (fewer nodes visited
+                           per ray).  Follows the LBVH mode's contract; a hierarchy too deep
+                           for the walk's stacks is built as the LBVH by the same call, with
+                           a note in crt_last_error */
 };
 
 /* Counter slots for crt_counters(). */
@@ -519,14 +526,18 @@ int crt_last_kernel_ms(crt_ctx *ctx, float *ms, uint32_t *launches);
  * rgba8 frame of each of the last F samples for crt_read_sample_rgba8; 0 = off);
  * "temporal_motion" (0 | 1, anything else is CRT_EINVAL: 1 keeps the history of crt_denoise_temporal across
  * crt_update_primitives, see "Temporal reuse"; costs 80 bytes per primitive on the device once an edit has happened);
+ * "ploc_radius" (1..32, anything else is CRT_EINVAL; default 8: clusters searched to either side by CRT_ACCEL_PLOC; at
+ * crt_build_accel);
  * "time_kernels"; "debug_fail_alloc" = k (test hook: the k-th device allocation from now on reports
- * out of memory).  Setting an option first finishes what is in flight. */
+ * out of memory); "debug_ploc_max_depth" (1..62, default 62) and "debug_ploc_max_rounds" (>= 1, default 256): test
+ * hooks, a CRT_ACCEL_PLOC build deeper than the one or unfinished after the other is abandoned and the same call builds
+ * the LBVH.  Setting an option first finishes what is in flight. */
 int crt_set_option(crt_ctx *ctx, const char *name, int64_t value);
 
 /* Accel statistics: out[0]=BVH2 inner nodes, [1]=leaves, [2]=max depth, [3]=device bytes,
  * [4]=bytes of node data fetched per child box tested by crt_trace (32: plain boxes, 16:
  * 16-bit quantised), [5]=node width crt_trace walks (2, 4 or 8), [6]=inner nodes of that tree,
- * [7]=builder (0: host binned SAH, 1: GPU LBVH). */
+ * [7]=builder (0: host binned SAH, 1: GPU LBVH, 2: GPU PLOC). */
 int crt_accel_stats(crt_ctx *ctx, uint64_t out[8]);
 
 /* Test hooks: one closest-hit query per ray (rays: n x 8 floats ox,oy,oz,dx,dy,dz,exclude_as_u32_bits,_;  out: n x 8:
@@ -558,14 +569,14 @@ int crt_debug_math(crt_ctx *ctx, int fn, const float *a, const float *b, float *
  * kernel runs).  `what` selects one part; *bytes (may be NULL) receives the part's size; out == NULL only reports it.
  *   CRT_ACCEL_PART_HEADER        CRT_ACCEL_HEADER_N doubles (every value is an integer or a float, exact in a double):
  *       [0] accel mode (CRT_ACCEL_NONE | CRT_ACCEL_BVH2: both builders make that structure), [1] builder (0 host SAH, 1 GPU
- *       LBVH), [2] nprim, [3] root, [4] root4, [5] root8 (child references; -1: none), [6] [7] [8] inner nodes of the BVH2 /
+ *       LBVH, 2 GPU PLOC), [2] nprim, [3] root, [4] root4, [5] root8 (child references; -1: none), [6] [7] [8] inner nodes of the BVH2 /
  *       the 4-wide / the 8-wide tree, [9] [10] [11] 1 = the float 4-wide / quantised 4-wide / quantised 8-wide nodes are
  *       live on the device, [12..14] qbase, [15..17] qscale, [18] hit_pad, [19] tree_pad (the pad the boxes were made with),
  *       [20] recorded depth of the BVH2, [21] of the 4-wide tree (the host collapse's, or the level count of the device
  *       collapse), [22] of the 8-wide tree, [23] wf_depth (inner levels of the tree the wavefront kernels walk),
  *       [24] stack entries a walk can need = (width - 1) x [23], [25] stack entries per lane in LDS, [26] overflow levels
  *       the context asks for, [27] overflow levels allocated now (0 before the first trace call), [28] 1 = the tree is
- *       stale (primitives updated, not refitted), [29] 1 = the all-device LBVH route built the tree (the host holds
+ *       stale (primitives updated, not refitted), [29] 1 = the all-device route (LBVH or PLOC) built the tree (the host holds
  *       statistics only)
  *   CRT_ACCEL_PART_NODES2        [6] x 16 floats (crt_bvh.h: c0.lo c0.hi c1.lo c1.hi ref0 ref1 - -)
  *   CRT_ACCEL_PART_NODES4        [7] x 32 floats where [9], else empty

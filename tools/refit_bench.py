@@ -2,6 +2,7 @@
 around synchronous calls, warm, median of --reps.
 
   build_lbvh_ms        crt_build_accel(CRT_ACCEL_LBVH)
+  build_ploc_ms        crt_build_accel(CRT_ACCEL_PLOC)
   refit_ms             crt_refit_accel after a crt_update_primitives (the update itself not timed)
   update_ms            crt_update_primitives of the moved tenth (records, hit_pad reduction, state reset)
   transform_ms         crt_transform_primitives of the same tenth by the same rigid move, one op (the records never leave
@@ -10,8 +11,9 @@ around synchronous calls, warm, median of --reps.
   refit_after_transform_ms   crt_refit_accel after such a call
   set_camera_ms        crt_set_camera with a pad that does not grow (no refit): sync + camera + state reset
   set_camera_refit_ms  crt_set_camera with an eye farther out each call (the pad grows: inline refit)
-  step_ms_refit / step_ms_fresh   ms per --spp step after a rigid move of a contiguous tenth of the primitives,
-                       refitted tree against a fresh LBVH build of the same buffers (the tree-quality cost)
+  step_ms_refit / step_ms_fresh / step_ms_fresh_ploc   ms per --spp step after a rigid move of a contiguous tenth of the
+                       primitives, refitted tree against a fresh LBVH / PLOC build of the same buffers (the tree-quality cost)
+  edit_total_ms        what one edited frame costs by each route: refit + step, LBVH rebuild + step, PLOC rebuild + step
 
 --parent DIR: a checkout of the parent commit with its library built.  Its crt_update_primitives of the same tenth is
 measured in child processes (this tool with --update-only --tree DIR) before and after this build's run, in one session:
@@ -60,6 +62,9 @@ def run_scene(name, ps, reps, spp, steps, update_only=False):
     try:
         r.upload(ps)
         res["build_lbvh_ms"] = timed(lambda: r.build_accel("lbvh"), reps)
+        if not update_only:
+            res["build_ploc_ms"] = timed(lambda: r.build_accel("ploc"), reps)
+            r.build_accel("lbvh")
         flip = [0]
 
         def update():
@@ -146,6 +151,11 @@ def run_scene(name, ps, reps, spp, steps, update_only=False):
         res["step_ms_refit"] = steps_ms()
         r.build_accel("lbvh")
         res["step_ms_fresh"] = steps_ms()
+        r.build_accel("ploc")
+        res["step_ms_fresh_ploc"] = steps_ms()
+        res["edit_total_ms"] = {"refit": round(res["refit_ms"] + res["step_ms_refit"], 3),
+                                "rebuild_lbvh": round(res["build_lbvh_ms"] + res["step_ms_fresh"], 3),
+                                "rebuild_ploc": round(res["build_ploc_ms"] + res["step_ms_fresh_ploc"], 3)}
         res["spp_per_step"] = spp
     finally:
         r.close()
