@@ -260,6 +260,7 @@ int crt_upload_scene(crt_ctx *c, const void *primitives, size_t nprim, const voi
     HIPCHK(c, hipMemcpy(c->d_spectra.p, spectra, nspectra * kNLambda * sizeof(float), hipMemcpyHostToDevice));
     HIPCHK(c, c->d_cie.alloc(3 * kNCie));
     HIPCHK(c, hipMemcpy(c->d_cie.p, cie, 3 * kNCie * sizeof(float), hipMemcpyHostToDevice));
+    c->cie_zero = tc_culled_is_zero(cie);                        // (what k_wf_gen stores for a MISS tile's chunk: DESIGN.md 5.9)
     std::vector<float4> hl(nlight * 3);
     for (size_t i = 0; i < nlight; i++) light_rows(c->lights[i], &hl[3 * i]);
     HIPCHK(c, c->d_lights.alloc(hl.size()));
@@ -802,6 +803,7 @@ int crt_set_option(crt_ctx *c, const char *name, int64_t value)
     if (!std::strcmp(name, "wf_gen_blocks")) { c->wf_gen_blocks = (int)std::min<int64_t>(4096, std::max<int64_t>(1, value)); return CRT_OK; }
     if (!std::strcmp(name, "wf_trace_form")) { c->wf_trace_form = value == 1 ? 1 : 2; return CRT_OK; }
     if (!std::strcmp(name, "wf_cull_miss")) { c->wf_cull_miss = value != 0; return CRT_OK; }
+    if (!std::strcmp(name, "wf_cull_classes")) { c->wf_cull_classes = value != 0; return CRT_OK; }
     if (!std::strcmp(name, "wf_pipes")) { c->wf_pipes = (int)std::min<int64_t>(crt_ctx::kMaxPipes, std::max<int64_t>(1, value)); return CRT_OK; }
     if (!std::strcmp(name, "wf_pool")) { c->wf_pool = (uint32_t)std::max<int64_t>(0, value); return CRT_OK; }
     if (!std::strcmp(name, "wf_waves_per_cu")) { c->wf_waves_per_cu = (uint32_t)std::min<int64_t>(32, std::max<int64_t>(0, value)); return CRT_OK; }

@@ -27,6 +27,7 @@
 #include "crt_device.h"
 #include "crt_launch.h"
 #include "crt_math.h"
+#include "crt_tile_class.h"
 #include "crt_wf_policy.h"
 
 namespace crt {
@@ -188,6 +189,7 @@ struct crt_ctx {
     DevBuf<uint4> w_rng, w_misc, w_recC;
     DevBuf<float2> w_hit;
     DevBuf<uint32_t> w_vis, w_dead, w_tea;
+    DevBuf<uint32_t> w_tile_cls;    // per 8x8 tile of the tile rectangle: 2 bits, what its camera rays' root step is for every sample
     static constexpr int kMaxPipes = crt::kWfMaxPipes;
     int wf_pipes = 2;
     int wf_defer = 1;               // 1: crt_trace returns with its batch in flight; its paths finish under the next batches (or at crt_sync)
@@ -195,6 +197,9 @@ struct crt_ctx {
     int wf_gen_blocks = 128;        // k_wf_gen: waves per shard (64 shards)
     int wf_trace_form = 2;          // traversal kernel: 2 = k_wf_trace2 (ray ring + primitive tasks), 1 = k_wf_trace
     int wf_cull_miss = 1;           // k_wf_gen decides whole work chunks whose camera rays all miss the tree's root boxes
+    int wf_cull_classes = 1;        // ... and looks the tile's class up first: the tiles that miss or enter for every sample are classified once per run
+    uint64_t tile_cls_setups = 0;   // run set-ups that launched k_wf_tile_classes so far (crt_debug_tile_class_setups)
+    bool cie_zero = false;          // the uploaded CIE table turns zero radiance into +0 for every wavelength (tc_culled_is_zero)
     int wf_chunk = 1;               // iterations per status record at most
     int wf_ahead = 3;               // iterations in flight per pipe before the pump waits for a status
     int wf_ring = 32;               // batches in flight at most (2..kWfRing): bounds how many calls a bound output can lag

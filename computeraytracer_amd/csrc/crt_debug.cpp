@@ -217,6 +217,60 @@ int crt_debug_read_moments(crt_ctx *c, float *out)
     return dn_finish(c, n, nullptr, nullptr, nullptr);
 }
 
+// The tile classes of the context's current camera, tile rectangle and root node: the inputs of the next
+// run, or of the one the flush below ends.  A run's set-up makes its table from the same inputs with the same launch.
+static int tile_class_inputs(crt_ctx *c, const char *what, size_t n_tiles, WfParams &W)
+{
+    if (!c->have_scene || c->accel_mode < 0) return fail(c, CRT_ESTATE, "%s: scene + accel required", what);
+    if (c->accel_stale) return fail(c, CRT_ESTATE, "%s: primitives were updated: call crt_refit_accel or crt_build_accel first", what);
+    CRT_TRY(quiesce(c, true));
+    W = WfParams{};
+    W.sc = c->sc;
+    W.x0 = c->x0; W.y0 = c->y0; W.tw = c->tw; W.th = c->th; W.band = c->band; W.stride = c->stride; W.phase = c->phase;
+    W.tiles_x = (c->tw + 7u) / 8u; W.tiles_y = (c->th + 7u) / 8u;
+    if (c->accel_mode != CRT_ACCEL_BVH2 || c->pipeline != 1 || !W.sc.nodes4q || W.sc.root4 < 0 || W.sc.root4 == 0x7FFFFFFF)
+        return fail(c, CRT_ESTATE, "%s: no quantised 4-wide tree with an inner root", what);
+    if (n_tiles != (size_t)W.tiles_x * W.tiles_y) return fail(c, CRT_EINVAL, "%s: the tile rectangle has %zu tiles of 8x8, not %zu", what, (size_t)W.tiles_x * W.tiles_y, n_tiles);
+    return CRT_OK;
+}
+
+int crt_debug_tile_classes(crt_ctx *c, uint8_t *out, size_t n_tiles)
+{
+    if (!c || (!out && n_tiles)) return CRT_EINVAL;
+    WfParams W;
+    CRT_TRY(tile_class_inputs(c, "crt_debug_tile_classes", n_tiles, W));
+    if (n_tiles == 0) return CRT_OK;
+    const size_t words = (n_tiles + 15u) / 16u;
+    CRT_ENSURE(c, c->w_tile_cls, words);
+    std::vector<uint32_t> h(words);
+    HIPCHK(c, wf_launch_tile_classes(W, c->w_tile_cls.p, c->stream));
+    HIPCHK(c, hipMemcpyAsync(h.data(), c->w_tile_cls.p, words * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (size_t t = 0; t < n_tiles; t++) out[t] = (uint8_t)((h[t >> 4] >> (2u * (t & 15u))) & 3u);
+    return CRT_OK;
+}
+
+int crt_debug_tile_classes_host(crt_ctx *c, uint8_t *out, size_t n_tiles)
+{
+    if (!c || (!out && n_tiles)) return CRT_EINVAL;
+    WfParams W;
+    CRT_TRY(tile_class_inputs(c, "crt_debug_tile_classes_host", n_tiles, W));
+    TcRoot R;
+    HIPCHK(c, hipMemcpy(R.q, W.sc.nodes4q + 4 * (size_t)W.sc.root4, sizeof R.q, hipMemcpyDeviceToHost));
+    R.qscale = f3{W.sc.qscale[0], W.sc.qscale[1], W.sc.qscale[2]}; R.qbase = f3{W.sc.qbase[0], W.sc.qbase[1], W.sc.qbase[2]};
+    const TcCam C = tc_cam(W.sc.cam, W.sc.W, W.sc.H);
+    const TcTiles T{W.x0, W.y0, W.tw, W.th, W.band, W.stride, W.phase, W.tiles_x};
+    for (size_t t = 0; t < n_tiles; t++) out[t] = (uint8_t)tc_tile_class(C, R, T, (uint32_t)t);
+    return CRT_OK;
+}
+
+int crt_debug_tile_class_setups(crt_ctx *c, uint64_t *out)
+{
+    if (!c || !out) return CRT_EINVAL;
+    *out = c->tile_cls_setups;
+    return CRT_OK;
+}
+
 int crt_debug_hit_pad(crt_ctx *c, float *out)
 {
     if (!c || !out) return CRT_EINVAL;

@@ -237,6 +237,10 @@ struct WfParams {
     uint32_t trace_form;             // 2: k_wf_trace2 (ray ring + primitive tasks) where the tree is the quantised 4-wide one; else k_wf_trace
     int *stack_overflow;             // [level - LDS entries][global lane], for stacks deeper than the LDS part (wf_overflow_levels levels)
     uint32_t overflow_lanes;
+    // DESIGN.md 5.9 (option "wf_cull_classes"): 2 bits per 8x8 tile, 16 tiles per word (crt_tile_class.h), written by
+    // k_wf_tile_classes at run set-up and read-only during the run; null = k_wf_gen's CULL form tests every sample
+    const uint32_t *tile_cls;
+    uint32_t cls_miss_zero;          // a culled path's staging value is +0 for every wavelength (tc_culled_is_zero): MISS chunks store the constant
 };
 
 // k_dn_reproject (crt_denoise.hip): the blend of a frame with the reprojected history of the previous one.

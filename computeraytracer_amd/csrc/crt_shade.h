@@ -480,7 +480,8 @@ __device__ __forceinline__ void primary_ray(const DevScene &S, uint32_t px, uint
     d = normalize(((llc + hor * fs) + ver * ft) - eye);
 }
 
-// spectral_to_xyz :419-426
+// spectral_to_xyz :419-426.  RESTATED for zero radiance, host + device, with wavelengths_of (crt_wavefront.hip), as
+// tc_culled_xyz in crt_tile_class.h: a change here or there is made in both.
 __device__ __forceinline__ f3 spectral_to_xyz(const DevScene &S, f4 radiance, const uint32_t wl[4])
 {
     const float *X = S.cie, *Y = S.cie + kNCie, *Z = S.cie + 2 * kNCie;

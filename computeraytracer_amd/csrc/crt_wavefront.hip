@@ -25,6 +25,7 @@
 // consumes no random numbers, so a diffuse bounce can draw its light, hemisphere
 // and roulette numbers in one go.
 #include "crt_shade.h"
+#include "crt_tile_class.h"
 #include "crt_launch.h"
 #include <algorithm>
 
@@ -63,6 +64,7 @@ namespace crt {
 #ifndef CRT_WF_MIN_WAVES
 #define CRT_WF_MIN_WAVES 1
 #endif
+static_assert(kTcGrid == kGrid && kTcNLambda == kNLambda && kTcNCie == kNCie, "crt_tile_class.h restates these");
 constexpr int kWfStack = CRT_WF_STACK;      // LDS stack entries per lane; deeper stacks go on in P.stack_overflow (crt_device.h)
 static_assert(kWfStack == kWfStackLds, "crt_scene.cpp sizes the overflow area from kWfStackLds");
 constexpr int kNoNode = 0x7FFFFFFF;          // "no node left to walk" (inner ids are smaller, leaf references negative)
@@ -156,6 +158,7 @@ struct PathRegs {
     uint32_t exclude, work, flags;
 };
 
+// (restated in tc_culled_xyz, crt_tile_class.h: a change is made in both)
 __device__ __forceinline__ void wavelengths_of(uint32_t lambda, uint32_t wl[4])
 {
     wl[0] = lambda; wl[1] = (lambda + 4u) % kNLambda; wl[2] = (lambda + 8u) % kNLambda;
@@ -896,6 +899,11 @@ __global__ __launch_bounds__(64) void k_wf_gen(const WfParams P, uint32_t it, co
         uint32_t slot = 0, slot_of = 0xFFFFFFFFu;                        // the dead slots of chunk j + slot_of * gen_blocks
         uint32_t started = 0, started_q = 0;                             // paths started and not yet added to alive[started_q]
         uint32_t c_rays = 0, c_cull = 0;
+        // the classes of 16 consecutive tiles (consecutive chunks of a segment are consecutive tiles): a
+        // scalar load from the constant address space, like the root node -- the table is written before the run
+        typedef const __attribute__((address_space(4))) uint32_t *cptr1u;
+        const cptr1u tile_cls = (cptr1u)P.tile_cls;
+        uint32_t cls_word = 0, cls_word_of = 0xFFFFFFFFu;
         // the started chunk whose list positions are on their way
         bool pend = false, p_valid = false;
         uint32_t p_base = 0, p_entry = 0, p_rank = 0;
@@ -921,6 +929,19 @@ __global__ __launch_bounds__(64) void k_wf_gen(const WfParams P, uint32_t it, co
                 const uint32_t lx = (tile % P.tiles_x) * 8u + (lane & 7u), ly = (tile / P.tiles_x) * 8u + (lane >> 3);
                 const bool valid = lx < P.tw && ly < P.th;               // (an item outside a ragged tile is consumed without a path)
                 const unsigned long long mv = __ballot(valid);
+                uint32_t cls = kTcMaybe;
+                if (tile_cls) {
+                    if (cls_word_of != (tile >> 4)) { cls_word_of = tile >> 4; cls_word = tile_cls[cls_word_of]; }
+                    cls = (cls_word >> (2u * (tile & 15u))) & 3u;
+                }
+                if (cls == kTcMiss && P.cls_miss_zero) {
+                    // every ray of the tile misses for every sample: what the branch below stores, without drawing one
+                    if (valid) {
+                        stnt(&P.staging[sg][(size_t)sample_off * ((size_t)P.tw * P.th) + (size_t)ly * P.tw + lx], float4{0.0f, 0.0f, 0.0f, 0.0f});
+                        c_cull++;
+                    }
+                    continue;
+                }
                 if (slot_of != filled) { slot = ldnt(&P.dead[region + (size_t)(j + filled * P.gen_blocks) * 64u + lane]); slot_of = filled; }
                 f3 d = f3{0.0f, 0.0f, 0.0f};
                 uint32_t sample = 0, seed = 0, lambda = 0;
@@ -932,7 +953,9 @@ __global__ __launch_bounds__(64) void k_wf_gen(const WfParams P, uint32_t it, co
                     seed = P.tea[(size_t)ly * P.tw + lx];
                     const CamRay c = camera_ray(S, px, py, sample, seed);
                     d = c.d; lambda = c.lambda; nan_ray = c.nan_ray;
-                    miss = !c.nan_ray && root_step_misses(Q0, Q1, Q2, qscale, qbase, c.eye, c.d);
+                    // (an ENTER tile: every ray is finite and enters one of the root's boxes, so the chunk starts; the class is
+                    // wave-uniform, and the compiled root step sits behind an exec-mask branch that a whole ENTER wave skips)
+                    miss = cls == kTcEnter ? false : !c.nan_ray && root_step_misses(Q0, Q1, Q2, qscale, qbase, c.eye, c.d);
                 }
                 if (__ballot(!miss) == 0ull) {
                     // every path of the chunk ends at its camera ray: what its shade step would store (same function, same bits)
@@ -2004,6 +2027,33 @@ __global__ __launch_bounds__(256) void k_wf_tea(const WfParams P, uint32_t *out)
     out[i] = tea(px, py * 100u);
 }
 
+// The class of every 8x8 tile of the tile rectangle (crt_tile_class.h): whether its camera rays miss the
+// root's four child boxes, or enter one, for every sample and jitter.  One wave per tile, lane = pixel, two ballots; the
+// tile's 2 bits are OR-ed into its word of the table, which the launcher clears first (MAYBE = 0 writes nothing).  The
+// root node is read from device memory, as k_wf_gen's CULL form reads it: refits and edits between runs are seen.  Once
+// per run, on the context's stream, before the pipes fork.
+__global__ __launch_bounds__(64) void k_wf_tile_classes(const WfParams P, uint32_t *out)
+{
+    const DevScene &S = P.sc;
+    const uint32_t lane = lane_id(), tile = blockIdx.x;
+    if (tile >= P.tiles_x * P.tiles_y) return;
+    const uint4 *rq = S.nodes4q + 4 * (size_t)S.root4;
+    const uint4 Q0 = rq[0], Q1 = rq[1], Q2 = rq[2];
+    TcRoot R;
+    R.q[0] = Q0.x; R.q[1] = Q0.y; R.q[2] = Q0.z; R.q[3] = Q0.w; R.q[4] = Q1.x; R.q[5] = Q1.y; R.q[6] = Q1.z; R.q[7] = Q1.w;
+    R.q[8] = Q2.x; R.q[9] = Q2.y; R.q[10] = Q2.z; R.q[11] = Q2.w;
+    R.qscale = f3{S.qscale[0], S.qscale[1], S.qscale[2]}; R.qbase = f3{S.qbase[0], S.qbase[1], S.qbase[2]};
+    const TcCam C = tc_cam(S.cam, S.W, S.H);
+    const TcTiles T{P.x0, P.y0, P.tw, P.th, P.band, P.stride, P.phase, P.tiles_x};
+    uint32_t px, py;
+    const bool valid = tc_pixel(T, tile, lane, px, py);
+    const uint32_t cls = valid ? tc_pixel_class(C, R, px, py) : kTcMaybe;
+    const unsigned long long mv = __ballot(valid);
+    const unsigned long long not_miss = __ballot(valid && cls != kTcMiss), not_enter = __ballot(valid && cls != kTcEnter);
+    const uint32_t tcls = mv == 0ull ? kTcMaybe : not_miss == 0ull ? kTcMiss : not_enter == 0ull ? kTcEnter : kTcMaybe;
+    if (lane == 0 && tcls != 0u) atomicOr(&out[tile >> 4], tcls << (2u * (tile & 15u)));
+}
+
 __global__ void k_wf_init(const WfParams P)
 {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
@@ -2040,6 +2090,17 @@ hipError_t wf_launch_tea(const WfParams &P, uint32_t *out, hipStream_t s)
     const size_t npix = (size_t)P.tw * P.th;
     if (npix == 0) return hipSuccess;
     hipLaunchKernelGGL(k_wf_tea, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, s, P, out);
+    return hipGetLastError();
+}
+
+hipError_t wf_launch_tile_classes(const WfParams &P, uint32_t *out, hipStream_t s)
+{
+    const size_t n_tiles = (size_t)P.tiles_x * P.tiles_y;
+    if (n_tiles == 0) return hipSuccess;
+    if (!out || !P.sc.nodes4q || P.sc.root4 < 0 || P.sc.root4 == kNoNode) return hipErrorInvalidValue;
+    const hipError_t e = hipMemsetAsync(out, 0, ((n_tiles + 15) / 16) * sizeof(uint32_t), s);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_wf_tile_classes, dim3((unsigned)n_tiles), dim3(64), 0, s, P, out);
     return hipGetLastError();
 }
 

@@ -82,6 +82,7 @@ static int wf_ensure(crt_ctx *c, size_t P, size_t staging_elems, size_t list_ele
     for (uint32_t b = 0; b < ring; b++)
         CRT_ENSURE(c, c->w_staging[b], staging_elems);
     CRT_ENSURE(c, c->w_tea, (size_t)c->tw * c->th);
+    CRT_ENSURE(c, c->w_tile_cls, ((size_t)((c->tw + 7u) / 8u) * ((c->th + 7u) / 8u) + 15u) / 16u);
     if (!c->wf_host_ready) {
         if (!c->w_wq.p) {
             HIPCHK(c, c->w_wq.alloc(kWfRing));
@@ -801,6 +802,10 @@ int wf_trace_batch(crt_ctx *c, uint32_t n, const AsBatch *as)
             W.overflow_lanes = (uint32_t)c->num_cu * wf_waves(o) * 64u;
             W.stack_overflow = c->w_overflow.p + (size_t)p * W.overflow_lanes * wf_overflow_levels(c);
             W.trace_form = (uint32_t)c->wf_trace_form;
+            // the tile classes: where k_wf_gen takes its CULL form.  They are this run's: every call that
+            // changes what they depend on (camera, frame, tile rectangle and row mapping, the tree) ends the run first.
+            W.tile_cls = (!as && c->wf_cull_classes && wf_gen_culls(W)) ? c->w_tile_cls.p : nullptr;
+            W.cls_miss_zero = c->cie_zero ? 1u : 0u;
             if (!c->pipe_stream[p]) {
                 // Streams beyond the hardware queues (4 by default) share one, and two pipes sharing a queue do not
                 // overlap at all (measured: 95 instead of 77 ms per S2 frame when the caller's framework had taken
@@ -819,6 +824,7 @@ int wf_trace_batch(crt_ctx *c, uint32_t n, const AsBatch *as)
         // resolves).  The pipes run on their own streams.
         HIPCHK(c, wf_launch_init(r.W[0], c->stream));
         HIPCHK(c, wf_launch_tea(r.W[0], c->w_tea.p, c->stream));          // per-pixel RNG seed words of this tile
+        if (r.W[0].tile_cls) { HIPCHK(c, wf_launch_tile_classes(r.W[0], c->w_tile_cls.p, c->stream)); c->tile_cls_setups++; }
         HIPCHK(c, hipEventRecord(c->ev_fork, c->stream));
         for (int p = 0; p < r.K; p++) {
             HIPCHK(c, hipStreamWaitEvent(r.stream[p], c->ev_fork, 0));

@@ -542,6 +542,25 @@ class Renderer:
         self._chk(self._lib.crt_debug_gen_culled(self._h, C.byref(n)))
         return int(n.value)
 
+    def tile_classes(self, host: bool = False) -> np.ndarray:
+        """The class of every 8x8 tile of the tile rectangle, (tiles_y, tiles_x) uint8: 1 = its camera rays miss the
+        tree's root boxes for every sample, 2 = they all enter one, 0 = it depends on the sample (option
+        "wf_cull_classes").  From the device kernel (crt_debug_tile_classes) or, with host=True, from the same definition
+        evaluated on the CPU (crt_debug_tile_classes_host).  A sync point."""
+        t = np.zeros(4, np.uint32)
+        self._chk(self._lib.crt_tile(self._h, t.ctypes.data))
+        ty, tx = (int(t[3]) + 7) // 8, (int(t[2]) + 7) // 8
+        out = np.zeros((ty, tx), np.uint8)
+        fn = self._lib.crt_debug_tile_classes_host if host else self._lib.crt_debug_tile_classes
+        self._chk(fn(self._h, out.ctypes.data, out.size))
+        return out
+
+    def tile_class_setups(self) -> int:
+        """Run set-ups of this context that launched the tile classifier so far (crt_debug_tile_class_setups)."""
+        n = C.c_uint64()
+        self._chk(self._lib.crt_debug_tile_class_setups(self._h, C.byref(n)))
+        return int(n.value)
+
     def debug_math(self, fn: int, a, b=None) -> np.ndarray:
         a = np.ascontiguousarray(a, np.float32)
         b = np.ascontiguousarray(b if b is not None else np.zeros_like(a), np.float32)

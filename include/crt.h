@@ -522,7 +522,10 @@ int crt_last_kernel_ms(crt_ctx *ctx, float *ms, uint32_t *launches);
  * "quantize", "wf_width" (4 | 8: node width of the wavefront traversal; at crt_build_accel);
  * "wf_trace_form" (2: ray ring + primitive tasks, default; 1: the first traversal kernel); "wf_cull_miss" (1, default:
  * work chunks whose camera rays all miss the tree's root boxes are finished where they are generated and take no path
- * slot; 0: every camera ray goes through the pool; same image and counters either way); "frame_ring" = F (keep the
+ * slot; 0: every camera ray goes through the pool; same image and counters either way); "wf_cull_classes" (1, default:
+ * where "wf_cull_miss" acts, the tiles whose camera rays miss, or enter, the root's boxes for EVERY sample are classified
+ * once per run, and their chunks skip the per-sample test -- and, where they miss, the draws; 0: every chunk is tested
+ * per sample; same image, counters and launches either way); "frame_ring" = F (keep the
  * rgba8 frame of each of the last F samples for crt_read_sample_rgba8; 0 = off);
  * "temporal_motion" (0 | 1, anything else is CRT_EINVAL: 1 keeps the history of crt_denoise_temporal across
  * crt_update_primitives, see "Temporal reuse"; costs 80 bytes per primitive on the device once an edit has happened);
@@ -601,6 +604,20 @@ int crt_debug_probes(crt_ctx *ctx, uint64_t out[8]);
  * the tree's root boxes, by whole 8x8 tiles of one sample (option "wf_cull_miss").  Counted with and without
  * crt_enable_counters.  A sync point; work in flight at a crt_reset_counters may count on either side of it. */
 int crt_debug_gen_culled(crt_ctx *ctx, uint64_t *out);
+/* Test hooks: the class of every 8x8 tile of the tile rectangle (row-major, n_tiles = ceil(tw / 8) * ceil(th / 8) bytes;
+ * option "wf_cull_classes"): 1 = the camera rays of every pixel of the tile miss the root's four child
+ * boxes for every sample, 2 = they all enter one, 0 = it depends on the sample (or nothing could be shown).
+ * crt_debug_tile_classes runs the kernel a run's set-up runs, on the context's current camera, tile rectangle and root node
+ * (the inputs of the next run, or of the one this call ends) and copies its table; crt_debug_tile_classes_host evaluates
+ * the same definition (csrc/crt_tile_class.h) on the CPU over the same inputs, the root node read back from the device.
+ * The two agree exactly.  Sync points; they only read.  CRT_ESTATE without a scene or tree, with a stale tree, and where
+ * the wavefront kernels walk no quantised 4-wide tree with an inner root; CRT_EINVAL for another n_tiles. */
+int crt_debug_tile_classes(crt_ctx *ctx, uint8_t *out, size_t n_tiles);
+int crt_debug_tile_classes_host(crt_ctx *ctx, uint8_t *out, size_t n_tiles);
+/* Test hook: how many run set-ups of this context have launched the tile classifier so far (the two reads above do not
+ * count).  It stays where it is wherever the classes do nothing: "wf_cull_classes" or "wf_cull_miss" 0, adaptive batches,
+ * the 8-wide or unquantised tree, four primitives or fewer.  No sync, nothing is finished. */
+int crt_debug_tile_class_setups(crt_ctx *ctx, uint64_t *out);
 
 #ifdef __cplusplus
 }
