@@ -245,9 +245,12 @@ __device__ __forceinline__ ShadowOut light_sample(const WfParams &P, const Light
         hit_test_rec<false>(L.A, L.B, L.C, L.D, S.hit_pad, L.slot, pos, ldir, b_index, 0.001f, t_l, l_index, l_slot);
         if (COUNT) cn.prims++;
     }
-    // cos_theta == 0 (the light sample is behind the surface): le = spec*0 is exactly 0, so the
-    // NEE term (:400) is exactly +0 whatever the visibility -- adding it changes nothing, and
-    // the shadow ray need not be walked (weight and pdf are finite: abs_cos >= 1e-5, :366).
+    // cos_theta == 0 (the light sample is behind the surface): le = spec*0 is exactly 0, and with a finite weight and
+    // pdf (abs_cos >= 1e-5, :366) the NEE term (:400) is exactly +0 whatever the visibility -- adding it changes
+    // nothing, and the shadow ray need not be walked.  The term itself decides that, below: a light of area 0 (the
+    // record of a sphere light: data3 = 0, so 1/area = inf) makes weight and term NaN whatever cos_theta is, and the
+    // reference adds that NaN wherever the light is visible -- also from a point that faces away from the light and
+    // sees it through its own, excluded, primitive.
     const float cos_theta = max_(0.0f, dot(nrm, ldir));
     if (!sh_finite) {
         // A non-finite shadow ray (the light sample coincides with the hit point, or a light record
@@ -265,21 +268,24 @@ __device__ __forceinline__ ShadowOut light_sample(const WfParams &P, const Light
             radiance = radiance + f4{qn, qn, qn, qn};
             rad_dirty = true;
         }
-    } else if (l_slot != kNoHit && cos_theta > 0.0f) {
-        if (COUNT) cn.hits++;
+    } else if (l_slot != kNoHit) {
         const f4 nee = nee_term(S, L, pos, ldir, t_l, cos_theta, sample_spectrum(S, f_bits(L.L0.w), wl));
         f4 c = (brdf * nee) * beta;          // added to radiance iff the light is visible
+        const bool zero = c.x == 0.0f && c.y == 0.0f && c.z == 0.0f && c.w == 0.0f;     // (false for a NaN)
+        if (cos_theta > 0.0f || !zero) {
+            if (COUNT) cn.hits++;
 #ifndef CRT_WHATIF_NO_NEE
-        stnt(&P.nee[slot], float4{c.x, c.y, c.z, c.w});
+            stnt(&P.nee[slot], float4{c.x, c.y, c.z, c.w});
 #else
-        if (c.x == 12345.678f) stnt(&P.nee[slot], float4{c.x, c.y, c.z, c.w});
+            if (c.x == 12345.678f) stnt(&P.nee[slot], float4{c.x, c.y, c.z, c.w});
 #endif
-        if (FINISH) {                        // (k_wf_finish traces from the slot arrays; the pool's
-            P.sh_d[slot] = float4{ldir.x, ldir.y, ldir.z, t_l};   //  traversal kernel from the ray records)
-            P.vis[slot] = include;
+            if (FINISH) {                        // (k_wf_finish traces from the slot arrays; the pool's
+                P.sh_d[slot] = float4{ldir.x, ldir.y, ldir.z, t_l};   //  traversal kernel from the ray records)
+                P.vis[slot] = include;
+            }
+            out = ShadowOut{true, ldir, t_l, include, l_slot};
+            if (COUNT) cn.walk++;
         }
-        out = ShadowOut{true, ldir, t_l, include, l_slot};
-        if (COUNT) cn.walk++;
     }
     return out;
 }
