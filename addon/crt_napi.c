@@ -346,6 +346,24 @@ static napi_value js_accel_stats(napi_env env, napi_callback_info info)
     return u64_array(env, c, 8);
 }
 
+/* accelQuality(h) -> 12 numbers, as crt_accel_quality lays them out (NaN where a value is absent). */
+static napi_value js_accel_quality(napi_env env, napi_callback_info info)
+{
+    ARGS(1)
+    crt_ctx *ctx = get_ctx(env, argv[0]);
+    if (!ctx) return NULL;
+    double q[12];
+    CRT_CHECK(env, ctx, "crt_accel_quality", crt_accel_quality(ctx, q));
+    napi_value arr;
+    NAPI_OK(env, napi_create_array_with_length(env, 12, &arr));
+    for (uint32_t i = 0; i < 12; i++) {
+        napi_value v;
+        NAPI_OK(env, napi_create_double(env, q[i], &v));
+        NAPI_OK(env, napi_set_element(env, arr, i, v));
+    }
+    return arr;
+}
+
 static napi_value js_last_trace_ms(napi_env env, napi_callback_info info)
 {
     ARGS(1)
@@ -1299,7 +1317,7 @@ static napi_value init(napi_env env, napi_value exports)
         {"trace", js_trace}, {"sync", js_sync}, {"sampleCount", js_sample_count}, {"tile", js_tile},
         {"readAccum", js_read_accum}, {"readRgba8", js_read_rgba8}, {"writeAccum", js_write_accum},
         {"enableCounters", js_enable_counters}, {"resetCounters", js_reset_counters},
-        {"counters", js_counters}, {"accelStats", js_accel_stats}, {"lastTraceMs", js_last_trace_ms},
+        {"counters", js_counters}, {"accelStats", js_accel_stats}, {"accelQuality", js_accel_quality}, {"lastTraceMs", js_last_trace_ms},
         {"setOption", js_set_option}, {"abiVersion", js_abi_version},
         {"traceAsync", js_trace_async}, {"syncAsync", js_sync_async},
         {"readRgba8Async", js_read_rgba8_async}, {"readAccumAsync", js_read_accum_async},

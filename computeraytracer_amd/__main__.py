@@ -1,4 +1,4 @@
-"""python -m computeraytracer_amd [--scene file.json] [--width W --height H] [--spp N] [--out image.png] [--denoise K] [--orbit N [--temporal [--variance] [--animate | --animate-device]]]
+"""python -m computeraytracer_amd [--scene file.json] [--width W --height H] [--spp N] [--out image.png] [--denoise K] [--orbit N [--temporal [--variance] [--animate | --animate-device [--rebuild-pct P]]]]
                                 [--adaptive THRESHOLD [--adaptive-step N] [--counts-out counts.png]]"""
 import argparse
 import json
@@ -37,6 +37,10 @@ def main():
                     help="with --orbit N --denoise K --temporal: --animate's motion without uploading records: before frame "
                          "k > 0 one transform_primitives call translates every sphere by (0, up(k) - up(k - 1), 0) on the device, "
                          "up(k) = 0.5 radius sin(2 pi k / 16) in float32 with the radius of frame 0 (then refit_accel)")
+    ap.add_argument("--rebuild-pct", type=int, default=None, metavar="P",
+                    help="with --animate-device: option refit_rebuild_pct = P (100..100000): refit_accel rebuilds the tree once its "
+                         "surface-area cost has passed P percent of what it was when built (accel_quality); the refits and the "
+                         "rebuilds are printed at the end")
     ap.add_argument("--adaptive", type=float, default=None, metavar="THRESHOLD",
                     help="adaptive sampling (crt_trace_adaptive): rounds of --adaptive-step samples for the 8x8 tiles whose "
                          "error is above THRESHOLD, --spp samples at most, until every tile is done")
@@ -55,6 +59,8 @@ def main():
         ap.error("--animate goes with --orbit N --denoise K --temporal")
     if args.animate_device and (not args.temporal or args.animate):
         ap.error("--animate-device goes with --orbit N --denoise K --temporal, and not with --animate")
+    if args.rebuild_pct is not None and not args.animate_device:
+        ap.error("--rebuild-pct goes with --animate-device")
     if args.adaptive is not None and (args.orbit is not None or args.checkpoint):
         ap.error("--adaptive goes with neither --orbit nor --checkpoint")
     if (args.counts_out or args.adaptive_min is not None) and args.adaptive is None:
@@ -73,6 +79,9 @@ def main():
                 import numpy as np
                 r.set_option("temporal_motion", 1)
                 spheres = [int(i) for i in (ps.primitives["category"] == scene.CATEGORY["sphere"]).nonzero()[0]]
+            refits = 0
+            if args.rebuild_pct is not None:
+                r.set_option("refit_rebuild_pct", args.rebuild_pct)
             for k, cam in enumerate(scene.orbit_cameras(ps.camera, args.orbit)):
                 if args.animate:
                     for i in spheres:
@@ -87,6 +96,7 @@ def main():
                         up0, up1 = (np.float32(0.5 * rad * math.sin(2.0 * math.pi * j / 16.0)) for j in (k - 1, k))
                         ops.append((i, 1, [1, 0, 0, 0, 0, 1, 0, np.float32(up1 - up0), 0, 0, 1, 0]))
                     r.transform_primitives(ops).refit_accel()
+                    refits += 1
                 r.set_camera(cam)
                 if args.temporal:
                     r.set_sample_offset(k * args.spp)
@@ -109,6 +119,10 @@ def main():
                 info["animate"] = True
             if args.animate_device:
                 info["animate_device"] = True
+            if args.rebuild_pct is not None:
+                info["rebuild_pct"] = args.rebuild_pct
+                info["refits"] = refits                            # refit_accel calls, of which the policy turned ...
+                info["rebuilds"] = r.accel_quality()["rebuilds"]   # ... this many into rebuilds
             print(json.dumps(info))
             return
         if args.adaptive is not None:

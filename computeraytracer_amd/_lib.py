@@ -81,6 +81,7 @@ SIGNATURES = {
     "crt_read_primitives": (C.c_int, [_P, C.c_uint32, C.c_uint32, _P]),
     "crt_update_lights": (C.c_int, [_P, C.c_uint32, C.c_uint32, _P]),
     "crt_refit_accel": (C.c_int, [_P, _P]),
+    "crt_accel_quality": (C.c_int, [_P, _P]),
     "crt_debug_hit_pad": (C.c_int, [_P, _P]),
     "crt_trace_adaptive": (C.c_int, [_P, _P, _P]),
     "crt_read_adaptive": (C.c_int, [_P, _P, _P]),

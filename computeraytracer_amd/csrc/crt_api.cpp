@@ -761,7 +761,12 @@ int crt_set_option(crt_ctx *c, const char *name, int64_t value)
         c->ploc.radius = (uint32_t)value;
         return CRT_OK;
     }
-    if (!std::strcmp(name, "debug_ploc_max_depth")) {        // test hooks: a PLOC build past these is abandoned for the LBVH
+    if (!std::strcmp(name, "refit_rebuild_pct")) {           // crt_refit_accel's rebuild policy (include/crt.h crt_accel_quality)
+        if (value != 0 && (value < 100 || value > 100000)) return fail(c, CRT_EINVAL, "crt_set_option: refit_rebuild_pct is 0 (off) or 100..100000");
+        c->refit_rebuild_pct = (int)value;
+        return CRT_OK;
+    }
+    if (!std::strcmp(name, "debug_ploc_max_depth")) {       // test hooks: a PLOC build past these is abandoned for the LBVH
         if (value < 1 || value > 62) return fail(c, CRT_EINVAL, "crt_set_option: debug_ploc_max_depth is 1..62");
         c->ploc.max_depth = (uint32_t)value;
         return CRT_OK;

@@ -286,6 +286,14 @@ struct crt_ctx {
     bool prims_moved = false;       // crt_transform_primitives moved records on the device: the geometry of `prims` is out of date
                                     // (refresh_prims before anything reads it; category, material, spectra and index never are)
     DevBuf<uint32_t> xf_tab;        // one call's ops table: prefix sums of the counts, then the ops (kept between calls)
+    // tree cost (crt_quality.hip, crt_accel_quality)
+    int refit_rebuild_pct = 0;      // option "refit_rebuild_pct": crt_refit_accel rebuilds once the walked tree's cost passes this share of q_built (0 = never)
+    bool q_built_ok = false;        // q_built belongs to the current tree (taken before its first refit, or by the first crt_accel_quality)
+    double q_built[4] = {0, 0, 0, 0};   // boxes2 prims2 boxes4 prims4 of the tree as it was built
+    uint64_t refits = 0;            // refits since the tree was built
+    uint64_t policy_rebuilds = 0;   // rebuilds "refit_rebuild_pct" has made since crt_create
+    DevBuf<double2> q_part;         // one pair per block of the node kernels: the BVH2's, then the 4-wide tree's
+    DevBuf<double> q_out;           // per tree 4 doubles: boxes, prims, A(root), -
 
     // adaptive sampling (crt_adaptive.hip): allocated by the first crt_trace_adaptive, released with the tile
     bool as_on = false;             // the adaptive state: per-tile counts instead of `sample` (left by everything that zeroes it)

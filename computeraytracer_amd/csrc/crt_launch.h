@@ -1,4 +1,4 @@
-// crt_launch.h -- every host entry into the device code, declared once: the launchers of the seven .hip files, the GPU tree
+// crt_launch.h -- every host entry into the device code, declared once: the launchers of the eight .hip files, the GPU tree
 // builders and the level lists of the refit.  The .hip file that defines one and every host unit that calls one include
 // this header.  (Parameter structs: crt_device.h.)
 #pragma once
@@ -70,6 +70,10 @@ hipError_t refit_launch_wide(const float4 *prim, float pad, const int *list, con
                              bool quantised, const uint32_t *nch, float *fb, hipStream_t s);
 hipError_t refit_launch_quant4(const float *fb, const uint32_t *nch, uint32_t n4, uint4 *nodes4q, const double base[3], const double scale[3],
                                hipStream_t s);
+
+// crt_quality.hip
+hipError_t quality_launch(int layout, const void *nodes, uint32_t n, uint32_t root, const float base[3], const float scale[3],
+                          double2 *partial, double *out, hipStream_t s);
 
 // crt_denoise.hip
 hipError_t dn_launch_gbuffer(const DevScene &S, uint32_t x0, uint32_t y0, uint32_t tw, uint32_t th, float4 *gbuf, uint32_t *key,

@@ -343,6 +343,8 @@ uint32_t wf_overflow_levels(const crt_ctx *c)
 int build_tree(crt_ctx *c, int mode)
 {
     c->rf_ready = false;
+    c->q_built_ok = false;
+    c->refits = 0;
     c->wf_depth = 0;
     int rc = upload_geometry(c, mode);
     if (rc == CRT_OK && mode == CRT_ACCEL_BVH2) {
@@ -383,6 +385,62 @@ static int edit_end(crt_ctx *c)
     return zero_state(c);
 }
 
+// The cost of the trees as they lie on the device (include/crt.h crt_accel_quality; crt_quality.hip): q = boxes2 prims2
+// boxes4 prims4.  Zeros without an inner node; the 4-wide pair is that of the tree the wavefront kernels walk (the
+// quantised one where there is one), NaN where they walk the 8-wide tree.  Two launches per tree, one readback, a sync.
+// walked_only: the BVH2's pair is left 0 where there is a 4-wide tree (what the policy of crt_refit_accel compares).
+// The 4-wide tree whose cost is reported and compared: 2 = the quantised one, 1 = the float one (a host build without
+// quantisation), 0 = none (no inner node, or the wavefront kernels walk the 8-wide tree).
+static int quality_wide_layout(const crt_ctx *c)
+{
+    const uint32_t n4 = c->bvh4.n_inner;
+    if (c->accel_mode != CRT_ACCEL_BVH2 || n4 == 0 || c->bvh8q.ok) return 0;
+    if (c->sc.nodes4q != nullptr) return 2;
+    return c->bvh4.nodes.size() >= (size_t)n4 * kNode4Floats ? 1 : 0;
+}
+
+static int tree_quality(crt_ctx *c, double q[4], bool walked_only = false)
+{
+    q[0] = q[1] = q[2] = q[3] = 0.0;
+    const uint32_t n2 = c->bvh.n_inner, n4 = c->bvh4.n_inner;
+    if (c->accel_mode != CRT_ACCEL_BVH2 || n2 == 0 || c->sc.root < 0) return CRT_OK;
+    const int layout4 = quality_wide_layout(c);
+    const bool wide = layout4 != 0, quant = layout4 == 2;
+    const size_t nb2 = (n2 + 255u) / 256u, nb4 = wide ? (n4 + 255u) / 256u : 0;
+    CRT_ENSURE(c, c->q_part, nb2 + nb4);
+    CRT_ENSURE(c, c->q_out, 8);
+    HIPCHK(c, hipMemsetAsync(c->q_out.p, 0, 8 * sizeof(double), c->stream));
+    if (!(walked_only && wide))
+        HIPCHK(c, quality_launch(0, c->d_nodes.p, n2, (uint32_t)c->sc.root, c->sc.qbase, c->sc.qscale, c->q_part.p, c->q_out.p, c->stream));
+    if (wide)
+        HIPCHK(c, quality_launch(quant ? 2 : 1, quant ? (const void *)c->d_nodes4q.p : (const void *)c->d_nodes4.p, n4, (uint32_t)c->sc.root4,
+                                 c->sc.qbase, c->sc.qscale, c->q_part.p + nb2, c->q_out.p + 4, c->stream));
+    double h[8];
+    HIPCHK(c, hipMemcpyAsync(h, c->q_out.p, sizeof h, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    q[0] = h[0]; q[1] = h[1];
+    q[2] = c->bvh8q.ok ? (double)NAN : h[4]; q[3] = c->bvh8q.ok ? (double)NAN : h[5];
+    return CRT_OK;
+}
+
+// The as-built values: from the untouched tree, at the first refit's set-up or the first crt_accel_quality after a build.
+static int quality_as_built(crt_ctx *c)
+{
+    if (c->q_built_ok) return CRT_OK;
+    CRT_TRY(tree_quality(c, c->q_built));
+    c->q_built_ok = true;
+    return CRT_OK;
+}
+
+// What option "refit_rebuild_pct" compares: boxes + prims of the walked tree -- the 4-wide one where there is one
+// (quality_wide_layout, the predicate tree_quality computes by), else the BVH2.  NaN under the 8-wide walk, whose refit is
+// a rebuild before the policy is asked.
+static double walked_cost(const crt_ctx *c, const double q[4])
+{
+    if (c->bvh8q.ok) return (double)NAN;
+    return quality_wide_layout(c) ? q[2] + q[3] : q[0] + q[1];
+}
+
 // Recompute every box of the current tree from the current primitives and hit_pad, its topology kept (BVH2, and the
 // 4-wide tree: float boxes, quantised planes on a re-derived grid).  Rebuilt instead, with the builder that made the
 // tree, where a refit cannot serve: an 8-wide tree, or refitted boxes that quantize_bvh4's rule refuses.  The host
@@ -404,7 +462,8 @@ static int refit_tree(crt_ctx *c, bool *rebuilt)
     const bool wide_float = n4 > 0 && c->bvh4.nodes.size() >= (size_t)n4 * kNode4Floats;   // the host build's float 4-wide tree
     const bool wide = quant || wide_float;
     const void *refs4 = quant ? (const void *)c->d_nodes4q.p : (const void *)c->d_nodes4.p;
-    if (!c->rf_ready) {                                  // once per tree: the level lists
+    if (!c->rf_ready) {                                  // once per tree: the cost of the tree as built, the level lists
+        CRT_TRY(quality_as_built(c));
         HIPCHK(c, c->rf_cnt.alloc(1));
         HIPCHK(c, c->rf_lv2.alloc(n2));
         HIPCHK(c, refit_levels(c->d_nodes.p, 2, false, c->sc.root, n2, c->rf_lv2.p, c->rf_cnt.p, nullptr, c->rf_off2, c->stream));
@@ -456,6 +515,7 @@ static int refit_tree(crt_ctx *c, bool *rebuilt)
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->tree_pad = pad;
     c->accel_stale = false;
+    c->refits++;
     return CRT_OK;
 }
 
@@ -644,8 +704,39 @@ int crt_refit_accel(crt_ctx *c, int *rebuilt)
     CRT_TRY(quiesce(c, true));
     bool rb = false;
     CRT_TRY(refit_tree(c, &rb));
+    if (!rb && c->refit_rebuild_pct && c->q_built_ok) {          // (no as-built values: no tree with an inner node)
+        double q[4];
+        CRT_TRY(tree_quality(c, q, true));
+        const double now = walked_cost(c, q), built = walked_cost(c, c->q_built);
+        if (std::isfinite(now) && std::isfinite(built) && now > built * (double)c->refit_rebuild_pct / 100.0) {
+            rb = true;                                           // the refitted tree has decayed: a fresh one, by the builder that made it
+            c->accel_mode = -1;
+            CRT_TRY(build_tree(c, CRT_ACCEL_BVH2));
+            CRT_TRY(quality_as_built(c));
+            c->policy_rebuilds++;
+        }
+    }
     if (rebuilt) *rebuilt = rb ? 1 : 0;
     return edit_end(c);
+}
+
+int crt_accel_quality(crt_ctx *c, double out[12])
+{
+    if (!c || !out) return CRT_EINVAL;
+    if (!c->have_scene || c->accel_mode < 0) return fail(c, CRT_ESTATE, "crt_accel_quality: scene + accel required");
+    CRT_TRY(quiesce(c, true));
+    if (!c->q_built_ok) {                                        // no refit since the build: the tree is as it was built
+        CRT_TRY(quality_as_built(c));
+        for (int k = 0; k < 4; k++) out[k] = c->q_built[k];
+    } else {
+        CRT_TRY(tree_quality(c, out));
+    }
+    for (int k = 0; k < 4; k++) out[4 + k] = c->q_built[k];
+    out[8] = (double)c->refits;
+    out[9] = (double)c->policy_rebuilds;
+    out[10] = c->bvh8q.ok ? 0.0 : 1.0;
+    out[11] = 0.0;
+    return CRT_OK;
 }
 
 }  // extern "C"

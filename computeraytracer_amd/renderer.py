@@ -147,6 +147,21 @@ class Renderer:
         self._chk(self._lib.crt_refit_accel(self._h, C.byref(rebuilt)))
         return bool(rebuilt.value)
 
+    def accel_quality(self) -> dict:
+        """The surface-area cost of the trees as they lie on the device (crt_accel_quality): now = (boxes2, prims2,
+        boxes4, prims4), built = the same for the tree before any refit, q_now / q_built = boxes + prims of the tree the
+        wavefront kernels walk (what option "refit_rebuild_pct" compares), refits since the build, the policy's rebuilds
+        since the context was created, and has4 (False: the 8-wide tree is walked; boxes4 / prims4, q_now and q_built are
+        NaN, and the policy never acts).  A sync point; works on a stale tree; reads only."""
+        out = np.zeros(12, np.float64)
+        self._chk(self._lib.crt_accel_quality(self._h, out.ctypes.data))
+        names = ("boxes2", "prims2", "boxes4", "prims4")
+        now, built = dict(zip(names, map(float, out[0:4]))), dict(zip(names, map(float, out[4:8])))
+        def q(d):                         # (has4 False: NaN, as the library's own comparison, which then takes no action)
+            return d["boxes4"] + d["prims4"]
+        return dict(now=now, built=built, q_now=q(now), q_built=q(built), refits=int(out[8]), rebuilds=int(out[9]),
+                    has4=bool(out[10]), raw=out)
+
     @property
     def debug_hit_pad(self) -> float:
         v = C.c_float()

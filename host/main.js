@@ -109,6 +109,10 @@ function Main(options = {}) {
     enableCounters: (on) => a.enableCounters(device, !!on),
     lastTraceMs: () => a.lastTraceMs(device),
     accelStats: () => a.accelStats(device),
+    // the surface-area cost of the trees (include/crt.h crt_accel_quality): 12 numbers -- [0..3] boxes2, prims2, boxes4,
+    // prims4 now, [4..7] as built, [8] refits since the build, [9] rebuilds that setOption('refit_rebuild_pct', P) has made
+    // inside refitAccel, [10] 1 = the 4-wide values are present (else NaN)
+    accelQuality: () => a.accelQuality(device),
     destroy: () => a.destroy(device),
   };
 }

@@ -308,8 +308,41 @@ int crt_update_lights(crt_ctx *ctx, uint32_t first, uint32_t count, const void *
 /* Recompute every box of the tree (BVH2 and 4-wide, float and quantised; the quantisation grid re-derived) from the
  * current primitives, topology kept.  Rebuilds with the builder that made the tree instead, and sets *rebuilt = 1
  * (rebuilt may be NULL), for an 8-wide tree (option "wf_width" = 8) or when the refitted boxes cannot be quantised.
- * A no-op on the tree without one.  Clears the stale state, as crt_build_accel does. */
+ * A no-op on the tree without one.  Clears the stale state, as crt_build_accel does.
+ * Option "refit_rebuild_pct" = P (below, with crt_accel_quality) also rebuilds once the refitted tree has decayed. */
 int crt_refit_accel(crt_ctx *ctx, int *rebuilt);
+/* The surface-area cost of the trees as they lie on the device, so that a caller who refits frame after frame can tell
+ * when a refitted tree has become worse than a fresh one.  All arithmetic is binary64 on box values
+ * converted from what the device holds.  A(box) = dx*dy + dy*dz + dz*dx with d = hi - lo, summed in that order.
+ *   BVH2 (16 floats per node: c0.lo c0.hi c1.lo c1.hi ref0 ref1): the box of inner node i is the union of its two child
+ *     boxes, the root box is the root node's;  boxes2 = sum over inner nodes of 2 A(box_i) / A(root),
+ *     prims2 = sum over leaf children of count A(child box) / A(root)  (a leaf is ref < 0, ~ref = first << 3 | count - 1).
+ *   The 4-wide tree the wavefront kernels walk, float (32 floats per node) or quantised (16 dwords per node; where both
+ *     exist, the quantised one): an empty slot has ref == 0 and is skipped; a quantised plane is
+ *     (double)base[a] + (double)q * (double)scale[a] (the product is exact, so the value is one rounded sum); the box of
+ *     node i is the union of its nch_i live child boxes;  boxes4 = sum over nodes of nch_i A(box_i) / A(root),
+ *     prims4 = sum over leaf children of count A(child box) / A(root).
+ * A union takes the smaller lo and the larger hi per axis (fmin / fmax).  The sums run over the dense node arrays in a
+ * fixed order without atomics (two calls on the same tree return the same bits) and are divided by A(root) once, at the
+ * end; boxes2 is twice the SAH cost of DESIGN.md 3.  A tree with no inner node (one leaf) and CRT_ACCEL_NONE: all four
+ * values are 0.  Where the wavefront kernels walk the 8-wide tree (option "wf_width" = 8, where a refit already
+ * rebuilds) boxes4 and prims4 are NaN.  Non-finite boxes give non-finite values, reported as they come.
+ *   out[0] boxes2  [1] prims2  [2] boxes4  [3] prims4 -- the tree as it lies on the device now
+ *   out[4..7] the same four for the tree as it was built (before any refit)
+ *   out[8] refits since the tree was built    [9] rebuilds "refit_rebuild_pct" has made since crt_create
+ *   out[10] 1 = [2], [3], [6], [7] are present (0: the 8-wide tree is walked and they are NaN)    [11] 0
+ * The as-built values are taken from the untouched tree by the first refit after a build, or by the first
+ * crt_accel_quality, and kept until the next build (crt_build_accel, an upload, any rebuild by crt_refit_accel);
+ * crt_build_accel itself computes nothing.  A sync point.  It only reads, and it works on a stale tree, whose boxes it
+ * shows as they are (like crt_debug_read_accel).  CRT_ESTATE without a scene or accel structure.
+ * Option "refit_rebuild_pct" = P: 0 (default) = off; 100..100000; anything else is CRT_EINVAL.  With P != 0,
+ * crt_refit_accel, after it has refitted, computes Q = boxes + prims of the walked tree (the 4-wide tree where there is
+ * one, else the BVH2).  If Q_now > Q_built * P / 100, both finite, it rebuilds with the builder that made the tree (the
+ * path of the 8-wide and unquantisable cases), sets *rebuilt = 1, takes the new tree's values as the as-built ones and
+ * adds one to out[9].  A non-finite Q on either side means no action.  The refit inside crt_set_camera does not apply
+ * the policy.  With P = 0 crt_refit_accel launches what it launched before the option existed (the first refit of a
+ * tree also takes the as-built values, once). */
+int crt_accel_quality(crt_ctx *ctx, double out[12]);
 /* Test hook: the hit_pad the kernels use. */
 int crt_debug_hit_pad(crt_ctx *ctx, float *out);
 
@@ -531,6 +564,8 @@ int crt_last_kernel_ms(crt_ctx *ctx, float *ms, uint32_t *launches);
  * crt_update_primitives, see "Temporal reuse"; costs 80 bytes per primitive on the device once an edit has happened);
  * "ploc_radius" (1..32, anything else is CRT_EINVAL; default 8: clusters searched to either side by CRT_ACCEL_PLOC; at
  * crt_build_accel);
+ * "refit_rebuild_pct" (0 = off, default | 100..100000, anything else is CRT_EINVAL: crt_refit_accel rebuilds once the
+ * refitted tree's cost has passed that percentage of its cost as built, see crt_accel_quality);
  * "time_kernels"; "debug_fail_alloc" = k (test hook: the k-th device allocation from now on reports
  * out of memory); "debug_ploc_max_depth" (1..62, default 62) and "debug_ploc_max_rounds" (>= 1, default 256): test
  * hooks, a CRT_ACCEL_PLOC build deeper than the one or unfinished after the other is abandoned and the same call builds

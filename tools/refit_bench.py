@@ -3,7 +3,11 @@ around synchronous calls, warm, median of --reps.
 
   build_lbvh_ms        crt_build_accel(CRT_ACCEL_LBVH)
   build_ploc_ms        crt_build_accel(CRT_ACCEL_PLOC)
-  refit_ms             crt_refit_accel after a crt_update_primitives (the update itself not timed)
+  refit_ms             crt_refit_accel after a crt_update_primitives (the update itself not timed); option
+                       "refit_rebuild_pct" = 0
+  refit_policy_ms      the same with "refit_rebuild_pct" = 100000: the policy computes the tree's cost after every refit
+                       and never fires; policy_added_ms = the difference
+  quality_ms           crt_accel_quality
   update_ms            crt_update_primitives of the moved tenth (records, hit_pad reduction, state reset)
   transform_ms         crt_transform_primitives of the same tenth by the same rigid move, one op (the records never leave
                        the device; forward and inverse alternate so that the geometry stays where it is)
@@ -14,13 +18,28 @@ around synchronous calls, warm, median of --reps.
   step_ms_refit / step_ms_fresh / step_ms_fresh_ploc   ms per --spp step after a rigid move of a contiguous tenth of the
                        primitives, refitted tree against a fresh LBVH / PLOC build of the same buffers (the tree-quality cost)
   edit_total_ms        what one edited frame costs by each route: refit + step, LBVH rebuild + step, PLOC rebuild + step
+  q_built / q_refit / q_fresh   Q = boxes + prims of the walked tree (crt_accel_quality): as built, after the rigid move of
+                       the tenth and the refit, and of the fresh LBVH of the moved buffers; q_ratio = q_refit / q_built is
+                       what "refit_rebuild_pct" compares, q_ratio_fresh = q_refit / q_fresh stands beside
+                       step_ratio = step_ms_refit / step_ms_fresh
 
 --parent DIR: a checkout of the parent commit with its library built.  Its crt_update_primitives of the same tenth is
-measured in child processes (this tool with --update-only --tree DIR) before and after this build's run, in one session:
-parent_update_ms holds both medians, their difference is the run-to-run spread the comparison allows for.
+and its crt_refit_accel after it are measured in child processes (this tool with --update-only --tree DIR) before and
+after this build's run, in one session: parent_update_ms and parent_refit_ms hold both medians, their difference is the
+run-to-run spread the comparison allows for.
 
 Per-kernel times come from a separate run under rocprofv3 --kernel-trace --stats.  Prints one JSON line; --out also
-writes it."""
+writes it.
+
+The kernel times of the tree cost (profiles/quality_kernel_stats.csv) are made in two steps:
+  rocprofv3 --kernel-trace --stats -d DIR -o quality -- python tools/refit_bench.py --policy-loop
+      per scene: an LBVH build, "refit_rebuild_pct" = 100000, ten times crt_update_primitives of the tenth (the records
+      it already holds) + crt_refit_accel, then one crt_accel_quality
+  python tools/refit_bench.py --kernel-stats DIR/quality_results.db --out profiles/quality_kernel_stats.csv
+      from the trace's `kernels` view: the dispatches of k_quality_nodes, k_quality_sum and k_refit_quant4 grouped by
+      (kernel name as the trace spells it, grid threads): calls, mean / min / max of end - start in microseconds.  The
+      grid tells the scenes and trees apart (a thread per node, blocks of 256); k_quality_sum, always one block, is
+      listed under the grid of the k_quality_nodes launch before it, whose pairs it adds."""
 import argparse
 import json
 import os
@@ -72,8 +91,28 @@ def run_scene(name, ps, reps, spp, steps, update_only=False):
             r.update_primitives(first, rec_b if flip[0] else rec_a)
 
         res["update_ms"] = timed(update, reps)
+
+        def refit_after_update():
+            ts = []
+            for _ in range(reps + 3):
+                update()
+                t = time.perf_counter()
+                rebuilt = r.refit_accel()
+                ts.append((time.perf_counter() - t) * 1e3)
+                assert not rebuilt
+            return round(statistics.median(ts[3:]), 4)
+
+        res["refit_ms"] = refit_after_update()
         if update_only:
             return res
+        r.set_option("refit_rebuild_pct", 100000)                        # the cost after every refit; never past 1000 x
+        res["refit_policy_ms"] = refit_after_update()
+        r.set_option("refit_rebuild_pct", 0)
+        res["policy_added_ms"] = round(res["refit_policy_ms"] - res["refit_ms"], 4)
+        res["quality_ms"] = timed(r.accel_quality, reps)
+        if flip[0]:
+            update()                                                     # the uploaded records again, for what follows
+        r.build_accel("lbvh")
         from computeraytracer_amd.scene import transform_ops            # (a parent tree has none: imported past --update-only)
         t3 = np.float64([6.0, 2.0, -4.0])
         fwd = np.concatenate([R, t3[:, None]], 1).astype(np.float32).reshape(12)
@@ -101,15 +140,8 @@ def run_scene(name, ps, reps, spp, steps, update_only=False):
             assert not rebuilt
         res["refit_after_transform_ms"] = round(statistics.median(ts[4:]), 4)
         r.update_primitives(first, rec_a)                                # the uploaded records again, for what follows
+        assert not r.refit_accel()                                       # (a stale tree is not refitted inside set_camera)
         flip[0] = 0
-        ts = []
-        for _ in range(reps + 3):
-            update()
-            t = time.perf_counter()
-            rebuilt = r.refit_accel()
-            ts.append((time.perf_counter() - t) * 1e3)
-            assert not rebuilt
-        res["refit_ms"] = round(statistics.median(ts[3:]), 4)
         res["refit_speedup"] = round(res["build_lbvh_ms"] / res["refit_ms"], 2)
         cam0 = ps.camera.copy()
         look = cam0[4:7].astype(np.float64)
@@ -136,8 +168,13 @@ def run_scene(name, ps, reps, spp, steps, update_only=False):
         res["set_camera_refit_ms"] = timed(cam_far, reps)
         # tree quality: the moved tenth, refitted, against a fresh build of the same buffers
         r.set_camera(cam0)
+        r.update_primitives(first, rec_a)
+        r.build_accel("lbvh")
         r.update_primitives(first, rec_b)
         r.refit_accel()
+        q = r.accel_quality()
+        res["q_built"], res["q_refit"] = q["q_built"], q["q_now"]
+        res["q_ratio"] = round(q["q_now"] / q["q_built"], 4)
 
         def steps_ms():
             r.reset()
@@ -151,6 +188,9 @@ def run_scene(name, ps, reps, spp, steps, update_only=False):
         res["step_ms_refit"] = steps_ms()
         r.build_accel("lbvh")
         res["step_ms_fresh"] = steps_ms()
+        res["q_fresh"] = r.accel_quality()["q_now"]
+        res["q_ratio_fresh"] = round(res["q_refit"] / res["q_fresh"], 4)
+        res["step_ratio"] = round(res["step_ms_refit"] / res["step_ms_fresh"], 4)
         r.build_accel("ploc")
         res["step_ms_fresh_ploc"] = steps_ms()
         res["edit_total_ms"] = {"refit": round(res["refit_ms"] + res["step_ms_refit"], 3),
@@ -162,6 +202,37 @@ def run_scene(name, ps, reps, spp, steps, update_only=False):
     return res
 
 
+def policy_loop(soup_tris):
+    for name, ps in [("s2", atrium250k(1920, 1080))] + ([("soup", soup(soup_tris, 1920, 1080))] if soup_tris else []):
+        n = len(ps.primitives)
+        first, cnt = n // 3, n // 10
+        with Renderer(0) as r:
+            r.upload(ps).build_accel("lbvh")
+            r.set_option("refit_rebuild_pct", 100000)
+            for _ in range(10):
+                r.update_primitives(first, ps.primitives[first:first + cnt])
+                assert not r.refit_accel()
+            print(json.dumps({"scene": name, "accel": r.accel_stats(), "quality": r.accel_quality()["now"]}), flush=True)
+
+
+def kernel_stats(db_path, out):
+    import csv
+    import sqlite3
+    db = sqlite3.connect(db_path)
+    groups, nodes_grid = {}, 0
+    for name, grid, ns in db.execute("select name, grid_x, end - start from kernels where name like '%k_quality_%' or name like '%k_refit_quant4%' order by start"):
+        if "k_quality_nodes" in name:
+            nodes_grid = grid
+        if "k_quality_sum" in name:
+            grid = nodes_grid                                     # one block always: listed under the grid of the launch whose pairs it adds
+        groups.setdefault((name, grid), []).append(ns / 1e3)
+    with (open(out, "w", newline="") if out else sys.stdout) as f:
+        w = csv.writer(f)
+        w.writerow(["kernel", "grid_threads", "calls", "avg_us", "min_us", "max_us"])
+        for (name, grid), us in sorted(groups.items()):
+            w.writerow([name, grid, len(us), round(statistics.mean(us), 3), round(min(us), 3), round(max(us), 3)])
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
@@ -170,9 +241,15 @@ def main():
     ap.add_argument("--soup-tris", type=int, default=10_000_000)
     ap.add_argument("--out", default=None)
     ap.add_argument("--parent", default=None, metavar="DIR", help="a built checkout of the parent commit: its update_ms, before and after")
-    ap.add_argument("--update-only", action="store_true", help="build_lbvh_ms and update_ms only")
+    ap.add_argument("--update-only", action="store_true", help="build_lbvh_ms, update_ms and refit_ms only")
     ap.add_argument("--tree", default=None, metavar="DIR", help="import the package from this checkout instead of the tool's own")
+    ap.add_argument("--policy-loop", action="store_true", help="only the refits with the policy on and one crt_accel_quality: the run to put under rocprofv3")
+    ap.add_argument("--kernel-stats", default=None, metavar="DB", help="reduce that run's rocprofv3 database to the CSV (--out, or stdout)")
     a = ap.parse_args()
+    if a.kernel_stats:
+        return kernel_stats(a.kernel_stats, a.out)
+    if a.policy_loop:
+        return policy_loop(a.soup_tris)
 
     def parent_update():
         import subprocess
@@ -187,6 +264,7 @@ def main():
         after = parent_update()
         for k in out:
             out[k]["parent_update_ms"] = [before[k]["update_ms"], after[k]["update_ms"]]
+            out[k]["parent_refit_ms"] = [before[k]["refit_ms"], after[k]["refit_ms"]]
     line = json.dumps(out)
     print(line)
     if a.out:
