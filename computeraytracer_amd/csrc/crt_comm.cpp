@@ -5,7 +5,8 @@
 // exchange of any kind; SURVEY 8(e) defines this one.
 //
 // Written against the public C ABI only (crt_set_row_bands / crt_set_tile, crt_bind_output, crt_get_stream): a context
-// does not know that it is part of a communicator, it renders its rows into the strip buffers bound here.
+// does not know that it is part of a communicator, it renders its rows into the strip buffers bound here.  Whether it
+// still does is asked of it the same way (crt_device_buffers, crt_image_size, crt_tile: `current` below).
 //
 // Transports behind one interface:
 //   RCCL   one process per GPU (or one thread per GPU): ncclCommInitRank + ncclAllGather.  librccl is loaded on first
@@ -128,6 +129,34 @@ uint32_t rows_of(uint32_t H, uint32_t band, uint32_t parts, uint32_t part)
     return n;
 }
 
+// Does the context still render what crt_comm_partition set up?  crt_upload_scene, crt_set_tile and crt_set_row_bands
+// unbind the strips (and may change W and H), crt_bind_output with other pointers does so by itself: the partition is
+// then STALE.  Asked of the context through the public ABI at every entry, so nothing has to tell the communicator.
+// (The strips stay allocated while stale, so no buffer of the context's own can take their addresses.)
+bool bound_to_strips(crt_ctx *c, const Comm *m)
+{
+    void *a = nullptr, *r = nullptr;
+    return m->partitioned && crt_device_buffers(c, &a, &r) == CRT_OK && a == m->strip_accum && r == m->strip_rgba;
+}
+
+bool current(crt_ctx *c, const Comm *m)
+{
+    if (!bound_to_strips(c, m)) return false;
+    uint32_t wh[2] = {0, 0}, t[4] = {0, 0, 0, 0};
+    if (crt_image_size(c, wh) != CRT_OK || wh[0] != m->W || wh[1] != m->H) return false;
+    return crt_tile(c, t) == CRT_OK && t[2] == m->W && t[3] == m->rows;
+}
+
+// What crt_gather, crt_read_frame_* and crt_frame_device_buffers answer before they touch anything.
+int refuse_unless_current(crt_ctx *c, const Comm *m, const char *who)
+{
+    if (!m || !m->partitioned) return fail(c, CRT_ESTATE, std::string(who) + ": crt_comm_init and crt_comm_partition first");
+    if (!current(c, m))
+        return fail(c, CRT_ESTATE, std::string(who) + ": the partition is stale (crt_upload_scene, crt_set_tile, crt_set_row_bands or "
+                                   "crt_bind_output since): call crt_comm_partition again");
+    return CRT_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -235,7 +264,7 @@ int crt_comm_destroy(crt_ctx *c)
     (void)hipSetDevice(m->device);
     void *st = nullptr;
     if (crt_get_stream(c, &st) == CRT_OK) (void)hipStreamSynchronize((hipStream_t)st);
-    if (m->partitioned) (void)crt_bind_output(c, nullptr, nullptr);
+    if (bound_to_strips(c, m.get())) (void)crt_bind_output(c, nullptr, nullptr);   // (a stale partition: the outputs are the application's)
     free_buffers(*m);
     if (m->nccl) (void)g_rccl.CommDestroy(m->nccl);
     if (m->ev_rgba) (void)hipEventDestroy(m->ev_rgba);
@@ -326,7 +355,7 @@ static int gather_one(crt_ctx *c, Comm *m, bool accum)
 int crt_gather(crt_ctx *c, int what)
 {
     Comm *m = find(c);
-    if (!m || !m->partitioned) return fail(c, CRT_ESTATE, "crt_gather: crt_comm_init and crt_comm_partition first");
+    { int rc = refuse_unless_current(c, m, "crt_gather"); if (rc) return rc; }
     if (!(what & (CRT_GATHER_RGBA8 | CRT_GATHER_ACCUM))) return fail(c, CRT_EINVAL, "crt_gather: nothing to gather");
     CHIP(c, hipSetDevice(m->device));
     if (what & CRT_GATHER_RGBA8) { int rc = gather_one(c, m, false); if (rc) return rc; }
@@ -368,7 +397,7 @@ static int assemble(crt_ctx *c, Comm *m, bool accum, hipStream_t s)
 static int read_frame(crt_ctx *c, void *out, bool accum)
 {
     Comm *m = find(c);
-    if (!m || !m->partitioned) return fail(c, CRT_ESTATE, "crt_read_frame: crt_comm_init and crt_comm_partition first");
+    { int rc = refuse_unless_current(c, m, "crt_read_frame"); if (rc) return rc; }
     if (!out) return CRT_EINVAL;
     CHIP(c, hipSetDevice(m->device));
     void *st = nullptr;
@@ -387,7 +416,7 @@ int crt_read_frame_accum(crt_ctx *c, float *out) { return read_frame(c, out, tru
 int crt_frame_device_buffers(crt_ctx *c, void **accum_dev, void **rgba8_dev)
 {
     Comm *m = find(c);
-    if (!m || !m->partitioned) return fail(c, CRT_ESTATE, "crt_frame_device_buffers: crt_comm_init and crt_comm_partition first");
+    { int rc = refuse_unless_current(c, m, "crt_frame_device_buffers"); if (rc) return rc; }
     CHIP(c, hipSetDevice(m->device));
     void *st = nullptr;
     { int rc = crt_get_stream(c, &st); if (rc) return rc; }
@@ -405,11 +434,11 @@ int crt_comm_info(crt_ctx *c, int out[4])
     return CRT_OK;
 }
 
-// (crt_api.cpp: crt_trace_adaptive refuses a partitioned context)
+// (crt_api.cpp: crt_trace_adaptive refuses a partitioned context; a stale partition is none)
 int crt_internal_comm_partitioned(crt_ctx *c)
 {
     Comm *m = find(c);
-    return m && m->partitioned ? 1 : 0;
+    return m && current(c, m) ? 1 : 0;
 }
 
 }  // extern "C"

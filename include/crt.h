@@ -205,7 +205,17 @@ int crt_image_size(crt_ctx *ctx, uint32_t out[2]);
  * crt_gather is asynchronous and stream-ordered like crt_trace: it ships what the strip holds THEN -- after crt_sync
  * every sample requested so far, in a pipelined loop the latest complete frame (crt_trace's contract for bound outputs).
  * CRT_COMM_LOCAL is the same interface for contexts of ONE process (any devices): strips are exchanged with
- * device-to-device copies, no RCCL; every rank posts its crt_gather before any rank reads the frame. */
+ * device-to-device copies, no RCCL; every rank posts its crt_gather before any rank reads the frame.
+ *
+ * A partition goes STALE when the application calls crt_upload_scene, crt_set_tile or crt_set_row_bands on the context
+ * after crt_comm_partition, or crt_bind_output with other pointers than the communicator's strips (crt_comm_partition's own
+ * use of those calls does not count): the context no longer renders into the strips, and W and H may have changed.  On a
+ * stale partition crt_gather, crt_read_frame_rgba8, crt_read_frame_accum and crt_frame_device_buffers return CRT_ESTATE
+ * ("call crt_comm_partition again"); they enqueue nothing and write nothing to `out`.  The communicator's buffers live until
+ * the next crt_comm_partition or crt_comm_destroy, so a copy a peer has in flight into them stays safe; crt_comm_info
+ * keeps answering; crt_trace_adaptive takes a stale partition for none; a fresh crt_comm_partition (on every rank, if W or
+ * H changed) makes everything work again.  A peer that is still current may post its crt_gather, but the frame of that
+ * gather is never complete (crt_read_frame_*: CRT_ESTATE). */
 #define CRT_COMM_ID_BYTES 128
 enum { CRT_COMM_RCCL = 0, CRT_COMM_LOCAL = 1 };
 enum { CRT_GATHER_RGBA8 = 1, CRT_GATHER_ACCUM = 2 };
