@@ -534,12 +534,12 @@ static int denoise_options(napi_env env, const char *fn, napi_value obj, int hav
 /* The outputs of a filter call on the tile: rgba8 (tw*th*4 bytes) and, where wanted, one float per pixel. */
 typedef struct { size_t px; void *rgba8, *plane; napi_value rgba8_ab, plane_ab; } dn_out;
 
-static int denoise_outputs(napi_env env, crt_ctx *ctx, bool plane, dn_out *o)
+static int outputs_of(napi_env env, crt_ctx *ctx, int frame, bool plane, dn_out *o)
 {
     uint32_t tl[4];
     memset(o, 0, sizeof *o);
-    const int rc = crt_tile(ctx, tl);
-    if (rc != CRT_OK) { throw_crt(env, ctx, rc, "crt_tile"); return 0; }
+    const int rc = frame ? crt_image_size(ctx, tl + 2) : crt_tile(ctx, tl);
+    if (rc != CRT_OK) { throw_crt(env, ctx, rc, frame ? "crt_image_size" : "crt_tile"); return 0; }
     o->px = (size_t)tl[2] * tl[3];
     if (napi_create_arraybuffer(env, o->px * 4, &o->rgba8, &o->rgba8_ab) != napi_ok ||
         (plane && napi_create_arraybuffer(env, o->px * 4, &o->plane, &o->plane_ab) != napi_ok)) {
@@ -548,6 +548,8 @@ static int denoise_outputs(napi_env env, crt_ctx *ctx, bool plane, dn_out *o)
     }
     return 1;
 }
+
+static int denoise_outputs(napi_env env, crt_ctx *ctx, bool plane, dn_out *o) { return outputs_of(env, ctx, 0, plane, o); }
 
 /* ... as the call's result: the Uint8Array, or {rgba8, <name>: Float32Array(tw*th)} where the plane was wanted. */
 static napi_value denoise_result(napi_env env, const dn_out *o, const char *name)
@@ -571,13 +573,20 @@ static napi_value denoise_result(napi_env env, const dn_out *o, const char *name
     crt_ctx *ctx = get_ctx(env, argv[0]);                                                           \
     if (!ctx) return NULL;
 
+static int denoise_plain_options(napi_env env, const char *fn, napi_value opts, int have_opts, crt_denoise_params *p)
+{
+    double it = 5.0, sc = 1.0, sn = 0.5, sx = 0.3;
+    const dn_opt o[] = {{"iterations", &it}, {"sigmaColor", &sc}, {"sigmaNormal", &sn}, {"sigmaPlane", &sx}};
+    if (!denoise_options(env, fn, opts, have_opts, o, 4, NULL, NULL)) return 0;
+    p->iterations = (uint32_t)it; p->sigma_color = (float)sc; p->sigma_normal = (float)sn; p->sigma_plane = (float)sx;
+    return 1;
+}
+
 static napi_value js_denoise(napi_env env, napi_callback_info info)
 {
     DENOISE_ARGS
-    double it = 5.0, sc = 1.0, sn = 0.5, sx = 0.3;
-    const dn_opt o[] = {{"iterations", &it}, {"sigmaColor", &sc}, {"sigmaNormal", &sn}, {"sigmaPlane", &sx}};
-    if (!denoise_options(env, "denoise", argc > 1 ? argv[1] : NULL, argc > 1, o, 4, NULL, NULL)) return NULL;
-    crt_denoise_params p = {(uint32_t)it, (float)sc, (float)sn, (float)sx};
+    crt_denoise_params p;
+    if (!denoise_plain_options(env, "denoise", argc > 1 ? argv[1] : NULL, argc > 1, &p)) return NULL;
     dn_out out;
     if (!denoise_outputs(env, ctx, false, &out)) return NULL;
     CRT_CHECK(env, ctx, "crt_denoise", crt_denoise(ctx, &p, NULL, (uint8_t *)out.rgba8));
@@ -607,6 +616,32 @@ static napi_value js_denoise_adaptive(napi_env env, napi_callback_info info)
     dn_out out;
     if (!denoise_outputs(env, ctx, variance, &out)) return NULL;
     CRT_CHECK(env, ctx, "crt_denoise_adaptive", crt_denoise_adaptive(ctx, &p, NULL, (uint8_t *)out.rgba8, (float *)out.plane));
+    return denoise_result(env, &out, "variance");
+}
+
+/* denoiseFrame(h, {...denoise's options}) and denoiseAdaptiveFrame(h, {...denoiseAdaptive's}): the two filters over the whole
+ * W x H frame of the latest PREVIEW gather, on any rank (include/crt.h "The frame of a partition"); the results as their
+ * per-context forms give them, W*H pixels.  denoiseFrameAsync / denoiseAdaptiveFrameAsync -> Promise of the Uint8Array. */
+static napi_value js_denoise_frame(napi_env env, napi_callback_info info)
+{
+    DENOISE_ARGS
+    crt_denoise_params p;
+    if (!denoise_plain_options(env, "denoiseFrame", argc > 1 ? argv[1] : NULL, argc > 1, &p)) return NULL;
+    dn_out out;
+    if (!outputs_of(env, ctx, 1, false, &out)) return NULL;
+    CRT_CHECK(env, ctx, "crt_denoise_frame", crt_denoise_frame(ctx, &p, NULL, (uint8_t *)out.rgba8));
+    return denoise_result(env, &out, NULL);
+}
+
+static napi_value js_denoise_adaptive_frame(napi_env env, napi_callback_info info)
+{
+    DENOISE_ARGS
+    crt_denoise_adaptive_params p;
+    bool variance = false;
+    if (!denoise_adaptive_options(env, argc > 1 ? argv[1] : NULL, argc > 1, &p, &variance)) return NULL;
+    dn_out out;
+    if (!outputs_of(env, ctx, 1, variance, &out)) return NULL;
+    CRT_CHECK(env, ctx, "crt_denoise_adaptive_frame", crt_denoise_adaptive_frame(ctx, &p, NULL, (uint8_t *)out.rgba8, (float *)out.plane));
     return denoise_result(env, &out, "variance");
 }
 
@@ -917,20 +952,24 @@ static napi_value js_trace_adaptive(napi_env env, napi_callback_info info)
     return v;
 }
 
-static napi_value js_read_adaptive(napi_env env, napi_callback_info info)
+/* readAdaptive(h) -> {counts, errors, tilesX, tilesY} of the context's rectangle; readFrameAdaptive(h): of the whole frame of
+ * the latest PREVIEW gather (include/crt.h "The frame of a partition"). */
+static napi_value read_adaptive(napi_env env, napi_callback_info info, int frame)
 {
     ARGS(1)
     crt_ctx *ctx = get_ctx(env, argv[0]);
     if (!ctx) return NULL;
     uint32_t tl[4];
-    CRT_CHECK(env, ctx, "crt_tile", crt_tile(ctx, tl));
+    if (frame) CRT_CHECK(env, ctx, "crt_image_size", crt_image_size(ctx, tl + 2));
+    else CRT_CHECK(env, ctx, "crt_tile", crt_tile(ctx, tl));
     const uint32_t tx = (tl[2] + 7) / 8, ty = (tl[3] + 7) / 8;
     const size_t nt = (size_t)tx * ty;
     void *dc = NULL, *de = NULL;
     napi_value abc, abe, tc, te, obj, vx, vy;
     NAPI_OK(env, napi_create_arraybuffer(env, nt * 4, &dc, &abc));
     NAPI_OK(env, napi_create_arraybuffer(env, nt * 4, &de, &abe));
-    CRT_CHECK(env, ctx, "crt_read_adaptive", crt_read_adaptive(ctx, (uint32_t *)dc, (float *)de));
+    if (frame) CRT_CHECK(env, ctx, "crt_read_frame_adaptive", crt_read_frame_adaptive(ctx, (uint32_t *)dc, (float *)de));
+    else CRT_CHECK(env, ctx, "crt_read_adaptive", crt_read_adaptive(ctx, (uint32_t *)dc, (float *)de));
     NAPI_OK(env, napi_create_typedarray(env, napi_uint32_array, nt, abc, 0, &tc));
     NAPI_OK(env, napi_create_typedarray(env, napi_float32_array, nt, abe, 0, &te));
     NAPI_OK(env, napi_create_object(env, &obj));
@@ -942,6 +981,8 @@ static napi_value js_read_adaptive(napi_env env, napi_callback_info info)
     NAPI_OK(env, napi_set_named_property(env, obj, "tilesY", vy));
     return obj;
 }
+static napi_value js_read_adaptive(napi_env env, napi_callback_info info) { return read_adaptive(env, info, 0); }
+static napi_value js_read_frame_adaptive(napi_env env, napi_callback_info info) { return read_adaptive(env, info, 1); }
 
 /* ------------------------------------------------------------------ multi-GPU (include/crt.h "Multi-GPU") and composition
  * The reference drives one GPUDevice (src/main.js:8-9); a Node host reaches the tile-partitioned configurations through
@@ -1138,14 +1179,16 @@ static napi_value js_set_stream(napi_env env, napi_callback_info info)
  * fire-and-forget (queue.submit, src/main.js:618-620): a Node display loop must not block its event loop on the
  * GPU either.  Jobs of one context run in call order. */
 enum { JOB_TRACE, JOB_SYNC, JOB_READ_RGBA8, JOB_READ_ACCUM, JOB_GATHER, JOB_READ_FRAME_RGBA8, JOB_READ_FRAME_ACCUM, JOB_READ_SAMPLE_RGBA8,
-       JOB_DENOISE_ADAPTIVE, JOB_DENOISE_TEMPORAL, JOB_DENOISE_SVGF, JOB_TRANSFORM_PRIMITIVES, JOB_READ_PRIMITIVES };
+       JOB_DENOISE_ADAPTIVE, JOB_DENOISE_TEMPORAL, JOB_DENOISE_SVGF, JOB_TRANSFORM_PRIMITIVES, JOB_READ_PRIMITIVES,
+       JOB_DENOISE_FRAME, JOB_DENOISE_ADAPTIVE_FRAME };
 typedef struct job {
     napi_async_work work;
     napi_deferred deferred;
     slot *sl;
     int op, rc;
     uint32_t n, px;
-    crt_denoise_adaptive_params dn;     /* JOB_DENOISE_ADAPTIVE */
+    crt_denoise_adaptive_params dn;     /* JOB_DENOISE_ADAPTIVE, JOB_DENOISE_ADAPTIVE_FRAME */
+    crt_denoise_params df;              /* JOB_DENOISE_FRAME */
     crt_denoise_temporal_params dt;     /* JOB_DENOISE_TEMPORAL */
     crt_denoise_svgf_params ds;         /* JOB_DENOISE_SVGF */
     crt_prim_transform *ops;            /* JOB_TRANSFORM_PRIMITIVES: the job's own copy of the n ops */
@@ -1170,6 +1213,8 @@ static void job_execute(napi_env env, void *data)
     case JOB_READ_FRAME_RGBA8: j->rc = crt_read_frame_rgba8(ctx, (uint8_t *)j->data); break;
     case JOB_READ_SAMPLE_RGBA8: j->rc = crt_read_sample_rgba8(ctx, j->n, (uint8_t *)j->data); break;
     case JOB_DENOISE_ADAPTIVE: j->rc = crt_denoise_adaptive(ctx, &j->dn, NULL, (uint8_t *)j->data, NULL); break;
+    case JOB_DENOISE_FRAME: j->rc = crt_denoise_frame(ctx, &j->df, NULL, (uint8_t *)j->data); break;
+    case JOB_DENOISE_ADAPTIVE_FRAME: j->rc = crt_denoise_adaptive_frame(ctx, &j->dn, NULL, (uint8_t *)j->data, NULL); break;
     case JOB_DENOISE_TEMPORAL: j->rc = crt_denoise_temporal(ctx, &j->dt, NULL, (uint8_t *)j->data, NULL); break;
     case JOB_DENOISE_SVGF: j->rc = crt_denoise_svgf(ctx, &j->ds, NULL, (uint8_t *)j->data, NULL, NULL); break;
     case JOB_TRANSFORM_PRIMITIVES: j->rc = crt_transform_primitives(ctx, j->ops, j->n); break;
@@ -1192,7 +1237,8 @@ static void job_complete(napi_env env, napi_status status, void *data)
         if (j->ab_ref) {
             napi_value ab;
             const int bytes8 = j->op == JOB_READ_RGBA8 || j->op == JOB_READ_FRAME_RGBA8 || j->op == JOB_READ_SAMPLE_RGBA8 ||
-                               j->op == JOB_DENOISE_ADAPTIVE || j->op == JOB_DENOISE_TEMPORAL || j->op == JOB_DENOISE_SVGF;
+                               j->op == JOB_DENOISE_ADAPTIVE || j->op == JOB_DENOISE_TEMPORAL || j->op == JOB_DENOISE_SVGF ||
+                               j->op == JOB_DENOISE_FRAME || j->op == JOB_DENOISE_ADAPTIVE_FRAME;
             if (napi_get_reference_value(env, j->ab_ref, &ab) == napi_ok) {
                 if (j->op == JOB_READ_PRIMITIVES) napi_create_typedarray(env, napi_uint8_array, (size_t)j->n * 80, ab, 0, &result);
                 else napi_create_typedarray(env, bytes8 ? napi_uint8_array : napi_float32_array, (size_t)j->px * 4, ab, 0, &result);
@@ -1229,7 +1275,8 @@ static napi_value start_job(napi_env env, napi_callback_info info, int op)
     if (!sl) return NULL;
     job *j = (job *)calloc(1, sizeof *j);
     j->sl = sl; j->op = op;
-    if (op == JOB_DENOISE_ADAPTIVE && !denoise_adaptive_options(env, argc > 1 ? argv[1] : NULL, argc > 1, &j->dn, NULL)) { free(j); return NULL; }
+    if (op == JOB_DENOISE_FRAME && !denoise_plain_options(env, "denoiseFrameAsync", argc > 1 ? argv[1] : NULL, argc > 1, &j->df)) { free(j); return NULL; }
+    if ((op == JOB_DENOISE_ADAPTIVE || op == JOB_DENOISE_ADAPTIVE_FRAME) && !denoise_adaptive_options(env, argc > 1 ? argv[1] : NULL, argc > 1, &j->dn, NULL)) { free(j); return NULL; }
     if (op == JOB_DENOISE_TEMPORAL && !denoise_temporal_options(env, argc > 1 ? argv[1] : NULL, argc > 1, &j->dt, NULL)) { free(j); return NULL; }
     if (op == JOB_DENOISE_SVGF && !denoise_svgf_options(env, argc > 1 ? argv[1] : NULL, argc > 1, &j->ds, NULL, NULL)) { free(j); return NULL; }
     if (op == JOB_TRACE || op == JOB_GATHER || op == JOB_READ_SAMPLE_RGBA8) {
@@ -1250,10 +1297,9 @@ static napi_value start_job(napi_env env, napi_callback_info info, int op)
             napi_create_reference(env, ab, 1, &j->ab_ref) != napi_ok) { free(j); napi_throw_error(env, NULL, "out of memory"); return NULL; }
     }
     if (op == JOB_READ_RGBA8 || op == JOB_READ_ACCUM || op == JOB_READ_FRAME_RGBA8 || op == JOB_READ_FRAME_ACCUM || op == JOB_READ_SAMPLE_RGBA8 ||
-        op == JOB_DENOISE_ADAPTIVE || op == JOB_DENOISE_TEMPORAL || op == JOB_DENOISE_SVGF) {
-        const int frame = op == JOB_READ_FRAME_RGBA8 || op == JOB_READ_FRAME_ACCUM;
-        const int bytes8 = op == JOB_READ_RGBA8 || op == JOB_READ_FRAME_RGBA8 || op == JOB_READ_SAMPLE_RGBA8 || op == JOB_DENOISE_ADAPTIVE ||
-                           op == JOB_DENOISE_TEMPORAL || op == JOB_DENOISE_SVGF;
+        op == JOB_DENOISE_ADAPTIVE || op == JOB_DENOISE_TEMPORAL || op == JOB_DENOISE_SVGF || op == JOB_DENOISE_FRAME || op == JOB_DENOISE_ADAPTIVE_FRAME) {
+        const int frame = op == JOB_READ_FRAME_RGBA8 || op == JOB_READ_FRAME_ACCUM || op == JOB_DENOISE_FRAME || op == JOB_DENOISE_ADAPTIVE_FRAME;
+        const int bytes8 = op != JOB_READ_ACCUM && op != JOB_READ_FRAME_ACCUM;
         uint32_t t[4];
         if (frame) { if (crt_image_size(sl->ctx, t + 2) != CRT_OK) { free(j); return throw_crt(env, sl->ctx, CRT_ESTATE, "crt_image_size"); } }
         else if (crt_tile(sl->ctx, t) != CRT_OK) { free(j); return throw_crt(env, sl->ctx, CRT_ESTATE, "crt_tile"); }
@@ -1296,6 +1342,8 @@ static napi_value js_read_sample_rgba8_async(napi_env env, napi_callback_info in
 static napi_value js_read_frame_rgba8_async(napi_env env, napi_callback_info info) { return start_job(env, info, JOB_READ_FRAME_RGBA8); }
 static napi_value js_read_frame_accum_async(napi_env env, napi_callback_info info) { return start_job(env, info, JOB_READ_FRAME_ACCUM); }
 static napi_value js_denoise_adaptive_async(napi_env env, napi_callback_info info) { return start_job(env, info, JOB_DENOISE_ADAPTIVE); }
+static napi_value js_denoise_frame_async(napi_env env, napi_callback_info info) { return start_job(env, info, JOB_DENOISE_FRAME); }
+static napi_value js_denoise_adaptive_frame_async(napi_env env, napi_callback_info info) { return start_job(env, info, JOB_DENOISE_ADAPTIVE_FRAME); }
 static napi_value js_denoise_temporal_async(napi_env env, napi_callback_info info) { return start_job(env, info, JOB_DENOISE_TEMPORAL); }
 static napi_value js_denoise_svgf_async(napi_env env, napi_callback_info info) { return start_job(env, info, JOB_DENOISE_SVGF); }
 static napi_value js_transform_primitives_async(napi_env env, napi_callback_info info) { return start_job(env, info, JOB_TRANSFORM_PRIMITIVES); }
@@ -1340,6 +1388,8 @@ static napi_value init(napi_env env, napi_value exports)
         {"denoiseTemporal", js_denoise_temporal}, {"denoiseTemporalAsync", js_denoise_temporal_async},
         {"denoiseSvgfDefaults", js_denoise_svgf_defaults}, {"denoiseSvgf", js_denoise_svgf}, {"denoiseSvgfAsync", js_denoise_svgf_async},
         {"readMoments", js_read_moments},
+        {"readFrameAdaptive", js_read_frame_adaptive}, {"denoiseFrame", js_denoise_frame}, {"denoiseFrameAsync", js_denoise_frame_async},
+        {"denoiseAdaptiveFrame", js_denoise_adaptive_frame}, {"denoiseAdaptiveFrameAsync", js_denoise_adaptive_frame_async},
         {"gatherAsync", js_gather_async}, {"readFrameRgba8Async", js_read_frame_rgba8_async}, {"readFrameAccumAsync", js_read_frame_accum_async},
     };
     for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++) {

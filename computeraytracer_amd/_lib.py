@@ -88,6 +88,9 @@ SIGNATURES = {
     "crt_adaptive_defaults": (C.c_int, [_P]),
     "crt_denoise_adaptive": (C.c_int, [_P, _P, _P, _P, _P]),
     "crt_denoise_adaptive_defaults": (C.c_int, [_P]),
+    "crt_read_frame_adaptive": (C.c_int, [_P, _P, _P]),
+    "crt_denoise_frame": (C.c_int, [_P, _P, _P, _P]),
+    "crt_denoise_adaptive_frame": (C.c_int, [_P, _P, _P, _P, _P]),
     "crt_set_sample_offset": (C.c_int, [_P, C.c_uint32]),
     "crt_sample_offset": (C.c_int, [_P, _P]),
     "crt_denoise_temporal": (C.c_int, [_P, _P, _P, _P, _P]),

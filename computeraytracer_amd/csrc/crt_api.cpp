@@ -93,7 +93,7 @@ namespace {
 // allocated, the frame state zeroed.
 int retile(crt_ctx *c)
 {
-    c->dn.valid = false;
+    c->dn.valid = false; c->fdn.valid = false;
     c->dn.drop();
     c->accum_bound = nullptr; c->rgba_bound = nullptr;
     CRT_TRY(alloc_tile(c));
@@ -229,7 +229,7 @@ int crt_upload_scene(crt_ctx *c, const void *primitives, size_t nprim, const voi
     // from here on the old scene is gone: a failure below must not leave a context that can still trace
     c->have_scene = false;
     c->accel_mode = -1;
-    c->dn.valid = false;
+    c->dn.valid = false; c->fdn.valid = false;
     c->sample_offset = 0;
     c->dn.drop();
     c->prims.swap(prims);
@@ -316,7 +316,7 @@ int crt_build_accel(crt_ctx *c, int mode)
     // The build releases the scene's device arrays before it allocates the new ones: until it has succeeded there is
     // no structure to trace against (upload_geometry / build_accel_on_device set accel_mode on success only).
     c->accel_mode = -1;
-    c->dn.valid = false;
+    c->dn.valid = false; c->fdn.valid = false;
     return build_tree(c, mode);
 }
 
@@ -431,7 +431,10 @@ int crt_trace_adaptive(crt_ctx *c, const crt_adaptive_params *params, uint32_t *
     if (!c->have_scene) return fail(c, CRT_ESTATE, "crt_trace: upload a scene first");
     if (c->accel_mode < 0) return fail(c, CRT_ESTATE, "crt_trace: call crt_build_accel first");
     if (c->accel_stale) return fail(c, CRT_ESTATE, "crt_trace: primitives were updated: call crt_refit_accel or crt_build_accel first");
-    if (crt_internal_comm_partitioned(c)) return fail(c, CRT_ESTATE, "crt_trace_adaptive: not under a crt_comm_partition (multi-GPU adaptivity is not supported)");
+    // (a band partition of a multiple of 8 rows: every local 8x8 tile is one of the frame's)
+    if (crt_internal_comm_partitioned(c) == 1)
+        return fail(c, CRT_ESTATE, "crt_trace_adaptive: not under this crt_comm_partition: its 8x8 tiles are not the frame's "
+                                   "(a band partition with band_rows a multiple of 8 is what works)");
     if (c->as_broken) return as_refuse_broken(c, "crt_trace_adaptive");
     if (c->sample_offset)
         return fail(c, CRT_ESTATE, "crt_trace_adaptive: not with a sample offset (%u): crt_set_sample_offset(ctx, 0) first", c->sample_offset);
@@ -500,6 +503,21 @@ int crt_read_adaptive(crt_ctx *c, uint32_t *counts, float *errors)
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return wf_check_dropped(c);
+}
+
+// crt_comm.cpp (CRT_GATHER_PREVIEW and the frame-level calls): the context's frame state.  out[0] = 0 uniform, 1 adaptive;
+// out[1] = the uniform sample count; out[2] = the epoch of the frame state (what zero_state and crt_write_accum bump).
+// With `finish`, a sync point first, as crt_read_adaptive is one: everything in flight is finished.  q_dev / counts_dev
+// (may be NULL) receive the adaptive state's device buffers: Q per tile pixel, the count per 8x8 tile.
+int crt_internal_frame_state(crt_ctx *c, int finish, const char *who, uint32_t out[3], void **q_dev, void **counts_dev)
+{
+    if (!c || !out) return CRT_EINVAL;
+    if (c->as_on && c->as_broken) return as_refuse_broken(c, who);
+    if (finish) CRT_TRY(quiesce(c, false));
+    out[0] = c->as_on ? 1u : 0u; out[1] = c->as_on ? 0u : c->sample; out[2] = c->frame_id;
+    if (q_dev) *q_dev = c->as_on ? c->as_q.p : nullptr;
+    if (counts_dev) *counts_dev = c->as_on ? c->as_counts.p : nullptr;
+    return CRT_OK;
 }
 
 int crt_sample_count(crt_ctx *c, uint32_t *out)

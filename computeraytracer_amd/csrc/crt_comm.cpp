@@ -6,7 +6,10 @@
 //
 // Written against the public C ABI only (crt_set_row_bands / crt_set_tile, crt_bind_output, crt_get_stream): a context
 // does not know that it is part of a communicator, it renders its rows into the strip buffers bound here.  Whether it
-// still does is asked of it the same way (crt_device_buffers, crt_image_size, crt_tile: `current` below).
+// still does is asked of it the same way (crt_device_buffers, crt_image_size, crt_tile: `current` below).  The one thing
+// the public ABI does not show -- the frame state that CRT_GATHER_PREVIEW ships and records (uniform or adaptive, the sample
+// count, the epoch, the adaptive state's Q and tile counts) -- comes through crt_internal_frame_state; the frame-level
+// filters of crt_denoise_api.cpp ask for the assembled planes through crt_internal_comm_frame_view.
 //
 // Transports behind one interface:
 //   RCCL   one process per GPU (or one thread per GPU): ncclCommInitRank + ncclAllGather.  librccl is loaded on first
@@ -35,6 +38,9 @@ hipError_t launch_assemble(const void *full, void *frame, uint32_t elem_bytes, u
                            uint32_t band, hipStream_t stream);
 }
 extern "C" int crt_internal_fail(crt_ctx *c, int code, const char *msg);
+// crt_api.cpp: out[3] = state (0 uniform, 1 adaptive), uniform sample count, epoch of the frame state; with `finish` a sync
+// point first; q_dev / counts_dev: the adaptive state's device buffers
+extern "C" int crt_internal_frame_state(crt_ctx *c, int finish, const char *who, uint32_t out[3], void **q_dev, void **counts_dev);
 
 namespace {
 
@@ -73,10 +79,35 @@ std::mutex g_mu;                                   // guards g_rccl, g_comms and
 
 // ---------------------------------------------------------------- the local transport's shared state
 struct Comm;
+// The gathered planes.  Each is a row partition of a small frame of its own: the two pixel planes every partition has, and,
+// under a band partition of a multiple of 8 rows (where crt_trace_adaptive works), the adaptive state's second moment Q per
+// pixel and its sample count per 8x8 tile -- the tile grid partitioned by crt_layout_rows(ceil(H/8), band/8, world, rank).
+enum { PL_RGBA = 0, PL_ACCUM = 1, PL_Q = 2, PL_COUNTS = 3, PL_N = 4 };
+
+// What a CRT_GATHER_PREVIEW records: which of the rank's PREVIEW gathers since the partition it was, and the frame state then.
+struct Preview {
+    uint64_t count = 0;
+    uint32_t adaptive = 0, n = 0;                  // the state; the uniform sample count (0 in the adaptive state)
+};
+
 struct LocalGroup {
     int world = 0;
     std::vector<Comm *> member;                    // by rank; null until that rank has joined
-    std::vector<uint64_t> posted_rgba, posted_accum;   // per rank: gathers posted so far
+    std::vector<uint64_t> posted[PL_N];            // per plane and rank: gathers posted so far
+    std::vector<Preview> preview;                  // per rank: its latest PREVIEW gather
+};
+
+struct Plane {
+    uint32_t elem = 0;                             // bytes per element; 0: this partition has no such plane
+    uint32_t W = 0, H = 0, band = 0, rows = 0, rows_max = 0;   // the frame it partitions, this rank's rows of it, the largest rank's
+    void *strip = nullptr;                         // this rank's rows, padded to rows_max (pixel planes: bound as the context's output)
+    void *full = nullptr;                          // [world][rows_max][W]: the gathered strips
+    void *frame = nullptr;                         // [H][W]: assembled frame
+    uint64_t n = 0, asm_n = 0;                     // gathers posted by this rank, and assembled
+    hipEvent_t ev = nullptr;                       // local transport: after this rank's copies of its latest gather
+    hipEvent_t ev_asm = nullptr;                   // ... and after this rank's latest assembly (it reads `full`: a peer's next copy waits for it)
+    bool asm_recorded = false;
+    size_t strip_bytes() const { return (size_t)std::max(rows_max, 1u) * W * elem; }
 };
 
 struct Comm {
@@ -89,14 +120,11 @@ struct Comm {
     // partition and buffers (valid once crt_comm_partition has run)
     bool partitioned = false;
     uint32_t W = 0, H = 0, band = 0, rows = 0, rows_max = 0;
-    void *strip_accum = nullptr, *strip_rgba = nullptr;      // this rank's rows, padded to rows_max (bound as the context's output)
-    void *full_accum = nullptr, *full_rgba = nullptr;        // [world][rows_max][W]: the gathered strips
-    void *frame_accum = nullptr, *frame_rgba = nullptr;      // [H][W]: assembled frame
-    uint64_t n_rgba = 0, n_accum = 0;                        // gathers posted by this rank
-    uint64_t asm_rgba = 0, asm_accum = 0;                    // ... and assembled
-    hipEvent_t ev_rgba = nullptr, ev_accum = nullptr;        // local transport: after this rank's copies of its latest gather
-    hipEvent_t ev_asm_rgba = nullptr, ev_asm_accum = nullptr;  // ... and after this rank's latest assembly (it reads `full`: a peer's next copy waits for it)
-    bool asm_rgba_recorded = false, asm_accum_recorded = false;
+    Plane pl[PL_N];
+    // the latest CRT_GATHER_PREVIEW since the partition (count == 0: none): what the frame-level calls work on
+    Preview pv;
+    uint32_t pv_epoch = 0;                                   // the context's frame-state epoch at that gather
+    uint64_t pv_accum_n = 0;                                 // ... and which gather of the accumulator plane it posted
 };
 std::map<crt_ctx *, std::unique_ptr<Comm>> g_comms;
 std::map<std::string, std::weak_ptr<LocalGroup>> g_groups;
@@ -114,8 +142,11 @@ Comm *find(crt_ctx *c)
 
 void free_buffers(Comm &m)
 {
-    for (void **p : {&m.strip_accum, &m.strip_rgba, &m.full_accum, &m.full_rgba, &m.frame_accum, &m.frame_rgba})
-        if (*p) { (void)hipFree(*p); *p = nullptr; }
+    for (Plane &q : m.pl) {
+        for (void **p : {&q.strip, &q.full, &q.frame})
+            if (*p) { (void)hipFree(*p); *p = nullptr; }
+        q.elem = 0;
+    }
     m.partitioned = false;
 }
 
@@ -136,7 +167,7 @@ uint32_t rows_of(uint32_t H, uint32_t band, uint32_t parts, uint32_t part)
 bool bound_to_strips(crt_ctx *c, const Comm *m)
 {
     void *a = nullptr, *r = nullptr;
-    return m->partitioned && crt_device_buffers(c, &a, &r) == CRT_OK && a == m->strip_accum && r == m->strip_rgba;
+    return m->partitioned && crt_device_buffers(c, &a, &r) == CRT_OK && a == m->pl[PL_ACCUM].strip && r == m->pl[PL_RGBA].strip;
 }
 
 bool current(crt_ctx *c, const Comm *m)
@@ -213,14 +244,15 @@ int crt_comm_init(crt_ctx *c, const void *id, int rank, int world)
     m->local = is_local_id(id);
     // (the events first: nothing below may fail once the rank has joined its group or its RCCL communicator exists)
     auto drop_events = [&]() {
-        for (hipEvent_t *e : {&m->ev_rgba, &m->ev_accum, &m->ev_asm_rgba, &m->ev_asm_accum}) if (*e) { (void)hipEventDestroy(*e); *e = nullptr; }
+        for (Plane &q : m->pl)
+            for (hipEvent_t *e : {&q.ev, &q.ev_asm}) if (*e) { (void)hipEventDestroy(*e); *e = nullptr; }
     };
-    if (hipEventCreateWithFlags(&m->ev_rgba, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&m->ev_accum, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&m->ev_asm_rgba, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&m->ev_asm_accum, hipEventDisableTiming) != hipSuccess) {
-        (void)hipGetLastError();
-        drop_events();
-        return fail(c, CRT_EDEVICE, "crt_comm_init: hipEventCreate failed");
-    }
+    for (Plane &q : m->pl)
+        if (hipEventCreateWithFlags(&q.ev, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&q.ev_asm, hipEventDisableTiming) != hipSuccess) {
+            (void)hipGetLastError();
+            drop_events();
+            return fail(c, CRT_EDEVICE, "crt_comm_init: hipEventCreate failed");
+        }
     if (m->local) {
         std::lock_guard<std::mutex> lk(g_mu);
         const std::string key((const char *)id, CRT_COMM_ID_BYTES);
@@ -228,7 +260,8 @@ int crt_comm_init(crt_ctx *c, const void *id, int rank, int world)
         if (!g) {
             g = std::make_shared<LocalGroup>();
             g->world = world; g->member.assign((size_t)world, nullptr);
-            g->posted_rgba.assign((size_t)world, 0); g->posted_accum.assign((size_t)world, 0);
+            for (auto &v : g->posted) v.assign((size_t)world, 0);
+            g->preview.assign((size_t)world, Preview());
             g_groups[key] = g;
         }
         if (g->world != world) { drop_events(); return fail(c, CRT_EINVAL, "crt_comm_init: the ranks of one id disagree about the world size"); }
@@ -267,10 +300,8 @@ int crt_comm_destroy(crt_ctx *c)
     if (bound_to_strips(c, m.get())) (void)crt_bind_output(c, nullptr, nullptr);   // (a stale partition: the outputs are the application's)
     free_buffers(*m);
     if (m->nccl) (void)g_rccl.CommDestroy(m->nccl);
-    if (m->ev_rgba) (void)hipEventDestroy(m->ev_rgba);
-    if (m->ev_accum) (void)hipEventDestroy(m->ev_accum);
-    if (m->ev_asm_rgba) (void)hipEventDestroy(m->ev_asm_rgba);
-    if (m->ev_asm_accum) (void)hipEventDestroy(m->ev_asm_accum);
+    for (Plane &q : m->pl)
+        for (hipEvent_t e : {q.ev, q.ev_asm}) if (e) (void)hipEventDestroy(e);
     return CRT_OK;
 }
 
@@ -300,34 +331,56 @@ int crt_comm_partition(crt_ctx *c, uint32_t band_rows)
         rc = crt_set_tile(c, 0, y0, W, std::min<uint64_t>((uint64_t)y0 + per, H));
     }
     if (rc) return rc;
-    const size_t strip_px = (size_t)std::max(rows_max, 1u) * W, frame_px = (size_t)std::max(H, 1u) * W;
-    CHIP(c, hipMalloc(&m->strip_accum, strip_px * 16)); CHIP(c, hipMalloc(&m->strip_rgba, strip_px * 4));
-    CHIP(c, hipMalloc(&m->full_accum, strip_px * 16 * (size_t)m->world)); CHIP(c, hipMalloc(&m->full_rgba, strip_px * 4 * (size_t)m->world));
-    CHIP(c, hipMalloc(&m->frame_accum, frame_px * 16)); CHIP(c, hipMalloc(&m->frame_rgba, frame_px * 4));
-    CHIP(c, hipMemset(m->strip_accum, 0, strip_px * 16)); CHIP(c, hipMemset(m->strip_rgba, 0, strip_px * 4));
-    CHIP(c, hipMemset(m->frame_accum, 0, frame_px * 16)); CHIP(c, hipMemset(m->frame_rgba, 0, frame_px * 4));
+    // the planes: the two of the pixels, and where crt_trace_adaptive works (every local 8x8 tile one of the frame's) Q and
+    // the tile counts, the tile grid being a small frame partitioned the same way with bands of band_rows / 8 tile rows
+    const bool tiles_align = band_rows && band_rows % 8u == 0;
+    for (int k : {PL_RGBA, PL_ACCUM, PL_Q}) {
+        if (k == PL_Q && !tiles_align) continue;
+        Plane &q = m->pl[k];
+        q.elem = k == PL_ACCUM ? 16u : 4u;
+        q.W = W; q.H = H; q.band = band_rows; q.rows = m->rows; q.rows_max = rows_max;
+    }
+    if (tiles_align) {
+        Plane &t = m->pl[PL_COUNTS];
+        t.elem = 4u; t.W = (W + 7u) / 8u; t.H = (H + 7u) / 8u; t.band = band_rows / 8u;
+        t.rows = rows_of(t.H, t.band, (uint32_t)m->world, (uint32_t)m->rank);
+        t.rows_max = 0;
+        for (int p = 0; p < m->world; p++) t.rows_max = std::max(t.rows_max, rows_of(t.H, t.band, (uint32_t)m->world, (uint32_t)p));
+        if (t.rows != (m->rows + 7u) / 8u) return fail(c, CRT_EDEVICE, "crt_comm_partition: the tile rows of this rank are not its rows' tiles");
+    }
+    for (Plane &q : m->pl) {
+        q.n = q.asm_n = 0; q.asm_recorded = false;
+        if (!q.elem) continue;
+        const size_t strip = q.strip_bytes(), frame = (size_t)std::max(q.H, 1u) * q.W * q.elem;
+        CHIP(c, hipMalloc(&q.strip, strip)); CHIP(c, hipMalloc(&q.full, strip * (size_t)m->world)); CHIP(c, hipMalloc(&q.frame, frame));
+        CHIP(c, hipMemset(q.strip, 0, strip)); CHIP(c, hipMemset(q.frame, 0, frame));
+    }
     m->partitioned = true;
-    m->n_rgba = m->n_accum = m->asm_rgba = m->asm_accum = 0;
-    if (m->group) { std::lock_guard<std::mutex> lk(g_mu); m->group->posted_rgba[(size_t)m->rank] = 0; m->group->posted_accum[(size_t)m->rank] = 0; }
+    m->pv = Preview();
+    if (m->group) {
+        std::lock_guard<std::mutex> lk(g_mu);
+        for (auto &v : m->group->posted) v[(size_t)m->rank] = 0;
+        m->group->preview[(size_t)m->rank] = Preview();
+    }
     // the context renders straight into the padded strips (and its accumulator starts at zero there)
-    return crt_bind_output(c, m->strip_accum, m->strip_rgba);
+    return crt_bind_output(c, m->pl[PL_ACCUM].strip, m->pl[PL_RGBA].strip);
 }
 
 // Post one gather of this rank's strip on the context's stream: what is in the strip THEN, in stream order -- after a
 // crt_sync every sample requested so far, in the middle of a pipelined run the latest complete frame (crt_trace's contract
 // for bound outputs).
-static int gather_one(crt_ctx *c, Comm *m, bool accum)
+static int gather_one(crt_ctx *c, Comm *m, int plane)
 {
     void *st = nullptr;
     { int rc = crt_get_stream(c, &st); if (rc) return rc; }
     hipStream_t s = (hipStream_t)st;
-    const size_t elem = accum ? 16 : 4, strip_bytes = (size_t)std::max(m->rows_max, 1u) * m->W * elem;
-    const void *src = accum ? m->strip_accum : m->strip_rgba;
-    void *dst = accum ? m->full_accum : m->full_rgba;
+    Plane &q = m->pl[plane];
+    const size_t strip_bytes = q.strip_bytes();
+    const void *src = q.strip;
     if (!m->local) {
-        const ncclResult_t r = g_rccl.AllGather(src, dst, strip_bytes, ncclUint8, m->nccl, s);
+        const ncclResult_t r = g_rccl.AllGather(src, q.full, strip_bytes, ncclUint8, m->nccl, s);
         if (r != ncclSuccess) return fail(c, CRT_EDEVICE, std::string("ncclAllGather: ") + g_rccl.GetErrorString(r));
-        (accum ? m->n_accum : m->n_rgba)++;
+        q.n++;
         return CRT_OK;
     }
     // local transport: this rank's strip into slot `rank` of every member's gather buffer
@@ -340,15 +393,57 @@ static int gather_one(crt_ctx *c, Comm *m, bool accum)
         if (!p || !p->partitioned) return fail(c, CRT_ESTATE, "crt_gather: every rank of the communicator must have called crt_comm_partition");
         if (p->rows_max != m->rows_max || p->W != m->W || p->H != m->H || p->band != m->band)
             return fail(c, CRT_EINVAL, "crt_gather: the ranks of the communicator disagree about the partition");
-        char *pd = (char *)(accum ? p->full_accum : p->full_rgba) + (size_t)m->rank * strip_bytes;
+        Plane &pq = p->pl[plane];
+        if (pq.elem != q.elem || pq.strip_bytes() != strip_bytes)   // (the same partition gives every rank the same planes)
+            return fail(c, CRT_EINVAL, "crt_gather: the ranks of the communicator disagree about the partition");
+        char *pd = (char *)pq.full + (size_t)m->rank * strip_bytes;
         // (the peer's assembly of the PREVIOUS gather reads the buffer this copy writes: behind it, whatever the streams)
-        if (p != m && (accum ? p->asm_accum_recorded : p->asm_rgba_recorded)) CHIP(c, hipStreamWaitEvent(s, accum ? p->ev_asm_accum : p->ev_asm_rgba, 0));
+        if (p != m && pq.asm_recorded) CHIP(c, hipStreamWaitEvent(s, pq.ev_asm, 0));
         CHIP(c, hipMemcpyPeerAsync(pd, p->device, src, m->device, strip_bytes, s));
     }
-    CHIP(c, hipEventRecord(accum ? m->ev_accum : m->ev_rgba, s));
+    CHIP(c, hipEventRecord(q.ev, s));
     std::lock_guard<std::mutex> lk(g_mu);
-    (accum ? m->n_accum : m->n_rgba)++;
-    (accum ? m->group->posted_accum : m->group->posted_rgba)[(size_t)m->rank] = accum ? m->n_accum : m->n_rgba;
+    q.n++;
+    m->group->posted[plane][(size_t)m->rank] = q.n;
+    return CRT_OK;
+}
+
+// CRT_GATHER_PREVIEW: what the frame-level calls need, in one step.  A sync point for this context (what is in flight is
+// finished, as crt_read_adaptive finishes it), then on its stream the accumulator's gather -- the plain one, so
+// crt_read_frame_accum sees it too -- and in the adaptive state those of Q and of the tile counts, staged from the
+// context's own unpadded buffers into the padded strips.  The frame state is recorded beside it.
+static int gather_preview(crt_ctx *c, Comm *m, int what)
+{
+    uint32_t st[3] = {0, 0, 0};
+    void *q_dev = nullptr, *counts_dev = nullptr;
+    { int rc = crt_internal_frame_state(c, 1, "crt_gather", st, &q_dev, &counts_dev); if (rc) return rc; }
+    const bool adaptive = st[0] != 0;
+    if (adaptive && (!m->pl[PL_Q].elem || !m->pl[PL_COUNTS].elem || !q_dev || !counts_dev))
+        return fail(c, CRT_ESTATE, "crt_gather: the adaptive state needs a band partition of a multiple of 8 rows");
+    if (m->local) {                                            // a peer that has posted this round already must hold the same kind of frame
+        std::lock_guard<std::mutex> lk(g_mu);
+        for (const Preview &p : m->group->preview)
+            if (p.count == m->pv.count + 1 && (p.adaptive != st[0] || p.n != st[1]))
+                return fail(c, CRT_EINVAL, "crt_gather: the ranks disagree about the frame state (uniform or adaptive, or the sample count)");
+    }
+    void *sv = nullptr;
+    { int rc = crt_get_stream(c, &sv); if (rc) return rc; }
+    hipStream_t s = (hipStream_t)sv;
+    if (what & CRT_GATHER_RGBA8) { int rc = gather_one(c, m, PL_RGBA); if (rc) return rc; }
+    { int rc = gather_one(c, m, PL_ACCUM); if (rc) return rc; }
+    if (adaptive) {
+        const void *src[2] = {q_dev, counts_dev};
+        const int plane[2] = {PL_Q, PL_COUNTS};
+        for (int k = 0; k < 2; k++) {
+            const Plane &q = m->pl[plane[k]];
+            const size_t bytes = (size_t)q.rows * q.W * q.elem;                // (the strip's padding stays zero)
+            if (bytes) CHIP(c, hipMemcpyAsync(q.strip, src[k], bytes, hipMemcpyDeviceToDevice, s));
+            { int rc = gather_one(c, m, plane[k]); if (rc) return rc; }
+        }
+    }
+    m->pv.count++; m->pv.adaptive = st[0]; m->pv.n = st[1];
+    m->pv_epoch = st[2]; m->pv_accum_n = m->pl[PL_ACCUM].n;
+    if (m->local) { std::lock_guard<std::mutex> lk(g_mu); m->group->preview[(size_t)m->rank] = m->pv; }
     return CRT_OK;
 }
 
@@ -356,18 +451,20 @@ int crt_gather(crt_ctx *c, int what)
 {
     Comm *m = find(c);
     { int rc = refuse_unless_current(c, m, "crt_gather"); if (rc) return rc; }
-    if (!(what & (CRT_GATHER_RGBA8 | CRT_GATHER_ACCUM))) return fail(c, CRT_EINVAL, "crt_gather: nothing to gather");
+    if (!(what & (CRT_GATHER_RGBA8 | CRT_GATHER_ACCUM | CRT_GATHER_PREVIEW))) return fail(c, CRT_EINVAL, "crt_gather: nothing to gather");
     CHIP(c, hipSetDevice(m->device));
-    if (what & CRT_GATHER_RGBA8) { int rc = gather_one(c, m, false); if (rc) return rc; }
-    if (what & CRT_GATHER_ACCUM) { int rc = gather_one(c, m, true); if (rc) return rc; }
+    if (what & CRT_GATHER_PREVIEW) return gather_preview(c, m, what);          // (it gathers the accumulator itself)
+    if (what & CRT_GATHER_RGBA8) { int rc = gather_one(c, m, PL_RGBA); if (rc) return rc; }
+    if (what & CRT_GATHER_ACCUM) { int rc = gather_one(c, m, PL_ACCUM); if (rc) return rc; }
     return CRT_OK;
 }
 
 // Assemble the frame of the latest gather on this rank's stream (full -> frame: the rows back in image order).
-static int assemble(crt_ctx *c, Comm *m, bool accum, hipStream_t s)
+static int assemble(crt_ctx *c, Comm *m, int plane, hipStream_t s)
 {
-    uint64_t &done = accum ? m->asm_accum : m->asm_rgba;
-    const uint64_t posted = accum ? m->n_accum : m->n_rgba;
+    Plane &q = m->pl[plane];
+    uint64_t &done = q.asm_n;
+    const uint64_t posted = q.n;
     if (posted == 0) return fail(c, CRT_ESTATE, "crt_read_frame: no crt_gather of that buffer yet");
     if (m->local) {
         // every rank's copies of gather number `posted` must be in: their streams are joined through their events
@@ -375,20 +472,19 @@ static int assemble(crt_ctx *c, Comm *m, bool accum, hipStream_t s)
         {
             std::lock_guard<std::mutex> lk(g_mu);
             for (int p = 0; p < m->world; p++)
-                if ((accum ? m->group->posted_accum : m->group->posted_rgba)[(size_t)p] < posted)
+                if (m->group->posted[plane][(size_t)p] < posted)
                     return fail(c, CRT_ESTATE, "crt_read_frame: rank " + std::to_string(p) + " of the communicator has not posted its crt_gather yet");
             peers = m->group->member;
         }
-        for (Comm *p : peers) if (p && p != m) CHIP(c, hipStreamWaitEvent(s, accum ? p->ev_accum : p->ev_rgba, 0));
+        for (Comm *p : peers) if (p && p != m) CHIP(c, hipStreamWaitEvent(s, p->pl[plane].ev, 0));
     }
     if (done != posted) {
-        const hipError_t e = crt::launch_assemble(accum ? m->full_accum : m->full_rgba, accum ? m->frame_accum : m->frame_rgba, accum ? 16u : 4u,
-                                                  m->W, m->H, (uint32_t)m->world, std::max(m->rows_max, 1u), m->band, s);
+        const hipError_t e = crt::launch_assemble(q.full, q.frame, q.elem, q.W, q.H, (uint32_t)m->world, std::max(q.rows_max, 1u), q.band, s);
         if (e != hipSuccess) return fail(c, CRT_EDEVICE, std::string("frame assembly: ") + hipGetErrorString(e));
         done = posted;
         if (m->local) {
-            CHIP(c, hipEventRecord(accum ? m->ev_asm_accum : m->ev_asm_rgba, s));
-            (accum ? m->asm_accum_recorded : m->asm_rgba_recorded) = true;
+            CHIP(c, hipEventRecord(q.ev_asm, s));
+            q.asm_recorded = true;
         }
     }
     return CRT_OK;
@@ -396,6 +492,7 @@ static int assemble(crt_ctx *c, Comm *m, bool accum, hipStream_t s)
 
 static int read_frame(crt_ctx *c, void *out, bool accum)
 {
+    const int plane = accum ? PL_ACCUM : PL_RGBA;
     Comm *m = find(c);
     { int rc = refuse_unless_current(c, m, "crt_read_frame"); if (rc) return rc; }
     if (!out) return CRT_EINVAL;
@@ -403,9 +500,9 @@ static int read_frame(crt_ctx *c, void *out, bool accum)
     void *st = nullptr;
     { int rc = crt_get_stream(c, &st); if (rc) return rc; }
     hipStream_t s = (hipStream_t)st;
-    { int rc = assemble(c, m, accum, s); if (rc) return rc; }
+    { int rc = assemble(c, m, plane, s); if (rc) return rc; }
     const size_t bytes = (size_t)m->W * m->H * (accum ? 16 : 4);
-    if (bytes) CHIP(c, hipMemcpyAsync(out, accum ? m->frame_accum : m->frame_rgba, bytes, hipMemcpyDeviceToHost, s));
+    if (bytes) CHIP(c, hipMemcpyAsync(out, m->pl[plane].frame, bytes, hipMemcpyDeviceToHost, s));
     CHIP(c, hipStreamSynchronize(s));
     return CRT_OK;
 }
@@ -420,8 +517,52 @@ int crt_frame_device_buffers(crt_ctx *c, void **accum_dev, void **rgba8_dev)
     CHIP(c, hipSetDevice(m->device));
     void *st = nullptr;
     { int rc = crt_get_stream(c, &st); if (rc) return rc; }
-    if (accum_dev) { if (m->n_accum) { int rc = assemble(c, m, true, (hipStream_t)st); if (rc) return rc; } *accum_dev = m->frame_accum; }
-    if (rgba8_dev) { if (m->n_rgba) { int rc = assemble(c, m, false, (hipStream_t)st); if (rc) return rc; } *rgba8_dev = m->frame_rgba; }
+    if (accum_dev) { if (m->pl[PL_ACCUM].n) { int rc = assemble(c, m, PL_ACCUM, (hipStream_t)st); if (rc) return rc; } *accum_dev = m->pl[PL_ACCUM].frame; }
+    if (rgba8_dev) { if (m->pl[PL_RGBA].n) { int rc = assemble(c, m, PL_RGBA, (hipStream_t)st); if (rc) return rc; } *rgba8_dev = m->pl[PL_RGBA].frame; }
+    return CRT_OK;
+}
+
+// crt_denoise_api.cpp (crt_denoise_frame, crt_denoise_adaptive_frame, crt_read_frame_adaptive): the frame of the latest
+// CRT_GATHER_PREVIEW, or why there is none for this call.  Every refusal comes before anything is enqueued; with
+// `assemble_now` the planes are then put in order on the context's stream.  planes[3] = the frame's accumulator, Q and tile
+// counts (the last two NULL for a uniform frame); dims[3] = W, H and the uniform sample count.
+int crt_internal_comm_frame_view(crt_ctx *c, const char *who, int adaptive, int assemble_now, const void *planes[3], uint32_t dims[3])
+{
+    Comm *m = find(c);
+    { int rc = refuse_unless_current(c, m, who); if (rc) return rc; }
+    if (m->pv.count == 0) return fail(c, CRT_ESTATE, std::string(who) + ": no crt_gather(CRT_GATHER_PREVIEW) since crt_comm_partition");
+    if ((m->pv.adaptive != 0) != (adaptive != 0))
+        return fail(c, CRT_ESTATE, std::string(who) + (m->pv.adaptive ? ": the gathered frame is an adaptive one (per-tile sample counts: crt_denoise_adaptive_frame, crt_read_frame_adaptive)"
+                                                                      : ": the gathered frame is a uniform one (crt_denoise_frame filters it)"));
+    uint32_t st[3] = {0, 0, 0};
+    { int rc = crt_internal_frame_state(c, 0, who, st, nullptr, nullptr); if (rc) return rc; }
+    if (st[2] != m->pv_epoch)
+        return fail(c, CRT_ESTATE, std::string(who) + ": the context's frame was reset or replaced since the PREVIEW gather (a reset, an edit, the camera): gather again");
+    if (m->pl[PL_ACCUM].n != m->pv_accum_n)
+        return fail(c, CRT_ESTATE, std::string(who) + ": the accumulator was gathered again since the PREVIEW gather, without the planes that go with it: gather again");
+    if (m->local) {
+        std::lock_guard<std::mutex> lk(g_mu);
+        for (int p = 0; p < m->world; p++) {
+            const Preview &pp = m->group->preview[(size_t)p];
+            if (pp.count < m->pv.count)
+                return fail(c, CRT_ESTATE, std::string(who) + ": rank " + std::to_string(p) + " of the communicator has not posted its crt_gather yet");
+            if (pp.count == m->pv.count && (pp.adaptive != m->pv.adaptive || pp.n != m->pv.n))
+                return fail(c, CRT_EINVAL, std::string(who) + ": the ranks disagree about the frame state (uniform or adaptive, or the sample count)");
+        }
+    }
+    dims[0] = m->W; dims[1] = m->H; dims[2] = m->pv.n;
+    planes[0] = m->pl[PL_ACCUM].frame;
+    planes[1] = adaptive ? m->pl[PL_Q].frame : nullptr;
+    planes[2] = adaptive ? m->pl[PL_COUNTS].frame : nullptr;
+    if (!assemble_now) return CRT_OK;
+    CHIP(c, hipSetDevice(m->device));
+    void *sv = nullptr;
+    { int rc = crt_get_stream(c, &sv); if (rc) return rc; }
+    { int rc = assemble(c, m, PL_ACCUM, (hipStream_t)sv); if (rc) return rc; }
+    if (adaptive) {
+        { int rc = assemble(c, m, PL_Q, (hipStream_t)sv); if (rc) return rc; }
+        { int rc = assemble(c, m, PL_COUNTS, (hipStream_t)sv); if (rc) return rc; }
+    }
     return CRT_OK;
 }
 
@@ -434,11 +575,13 @@ int crt_comm_info(crt_ctx *c, int out[4])
     return CRT_OK;
 }
 
-// (crt_api.cpp: crt_trace_adaptive refuses a partitioned context; a stale partition is none)
+// (crt_api.cpp, crt_trace_adaptive.  0: no partition, a stale one is none; 2: bands of a multiple of 8 rows, so every local
+// 8x8 tile is one of the frame's and the call works; 1: any other partition, which it refuses)
 int crt_internal_comm_partitioned(crt_ctx *c)
 {
     Comm *m = find(c);
-    return m && current(c, m) ? 1 : 0;
+    if (!m || !current(c, m)) return 0;
+    return m->band && m->band % 8u == 0 ? 2 : 1;
 }
 
 }  // extern "C"

@@ -274,6 +274,19 @@ struct crt_ctx {
         void drop() { cur.clear(); prev.clear(); snap.release(); }
     } dn;
 
+    // The frame-level filters of a partitioned context (crt_denoise_frame, crt_denoise_adaptive_frame, crt_read_frame_adaptive;
+    // DESIGN.md 6h): W x H buffers of their own -- dn is tile-sized and belongs to the history slots.  No history here.
+    struct FrameDenoise {
+        DnGuideSet guides;          // the G-buffer of the whole frame while `valid`: kept until the scene, the tree, the
+        bool valid = false;         // camera or the partition changes (dropped wherever dn.valid is)
+        DevBuf<float4> c[2];
+        DevBuf<uchar4> rgba;
+        DevBuf<uint2> kv;
+        DevBuf<float> var;
+        DevBuf<float> errors;       // crt_read_frame_adaptive: E per tile of the frame's grid ...
+        DevBuf<uint32_t> flags;     // ... and the flags the selection kernel writes beside it
+    } fdn;
+
     // scene edits (crt_refit.hip)
     float s_prims = 0.0f;           // max |corner coordinate| of the primitives: hit_pad = max(s_prims, |eye|) * 2^-17
     float tree_pad = 0.0f;          // the hit_pad the tree's boxes were made with (a larger one needs a refit)

@@ -21,12 +21,18 @@ static int dn_check_state(crt_ctx *c, const char *what, bool adaptive = false)  
 
 // What the four entry points below do first: the checks, then the context's device and everything in flight finished.
 // `values` must be positive and finite; `which` names them in the refusal.
-int dn_begin(crt_ctx *c, const char *what, uint32_t iterations, const float *values, int count, const char *which, DnState state)
+static int dn_check_params(crt_ctx *c, const char *what, uint32_t iterations, const float *values, int count, const char *which)
 {
-    if (!c) return CRT_EINVAL;
     if (iterations > 10u) return fail(c, CRT_EINVAL, "%s: iterations %u > 10", what, iterations);
     for (int k = 0; k < count; k++)
         if (!(values[k] > 0.0f && values[k] <= 3.40282347e38f)) return fail(c, CRT_EINVAL, "%s: %s must be positive and finite", what, which);
+    return CRT_OK;
+}
+
+int dn_begin(crt_ctx *c, const char *what, uint32_t iterations, const float *values, int count, const char *which, DnState state)
+{
+    if (!c) return CRT_EINVAL;
+    CRT_TRY(dn_check_params(c, what, iterations, values, count, which));
     if (state == DN_UNIFORM && c->as_on) return as_refuse(c, what);
     if (state == DN_ADAPTIVE && !c->as_on)
         return fail(c, CRT_ESTATE, "%s: the context is in the uniform state (crt_denoise filters a uniform render; "
@@ -353,6 +359,143 @@ int crt_read_gbuffer(crt_ctx *c, float *out)
         HIPCHK(c, hipMemcpyAsync(out, c->dn.sets[c->dn.set].gbuf.p, n * 2 * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
     }
     return dn_finish(c, n, nullptr, nullptr, nullptr);
+}
+
+// ---------------------------------------------------------------- the frame of a partition
+// crt_comm.cpp: the assembled planes of the latest CRT_GATHER_PREVIEW (accumulator, Q, tile counts) and W, H, n -- or the refusal.
+int crt_internal_comm_frame_view(crt_ctx *c, const char *who, int adaptive, int assemble_now, const void *planes[3], uint32_t dims[3]);
+
+namespace {
+
+struct FrameView {
+    const float4 *accum = nullptr;
+    const float *q = nullptr;
+    const uint32_t *counts = nullptr;
+    uint32_t W = 0, H = 0, n = 0;
+};
+
+// How the three frame-level calls open: every refusal that needs no allocation, with nothing enqueued; then a sync point.
+int fr_begin(crt_ctx *c, const char *what, bool adaptive, FrameView &v)
+{
+    if (!c->have_scene || c->accel_mode < 0) return fail(c, CRT_ESTATE, "%s: scene + accel required", what);
+    if (c->accel_stale) return fail(c, CRT_ESTATE, "%s: primitives were updated: call crt_refit_accel or crt_build_accel first", what);
+    const void *planes[3] = {nullptr, nullptr, nullptr};
+    uint32_t dims[3] = {0, 0, 0};
+    CRT_TRY(crt_internal_comm_frame_view(c, what, adaptive ? 1 : 0, 0, planes, dims));
+    v.accum = (const float4 *)planes[0]; v.q = (const float *)planes[1]; v.counts = (const uint32_t *)planes[2];
+    v.W = dims[0]; v.H = dims[1]; v.n = dims[2];
+    return quiesce(c, false);
+}
+
+// ... and how they go on once their buffers exist: the planes in image order, on the context's stream.
+int fr_assemble(crt_ctx *c, const char *what, bool adaptive)
+{
+    const void *planes[3];
+    uint32_t dims[3];
+    return crt_internal_comm_frame_view(c, what, adaptive ? 1 : 0, 1, planes, dims);
+}
+
+// The filters' buffers (kv: the adaptive filter's) and the frame's G-buffer: one camera ray per pixel of the whole image
+// against this rank's replica of the scene.  Allocations first; a failed one leaves complete buffers or none.
+int fr_ensure(crt_ctx *c, const char *what, bool adaptive, const FrameView &v)
+{
+    crt_ctx::FrameDenoise &f = c->fdn;
+    const size_t n = (size_t)v.W * v.H;
+    if (f.guides.gbuf.n < 2 * n || f.guides.key.n < n) f.valid = false;
+    CRT_ENSURE(c, f.guides.gbuf, 2 * n);
+    CRT_ENSURE(c, f.guides.key, n);
+    CRT_ENSURE(c, f.c[0], n);
+    CRT_ENSURE(c, f.c[1], n);
+    CRT_ENSURE(c, f.rgba, n);
+    if (adaptive) {
+        CRT_ENSURE(c, f.kv, n);
+        CRT_ENSURE(c, f.var, n);
+    }
+    CRT_TRY(fr_assemble(c, what, adaptive));
+    if (!f.valid) {
+        HIPCHK(c, dn_launch_gbuffer(c->sc, 0, 0, v.W, v.H, f.guides.gbuf.p, f.guides.key.p, c->accel_mode == CRT_ACCEL_NONE, c->stream));
+        f.valid = true;
+    }
+    return CRT_OK;
+}
+
+DnFilter fr_filter(crt_ctx *c, const FrameView &v, uint32_t iterations, float sigma_normal, float sigma_plane, bool rgba)
+{
+    crt_ctx::FrameDenoise &f = c->fdn;
+    return DnFilter{f.guides.gbuf.p, f.guides.key.p, {f.c[0].p, f.c[1].p}, rgba ? f.rgba.p : nullptr, v.W, v.H, iterations,
+                    sigma_normal, sigma_plane, c->stream};
+}
+
+int fr_finish(crt_ctx *c, size_t n, const float4 *res, float *rgb_out, uint8_t *rgba8_out, float *var_out)
+{
+    if (n && rgb_out) HIPCHK(c, hipMemcpyAsync(rgb_out, res, n * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+    if (n && rgba8_out) HIPCHK(c, hipMemcpyAsync(rgba8_out, c->fdn.rgba.p, n * sizeof(uchar4), hipMemcpyDeviceToHost, c->stream));
+    if (n && var_out) HIPCHK(c, hipMemcpyAsync(var_out, c->fdn.var.p, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return wf_check_dropped(c);
+}
+
+}  // namespace
+
+int crt_denoise_frame(crt_ctx *c, const crt_denoise_params *params, float *rgb_out, uint8_t *rgba8_out)
+{
+    if (!c) return CRT_EINVAL;
+    const crt_denoise_params dp = params ? *params : kDnDefaults;
+    const float sig[3] = {dp.sigma_color, dp.sigma_normal, dp.sigma_plane};
+    CRT_TRY(dn_check_params(c, "crt_denoise_frame", dp.iterations, sig, 3, "every sigma"));
+    FrameView v;
+    CRT_TRY(fr_begin(c, "crt_denoise_frame", false, v));
+    if (v.n == 0) return fail(c, CRT_ESTATE, "crt_denoise_frame: no sample traced at the PREVIEW gather");
+    const size_t n = (size_t)v.W * v.H;
+    float4 *res = nullptr;
+    if (n) {
+        CRT_TRY(fr_ensure(c, "crt_denoise_frame", false, v));
+        const DnFilter F = fr_filter(c, v, dp.iterations, dp.sigma_normal, dp.sigma_plane, rgba8_out != nullptr);
+        HIPCHK(c, dn_launch_filter(F, v.accum, (float)v.n, dp.sigma_color, &res));
+    }
+    return fr_finish(c, n, res, rgb_out, rgba8_out, nullptr);
+}
+
+int crt_denoise_adaptive_frame(crt_ctx *c, const crt_denoise_adaptive_params *params, float *rgb_out, uint8_t *rgba8_out, float *var_out)
+{
+    if (!c) return CRT_EINVAL;
+    const crt_denoise_adaptive_params dp = params ? *params : kDnAsDefaults;
+    const float sig[3] = {dp.sigma_variance, dp.sigma_normal, dp.sigma_plane};
+    CRT_TRY(dn_check_params(c, "crt_denoise_adaptive_frame", dp.iterations, sig, 3, "every sigma"));
+    FrameView v;
+    CRT_TRY(fr_begin(c, "crt_denoise_adaptive_frame", true, v));
+    const size_t n = (size_t)v.W * v.H;
+    float4 *res = nullptr;
+    if (n) {
+        CRT_TRY(fr_ensure(c, "crt_denoise_adaptive_frame", true, v));
+        const DnFilter F = fr_filter(c, v, dp.iterations, dp.sigma_normal, dp.sigma_plane, rgba8_out != nullptr);
+        HIPCHK(c, dn_launch_filter_adaptive(F, v.accum, v.q, v.counts, c->fdn.kv.p, var_out ? c->fdn.var.p : nullptr, dp.sigma_variance, &res));
+    }
+    return fr_finish(c, n, res, rgb_out, rgba8_out, var_out);
+}
+
+int crt_read_frame_adaptive(crt_ctx *c, uint32_t *counts, float *errors)
+{
+    if (!c) return CRT_EINVAL;
+    FrameView v;
+    CRT_TRY(fr_begin(c, "crt_read_frame_adaptive", true, v));
+    const uint32_t tiles_x = (v.W + 7) / 8, tiles_y = (v.H + 7) / 8;
+    const size_t ntiles = (size_t)tiles_x * tiles_y;
+    if (ntiles) {
+        CRT_ENSURE(c, c->fdn.errors, ntiles);
+        CRT_ENSURE(c, c->fdn.flags, ntiles);
+        CRT_TRY(fr_assemble(c, "crt_read_frame_adaptive", true));
+        // E is a function of the frame's accumulator, Q and counts alone: crt_read_adaptive's kernel over the assembled frame
+        AsParams A{};
+        A.accum = v.accum; A.q = v.q; A.counts = v.counts; A.errors = c->fdn.errors.p; A.flags = c->fdn.flags.p;
+        A.tw = v.W; A.th = v.H; A.tiles_x = tiles_x; A.tiles_y = tiles_y;
+        A.min_samples = 0u; A.max_samples = 0u; A.threshold = 0.0f;
+        HIPCHK(c, as_launch_select(A, false, c->stream));
+        if (counts) HIPCHK(c, hipMemcpyAsync(counts, v.counts, ntiles * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        if (errors) HIPCHK(c, hipMemcpyAsync(errors, c->fdn.errors.p, ntiles * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return wf_check_dropped(c);
 }
 
 }  // extern "C"

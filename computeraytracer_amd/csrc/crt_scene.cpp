@@ -381,7 +381,7 @@ extern "C" {
 // Tile, row bands, bound outputs, stream, options and a communicator partition stay.
 static int edit_end(crt_ctx *c)
 {
-    c->dn.valid = false;
+    c->dn.valid = false; c->fdn.valid = false;
     return zero_state(c);
 }
 

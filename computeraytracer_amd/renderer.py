@@ -272,11 +272,11 @@ class Renderer:
         return self
 
     # -- denoised preview (include/crt.h, "Denoised preview")
-    def _denoise(self, call, p, overrides: dict, rgb: bool, plane: bool | None = None):
+    def _denoise(self, call, p, overrides: dict, rgb: bool, plane: bool | None = None, shape=None):
         """One filter call.  The overrides that are not None replace fields of the parameter struct p, as the field's
         type.  Returns rgba8, or a tuple of it, the linear rgb (rgb) and the filter's own float plane (plane; None: the
-        call has none)."""
-        _, _, tw, th = self.tile
+        call has none).  shape: (W, H) of the outputs, the tile's by default."""
+        tw, th = shape if shape else self.tile[2:]
         for k, v in overrides.items():
             if v is not None:
                 setattr(p, k, type(getattr(p, k))(v))
@@ -408,9 +408,37 @@ class Renderer:
         self._chk(self._lib.crt_comm_partition(self._h, int(band_rows)))
         return self
 
-    def gather(self, rgba8: bool = True, accum: bool = False):
-        self._chk(self._lib.crt_gather(self._h, (1 if rgba8 else 0) | (2 if accum else 0)))
+    def gather(self, rgba8: bool = True, accum: bool = False, preview: bool = False):
+        """Post the gathers of this rank's strips.  preview=True (CRT_GATHER_PREVIEW) is a sync point and ships what
+        read_frame_adaptive, denoise_frame and denoise_adaptive_frame need: the accumulator and, in the adaptive state,
+        the second moments and the tile counts."""
+        self._chk(self._lib.crt_gather(self._h, (1 if rgba8 else 0) | (2 if accum else 0) | (4 if preview else 0)))
         return self
+
+    # -- the frame of a partition (include/crt.h, "The frame of a partition"): any rank, after gather(preview=True) on every rank
+    def read_frame_adaptive(self):
+        """read_adaptive of the whole frame: (counts, errors), each (ceil(H/8), ceil(W/8))."""
+        W, H = self.image_size
+        tx, ty = (W + 7) // 8, (H + 7) // 8
+        counts = np.zeros((ty, tx), np.uint32)
+        errors = np.zeros((ty, tx), np.float32)
+        self._chk(self._lib.crt_read_frame_adaptive(self._h, counts.ctypes.data, errors.ctypes.data))
+        return counts, errors
+
+    def denoise_frame(self, iterations: int = 5, sigma_color: float = 1.0, sigma_normal: float = 0.5,
+                      sigma_plane: float = 0.3, rgb: bool = False):
+        """denoise of the gathered uniform frame, (H, W, ...) of the whole image: what one unpartitioned context returns."""
+        return self._denoise(self._lib.crt_denoise_frame, _lib.DenoiseParams(), dict(
+            iterations=iterations, sigma_color=sigma_color, sigma_normal=sigma_normal, sigma_plane=sigma_plane), rgb,
+            shape=self.image_size)
+
+    def denoise_adaptive_frame(self, iterations: int | None = None, sigma_variance: float | None = None,
+                               sigma_normal: float | None = None, sigma_plane: float | None = None, rgb: bool = False,
+                               var: bool = False):
+        """denoise_adaptive of the gathered adaptive frame, (H, W, ...) of the whole image; the same tuple."""
+        return self._denoise(self._lib.crt_denoise_adaptive_frame, _lib.denoise_adaptive_defaults(), dict(
+            iterations=iterations, sigma_variance=sigma_variance, sigma_normal=sigma_normal, sigma_plane=sigma_plane), rgb, bool(var),
+            shape=self.image_size)
 
     @property
     def image_size(self):

@@ -14,7 +14,9 @@
  *            -> { trace(spp); gather(rgba8) } x frames -> sync -> gather(rgba8 | accum); rank 0 writes the image
  *
  *   node host/multi.js --gpus 8 [--scene file.json] [--width W --height H] [--spp 64] [--frames 4] [--band 8]
- *                      [--accel bvh2|lbvh|ploc] [--out frame.ppm] [--local]
+ *                      [--accel bvh2|lbvh|ploc] [--out frame.ppm] [--local] [--denoise K]
+ *   --denoise K: the image written is the whole frame filtered with K a-trous passes (crt_denoise_frame on rank 0 after a
+ *            PREVIEW gather, include/crt.h "The frame of a partition"): what one GPU's --denoise K shows, whatever the bands.
  *   --local: all ranks in THIS process on device 0, joined by the in-process transport (CRT_COMM_LOCAL: device-to-device
  *            copies stand where the RCCL all-gather does) -- how the path is exercised on a one-GPU box.
  */
@@ -24,7 +26,7 @@ const { writePPM, loadAddon } = require('./main');
 const sceneLoader = require('./sceneLoader');
 
 const ACCEL = { none: 0, brute: 0, bvh2: 1, bvh: 1, lbvh: 2, ploc: 3 };
-const GATHER_RGBA8 = 1, GATHER_ACCUM = 2;
+const GATHER_RGBA8 = 1, GATHER_ACCUM = 2, GATHER_PREVIEW = 4;
 
 function parseArgs(argv) {
   const args = {};
@@ -61,8 +63,10 @@ function runFrames(a, ranks, opt) {
     for (const r of ranks) if (f > 0) a.gather(r.h, GATHER_RGBA8);
   }
   for (const r of ranks) a.sync(r.h);
-  for (const r of ranks) a.gather(r.h, GATHER_RGBA8 | GATHER_ACCUM);
-  const rgba = a.readFrameRgba8(ranks[0].h);                     // (an all-gather: every rank holds the frame; rank 0 reads it)
+  const denoise = opt.denoise !== undefined && opt.denoise !== true;
+  for (const r of ranks) a.gather(r.h, GATHER_RGBA8 | (denoise ? GATHER_PREVIEW : GATHER_ACCUM));
+  // (an all-gather: every rank holds the frame, and can filter it with its own replica of the scene; rank 0 does)
+  const rgba = denoise ? a.denoiseFrame(ranks[0].h, { iterations: Number(opt.denoise) }) : a.readFrameRgba8(ranks[0].h);
   const seconds = Number(process.hrtime.bigint() - t0) / 1e9;
   return { rgba, seconds, samples: spp * frames };
 }

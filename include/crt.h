@@ -218,7 +218,7 @@ int crt_image_size(crt_ctx *ctx, uint32_t out[2]);
  * gather is never complete (crt_read_frame_*: CRT_ESTATE). */
 #define CRT_COMM_ID_BYTES 128
 enum { CRT_COMM_RCCL = 0, CRT_COMM_LOCAL = 1 };
-enum { CRT_GATHER_RGBA8 = 1, CRT_GATHER_ACCUM = 2 };
+enum { CRT_GATHER_RGBA8 = 1, CRT_GATHER_ACCUM = 2, CRT_GATHER_PREVIEW = 4 /* "The frame of a partition" below */ };
 int crt_comm_unique_id(void *out_id /* CRT_COMM_ID_BYTES */, int transport);
 int crt_comm_init(crt_ctx *ctx, const void *id, int rank, int world);
 int crt_comm_partition(crt_ctx *ctx, uint32_t band_rows);
@@ -242,8 +242,8 @@ int crt_layout_rows(uint32_t H, uint32_t band_rows, uint32_t parts, uint32_t par
  * the sample count: alt_color_buffer, the rgba8 framebuffer, `sample` and the counters stay as they are.
  * Both calls are sync points like crt_read_rgba8 (every pipelined batch is finished first).  CRT_ESTATE without a
  * scene or accel structure, at sample 0, or under a row-band partition (crt_set_row_bands, crt_comm_partition with
- * band_rows > 0: neighbouring local rows are not neighbouring image rows); a crt_set_tile rectangle is filtered on its
- * own, its edges taken as image borders.  The G-buffer is built on first use and kept until crt_upload_scene,
+ * band_rows > 0: neighbouring local rows are not neighbouring image rows; crt_denoise_frame filters the gathered frame
+ * instead); a crt_set_tile rectangle is filtered on its own, its edges taken as image borders.  The G-buffer is built on first use and kept until crt_upload_scene,
  * crt_build_accel, crt_set_tile or crt_set_row_bands. */
 typedef struct {
     uint32_t iterations;   /* filter passes, step 2^i in pass i: 0..10 (0 = the plain average, as crt_read_rgba8) */
@@ -372,7 +372,8 @@ int crt_debug_hit_pad(crt_ctx *ctx, float *out);
  * In the adaptive state crt_trace, crt_sample_count, crt_read_latest_rgba8, crt_latest_sample, crt_read_sample_rgba8 and
  * crt_denoise return CRT_ESTATE; crt_read_accum / crt_read_rgba8 / crt_bind_output / counters keep working, and
  * crt_denoise_adaptive (below) is the preview filter of this state.
- * CRT_ESTATE also under a crt_comm_partition, and without a scene / accel structure or with a stale tree.  CRT_EINVAL (the
+ * CRT_ESTATE also under a crt_comm_partition whose 8x8 tiles are not the frame's (strips, bands that are no multiple of 8
+ * rows; "The frame of a partition" below), and without a scene / accel structure or with a stale tree.  CRT_EINVAL (the
  * context unchanged) for samples == 0, a negative or non-finite threshold, or max_samples != 0 && max_samples < min_samples. */
 typedef struct {
     uint32_t samples;      /* samples added to every ACTIVE tile by this call, >= 1                    */
@@ -406,8 +407,8 @@ int crt_read_adaptive(crt_ctx *ctx, uint32_t *counts, float *errors);
  * rgba8 framebuffer, counts, errors, counters and the adaptive state stay as they are, and the next crt_trace_adaptive
  * continues bit for bit.  CRT_ESTATE in the uniform state (crt_denoise filters a uniform render; crt_trace_adaptive with
  * min_samples == max_samples gives this filter a uniform one), after a crt_trace_adaptive that failed part way, without
- * a scene or accel structure, with a stale tree, or under a row-band partition.  A crt_set_tile rectangle is filtered
- * on its own. */
+ * a scene or accel structure, with a stale tree, or under a row-band partition (crt_denoise_adaptive_frame filters the
+ * gathered frame instead).  A crt_set_tile rectangle is filtered on its own. */
 typedef struct {
     uint32_t iterations;    /* 0..10, step 2^i in pass i; 0 = the plain per-tile average, as crt_read_rgba8 */
     float sigma_variance;   /* colour edge-stopping scale in standard errors; > 0 and finite */
@@ -421,6 +422,49 @@ int crt_denoise_adaptive_defaults(crt_denoise_adaptive_params *out);
  * or NULL.  CRT_EINVAL (the context unchanged) for iterations > 10 or a sigma that is not positive and finite. */
 int crt_denoise_adaptive(crt_ctx *ctx, const crt_denoise_adaptive_params *params, float *rgb_out, uint8_t *rgba8_out,
                          float *var_out);
+
+/* ------------------------------------------------------------------ The frame of a partition: adaptive sampling and previews
+ * Across a partition the three families work together:
+ *
+ * crt_trace_adaptive works under a partition made with band_rows > 0 and band_rows % 8 == 0: every local 8x8 tile is then
+ * one of the frame's, the last tile row partial exactly where the image's is.  Each rank selects, traces and commits its
+ * own tiles as an unpartitioned context does for those tiles (*active_tiles is the rank's own number; a rank without an
+ * active tile enqueues nothing and still takes part in the gathers), and the assembled frame is the unpartitioned
+ * context's bit for bit.  Contiguous strips and other bands keep refusing (CRT_ESTATE).  Rows are not rebalanced between
+ * ranks as tiles retire.
+ *
+ * crt_gather(ctx, CRT_GATHER_PREVIEW [| CRT_GATHER_RGBA8]) ships what the frame-level calls below need.  Unlike the other
+ * two flags it is a sync point for this context: it finishes what is in flight, as crt_read_adaptive does, then posts on
+ * the context's stream the gather of the accumulator (the CRT_GATHER_ACCUM one: crt_read_frame_accum sees it too) and,
+ * in the adaptive state, those of the second moment Q (4 bytes per pixel) and of the tile counts (4 bytes per tile; the
+ * tile grid is partitioned by crt_layout_rows(ceil(H/8), band_rows/8, world, rank)).  The state, the uniform sample count
+ * and the epoch of the context's frame state are recorded with it.  With CRT_COMM_LOCAL a rank whose state or sample
+ * count differs from a peer's that has posted the same gather gets CRT_EINVAL ("the ranks disagree") and posts nothing;
+ * once it holds what its peers hold it gathers again.  CRT_ESTATE after a crt_trace_adaptive that failed part way.
+ *
+ * The three calls below work on ANY rank, over the whole W x H frame of the latest PREVIEW gather, with this rank's own
+ * replica of the scene and tree; the outputs are W x H (crt_read_frame_adaptive: the frame's tile grid, ceil(W/8) x
+ * ceil(H/8), row-major; either pointer may be NULL; the errors are crt_read_adaptive's kernel run over the assembled
+ * accumulator, Q and counts).  crt_denoise_frame is crt_denoise, crt_denoise_adaptive_frame is crt_denoise_adaptive, of
+ * the frame: the same launches over a frame-sized view, so they equal what one unpartitioned context returns after the
+ * same calls, bit for bit -- under strips too, where they remove the seams of the per-strip filter.  They own frame-sized
+ * guide and colour buffers apart from the per-context filters'; the frame's G-buffer is built on first use and kept until
+ * the scene, the tree, the camera or the partition changes.  There is no temporal history at frame level:
+ * crt_denoise_temporal, crt_denoise_svgf and crt_read_motion stay per context (and keep refusing under row bands).
+ * All three are sync points that only read: accumulator, strips, counts, counters, the adaptive state and the per-context
+ * denoise state stay as they are, and the next crt_trace / crt_trace_adaptive continues bit for bit.
+ * They refuse, with nothing enqueued and nothing written: CRT_ESTATE without a communicator or with a stale partition;
+ * without a PREVIEW gather since crt_comm_partition; while a peer of a local group has not posted its PREVIEW gather; when
+ * the gathered state is not the one the call is for (crt_denoise_frame: uniform; the other two: adaptive); when the
+ * context's frame state was zeroed or replaced since the gather (crt_reset, crt_set_camera, an edit, crt_write_accum:
+ * "gather again"), or the accumulator alone was gathered again; without a scene or tree, or with a stale tree;
+ * crt_denoise_frame at n == 0.  CRT_EINVAL for what the per-context filters reject (iterations > 10, a bad sigma).
+ * CRT_ENOMEM when one of the frame-sized buffers cannot be allocated; the next call tries again.
+ * NULL params = the per-context defaults. */
+int crt_read_frame_adaptive(crt_ctx *ctx, uint32_t *counts, float *errors);
+int crt_denoise_frame(crt_ctx *ctx, const crt_denoise_params *params, float *rgb_out /* W*H*4 floats */, uint8_t *rgba8_out /* W*H*4 */);
+int crt_denoise_adaptive_frame(crt_ctx *ctx, const crt_denoise_adaptive_params *params, float *rgb_out, uint8_t *rgba8_out,
+                               float *var_out /* W*H floats */);
 
 /* ------------------------------------------------------------------ Sample offset
  * Sample s of pixel (x, y) is seeded by (x, y, s) only, and every frame after a reset draws samples 1..n again: the
