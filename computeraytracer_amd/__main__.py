@@ -1,5 +1,7 @@
 """python -m computeraytracer_amd [--scene file.json] [--width W --height H] [--spp N] [--out image.png] [--denoise K] [--orbit N [--temporal [--variance] [--animate | --animate-device [--rebuild-pct P]]]]
-                                [--adaptive THRESHOLD [--adaptive-step N] [--counts-out counts.png]]"""
+                                [--adaptive THRESHOLD [--adaptive-step N] [--counts-out counts.png]]
+--adaptive goes with --orbit: every frame is sampled adaptively up to --spp, and with --denoise K --temporal [--variance] the
+temporal filters blend it with each pixel's own tile count (option "adaptive_temporal")."""
 import argparse
 import json
 import os
@@ -8,7 +10,8 @@ import time
 from . import Renderer, image, scene
 
 
-def main():
+def parse_args(argv=None):
+    """The command line, checked: argparse's namespace, or its error exit (status 2) for a combination that does not go."""
     ap = argparse.ArgumentParser(prog="computeraytracer_amd")
     ap.add_argument("--scene", default=None, help="scene JSON in the reference's schema (default: the cornell box)")
     ap.add_argument("--width", type=int)
@@ -43,12 +46,15 @@ def main():
                          "rebuilds are printed at the end")
     ap.add_argument("--adaptive", type=float, default=None, metavar="THRESHOLD",
                     help="adaptive sampling (crt_trace_adaptive): rounds of --adaptive-step samples for the 8x8 tiles whose "
-                         "error is above THRESHOLD, --spp samples at most, until every tile is done")
+                         "error is above THRESHOLD, --spp samples at most, until every tile is done; with --orbit N every "
+                         "frame is sampled so (frame k from sample index k * spp + 1 on with --temporal) and the mean samples "
+                         "per pixel of each frame are printed")
     ap.add_argument("--adaptive-step", type=int, default=16, metavar="N", help="with --adaptive: samples per round (16)")
     ap.add_argument("--adaptive-min", type=int, default=None, metavar="M",
                     help="with --adaptive: a tile below M samples is sampled whatever its error (default: min(--spp, 2N))")
-    ap.add_argument("--counts-out", default=None, help="with --adaptive: the per-tile sample counts as a grey PNG")
-    args = ap.parse_args()
+    ap.add_argument("--counts-out", default=None,
+                    help="with --adaptive: the per-tile sample counts as a grey PNG (with --orbit: the last frame's)")
+    args = ap.parse_args(argv)
     if args.orbit is not None and (args.orbit < 1 or args.checkpoint):
         ap.error("--orbit needs N >= 1 and no --checkpoint")
     if args.temporal and (args.orbit is None or args.denoise is None):
@@ -61,10 +67,15 @@ def main():
         ap.error("--animate-device goes with --orbit N --denoise K --temporal, and not with --animate")
     if args.rebuild_pct is not None and not args.animate_device:
         ap.error("--rebuild-pct goes with --animate-device")
-    if args.adaptive is not None and (args.orbit is not None or args.checkpoint):
-        ap.error("--adaptive goes with neither --orbit nor --checkpoint")
+    if args.adaptive is not None and args.checkpoint:
+        ap.error("--adaptive does not go with --checkpoint")
     if (args.counts_out or args.adaptive_min is not None) and args.adaptive is None:
         ap.error("--counts-out and --adaptive-min need --adaptive")
+    return args
+
+
+def main(argv=None):
+    args = parse_args(argv)
     sc = scene.load_scene(args.scene)
     if args.width:
         sc["camera"]["width"], sc["camera"]["height"] = args.width, args.height or args.width
@@ -79,7 +90,9 @@ def main():
                 import numpy as np
                 r.set_option("temporal_motion", 1)
                 spheres = [int(i) for i in (ps.primitives["category"] == scene.CATEGORY["sphere"]).nonzero()[0]]
-            refits = 0
+            refits, mean_samples = 0, []
+            if args.adaptive is not None and args.temporal:
+                r.set_option("adaptive_temporal", 1)
             if args.rebuild_pct is not None:
                 r.set_option("refit_rebuild_pct", args.rebuild_pct)
             for k, cam in enumerate(scene.orbit_cameras(ps.camera, args.orbit)):
@@ -100,15 +113,28 @@ def main():
                 r.set_camera(cam)
                 if args.temporal:
                     r.set_sample_offset(k * args.spp)
-                r.frame(args.spp).sync()
+                if args.adaptive is not None:
+                    # few samples per frame, placed where the noise is, accumulated over time (option "adaptive_temporal")
+                    counts = _adaptive_rounds(r, args)[0]
+                    mean_samples.append(round(_pixel_samples(counts, ps) / (ps.width * ps.height), 4))
+                else:
+                    r.frame(args.spp).sync()
                 if args.temporal:
                     rgba = r.denoise_svgf(args.denoise) if args.variance else r.denoise_temporal(args.denoise)
+                elif args.adaptive is not None:
+                    rgba = r.read_rgba8() if args.denoise is None else r.denoise_adaptive(args.denoise)
                 else:
                     rgba = r.read_rgba8() if args.denoise is None else r.denoise(args.denoise)
                 outs.append(f"{base}_{k:03d}{ext}")
                 (image.write_ppm if ext == ".ppm" else image.write_png)(outs[-1], rgba)
             info = {"width": ps.width, "height": ps.height, "frames": args.orbit, "spp": args.spp,
                     "seconds": round(time.time() - t0, 4), "out": outs}
+            if args.adaptive is not None:
+                info["adaptive"] = args.adaptive
+                info["mean_samples"] = mean_samples               # per frame: samples per pixel
+                if args.counts_out:
+                    _write_counts(args.counts_out, counts, ps, args.spp)
+                    info["counts_out"] = args.counts_out
             if args.denoise is not None:
                 info["denoise"] = args.denoise
             if args.temporal:
@@ -143,28 +169,43 @@ def main():
         print(json.dumps(info))
 
 
-def _adaptive(r, ps, args):
-    import numpy as np
-    t0, rounds = time.time(), 0
+def _adaptive_rounds(r, args):
+    """Rounds of --adaptive-step samples until no tile is active: (the tile counts, the rounds)."""
+    rounds = 0
     min_samples = min(args.spp, 2 * args.adaptive_step) if args.adaptive_min is None else args.adaptive_min
     while r.trace_adaptive(samples=args.adaptive_step, threshold=args.adaptive, min_samples=min_samples, max_samples=args.spp):
         rounds += 1
-    counts, _ = r.read_adaptive()
+    return r.read_adaptive()[0], rounds
+
+
+def _pixel_samples(counts, ps):
+    import numpy as np
+    return int(np.repeat(np.repeat(counts, 8, 0), 8, 1)[:ps.height, :ps.width].sum(dtype=np.uint64))
+
+
+def _write_counts(path, counts, ps, spp):
+    import numpy as np
+    grey = (counts.astype(np.float64) * (255.0 / max(1, spp))).clip(0, 255).astype(np.uint8)
+    rgba = np.repeat(np.repeat(grey, 8, 0), 8, 1)[:ps.height, :ps.width, None].repeat(4, 2)
+    rgba[..., 3] = 255
+    image.write_png(path, rgba)
+
+
+def _adaptive(r, ps, args):
+    import numpy as np
+    t0 = time.time()
+    counts, rounds = _adaptive_rounds(r, args)
     dt = time.time() - t0
     rgba = r.read_rgba8() if args.denoise is None else r.denoise_adaptive(args.denoise)
     (image.write_ppm if args.out.endswith(".ppm") else image.write_png)(args.out, rgba)
-    pixel_counts = np.repeat(np.repeat(counts, 8, 0), 8, 1)[:ps.height, :ps.width]
     info = {"width": ps.width, "height": ps.height, "adaptive": args.adaptive, "rounds": rounds,
-            "pixel_samples": int(pixel_counts.sum(dtype=np.uint64)), "seconds": round(dt, 4),
+            "pixel_samples": _pixel_samples(counts, ps), "seconds": round(dt, 4),
             "tile_samples": {"min": int(counts.min()), "median": float(np.median(counts)), "max": int(counts.max())},
             "out": args.out}
     if args.denoise is not None:
         info["denoise"] = args.denoise
     if args.counts_out:
-        grey = (counts.astype(np.float64) * (255.0 / max(1, args.spp))).clip(0, 255).astype(np.uint8)
-        rgba = np.repeat(np.repeat(grey, 8, 0), 8, 1)[:ps.height, :ps.width, None].repeat(4, 2)
-        rgba[..., 3] = 255
-        image.write_png(args.counts_out, rgba)
+        _write_counts(args.counts_out, counts, ps, args.spp)
         info["counts_out"] = args.counts_out
     print(json.dumps(info))
 

@@ -404,6 +404,7 @@ static int as_begin(crt_ctx *c)
     HIPCHK(c, hipMemsetAsync(c->as_counts.p, 0, ntiles * sizeof(uint32_t), c->stream));
     HIPCHK(c, hipMemsetAsync(c->as_q.p, 0, npix * sizeof(float), c->stream));
     c->as_on = true;
+    c->as_requested = 0;
     return CRT_OK;
 }
 
@@ -436,10 +437,21 @@ int crt_trace_adaptive(crt_ctx *c, const crt_adaptive_params *params, uint32_t *
         return fail(c, CRT_ESTATE, "crt_trace_adaptive: not under this crt_comm_partition: its 8x8 tiles are not the frame's "
                                    "(a band partition with band_rows a multiple of 8 is what works)");
     if (c->as_broken) return as_refuse_broken(c, "crt_trace_adaptive");
-    if (c->sample_offset)
-        return fail(c, CRT_ESTATE, "crt_trace_adaptive: not with a sample offset (%u): crt_set_sample_offset(ctx, 0) first", c->sample_offset);
+    if (c->sample_offset && !c->adaptive_temporal)
+        return fail(c, CRT_ESTATE, "crt_trace_adaptive: not with a sample offset (%u): crt_set_sample_offset(ctx, 0) first "
+                                   "(or option \"adaptive_temporal\" = 1)", c->sample_offset);
     if (!c->as_on && c->sample > 0)
         return fail(c, CRT_ESTATE, "crt_trace_adaptive: the context holds %u uniform samples whose second moment was not kept: crt_reset first", c->sample);
+    // (no tile holds more than the calls of this adaptive state have asked for: what bounds every tile's last index)
+    const unsigned long long requested = c->as_on ? c->as_requested : 0ull;
+    if (c->sample_offset) {
+        if (!(c->pipeline == 1 && c->accel_mode == CRT_ACCEL_BVH2))
+            return fail(c, CRT_ESTATE, "crt_trace_adaptive: a sample offset needs the wavefront pipeline (\"pipeline\" = 1 and a tree): "
+                                       "crt_set_sample_offset(ctx, 0) first");
+        if ((unsigned long long)c->sample_offset + requested + p.samples > 0xFFFFFFFFull)
+            return fail(c, CRT_EINVAL, "crt_trace_adaptive: sample offset %u + %llu samples requested so far + %u pass 2^32 - 1",
+                        c->sample_offset, requested, p.samples);
+    }
     HIPCHK(c, hipSetDevice(c->device));
     if ((size_t)c->tw * c->th != 0 && (!accum_ptr(c) || !rgba_ptr(c)))
         return fail(c, CRT_ENOMEM, "crt_trace_adaptive: the tile's output buffers are not allocated (an earlier crt_set_tile / crt_set_row_bands failed)");
@@ -455,6 +467,7 @@ int crt_trace_adaptive(crt_ctx *c, const crt_adaptive_params *params, uint32_t *
     }
     if (active_tiles) *active_tiles = n_active;
     if (n_active == 0) return CRT_OK;
+    c->as_requested = requested + p.samples;
     c->last_launches = 0;
     c->last_timed = true;
     c->last_iterations = 0;
@@ -815,6 +828,11 @@ int crt_set_option(crt_ctx *c, const char *name, int64_t value)
         if (!value && (c->dn.cur.snap || c->dn.prev.snap)) c->dn.drop();    // (history across an edit is this option's)
         if (!value) c->dn.snap.release();
         c->dn.motion = value != 0;
+        return CRT_OK;
+    }
+    if (!std::strcmp(name, "adaptive_temporal")) {          // (nothing is dropped either way)
+        if (value != 0 && value != 1) return fail(c, CRT_EINVAL, "crt_set_option: adaptive_temporal is 0 or 1");
+        c->adaptive_temporal = value != 0;
         return CRT_OK;
     }
     if (!std::strcmp(name, "frame_ring")) {

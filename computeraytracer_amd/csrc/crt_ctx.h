@@ -311,6 +311,10 @@ struct crt_ctx {
     // adaptive sampling (crt_adaptive.hip): allocated by the first crt_trace_adaptive, released with the tile
     bool as_on = false;             // the adaptive state: per-tile counts instead of `sample` (left by everything that zeroes it)
     bool as_broken = false;         // a crt_trace_adaptive failed part way: the counts lag the accumulator until crt_reset
+    bool adaptive_temporal = false; // option "adaptive_temporal" (DESIGN.md 6i): crt_trace_adaptive takes the sample offset, and the
+                                    // temporal calls take the adaptive state with the tile's count as each pixel's n
+    unsigned long long as_requested = 0;   // samples the crt_trace_adaptive calls of this adaptive state have enqueued per
+                                           // active tile: no tile's count is above it
     DevBuf<uint32_t> as_counts;     // per 8x8 tile: samples it holds
     DevBuf<float> as_errors;        // per tile: E as the selection judged it
     DevBuf<uint32_t> as_flags;      // per tile: active in the last selection
@@ -373,7 +377,8 @@ uint32_t wf_overflow_levels(const crt_ctx *c);
 // crt_denoise_api.cpp: what the filters' entry points (and the debug read-outs of their state) do first -- the checks, then
 // the context's device and everything in flight finished; `values` must be positive and finite, `which` names them in
 // the refusal -- and last.
-enum DnState { DN_UNIFORM, DN_ADAPTIVE, DN_EITHER };
+// DN_TEMPORAL: the uniform state, or with option "adaptive_temporal" the adaptive one (the temporal calls).
+enum DnState { DN_UNIFORM, DN_ADAPTIVE, DN_EITHER, DN_TEMPORAL };
 int dn_begin(crt_ctx *c, const char *what, uint32_t iterations, const float *values, int count, const char *which, DnState state);
 int dn_finish(crt_ctx *c, size_t n, const float4 *res, float *rgb_out, uint8_t *rgba8_out, const float *plane = nullptr,
               float *plane_out = nullptr);

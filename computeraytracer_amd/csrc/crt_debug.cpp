@@ -208,7 +208,7 @@ int crt_debug_math(crt_ctx *c, int fn, const float *a, const float *b, float *ou
 int crt_debug_read_moments(crt_ctx *c, float *out)
 {
     if (!c || !out) return CRT_EINVAL;
-    CRT_TRY(dn_begin(c, "crt_debug_read_moments", 0, nullptr, 0, "", DN_UNIFORM));
+    CRT_TRY(dn_begin(c, "crt_debug_read_moments", 0, nullptr, 0, "", DN_TEMPORAL));
     if (!c->dn.cur.valid || c->dn.cur.frame != c->frame_id || !c->dn.cur.has_m)
         return fail(c, CRT_ESTATE, "crt_debug_read_moments: no crt_denoise_svgf in this frame yet, or a crt_denoise_temporal after it "
                                    "(the CURRENT slot carries no moments)");

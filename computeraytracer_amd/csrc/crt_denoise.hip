@@ -362,19 +362,27 @@ __device__ __forceinline__ bool dn_film_position(const DnReprojParams &P, f3 x_p
 // <*, true> (crt_denoise_svgf; tests/denoise_svgf_ref.py): the accepted taps also carry the temporal moments
 // of the luminance -- one more float4 per tap that passed every test -- and the variance they give goes out as the w of
 // the filter's input P.cv.  What reaches P.h_cur is <*, false>'s bit for bit.
-template <bool MOTION, bool MOMENTS>
-__global__ __launch_bounds__(256) void k_dn_reproject(const std::conditional_t<MOMENTS, DnSvgfParams, DnReprojParams> P)
+// <*, *, true> (option "adaptive_temporal"; tests/denoise_temporal_adaptive_ref.py): the context is in the
+// adaptive state, and the n of the pixel is the count of its 8x8 tile wherever 6e-6g say n.  Nothing else differs.
+template <bool MOMENTS, bool ADAPT>
+using DnReprojArg = std::conditional_t<ADAPT, DnAdaptive<std::conditional_t<MOMENTS, DnSvgfParams, DnReprojParams>>,
+                                       std::conditional_t<MOMENTS, DnSvgfParams, DnReprojParams>>;
+
+template <bool MOTION, bool MOMENTS, bool ADAPT>
+__global__ __launch_bounds__(256) void k_dn_reproject(const DnReprojArg<MOMENTS, ADAPT> P)
 {
     const int x = dn_x16(), y = dn_y16();
     const int tw = (int)P.tw, th = (int)P.th;
     if (x >= tw || y >= th) return;
     const size_t p = (size_t)y * P.tw + (size_t)x;
     const float4 a = P.accum[p];
-    const f3 c_new = xyz_to_linear_rgb(f3{a.x, a.y, a.z} / P.n);
+    float n = P.n;
+    if constexpr (ADAPT) n = (float)P.counts[(size_t)((uint32_t)y >> 3) * P.tiles_x + ((uint32_t)x >> 3)];
+    const f3 c_new = xyz_to_linear_rgb(f3{a.x, a.y, a.z} / n);
     f3 c = c_new;
-    float Hw = P.n;
-    const float lum = a.y / P.n;                                // y of 6g: the frame's mean luminance
-    float m1 = lum, ms = 0.0f, Mw = P.n;                          // (MOMENTS only)
+    float Hw = n;
+    const float lum = a.y / n;                                  // y of 6g: the frame's mean luminance
+    float m1 = lum, ms = 0.0f, Mw = n;                            // (MOMENTS only)
     const uint32_t key_p = P.key[p];
     if (P.h_prev && key_p != kNoHit && (key_p >> 24) != kGlass && finite4(float4{c_new.x, c_new.y, c_new.z, 0.0f})) {
         const float4 g0 = P.gbuf[2 * p], g1 = P.gbuf[2 * p + 1];
@@ -426,16 +434,16 @@ __global__ __launch_bounds__(256) void k_dn_reproject(const std::conditional_t<M
                 if (sw > 0.0f) {
                     const f3 h = sc / sw;
                     const float Hp = min_(sh / sw, P.max_history);
-                    Hw = P.n + Hp;
-                    c = (c_new * P.n + h * Hp) / Hw;
+                    Hw = n + Hp;
+                    c = (c_new * n + h * Hp) / Hw;
                     if constexpr (MOMENTS) {
                         if (P.m_prev) {                         // the pairwise merge of (lum, 0, n) with the taps' (h1, hs, Mp)
                             const float h1 = sm.x / sw, hs = sm.y / sw;
                             const float Mp = min_(sm.z / sw, P.max_history);
                             const float d = lum - h1;
-                            Mw = P.n + Mp;
-                            m1 = (lum * P.n + h1 * Mp) / Mw;
-                            ms = (Mp / Mw) * hs + ((P.n * Mp) * (d * d)) / (Mw * Mw);
+                            Mw = n + Mp;
+                            m1 = (lum * n + h1 * Mp) / Mw;
+                            ms = (Mp / Mw) * hs + ((n * Mp) * (d * d)) / (Mw * Mw);
                         }
                     }
                 }
@@ -449,7 +457,7 @@ __global__ __launch_bounds__(256) void k_dn_reproject(const std::conditional_t<M
         // the variance of the blend in display units: s / (F - 1) over F = Mw / n frames, through the exposure curve's slope
         // at m1 (as pixel_error); 1 ("nothing known", as k_dn_prepare_as) below min_frames or where it is not finite
         float v = 1.0f;
-        const float F = Mw / P.n;
+        const float F = Mw / n;
         if (F >= P.min_frames) {
             const float g = 2.2f * exp_(-2.2f * max_(m1, 0.0f));
             const float t = (g * g) * (ms / (F - 1.0f));
@@ -534,16 +542,32 @@ hipError_t dn_launch_filter(const DnFilter &F, const float4 *accum, float n, flo
     return e != hipSuccess ? e : dn_run_atrous(F, F.c[0], sigma_color, out);
 }
 
+// The instantiation of k_dn_reproject that P asks for: <true, *, *> where the PREVIOUS slot has a geometry snapshot,
+// <*, *, true> where `counts` gives every 8x8 tile its own n (the adaptive state) in place of P.n.
+template <bool MOMENTS, class Params>
+static hipError_t dn_launch_reproject(const DnFilter &F, const Params &P, const uint32_t *counts)
+{
+    if (counts) {
+        DnAdaptive<Params> A{};
+        static_cast<Params &>(A) = P;
+        A.counts = counts; A.tiles_x = (F.tw + 7u) / 8u;
+        if (P.raw_prev) hipLaunchKernelGGL((k_dn_reproject<true, MOMENTS, true>), dn_grid16(F), dim3(256), 0, F.stream, A);
+        else hipLaunchKernelGGL((k_dn_reproject<false, MOMENTS, true>), dn_grid16(F), dim3(256), 0, F.stream, A);
+    } else {
+        if (P.raw_prev) hipLaunchKernelGGL((k_dn_reproject<true, MOMENTS, false>), dn_grid16(F), dim3(256), 0, F.stream, P);
+        else hipLaunchKernelGGL((k_dn_reproject<false, MOMENTS, false>), dn_grid16(F), dim3(256), 0, F.stream, P);
+    }
+    return hipGetLastError();
+}
+
 // The blend into P.h_cur, then the passes reading h_cur first and writing c[0], c[1], ... (h_cur itself stays
-// unfiltered: it is the next frame's history).
-hipError_t dn_launch_temporal(const DnFilter &F, DnReprojParams P, float sigma_color, float4 **out)
+// unfiltered: it is the next frame's history).  counts: null, or the tile counts of the adaptive state.
+hipError_t dn_launch_temporal(const DnFilter &F, DnReprojParams P, const uint32_t *counts, float sigma_color, float4 **out)
 {
     *out = P.h_cur;
     if ((size_t)F.tw * F.th == 0) return hipSuccess;
     P.rgba = F.iterations == 0 ? F.rgba : nullptr;
-    if (P.raw_prev) hipLaunchKernelGGL((k_dn_reproject<true, false>), dn_grid16(F), dim3(256), 0, F.stream, P);
-    else hipLaunchKernelGGL((k_dn_reproject<false, false>), dn_grid16(F), dim3(256), 0, F.stream, P);
-    const hipError_t e = hipGetLastError();
+    const hipError_t e = dn_launch_reproject<false>(F, P, counts);
     return e != hipSuccess ? e : dn_run_atrous(F, P.h_cur, sigma_color, out);
 }
 
@@ -599,8 +623,9 @@ hipError_t dn_launch_filter_adaptive(const DnFilter &F, const float4 *accum, con
 }
 
 // crt_denoise_svgf: the blend into P.h_cur and the moments into P.m_cur, (c, v) into c[0], then the variance-guided passes
-// (h_cur and m_cur stay unfiltered: they are the next frame's history).
-hipError_t dn_launch_svgf(const DnFilter &F, DnSvgfParams P, uint2 *kv, float *var, float sigma_variance, float4 **out)
+// (h_cur and m_cur stay unfiltered: they are the next frame's history).  counts: as dn_launch_temporal.
+hipError_t dn_launch_svgf(const DnFilter &F, DnSvgfParams P, const uint32_t *counts, uint2 *kv, float *var, float sigma_variance,
+                          float4 **out)
 {
     *out = F.c[0];
     if ((size_t)F.tw * F.th == 0) return hipSuccess;
@@ -608,9 +633,7 @@ hipError_t dn_launch_svgf(const DnFilter &F, DnSvgfParams P, uint2 *kv, float *v
     P.rgba = last0 ? F.rgba : nullptr;
     P.var = last0 ? var : nullptr;
     P.cv = F.c[0];
-    if (P.raw_prev) hipLaunchKernelGGL((k_dn_reproject<true, true>), dn_grid16(F), dim3(256), 0, F.stream, P);
-    else hipLaunchKernelGGL((k_dn_reproject<false, true>), dn_grid16(F), dim3(256), 0, F.stream, P);
-    const hipError_t e = hipGetLastError();
+    const hipError_t e = dn_launch_reproject<true>(F, P, counts);
     return e != hipSuccess ? e : dn_run_atrous_as(F, kv, var, sigma_variance, out);
 }
 

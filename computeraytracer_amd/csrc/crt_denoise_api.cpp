@@ -33,6 +33,7 @@ int dn_begin(crt_ctx *c, const char *what, uint32_t iterations, const float *val
 {
     if (!c) return CRT_EINVAL;
     CRT_TRY(dn_check_params(c, what, iterations, values, count, which));
+    if (state == DN_TEMPORAL) state = c->as_on && c->adaptive_temporal ? DN_ADAPTIVE : DN_UNIFORM;
     if (state == DN_UNIFORM && c->as_on) return as_refuse(c, what);
     if (state == DN_ADAPTIVE && !c->as_on)
         return fail(c, CRT_ESTATE, "%s: the context is in the uniform state (crt_denoise filters a uniform render; "
@@ -265,6 +266,7 @@ static int th_blend_and_filter(crt_ctx *c, const ThCall &t, bool rgba, bool hist
     P.h_cur = cur.c.p;
     P.hist = hist ? c->dn.hist.p : nullptr;
     P.n = (float)c->sample;
+    const uint32_t *counts = c->as_on ? c->as_counts.p : nullptr;    // (dn_begin let the adaptive state in: every tile has its own n)
     P.max_history = t.max_history;
     P.normal_tol2 = (float)std::min(3.0e38, (double)t.normal_tol * t.normal_tol);
     P.plane_tol = t.plane_tol;
@@ -273,9 +275,9 @@ static int th_blend_and_filter(crt_ctx *c, const ThCall &t, bool rgba, bool hist
         P.m_prev = P.h_prev && prev.has_m ? prev.m.p : nullptr;
         P.m_cur = cur.m.p;
         P.min_frames = t.min_frames;
-        HIPCHK(c, dn_launch_svgf(F, P, c->dn.kv.p, var ? c->dn.var.p : nullptr, t.sigma_variance, res));
+        HIPCHK(c, dn_launch_svgf(F, P, counts, c->dn.kv.p, var ? c->dn.var.p : nullptr, t.sigma_variance, res));
     } else {
-        HIPCHK(c, dn_launch_temporal(F, P, t.sigma_color, res));
+        HIPCHK(c, dn_launch_temporal(F, P, counts, t.sigma_color, res));
     }
     std::memcpy(cur.cam, c->sc.cam, sizeof cur.cam);
     cur.guides = c->dn.set; cur.frame = c->frame_id;
@@ -287,7 +289,7 @@ int crt_denoise_temporal(crt_ctx *c, const crt_denoise_temporal_params *params, 
 {
     const crt_denoise_temporal_params dp = params ? *params : kDnTpDefaults;
     const float pos[6] = {dp.sigma_color, dp.sigma_normal, dp.sigma_plane, dp.max_history, dp.normal_tol, dp.plane_tol};
-    CRT_TRY(dn_begin(c, "crt_denoise_temporal", dp.iterations, pos, 6, "every sigma, tolerance and max_history", DN_UNIFORM));
+    CRT_TRY(dn_begin(c, "crt_denoise_temporal", dp.iterations, pos, 6, "every sigma, tolerance and max_history", DN_TEMPORAL));
     const size_t n = (size_t)c->tw * c->th;
     float4 *res = nullptr;
     std::vector<float> hw;                                       // (rgb_out's channel 3 is Hw: the filter passes leave it 0)
@@ -321,7 +323,7 @@ int crt_denoise_svgf(crt_ctx *c, const crt_denoise_svgf_params *params, float *r
     const float pos[6] = {dp.sigma_variance, dp.sigma_normal, dp.sigma_plane, dp.max_history, dp.normal_tol, dp.plane_tol};
     if (c && !(dp.min_frames >= 2.0f && dp.min_frames <= 3.40282347e38f))
         return fail(c, CRT_EINVAL, "crt_denoise_svgf: min_frames must be >= 2 and finite");
-    CRT_TRY(dn_begin(c, "crt_denoise_svgf", dp.iterations, pos, 6, "every sigma, tolerance and max_history", DN_UNIFORM));
+    CRT_TRY(dn_begin(c, "crt_denoise_svgf", dp.iterations, pos, 6, "every sigma, tolerance and max_history", DN_TEMPORAL));
     const size_t n = (size_t)c->tw * c->th;
     float4 *res = nullptr;
     if (n) {
@@ -336,7 +338,7 @@ int crt_denoise_svgf(crt_ctx *c, const crt_denoise_svgf_params *params, float *r
 int crt_read_motion(crt_ctx *c, float *out)
 {
     if (!c || !out) return CRT_EINVAL;
-    CRT_TRY(dn_begin(c, "crt_read_motion", 0, nullptr, 0, "", DN_UNIFORM));
+    CRT_TRY(dn_begin(c, "crt_read_motion", 0, nullptr, 0, "", DN_TEMPORAL));
     if (!c->dn.cur.valid || c->dn.cur.frame != c->frame_id)
         return fail(c, CRT_ESTATE, "crt_read_motion: no crt_denoise_temporal in this frame yet (it reports where that call's blend looked)");
     const size_t n = (size_t)c->tw * c->th;

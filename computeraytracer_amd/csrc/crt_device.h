@@ -279,6 +279,14 @@ struct DnSvgfParams : DnReprojParams {
     float min_frames;               // v is trusted from Mw / n >= this on
 };
 
+// k_dn_reproject<*, *, true>: the blend in the adaptive state, where the n of pixel p is the count of its 8x8
+// tile.  Derived from either block above, so that the <*, *, false> kernels keep theirs.
+template <class Base>
+struct DnAdaptive : Base {
+    const uint32_t *counts;         // per 8x8 tile of the rectangle, row-major: samples it holds (>= 1)
+    uint32_t tiles_x;               // ceil(tw / 8)
+};
+
 // What the launchers of the four preview filters share (crt_denoise.hip; declared in crt_launch.h).
 struct DnFilter {
     const float4 *gbuf;             // the guides: G-buffer and keys of the tile

@@ -82,8 +82,10 @@ hipError_t dn_launch_gbuffer(const DevScene &S, uint32_t x0, uint32_t y0, uint32
 hipError_t dn_launch_filter(const DnFilter &F, const float4 *accum, float n, float sigma_color, float4 **out);
 hipError_t dn_launch_filter_adaptive(const DnFilter &F, const float4 *accum, const float *q, const uint32_t *counts, uint2 *kv,
                                      float *var, float sigma_variance, float4 **out);
-hipError_t dn_launch_temporal(const DnFilter &F, DnReprojParams P, float sigma_color, float4 **out);
-hipError_t dn_launch_svgf(const DnFilter &F, DnSvgfParams P, uint2 *kv, float *var, float sigma_variance, float4 **out);
+// (counts: null in the uniform state, where P.n is every pixel's n; else the adaptive state's count per 8x8 tile)
+hipError_t dn_launch_temporal(const DnFilter &F, DnReprojParams P, const uint32_t *counts, float sigma_color, float4 **out);
+hipError_t dn_launch_svgf(const DnFilter &F, DnSvgfParams P, const uint32_t *counts, uint2 *kv, float *var, float sigma_variance,
+                          float4 **out);
 hipError_t dn_launch_motion(const DnReprojParams &P, float2 *out, hipStream_t stream);
 
 }  // namespace crt

@@ -729,7 +729,8 @@ int wf_trace_batch(crt_ctx *c, uint32_t n, const AsBatch *as)
     }
     // (adaptive: + the tile's count, in k_wf_gen.  The sample offset moves the RNG / stratum index alone: work ids, the
     // staging layout and last_sample, which the resolve pass tone-maps with and indexes the frame ring by, count from the reset)
-    const uint32_t first_sample = as ? as->off + 1u : c->sample_offset + c->published + 1u;
+    // (adaptive: the offset is 0 unless option "adaptive_temporal" let it in)
+    const uint32_t first_sample = as ? c->sample_offset + as->off + 1u : c->sample_offset + c->published + 1u;
     const uint32_t last_sample = as ? as->off + n : c->published + n;
     // counting folds counters on the host after every batch; otherwise batches are pipelined across calls
     const bool defer = c->wf_defer && !c->counting;

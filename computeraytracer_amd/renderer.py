@@ -309,7 +309,9 @@ class Renderer:
 
     # -- temporal reuse (include/crt.h, "Sample offset" and "Temporal reuse across camera moves")
     def set_sample_offset(self, offset: int):
-        """Sample j since the reset is drawn with the reference's index offset + j (set at sample 0; wavefront only)."""
+        """Sample j since the reset is drawn with the reference's index offset + j (set at sample 0; wavefront only).
+        trace_adaptive takes it with set_option("adaptive_temporal", 1), which also lets denoise_temporal, denoise_svgf
+        and read_motion work on an adaptive frame, each pixel blended with its own tile's count."""
         self._chk(self._lib.crt_set_sample_offset(self._h, int(offset)))
         return self
 

@@ -12,7 +12,10 @@
 //            frame means (denoiseSvgf)
 // --adaptive T [--adaptive-step N] [--adaptive-min M]: adaptive sampling (traceAdaptive), rounds of N (16) samples until
 //            every 8x8 tile has an error <= T or holds --spp samples; a tile below M (default min(--spp, 2N)) samples is
-//            sampled whatever its error; prints rounds, pixel-samples, seconds and the min / median / max tile count
+//            sampled whatever its error; prints rounds, pixel-samples, seconds and the min / median / max tile count.
+//            With --orbit N every frame is sampled so and its mean samples per pixel are printed; with --denoise K
+//            --temporal [--variance] besides, option "adaptive_temporal" lets frame k start at sample index k * spp + 1
+//            and the temporal filters blend every pixel with its own tile's count
 const fs = require('fs');
 const { Main, writePPM, orbitCameras } = require('./main');
 const sceneLoader = require('./sceneLoader');
@@ -40,37 +43,47 @@ if (args['pack-only']) { // dump the packed host buffers (used by the packer par
 }
 
 const spp = num('spp', 16);
-const r = Main({ sceneFile: args.scene, width: args.width ? num('width') : undefined, height: args.height ? num('height') : undefined,
-  accel: args.accel || 'bvh2', device: num('device', 0) });
-if ('adaptive' in args && args.orbit) { console.error('--adaptive does not go with --orbit'); process.exit(2); }
 if (args.temporal && !(args.orbit && 'denoise' in args)) { console.error('--temporal goes with --orbit N --denoise K'); process.exit(2); }
 if (args.variance && !args.temporal) { console.error('--variance goes with --orbit N --denoise K --temporal'); process.exit(2); }
-if (args.orbit) {
-  const n = num('orbit'), base = String(args.out || 'orbit.ppm').replace(/\.ppm$/, ''), outs = [];
-  const t1 = process.hrtime.bigint();
-  orbitCameras(r.packed.camera, n).forEach((cam, k) => {
-    r.setCamera(cam);
-    if (args.temporal) r.setSampleOffset(k * spp);
-    r.run(spp);
-    outs.push(`${base}_${String(k).padStart(3, '0')}.ppm`);
-    const rgba = args.variance ? r.denoiseSvgf({ iterations: num('denoise') })
-      : args.temporal ? r.denoiseTemporal({ iterations: num('denoise') })
-      : 'denoise' in args ? r.denoise({ iterations: num('denoise') }) : r.readRgba8();
-    writePPM(outs[k], rgba, r.width, r.height);
-  });
-  console.log(JSON.stringify({ width: r.width, height: r.height, frames: n, spp, seconds: Number(process.hrtime.bigint() - t1) / 1e9, out: outs }));
-  r.destroy();
-  process.exit(0);
-}
-if ('adaptive' in args) {
-  const step = num('adaptive-step', 16), minS = num('adaptive-min', Math.min(spp, 2 * step)), t1 = process.hrtime.bigint();
+const r = Main({ sceneFile: args.scene, width: args.width ? num('width') : undefined, height: args.height ? num('height') : undefined,
+  accel: args.accel || 'bvh2', device: num('device', 0) });
+// --adaptive: rounds of --adaptive-step samples until no tile is active; {rounds, ad: readAdaptive(), pixelSamples}
+function adaptiveRounds() {
+  const step = num('adaptive-step', 16), minS = num('adaptive-min', Math.min(spp, 2 * step));
   let rounds = 0;
   while (r.traceAdaptive({ samples: step, threshold: num('adaptive'), minSamples: minS, maxSamples: spp })) rounds++;
-  const ad = r.readAdaptive(), counts = Array.from(ad.counts).sort((a, b) => a - b);
+  const ad = r.readAdaptive();
   let pixelSamples = 0;
   for (let ty = 0; ty < ad.tilesY; ty++)
     for (let tx = 0; tx < ad.tilesX; tx++)
       pixelSamples += ad.counts[ty * ad.tilesX + tx] * Math.min(8, r.width - 8 * tx) * Math.min(8, r.height - 8 * ty);
+  return { rounds, ad, pixelSamples };
+}
+if (args.orbit) {
+  const n = num('orbit'), base = String(args.out || 'orbit.ppm').replace(/\.ppm$/, ''), outs = [], meanSamples = [];
+  const t1 = process.hrtime.bigint();
+  // --adaptive with --temporal: few samples per frame, placed where the noise is, accumulated over time
+  if ('adaptive' in args && args.temporal) r.setOption('adaptive_temporal', 1);
+  orbitCameras(r.packed.camera, n).forEach((cam, k) => {
+    r.setCamera(cam);
+    if (args.temporal) r.setSampleOffset(k * spp);
+    if ('adaptive' in args) meanSamples.push(adaptiveRounds().pixelSamples / (r.width * r.height));
+    else r.run(spp);
+    outs.push(`${base}_${String(k).padStart(3, '0')}.ppm`);
+    const rgba = args.variance ? r.denoiseSvgf({ iterations: num('denoise') })
+      : args.temporal ? r.denoiseTemporal({ iterations: num('denoise') })
+      : !('denoise' in args) ? r.readRgba8()
+      : 'adaptive' in args ? r.denoiseAdaptive({ iterations: num('denoise') }) : r.denoise({ iterations: num('denoise') });
+    writePPM(outs[k], rgba, r.width, r.height);
+  });
+  console.log(JSON.stringify({ width: r.width, height: r.height, frames: n, spp, seconds: Number(process.hrtime.bigint() - t1) / 1e9, out: outs,
+    ...('adaptive' in args ? { adaptive: num('adaptive'), mean_samples: meanSamples } : {}) }));
+  r.destroy();
+  process.exit(0);
+}
+if ('adaptive' in args) {
+  const t1 = process.hrtime.bigint();
+  const { rounds, ad, pixelSamples } = adaptiveRounds(), counts = Array.from(ad.counts).sort((a, b) => a - b);
   const seconds = Number(process.hrtime.bigint() - t1) / 1e9;
   if (args.out) writePPM(args.out, 'denoise' in args ? r.denoiseAdaptive({ iterations: num('denoise') }) : r.readRgba8(), r.width, r.height);
   const mid = counts.length >> 1, median = counts.length % 2 ? counts[mid] : (counts[mid - 1] + counts[mid]) / 2;

@@ -477,7 +477,14 @@ int crt_denoise_adaptive_frame(crt_ctx *ctx, const crt_denoise_adaptive_params *
  * scene edits, crt_upload_scene returns it to 0, and crt_write_accum(in, s) continues at index B + s + 1.  crt_trace
  * returns CRT_EINVAL if B plus the samples requested since the reset would pass 2^32 - 1.  Wavefront pipeline only: with
  * a non-zero offset crt_trace under "pipeline" = 0 or CRT_ACCEL_NONE, and crt_trace_adaptive, return CRT_ESTATE.
- * Offset 0 (the default) is the behaviour without this call. */
+ * Offset 0 (the default) is the behaviour without this call.
+ * With option "adaptive_temporal" = 1 (default 0) crt_trace_adaptive takes the offset too: sample j of a tile (j = n_t + 1,
+ * n_t + 2, ...) is drawn with the reference's index B + j, while the counts, the tone map's divisor and E keep counting
+ * from the reset; each pixel then holds the reference's samples B+1 .. B+n_t of its tile's count n_t, bit for bit.  With
+ * B != 0 it is the wavefront pipeline's alone (CRT_ESTATE under "pipeline" = 0 or CRT_ACCEL_NONE, as crt_trace), and
+ * CRT_EINVAL, the context unchanged, if B plus the samples that the crt_trace_adaptive calls of this adaptive state have
+ * requested, this call's included, would pass 2^32 - 1 (that sum bounds every tile's count).  The offset is still set at
+ * sample 0 in the uniform state: crt_set_camera, crt_set_sample_offset, then the adaptive rounds. */
 int crt_set_sample_offset(crt_ctx *ctx, uint32_t offset);
 int crt_sample_offset(crt_ctx *ctx, uint32_t *out);
 
@@ -514,7 +521,17 @@ int crt_sample_offset(crt_ctx *ctx, uint32_t *out);
  * A sync point like crt_denoise, and it only READS the accumulator and the sample count: accumulator, rgba8
  * framebuffer, counters and frame ring stay as they are and the next crt_trace continues bit for bit.  CRT_ESTATE where
  * crt_denoise returns it (no scene or tree, a stale tree, sample 0, row bands, the adaptive state).  A crt_set_tile
- * rectangle is filtered on its own. */
+ * rectangle is filtered on its own.
+ * The adaptive state: with option "adaptive_temporal" = 1 (default 0) crt_denoise_temporal, crt_denoise_svgf,
+ * crt_read_motion and crt_debug_read_moments accept the adaptive state, and refuse it after a
+ * crt_trace_adaptive that failed part way, as crt_denoise_adaptive does.  The definition is the one above and that of
+ * "Variance-guided temporal filter" with one substitution: wherever n stands for pixel p it is n_p, the count of p's 8x8
+ * tile as a float -- in c_new = M (accum / n_p) and y = accum.y / n_p, in Hw = n_p + Hp and c = (n_p c_new + Hp h) / Hw, in
+ * Mw = n_p + Mp and the merge of the moments, and in F = Mw / n_p.  Taps, tests, weights, caps, passes, slots, promotion,
+ * frame notion, "temporal_motion" and outputs are unchanged, and where every tile holds the same count the calls return
+ * what they return for a uniform render of that count, bit for bit.  Entering or leaving the adaptive state drops no
+ * history: a uniform frame may precede an adaptive one and the reverse.  Setting the option back to 0 makes the calls
+ * refuse the adaptive state again and drops nothing.  Row bands keep refusing. */
 typedef struct {
     uint32_t iterations;    /* a-trous passes after the blend, 0..10 */
     float sigma_color;      /* as crt_denoise_params */
@@ -616,6 +633,9 @@ int crt_last_kernel_ms(crt_ctx *ctx, float *ms, uint32_t *launches);
  * rgba8 frame of each of the last F samples for crt_read_sample_rgba8; 0 = off);
  * "temporal_motion" (0 | 1, anything else is CRT_EINVAL: 1 keeps the history of crt_denoise_temporal across
  * crt_update_primitives, see "Temporal reuse"; costs 80 bytes per primitive on the device once an edit has happened);
+ * "adaptive_temporal" (0 | 1, anything else is CRT_EINVAL; default 0: 1 lets crt_trace_adaptive take the sample offset
+ * and the temporal filters take the adaptive state, each pixel blended with its own tile's count, see "Sample offset"
+ * and "Temporal reuse"; with 0 every call launches what it launches without the option);
  * "ploc_radius" (1..32, anything else is CRT_EINVAL; default 8: clusters searched to either side by CRT_ACCEL_PLOC; at
  * crt_build_accel);
  * "refit_rebuild_pct" (0 = off, default | 100..100000, anything else is CRT_EINVAL: crt_refit_accel rebuilds once the
