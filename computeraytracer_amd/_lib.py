@@ -71,6 +71,7 @@ SIGNATURES = {
     "crt_debug_read_accel": (C.c_int, [_P, C.c_int, _P, C.c_size_t, _P]),
     "crt_debug_probes": (C.c_int, [_P, _P]),
     "crt_debug_gen_culled": (C.c_int, [_P, _P]),
+    "crt_debug_deferred_nee": (C.c_int, [_P, _P]),
     "crt_debug_tile_classes": (C.c_int, [_P, _P, C.c_size_t]),
     "crt_debug_tile_classes_host": (C.c_int, [_P, _P, C.c_size_t]),
     "crt_debug_tile_class_setups": (C.c_int, [_P, _P]),

@@ -703,7 +703,10 @@ int crt_reset_counters(crt_ctx *c)
     HIPCHK(c, hipMemsetAsync(c->d_counters.p, 0, CRT_NCOUNTERS * sizeof(unsigned long long), c->stream));
     // (k_wf_gen's own count lives in the pipes' control blocks; every run's pipes start behind the context's stream)
     for (int p = 0; p < crt_ctx::kMaxPipes; p++)
-        if (c->w_ctl[p].p) HIPCHK(c, hipMemsetAsync(&c->w_ctl[p].p->gen_culled[0], 0, sizeof(unsigned long long) * kWfShards, c->stream));
+        if (c->w_ctl[p].p) {
+            HIPCHK(c, hipMemsetAsync(&c->w_ctl[p].p->gen_culled[0], 0, sizeof(unsigned long long) * kWfShards, c->stream));
+            HIPCHK(c, hipMemsetAsync(&c->w_ctl[p].p->deferred_nee[0], 0, sizeof(unsigned long long) * kWfShards, c->stream));
+        }
     return CRT_OK;
 }
 
@@ -716,6 +719,21 @@ int crt_debug_gen_culled(crt_ctx *c, uint64_t *out)
         if (!c->w_ctl[p].p) continue;
         unsigned long long sh[kWfShards];
         HIPCHK(c, hipMemcpy(sh, &c->w_ctl[p].p->gen_culled[0], sizeof sh, hipMemcpyDeviceToHost));
+        for (uint32_t s_ = 0; s_ < kWfShards; s_++) n += sh[s_];
+    }
+    *out = n;
+    return CRT_OK;
+}
+
+int crt_debug_deferred_nee(crt_ctx *c, uint64_t *out)
+{
+    if (!c || !out) return CRT_EINVAL;
+    CRT_TRY(quiesce(c, true));
+    uint64_t n = 0;
+    for (int p = 0; p < crt_ctx::kMaxPipes; p++) {
+        if (!c->w_ctl[p].p) continue;
+        unsigned long long sh[kWfShards];
+        HIPCHK(c, hipMemcpy(sh, &c->w_ctl[p].p->deferred_nee[0], sizeof sh, hipMemcpyDeviceToHost));
         for (uint32_t s_ = 0; s_ < kWfShards; s_++) n += sh[s_];
     }
     *out = n;
@@ -845,6 +863,7 @@ int crt_set_option(crt_ctx *c, const char *name, int64_t value)
     if (!std::strcmp(name, "wf_trace_form")) { c->wf_trace_form = value == 1 ? 1 : 2; return CRT_OK; }
     if (!std::strcmp(name, "wf_cull_miss")) { c->wf_cull_miss = value != 0; return CRT_OK; }
     if (!std::strcmp(name, "wf_cull_classes")) { c->wf_cull_classes = value != 0; return CRT_OK; }
+    if (!std::strcmp(name, "wf_defer_nee")) { c->wf_defer_nee = value != 0; return CRT_OK; }
     if (!std::strcmp(name, "wf_pipes")) { c->wf_pipes = (int)std::min<int64_t>(crt_ctx::kMaxPipes, std::max<int64_t>(1, value)); return CRT_OK; }
     if (!std::strcmp(name, "wf_pool")) { c->wf_pool = (uint32_t)std::max<int64_t>(0, value); return CRT_OK; }
     if (!std::strcmp(name, "wf_waves_per_cu")) { c->wf_waves_per_cu = (uint32_t)std::min<int64_t>(32, std::max<int64_t>(0, value)); return CRT_OK; }

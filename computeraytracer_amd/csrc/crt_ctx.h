@@ -189,6 +189,7 @@ struct crt_ctx {
     DevBuf<uint4> w_rng, w_misc, w_recC;
     DevBuf<float2> w_hit;
     DevBuf<uint32_t> w_vis, w_dead, w_tea;
+    DevBuf<uint8_t> w_dflag;        // per slot: a deferred NEE entry waits in w_nee
     DevBuf<uint32_t> w_tile_cls;    // per 8x8 tile of the tile rectangle: 2 bits, what its camera rays' root step is for every sample
     static constexpr int kMaxPipes = crt::kWfMaxPipes;
     int wf_pipes = 2;
@@ -198,6 +199,7 @@ struct crt_ctx {
     int wf_trace_form = 2;          // traversal kernel: 2 = k_wf_trace2 (ray ring + primitive tasks), 1 = k_wf_trace
     int wf_cull_miss = 1;           // k_wf_gen decides whole work chunks whose camera rays all miss the tree's root boxes
     int wf_cull_classes = 1;        // ... and looks the tile's class up first: the tiles that miss or enter for every sample are classified once per run
+    int wf_defer_nee = 1;           // k_wf_shade finishes a path roulette ends at once and defers its pending NEE term
     uint64_t tile_cls_setups = 0;   // run set-ups that launched k_wf_tile_classes so far (crt_debug_tile_class_setups)
     bool cie_zero = false;          // the uploaded CIE table turns zero radiance into +0 for every wavelength (tc_culled_is_zero)
     int wf_chunk = 1;               // iterations per status record at most

@@ -101,6 +101,7 @@ struct AsParams {
 //   misc    (work id, flags, last_bounce_pdf bits, etaScale bits); a fresh slot (kWfFresh): (work id, flags, sample, tea seed)
 //   hit     (t, hit slot bits)            written by the trace kernel for extension rays
 //   vis     in: light primitive index, out: 1 = light visible    (shadow rays)
+//   dflag   one byte: a deferred NEE entry waits in nee[slot] (WfParams::dflag)
 //   list[parity][class]                   slots with an active ray this iteration (ballot/popc compacted)
 //   staging[b] (xyz, -) per (sample, pixel)  finished samples of the batch with id b, summed in sample order by k_wf_resolve
 constexpr uint32_t kWfAlive = 1u, kWfDying = 2u, kWfShadow = 4u, kWfSpecular = 8u, kWfInTrans = 16u;
@@ -145,6 +146,7 @@ struct WfCtl {                       // device control block, one per context
                                      // k_wf_finish): must stay 0 -- the host turns anything else into CRT_EDEVICE
     uint32_t max_sp[kWfShards];      // counting traversal kernels only: the deepest stack (entries) a lane of the shard's waves reached
     unsigned long long gen_culled[kWfShards];   // (pixel, sample) k_wf_gen decided without a slot (its CULL form), always counted: crt_debug_gen_culled
+    unsigned long long deferred_nee[kWfShards]; // paths k_wf_shade finished at once with their NEE term deferred, always counted: crt_debug_deferred_nee
 };
 // The work queue is shared by the pipes of a context (two half-pools run on two streams so that
 // one half's streaming shade pass overlaps the other half's latency-bound traversal).  There are kWfRing
@@ -241,7 +243,15 @@ struct WfParams {
     // k_wf_tile_classes at run set-up and read-only during the run; null = k_wf_gen's CULL form tests every sample
     const uint32_t *tile_cls;
     uint32_t cls_miss_zero;          // a culled path's staging value is +0 for every wavelength (tc_culled_is_zero): MISS chunks store the constant
+    // DESIGN.md 5.10 (option "wf_defer_nee"): a path that roulette ends with its NEE shadow ray pending finishes in that
+    // shade step and frees its slot; what stays behind is a deferred entry -- nee[slot] = (the sample's XYZ WITH the term,
+    // staging cell index) and dflag[slot] = kWfDeferred | batch id -- which the slot's thread of the pipe's NEXT shade
+    // launch turns into a staging store iff vis[slot] == 1, whatever the slot holds by then.
+    uint8_t *dflag;                  // one byte per slot, 0 = no entry
+    uint32_t defer;                  // k_wf_shade: create such entries in this launch (the host: rearm && wf_defer_nee; I11 of crt_wf_driver.cpp)
 };
+constexpr uint32_t kWfDeferred = 0x80u;                         // WfParams::dflag: an entry is pending; the low 5 bits are its batch id
+static_assert(kWfRing <= 32u, "a deferred entry's batch id has 5 bits");
 
 // k_dn_reproject (crt_denoise.hip): the blend of a frame with the reprojected history of the previous one.
 // The projection into the previous film plane is binary64 (binary32 places a tap no better than 5e-5 pixel at 480 pixels,

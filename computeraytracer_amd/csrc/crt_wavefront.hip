@@ -222,7 +222,7 @@ __device__ __forceinline__ f4 nee_term(const DevScene &S, const LightRec &L, f3 
 }
 
 struct ShadeCnt { uint32_t rays = 0, bounces = 0, shadow = 0, hits = 0, paths = 0, prims = 0, walk = 0; };
-struct ShadowOut { bool emit; f3 d; float t_l; uint32_t l_index, l_slot; };
+struct ShadowOut { bool emit; f3 d; float t_l; uint32_t l_index, l_slot; f4 c; };   // c: the very term stored to nee[slot]
 
 // compute_light_radiance (:379-408) from the sampled point on the light to the visibility test: intersects the light's own
 // primitive (shadow_intersect's "closest hit == the light", :697-705, starts there), and either adds what can be decided
@@ -232,7 +232,7 @@ __device__ __forceinline__ ShadowOut light_sample(const WfParams &P, const Light
                                                   float u, float v2, f4 brdf, f4 beta, f4 &radiance, bool &rad_dirty, const uint32_t wl[4], ShadeCnt &cn)
 {
     const DevScene &S = P.sc;
-    ShadowOut out{false, f3{0.0f, 0.0f, 0.0f}, 0.0f, 0u, 0u};
+    ShadowOut out{false, f3{0.0f, 0.0f, 0.0f}, 0.0f, 0u, 0u, f4{0.0f, 0.0f, 0.0f, 0.0f}};
     f3 pl = (xyz(L.L0) + xyz(L.L1) * u) + xyz(L.L2) * v2;
     f3 ldir = normalize(pl - pos);
     const uint32_t include = f_bits(L.L1.w);
@@ -283,7 +283,7 @@ __device__ __forceinline__ ShadowOut light_sample(const WfParams &P, const Light
                 P.sh_d[slot] = float4{ldir.x, ldir.y, ldir.z, t_l};   //  traversal kernel from the ray records)
                 P.vis[slot] = include;
             }
-            out = ShadowOut{true, ldir, t_l, include, l_slot};
+            out = ShadowOut{true, ldir, t_l, include, l_slot, c};
             if (COUNT) cn.walk++;
         }
     }
@@ -294,6 +294,7 @@ __device__ __forceinline__ ShadowOut light_sample(const WfParams &P, const Light
 // R.exclude) and the shadow ray, if one is emitted (it starts where the extension ray does).
 struct ShadeOut {
     bool alive, emit_ext, emit_sh, sh_primary, rad_dirty; uint32_t batch;
+    bool deferred;                  // the path finished in this step and left a deferred NEE entry behind
     PathRegs R;
     f3 sd; float t_l; uint32_t l_index, l_slot;
 };
@@ -321,20 +322,30 @@ __device__ __forceinline__ ShadeOut shade_body(const WfParams &P, uint32_t slot,
     uint4 misc = uint4{0, 0, 0, 0}, rs = uint4{0, 0, 0, 0};
     float4 v_ro = float4{0, 0, 0, 0}, v_rd = v_ro, v_beta = v_ro, v_rad = v_ro, v_nee = v_ro;
     float2 h = float2{0.0f, 0.0f};
-    uint32_t vis_in = 0;
+    uint32_t vis_in = 0, dflag = 0;
     if (in_pool) {
         misc = ldnt(&P.misc[slot]); v_ro = ldnt(&P.ray_o[slot]); v_rd = ldnt(&P.ray_d[slot]); v_beta = ldnt(&P.beta[slot]);
         v_rad = ldnt(&P.radiance[slot]); rs = ldnt(&P.rng[slot]); h = ldnt(&P.hit[slot]); vis_in = ldnt(&P.vis[slot]);
 #ifndef CRT_WHATIF_NO_NEE                 /* sensitivity probe (wrong image): the pass without the nee stream */
         v_nee = ldnt(&P.nee[slot]);
 #endif
+        if (!FINISH) dflag = P.dflag[slot];
     }
     CRT_PROBE(tp, 1)
+    // 0. The deferred NEE entry the slot's LAST path left behind, whatever the slot holds now -- nothing,
+    // or a fresh path, which first writes nee[slot] behind the load above and cannot leave an entry itself in its first
+    // step (roulette starts at depth 2).  The traversal launch between that shade launch and this one has stored the
+    // shadow ray's visibility to vis[slot]: visible, the sample's staging cell gets the value WITH the term.
+    if (!FINISH && (dflag & kWfDeferred)) {
+        if (vis_in == 1u) stnt(&P.staging[dflag & (kWfRing - 1u)][f_bits(v_nee.w)], float4{v_nee.x, v_nee.y, v_nee.z, 0.0f});
+        P.dflag[slot] = (uint8_t)0;
+    }
     R.work = misc.x; R.flags = misc.y; R.last_pdf = bits_f(misc.z); R.etaScale = bits_f(misc.w);
     bool alive = in_pool && (R.flags & kWfAlive);
     bool emit_ext = false, emit_sh = false;
     bool sh_primary = false;                          // ray class: shadow ray of a camera-ray hit
-    bool finished = false, rad_dirty = false;
+    bool finished = false, rad_dirty = false, deferred = false;
+    f4 sh_c = f4{0.0f, 0.0f, 0.0f, 0.0f};             // the NEE term of the shadow ray emitted in this step
     f3 out_sd = f3{0, 0, 0}; float out_tl = 0.0f; uint32_t out_lindex = 0, out_lslot = 0;   // the shadow ray, if one is emitted
     // A non-finite camera ray of k_wf_gen (the camera itself is not finite) has not been traced: this step only re-emits it,
     // and the write-back below decides it with the reference loop like any other non-finite ray (shade_store) -- the path
@@ -443,6 +454,7 @@ __device__ __forceinline__ ShadeOut shade_body(const WfParams &P, uint32_t slot,
                             sh_primary = depth == 0u;
                             R.flags |= kWfShadow;
                             out_sd = sh.d; out_tl = sh.t_l; out_lindex = sh.l_index; out_lslot = sh.l_slot;
+                            sh_c = sh.c;
                         }
                         f3 new_direction = cosine_hemisphere(R.rng, nrm, R.last_pdf);
                         float cos_theta2 = abs_(dot(nrm, new_direction));
@@ -486,7 +498,9 @@ __device__ __forceinline__ ShadeOut shade_body(const WfParams &P, uint32_t slot,
                         }
                     }
                     if (rr_break) {
-                        if (emit_sh) R.flags |= kWfDying;        // wait for the NEE visibility, then finish
+                        // (pool, in a launch the host has flagged: the path finishes now, its NEE term is deferred)
+                        if (emit_sh && !FINISH && P.defer) { finished = true; deferred = true; }
+                        else if (emit_sh) R.flags |= kWfDying;   // wait for the NEE visibility, then finish
                         else finished = true;
                     } else {
                         depth++;
@@ -503,17 +517,28 @@ __device__ __forceinline__ ShadeOut shade_body(const WfParams &P, uint32_t slot,
             const uint32_t tile = pp >> 6, l = pp & 63u;
             const uint32_t lx = (tile % P.tiles_x) * 8u + (l & 7u), ly = (tile / P.tiles_x) * 8u + (l >> 3);
             f3 c = spectral_to_xyz(S, R.radiance, wl);
-            stnt(&P.staging[(R.flags >> kWfBatchShift) & (kWfRing - 1u)][(size_t)sample_off * ((size_t)P.tw * P.th) + (size_t)ly * P.tw + lx], float4{c.x, c.y, c.z, 0.0f});
+            const size_t cell = (size_t)sample_off * ((size_t)P.tw * P.th) + (size_t)ly * P.tw + lx;
+            stnt(&P.staging[(R.flags >> kWfBatchShift) & (kWfRing - 1u)][cell], float4{c.x, c.y, c.z, 0.0f});
+            if (!FINISH && deferred) {
+                // What the kWfDying step would store one iteration later with the light visible: the radiance that step
+                // rebuilds is the one in registers here, the term it adds is sh_c as light_sample stored it, and the
+                // conversion is this function with these wavelengths.  (cell < work id, which fits 32 bits: wf_batch_cap.)
+                const f3 c1 = spectral_to_xyz(S, R.radiance + sh_c, wl);
+                stnt(&P.nee[slot], float4{c1.x, c1.y, c1.z, bits_f((uint32_t)cell)});
+                P.dflag[slot] = (uint8_t)(kWfDeferred | ((R.flags >> kWfBatchShift) & (kWfRing - 1u)));
+            }
             alive = false;
             if (COUNT) cn.paths++;
         }
     }
 
     CRT_PROBE(tp, 3)
+    const uint32_t batch = (R.flags >> kWfBatchShift) & (kWfRing - 1u);
     if (!alive) R.flags = 0;
     ShadeOut so;
+    so.deferred = deferred;
     so.alive = alive; so.emit_ext = emit_ext; so.emit_sh = emit_sh; so.sh_primary = sh_primary; so.rad_dirty = rad_dirty;
-    so.batch = (R.flags >> kWfBatchShift) & (kWfRing - 1u);
+    so.batch = batch;
     so.R = R; so.sd = out_sd; so.t_l = out_tl; so.l_index = out_lindex; so.l_slot = out_lslot;
     return so;
 }
@@ -701,14 +726,20 @@ __global__ __launch_bounds__(CRT_WF_SHADE_BLOCK, CRT_WF_SHADE_MIN_WAVES) void k_
             if (m3) b3 = atomicAdd(&sh.n[3], (uint32_t)__popcll(m3));
             if (md) bd = atomicAdd(&sh.n_dead, (uint32_t)__popcll(md));
         }
+        if (P.defer) {                                           // (crt_debug_deferred_nee; nothing waits for it)
+            const unsigned long long mq = __ballot(so.deferred);
+            if (lane == 0 && mq) atomicAdd(&ctl->deferred_nee[my_shard], (unsigned long long)__popcll(mq));
+        }
         if (P.count_alive) {
             // paths still in the pool, per batch id: the host retires a batch (eviction of its last paths, resolve)
             // by these counts (k_wf_gen adds the paths it starts).  A wave holds paths of one to three batches as a
-            // rule: one ballot + atomic for each.
-            unsigned long long am = __ballot(so.alive);
+            // rule: one ballot + atomic for each.  A deferred NEE entry counts in the slot's place for the iteration the
+            // slot used to be held (kWfDying): the host sees the timeline it saw before (I11 of crt_wf_driver.cpp).
+            const bool held = so.alive || so.deferred;
+            unsigned long long am = __ballot(held);
             while (am) {
                 const uint32_t b = (uint32_t)__shfl((int)so.batch, __ffsll((long long)am) - 1, 64);
-                const unsigned long long m = __ballot(so.alive && so.batch == b);
+                const unsigned long long m = __ballot(held && so.batch == b);
                 if (lane == 0) atomicAdd(&sh.alive[b], (uint32_t)__popcll(m));
                 am &= ~m;
             }
@@ -2063,7 +2094,7 @@ __global__ __launch_bounds__(64) void k_wf_tile_classes(const WfParams P, uint32
 __global__ void k_wf_init(const WfParams P)
 {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    if (i < P.P && !P.keep_pool) P.misc[P.slot_base + i] = uint4{0, 0, 0, 0};
+    if (i < P.P && !P.keep_pool) { P.misc[P.slot_base + i] = uint4{0, 0, 0, 0}; P.dflag[P.slot_base + i] = (uint8_t)0; }
     if (i < kWfShards) {
         WfCtl *c = P.ctl;
         if (!P.keep_pool)

@@ -79,6 +79,7 @@ static int wf_ensure(crt_ctx *c, size_t P, size_t staging_elems, size_t list_ele
     CRT_ENSURE(c, c->w_misc, P);
     CRT_ENSURE(c, c->w_hit, P);
     CRT_ENSURE(c, c->w_vis, P);
+    CRT_ENSURE(c, c->w_dflag, P);
     for (uint32_t b = 0; b < ring; b++)
         CRT_ENSURE(c, c->w_staging[b], staging_elems);
     CRT_ENSURE(c, c->w_tea, (size_t)c->tw * c->th);
@@ -192,15 +193,15 @@ static int wf_enqueue(crt_ctx *c, int p, uint32_t iters)
     WfParams &W = r.W[p];
     const hipStream_t stream = r.stream[p];
     if (pp.it - pp.it_confirmed + iters >= (uint32_t)kStatusRing || iters == 0) return fail(c, CRT_EDEVICE, "wavefront driver: status ring overrun");
-    W.tail_bound = pp.tail_bound;
     W.count_alive = r.open.size() > 1 ? 1u : 0u;
     wf_set_queues(c, W);
-    // Dead slots are listed by the shade launch and re-armed by a k_wf_gen launch behind it while a listed queue may
-    // hold work (the host's view lags the device's: a launch too many finds the queues dry, a launch too few leaves
-    // the slots dead for one more iteration).
-    W.rearm = (pp.tail_bound == 0u && r.work_left) ? 1u : 0u;
     const bool evicted = pp.evict_next != 0;
     for (uint32_t k = 0; k < iters; k++, pp.it++) {
+        // Dead slots are listed by the shade launch and re-armed by a k_wf_gen launch behind it while a listed queue may
+        // hold work (the host's view lags the device's: a launch too many finds the queues dry, a launch too few leaves
+        // the slots dead for one more iteration).  (I11: a sweep of the whole pool behind a launch that deferred.)
+        const WfLaunchMode mode = wf_launch_mode(pp, r.work_left, c->wf_defer_nee != 0);
+        W.tail_bound = mode.tail_bound; W.rearm = mode.rearm; W.defer = mode.defer;
         W.evict_mask = pp.evict_next;
         W.status_out = pp.it > pp.it_first ? c->d_status[p] + (pp.it - 1u) % kStatusRing : nullptr;
         HIPCHK(c, wf_launch_shade(W, pp.it, stream));
@@ -456,6 +457,24 @@ static bool wf_has_room(crt_ctx *c)
 //      may come from the other pipe's status, and a frame that is culled whole or nearly so lists no rays while its work
 //      is still being taken, which without the cull practically never happened).  The batches still open when the flush
 //      loop ends are resolved behind ev_join of every pipe.
+//  I11 A deferred NEE entry (option "wf_defer_nee") stands where its slot stood.  Shade launch i of a pipe,
+//      flagged `defer` (= rearm && wf_defer_nee), finishes a path that roulette ends with its shadow ray pending, frees
+//      the slot and leaves an entry in nee[slot] / dflag[slot]; the slot's thread of launch i + 1 -- behind traversal launch
+//      i in the stream -- stores the sample's final value iff the ray was visible and clears the entry.  The host sees
+//      the timeline of the kWfDying route it replaces: the entry's shadow ray is in `rays` of iteration i and, where the
+//      launch counts, the entry is in `alive[batch]` of iteration i; launch i + 1 adds nothing for it.  So whatever lets
+//      the batch drain, be evicted or retire is a status of iteration i + 1 or later, which launch i + 2 writes -- the
+//      host has READ it only when launch i + 1, and the fix-up store with it, has completed, before a finish or resolve
+//      pass is enqueued (the argument of I10).  An evicting launch sweeps the pool (below), so it also consumes the
+//      entries of the batches it evicts, ahead of the ev_evict it records for k_wf_finish and the resolve.
+//      What makes this hold is that EVERY slot is visited by the launch behind one that deferred: tail mode visits only
+//      the slots the ray lists name, and would miss an entry whose slot stayed dead or visit a re-armed slot twice
+//      (through its camera-ray entry and through the old shadow entry).  Hence the rule: a pipe's launch is a pool sweep
+//      whenever its previous launch had `defer` on, whatever pp.tail_bound says (wf_launch_mode, crt_wf_policy.h, which
+//      alone keeps pp.last_defer).  Tail mode is chosen only when no work is left, when rearm and with it defer are off:
+//      the sweep is one launch per run end at most, it creates no entry itself, and tail mode starts with the launch
+//      after it.  The flush's final evicting launch obeys the same rule, so no entry outlives a run; k_wf_init clears
+//      the flags of a pool that is set up afresh (a run abandoned after an error may have left some).
 //
 // Feed the pool: enqueue the iterations the published work needs (see the head of this section).  for_room = false:
 // return once they are enqueued (the call does not wait for its work); for_room = true: keep feeding and reading
@@ -774,9 +793,9 @@ int wf_trace_batch(crt_ctx *c, uint32_t n, const AsBatch *as)
             W.sc = c->sc;
             W.ray_o = c->w_ray_o.p; W.ray_d = c->w_ray_d.p; W.sh_d = c->w_sh_d.p; W.beta = c->w_beta.p;
             W.radiance = c->w_radiance.p; W.nee = c->w_nee.p; W.rng = c->w_rng.p; W.misc = c->w_misc.p;
-            W.hit = c->w_hit.p; W.vis = c->w_vis.p;
+            W.hit = c->w_hit.p; W.vis = c->w_vis.p; W.dflag = c->w_dflag.p;
             W.dead = c->w_dead.p + (g.list_per_pipe / 8) * (size_t)p;
-            W.rearm = 0;
+            W.rearm = 0; W.defer = 0;
             W.gen_blocks = wf_gen_blocks(o, g.list_cap);
             W.cull_miss = c->wf_cull_miss ? 1u : 0u;
             W.recA = c->w_recA.p + g.list_per_pipe * (size_t)p; W.recB = c->w_recB.p + g.list_per_pipe * (size_t)p;

@@ -47,6 +47,7 @@ struct WfPipeView {
     bool dry[kWfRing] = {};         // a status of this pipe saw that batch's queue empty (its OWN view: its count of
                                     // alive paths only bounds the future once no more such paths can start here)
     uint32_t evict_next = 0;        // evict_mask for the next shade launch
+    bool last_defer = false;        // the last shade launch enqueued for this pipe could leave deferred NEE entries (WfParams::defer)
 };
 
 // A batch of samples whose paths are (or may still be) in flight.
@@ -280,6 +281,22 @@ inline bool wf_tail_walk(WfView &r, const WfOptions &o, int p)
     pp.tail_bound = std::max<uint32_t>(64u, (pp.bound + 63u) & ~63u);
     pp.blocks_now = (uint32_t)std::min<unsigned long long>(r.trace_blocks, std::max<unsigned long long>(64, pp.rays / 32u + 64u));
     return true;
+}
+
+// The mode of pipe pp's next shade launch (wf_enqueue asks once per launch).  rearm: dead slots are listed and a k_wf_gen
+// launch follows -- in pool mode, while the host sees work in a queue.  defer: the launch may leave deferred NEE entries
+// (option "wf_defer_nee"); a slot freed early is worth something only while there is work to put into
+// it.  I11 of crt_wf_driver.cpp: the launch behind one that deferred visits EVERY slot of the pool -- tail mode, which
+// walks the ray lists, waits one iteration (a sweep that neither re-arms nor defers).
+struct WfLaunchMode { uint32_t tail_bound, rearm, defer; };
+inline WfLaunchMode wf_launch_mode(WfPipeView &pp, bool work_left, bool defer_nee)
+{
+    WfLaunchMode m;
+    m.tail_bound = pp.last_defer ? 0u : pp.tail_bound;
+    m.rearm = (pp.tail_bound == 0u && work_left) ? 1u : 0u;
+    m.defer = (m.rearm && defer_nee) ? 1u : 0u;
+    pp.last_defer = m.defer != 0u;
+    return m;
 }
 
 inline unsigned long long wf_flush_at(const WfOptions &o) { return std::min<unsigned long long>(o.wf_flush_at, kWfSideCap); }

@@ -587,6 +587,14 @@ class Renderer:
         self._chk(self._lib.crt_debug_gen_culled(self._h, C.byref(n)))
         return int(n.value)
 
+    def deferred_nee(self) -> int:
+        """Paths the shade kernel finished at once since reset_counters() (crt_debug_deferred_nee): roulette ended them
+        while their NEE shadow ray was pending, and the term was added one iteration later (option "wf_defer_nee").
+        A sync point."""
+        n = C.c_uint64()
+        self._chk(self._lib.crt_debug_deferred_nee(self._h, C.byref(n)))
+        return int(n.value)
+
     def tile_classes(self, host: bool = False) -> np.ndarray:
         """The class of every 8x8 tile of the tile rectangle, (tiles_y, tiles_x) uint8: 1 = its camera rays miss the
         tree's root boxes for every sample, 2 = they all enter one, 0 = it depends on the sample (option

@@ -629,7 +629,10 @@ int crt_last_kernel_ms(crt_ctx *ctx, float *ms, uint32_t *launches);
  * slot; 0: every camera ray goes through the pool; same image and counters either way); "wf_cull_classes" (1, default:
  * where "wf_cull_miss" acts, the tiles whose camera rays miss, or enter, the root's boxes for EVERY sample are classified
  * once per run, and their chunks skip the per-sample test -- and, where they miss, the draws; 0: every chunk is tested
- * per sample; same image, counters and launches either way); "frame_ring" = F (keep the
+ * per sample; same image, counters and launches either way); "wf_defer_nee" (1, default: a path that
+ * Russian roulette ends while its NEE shadow ray is pending finishes in that shade step and frees its slot, the term is
+ * added by the next shade launch; 0: the slot is held one more iteration; same image and counters either way, fewer
+ * launches with 1); "frame_ring" = F (keep the
  * rgba8 frame of each of the last F samples for crt_read_sample_rgba8; 0 = off);
  * "temporal_motion" (0 | 1, anything else is CRT_EINVAL: 1 keeps the history of crt_denoise_temporal across
  * crt_update_primitives, see "Temporal reuse"; costs 80 bytes per primitive on the device once an edit has happened);
@@ -713,6 +716,11 @@ int crt_debug_probes(crt_ctx *ctx, uint64_t out[8]);
  * the tree's root boxes, by whole 8x8 tiles of one sample (option "wf_cull_miss").  Counted with and without
  * crt_enable_counters.  A sync point; work in flight at a crt_reset_counters may count on either side of it. */
 int crt_debug_gen_culled(crt_ctx *ctx, uint64_t *out);
+/* Test hook: paths that k_wf_shade finished at once since the last crt_reset_counters -- paths that Russian roulette ended
+ * while their NEE shadow ray was still pending, whose slot is freed in that step and whose term is added one iteration
+ * later (option "wf_defer_nee").  0 with the option off.  Counted with and without crt_enable_counters.
+ * A sync point; work in flight at a crt_reset_counters may count on either side of it. */
+int crt_debug_deferred_nee(crt_ctx *ctx, uint64_t *out);
 /* Test hooks: the class of every 8x8 tile of the tile rectangle (row-major, n_tiles = ceil(tw / 8) * ceil(th / 8) bytes;
  * option "wf_cull_classes"): 1 = the camera rays of every pixel of the tile miss the root's four child
  * boxes for every sample, 2 = they all enter one, 0 = it depends on the sample (or nothing could be shown).
