@@ -884,6 +884,41 @@ static napi_value js_transform_primitives(napi_env env, napi_callback_info info)
     return undefined(env);
 }
 
+/* removePrimitives(h, ranges: k*8 B, packed crt_prim_range records {u32 first, u32 count}, lights?: m*80 B) and
+ * appendPrimitives(h, records: k*80 B, lights?: m*80 B): crt_remove_primitives / crt_append_primitives.  lights missing,
+ * undefined or null keeps the light list.  removePrimitivesAsync / appendPrimitivesAsync: the Promise forms (below). */
+static int optional_lights(napi_env env, size_t argc, napi_value *argv, void **p, size_t *n)
+{
+    napi_valuetype t = napi_undefined;
+    *p = NULL; *n = 0;
+    if (argc < 3 || napi_typeof(env, argv[2], &t) != napi_ok || t == napi_undefined || t == napi_null) return 1;
+    return get_bytes(env, argv[2], p, n) && *n % 80 == 0;
+}
+
+static napi_value edit_topology(napi_env env, napi_callback_info info, int append)
+{
+    size_t argc = 3;
+    napi_value argv[3];
+    NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    if (argc < 2) { napi_throw_type_error(env, NULL, "too few arguments"); return NULL; }
+    crt_ctx *ctx = get_ctx(env, argv[0]);
+    if (!ctx) return NULL;
+    void *p = NULL, *lp = NULL; size_t n = 0, ln = 0;
+    if (!get_bytes(env, argv[1], &p, &n) || n % (append ? 80 : sizeof(crt_prim_range))) {
+        napi_throw_type_error(env, NULL, append ? "appendPrimitives: records must be k*80 bytes" : "removePrimitives: ranges must be k*8 bytes");
+        return NULL;
+    }
+    if (!optional_lights(env, argc, argv, &lp, &ln)) {
+        napi_throw_type_error(env, NULL, "removePrimitives / appendPrimitives: lights must be m*80 bytes, null or left out");
+        return NULL;
+    }
+    if (append) CRT_CHECK(env, ctx, "crt_append_primitives", crt_append_primitives(ctx, p, (uint32_t)(n / 80), lp, ln / 80));
+    else CRT_CHECK(env, ctx, "crt_remove_primitives", crt_remove_primitives(ctx, (const crt_prim_range *)p, (uint32_t)(n / sizeof(crt_prim_range)), lp, ln / 80));
+    return undefined(env);
+}
+static napi_value js_remove_primitives(napi_env env, napi_callback_info info) { return edit_topology(env, info, 0); }
+static napi_value js_append_primitives(napi_env env, napi_callback_info info) { return edit_topology(env, info, 1); }
+
 static napi_value js_read_primitives(napi_env env, napi_callback_info info)
 {
     ARGS(3)
@@ -1180,7 +1215,7 @@ static napi_value js_set_stream(napi_env env, napi_callback_info info)
  * GPU either.  Jobs of one context run in call order. */
 enum { JOB_TRACE, JOB_SYNC, JOB_READ_RGBA8, JOB_READ_ACCUM, JOB_GATHER, JOB_READ_FRAME_RGBA8, JOB_READ_FRAME_ACCUM, JOB_READ_SAMPLE_RGBA8,
        JOB_DENOISE_ADAPTIVE, JOB_DENOISE_TEMPORAL, JOB_DENOISE_SVGF, JOB_TRANSFORM_PRIMITIVES, JOB_READ_PRIMITIVES,
-       JOB_DENOISE_FRAME, JOB_DENOISE_ADAPTIVE_FRAME };
+       JOB_DENOISE_FRAME, JOB_DENOISE_ADAPTIVE_FRAME, JOB_REMOVE_PRIMITIVES, JOB_APPEND_PRIMITIVES };
 typedef struct job {
     napi_async_work work;
     napi_deferred deferred;
@@ -1193,6 +1228,8 @@ typedef struct job {
     crt_denoise_svgf_params ds;         /* JOB_DENOISE_SVGF */
     crt_prim_transform *ops;            /* JOB_TRANSFORM_PRIMITIVES: the job's own copy of the n ops */
     uint32_t first;                     /* JOB_READ_PRIMITIVES: records [first, first + n) */
+    void *edit, *lights;                /* JOB_REMOVE_PRIMITIVES / JOB_APPEND_PRIMITIVES: the job's own copies of the n ranges / records */
+    size_t nlight;                      /* ... and of the light list (lights NULL: kept) */
     void *data;              /* ArrayBuffer memory of a read job (kept alive by ab_ref) */
     napi_ref ab_ref;
     char err[640];
@@ -1218,6 +1255,8 @@ static void job_execute(napi_env env, void *data)
     case JOB_DENOISE_TEMPORAL: j->rc = crt_denoise_temporal(ctx, &j->dt, NULL, (uint8_t *)j->data, NULL); break;
     case JOB_DENOISE_SVGF: j->rc = crt_denoise_svgf(ctx, &j->ds, NULL, (uint8_t *)j->data, NULL, NULL); break;
     case JOB_TRANSFORM_PRIMITIVES: j->rc = crt_transform_primitives(ctx, j->ops, j->n); break;
+    case JOB_REMOVE_PRIMITIVES: j->rc = crt_remove_primitives(ctx, (const crt_prim_range *)j->edit, j->n, j->lights, j->nlight); break;
+    case JOB_APPEND_PRIMITIVES: j->rc = crt_append_primitives(ctx, j->edit, j->n, j->lights, j->nlight); break;
     case JOB_READ_PRIMITIVES: j->rc = crt_read_primitives(ctx, j->first, j->n, j->n ? j->data : NULL); break;
     default: j->rc = crt_read_frame_accum(ctx, (float *)j->data); break;
     }
@@ -1255,7 +1294,7 @@ static void job_complete(napi_env env, napi_status status, void *data)
     }
     if (j->ab_ref) napi_delete_reference(env, j->ab_ref);
     napi_delete_async_work(env, j->work);
-    free(j->ops);
+    free(j->ops); free(j->edit); free(j->lights);
     /* the next job of this context */
     sl->head = j->next;
     if (!sl->head) {
@@ -1270,7 +1309,7 @@ static napi_value start_job(napi_env env, napi_callback_info info, int op)
     size_t argc = 3;
     napi_value argv[3];
     NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
-    if (argc < (op == JOB_READ_PRIMITIVES ? 3u : (op == JOB_TRACE || op == JOB_GATHER || op == JOB_READ_SAMPLE_RGBA8 || op == JOB_TRANSFORM_PRIMITIVES) ? 2u : 1u)) { napi_throw_type_error(env, NULL, "too few arguments"); return NULL; }
+    if (argc < (op == JOB_READ_PRIMITIVES ? 3u : (op == JOB_TRACE || op == JOB_GATHER || op == JOB_READ_SAMPLE_RGBA8 || op == JOB_TRANSFORM_PRIMITIVES || op == JOB_REMOVE_PRIMITIVES || op == JOB_APPEND_PRIMITIVES) ? 2u : 1u)) { napi_throw_type_error(env, NULL, "too few arguments"); return NULL; }
     slot *sl = get_slot(env, argv[0]);
     if (!sl) return NULL;
     job *j = (job *)calloc(1, sizeof *j);
@@ -1289,6 +1328,22 @@ static napi_value start_job(napi_env env, napi_callback_info info, int op)
         j->ops = (crt_prim_transform *)malloc(n ? n : 1);
         if (!j->ops) { free(j); napi_throw_error(env, NULL, "out of memory"); return NULL; }
         memcpy(j->ops, p, n);
+    }
+    if (op == JOB_REMOVE_PRIMITIVES || op == JOB_APPEND_PRIMITIVES) {   /* copies, as for the ops above */
+        const size_t unit = op == JOB_APPEND_PRIMITIVES ? 80 : sizeof(crt_prim_range);
+        void *p = NULL, *lp = NULL; size_t n = 0, ln = 0;
+        if (!get_bytes(env, argv[1], &p, &n) || n % unit || !optional_lights(env, argc, argv, &lp, &ln)) {
+            free(j);
+            napi_throw_type_error(env, NULL, "removePrimitivesAsync / appendPrimitivesAsync: k*8 bytes of ranges / k*80 bytes of records, then lights (m*80 bytes) or null");
+            return NULL;
+        }
+        j->n = (uint32_t)(n / unit);
+        j->nlight = ln / 80;
+        j->edit = malloc(n ? n : 1);
+        j->lights = lp ? malloc(ln ? ln : 1) : NULL;
+        if (!j->edit || (lp && !j->lights)) { free(j->edit); free(j->lights); free(j); napi_throw_error(env, NULL, "out of memory"); return NULL; }
+        memcpy(j->edit, p, n);
+        if (lp) memcpy(j->lights, lp, ln);
     }
     if (op == JOB_READ_PRIMITIVES) {
         napi_value ab;
@@ -1312,7 +1367,7 @@ static napi_value start_job(napi_env env, napi_callback_info info, int op)
     if (napi_create_promise(env, &j->deferred, &promise) != napi_ok ||
         napi_create_string_utf8(env, "crt_async", NAPI_AUTO_LENGTH, &name) != napi_ok ||
         napi_create_async_work(env, NULL, name, job_execute, job_complete, j, &j->work) != napi_ok) {
-        free(j->ops);
+        free(j->ops); free(j->edit); free(j->lights);
         free(j);
         napi_throw_error(env, NULL, "crt_napi: could not create the asynchronous job");
         return NULL;
@@ -1323,7 +1378,7 @@ static napi_value start_job(napi_env env, napi_callback_info info, int op)
             sl->self = NULL;
             napi_delete_async_work(env, j->work);
             if (j->ab_ref) napi_delete_reference(env, j->ab_ref);
-            free(j->ops);
+            free(j->ops); free(j->edit); free(j->lights);
             free(j);
             napi_throw_error(env, NULL, "crt_napi: could not pin the context handle");
             return NULL;
@@ -1348,6 +1403,8 @@ static napi_value js_denoise_temporal_async(napi_env env, napi_callback_info inf
 static napi_value js_denoise_svgf_async(napi_env env, napi_callback_info info) { return start_job(env, info, JOB_DENOISE_SVGF); }
 static napi_value js_transform_primitives_async(napi_env env, napi_callback_info info) { return start_job(env, info, JOB_TRANSFORM_PRIMITIVES); }
 static napi_value js_read_primitives_async(napi_env env, napi_callback_info info) { return start_job(env, info, JOB_READ_PRIMITIVES); }
+static napi_value js_remove_primitives_async(napi_env env, napi_callback_info info) { return start_job(env, info, JOB_REMOVE_PRIMITIVES); }
+static napi_value js_append_primitives_async(napi_env env, napi_callback_info info) { return start_job(env, info, JOB_APPEND_PRIMITIVES); }
 
 static napi_value js_abi_version(napi_env env, napi_callback_info info)
 {
@@ -1382,6 +1439,8 @@ static napi_value init(napi_env env, napi_value exports)
         {"refitAccel", js_refit_accel},
         {"transformPrimitives", js_transform_primitives}, {"transformPrimitivesAsync", js_transform_primitives_async},
         {"readPrimitives", js_read_primitives}, {"readPrimitivesAsync", js_read_primitives_async},
+        {"removePrimitives", js_remove_primitives}, {"removePrimitivesAsync", js_remove_primitives_async},
+        {"appendPrimitives", js_append_primitives}, {"appendPrimitivesAsync", js_append_primitives_async},
         {"traceAdaptive", js_trace_adaptive}, {"readAdaptive", js_read_adaptive},
         {"denoiseAdaptive", js_denoise_adaptive}, {"denoiseAdaptiveAsync", js_denoise_adaptive_async},
         {"setSampleOffset", js_set_sample_offset}, {"sampleOffset", js_sample_offset}, {"temporalReset", js_temporal_reset},

@@ -1,4 +1,4 @@
-"""python -m computeraytracer_amd [--scene file.json] [--width W --height H] [--spp N] [--out image.png] [--denoise K] [--orbit N [--temporal [--variance] [--animate | --animate-device [--rebuild-pct P]]]]
+"""python -m computeraytracer_amd [--scene file.json] [--width W --height H] [--spp N] [--out image.png] [--denoise K] [--orbit N [--temporal [--variance] [--animate | --animate-device [--rebuild-pct P] | --blink P]]]
                                 [--adaptive THRESHOLD [--adaptive-step N] [--counts-out counts.png]]
 --adaptive goes with --orbit: every frame is sampled adaptively up to --spp, and with --denoise K --temporal [--variance] the
 temporal filters blend it with each pixel's own tile count (option "adaptive_temporal")."""
@@ -44,6 +44,11 @@ def parse_args(argv=None):
                     help="with --animate-device: option refit_rebuild_pct = P (100..100000): refit_accel rebuilds the tree once its "
                          "surface-area cost has passed P percent of what it was when built (accel_quality); the refits and the "
                          "rebuilds are printed at the end")
+    ap.add_argument("--blink", type=int, default=None, metavar="P",
+                    help="with --orbit N --denoise K --temporal (not with --animate / --animate-device): before every frame "
+                         "k > 0 with k %% P == 0 the run of spheres that ends the scene is removed on the device if it is there, "
+                         "else appended back (remove_primitives / append_primitives, then refit_accel); option temporal_motion "
+                         "keeps the history across those edits")
     ap.add_argument("--adaptive", type=float, default=None, metavar="THRESHOLD",
                     help="adaptive sampling (crt_trace_adaptive): rounds of --adaptive-step samples for the 8x8 tiles whose "
                          "error is above THRESHOLD, --spp samples at most, until every tile is done; with --orbit N every "
@@ -67,6 +72,8 @@ def parse_args(argv=None):
         ap.error("--animate-device goes with --orbit N --denoise K --temporal, and not with --animate")
     if args.rebuild_pct is not None and not args.animate_device:
         ap.error("--rebuild-pct goes with --animate-device")
+    if args.blink is not None and (not args.temporal or args.animate or args.animate_device or args.blink < 1):
+        ap.error("--blink P goes with --orbit N --denoise K --temporal, P >= 1, and not with --animate or --animate-device")
     if args.adaptive is not None and args.checkpoint:
         ap.error("--adaptive does not go with --checkpoint")
     if (args.counts_out or args.adaptive_min is not None) and args.adaptive is None:
@@ -90,6 +97,12 @@ def main(argv=None):
                 import numpy as np
                 r.set_option("temporal_motion", 1)
                 spheres = [int(i) for i in (ps.primitives["category"] == scene.CATEGORY["sphere"]).nonzero()[0]]
+            if args.blink is not None:
+                run = _closing_spheres(ps)
+                if not 0 < run < len(ps.primitives):
+                    raise SystemExit("--blink: the scene must end in a run of spheres, with a primitive before it")
+                r.set_option("temporal_motion", 1)
+                blink_first, blink_tail, edits = len(ps.primitives) - run, ps.primitives[len(ps.primitives) - run:], 0
             refits, mean_samples = 0, []
             if args.adaptive is not None and args.temporal:
                 r.set_option("adaptive_temporal", 1)
@@ -110,6 +123,13 @@ def main(argv=None):
                         ops.append((i, 1, [1, 0, 0, 0, 0, 1, 0, np.float32(up1 - up0), 0, 0, 1, 0]))
                     r.transform_primitives(ops).refit_accel()
                     refits += 1
+                if args.blink is not None and k and k % args.blink == 0:
+                    if len(r.scene.primitives) > blink_first:
+                        r.remove_primitives([(blink_first, len(blink_tail))])
+                    else:
+                        r.append_primitives(blink_tail)
+                    r.refit_accel()
+                    edits += 1
                 r.set_camera(cam)
                 if args.temporal:
                     r.set_sample_offset(k * args.spp)
@@ -145,6 +165,8 @@ def main(argv=None):
                 info["animate"] = True
             if args.animate_device:
                 info["animate_device"] = True
+            if args.blink is not None:
+                info["blink"], info["edits"] = args.blink, edits
             if args.rebuild_pct is not None:
                 info["rebuild_pct"] = args.rebuild_pct
                 info["refits"] = refits                            # refit_accel calls, of which the policy turned ...
@@ -167,6 +189,15 @@ def main(argv=None):
         if args.denoise is not None:
             info["denoise"] = args.denoise
         print(json.dumps(info))
+
+
+def _closing_spheres(ps) -> int:
+    """How many spheres end the primitive list (--blink's object)."""
+    cat = ps.primitives["category"]
+    run = 0
+    while run < len(cat) and cat[len(cat) - 1 - run] == scene.CATEGORY["sphere"]:
+        run += 1
+    return run
 
 
 def _adaptive_rounds(r, args):

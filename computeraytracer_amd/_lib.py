@@ -79,6 +79,8 @@ SIGNATURES = {
     "crt_set_camera": (C.c_int, [_P, _P]),
     "crt_update_primitives": (C.c_int, [_P, C.c_uint32, C.c_uint32, _P]),
     "crt_transform_primitives": (C.c_int, [_P, _P, C.c_uint32]),
+    "crt_remove_primitives": (C.c_int, [_P, _P, C.c_uint32, _P, C.c_size_t]),
+    "crt_append_primitives": (C.c_int, [_P, _P, C.c_uint32, _P, C.c_size_t]),
     "crt_read_primitives": (C.c_int, [_P, C.c_uint32, C.c_uint32, _P]),
     "crt_update_lights": (C.c_int, [_P, C.c_uint32, C.c_uint32, _P]),
     "crt_refit_accel": (C.c_int, [_P, _P]),

@@ -247,7 +247,7 @@ int crt_upload_scene(crt_ctx *c, const void *primitives, size_t nprim, const voi
     S.inv_nlight = 1.0f / (float)S.nlight;                       // :372-373
     c->s_prims = prims_scale(c->prims);
     S.hit_pad = pad_of(c->s_prims, c->camera);                  // = scene_hit_pad(c->prims, c->camera)
-    c->accel_stale = false;
+    c->accel_stale = false; c->accel_topo = false;
     c->rf_ready = false;
     S.nf_last[0] = S.nf_last[1] = kNoHit;
     for (size_t i = c->prims.size(); i-- > 0 && S.nf_last[1] == kNoHit;)
@@ -789,6 +789,7 @@ int crt_last_kernel_ms(crt_ctx *c, float *ms, uint32_t *launches)
 int crt_accel_stats(crt_ctx *c, uint64_t out[8])
 {
     if (!c || !out) return CRT_EINVAL;
+    if (c->accel_topo) return fail(c, CRT_ESTATE, "crt_accel_stats: the tree belongs to another primitive list: call crt_refit_accel or crt_build_accel first");
     const bool wide = c->pipeline == 1 && c->accel_mode == CRT_ACCEL_BVH2 && c->bvh4.n_inner > 0;
     const bool wide8 = wide && c->bvh8q.ok;
     out[4] = wide ? (c->bvh4q.ok ? 16 : 32) : 32;      // bytes of node data per child box tested

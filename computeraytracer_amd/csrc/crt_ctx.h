@@ -144,7 +144,8 @@ struct crt_ctx {
 
     template <typename T> using DevBuf = crt::DevBuf<T>;
     // device scene
-    DevBuf<unsigned char> d_raw;    // the scene's 80-byte records as uploaded (input of the all-device LBVH build)
+    DevBuf<unsigned char> d_raw;    // the scene's 80-byte records as uploaded (input of the all-device LBVH build); n is its
+                                    // capacity in bytes since crt_append_primitives: the records are prims.size() * 80
     DevBuf<float4> d_prim, d_primD, d_nodes, d_nodes4, d_lights;
     DevBuf<int> w_overflow;
     DevBuf<uint4> d_nodes4q, d_nodes8q;
@@ -267,7 +268,8 @@ struct crt_ctx {
         DnSlot cur, prev;           // CURRENT: the last temporal call of this frame; PREVIOUS: what it was blended with
         DevBuf<float> hist;         // Hw alone, for history_out
         // option "temporal_motion" (DESIGN.md 6f): the history outlives crt_update_primitives.  snap is a copy of d_raw, the
-        // scene as the newest valid slot saw it, taken by the first update after that slot was written.
+        // scene as the newest valid slot saw it, taken by the first update after that slot was written.  Like d_raw it
+        // may be larger than the records; a removal or an append edits it as it edits d_raw.
         bool motion = false;
         DevBuf<unsigned char> snap;
         DevBuf<float2> uv;          // crt_read_motion's output
@@ -293,6 +295,8 @@ struct crt_ctx {
     float s_prims = 0.0f;           // max |corner coordinate| of the primitives: hit_pad = max(s_prims, |eye|) * 2^-17
     float tree_pad = 0.0f;          // the hit_pad the tree's boxes were made with (a larger one needs a refit)
     bool accel_stale = false;       // primitives changed since the tree's boxes were made: crt_refit_accel / crt_build_accel
+    bool accel_topo = false;        // ... and records were added or removed (crt_remove_primitives, crt_append_primitives): the tree's
+                                    // arrays belong to another primitive list, and crt_refit_accel rebuilds
     bool rf_ready = false;          // the level lists below belong to the current tree
     DevBuf<int> rf_lv2, rf_lv4;     // inner nodes of the BVH2 / the 4-wide tree, level by level from the root ...
     std::vector<uint32_t> rf_off2, rf_off4;   // ... level l = list[off[l] .. off[l+1])
@@ -300,7 +304,8 @@ struct crt_ctx {
     DevBuf<float> rf_fb;            // float boxes of the quantised 4-wide tree (32 floats per node)
     bool prims_moved = false;       // crt_transform_primitives moved records on the device: the geometry of `prims` is out of date
                                     // (refresh_prims before anything reads it; category, material, spectra and index never are)
-    DevBuf<uint32_t> xf_tab;        // one call's ops table: prefix sums of the counts, then the ops (kept between calls)
+    DevBuf<uint32_t> xf_tab;        // one call's ops table: prefix sums of the counts, then the ops (kept between calls);
+                                    // crt_remove_primitives: the gaps, then the prefix sums of the removed counts
     // tree cost (crt_quality.hip, crt_accel_quality)
     int refit_rebuild_pct = 0;      // option "refit_rebuild_pct": crt_refit_accel rebuilds once the walked tree's cost passes this share of q_built (0 = never)
     bool q_built_ok = false;        // q_built belongs to the current tree (taken before its first refit, or by the first crt_accel_quality)

@@ -147,6 +147,7 @@ int crt_debug_read_accel(crt_ctx *c, int what, void *out, size_t capacity, size_
     if (!c) return CRT_EINVAL;
     if (bytes) *bytes = 0;
     if (!c->have_scene || c->accel_mode < 0) return fail(c, CRT_ESTATE, "crt_debug_read_accel: scene + accel required");
+    if (c->accel_topo) return fail(c, CRT_ESTATE, "crt_debug_read_accel: the tree belongs to another primitive list: call crt_refit_accel or crt_build_accel first");
     if (what < CRT_ACCEL_PART_HEADER || what > CRT_ACCEL_PART_SLOT_OF_INDEX) return fail(c, CRT_EINVAL, "crt_debug_read_accel: unknown part %d", what);
     CRT_TRY(quiesce(c, true));
     const bool tree = c->accel_mode == CRT_ACCEL_BVH2;

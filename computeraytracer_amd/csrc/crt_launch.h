@@ -63,6 +63,7 @@ hipError_t refit_launch_prims(const unsigned char *raw, uint32_t first, uint32_t
                               float4 *primD, hipStream_t s);
 hipError_t refit_launch_transform(unsigned char *raw, const uint32_t *start, const crt_prim_transform *ops, uint32_t n_ops, uint32_t total,
                                   const uint32_t *slot_of_index, float4 *prim, float4 *primD, hipStream_t s);
+hipError_t refit_launch_compact(const unsigned char *src, unsigned char *dst, const uint32_t *tab, uint32_t n_gaps, uint32_t n_new, hipStream_t s);
 hipError_t refit_levels(const void *nodes, uint32_t width, bool quantised, int root, uint32_t cap, int *list, uint32_t *counter,
                         uint32_t *nch, std::vector<uint32_t> &off, hipStream_t s);
 hipError_t refit_launch_bvh2(const float4 *prim, float pad, const int *list, const std::vector<uint32_t> &off, float *nodes, hipStream_t s);

@@ -6,6 +6,7 @@
 //   k_refit_prims     48-byte records + D of primitives [first, first+count) into their slots (slot_of_index)
 //   k_refit_transform every op of one crt_transform_primitives call: the 80-byte records moved where they lie, and their
 //                     48-byte records + D in the same thread
+//   k_edit_compact    crt_remove_primitives: the surviving 80-byte records into a fresh array, renumbered
 //   k_refit_expand    once per tree: the inner nodes level by level from the root (one launch per level), so that a
 //                     refit can walk the levels bottom-up
 //   k_refit_bvh2      one launch per BVH2 level, deepest first: each node's two child boxes, from the leaf's primitives
@@ -129,6 +130,28 @@ __global__ __launch_bounds__(256) void k_refit_transform(unsigned char *raw, con
     const uint32_t slot = slot_of_index[i];
     prim[3 * (size_t)slot + 0] = A; prim[3 * (size_t)slot + 1] = B; prim[3 * (size_t)slot + 2] = C;
     primD[slot] = D;
+}
+
+// crt_remove_primitives: the surviving records, in their order, into a fresh array (out of place: a record's new home
+// may be another survivor's old one).  One thread per 16 bytes of the new array, five per record, so the reads within a
+// run of survivors and all the writes are whole coalesced 16-byte accesses.  gap[k] (ascending; touching ranges give
+// equal entries) is the new index before which removed range k fell, cum[k] the primitives the first k ranges removed
+// (cum[0] = 0): new record j was old record j + cum[r], r = the number of gaps <= j.  Chunk 4 is data4, whose .w is the
+// record's position.  No atomics, no LDS; the same launch parameters serve d_raw and the history's snapshot of it.
+__global__ __launch_bounds__(256) void k_edit_compact(const uint4 *__restrict__ src, uint4 *__restrict__ dst, const uint32_t *__restrict__ gap,
+                                                      const uint32_t *__restrict__ cum, uint32_t n_gaps, uint32_t n_new)
+{
+    const size_t t = (size_t)blockIdx.x * 256u + threadIdx.x;
+    if (t >= (size_t)n_new * 5u) return;
+    const uint32_t j = (uint32_t)(t / 5u), chunk = (uint32_t)(t - (size_t)j * 5u);
+    uint32_t lo = 0, hi = n_gaps;                                // gap[k] <= j for k < lo, gap[k] > j for k >= hi
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (gap[mid] <= j) lo = mid + 1; else hi = mid;
+    }
+    uint4 v = src[((size_t)j + cum[lo]) * 5u + chunk];
+    if (chunk == 4u) v.w = j;
+    dst[t] = v;
 }
 
 // One level of the walk from the root: the inner children of the nodes in `in` are appended to `out` (at most cap
@@ -256,6 +279,15 @@ hipError_t refit_launch_transform(unsigned char *raw, const uint32_t *start, con
 {
     if (total == 0) return hipSuccess;
     hipLaunchKernelGGL(k_refit_transform, dim3(blocks_of(total)), dim3(256), 0, s, raw, start, ops, n_ops, total, slot_of_index, prim, primD);
+    return hipGetLastError();
+}
+
+// tab: n_gaps gaps, then n_gaps + 1 prefix sums, on the device; src holds n_new + tab[2 * n_gaps] records, dst n_new.
+hipError_t refit_launch_compact(const unsigned char *src, unsigned char *dst, const uint32_t *tab, uint32_t n_gaps, uint32_t n_new, hipStream_t s)
+{
+    if (n_new == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_edit_compact, dim3(blocks_of((size_t)n_new * 5u)), dim3(256), 0, s, (const uint4 *)src, (uint4 *)dst, tab, tab + n_gaps,
+                       n_gaps, n_new);
     return hipGetLastError();
 }
 

@@ -367,7 +367,7 @@ int build_tree(crt_ctx *c, int mode)
             }
         }
     }
-    if (rc == CRT_OK) { c->accel_stale = false; c->tree_pad = c->sc.hit_pad; }
+    if (rc == CRT_OK) { c->accel_stale = false; c->accel_topo = false; c->tree_pad = c->sc.hit_pad; }
     return rc;
 }
 
@@ -450,6 +450,12 @@ static int refit_tree(crt_ctx *c, bool *rebuilt)
 {
     *rebuilt = false;
     if (c->accel_mode != CRT_ACCEL_BVH2) { c->accel_stale = false; return CRT_OK; }
+    if (c->accel_topo) {                                         // records were added or removed: no topology to keep
+        *rebuilt = true;
+        c->accel_mode = -1;
+        CRT_TRY(build_tree(c, CRT_ACCEL_BVH2));
+        return quality_as_built(c);
+    }
     if (c->bvh8q.ok) {
         *rebuilt = true;
         c->accel_mode = -1;
@@ -547,13 +553,14 @@ static int prims_edit_history(crt_ctx *c)
     crt_ctx::Denoise &d = c->dn;
     crt_ctx::DnSlot *const newest = !d.motion ? nullptr : d.cur.valid ? &d.cur : d.prev.valid ? &d.prev : nullptr;
     const bool take = newest && !newest->snap;
-    if (take && d.snap.n < c->d_raw.n) {                         // before anything changes: CRT_ENOMEM leaves all as it was
+    const size_t nb = c->prims.size() * 80;                      // (the records: d_raw.n and snap.n are capacities)
+    if (take && d.snap.n < nb) {                                 // before anything changes: CRT_ENOMEM leaves all as it was
         DevBuf<unsigned char> fresh;
-        HIPCHK(c, fresh.alloc(c->d_raw.n));
+        HIPCHK(c, fresh.alloc(nb));
         d.snap = std::move(fresh);
     }
     if (take) {
-        HIPCHK(c, hipMemcpyAsync(d.snap.p, c->d_raw.p, c->d_raw.n, hipMemcpyDeviceToDevice, c->stream));
+        if (nb) HIPCHK(c, hipMemcpyAsync(d.snap.p, c->d_raw.p, nb, hipMemcpyDeviceToDevice, c->stream));
         d.cur.snap = d.prev.snap = false;
         newest->snap = true;
     }
@@ -562,14 +569,15 @@ static int prims_edit_history(crt_ctx *c)
 }
 
 // After d_raw (and the leaf-ordered records) changed: hit_pad exactly as a fresh upload computes it (the full scan: the
-// value enters the kernels), the tree stale, the frame state reset.
-static int prims_edit_end(crt_ctx *c)
+// value enters the kernels), the tree stale, the frame state reset.  scan_out: the scan's word on the device, from a
+// caller that allocates everything before it changes anything.
+static int prims_edit_end(crt_ctx *c, uint32_t *scan_out = nullptr)
 {
     DevBuf<uint32_t> s;
-    HIPCHK(c, s.alloc(1));
-    HIPCHK(c, refit_launch_pad(c->d_raw.p, (uint32_t)c->prims.size(), s.p, c->stream));
+    if (!scan_out) { HIPCHK(c, s.alloc(1)); scan_out = s.p; }
+    HIPCHK(c, refit_launch_pad(c->d_raw.p, (uint32_t)c->prims.size(), scan_out, c->stream));
     uint32_t sb = 0;
-    HIPCHK(c, hipMemcpyAsync(&sb, s.p, 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(&sb, scan_out, 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->s_prims = bits_f(sb);
     c->sc.hit_pad = pad_of(c->s_prims, c->camera);
@@ -601,7 +609,7 @@ int crt_update_primitives(crt_ctx *c, uint32_t first, uint32_t count, const void
     std::copy(np.begin(), np.end(), c->prims.begin() + first);   // the host SAH builder reads these
     if (count) {
         HIPCHK(c, hipMemcpyAsync(c->d_raw.p + (size_t)first * 80, records, (size_t)count * 80, hipMemcpyHostToDevice, c->stream));   // the LBVH builder's input
-        if (c->accel_mode >= 0)                                  // the leaf-ordered records, in their slots
+        if (c->accel_mode >= 0 && !c->accel_topo)                // the leaf-ordered records, in their slots (not those of another primitive list)
             HIPCHK(c, refit_launch_prims(c->d_raw.p, first, count, c->d_slot_of_index.p, c->d_prim.p, c->d_primD.p, c->stream));
     }
     return prims_edit_end(c);
@@ -647,12 +655,212 @@ int crt_transform_primitives(crt_ctx *c, const crt_prim_transform *ops, uint32_t
     CRT_TRY(prims_edit_history(c));
     if (total) {
         HIPCHK(c, hipMemcpyAsync(c->xf_tab.p, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, c->stream));
-        const bool built = c->accel_mode >= 0;                   // the leaf-ordered records exist: moved in the same thread
+        const bool built = c->accel_mode >= 0 && !c->accel_topo; // the leaf-ordered records exist: moved in the same thread
         HIPCHK(c, refit_launch_transform(c->d_raw.p, c->xf_tab.p, (const crt_prim_transform *)(c->xf_tab.p + head), (uint32_t)live.size(), total,
                                          c->d_slot_of_index.p, built ? c->d_prim.p : nullptr, built ? c->d_primD.p : nullptr, c->stream));
         c->prims_moved = true;
     }
     return prims_edit_end(c);                                    // (its sync covers the table's upload from `tab`)
+}
+
+// ---------------------------------------------------------------- topology edits (crt_remove_primitives, crt_append_primitives)
+// Both calls run in the same four steps: validate (nothing touched), allocate (TopoEdit holds every new buffer until the
+// commit, so CRT_ENOMEM frees them and leaves all as it was), prims_edit_history, then change records, mirror, lights and
+// derived state -- nothing after the allocations can fail short of a device error.
+
+struct TopoEdit {
+    std::vector<HostPrim> lights;       // the light list after the call
+    bool lights_replaced = false;       // the caller passed a list: d_lights is re-made
+    bool lights_changed = false;        // ... or kept lights were renumbered: their rows are re-sent
+    DevBuf<float4> d_lights;
+    DevBuf<unsigned char> raw, snap;    // a new d_raw / history snapshot, where the call needs one
+    DevBuf<float4> prim, primD;         // CRT_ACCEL_NONE: the packed records in array order, re-derived here
+    DevBuf<uint32_t> slot, scan;        // (scan: prims_edit_end's word)
+    std::vector<uint32_t> iota, tab;    // (host sources of asynchronous copies: they live until the call's last sync)
+    std::vector<float4> rows;
+};
+
+// The caller's light list, if there is one, with the upload's validation.
+static int topo_lights(crt_ctx *c, const char *what, const void *lights, size_t nlight, TopoEdit &e)
+{
+    if (!lights) {
+        if (nlight) return fail(c, CRT_EINVAL, "%s: lights is NULL with nlight = %zu (NULL, 0 keeps the light list)", what, nlight);
+        e.lights = c->lights;
+        return CRT_OK;
+    }
+    if (nlight < 1) return fail(c, CRT_EINVAL, "%s: at least one light record is required", what);
+    e.lights.resize(nlight);
+    for (size_t i = 0; i < nlight; i++) {
+        e.lights[i] = read_prim((const uint8_t *)lights, i);
+        if (e.lights[i].emission >= c->sc.nspectra) return fail(c, CRT_EINVAL, "%s: light %zu: emission index out of range", what, i);
+    }
+    e.lights_replaced = true;
+    return CRT_OK;
+}
+
+// Every allocation of the call, for a scene of n_new primitives: new_raw / new_snap bytes (0 = that buffer stays).
+static int topo_alloc(crt_ctx *c, TopoEdit &e, size_t n_new, size_t new_raw, size_t new_snap, bool records_change)
+{
+    if (new_raw) HIPCHK(c, e.raw.alloc(new_raw));
+    if (new_snap) HIPCHK(c, e.snap.alloc(new_snap));
+    if (e.lights_replaced) HIPCHK(c, e.d_lights.alloc(e.lights.size() * 3));
+    if (records_change && c->accel_mode == CRT_ACCEL_NONE) {
+        HIPCHK(c, e.prim.alloc(std::max<size_t>(n_new * 3, 3)));
+        HIPCHK(c, e.primD.alloc(std::max<size_t>(n_new, 1)));
+        HIPCHK(c, e.slot.alloc(std::max<size_t>(n_new, 1)));
+    }
+    HIPCHK(c, e.scan.alloc(1));
+    return CRT_OK;
+}
+
+// After d_raw and c->prims hold the new list: the lights, the state derived from the list as a fresh upload derives
+// it, the packed records (CRT_ACCEL_NONE) or the topology-stale tree, and the end of every primitive edit.
+static int topo_commit(crt_ctx *c, TopoEdit &e, bool records_change)
+{
+    DevScene &S = c->sc;
+    const uint32_t n = (uint32_t)c->prims.size();
+    if (e.lights_replaced || e.lights_changed) {
+        e.rows.resize(e.lights.size() * 3);
+        for (size_t i = 0; i < e.lights.size(); i++) light_rows(e.lights[i], &e.rows[3 * i]);
+        if (e.lights_replaced) {
+            c->d_lights = std::move(e.d_lights);
+            S.lights = c->d_lights.p;
+            S.nlight = (uint32_t)e.lights.size();
+            S.inv_nlight = 1.0f / (float)S.nlight;
+            c->dn.drop();                                        // other illumination: as crt_update_lights
+        }
+        c->lights.swap(e.lights);
+        HIPCHK(c, hipMemcpyAsync(c->d_lights.p, e.rows.data(), e.rows.size() * sizeof(float4), hipMemcpyHostToDevice, c->stream));
+    }
+    if (records_change) {
+        S.nf_last[0] = S.nf_last[1] = kNoHit;
+        for (size_t i = n; i-- > 0 && S.nf_last[1] == kNoHit;)
+            if (c->prims[i].category != 2u) (S.nf_last[0] == kNoHit ? S.nf_last[0] : S.nf_last[1]) = (uint32_t)i;
+        if (c->accel_mode == CRT_ACCEL_NONE) {
+            e.iota.resize(n);
+            for (uint32_t i = 0; i < n; i++) e.iota[i] = i;
+            HIPCHK(c, hipMemcpyAsync(e.slot.p, e.iota.data(), (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+            HIPCHK(c, refit_launch_prims(c->d_raw.p, 0, n, e.slot.p, e.prim.p, e.primD.p, c->stream));
+            c->d_prim = std::move(e.prim); c->d_primD = std::move(e.primD); c->d_slot_of_index = std::move(e.slot);
+            S.prim = c->d_prim.p; S.primD = c->d_primD.p; S.slot_of_index = c->d_slot_of_index.p;
+            S.nprim = n;
+            S.npatch = 0;
+            for (const HostPrim &p : c->prims) S.npatch += p.category == 0u ? 1u : 0u;
+        }
+        if (c->accel_mode == CRT_ACCEL_BVH2) c->accel_topo = true;   // (nprim, npatch and the packed records: the rebuild's)
+    }
+    return prims_edit_end(c, e.scan.p);                          // (its sync: before `e` frees what the kernels above still read)
+}
+
+int crt_remove_primitives(crt_ctx *c, const crt_prim_range *ranges, uint32_t n_ranges, const void *lights, size_t nlight)
+{
+    if (!c) return CRT_EINVAL;
+    if (!ranges && n_ranges) return fail(c, CRT_EINVAL, "crt_remove_primitives: ranges is NULL");
+    if (!c->have_scene) return fail(c, CRT_ESTATE, "crt_remove_primitives: upload a scene first");
+    const size_t n = c->prims.size();
+    std::vector<crt_prim_range> live;                            // the ranges that remove something, ascending
+    for (uint32_t k = 0; k < n_ranges; k++) {
+        if ((uint64_t)ranges[k].first + ranges[k].count > n)
+            return fail(c, CRT_EINVAL, "crt_remove_primitives: range %u: [%u, %llu) outside the scene's %zu primitives", k, ranges[k].first,
+                        (unsigned long long)ranges[k].first + ranges[k].count, n);
+        if (ranges[k].count) live.push_back(ranges[k]);
+    }
+    std::sort(live.begin(), live.end(), [](const crt_prim_range &a, const crt_prim_range &b) { return a.first < b.first; });
+    for (size_t j = 1; j < live.size(); j++)
+        if (live[j - 1].first + live[j - 1].count > live[j].first)
+            return fail(c, CRT_EINVAL, "crt_remove_primitives: two ranges overlap: both remove primitive %u", live[j].first);
+    // the device table: the new index before which each range fell, then the prefix sums of the counts
+    const size_t m = live.size();
+    TopoEdit e;
+    e.tab.assign(2 * m + 1, 0u);
+    uint32_t total = 0;                                          // <= n: the ranges are disjoint
+    for (size_t j = 0; j < m; j++) {
+        e.tab[j] = live[j].first - total;
+        total += live[j].count;
+        e.tab[m + 1 + j] = total;
+    }
+    if (total && total == n)
+        return fail(c, CRT_EINVAL, "crt_remove_primitives: the call would remove all %zu primitives (an empty scene is crt_upload_scene's)", n);
+    CRT_TRY(topo_lights(c, "crt_remove_primitives", lights, nlight, e));
+    if (!e.lights_replaced && total)
+        for (size_t i = 0; i < e.lights.size(); i++) {
+            const uint32_t x = e.lights[i].index;
+            if (x >= n) continue;                                // (names no primitive: the kernels guard, as after an upload)
+            size_t r = std::upper_bound(live.begin(), live.end(), x, [](uint32_t v, const crt_prim_range &a) { return v < a.first; }) - live.begin();
+            if (r && x < live[r - 1].first + live[r - 1].count)
+                return fail(c, CRT_EINVAL, "crt_remove_primitives: light %zu lies on primitive %u, which the call removes: pass the new light list", i, x);
+            if (e.tab[m + r]) { e.lights[i].index = x - e.tab[m + r]; e.lights_changed = true; }
+        }
+    const size_t n_new = n - total;
+    CRT_TRY(quiesce(c, true));
+    crt_ctx::Denoise &d = c->dn;
+    const bool keep = d.motion && (d.cur.valid || d.prev.valid);   // prims_edit_history keeps the history, with a snapshot
+    CRT_TRY(topo_alloc(c, e, n_new, total ? n_new * 80 : 0, total && keep ? n_new * 80 : 0, total != 0));
+    if (total && c->xf_tab.n < e.tab.size()) HIPCHK(c, c->xf_tab.alloc(std::max(e.tab.size(), 2 * c->xf_tab.n)));
+    CRT_TRY(prims_edit_history(c));
+    if (total) {
+        HIPCHK(c, hipMemcpyAsync(c->xf_tab.p, e.tab.data(), e.tab.size() * 4, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, refit_launch_compact(c->d_raw.p, e.raw.p, c->xf_tab.p, (uint32_t)m, (uint32_t)n_new, c->stream));
+        if (keep) HIPCHK(c, refit_launch_compact(d.snap.p, e.snap.p, c->xf_tab.p, (uint32_t)m, (uint32_t)n_new, c->stream));
+        std::swap(c->d_raw, e.raw);                              // (the old arrays go with `e`, after the commit's sync)
+        if (keep) std::swap(d.snap, e.snap);
+        size_t w = 0, r = 0;                                     // the mirror: survivors close ranks, renumbered
+        for (size_t j = 0; j <= m; j++) {
+            const size_t stop = j < m ? live[j].first : n;
+            if (w != r) std::copy(c->prims.begin() + r, c->prims.begin() + stop, c->prims.begin() + w);
+            w += stop - r;
+            if (j < m) r = (size_t)live[j].first + live[j].count;
+        }
+        c->prims.resize(n_new);
+        for (size_t i = live[0].first; i < n_new; i++) c->prims[i].index = (uint32_t)i;
+    }
+    return topo_commit(c, e, total != 0);
+}
+
+int crt_append_primitives(crt_ctx *c, const void *records, uint32_t count, const void *lights, size_t nlight)
+{
+    if (!c) return CRT_EINVAL;
+    if (!records && count) return fail(c, CRT_EINVAL, "crt_append_primitives: records is NULL");
+    if (!c->have_scene) return fail(c, CRT_ESTATE, "crt_append_primitives: upload a scene first");
+    const size_t n = c->prims.size(), n_new = n + count;
+    if (n_new >= (1u << 28)) return fail(c, CRT_EINVAL, "crt_append_primitives: too many primitives (%zu + %u)", n, count);
+    std::vector<HostPrim> np(count);
+    for (uint32_t k = 0; k < count; k++) {
+        const HostPrim &p = np[k] = read_prim((const uint8_t *)records, k);
+        if (p.category > 2u) return fail(c, CRT_EINVAL, "crt_append_primitives: record %u: category %u not in {0,1,2}", k, p.category);
+        if (p.material > 2u) return fail(c, CRT_EINVAL, "crt_append_primitives: record %u: material %u not in {0,1,2}", k, p.material);
+        if (p.index != n + k)
+            return fail(c, CRT_EINVAL, "crt_append_primitives: record %u: index is %u, must equal its array position %zu", k, p.index, n + k);
+        if (p.emission >= c->sc.nspectra || p.reflectance >= c->sc.nspectra)
+            return fail(c, CRT_EINVAL, "crt_append_primitives: record %u: spectrum index out of range", k);
+    }
+    TopoEdit e;
+    CRT_TRY(topo_lights(c, "crt_append_primitives", lights, nlight, e));
+    CRT_TRY(quiesce(c, true));
+    crt_ctx::Denoise &d = c->dn;
+    const bool keep = d.motion && (d.cur.valid || d.prev.valid);
+    // a buffer that cannot take the records grows by half of itself at least, device to device
+    const auto grown = [&](size_t have) { return have >= n_new * 80 ? (size_t)0 : std::max(n_new * 80, have + have / 2); };
+    CRT_TRY(topo_alloc(c, e, n_new, count ? grown(c->d_raw.n) : 0, count && keep ? grown(d.snap.n) : 0, count != 0));
+    if (c->prims.capacity() < n_new)                             // (the mirror grows as d_raw does; std::bad_alloc: nothing has changed)
+        c->prims.reserve(std::max(n_new, c->prims.capacity() + c->prims.capacity() / 2));
+    CRT_TRY(prims_edit_history(c));
+    if (count) {
+        if (e.raw.p) {
+            HIPCHK(c, hipMemcpyAsync(e.raw.p, c->d_raw.p, n * 80, hipMemcpyDeviceToDevice, c->stream));
+            std::swap(c->d_raw, e.raw);
+        }
+        HIPCHK(c, hipMemcpyAsync(c->d_raw.p + n * 80, records, (size_t)count * 80, hipMemcpyHostToDevice, c->stream));
+        if (keep) {                                              // the snapshot takes them too: new records compare equal
+            if (e.snap.p) {
+                HIPCHK(c, hipMemcpyAsync(e.snap.p, d.snap.p, n * 80, hipMemcpyDeviceToDevice, c->stream));
+                std::swap(d.snap, e.snap);
+            }
+            HIPCHK(c, hipMemcpyAsync(d.snap.p + n * 80, records, (size_t)count * 80, hipMemcpyHostToDevice, c->stream));
+        }
+        c->prims.insert(c->prims.end(), np.begin(), np.end());
+    }
+    return topo_commit(c, e, count != 0);
 }
 
 int crt_read_primitives(crt_ctx *c, uint32_t first, uint32_t count, void *out)
@@ -724,6 +932,7 @@ int crt_accel_quality(crt_ctx *c, double out[12])
 {
     if (!c || !out) return CRT_EINVAL;
     if (!c->have_scene || c->accel_mode < 0) return fail(c, CRT_ESTATE, "crt_accel_quality: scene + accel required");
+    if (c->accel_topo) return fail(c, CRT_ESTATE, "crt_accel_quality: the tree belongs to another primitive list: call crt_refit_accel or crt_build_accel first");
     CRT_TRY(quiesce(c, true));
     if (!c->q_built_ok) {                                        // no refit since the build: the tree is as it was built
         CRT_TRY(quality_as_built(c));

@@ -126,6 +126,39 @@ class Renderer:
         self._chk(self._lib.crt_transform_primitives(self._h, t.ctypes.data if len(t) else None, len(t)))
         return self
 
+    def _edited(self, ps: PackedScene, lights):
+        """self.scene after a topology edit: the records of `ps`, and its remapped lights unless the caller gave a list."""
+        if lights is not None:
+            from .scene import PRIM_DTYPE
+            ps = PackedScene(ps.primitives, np.ascontiguousarray(lights).view(PRIM_DTYPE).reshape(-1).copy(), ps.camera, ps.spectra,
+                             ps.cie, ps.patches, ps.spectrum_index)
+        self.scene = ps
+
+    def remove_primitives(self, ranges, lights=None):
+        """Remove primitive ranges [(first, count), ...] on the device (crt_remove_primitives): the survivors close ranks and
+        are renumbered.  lights None keeps the light list (its primitive indices follow); else the new list, whole.  With a
+        tree, refit_accel() then rebuilds it.  self.scene becomes scene.remove_records(self.scene, ranges)."""
+        from .scene import remove_records
+        rg = np.ascontiguousarray(np.asarray(ranges, np.int64).reshape(-1, 2).astype(np.uint32))
+        lt = None if lights is None else self._records(lights)
+        self._chk(self._lib.crt_remove_primitives(self._h, rg.ctypes.data if len(rg) else None, len(rg),
+                                                  None if lt is None else lt.ctypes.data, 0 if lt is None else lt.nbytes // 80))
+        if self.scene is not None:
+            self._edited(remove_records(self.scene, rg, remap_lights=lights is None), lights)
+        return self
+
+    def append_primitives(self, records, lights=None):
+        """Add records after the last primitive (crt_append_primitives; each record's index is its position in the new
+        list).  lights as for remove_primitives.  With a tree, refit_accel() then rebuilds it."""
+        from .scene import append_records
+        rec = self._records(records)
+        lt = None if lights is None else self._records(lights)
+        self._chk(self._lib.crt_append_primitives(self._h, rec.ctypes.data if rec.nbytes else None, rec.nbytes // 80,
+                                                  None if lt is None else lt.ctypes.data, 0 if lt is None else lt.nbytes // 80))
+        if self.scene is not None:
+            self._edited(append_records(self.scene, rec), lights)
+        return self
+
     def read_primitives(self, first: int = 0, count: int | None = None) -> np.ndarray:
         """Primitive records [first, first + count) as they lie on the device (PRIM_DTYPE; count None: to the end)."""
         from .scene import PRIM_DTYPE

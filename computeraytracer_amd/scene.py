@@ -198,6 +198,60 @@ def transform_ops(ops) -> np.ndarray:
     return out
 
 
+def _live_ranges(ranges, n: int) -> np.ndarray:
+    """The ranges of a removal that remove something, ascending, as an int64 [m, 2] array; ValueError for what
+    crt_remove_primitives refuses (a range outside the n primitives, two ranges that share one, nothing left)."""
+    rg = np.asarray(ranges, np.int64).reshape(-1, 2)
+    if ((rg < 0) | (rg[:, :1] + rg[:, 1:] > n)).any():
+        raise ValueError(f"a range lies outside the scene's {n} primitives")
+    rg = rg[rg[:, 1] > 0]
+    rg = rg[np.argsort(rg[:, 0], kind="stable")]
+    if (rg[:-1, 0] + rg[:-1, 1] > rg[1:, 0]).any():
+        raise ValueError("two ranges share a primitive")
+    if len(rg) and rg[:, 1].sum() == n:
+        raise ValueError("the ranges would remove every primitive")
+    return rg
+
+
+def remove_records(ps: PackedScene, ranges, remap_lights: bool = True) -> PackedScene:
+    """The scene without primitives [first, first + count) of every range, as a fresh upload takes it (what
+    Renderer.remove_primitives leaves on the device): survivors keep their order, data4.w is the new position, every
+    other byte stays.  A light's data4.w follows its primitive (an index at or above the old count is left alone);
+    ValueError if that primitive is removed -- then the caller makes the new light list (remap_lights False keeps
+    ps.lights as they are for that)."""
+    src = np.ascontiguousarray(ps.primitives, PRIM_DTYPE).reshape(-1)
+    n = len(src)
+    rg = _live_ranges(ranges, n)
+    keep = np.ones(n, bool)
+    for first, count in rg:
+        keep[first:first + count] = False
+    prims = src.view(np.uint8).reshape(n, 80)[keep].reshape(-1).view(PRIM_DTYPE)   # (byte rows: the padding words come along)
+    prims["data4"][:, 3] = np.arange(len(prims), dtype=np.uint32)
+    lights = ps.lights
+    if remap_lights and len(rg):
+        lights = np.ascontiguousarray(lights, PRIM_DTYPE).reshape(-1).view(np.uint8).copy().view(PRIM_DTYPE)
+        idx = lights["data4"][:, 3].astype(np.int64)
+        named = idx < n
+        if (~keep[idx[named]]).any():
+            raise ValueError("a light lies on a removed primitive: pass the new light list")
+        before = np.concatenate([[0], np.cumsum(~keep)])          # primitives removed before position i
+        idx[named] -= before[idx[named]]
+        lights["data4"][:, 3] = idx.astype(np.uint32)
+    return PackedScene(prims, lights, ps.camera, ps.spectra, ps.cie, ps.patches, ps.spectrum_index)   # (patches: not uploaded)
+
+
+def append_records(ps: PackedScene, records) -> PackedScene:
+    """The scene with `records` after its last primitive (what Renderer.append_primitives leaves on the device).  Each
+    record's data4.w must be its position in the new list, as crt_append_primitives demands; the lights stay."""
+    src = np.ascontiguousarray(ps.primitives, PRIM_DTYPE).reshape(-1)
+    rec = np.ascontiguousarray(records).view(np.uint8).reshape(-1).view(PRIM_DTYPE)
+    n = len(src)
+    if not np.array_equal(rec["data4"][:, 3], np.arange(n, n + len(rec), dtype=np.uint32)):
+        raise ValueError(f"appended records must be numbered {n} .. {n + len(rec) - 1} in data4.w")
+    prims = np.concatenate([src.view(np.uint8), rec.view(np.uint8)]).view(PRIM_DTYPE)
+    return PackedScene(prims, ps.lights, ps.camera, ps.spectra, ps.cie, ps.patches, ps.spectrum_index)
+
+
 def orbit_cameras(camera, n: int) -> np.ndarray:
     """n cameras (n x 16 float32) whose eye turns about the look-at point around the up axis, k / n of a full turn for
     k = 0 .. n-1; look-at, up, width, height and focal length kept."""

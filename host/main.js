@@ -13,6 +13,7 @@
  *           (no counterpart)                      denoise(): filtered preview of the same average
  *           queue.writeBuffer(camera / primitives / lights)   setCamera / updatePrimitives + refitAccel / updateLights
  *           (no counterpart)                      transformPrimitives: ranges moved on the device, nothing uploaded
+ *           (no counterpart)                      removePrimitives / appendPrimitives: the primitive list edited on the device
  *   620     requestAnimationFrame(frame) forever  run(spp): spp frames, optionally fused
  */
 const fs = require('fs');
@@ -77,6 +78,14 @@ function Main(options = {}) {
     transformPrimitivesAsync: (ops) => a.transformPrimitivesAsync(device, packTransforms(ops)),
     readPrimitives: (first, count) => a.readPrimitives(device, first, count),
     readPrimitivesAsync: (first, count) => a.readPrimitivesAsync(device, first, count),
+    // remove or append primitives on the device instead of uploading the scene again (include/crt.h
+    // crt_remove_primitives, crt_append_primitives): ranges = [{first, count}] or [[first, count]]; records = k * 80 bytes,
+    // each numbered by its position in the new list; lights = the new light list (m * 80 bytes), or left out / null to
+    // keep the list (its primitive indices follow a removal).  With a tree, refitAccel() then rebuilds it.
+    removePrimitives: (ranges, lights = null) => a.removePrimitives(device, packRanges(ranges), lights),
+    removePrimitivesAsync: (ranges, lights = null) => a.removePrimitivesAsync(device, packRanges(ranges), lights),
+    appendPrimitives: (records, lights = null) => a.appendPrimitives(device, records, lights),
+    appendPrimitivesAsync: (records, lights = null) => a.appendPrimitivesAsync(device, records, lights),
     // adaptive sampling (include/crt.h "Adaptive sampling"): more samples for the 8x8 tiles that have not converged;
     // returns how many tiles that was (0: done).  readAdaptive: {counts, errors, tilesX, tilesY}
     traceAdaptive: (opts = {}) => a.traceAdaptive(device, opts),
@@ -131,6 +140,16 @@ function packTransforms(ops) {
   return new Uint8Array(buf);
 }
 
+// The ranges of removePrimitives as packed crt_prim_range records (8 bytes each: u32 first, u32 count).
+function packRanges(ranges) {
+  const out = new Uint32Array(2 * ranges.length);
+  ranges.forEach((r, k) => {
+    out[2 * k] = Array.isArray(r) ? r[0] : r.first;
+    out[2 * k + 1] = Array.isArray(r) ? r[1] : r.count;
+  });
+  return new Uint8Array(out.buffer);
+}
+
 // n cameras (Float32Array(16) each) whose eye turns about the look-at point around the up axis, k/n of a full turn for
 // k = 0..n-1 (Rodrigues' rotation in doubles); look-at, up, width, height and focal length kept (scene.orbit_cameras).
 function orbitCameras(camera, n) {
@@ -157,4 +176,4 @@ function writePPM(file, rgba, width, height) {
   fs.writeFileSync(file, Buffer.concat([Buffer.from(`P6\n${width} ${height}\n255\n`), out]));
 }
 
-module.exports = { Main, writePPM, loadAddon, orbitCameras, packTransforms };
+module.exports = { Main, writePPM, loadAddon, orbitCameras, packTransforms, packRanges };

@@ -262,15 +262,15 @@ int crt_read_gbuffer(crt_ctx *ctx, float *out);
  * Move the camera or edit primitives and lights of the uploaded scene in place (DESIGN.md "Scene edits"), instead of
  * crt_upload_scene + crt_build_accel.  The tree's topology is kept; crt_refit_accel recomputes its boxes on the GPU.
  * Culling never decides a hit, so the image equals the one a fresh upload and build of the edited buffers gives.
- * Rules shared by the five edit calls (crt_set_camera, crt_update_primitives, crt_transform_primitives, crt_update_lights,
- * crt_refit_accel):
+ * Rules shared by the edit calls (crt_set_camera, crt_update_primitives, crt_transform_primitives, crt_update_lights,
+ * crt_remove_primitives, crt_append_primitives, crt_refit_accel):
  *   - each is a sync point (what is in flight finishes first, against the old scene);
  *   - then the frame state resets as crt_reset does: accumulator zeroed, sample 0, frame ring emptied;
  *   - tile, row bands, bound outputs, stream, options and a crt_comm_partition stay (W and H never change: every rank
  *     of a partitioned run makes the same call);
  *   - the denoise G-buffer is rebuilt on next use;
  *   - every input is validated before anything changes: on CRT_EINVAL the context is as it was.
- * Out of scope: adding or removing primitives, changing a category or material, resolution changes (crt_upload_scene). */
+ * Out of scope: changing a category or material, resolution changes (crt_upload_scene). */
 /* camera: 16 floats as for crt_upload_scene; floats 11, 12 must equal the current width and height.  hit_pad is
  * recomputed as max(primitive scale, |eye|) * 2^-17 without scanning the primitives; a pad larger than the one the
  * tree's boxes were made with refits the tree here (the caller need not). */
@@ -309,6 +309,42 @@ typedef struct {
     float radius_scale;      /* spheres: radius' = radius * radius_scale */
 } crt_prim_transform;
 int crt_transform_primitives(crt_ctx *ctx, const crt_prim_transform *ops, uint32_t n_ops);
+/* Remove or append primitives of the uploaded scene on the device, instead of crt_upload_scene +
+ * crt_build_accel: no record crosses the bus again but the appended ones, and tile, bound outputs, sample offset, options and a
+ * crt_comm_partition stay.  The contract is crt_update_primitives'; beyond it, every allocation is made before anything
+ * changes: on CRT_EINVAL or CRT_ENOMEM records, lights, tree, temporal history and accumulator are as they were, and
+ * the call can be repeated.  After either call nprim, the patch count, hit_pad and the host copy of the records are
+ * what a fresh upload of the resulting buffers gives; crt_update_primitives validates against the new list at once.
+ * crt_remove_primitives removes the ranges (any order; they may touch; count 0 is allowed).  The survivors keep their
+ * order and close ranks; each survivor's data4.w becomes its new position, every other byte of its record stays.
+ * CRT_EINVAL: ranges NULL with n_ranges > 0, a range outside the scene, two ranges that share a primitive, a call that
+ * would leave no primitive (the empty scene is crt_upload_scene's).
+ * crt_append_primitives adds count records (80 bytes each) after the last one, validated as crt_upload_scene validates:
+ * category and material in {0, 1, 2}, spectrum indices < nspectra, data4.w == nprim + k, the total below 2^28.  The
+ * record array on the device has a capacity: an append that fits is a copy to its tail; one that does not moves the
+ * records, device to device, to an array at least half as large again.
+ * Lights: lights == NULL (then nlight must be 0) keeps the light list.  After a removal a kept light whose data4.w names
+ * a primitive (is below the old nprim) has it lowered by the number of primitives removed before that one; CRT_EINVAL
+ * if that primitive is itself removed -- pass the new light list.  An index at or above the old nprim is left alone.
+ * With lights != NULL the list is replaced whole, with the upload's validation (nlight >= 1, emission index in range);
+ * its indices are taken as given, in the new numbering; 1/area is recomputed.  So an emitter appears or goes in one call.
+ * The tree: under CRT_ACCEL_NONE the packed records are re-derived here and nothing goes stale.  With a tree, a call
+ * that added or removed a record leaves it TOPOLOGY-STALE: stale as after crt_update_primitives (the same calls refuse
+ * with the same message), and crt_refit_accel rebuilds it with the builder that made it (*rebuilt = 1, refits back to
+ * 0, the as-built quality retaken, out[9] of crt_accel_quality not counted up); crt_build_accel clears the state too.
+ * Any number of edits of any kind may precede one refit.  Until then the tree's arrays belong to another primitive
+ * list: crt_debug_read_accel, crt_accel_quality and crt_accel_stats return CRT_ESTATE (they keep working on an ordinarily
+ * stale tree); crt_read_primitives and crt_debug_hit_pad keep working.  A call that changes no record (no live range,
+ * count 0) stales the tree in the ordinary sense only, as an empty crt_transform_primitives does.
+ * The history of crt_denoise_temporal is dropped, unless option "temporal_motion" is 1 and lights == NULL: then it is
+ * kept; the copy of the records as the newest slot saw them is taken first if it has none, a removal compacts and
+ * renumbers that copy exactly as it does the records (an unchanged record still compares equal, byte for byte), and an
+ * append adds the new records to it as well, so that a pixel on an appended primitive takes the camera-only path,
+ * whose key and plane tests reject what was there before.  A new light list drops the history as crt_update_lights
+ * does.  Transient device memory: one more copy of the records, and one of the history's copy where it is kept. */
+typedef struct { uint32_t first, count; } crt_prim_range;   /* primitives [first, first+count) */
+int crt_remove_primitives(crt_ctx *ctx, const crt_prim_range *ranges, uint32_t n_ranges, const void *lights, size_t nlight);
+int crt_append_primitives(crt_ctx *ctx, const void *records, uint32_t count, const void *lights, size_t nlight);
 /* Primitive records [first, first+count) as they lie on the device (count x 80 bytes): after crt_transform_primitives the
  * only place where the caller sees the geometry.  A sync point like crt_read_gbuffer; it only reads, and it works on a
  * stale tree.  CRT_EINVAL for a range outside the scene or out NULL with count > 0. */

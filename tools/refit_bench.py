@@ -28,6 +28,20 @@ and its crt_refit_accel after it are measured in child processes (this tool with
 after this build's run, in one session: parent_update_ms and parent_refit_ms hold both medians, their difference is the
 run-to-run spread the comparison allows for.
 
+--topology: crt_remove_primitives / crt_append_primitives instead (--out profiles/topology_edit_bench.json), the library
+calls alone (the Renderer methods also restate the edit on the host copy of the scene, which is not the library's cost):
+  remove_one_ms / remove_1000_ms     crt_remove_primitives of the last tenth as one range / as 1000 touching ranges
+  append_ms                          crt_append_primitives of that tenth, back where it was (the record array still has the room)
+  remove_mid_ms                      crt_remove_primitives of a tenth from the middle of a freshly uploaded scene (from n / 3 on:
+                                     the host mirror moves everything behind it down and renumbers it; the tail range above
+                                     moves nothing on the host)
+  append_grow_ms                     the same into an array without room: a fresh upload, then the tenth appended (once per rep)
+  rebuild_after_remove_ms / rebuild_after_append_ms   the rebuilding crt_refit_accel after each (LBVH)
+  edit_rebuild_ms                    remove + rebuild and append + rebuild, the two sums
+  upload_build_ms                    crt_upload_scene + crt_build_accel(LBVH) of the resulting buffers, this build: [without the
+                                     tenth, with it]; parent_upload_build_ms (--parent): the parent commit's, before and after
+  ratio                              edit_rebuild_ms / the parent's upload_build_ms (the faster of before / after), per edit
+
 Per-kernel times come from a separate run under rocprofv3 --kernel-trace --stats.  Prints one JSON line; --out also
 writes it.
 
@@ -202,6 +216,77 @@ def run_scene(name, ps, reps, spp, steps, update_only=False):
     return res
 
 
+def upload_build(ps, cnt, reps):
+    """crt_upload_scene + crt_build_accel(LBVH) of the scene without its last `cnt` primitives and of the whole scene."""
+    from computeraytracer_amd.scene import PackedScene
+    n = len(ps.primitives)
+    out = []
+    with Renderer(0) as r:
+        for m in (n - cnt, n):
+            part = PackedScene(ps.primitives[:m], ps.lights, ps.camera, ps.spectra, ps.cie)
+            out.append(timed(lambda: r.upload(part).build_accel("lbvh"), reps, warm=1))
+    return out
+
+
+def run_topology(name, ps, reps, upload_only=False):
+    import ctypes as C
+    n = len(ps.primitives)
+    cnt = n // 10
+    res = {"scene": name, "primitives": n, "edited": cnt, "reps": reps, "upload_build_ms": upload_build(ps, cnt, reps)}
+    if upload_only:
+        return res
+    tail = np.ascontiguousarray(ps.primitives[n - cnt:])
+    one = np.array([[n - cnt, cnt]], np.uint32)
+    bounds = np.linspace(n - cnt, n, 1001).astype(np.int64)
+    many = np.ascontiguousarray(np.stack([bounds[:-1], bounds[1:] - bounds[:-1]], 1).astype(np.uint32))
+    with Renderer(0) as r:
+        lib, h = r._lib, r._h
+        r.upload(ps).build_accel("lbvh")
+
+        def cycle(ranges, grow=False):
+            """remove, rebuild, append, rebuild: the four times of one round"""
+            t = [time.perf_counter()]
+            r._chk(lib.crt_remove_primitives(h, ranges.ctypes.data, len(ranges), None, 0)); t.append(time.perf_counter())
+            rebuilt = C.c_int()
+            r._chk(lib.crt_refit_accel(h, C.byref(rebuilt))); t.append(time.perf_counter())
+            assert rebuilt.value == 1
+            if grow:                                              # an array without room: the cut scene uploaded afresh
+                from computeraytracer_amd.scene import PackedScene
+                r.upload(PackedScene(ps.primitives[:n - cnt], ps.lights, ps.camera, ps.spectra, ps.cie)).build_accel("lbvh")
+                t[-1] = time.perf_counter()
+            r._chk(lib.crt_append_primitives(h, tail.ctypes.data, cnt, None, 0)); t.append(time.perf_counter())
+            r._chk(lib.crt_refit_accel(h, C.byref(rebuilt))); t.append(time.perf_counter())
+            assert rebuilt.value == 1
+            return [(b - a) * 1e3 for a, b in zip(t[:-1], t[1:])]
+
+        def med(rows, k):
+            return round(statistics.median(row[k] for row in rows), 4)
+
+        cycle(one)
+        a = [cycle(one) for _ in range(reps)]
+        b = [cycle(many) for _ in range(reps)]
+        g = [cycle(one, grow=True) for _ in range(max(3, reps // 4))]
+        r.scene = ps                                              # (the raw calls above kept the Renderer's host copy out of it)
+        assert r.read_primitives(n - 2, 2).tobytes() == ps.primitives[n - 2:].tobytes()
+        from computeraytracer_amd.scene import PackedScene
+        mid = np.array([[n // 3, cnt]], np.uint32)
+        ts = []
+        for _ in range(max(3, reps // 4)):
+            r.upload(PackedScene(ps.primitives, ps.lights, ps.camera, ps.spectra, ps.cie)).build_accel("lbvh")
+            t = time.perf_counter()
+            r._chk(lib.crt_remove_primitives(h, mid.ctypes.data, 1, None, 0))
+            ts.append((time.perf_counter() - t) * 1e3)
+        res["remove_mid_ms"] = round(statistics.median(ts), 4)
+        res.update(remove_one_ms=med(a, 0), rebuild_after_remove_ms=med(a, 1), append_ms=med(a, 2), rebuild_after_append_ms=med(a, 3),
+                   remove_1000_ms=med(b, 0), append_grow_ms=med(g, 2))
+        res["edit_rebuild_ms"] = {"remove_one": round(res["remove_one_ms"] + res["rebuild_after_remove_ms"], 4),
+                                  "remove_1000": round(res["remove_1000_ms"] + med(b, 1), 4),
+                                  "remove_mid": round(res["remove_mid_ms"] + res["rebuild_after_remove_ms"], 4),
+                                  "append": round(res["append_ms"] + res["rebuild_after_append_ms"], 4),
+                                  "append_grow": round(res["append_grow_ms"] + med(g, 3), 4)}
+    return res
+
+
 def policy_loop(soup_tris):
     for name, ps in [("s2", atrium250k(1920, 1080))] + ([("soup", soup(soup_tris, 1920, 1080))] if soup_tris else []):
         n = len(ps.primitives)
@@ -243,6 +328,8 @@ def main():
     ap.add_argument("--parent", default=None, metavar="DIR", help="a built checkout of the parent commit: its update_ms, before and after")
     ap.add_argument("--update-only", action="store_true", help="build_lbvh_ms, update_ms and refit_ms only")
     ap.add_argument("--tree", default=None, metavar="DIR", help="import the package from this checkout instead of the tool's own")
+    ap.add_argument("--topology", action="store_true", help="crt_remove_primitives / crt_append_primitives and the rebuilding refit instead")
+    ap.add_argument("--upload-only", action="store_true", help="with --topology: upload_build_ms only (what --parent runs)")
     ap.add_argument("--policy-loop", action="store_true", help="only the refits with the policy on and one crt_accel_quality: the run to put under rocprofv3")
     ap.add_argument("--kernel-stats", default=None, metavar="DB", help="reduce that run's rocprofv3 database to the CSV (--out, or stdout)")
     a = ap.parse_args()
@@ -253,10 +340,31 @@ def main():
 
     def parent_update():
         import subprocess
-        cmd = [sys.executable, os.path.abspath(__file__), "--update-only", "--tree", a.parent, "--reps", str(a.reps), "--soup-tris", str(a.soup_tris)]
+        mode = ["--topology", "--upload-only"] if a.topology else ["--update-only"]
+        cmd = [sys.executable, os.path.abspath(__file__), *mode, "--tree", a.parent, "--reps", str(a.reps), "--soup-tris", str(a.soup_tris)]
         return json.loads(subprocess.run(cmd, check=True, capture_output=True, text=True).stdout.strip().splitlines()[-1])
 
     before = parent_update() if a.parent else None
+    if a.topology:
+        out = {"s2": run_topology("S2 atrium250k", atrium250k(1920, 1080), a.reps, a.upload_only)}
+        if a.soup_tris:
+            out["soup"] = run_topology(f"soup {a.soup_tris}", soup(a.soup_tris, 1920, 1080), a.reps, a.upload_only)
+        if a.parent:
+            after = parent_update()
+            for k in out:
+                pb = out[k]["parent_upload_build_ms"] = [before[k]["upload_build_ms"], after[k]["upload_build_ms"]]
+                slow = [min(pb[0][i], pb[1][i]) for i in (0, 1)]         # [without the tenth, with it]: the faster run of each
+                e = out[k]["edit_rebuild_ms"]
+                out[k]["ratio"] = {"remove_one": round(e["remove_one"] / slow[0], 4), "remove_1000": round(e["remove_1000"] / slow[0], 4),
+                                   "remove_mid": round(e["remove_mid"] / slow[0], 4),
+                                   "append": round(e["append"] / slow[1], 4), "append_grow": round(e["append_grow"] / slow[1], 4)}
+        line = json.dumps(out)
+        print(line)
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as f:
+                f.write(line + "\n")
+        return
     out = {"s2": run_scene("S2 atrium250k", atrium250k(1920, 1080), a.reps, a.spp, a.steps, a.update_only)}
     if a.soup_tris:
         out["soup"] = run_scene(f"soup {a.soup_tris}", soup(a.soup_tris, 1920, 1080), a.reps, a.spp, a.steps, a.update_only)
