@@ -32,6 +32,10 @@ def parse_args(argv=None):
     ap.add_argument("--variance", action="store_true",
                     help="with --orbit N --denoise K --temporal: the passes after the blend are variance-guided, the variance "
                          "taken from the spread of the frame means (crt_denoise_svgf)")
+    ap.add_argument("--spatial", type=int, nargs="?", const=400, default=None, metavar="PCT",
+                    help="with --orbit N --denoise K --temporal --variance: option svgf_spatial_pct = PCT (25..10000, 400 when "
+                         "given bare): a pixel with too short a history for a temporal variance takes one from the spread of "
+                         "its 7x7 neighbourhood, times PCT / 100")
     ap.add_argument("--animate", action="store_true",
                     help="with --orbit N --denoise K --temporal: before frame k every sphere is moved to its frame-0 centre plus "
                          "(0, 0.5 radius sin(2 pi k / 16), 0) (update_primitives + refit_accel), and option temporal_motion keeps "
@@ -66,6 +70,8 @@ def parse_args(argv=None):
         ap.error("--temporal goes with --orbit N --denoise K")
     if args.variance and not args.temporal:
         ap.error("--variance goes with --orbit N --denoise K --temporal")
+    if args.spatial is not None and (not args.variance or not 25 <= args.spatial <= 10000):
+        ap.error("--spatial [PCT] goes with --orbit N --denoise K --temporal --variance, PCT in 25..10000")
     if args.animate and not args.temporal:
         ap.error("--animate goes with --orbit N --denoise K --temporal")
     if args.animate_device and (not args.temporal or args.animate):
@@ -108,6 +114,8 @@ def main(argv=None):
                 r.set_option("adaptive_temporal", 1)
             if args.rebuild_pct is not None:
                 r.set_option("refit_rebuild_pct", args.rebuild_pct)
+            if args.spatial is not None:
+                r.set_option("svgf_spatial_pct", args.spatial)
             for k, cam in enumerate(scene.orbit_cameras(ps.camera, args.orbit)):
                 if args.animate:
                     for i in spheres:
@@ -161,6 +169,8 @@ def main(argv=None):
                 info["temporal"] = True
             if args.variance:
                 info["variance"] = True
+            if args.spatial is not None:
+                info["spatial"] = args.spatial
             if args.animate:
                 info["animate"] = True
             if args.animate_device:

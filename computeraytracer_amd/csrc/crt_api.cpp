@@ -854,6 +854,11 @@ int crt_set_option(crt_ctx *c, const char *name, int64_t value)
         c->adaptive_temporal = value != 0;
         return CRT_OK;
     }
+    if (!std::strcmp(name, "svgf_spatial_pct")) {           // (nothing is dropped: history does not depend on it)
+        if (value != 0 && (value < 25 || value > 10000)) return fail(c, CRT_EINVAL, "crt_set_option: svgf_spatial_pct is 0 (off) or 25..10000");
+        c->svgf_spatial_pct = (int)value;
+        return CRT_OK;
+    }
     if (!std::strcmp(name, "frame_ring")) {
         c->frame_ring = (uint32_t)std::min<int64_t>(256, std::max<int64_t>(0, value));
         c->ring_from = c->sample + 1u;                          // (a new ring starts empty)

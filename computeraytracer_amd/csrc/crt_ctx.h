@@ -320,6 +320,8 @@ struct crt_ctx {
     bool as_broken = false;         // a crt_trace_adaptive failed part way: the counts lag the accumulator until crt_reset
     bool adaptive_temporal = false; // option "adaptive_temporal" (DESIGN.md 6i): crt_trace_adaptive takes the sample offset, and the
                                     // temporal calls take the adaptive state with the tile's count as each pixel's n
+    int svgf_spatial_pct = 0;       // option "svgf_spatial_pct" (DESIGN.md 6j): crt_denoise_svgf estimates the variance of pixels with
+                                    // short history from their 7x7 neighbourhood, times this / 100 (0 = off: v = 1 there)
     unsigned long long as_requested = 0;   // samples the crt_trace_adaptive calls of this adaptive state have enqueued per
                                            // active tile: no tile's count is above it
     DevBuf<uint32_t> as_counts;     // per 8x8 tile: samples it holds

@@ -109,17 +109,23 @@ __device__ __forceinline__ DnGuides dn_centre_guides(const float4 *gbuf, size_t 
     return DnGuides{x_p, n_p};
 }
 
-// e plus the normal and plane terms of tap q against the centre's guides.
-__device__ __forceinline__ float dn_guide_term(float e, const float4 *gbuf, size_t q, f3 n_p, f3 x_p, float inv_n, float inv_x)
+// e plus the normal and plane terms of a tap with normal n_q at x_q against the centre's guides.
+__device__ __forceinline__ float dn_guide_term(float e, f3 n_q, f3 x_q, f3 n_p, f3 x_p, float inv_n, float inv_x)
 {
-    const float4 g0 = gbuf[2 * q], g1 = gbuf[2 * q + 1];
-    const f3 dn = n_p - f3{g1.x, g1.y, g1.z};
+    const f3 dn = n_p - n_q;
     e = e + dot(dn, dn) * inv_n;
-    const f3 v = f3{g0.y, g0.z, g0.w} - x_p;
+    const f3 v = x_q - x_p;
     // (length > 0, not v != 0: positions ~1e-24 apart give v != 0 with dot(v, v) = 0, and 0 / 0 = NaN)
     const float len = length(v);
     if (len > 0.0f) e = e + (abs_(dot(n_p, v)) / len) * inv_x;
     return e;
+}
+
+// ... of tap q of the G-buffer.
+__device__ __forceinline__ float dn_guide_term(float e, const float4 *gbuf, size_t q, f3 n_p, f3 x_p, float inv_n, float inv_x)
+{
+    const float4 g0 = gbuf[2 * q], g1 = gbuf[2 * q + 1];
+    return dn_guide_term(e, f3{g1.x, g1.y, g1.z}, f3{g0.y, g0.z, g0.w}, n_p, x_p, inv_n, inv_x);
 }
 
 // One a-trous iteration (grid: dn_x16).  Taps at step * (-2..2)^2 inside the tile; the centre pixel's guides stay in
@@ -364,6 +370,20 @@ __device__ __forceinline__ bool dn_film_position(const DnReprojParams &P, f3 x_p
 // the filter's input P.cv.  What reaches P.h_cur is <*, false>'s bit for bit.
 // <*, *, true> (option "adaptive_temporal"; tests/denoise_temporal_adaptive_ref.py): the context is in the
 // adaptive state, and the n of the pixel is the count of its 8x8 tile wherever 6e-6g say n.  Nothing else differs.
+// 6g's variance of a pixel from its moments and whether it is known: F = Mw / n >= min_frames and t finite.  v = t where
+// known, 1 elsewhere.  The one statement of that test: k_dn_reproject<*, true> and k_dn_spatial_var (6j) both call it.
+__device__ __forceinline__ bool dn_known(float m1, float ms, float Mw, float n, float min_frames, float &v)
+{
+    v = 1.0f;
+    const float F = Mw / n;
+    if (!(F >= min_frames)) return false;
+    const float g = 2.2f * exp_(-2.2f * max_(m1, 0.0f));
+    const float t = (g * g) * (ms / (F - 1.0f));
+    if (!dn_finite(t)) return false;
+    v = t;
+    return true;
+}
+
 template <bool MOMENTS, bool ADAPT>
 using DnReprojArg = std::conditional_t<ADAPT, DnAdaptive<std::conditional_t<MOMENTS, DnSvgfParams, DnReprojParams>>,
                                        std::conditional_t<MOMENTS, DnSvgfParams, DnReprojParams>>;
@@ -456,13 +476,8 @@ __global__ __launch_bounds__(256) void k_dn_reproject(const DnReprojArg<MOMENTS,
     if constexpr (MOMENTS) {
         // the variance of the blend in display units: s / (F - 1) over F = Mw / n frames, through the exposure curve's slope
         // at m1 (as pixel_error); 1 ("nothing known", as k_dn_prepare_as) below min_frames or where it is not finite
-        float v = 1.0f;
-        const float F = Mw / n;
-        if (F >= P.min_frames) {
-            const float g = 2.2f * exp_(-2.2f * max_(m1, 0.0f));
-            const float t = (g * g) * (ms / (F - 1.0f));
-            if (dn_finite(t)) v = t;
-        }
+        float v;
+        dn_known(m1, ms, Mw, n, P.min_frames, v);
         P.m_cur[p] = float4{m1, ms, Mw, 0.0f};
         P.cv[p] = float4{c.x, c.y, c.z, v};
         if (P.var) P.var[p] = v;
@@ -487,6 +502,158 @@ __global__ __launch_bounds__(256) void k_dn_motion(const DnReprojParams P, float
     }
     out[p] = uv;
 }
+
+// ---------------------------------------------------------------- the spatial variance estimate (option "svgf_spatial_pct")
+// DESIGN.md 6j defines it operation by operation (tests/denoise_svgf_spatial_ref.py is its numpy restatement).  Launched
+// after k_dn_reproject<*, true> on the same grid: a pixel that is not `known` (dn_known) and not excluded takes
+// v = b g^2 (S / (A - 1)) / Mw_p from the precision-weighted spread of m1 over the 7x7 taps of its own key.
+//
+// The block's 22 x 22 halo tile is staged once in LDS as nine planes (key, m1, Mw, normal, position); both passes read LDS
+// only.  Row pitch 48 dwords: the two rows a 32-lane half of the wave reads in one ds_read_b32 lie 48 = 16 (mod 32) banks
+// apart, 16 consecutive dwords each, so the 32 lanes hit 32 different banks.  A row holds 22 of its 48 dwords, so two
+// planes share one set of rows, the second from dword 24 on.
+constexpr int kSvRadius = 3, kSvTile = 16 + 2 * kSvRadius, kSvPitch = 48, kSvPair = kSvTile * kSvPitch;
+constexpr uint32_t kDnNoTap = 0xFFFFFFFEu;                       // the key of a cell no pixel accepts (keys are < 2^26, or kNoHit)
+__device__ __forceinline__ constexpr int dn_sv_plane(int k) { return (k >> 1) * kSvPair + (k & 1) * (kSvPitch / 2); }
+
+// What a pixel's moments must hold to take part, as centre or as tap: m1 and Mw finite, Mw > 0.
+__device__ __forceinline__ bool dn_sv_holds(float m1, float Mw) { return dn_finite(m1) && dn_finite(Mw) && Mw > 0.0f; }
+
+template <bool ADAPT>
+__global__ __launch_bounds__(256) void k_dn_spatial_var(const std::conditional_t<ADAPT, DnAdaptive<DnSpatialParams>, DnSpatialParams> P)
+{
+    __shared__ float tile[5 * kSvPair];
+    const int x = dn_x16(), y = dn_y16();
+    const int tw = (int)P.tw, th = (int)P.th;
+    const size_t p = (size_t)y * P.tw + (size_t)x;
+    uint32_t key_p = kNoHit;
+    float Mw_p = 0.0f;
+    bool need = false;
+    if (x < tw && y < th) {
+        key_p = P.key[p];
+        const float4 m = P.m_cur[p];
+        float n = P.n, v;
+        if constexpr (ADAPT) n = (float)P.counts[(size_t)((uint32_t)y >> 3) * P.tiles_x + ((uint32_t)x >> 3)];
+        Mw_p = m.z;
+        need = !dn_known(m.x, m.y, m.z, n, P.min_frames, v) && key_p != kNoHit && (key_p >> 24) != kGlass && dn_sv_holds(m.x, m.z);
+    }
+    // every pixel of the block known or excluded (most blocks of a steady orbit): nothing is staged
+    if (!__syncthreads_or(need ? 1 : 0)) return;
+    const int bx = (int)(blockIdx.x * 16u) - kSvRadius, by = (int)(blockIdx.y * 16u) - kSvRadius;
+    for (int i = (int)threadIdx.x; i < kSvTile * kSvTile; i += 256) {
+        const int cy = i / kSvTile, cx = i - cy * kSvTile;
+        const int qx = bx + cx, qy = by + cy;
+        uint32_t k = kDnNoTap;                                  // outside the rectangle, or moments that take no part
+        float m1 = 0.0f, Mw = 0.0f;
+        float4 g0 = float4{0, 0, 0, 0}, g1 = float4{0, 0, 0, 0};
+        if (qx >= 0 && qx < tw && qy >= 0 && qy < th) {
+            const size_t q = (size_t)qy * P.tw + (size_t)qx;
+            const float4 m = P.m_cur[q];
+            if (dn_sv_holds(m.x, m.z)) {
+                k = P.key[q]; m1 = m.x; Mw = m.z;
+                if (k != kNoHit) { g0 = P.gbuf[2 * q]; g1 = P.gbuf[2 * q + 1]; }
+            }
+        }
+        const int c = cy * kSvPitch + cx;
+        tile[dn_sv_plane(0) + c] = bits_f(k);
+        tile[dn_sv_plane(1) + c] = m1;
+        tile[dn_sv_plane(2) + c] = Mw;
+        tile[dn_sv_plane(3) + c] = g1.x; tile[dn_sv_plane(4) + c] = g1.y; tile[dn_sv_plane(5) + c] = g1.z;
+        tile[dn_sv_plane(6) + c] = g0.y; tile[dn_sv_plane(7) + c] = g0.z; tile[dn_sv_plane(8) + c] = g0.w;
+    }
+    __syncthreads();
+    if (!need) return;
+    const int c0 = ((int)(threadIdx.x >> 4) + kSvRadius) * kSvPitch + (int)(threadIdx.x & 15u) + kSvRadius;
+    const auto nrm = [&](int c) { return f3{tile[dn_sv_plane(3) + c], tile[dn_sv_plane(4) + c], tile[dn_sv_plane(5) + c]}; };
+    const auto pos = [&](int c) { return f3{tile[dn_sv_plane(6) + c], tile[dn_sv_plane(7) + c], tile[dn_sv_plane(8) + c]}; };
+    const f3 n_p = nrm(c0), x_p = pos(c0);
+    // w Mw_q of the tap at cell c, and w itself; false: the tap is not accepted
+    const auto tap = [&](int c, bool centre, float &w, float &wm) {
+        if (f_bits(tile[dn_sv_plane(0) + c]) != key_p) return false;
+        w = centre ? 1.0f : exp_(-dn_guide_term(0.0f, nrm(c), pos(c), n_p, x_p, P.inv_n, P.inv_x));
+        wm = w * tile[dn_sv_plane(2) + c];
+        return true;
+    };
+    // Both loops are unrolled in full: the accepted taps and their w Mw_q stay in registers (a 49-bit mask, 49 floats), so
+    // the second pass reads m1 alone and evaluates no weight again.
+    constexpr int kSide = 2 * kSvRadius + 1;
+    float A = 0.0f, B = 0.0f, C = 0.0f, S = 0.0f, w, wm, wms[kSide * kSide];
+    uint64_t accepted = 0;
+#pragma unroll
+    for (int dy = -kSvRadius; dy <= kSvRadius; dy++)
+#pragma unroll
+        for (int dx = -kSvRadius; dx <= kSvRadius; dx++) {
+            const int c = c0 + dy * kSvPitch + dx, i = (dy + kSvRadius) * kSide + dx + kSvRadius;
+            wms[i] = 0.0f;
+            if (!tap(c, dx == 0 && dy == 0, w, wm)) continue;
+            accepted |= 1ull << i;
+            wms[i] = wm;
+            A = A + w;
+            B = B + wm;
+            C = C + wm * tile[dn_sv_plane(1) + c];
+        }
+    const float mu = C / B;
+    // (a second pass, not m2 - m1^2: 6g's cancellation; the window is in LDS, so it costs no traffic)
+#pragma unroll
+    for (int dy = -kSvRadius; dy <= kSvRadius; dy++)
+#pragma unroll
+        for (int dx = -kSvRadius; dx <= kSvRadius; dx++) {
+            const int c = c0 + dy * kSvPitch + dx, i = (dy + kSvRadius) * kSide + dx + kSvRadius;
+            if (!((accepted >> i) & 1ull)) continue;
+            const float d = tile[dn_sv_plane(1) + c] - mu;
+            S = S + wms[i] * (d * d);
+        }
+    const float s2 = S / (A - 1.0f);
+    const float g = 2.2f * exp_(-2.2f * max_(mu, 0.0f));
+    const float t = P.b * ((g * g) * (s2 / Mw_p));
+    const float v = A >= 4.0f && dn_finite(t) ? t : 1.0f;
+    P.cv[p].w = v;
+    if (P.var) P.var[p] = v;
+}
+
+#ifdef CRT_PROBE_SV_DIRECT
+// The probe build of DESIGN.md 6j (EXTRA=-DCRT_PROBE_SV_DIRECT): the same estimate with every tap gathered from global
+// memory, nothing staged -- what the LDS tile is measured against (timing only: no test runs it).
+template <bool ADAPT>
+__global__ __launch_bounds__(256) void k_dn_spatial_var_direct(const std::conditional_t<ADAPT, DnAdaptive<DnSpatialParams>, DnSpatialParams> P)
+{
+    const int x = dn_x16(), y = dn_y16();
+    const int tw = (int)P.tw, th = (int)P.th;
+    if (x >= tw || y >= th) return;
+    const size_t p = (size_t)y * P.tw + (size_t)x;
+    const uint32_t key_p = P.key[p];
+    const float4 m = P.m_cur[p];
+    float n = P.n, v0;
+    if constexpr (ADAPT) n = (float)P.counts[(size_t)((uint32_t)y >> 3) * P.tiles_x + ((uint32_t)x >> 3)];
+    if (dn_known(m.x, m.y, m.z, n, P.min_frames, v0) || key_p == kNoHit || (key_p >> 24) == kGlass || !dn_sv_holds(m.x, m.z)) return;
+    const DnGuides g_p = dn_centre_guides(P.gbuf, p, true);
+    float A = 0.0f, B = 0.0f, C = 0.0f, S = 0.0f, mu = 0.0f;
+    for (int pass = 0; pass < 2; pass++) {
+#pragma unroll 1
+        for (int dy = -kSvRadius; dy <= kSvRadius; dy++)
+#pragma unroll
+            for (int dx = -kSvRadius; dx <= kSvRadius; dx++) {
+                const int qx = x + dx, qy = y + dy;
+                if (qx < 0 || qx >= tw || qy < 0 || qy >= th) continue;
+                const size_t q = (size_t)qy * P.tw + (size_t)qx;
+                if (P.key[q] != key_p) continue;
+                const float4 mq = P.m_cur[q];
+                if (!dn_sv_holds(mq.x, mq.z)) continue;
+                const float w = dx == 0 && dy == 0 ? 1.0f : exp_(-dn_guide_term(0.0f, P.gbuf, q, g_p.n, g_p.x, P.inv_n, P.inv_x));
+                const float wm = w * mq.z;
+                if (pass == 0) { A = A + w; B = B + wm; C = C + wm * mq.x; }
+                else { const float d = mq.x - mu; S = S + wm * (d * d); }
+            }
+        mu = C / B;
+    }
+    const float g = 2.2f * exp_(-2.2f * max_(mu, 0.0f));
+    const float t = P.b * ((g * g) * ((S / (A - 1.0f)) / m.z));
+    const float v = A >= 4.0f && dn_finite(t) ? t : 1.0f;
+    P.cv[p].w = v;
+    if (P.var) P.var[p] = v;
+}
+#define k_dn_spatial_var k_dn_spatial_var_direct
+#endif
 
 // ---------------------------------------------------------------- launchers (declared in crt_launch.h; DnFilter: crt_device.h)
 hipError_t dn_launch_gbuffer(const DevScene &S, uint32_t x0, uint32_t y0, uint32_t tw, uint32_t th, float4 *gbuf, uint32_t *key,
@@ -624,8 +791,10 @@ hipError_t dn_launch_filter_adaptive(const DnFilter &F, const float4 *accum, con
 
 // crt_denoise_svgf: the blend into P.h_cur and the moments into P.m_cur, (c, v) into c[0], then the variance-guided passes
 // (h_cur and m_cur stay unfiltered: they are the next frame's history).  counts: as dn_launch_temporal.
+// spatial_b: 0, or the factor of option "svgf_spatial_pct" -- k_dn_spatial_var then rewrites the v of the pixels the moments
+// do not cover before the passes read it; what stays behind in h_cur and m_cur does not depend on it.
 hipError_t dn_launch_svgf(const DnFilter &F, DnSvgfParams P, const uint32_t *counts, uint2 *kv, float *var, float sigma_variance,
-                          float4 **out)
+                          float spatial_b, float4 **out)
 {
     *out = F.c[0];
     if ((size_t)F.tw * F.th == 0) return hipSuccess;
@@ -633,7 +802,19 @@ hipError_t dn_launch_svgf(const DnFilter &F, DnSvgfParams P, const uint32_t *cou
     P.rgba = last0 ? F.rgba : nullptr;
     P.var = last0 ? var : nullptr;
     P.cv = F.c[0];
-    const hipError_t e = dn_launch_reproject<true>(F, P, counts);
+    hipError_t e = dn_launch_reproject<true>(F, P, counts);
+    if (e == hipSuccess && spatial_b != 0.0f) {
+        DnAdaptive<DnSpatialParams> A{};
+        A.m_cur = P.m_cur; A.gbuf = F.gbuf; A.key = F.key;
+        A.cv = P.cv; A.var = P.var;
+        A.tw = F.tw; A.th = F.th;
+        A.n = P.n; A.min_frames = P.min_frames; A.b = spatial_b;
+        dn_guide_sigmas(F, A.inv_n, A.inv_x);
+        A.counts = counts; A.tiles_x = (F.tw + 7u) / 8u;
+        if (counts) hipLaunchKernelGGL(k_dn_spatial_var<true>, dn_grid16(F), dim3(256), 0, F.stream, A);
+        else hipLaunchKernelGGL(k_dn_spatial_var<false>, dn_grid16(F), dim3(256), 0, F.stream, static_cast<const DnSpatialParams &>(A));
+        e = hipGetLastError();
+    }
     return e != hipSuccess ? e : dn_run_atrous_as(F, kv, var, sigma_variance, out);
 }
 

@@ -236,6 +236,7 @@ struct ThCall {
     bool svgf;
     float sigma_color;                  // !svgf
     float sigma_variance, min_frames;   // svgf
+    float spatial_b;                    // svgf: 0, or the factor of option "svgf_spatial_pct" 
 };
 
 static int th_blend_and_filter(crt_ctx *c, const ThCall &t, bool rgba, bool hist, bool var, float4 **res)
@@ -275,7 +276,7 @@ static int th_blend_and_filter(crt_ctx *c, const ThCall &t, bool rgba, bool hist
         P.m_prev = P.h_prev && prev.has_m ? prev.m.p : nullptr;
         P.m_cur = cur.m.p;
         P.min_frames = t.min_frames;
-        HIPCHK(c, dn_launch_svgf(F, P, counts, c->dn.kv.p, var ? c->dn.var.p : nullptr, t.sigma_variance, res));
+        HIPCHK(c, dn_launch_svgf(F, P, counts, c->dn.kv.p, var ? c->dn.var.p : nullptr, t.sigma_variance, t.spatial_b, res));
     } else {
         HIPCHK(c, dn_launch_temporal(F, P, counts, t.sigma_color, res));
     }
@@ -297,7 +298,7 @@ int crt_denoise_temporal(crt_ctx *c, const crt_denoise_temporal_params *params, 
     float *hw_host = history_out ? history_out : hw.empty() ? nullptr : hw.data();
     if (n) {
         const ThCall t{dp.iterations, dp.sigma_normal, dp.sigma_plane, dp.max_history, dp.normal_tol, dp.plane_tol, false,
-                       dp.sigma_color, 0.0f, 0.0f};
+                       dp.sigma_color, 0.0f, 0.0f, 0.0f};
         CRT_TRY(th_blend_and_filter(c, t, rgba8_out != nullptr, history_out || rgb_out, false, &res));
     }
     const int rc = dn_finish(c, n, res, rgb_out, rgba8_out, c->dn.hist.p, hw_host);
@@ -328,7 +329,7 @@ int crt_denoise_svgf(crt_ctx *c, const crt_denoise_svgf_params *params, float *r
     float4 *res = nullptr;
     if (n) {
         const ThCall t{dp.iterations, dp.sigma_normal, dp.sigma_plane, dp.max_history, dp.normal_tol, dp.plane_tol, true,
-                       0.0f, dp.sigma_variance, dp.min_frames};
+                       0.0f, dp.sigma_variance, dp.min_frames, (float)c->svgf_spatial_pct / 100.0f};
         CRT_TRY(th_blend_and_filter(c, t, rgba8_out != nullptr, history_out != nullptr, var_out != nullptr, &res));
         if (var_out) HIPCHK(c, hipMemcpyAsync(var_out, c->dn.var.p, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     }

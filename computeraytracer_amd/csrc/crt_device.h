@@ -289,6 +289,21 @@ struct DnSvgfParams : DnReprojParams {
     float min_frames;               // v is trusted from Mw / n >= this on
 };
 
+// k_dn_spatial_var (option "svgf_spatial_pct"): after k_dn_reproject<*, true>, the pixels whose variance the
+// moments do not give yet take an estimate from the spread of m1 over their 7x7 neighbourhood.  A struct of its own, so that
+// k_dn_reproject keeps its argument block.
+struct DnSpatialParams {
+    const float4 *m_cur;            // this frame's moments (m1, s, Mw, 0), as k_dn_reproject left them
+    const float4 *gbuf;             // its G-buffer and keys
+    const uint32_t *key;
+    float4 *cv;                     // (c, v): only the w lane is rewritten
+    float *var;                     // null, or v alone (no filter pass follows)
+    uint32_t tw, th;
+    float n, min_frames;            // what decides `known`, as in DnSvgfParams
+    float b;                        // the option's factor, P / 100
+    float inv_n, inv_x;             // the filter's 1 / sigma_normal^2 and 1 / sigma_plane
+};
+
 // k_dn_reproject<*, *, true>: the blend in the adaptive state, where the n of pixel p is the count of its 8x8
 // tile.  Derived from either block above, so that the <*, *, false> kernels keep theirs.
 template <class Base>

@@ -85,8 +85,9 @@ hipError_t dn_launch_filter_adaptive(const DnFilter &F, const float4 *accum, con
                                      float *var, float sigma_variance, float4 **out);
 // (counts: null in the uniform state, where P.n is every pixel's n; else the adaptive state's count per 8x8 tile)
 hipError_t dn_launch_temporal(const DnFilter &F, DnReprojParams P, const uint32_t *counts, float sigma_color, float4 **out);
+// (spatial_b: 0, or the factor of option "svgf_spatial_pct")
 hipError_t dn_launch_svgf(const DnFilter &F, DnSvgfParams P, const uint32_t *counts, uint2 *kv, float *var, float sigma_variance,
-                          float4 **out);
+                          float spatial_b, float4 **out);
 hipError_t dn_launch_motion(const DnReprojParams &P, float2 *out, hipStream_t stream);
 
 }  // namespace crt

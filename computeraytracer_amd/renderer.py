@@ -379,7 +379,9 @@ class Renderer:
         of the pixel's luminance (include/crt.h "Variance-guided temporal filter"): rgba8 (H, W, 4); with rgb=True also
         linear rgb (H, W, 4) float32 (channel 3 = the variance), with history=True also Hw, with var=True also the
         variance left after filtering, both (H, W) float32 -- a tuple in that order.  A parameter left out takes the
-        library's default (crt_denoise_svgf_defaults).  Reads the accumulator only; finishes what is in flight."""
+        library's default (crt_denoise_svgf_defaults).  Reads the accumulator only; finishes what is in flight.
+        set_option("svgf_spatial_pct", P) (0 = off, the default; 25..10000) gives the pixels whose history is too short for
+        that variance one from the spread of their 7x7 neighbourhood, times P / 100; the history does not depend on it."""
         _, _, tw, th = self.tile
         p = _lib.denoise_svgf_defaults()
         for k, v in dict(iterations=iterations, sigma_variance=sigma_variance, sigma_normal=sigma_normal, sigma_plane=sigma_plane,

@@ -1,7 +1,7 @@
 #!/usr/bin/env node
 'use strict';
 // CLI: node host/index.js [--scene file.json] [--width W --height H] [--spp N] [--accel bvh2|lbvh|ploc|none]
-//                         [--out image.ppm] [--dump prefix] [--pack-only prefix] [--denoise K] [--orbit N [--temporal [--variance]]]
+//                         [--out image.ppm] [--dump prefix] [--pack-only prefix] [--denoise K] [--orbit N [--temporal [--variance [--spatial [PCT]]]]]
 // --denoise K: --out gets the image denoised with K a-trous iterations (crt_denoise; with --adaptive the variance-guided
 //            crt_denoise_adaptive) instead of the plain average
 // --orbit N: N frames of --spp each, the eye turned about the look-at point (one upload and build, then setCamera per
@@ -10,6 +10,8 @@
 //            reprojected result of frame k - 1 before the filter (denoiseTemporal)
 // --variance: with --temporal, the passes after the blend are variance-guided, the variance taken from the spread of the
 //            frame means (denoiseSvgf)
+// --spatial [PCT]: with --variance, option "svgf_spatial_pct" = PCT (25..10000, 400 when given bare): a pixel with too short
+//            a history for a temporal variance takes one from the spread of its 7x7 neighbourhood, times PCT / 100
 // --adaptive T [--adaptive-step N] [--adaptive-min M]: adaptive sampling (traceAdaptive), rounds of N (16) samples until
 //            every 8x8 tile has an error <= T or holds --spp samples; a tile below M (default min(--spp, 2N)) samples is
 //            sampled whatever its error; prints rounds, pixel-samples, seconds and the min / median / max tile count.
@@ -45,6 +47,10 @@ if (args['pack-only']) { // dump the packed host buffers (used by the packer par
 const spp = num('spp', 16);
 if (args.temporal && !(args.orbit && 'denoise' in args)) { console.error('--temporal goes with --orbit N --denoise K'); process.exit(2); }
 if (args.variance && !args.temporal) { console.error('--variance goes with --orbit N --denoise K --temporal'); process.exit(2); }
+const spatial = !('spatial' in args) ? null : args.spatial === true ? 400 : Number(args.spatial);
+if (spatial !== null && !(args.variance && Number.isInteger(spatial) && spatial >= 25 && spatial <= 10000)) {
+  console.error('--spatial [PCT] goes with --orbit N --denoise K --temporal --variance, PCT in 25..10000'); process.exit(2);
+}
 const r = Main({ sceneFile: args.scene, width: args.width ? num('width') : undefined, height: args.height ? num('height') : undefined,
   accel: args.accel || 'bvh2', device: num('device', 0) });
 // --adaptive: rounds of --adaptive-step samples until no tile is active; {rounds, ad: readAdaptive(), pixelSamples}
@@ -64,6 +70,7 @@ if (args.orbit) {
   const t1 = process.hrtime.bigint();
   // --adaptive with --temporal: few samples per frame, placed where the noise is, accumulated over time
   if ('adaptive' in args && args.temporal) r.setOption('adaptive_temporal', 1);
+  if (spatial !== null) r.setOption('svgf_spatial_pct', spatial);
   orbitCameras(r.packed.camera, n).forEach((cam, k) => {
     r.setCamera(cam);
     if (args.temporal) r.setSampleOffset(k * spp);

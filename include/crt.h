@@ -611,7 +611,23 @@ int crt_read_motion(crt_ctx *ctx, float *out);
  * contract (a sync point, reads only, CRT_ESTATE in the same places) are crt_denoise_temporal's, and what it leaves in
  * CURRENT's colour plane is bit for bit what crt_denoise_temporal leaves there.  The two calls mix: a
  * crt_denoise_temporal writes CURRENT without moments, and a later crt_denoise_svgf reuses its colour history and starts
- * the moments again (Mw = n).  A failed allocation (CRT_ENOMEM) leaves the slots as they were. */
+ * the moments again (Mw = n).  A failed allocation (CRT_ENOMEM) leaves the slots as they were.
+ *
+ * Option "svgf_spatial_pct" = P (default 0 = off; 25..10000; anything else is CRT_EINVAL): v = 1 is a very
+ * wide colour term, and it is what every pixel carries on the first min_frames - 1 frames after the history was dropped and
+ * what every disoccluded pixel carries afterwards.  With P != 0 a pixel whose v is not known from the moments (F <
+ * min_frames, or a value that is not finite) and that is neither a miss nor glass takes a spatial estimate instead, from its
+ * 7x7 neighbourhood at unit step: over the taps q inside the rectangle with the pixel's key and finite m1, Mw > 0, weighted
+ * with the filter's normal and plane terms w_q (no colour term; w = 1 at the centre), A = sum w, mu = sum w Mw_q m1_q /
+ * sum w Mw_q, sigma^2 = sum w Mw_q (m1_q - mu)^2 / (A - 1) -- each m1_q is a mean over Mw_q samples, so this is the
+ * variance per sample -- and v = (P / 100) g(mu)^2 sigma^2 / Mw_p where A >= 4 and the value is finite, v = 1 elsewhere.
+ * Only the v that enters the passes changes (at iterations = 0 that is var_out and rgb_out's channel 3): what the call
+ * leaves in CURRENT -- colour, Hw, moments -- is bit for bit what it leaves with P = 0, so the history never depends on the
+ * option, the option may change between frames, and the pixels whose v is known keep it bit for bit.
+ * crt_denoise_temporal and crt_denoise_adaptive ignore the option.  It costs 0-3 % of quality on frames where most pixels
+ * are known and 9 % on the very first frame, and gains up to 24 % on the frames between, on scenes whose surfaces are
+ * large against the window; on a finely detailed scene (S2) it made the preview worse at every P measured, and
+ * crt_denoise_temporal stays the better preview there: DESIGN.md 6j has the tables. */
 typedef struct {
     uint32_t iterations;    /* variance-guided passes after the blend, 0..10 */
     float sigma_variance;   /* as crt_denoise_adaptive_params */
@@ -675,6 +691,9 @@ int crt_last_kernel_ms(crt_ctx *ctx, float *ms, uint32_t *launches);
  * "adaptive_temporal" (0 | 1, anything else is CRT_EINVAL; default 0: 1 lets crt_trace_adaptive take the sample offset
  * and the temporal filters take the adaptive state, each pixel blended with its own tile's count, see "Sample offset"
  * and "Temporal reuse"; with 0 every call launches what it launches without the option);
+ * "svgf_spatial_pct" (0 = off, default | 25..10000, anything else is CRT_EINVAL: crt_denoise_svgf gives the pixels whose
+ * variance the temporal moments do not cover yet an estimate from their 7x7 neighbourhood, times that percentage, see
+ * "Variance-guided temporal filter"; it drops nothing, and with 0 the call launches what it launches without the option);
  * "ploc_radius" (1..32, anything else is CRT_EINVAL; default 8: clusters searched to either side by CRT_ACCEL_PLOC; at
  * crt_build_accel);
  * "refit_rebuild_pct" (0 = off, default | 100..100000, anything else is CRT_EINVAL: crt_refit_accel rebuilds once the

@@ -8,10 +8,13 @@ alternation also exercises the hand-over of CURRENT between the two calls.
   svgf.k0_compute       K = 0: k_dn_reproject<*, true> alone
   temporal.k5_compute   crt_denoise_temporal, K = 5
   k5_ratio              svgf.k5_compute / temporal.k5_compute (medians); DESIGN.md 6g accepts <= 1.5
+  svgf.k5_compute_pP    with --spatial-pct P [P ...]: the K = 5 call under option "svgf_spatial_pct" = P, in the
+                        same alternation; the option is set outside the timed region.  --frames 1 times the frame on which no
+                        pixel's variance is known, --frames 8 a frame of the steady orbit
 
 --sweep instead measures quality on S2 at 480 x 270: an orbit of --frames frames of --spp samples, 1/--turn of a turn
 apart; MSE in display space T of the last frame's crt_denoise_svgf (K = 5) over that of crt_denoise_temporal on the same
-frames, against --converged-spp samples, for sigma_variance x min_frames.
+frames, against --converged-spp samples, for sigma_variance x min_frames (x --spatial-pct, where given).
 
 Per-kernel times come from a separate run of the default mode under rocprofv3 --kernel-trace --stats.  Prints one JSON
 line; --out also writes it."""
@@ -54,9 +57,14 @@ def speed(a):
     calls = {"svgf_k5": lambda: r._chk(lib.crt_denoise_svgf(h, C.byref(s5), None, None, None, None)),
              "temporal_k5": lambda: r._chk(lib.crt_denoise_temporal(h, C.byref(t5), None, None, None)),
              "svgf_k0": lambda: r._chk(lib.crt_denoise_svgf(h, C.byref(s0), None, None, None, None))}
+    pct = {k: 0 for k in calls}
+    for p in a.spatial_pct or []:
+        calls[f"svgf_k5_p{p}"], pct[f"svgf_k5_p{p}"] = calls["svgf_k5"], p
     ts = {k: [] for k in calls}
-    for i in range(10 + a.reps):                                # alternately: what shares the machine hits all three alike
+    for i in range(10 + a.reps):                                # alternately: what shares the machine hits all of them alike
         for k, fn in calls.items():
+            if a.spatial_pct:
+                r.set_option("svgf_spatial_pct", pct[k])
             t = time.perf_counter()
             fn()
             if i >= 10:
@@ -67,6 +75,8 @@ def speed(a):
            "pixels_with_known_variance": round(float((mom[..., 2] / np.float32(a.spp) >= d.min_frames).mean()), 4),
            "svgf": {"k5_compute": summary(ts["svgf_k5"]), "k0_compute": summary(ts["svgf_k0"])},
            "temporal": {"k5_compute": summary(ts["temporal_k5"])}}
+    for p in a.spatial_pct or []:
+        res["svgf"][f"k5_compute_p{p}"] = summary(ts[f"svgf_k5_p{p}"])
     res["k5_ratio"] = round(res["svgf"]["k5_compute"]["median_ms"] / res["temporal"]["k5_compute"]["median_ms"], 4)
     r.close()
     return res
@@ -93,8 +103,12 @@ def sweep(a):
     out["mse_temporal"] = orbit(lambda: r.denoise_temporal(rgb=True))
     for sv in a.sigma_variance:
         for mf in a.min_frames:
-            m = orbit(lambda: r.denoise_svgf(sigma_variance=sv, min_frames=mf, rgb=True))
-            out["rows"].append({"sigma_variance": sv, "min_frames": mf, "mse_svgf": m, "ratio": round(m / out["mse_temporal"], 4)})
+            for p in a.spatial_pct or [None]:
+                if p is not None:
+                    r.set_option("svgf_spatial_pct", p)
+                m = orbit(lambda: r.denoise_svgf(sigma_variance=sv, min_frames=mf, rgb=True))
+                row = {"sigma_variance": sv, "min_frames": mf, "mse_svgf": m, "ratio": round(m / out["mse_temporal"], 4)}
+                out["rows"].append(row if p is None else dict(row, spatial_pct=p))
     r.close()
     return out
 
@@ -111,6 +125,8 @@ def main():
     ap.add_argument("--converged-spp", type=int, default=1024)
     ap.add_argument("--sigma-variance", type=float, nargs="+", default=[1.0, 2.0, 4.0, 8.0])
     ap.add_argument("--min-frames", type=float, nargs="+", default=[2.0, 3.0, 4.0])
+    ap.add_argument("--spatial-pct", type=int, nargs="+", default=None, metavar="P",
+                    help="option svgf_spatial_pct: the values to time the K = 5 call under, or with --sweep to measure")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     line = json.dumps(sweep(a) if a.sweep else speed(a))
