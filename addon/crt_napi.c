@@ -597,12 +597,13 @@ static napi_value js_denoise(napi_env env, napi_callback_info info)
  * with variance: true -> {rgba8, variance: Float32Array(tw*th)}: the variance-guided filter of an adaptive render
  * (include/crt.h "Denoised preview of an adaptive render").  A missing option takes the library's default
  * (crt_denoise_adaptive_defaults).  denoiseAdaptiveAsync(h, {...}) -> Promise of the Uint8Array (below). */
-static int denoise_adaptive_options(napi_env env, napi_value opts, int have_opts, crt_denoise_adaptive_params *p, bool *variance)
+static int denoise_adaptive_options(napi_env env, const char *fn, napi_value opts, int have_opts, crt_denoise_adaptive_params *p,
+                                    bool *variance)
 {
     if (crt_denoise_adaptive_defaults(p) != CRT_OK) { napi_throw_error(env, NULL, "crt_denoise_adaptive_defaults failed"); return 0; }
     double it = p->iterations, sv = p->sigma_variance, sn = p->sigma_normal, sx = p->sigma_plane;
     const dn_opt o[] = {{"iterations", &it}, {"sigmaVariance", &sv}, {"sigmaNormal", &sn}, {"sigmaPlane", &sx}};
-    if (!denoise_options(env, "denoiseAdaptive", opts, have_opts, o, 4, "variance", variance)) return 0;
+    if (!denoise_options(env, fn, opts, have_opts, o, 4, variance ? "variance" : NULL, variance)) return 0;
     p->iterations = (uint32_t)it; p->sigma_variance = (float)sv; p->sigma_normal = (float)sn; p->sigma_plane = (float)sx;
     return 1;
 }
@@ -612,7 +613,7 @@ static napi_value js_denoise_adaptive(napi_env env, napi_callback_info info)
     DENOISE_ARGS
     crt_denoise_adaptive_params p;
     bool variance = false;
-    if (!denoise_adaptive_options(env, argc > 1 ? argv[1] : NULL, argc > 1, &p, &variance)) return NULL;
+    if (!denoise_adaptive_options(env, "denoiseAdaptive", argc > 1 ? argv[1] : NULL, argc > 1, &p, &variance)) return NULL;
     dn_out out;
     if (!denoise_outputs(env, ctx, variance, &out)) return NULL;
     CRT_CHECK(env, ctx, "crt_denoise_adaptive", crt_denoise_adaptive(ctx, &p, NULL, (uint8_t *)out.rgba8, (float *)out.plane));
@@ -638,7 +639,7 @@ static napi_value js_denoise_adaptive_frame(napi_env env, napi_callback_info inf
     DENOISE_ARGS
     crt_denoise_adaptive_params p;
     bool variance = false;
-    if (!denoise_adaptive_options(env, argc > 1 ? argv[1] : NULL, argc > 1, &p, &variance)) return NULL;
+    if (!denoise_adaptive_options(env, "denoiseAdaptive", argc > 1 ? argv[1] : NULL, argc > 1, &p, &variance)) return NULL;
     dn_out out;
     if (!outputs_of(env, ctx, 1, variance, &out)) return NULL;
     CRT_CHECK(env, ctx, "crt_denoise_adaptive_frame", crt_denoise_adaptive_frame(ctx, &p, NULL, (uint8_t *)out.rgba8, (float *)out.plane));
@@ -950,8 +951,10 @@ static napi_value js_refit_accel(napi_env env, napi_callback_info info)
 /* ------------------------------------------------------------------ adaptive sampling (include/crt.h "Adaptive sampling")
  * traceAdaptive(h, {samples, threshold, minSamples, maxSamples}) -> active tiles (0: done); a missing option takes the
  * library's default (crt_adaptive_defaults).  readAdaptive(h) -> {counts: Uint32Array, errors: Float32Array, tilesX, tilesY}. */
-static napi_value js_trace_adaptive(napi_env env, napi_callback_info info)
+static napi_value trace_adaptive(napi_env env, napi_callback_info info, int filtered)
 {
+    const char *fn = filtered ? "traceAdaptiveFiltered" : "traceAdaptive";
+    char msg[128];
     size_t argc = 2;
     napi_value argv[2];
     NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
@@ -966,34 +969,56 @@ static napi_value js_trace_adaptive(napi_env env, napi_callback_info info)
     if (t == napi_object) {
         if (!opt_number(env, argv[1], "samples", &s) || !opt_number(env, argv[1], "threshold", &thr) ||
             !opt_number(env, argv[1], "minSamples", &mn) || !opt_number(env, argv[1], "maxSamples", &mx)) {
-            napi_throw_type_error(env, NULL, "traceAdaptive: options must be numbers");
+            snprintf(msg, sizeof msg, "%s: options must be numbers", fn);
+            napi_throw_type_error(env, NULL, msg);
             return NULL;
         }
     } else if (t != napi_undefined && t != napi_null) {
-        napi_throw_type_error(env, NULL, "traceAdaptive: options object expected");
+        snprintf(msg, sizeof msg, "%s: options object expected", fn);
+        napi_throw_type_error(env, NULL, msg);
         return NULL;
     }
     const double counts[3] = {s, mn, mx};
     for (int k = 0; k < 3; k++)
         if (!(counts[k] >= 0.0 && counts[k] <= 4294967295.0) || counts[k] != (double)(uint32_t)counts[k]) {
-            napi_throw_range_error(env, NULL, "traceAdaptive: samples, minSamples and maxSamples must be non-negative integers");
+            snprintf(msg, sizeof msg, "%s: samples, minSamples and maxSamples must be non-negative integers", fn);
+            napi_throw_range_error(env, NULL, msg);
             return NULL;
         }
     crt_adaptive_params p = {(uint32_t)s, (uint32_t)mn, (uint32_t)mx, (float)thr};
     uint32_t n = 0;
-    CRT_CHECK(env, ctx, "crt_trace_adaptive", crt_trace_adaptive(ctx, &p, &n));
+    if (filtered) {                                              /* (the filter's options live in the same object) */
+        crt_denoise_adaptive_params f;
+        if (!denoise_adaptive_options(env, fn, argc > 1 ? argv[1] : NULL, argc > 1, &f, NULL)) return NULL;
+        CRT_CHECK(env, ctx, "crt_trace_adaptive_filtered", crt_trace_adaptive_filtered(ctx, &p, &f, &n));
+    } else {
+        CRT_CHECK(env, ctx, "crt_trace_adaptive", crt_trace_adaptive(ctx, &p, &n));
+    }
     napi_value v;
     NAPI_OK(env, napi_create_uint32(env, n, &v));
     return v;
 }
+static napi_value js_trace_adaptive(napi_env env, napi_callback_info info) { return trace_adaptive(env, info, 0); }
+/* traceAdaptiveFiltered(h, {samples, threshold, minSamples, maxSamples, iterations, sigmaVariance, sigmaNormal, sigmaPlane})
+ * -> active tiles: traceAdaptive with the tiles judged by the variance denoiseAdaptive leaves (include/crt.h "Adaptive
+ * sampling judged by the filtered preview"); readAdaptiveFiltered(h, {iterations, sigmaVariance, sigmaNormal, sigmaPlane})
+ * -> readAdaptive's object with errors = E'. */
+static napi_value js_trace_adaptive_filtered(napi_env env, napi_callback_info info) { return trace_adaptive(env, info, 1); }
 
 /* readAdaptive(h) -> {counts, errors, tilesX, tilesY} of the context's rectangle; readFrameAdaptive(h): of the whole frame of
  * the latest PREVIEW gather (include/crt.h "The frame of a partition"). */
 static napi_value read_adaptive(napi_env env, napi_callback_info info, int frame)
 {
-    ARGS(1)
+    size_t argc = 2;
+    napi_value argv[2];
+    NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    if (argc < 1) { napi_throw_type_error(env, NULL, "too few arguments"); return NULL; }
     crt_ctx *ctx = get_ctx(env, argv[0]);
     if (!ctx) return NULL;
+    const int filtered = frame == 2;                             /* readAdaptiveFiltered(h, {the filter's options}) */
+    frame = frame == 1;
+    crt_denoise_adaptive_params f;
+    if (filtered && !denoise_adaptive_options(env, "readAdaptiveFiltered", argc > 1 ? argv[1] : NULL, argc > 1, &f, NULL)) return NULL;
     uint32_t tl[4];
     if (frame) CRT_CHECK(env, ctx, "crt_image_size", crt_image_size(ctx, tl + 2));
     else CRT_CHECK(env, ctx, "crt_tile", crt_tile(ctx, tl));
@@ -1004,6 +1029,7 @@ static napi_value read_adaptive(napi_env env, napi_callback_info info, int frame
     NAPI_OK(env, napi_create_arraybuffer(env, nt * 4, &dc, &abc));
     NAPI_OK(env, napi_create_arraybuffer(env, nt * 4, &de, &abe));
     if (frame) CRT_CHECK(env, ctx, "crt_read_frame_adaptive", crt_read_frame_adaptive(ctx, (uint32_t *)dc, (float *)de));
+    else if (filtered) CRT_CHECK(env, ctx, "crt_read_adaptive_filtered", crt_read_adaptive_filtered(ctx, &f, (uint32_t *)dc, (float *)de));
     else CRT_CHECK(env, ctx, "crt_read_adaptive", crt_read_adaptive(ctx, (uint32_t *)dc, (float *)de));
     NAPI_OK(env, napi_create_typedarray(env, napi_uint32_array, nt, abc, 0, &tc));
     NAPI_OK(env, napi_create_typedarray(env, napi_float32_array, nt, abe, 0, &te));
@@ -1018,6 +1044,7 @@ static napi_value read_adaptive(napi_env env, napi_callback_info info, int frame
 }
 static napi_value js_read_adaptive(napi_env env, napi_callback_info info) { return read_adaptive(env, info, 0); }
 static napi_value js_read_frame_adaptive(napi_env env, napi_callback_info info) { return read_adaptive(env, info, 1); }
+static napi_value js_read_adaptive_filtered(napi_env env, napi_callback_info info) { return read_adaptive(env, info, 2); }
 
 /* ------------------------------------------------------------------ multi-GPU (include/crt.h "Multi-GPU") and composition
  * The reference drives one GPUDevice (src/main.js:8-9); a Node host reaches the tile-partitioned configurations through
@@ -1315,7 +1342,7 @@ static napi_value start_job(napi_env env, napi_callback_info info, int op)
     job *j = (job *)calloc(1, sizeof *j);
     j->sl = sl; j->op = op;
     if (op == JOB_DENOISE_FRAME && !denoise_plain_options(env, "denoiseFrameAsync", argc > 1 ? argv[1] : NULL, argc > 1, &j->df)) { free(j); return NULL; }
-    if ((op == JOB_DENOISE_ADAPTIVE || op == JOB_DENOISE_ADAPTIVE_FRAME) && !denoise_adaptive_options(env, argc > 1 ? argv[1] : NULL, argc > 1, &j->dn, NULL)) { free(j); return NULL; }
+    if ((op == JOB_DENOISE_ADAPTIVE || op == JOB_DENOISE_ADAPTIVE_FRAME) && !denoise_adaptive_options(env, "denoiseAdaptive", argc > 1 ? argv[1] : NULL, argc > 1, &j->dn, NULL)) { free(j); return NULL; }
     if (op == JOB_DENOISE_TEMPORAL && !denoise_temporal_options(env, argc > 1 ? argv[1] : NULL, argc > 1, &j->dt, NULL)) { free(j); return NULL; }
     if (op == JOB_DENOISE_SVGF && !denoise_svgf_options(env, argc > 1 ? argv[1] : NULL, argc > 1, &j->ds, NULL, NULL)) { free(j); return NULL; }
     if (op == JOB_TRACE || op == JOB_GATHER || op == JOB_READ_SAMPLE_RGBA8) {
@@ -1442,6 +1469,7 @@ static napi_value init(napi_env env, napi_value exports)
         {"removePrimitives", js_remove_primitives}, {"removePrimitivesAsync", js_remove_primitives_async},
         {"appendPrimitives", js_append_primitives}, {"appendPrimitivesAsync", js_append_primitives_async},
         {"traceAdaptive", js_trace_adaptive}, {"readAdaptive", js_read_adaptive},
+        {"traceAdaptiveFiltered", js_trace_adaptive_filtered}, {"readAdaptiveFiltered", js_read_adaptive_filtered},
         {"denoiseAdaptive", js_denoise_adaptive}, {"denoiseAdaptiveAsync", js_denoise_adaptive_async},
         {"setSampleOffset", js_set_sample_offset}, {"sampleOffset", js_sample_offset}, {"temporalReset", js_temporal_reset},
         {"denoiseTemporal", js_denoise_temporal}, {"denoiseTemporalAsync", js_denoise_temporal_async},

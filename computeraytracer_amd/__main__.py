@@ -1,5 +1,5 @@
 """python -m computeraytracer_amd [--scene file.json] [--width W --height H] [--spp N] [--out image.png] [--denoise K] [--orbit N [--temporal [--variance] [--animate | --animate-device [--rebuild-pct P] | --blink P]]]
-                                [--adaptive THRESHOLD [--adaptive-step N] [--counts-out counts.png]]
+                                [--adaptive THRESHOLD [--adaptive-filtered] [--adaptive-step N] [--counts-out counts.png]]
 --adaptive goes with --orbit: every frame is sampled adaptively up to --spp, and with --denoise K --temporal [--variance] the
 temporal filters blend it with each pixel's own tile count (option "adaptive_temporal")."""
 import argparse
@@ -58,6 +58,10 @@ def parse_args(argv=None):
                          "error is above THRESHOLD, --spp samples at most, until every tile is done; with --orbit N every "
                          "frame is sampled so (frame k from sample index k * spp + 1 on with --temporal) and the mean samples "
                          "per pixel of each frame are printed")
+    ap.add_argument("--adaptive-filtered", action="store_true",
+                    help="with --adaptive: THRESHOLD judges the noise the variance-guided filter leaves in the tile instead of "
+                         "the raw pixel error (crt_trace_adaptive_filtered; the filter runs --denoise K iterations where given, "
+                         "else its default)")
     ap.add_argument("--adaptive-step", type=int, default=16, metavar="N", help="with --adaptive: samples per round (16)")
     ap.add_argument("--adaptive-min", type=int, default=None, metavar="M",
                     help="with --adaptive: a tile below M samples is sampled whatever its error (default: min(--spp, 2N))")
@@ -84,6 +88,8 @@ def parse_args(argv=None):
         ap.error("--adaptive does not go with --checkpoint")
     if (args.counts_out or args.adaptive_min is not None) and args.adaptive is None:
         ap.error("--counts-out and --adaptive-min need --adaptive")
+    if args.adaptive_filtered and args.adaptive is None:
+        ap.error("--adaptive-filtered needs --adaptive")
     return args
 
 
@@ -214,7 +220,12 @@ def _adaptive_rounds(r, args):
     """Rounds of --adaptive-step samples until no tile is active: (the tile counts, the rounds)."""
     rounds = 0
     min_samples = min(args.spp, 2 * args.adaptive_step) if args.adaptive_min is None else args.adaptive_min
-    while r.trace_adaptive(samples=args.adaptive_step, threshold=args.adaptive, min_samples=min_samples, max_samples=args.spp):
+    rule = dict(samples=args.adaptive_step, threshold=args.adaptive, min_samples=min_samples, max_samples=args.spp)
+    if args.adaptive_filtered:
+        trace = lambda: r.trace_adaptive_filtered(iterations=args.denoise, **rule)
+    else:
+        trace = lambda: r.trace_adaptive(**rule)
+    while trace():
         rounds += 1
     return r.read_adaptive()[0], rounds
 

@@ -89,6 +89,8 @@ SIGNATURES = {
     "crt_trace_adaptive": (C.c_int, [_P, _P, _P]),
     "crt_read_adaptive": (C.c_int, [_P, _P, _P]),
     "crt_adaptive_defaults": (C.c_int, [_P]),
+    "crt_trace_adaptive_filtered": (C.c_int, [_P, _P, _P, _P]),
+    "crt_read_adaptive_filtered": (C.c_int, [_P, _P, _P, _P]),
     "crt_denoise_adaptive": (C.c_int, [_P, _P, _P, _P, _P]),
     "crt_denoise_adaptive_defaults": (C.c_int, [_P]),
     "crt_read_frame_adaptive": (C.c_int, [_P, _P, _P]),

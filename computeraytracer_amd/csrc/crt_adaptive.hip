@@ -3,6 +3,8 @@
 //
 //   k_as_select    one wave per tile: each lane the error e of its pixel (the f32 contract below), the wave the tile's
 //                  error E = max e (NaN -> +inf, so the maximum does not depend on order); writes E and the active flag
+//   k_as_select_var  the same shape for crt_trace_adaptive_filtered: each lane the variance v' that the
+//                  adaptive filter left for its pixel, the wave E' = sqrt(max v'); E' and the flag go where E and its go
 //   k_as_compact   one block: the active tiles into a list in ascending tile order (neighbouring tiles stay neighbouring
 //                  work), and its length -- the only number the host reads back
 //   k_as_commit    after the call's last resolve, in stream order: the active tiles' counts grow by the call's samples
@@ -40,6 +42,26 @@ __global__ __launch_bounds__(64) void k_as_select(const AsParams A)
         A.errors[tile] = E;
         const bool below_max = A.max_samples == 0u || n_t < A.max_samples;
         A.flags[tile] = (below_max && (n_t < A.min_samples || !(E <= A.threshold))) ? 1u : 0u;
+    }
+}
+
+// v' >= +0 wherever it is a number, so 0 is neutral here too; the square root is taken once, of the maximum.
+__global__ __launch_bounds__(64) void k_as_select_var(const AsVarParams V)
+{
+    const uint32_t tile = blockIdx.x, lane = threadIdx.x;
+    const uint32_t lx = (tile % V.tiles_x) * 8u + (lane & 7u), ly = (tile / V.tiles_x) * 8u + (lane >> 3);
+    const uint32_t n_t = V.counts[tile];
+    float v = 0.0f;
+    if (lx < V.tw && ly < V.th && n_t >= 2u) {
+        v = V.var[(size_t)ly * V.tw + lx];
+        if (v != v) v = kInf;
+    }
+    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+    if (lane == 0) {
+        const float E = n_t < 2u ? kInf : sqrt_(v);
+        V.errors[tile] = E;
+        const bool below_max = V.max_samples == 0u || n_t < V.max_samples;
+        V.flags[tile] = (below_max && (n_t < V.min_samples || !(E <= V.threshold))) ? 1u : 0u;
     }
 }
 
@@ -83,6 +105,16 @@ hipError_t as_launch_select(const AsParams &A, bool compact, hipStream_t s)
     if (ntiles == 0) return hipSuccess;
     hipLaunchKernelGGL(k_as_select, dim3(ntiles), dim3(64), 0, s, A);
     if (compact) hipLaunchKernelGGL(k_as_compact, dim3(1), dim3(1024), 0, s, A);
+    return hipGetLastError();
+}
+
+// The same from the filter's variance plane (E' of DESIGN.md 6k); compact: null, or what k_as_compact takes.
+hipError_t as_launch_select_var(const AsVarParams &V, const AsParams *compact, hipStream_t s)
+{
+    const uint32_t ntiles = V.tiles_x * V.tiles_y;
+    if (ntiles == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_as_select_var, dim3(ntiles), dim3(64), 0, s, V);
+    if (compact) hipLaunchKernelGGL(k_as_compact, dim3(1), dim3(1024), 0, s, *compact);
     return hipGetLastError();
 }
 

@@ -421,46 +421,69 @@ int crt_adaptive_defaults(crt_adaptive_params *out)
     return CRT_OK;
 }
 
-int crt_trace_adaptive(crt_ctx *c, const crt_adaptive_params *params, uint32_t *active_tiles)
+// E' of every tile from the variance plane the adaptive filter left, in E's place.
+static AsVarParams as_var_params(crt_ctx *c, const crt_adaptive_params &p, const float *var)
+{
+    const AsParams A = as_params(c, p);
+    return AsVarParams{var, A.counts, A.errors, A.flags, A.tw, A.th, A.tiles_x, A.tiles_y, A.min_samples, A.max_samples, A.threshold};
+}
+
+// crt_trace_adaptive and crt_trace_adaptive_filtered (`filter` set; `what` names the call): they differ in the selection.
+static int as_trace(crt_ctx *c, const char *what, const crt_adaptive_params *params, const crt_denoise_adaptive_params *filter,
+                    bool filtered, uint32_t *active_tiles)
 {
     if (!c) return CRT_EINVAL;
     const crt_adaptive_params p = params ? *params : kAsDefaults;
-    if (p.samples == 0) return fail(c, CRT_EINVAL, "crt_trace_adaptive: samples must be >= 1");
-    if (!(p.threshold >= 0.0f && p.threshold <= FLT_MAX)) return fail(c, CRT_EINVAL, "crt_trace_adaptive: threshold must be finite and >= 0");
+    if (p.samples == 0) return fail(c, CRT_EINVAL, "%s: samples must be >= 1", what);
+    if (!(p.threshold >= 0.0f && p.threshold <= FLT_MAX)) return fail(c, CRT_EINVAL, "%s: threshold must be finite and >= 0", what);
+    crt_denoise_adaptive_params dp{};
+    if (filtered) CRT_TRY(dn_adaptive_params(c, what, filter, &dp));
     if (p.max_samples != 0 && p.max_samples < p.min_samples)
-        return fail(c, CRT_EINVAL, "crt_trace_adaptive: max_samples %u < min_samples %u", p.max_samples, p.min_samples);
+        return fail(c, CRT_EINVAL, "%s: max_samples %u < min_samples %u", what, p.max_samples, p.min_samples);
     if (!c->have_scene) return fail(c, CRT_ESTATE, "crt_trace: upload a scene first");
     if (c->accel_mode < 0) return fail(c, CRT_ESTATE, "crt_trace: call crt_build_accel first");
     if (c->accel_stale) return fail(c, CRT_ESTATE, "crt_trace: primitives were updated: call crt_refit_accel or crt_build_accel first");
     // (a band partition of a multiple of 8 rows: every local 8x8 tile is one of the frame's)
     if (crt_internal_comm_partitioned(c) == 1)
-        return fail(c, CRT_ESTATE, "crt_trace_adaptive: not under this crt_comm_partition: its 8x8 tiles are not the frame's "
-                                   "(a band partition with band_rows a multiple of 8 is what works)");
-    if (c->as_broken) return as_refuse_broken(c, "crt_trace_adaptive");
+        return fail(c, CRT_ESTATE, "%s: not under this crt_comm_partition: its 8x8 tiles are not the frame's "
+                                   "(a band partition with band_rows a multiple of 8 is what works)", what);
+    if (c->as_broken) return as_refuse_broken(c, what);
+    if (filtered) CRT_TRY(dn_check_state(c, what, true));         // (where crt_denoise_adaptive refuses: row bands)
     if (c->sample_offset && !c->adaptive_temporal)
-        return fail(c, CRT_ESTATE, "crt_trace_adaptive: not with a sample offset (%u): crt_set_sample_offset(ctx, 0) first "
-                                   "(or option \"adaptive_temporal\" = 1)", c->sample_offset);
+        return fail(c, CRT_ESTATE, "%s: not with a sample offset (%u): crt_set_sample_offset(ctx, 0) first "
+                                   "(or option \"adaptive_temporal\" = 1)", what, c->sample_offset);
     if (!c->as_on && c->sample > 0)
-        return fail(c, CRT_ESTATE, "crt_trace_adaptive: the context holds %u uniform samples whose second moment was not kept: crt_reset first", c->sample);
+        return fail(c, CRT_ESTATE, "%s: the context holds %u uniform samples whose second moment was not kept: crt_reset first", what, c->sample);
     // (no tile holds more than the calls of this adaptive state have asked for: what bounds every tile's last index)
     const unsigned long long requested = c->as_on ? c->as_requested : 0ull;
     if (c->sample_offset) {
         if (!(c->pipeline == 1 && c->accel_mode == CRT_ACCEL_BVH2))
-            return fail(c, CRT_ESTATE, "crt_trace_adaptive: a sample offset needs the wavefront pipeline (\"pipeline\" = 1 and a tree): "
-                                       "crt_set_sample_offset(ctx, 0) first");
+            return fail(c, CRT_ESTATE, "%s: a sample offset needs the wavefront pipeline (\"pipeline\" = 1 and a tree): "
+                                       "crt_set_sample_offset(ctx, 0) first", what);
         if ((unsigned long long)c->sample_offset + requested + p.samples > 0xFFFFFFFFull)
-            return fail(c, CRT_EINVAL, "crt_trace_adaptive: sample offset %u + %llu samples requested so far + %u pass 2^32 - 1",
-                        c->sample_offset, requested, p.samples);
+            return fail(c, CRT_EINVAL, "%s: sample offset %u + %llu samples requested so far + %u pass 2^32 - 1",
+                        what, c->sample_offset, requested, p.samples);
     }
     HIPCHK(c, hipSetDevice(c->device));
     if ((size_t)c->tw * c->th != 0 && (!accum_ptr(c) || !rgba_ptr(c)))
-        return fail(c, CRT_ENOMEM, "crt_trace_adaptive: the tile's output buffers are not allocated (an earlier crt_set_tile / crt_set_row_bands failed)");
+        return fail(c, CRT_ENOMEM, "%s: the tile's output buffers are not allocated (an earlier crt_set_tile / crt_set_row_bands failed)", what);
     CRT_TRY(wf_flush(c));                 // (the selection reads the accumulator)
-    if (!c->as_on) CRT_TRY(as_begin(c));
+    const bool entering = !c->as_on;
+    if (entering) CRT_TRY(as_begin(c));
     const uint32_t tiles_x = (c->tw + 7) / 8, tiles_y = (c->th + 7) / 8;
     uint32_t n_active = 0;
     if (tiles_x * tiles_y) {
-        HIPCHK(c, as_launch_select(as_params(c, p), true, c->stream));
+        if (filtered && !entering) {
+            // the filter's own launches, then E' from the variance they leave; every allocation comes before the first launch
+            float4 *res = nullptr;
+            const float *var = nullptr;
+            CRT_TRY(dn_adaptive_run(c, dp, false, true, &res, &var));
+            const AsParams A = as_params(c, p);
+            HIPCHK(c, as_launch_select_var(as_var_params(c, p, var), &A, c->stream));
+        } else {
+            // (entering the state every count is 0 and every tile active under either rule: no filter, no G-buffer)
+            HIPCHK(c, as_launch_select(as_params(c, p), true, c->stream));
+        }
         HIPCHK(c, hipMemcpyAsync(&n_active, c->as_n.p, sizeof n_active, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         CRT_TRY(wf_check_dropped(c));
@@ -501,6 +524,17 @@ int crt_trace_adaptive(crt_ctx *c, const crt_adaptive_params *params, uint32_t *
     return CRT_OK;
 }
 
+int crt_trace_adaptive(crt_ctx *c, const crt_adaptive_params *params, uint32_t *active_tiles)
+{
+    return as_trace(c, "crt_trace_adaptive", params, nullptr, false, active_tiles);
+}
+
+int crt_trace_adaptive_filtered(crt_ctx *c, const crt_adaptive_params *params, const crt_denoise_adaptive_params *filter,
+                                uint32_t *active_tiles)
+{
+    return as_trace(c, "crt_trace_adaptive_filtered", params, filter, true, active_tiles);
+}
+
 int crt_read_adaptive(crt_ctx *c, uint32_t *counts, float *errors)
 {
     if (!c) return CRT_EINVAL;
@@ -511,6 +545,30 @@ int crt_read_adaptive(crt_ctx *c, uint32_t *counts, float *errors)
     if (ntiles) {
         // (the selection's thresholds do not enter E: any will do; the active list is left alone)
         HIPCHK(c, as_launch_select(as_params(c, crt_adaptive_params{1u, 0u, 0u, 0.0f}), false, c->stream));
+        if (counts) HIPCHK(c, hipMemcpyAsync(counts, c->as_counts.p, ntiles * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        if (errors) HIPCHK(c, hipMemcpyAsync(errors, c->as_errors.p, ntiles * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return wf_check_dropped(c);
+}
+
+int crt_read_adaptive_filtered(crt_ctx *c, const crt_denoise_adaptive_params *filter, uint32_t *counts, float *errors)
+{
+    if (!c) return CRT_EINVAL;
+    const char *what = "crt_read_adaptive_filtered";
+    crt_denoise_adaptive_params dp{};
+    CRT_TRY(dn_adaptive_params(c, what, filter, &dp));
+    if (!c->as_on) return fail(c, CRT_ESTATE, "%s: the context is in the uniform state (crt_trace_adaptive_filtered first)", what);
+    if (c->as_broken) return as_refuse_broken(c, what);
+    CRT_TRY(dn_check_state(c, what, true));
+    CRT_TRY(quiesce(c, false));
+    const size_t ntiles = (size_t)((c->tw + 7) / 8) * ((c->th + 7) / 8);
+    if (ntiles) {
+        float4 *res = nullptr;
+        const float *var = nullptr;
+        CRT_TRY(dn_adaptive_run(c, dp, false, true, &res, &var));
+        // (as in crt_read_adaptive the thresholds do not enter E', and the active list is left alone)
+        HIPCHK(c, as_launch_select_var(as_var_params(c, crt_adaptive_params{1u, 0u, 0u, 0.0f}, var), nullptr, c->stream));
         if (counts) HIPCHK(c, hipMemcpyAsync(counts, c->as_counts.p, ntiles * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
         if (errors) HIPCHK(c, hipMemcpyAsync(errors, c->as_errors.p, ntiles * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     }

@@ -391,6 +391,13 @@ enum DnState { DN_UNIFORM, DN_ADAPTIVE, DN_EITHER, DN_TEMPORAL };
 int dn_begin(crt_ctx *c, const char *what, uint32_t iterations, const float *values, int count, const char *which, DnState state);
 int dn_finish(crt_ctx *c, size_t n, const float4 *res, float *rgb_out, uint8_t *rgba8_out, const float *plane = nullptr,
               float *plane_out = nullptr);
+// The adaptive filter for its two callers, crt_denoise_adaptive and the selection of crt_trace_adaptive_filtered (DESIGN.md
+// 6k): its parameters checked (NULL = the defaults), the filters' refusals that do not depend on the frame state (row bands,
+// ...; adaptive: the counts are per tile), and the filter itself on the context's stream with everything in flight finished;
+// *var_dev = the plane of v' (with `var`).
+int dn_adaptive_params(crt_ctx *c, const char *what, const crt_denoise_adaptive_params *params, crt_denoise_adaptive_params *out);
+int dn_check_state(crt_ctx *c, const char *what, bool adaptive = false);
+int dn_adaptive_run(crt_ctx *c, const crt_denoise_adaptive_params &dp, bool rgba, bool var, float4 **res, const float **var_dev);
 
 // crt_wf_driver.cpp
 struct AsBatch {                    // one batch of a crt_trace_adaptive call: its samples off + 1 .. off + n of every active tile

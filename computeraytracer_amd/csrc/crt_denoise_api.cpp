@@ -6,7 +6,7 @@ using namespace crt;
 
 namespace crt {
 
-static int dn_check_state(crt_ctx *c, const char *what, bool adaptive = false)   // adaptive: the counts are per tile, >= 1
+int dn_check_state(crt_ctx *c, const char *what, bool adaptive)   // adaptive: the counts are per tile, >= 1
 {
     if (!c->have_scene || c->accel_mode < 0) return fail(c, CRT_ESTATE, "%s: scene + accel required", what);
     if (c->accel_stale) return fail(c, CRT_ESTATE, "%s: primitives were updated: call crt_refit_accel or crt_build_accel first", what);
@@ -127,23 +127,51 @@ int crt_denoise_adaptive_defaults(crt_denoise_adaptive_params *out)
     return CRT_OK;
 }
 
+}  // extern "C"
+
+namespace crt {
+
+// The filter parameters of a call that takes them (NULL = the defaults), checked as crt_denoise_adaptive checks them.
+int dn_adaptive_params(crt_ctx *c, const char *what, const crt_denoise_adaptive_params *params, crt_denoise_adaptive_params *out)
+{
+    *out = params ? *params : kDnAsDefaults;
+    const float sig[3] = {out->sigma_variance, out->sigma_normal, out->sigma_plane};
+    return dn_check_params(c, what, out->iterations, sig, 3, "every sigma");
+}
+
+// The adaptive filter of the context's tile on its stream, everything in flight already finished: what crt_denoise_adaptive
+// and the selection of crt_trace_adaptive_filtered (crt_api.cpp) both run.  Every allocation comes before
+// the first launch.  *res: the buffer that holds the colours; with `var`, *var_dev: the plane of v'.
+int dn_adaptive_run(crt_ctx *c, const crt_denoise_adaptive_params &dp, bool rgba, bool var, float4 **res, const float **var_dev)
+{
+    const size_t n = (size_t)c->tw * c->th;
+    *res = nullptr;
+    if (var_dev) *var_dev = nullptr;
+    if (!n) return CRT_OK;
+    CRT_TRY(dn_ensure_buffers(c, n));
+    CRT_ENSURE(c, c->dn.kv, n);
+    CRT_ENSURE(c, c->dn.var, n);
+    CRT_TRY(dn_ensure_gbuffer(c));
+    const DnFilter F = dn_filter(c, dp.iterations, dp.sigma_normal, dp.sigma_plane, rgba);
+    HIPCHK(c, dn_launch_filter_adaptive(F, accum_ptr(c), c->as_q.p, c->as_counts.p, c->dn.kv.p, var ? c->dn.var.p : nullptr,
+                                        dp.sigma_variance, res));
+    if (var_dev) *var_dev = c->dn.var.p;
+    return CRT_OK;
+}
+
+}  // namespace crt
+
+extern "C" {
+
 int crt_denoise_adaptive(crt_ctx *c, const crt_denoise_adaptive_params *params, float *rgb_out, uint8_t *rgba8_out, float *var_out)
 {
-    const crt_denoise_adaptive_params dp = params ? *params : kDnAsDefaults;
-    const float sig[3] = {dp.sigma_variance, dp.sigma_normal, dp.sigma_plane};
-    CRT_TRY(dn_begin(c, "crt_denoise_adaptive", dp.iterations, sig, 3, "every sigma", DN_ADAPTIVE));
-    const size_t n = (size_t)c->tw * c->th;
+    if (!c) return CRT_EINVAL;
+    crt_denoise_adaptive_params dp;
+    CRT_TRY(dn_adaptive_params(c, "crt_denoise_adaptive", params, &dp));
+    CRT_TRY(dn_begin(c, "crt_denoise_adaptive", 0, nullptr, 0, "", DN_ADAPTIVE));
     float4 *res = nullptr;
-    if (n) {
-        CRT_TRY(dn_ensure_gbuffer(c));
-        CRT_TRY(dn_ensure_buffers(c, n));
-        CRT_ENSURE(c, c->dn.kv, n);
-        CRT_ENSURE(c, c->dn.var, n);
-        const DnFilter F = dn_filter(c, dp.iterations, dp.sigma_normal, dp.sigma_plane, rgba8_out != nullptr);
-        HIPCHK(c, dn_launch_filter_adaptive(F, accum_ptr(c), c->as_q.p, c->as_counts.p, c->dn.kv.p, var_out ? c->dn.var.p : nullptr,
-                                            dp.sigma_variance, &res));
-    }
-    return dn_finish(c, n, res, rgb_out, rgba8_out, c->dn.var.p, var_out);
+    CRT_TRY(dn_adaptive_run(c, dp, rgba8_out != nullptr, var_out != nullptr, &res, nullptr));
+    return dn_finish(c, (size_t)c->tw * c->th, res, rgb_out, rgba8_out, c->dn.var.p, var_out);
 }
 
 // ---------------------------------------------------------------- temporal reuse

@@ -89,6 +89,17 @@ struct AsParams {
     float threshold;
 };
 
+// ... of crt_trace_adaptive_filtered: the tile's error from the variance the adaptive filter carried.
+struct AsVarParams {
+    const float *var;               // per tile pixel: v' after the filter's last pass (crt_denoise_adaptive's var_out)
+    const uint32_t *counts;         // per tile: samples it holds
+    float *errors;                  // per tile: E' = sqrt(max v')
+    uint32_t *flags;                // per tile: 1 = active
+    uint32_t tw, th, tiles_x, tiles_y;
+    uint32_t min_samples, max_samples;
+    float threshold;
+};
+
 
 // ---------------------------------------------------------------------------------------------
 // Wavefront pipeline state (crt_wavefront.hip).  A pool of P path slots lives in HBM (SoA,

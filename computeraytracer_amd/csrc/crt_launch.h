@@ -35,6 +35,7 @@ hipError_t wf_launch_resolve_adaptive(const WfParams &P, const AsTiles &A, uint3
 
 // crt_adaptive.hip
 hipError_t as_launch_select(const AsParams &A, bool compact, hipStream_t s);
+hipError_t as_launch_select_var(const AsVarParams &V, const AsParams *compact, hipStream_t s);
 hipError_t as_launch_commit(uint32_t *counts, const uint32_t *active, uint32_t n_active, uint32_t samples, hipStream_t s);
 
 // crt_lbvh.hip

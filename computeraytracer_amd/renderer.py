@@ -217,15 +217,56 @@ class Renderer:
         """`samples` more samples for every 8x8 tile that is still active (asynchronous); returns how many tiles that
         was -- 0 when every tile has converged or reached max_samples (0 = no limit).  The first call needs sample 0.
         A parameter left out takes the library's default (crt_adaptive_defaults)."""
+        n = C.c_uint32()
+        self._chk(self._lib.crt_trace_adaptive(self._h, C.byref(self._adaptive_params(samples, threshold, min_samples, max_samples)),
+                                               C.byref(n)))
+        return int(n.value)
+
+    @staticmethod
+    def _adaptive_params(samples, threshold, min_samples, max_samples):
         p = _lib.adaptive_defaults()
         for k, v in (("samples", samples), ("min_samples", min_samples), ("max_samples", max_samples)):
             if v is not None:
                 setattr(p, k, int(v))
         if threshold is not None:
             p.threshold = float(threshold)
+        return p
+
+    @staticmethod
+    def _filter_params(iterations, sigma_variance, sigma_normal, sigma_plane):
+        d = _lib.denoise_adaptive_defaults()
+        if iterations is not None:
+            d.iterations = int(iterations)
+        for k, v in (("sigma_variance", sigma_variance), ("sigma_normal", sigma_normal), ("sigma_plane", sigma_plane)):
+            if v is not None:
+                setattr(d, k, float(v))
+        return d
+
+    def trace_adaptive_filtered(self, samples: int | None = None, threshold: float | None = None, min_samples: int | None = None,
+                                max_samples: int | None = None, iterations: int | None = None,
+                                sigma_variance: float | None = None, sigma_normal: float | None = None,
+                                sigma_plane: float | None = None) -> int:
+        """trace_adaptive with the tiles judged by what denoise_adaptive(iterations, sigma_variance, sigma_normal,
+        sigma_plane) leaves of their noise (include/crt.h "Adaptive sampling judged by the filtered preview"): E' =
+        sqrt(max of the filter's var over the tile) in E's place.  Returns the tiles it sampled.  A parameter left out
+        takes the library's default (crt_adaptive_defaults, crt_denoise_adaptive_defaults)."""
         n = C.c_uint32()
-        self._chk(self._lib.crt_trace_adaptive(self._h, C.byref(p), C.byref(n)))
+        p = self._adaptive_params(samples, threshold, min_samples, max_samples)
+        d = self._filter_params(iterations, sigma_variance, sigma_normal, sigma_plane)
+        self._chk(self._lib.crt_trace_adaptive_filtered(self._h, C.byref(p), C.byref(d), C.byref(n)))
         return int(n.value)
+
+    def read_adaptive_filtered(self, iterations: int | None = None, sigma_variance: float | None = None,
+                               sigma_normal: float | None = None, sigma_plane: float | None = None):
+        """read_adaptive with errors = E' as the next trace_adaptive_filtered with this filter judges it; the same
+        shapes.  Reads only; finishes what is in flight."""
+        _, _, tw, th = self.tile
+        tx, ty = (tw + 7) // 8, (th + 7) // 8
+        counts = np.zeros((ty, tx), np.uint32)
+        errors = np.zeros((ty, tx), np.float32)
+        d = self._filter_params(iterations, sigma_variance, sigma_normal, sigma_plane)
+        self._chk(self._lib.crt_read_adaptive_filtered(self._h, C.byref(d), counts.ctypes.data, errors.ctypes.data))
+        return counts, errors
 
     def read_adaptive(self):
         """(counts (tiles_y, tiles_x) uint32, errors (tiles_y, tiles_x) float32): the samples each tile holds and its

@@ -90,6 +90,11 @@ function Main(options = {}) {
     // returns how many tiles that was (0: done).  readAdaptive: {counts, errors, tilesX, tilesY}
     traceAdaptive: (opts = {}) => a.traceAdaptive(device, opts),
     readAdaptive: () => a.readAdaptive(device),
+    // ... judged by the noise denoiseAdaptive leaves instead of the raw pixel error (include/crt.h "Adaptive sampling
+    // judged by the filtered preview"): opts = traceAdaptive's plus the filter's {iterations, sigmaVariance, sigmaNormal,
+    // sigmaPlane}; readAdaptiveFiltered(the filter's options): readAdaptive's object with that error
+    traceAdaptiveFiltered: (opts = {}) => a.traceAdaptiveFiltered(device, opts),
+    readAdaptiveFiltered: (opts = {}) => a.readAdaptiveFiltered(device, opts),
     // the variance-guided preview filter of an adaptive render (include/crt.h "Denoised preview of an adaptive render"):
     // rgba8 of the tile, or {rgba8, variance} with opts.variance; reads only.  The Promise form resolves to the rgba8.
     denoiseAdaptive: (opts = {}) => a.denoiseAdaptive(device, opts),

@@ -459,6 +459,40 @@ int crt_denoise_adaptive_defaults(crt_denoise_adaptive_params *out);
 int crt_denoise_adaptive(crt_ctx *ctx, const crt_denoise_adaptive_params *params, float *rgb_out, uint8_t *rgba8_out,
                          float *var_out);
 
+/* ------------------------------------------------------------------ Adaptive sampling judged by the filtered preview
+ * crt_trace_adaptive_filtered is crt_trace_adaptive with the tile's error taken from what crt_denoise_adaptive leaves
+ * (DESIGN.md 6k): an adaptive render that is shown through that filter keeps sampling only where the FILTERED image is
+ * still noisy.  For filter parameters D (NULL = crt_denoise_adaptive_defaults) and tile t holding n_t samples:
+ *   v'_p  is, bit for bit, what crt_denoise_adaptive(ctx, D, ..., var_out) returns for pixel p in the same state;
+ *   E'_t  = sqrt(max over the tile's in-frame pixels of v'_p): a NaN counts as +inf, the square root is one IEEE
+ *           operation taken once, of the maximum; E'_t = +inf where n_t < 2;
+ *   ACTIVE iff (max_samples == 0 || n_t < max_samples) && (n_t < min_samples || !(E'_t <= threshold)).
+ * E' is in the display units of E, so `threshold` keeps its meaning and crt_adaptive_defaults stays the NULL default;
+ * the filter averages noise away, so E' <= about E and a given threshold stops earlier.  min_samples matters more than
+ * under crt_trace_adaptive: below about 8 samples per pixel the variance estimate that guides the filter is itself too
+ * noisy (see crt_denoise_adaptive), and a tile that stops there stops on an unreliable E'.
+ * E' of a tile depends on its neighbours through the filter, so a tile that was at rest may become active again.
+ * What it buys (DESIGN.md 6k has the numbers): on the Cornell box, large smooth surfaces, the filtered preview has
+ * 0.75 times the error of crt_trace_adaptive's at the same 30 samples per pixel.  On S2 (atrium250k, small triangles
+ * everywhere) it buys NOTHING: both rules lie on one error-against-samples curve within 5 %, the new one needs more
+ * rounds, and its selection costs 1.14 ms a call at 1920x1080 against 0.05 ms (the filter's K = 5 launches; under 2 % of
+ * a 64-sample round).  crt_trace_adaptive stays the rule to start from.
+ * State machine, batches, commit, the failed-part-way state and the "adaptive_temporal" / sample-offset rules are
+ * crt_trace_adaptive's; the two calls may be mixed within one adaptive state.  The call that enters the adaptive state
+ * runs no filter (every tile is active); every later one enqueues the filter's launches on the context's stream before
+ * the selection and reads back the same 4 bytes.  It only READS the denoise state: the temporal history stays untouched.
+ * A crt_set_tile rectangle is filtered and selected on its own.
+ * Beyond crt_trace_adaptive's refusals: CRT_ESTATE where crt_denoise_adaptive refuses, namely under row bands and hence
+ * under every crt_comm_partition; CRT_EINVAL for filter parameters crt_denoise_adaptive rejects; CRT_ENOMEM when a filter
+ * buffer cannot be allocated.  In all three cases nothing is enqueued and the context, counts and accumulator stay as
+ * they were. */
+int crt_trace_adaptive_filtered(crt_ctx *ctx, const crt_adaptive_params *params, const crt_denoise_adaptive_params *filter,
+                                uint32_t *active_tiles);
+/* crt_read_adaptive with errors = E' as the NEXT crt_trace_adaptive_filtered with this filter will judge it (counts are
+ * crt_read_adaptive's; crt_read_adaptive keeps returning E).  A sync point that only reads.  CRT_ESTATE in the uniform
+ * state, after a call that failed part way, and where the filter refuses; CRT_EINVAL for the filter's parameters. */
+int crt_read_adaptive_filtered(crt_ctx *ctx, const crt_denoise_adaptive_params *filter, uint32_t *counts, float *errors);
+
 /* ------------------------------------------------------------------ The frame of a partition: adaptive sampling and previews
  * Across a partition the three families work together:
  *
