@@ -68,6 +68,7 @@ SIGNATURES = {
     "crt_read_motion": (C.c_int, [_P, _P]),
     "crt_debug_intersect": (C.c_int, [_P, _P, C.c_size_t, _P]),
     "crt_debug_trace_rays": (C.c_int, [_P, _P, C.c_size_t, _P, _P]),
+    "crt_debug_walk_rays": (C.c_int, [_P, C.c_int, _P, C.c_size_t, _P, _P]),
     "crt_debug_read_accel": (C.c_int, [_P, C.c_int, _P, C.c_size_t, _P]),
     "crt_debug_probes": (C.c_int, [_P, _P]),
     "crt_debug_gen_culled": (C.c_int, [_P, _P]),

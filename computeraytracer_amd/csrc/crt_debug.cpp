@@ -141,6 +141,52 @@ int crt_debug_trace_rays(crt_ctx *c, const float *rays, size_t n, uint32_t *out,
     return CRT_OK;
 }
 
+// Caller-chosen rays through the single-ray walks (k_debug_walk_rays: the call patterns of crt_shade.h that k_wf_finish
+// and k_trace use), one lane per ray.  The buffers are the call's own.
+int crt_debug_walk_rays(crt_ctx *c, int walk, const float *rays, size_t n, uint32_t *out, uint64_t report[8])
+{
+    if (!c || (!rays && n) || (!out && n)) return CRT_EINVAL;
+    if (!c->have_scene || c->accel_mode < 0) return fail(c, CRT_ESTATE, "crt_debug_walk_rays: scene + accel required");
+    if (c->accel_stale) return fail(c, CRT_ESTATE, "crt_debug_walk_rays: primitives were updated: call crt_refit_accel or crt_build_accel first");
+    if (c->accel_mode != CRT_ACCEL_BVH2) return fail(c, CRT_ESTATE, "crt_debug_walk_rays: no tree (CRT_ACCEL_NONE)");
+    if (walk != 0 && walk != 1) return fail(c, CRT_EINVAL, "crt_debug_walk_rays: walk must be 0 (as k_wf_finish) or 1 (as the pipeline = 0 kernel)");
+    const uint32_t nprim = (uint32_t)c->prims.size();
+    for (size_t i = 0; i < n; i++) {
+        const float *r = rays + 12 * i;
+        uint32_t u[4];
+        std::memcpy(u, r + 6, 16);                               // exclude, kind, t_light, light index
+        for (int k = 0; k < 6; k++)
+            if (!std::isfinite(r[k])) return fail(c, CRT_EINVAL, "crt_debug_walk_rays: ray %zu is not finite (crt_trace resolves such rays without a walk)", i);
+        if (u[1] > 1u) return fail(c, CRT_EINVAL, "crt_debug_walk_rays: ray %zu: kind must be 0 (extension) or 1 (shadow)", i);
+        if (u[1] == 1u && (!std::isfinite(r[8]) || u[3] >= nprim))
+            return fail(c, CRT_EINVAL, "crt_debug_walk_rays: shadow ray %zu: t_light must be finite and the light index below %u", i, nprim);
+    }
+    CRT_TRY(quiesce(c, true));
+    const bool wide = c->sc.nodes4q != nullptr && c->sc.nodes8q == nullptr;     // finish_walks_wide (crt_shade.h)
+    if (report) {
+        report[0] = report[1] = 0;                               // rays that walked the 4-wide tree / that fell back to the BVH2
+        report[2] = (uint64_t)kStackDepth;                       // stack entries per lane
+        report[3] = c->bvh4.max_depth;                           // inner levels of the 4-wide tree
+        report[4] = c->bvh.max_depth;                            // recorded depth of the BVH2
+        report[5] = wide ? 1 : 0;
+        report[6] = report[7] = 0;
+    }
+    if (n == 0) return CRT_OK;
+    DevBuf<float> din;
+    DevBuf<uint32_t> dout;
+    HIPCHK(c, din.alloc(n * 12)); HIPCHK(c, dout.alloc(n * 4));
+    HIPCHK(c, hipMemcpyAsync(din.p, rays, n * 12 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemsetAsync(dout.p, 0xEE, n * 4 * sizeof(uint32_t), c->stream));     // "never written"
+    HIPCHK(c, launch_debug_walk_rays(c->sc, walk, din.p, n, dout.p, c->stream));
+    HIPCHK(c, hipMemcpyAsync(out, dout.p, n * 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (size_t i = 0; i < n; i++) {
+        if (out[4 * i + 2] > (kWalk4q | kWalkFellBack)) return fail(c, CRT_EDEVICE, "crt_debug_walk_rays: ray %zu was not resolved (flags = 0x%08x)", i, out[4 * i + 2]);
+        if (report) { report[0] += out[4 * i + 2] & kWalk4q ? 1 : 0; report[1] += out[4 * i + 2] & kWalkFellBack ? 1 : 0; }
+    }
+    return CRT_OK;
+}
+
 // The current structure as it lies on the device, part by part (include/crt.h): device-to-host copies only.
 int crt_debug_read_accel(crt_ctx *c, int what, void *out, size_t capacity, size_t *bytes)
 {

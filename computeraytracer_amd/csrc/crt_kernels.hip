@@ -111,6 +111,8 @@ __global__ __launch_bounds__(64) void k_trace(const TraceParams P, const AsTiles
                 } else if (shadow_mode) {
                     // shadow_intersect (:697-705) == "is the light's own primitive the closest
                     // hit?"  Hit the light first, then ask the BVH for anything that beats it.
+                    // (RESTATED for the test hook k_debug_walk_rays as trace_walk_shadow below: a
+                    // change here is made there.)
                     uint32_t include = f_bits(S.lights[3 * s_light + 1].w);
                     if (include < S.nprim) {
                         hit_test<false>(S, S.slot_of_index[include], o, d, excl, 0.001f, t_max, b_index, b_slot);
@@ -286,6 +288,69 @@ __global__ void k_debug_intersect(const DevScene S, const float *rays, size_t n,
     r[7] = bits_f(b_slot != kNoHit ? b_index : kNoHit);
 }
 
+// The shadow walk of k_trace RESTATED (its `else if (shadow_mode)` branch above, which stays inline there: a change in
+// one is made in the other): the light's own primitive first (t_light = its t, CRT_INFINITY when the ray misses it),
+// then the BVH2 any-hit for anything that beats it.
+// Sets occluded, and light_seen where the light is the closest hit; (t_max, b_index, b_slot) are the light's hit then.
+template <bool COUNT>
+__device__ __forceinline__ void trace_walk_shadow(const DevScene &S, int *stk, f3 o, f3 d, uint32_t exclude, uint32_t include, float &t_max,
+                                                  uint32_t &b_index, uint32_t &b_slot, uint32_t &c_nodes, uint32_t &c_prims, bool &occluded,
+                                                  bool &light_seen, float &t_light)
+{
+    if (include < S.nprim) {
+        hit_test<false>(S, S.slot_of_index[include], o, d, exclude, 0.001f, t_max, b_index, b_slot);
+        if (COUNT) c_prims++;
+    }
+    t_light = t_max;
+    if (b_slot != kNoHit) {
+        const uint32_t l_slot = b_slot;
+        traverse<COUNT>(S, stk, o, d, exclude, true, t_max, b_index, b_slot, c_nodes, c_prims);
+        occluded = (b_slot != l_slot);
+        light_seen = !occluded;
+    } else {
+        occluded = true;
+    }
+}
+
+// crt_debug_walk_rays: one lane per ray through the single-ray walks as the product calls them (crt_shade.h) -- walk 0:
+// as k_wf_finish (finish_walk_extension / finish_walk_shadow), walk 1: as k_trace (traverse / trace_walk_shadow above) -- with
+// k_wf_finish's block and stack: 64 lanes, kStackDepth x 64 LDS entries, lane i on column i.  rays: n x 12 as
+// crt_debug_trace_rays takes them; out: n x 4 (include/crt.h).
+__global__ __launch_bounds__(64) void k_debug_walk_rays(const DevScene S, int walk, const float *rays, size_t n, uint32_t *out)
+{
+    __shared__ int lds_stack[kStackDepth * 64];
+    const size_t i = (size_t)blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    int *stk = lds_stack + threadIdx.x;
+    const float *r = rays + 12 * i;
+    const f3 o = f3{r[0], r[1], r[2]}, d = f3{r[3], r[4], r[5]};
+    const uint32_t excl = f_bits(r[6]), shadow = f_bits(r[7]), light = f_bits(r[9]);
+    const bool wide = finish_walks_wide(S);
+    uint32_t cn = 0, cp = 0, how = 0, w0, w1, w3 = 0;
+    if (shadow) {
+        if (walk == 0) {
+            w0 = finish_walk_shadow<false>(S, stk, wide, o, d, excl, r[8], light, cn, cp, how) ? 1u : 0u;
+        } else {
+            float t_max = CRT_INFINITY, t_light;
+            uint32_t b_index = kNoHit, b_slot = kNoHit;
+            bool occluded = false, light_seen = false;
+            trace_walk_shadow<false>(S, stk, o, d, excl, light, t_max, b_index, b_slot, cn, cp, occluded, light_seen, t_light);
+            w0 = light_seen ? 1u : 0u;
+            w3 = f_bits(t_light);
+        }
+        w1 = 0u;
+    } else {
+        float t_max = CRT_INFINITY;
+        uint32_t b_index = kNoHit, b_slot = kNoHit;
+        if (walk == 0) finish_walk_extension<false>(S, stk, wide, o, d, excl, t_max, b_index, b_slot, cn, cp, how);
+        else traverse<false>(S, stk, o, d, excl, false, t_max, b_index, b_slot, cn, cp);       // (k_trace's extension walk)
+        w0 = f_bits(t_max);
+        w1 = b_slot != kNoHit ? b_index : kNoHit;
+    }
+    uint32_t *w = out + 4 * i;
+    w[0] = w0; w[1] = w1; w[2] = how; w[3] = w3;
+}
+
 __global__ void k_debug_math(int fn, const float *a, const float *b, float *out, size_t n)
 {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -341,6 +406,13 @@ hipError_t launch_debug_intersect(const DevScene &S, const float *rays, size_t n
 {
     if (n == 0) return hipSuccess;
     hipLaunchKernelGGL(k_debug_intersect, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, stream, S, rays, n, out, brute);
+    return hipGetLastError();
+}
+
+hipError_t launch_debug_walk_rays(const DevScene &S, int walk, const float *rays, size_t n, uint32_t *out, hipStream_t stream)
+{
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_debug_walk_rays, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, stream, S, walk, rays, n, out);
     return hipGetLastError();
 }
 

@@ -16,6 +16,7 @@ namespace crt {
 hipError_t launch_trace(const TraceParams &P, bool count, bool brute, hipStream_t stream);
 hipError_t launch_trace_adaptive(const TraceParams &P, const AsTiles &A, bool count, bool brute, hipStream_t stream);
 hipError_t launch_debug_intersect(const DevScene &S, const float *rays, size_t n, float *out, int brute, hipStream_t stream);
+hipError_t launch_debug_walk_rays(const DevScene &S, int walk, const float *rays, size_t n, uint32_t *out, hipStream_t stream);
 hipError_t launch_debug_math(int fn, const float *a, const float *b, float *out, size_t n, hipStream_t stream);
 hipError_t launch_assemble(const void *full, void *frame, uint32_t elem_bytes, uint32_t W, uint32_t H, uint32_t world, uint32_t rows_max,
                            uint32_t band, hipStream_t stream);

@@ -324,6 +324,44 @@ __device__ __forceinline__ bool traverse4q(const DevScene &S, int *stk, f3 o, f3
     }
 }
 
+// ---------------------------------------------------------------- the single-ray walks as the kernels call them
+// Each call pattern of k_wf_finish (crt_wavefront.hip) once: it and the test hook k_debug_walk_rays (crt_kernels.hip) call
+// these, so the hook walks what the product walks.  (k_trace keeps its shadow walk inline -- as a function it compiled
+// to other registers; trace_walk_shadow in crt_kernels.hip restates it for the hook.)  `how` reports which walk ran
+// (kWalk4q: traverse4q was entered, kWalkFellBack: it gave up on its stack and traverse() repeated the ray); a caller
+// that drops it pays nothing for it.
+
+// k_wf_finish walks the quantised 4-wide tree when there is one and no 8-wide tree.
+__device__ __forceinline__ bool finish_walks_wide(const DevScene &S) { return S.nodes4q != nullptr && S.nodes8q == nullptr; }
+
+// The extension walk of k_wf_finish: the closest hit from (t_max, b_index, b_slot) as primed by the caller.
+template <bool COUNT>
+__device__ __forceinline__ void finish_walk_extension(const DevScene &S, int *stk, bool wide, f3 o, f3 d, uint32_t exclude, float &t_max,
+                                                      uint32_t &b_index, uint32_t &b_slot, uint32_t &c_nodes, uint32_t &c_prims, uint32_t &how)
+{
+    bool fell_back = false;
+    if (!wide || (fell_back = !traverse4q<COUNT>(S, stk, o, d, exclude, false, t_max, b_index, b_slot, c_nodes, c_prims)))
+        traverse<COUNT>(S, stk, o, d, exclude, false, t_max, b_index, b_slot, c_nodes, c_prims);
+    how = (wide ? kWalk4q : 0u) | (fell_back ? kWalkFellBack : 0u);
+}
+
+// The shadow walk of k_wf_finish, primed with the light's own hit (its t along the ray, its primitive index): any-hit
+// for something that beats it.  True = the light is visible.
+template <bool COUNT>
+__device__ __forceinline__ bool finish_walk_shadow(const DevScene &S, int *stk, bool wide, f3 o, f3 d, uint32_t exclude, float t_light,
+                                                   uint32_t light, uint32_t &c_nodes, uint32_t &c_prims, uint32_t &how)
+{
+    float t_max = t_light;
+    uint32_t b_index = light;                                    // the light's primitive index
+    const uint32_t l_slot = S.slot_of_index[b_index];
+    uint32_t b_slot = l_slot;
+    bool fell_back = false;
+    if (!wide || (fell_back = !traverse4q<COUNT>(S, stk, o, d, exclude, true, t_max, b_index, b_slot, c_nodes, c_prims)))
+        traverse<COUNT>(S, stk, o, d, exclude, true, t_max, b_index, b_slot, c_nodes, c_prims);
+    how = (wide ? kWalk4q : 0u) | (fell_back ? kWalkFellBack : 0u);
+    return b_slot == l_slot;
+}
+
 // ---------------------------------------------------------------- shading helpers
 __device__ __forceinline__ f4 sample_spectrum(const DevScene &S, uint32_t index, const uint32_t l[4])
 {

@@ -1931,7 +1931,8 @@ __global__ __launch_bounds__(64, CRT_WF_T2_WAVES) void k_wf_trace2(const WfParam
 // exactly as in k_wf_shade's tail mode.
 // ------------------------------------------------------------------ stragglers
 // k_wf_finish: one lane per side-pool path, run to the path's end (shade step, then trace what it emits,
-// ...) with the single-ray BVH2 walk.  Runs on its own stream while the pool works on the next batch.
+// ...) with the single-ray walks as crt_shade.h states them (finish_walk_*).  Runs on its own stream while the pool
+// works on the next batch.
 template <bool COUNT>
 __global__ __launch_bounds__(64) void k_wf_finish(const WfParams P, const WfFinishSegs G)
 {
@@ -1955,7 +1956,7 @@ __global__ __launch_bounds__(64) void k_wf_finish(const WfParams P, const WfFini
     // The rays these paths listed in their last pool iteration were traced there: start with the shade
     // step; from then on this lane traces what its own shade steps emit.
     bool pend_sh = false, pend_ext = false;
-    const bool wide = S.nodes4q != nullptr && S.nodes8q == nullptr;     // walk the quantised 4-wide tree when there is one
+    const bool wide = finish_walks_wide(S);                             // walk the quantised 4-wide tree when there is one
     ShadeCnt cn;
     uint32_t c_nodes = 0, c_prims = 0;
     for (int guard = 0; guard < 512 && __ballot(alive) != 0ull; guard++) {
@@ -1965,21 +1966,15 @@ __global__ __launch_bounds__(64) void k_wf_finish(const WfParams P, const WfFini
             const uint32_t excl = f_bits(ro.w);
             if (pend_sh) {
                 const float4 sd = P.sh_d[slot];
-                float t_max = sd.w;
-                uint32_t b_index = P.vis[slot];                          // the light's primitive index
-                const uint32_t l_slot = S.slot_of_index[b_index];
-                uint32_t b_slot = l_slot;
-                if (!wide || !traverse4q<COUNT>(S, stk, o, xyz(sd), excl, true, t_max, b_index, b_slot, c_nodes, c_prims))
-                    traverse<COUNT>(S, stk, o, xyz(sd), excl, true, t_max, b_index, b_slot, c_nodes, c_prims);
-                P.vis[slot] = (b_slot == l_slot) ? 1u : 0u;
+                uint32_t how;                                            // (P.vis holds the light's primitive index)
+                P.vis[slot] = finish_walk_shadow<COUNT>(S, stk, wide, o, xyz(sd), excl, sd.w, P.vis[slot], c_nodes, c_prims, how) ? 1u : 0u;
             }
             if (pend_ext) {
                 const float4 rd = P.ray_d[slot];
                 if (f_bits(rd.w) == 0u) {                                // (else: non-finite ray, resolved by the shade step)
                     float t_max = CRT_INFINITY;
-                    uint32_t b_index = kNoHit, b_slot = kNoHit;
-                    if (!wide || !traverse4q<COUNT>(S, stk, o, xyz(rd), excl, false, t_max, b_index, b_slot, c_nodes, c_prims))
-                        traverse<COUNT>(S, stk, o, xyz(rd), excl, false, t_max, b_index, b_slot, c_nodes, c_prims);
+                    uint32_t b_index = kNoHit, b_slot = kNoHit, how;
+                    finish_walk_extension<COUNT>(S, stk, wide, o, xyz(rd), excl, t_max, b_index, b_slot, c_nodes, c_prims, how);
                     P.hit[slot] = float2{t_max, bits_f(b_slot)};
                 }
             }

@@ -623,6 +623,36 @@ class Renderer:
         t = np.where(sh, np.uint32(0), out[:, 0]).astype(np.uint32).view(np.float32)
         return t, np.where(sh, np.uint32(0), out[:, 1]).astype(np.uint32), np.where(sh, out[:, 0], np.uint32(0)).astype(np.uint32), report
 
+    WALKS = {"finish": 0, "bvh2": 1}
+
+    def debug_walk_rays(self, origins, directions, exclude=None, shadow=None, t_light=None, light=None, walk="finish"):
+        """Rays through the single-ray walks (crt_debug_walk_rays): walk="finish" as k_wf_finish calls them (the quantised
+        4-wide tree where it is live, the BVH2 on overflow), walk="bvh2" as the pipeline = 0 kernel does (a shadow ray
+        tests its light's primitive itself).  Arguments as debug_trace_rays.  Returns (t, index, visible, flags uint32
+        (n,) -- bit 0: walked the 4-wide tree, bit 1: fell back --, t_light float32 (n,) -- what the kernel computed,
+        walk="bvh2" shadow rays only --, report dict)."""
+        o = np.asarray(origins, np.float32).reshape(-1, 3)
+        d = np.asarray(directions, np.float32).reshape(-1, 3)
+        n = o.shape[0]
+        rays = np.zeros((n, 12), np.float32)
+        rays[:, 0:3] = o
+        rays[:, 3:6] = d
+        ru = rays.view(np.uint32)
+        ru[:, 6] = 0xFFFFFFFF if exclude is None else np.asarray(exclude, np.uint32)
+        sh = np.zeros(n, bool) if shadow is None else np.asarray(shadow, bool)
+        if sh.any():
+            ru[:, 7] = sh
+            rays[sh, 8] = np.asarray(t_light, np.float32)[sh]
+            ru[sh, 9] = np.asarray(light, np.uint32)[sh]
+        out = np.zeros((n, 4), np.uint32)
+        rep = np.zeros(8, np.uint64)
+        self._chk(self._lib.crt_debug_walk_rays(self._h, self.WALKS[walk], rays.ctypes.data, n, out.ctypes.data, rep.ctypes.data))
+        report = dict(walked_wide=int(rep[0]), fell_back=int(rep[1]), stack_entries=int(rep[2]), depth4=int(rep[3]), depth2=int(rep[4]),
+                      wide=bool(rep[5]))
+        t = np.where(sh, np.uint32(0), out[:, 0]).astype(np.uint32).view(np.float32)
+        return (t, np.where(sh, np.uint32(0), out[:, 1]).astype(np.uint32), np.where(sh, out[:, 0], np.uint32(0)).astype(np.uint32),
+                out[:, 2].copy(), out[:, 3].copy().view(np.float32), report)
+
     ACCEL_HEADER = ("accel_mode", "builder", "nprim", "root", "root4", "root8", "n2", "n4", "n8", "live4", "live4q", "live8q",
                     "qbase_x", "qbase_y", "qbase_z", "qscale_x", "qscale_y", "qscale_z", "hit_pad", "tree_pad", "depth2", "depth4",
                     "depth8", "wf_depth", "wf_stack_need", "wf_stack_lds", "wf_overflow_levels", "overflow_allocated", "stale",

@@ -745,10 +745,11 @@ int crt_set_option(crt_ctx *ctx, const char *name, int64_t value);
 int crt_accel_stats(crt_ctx *ctx, uint64_t out[8]);
 
 /* Test hooks: one closest-hit query per ray (rays: n x 8 floats ox,oy,oz,dx,dy,dz,exclude_as_u32_bits,_;  out: n x 8:
- * t, px,py,pz, nx,ny,nz, index_bits (0xFFFFFFFF = miss)) through the SINGLE-RAY walk: of the BVH2 under
- * CRT_ACCEL_BVH2 / LBVH (the walk of the "pipeline" = 0 form, of k_wf_finish and of the denoise G-buffer -- not the
- * wide tree the wavefront kernels of crt_trace walk: crt_debug_trace_rays), the reference's loop over every primitive
- * under CRT_ACCEL_NONE; and elementwise evaluation of the device math (fn codes: 0 sin 1 cos 2 exp 3 log2 4 exp2
+ * t, px,py,pz, nx,ny,nz, index_bits (0xFFFFFFFF = miss)) through the SINGLE-RAY walk of the BVH2 under
+ * CRT_ACCEL_BVH2 / LBVH / PLOC (the walk of the closest-hit rays of the "pipeline" = 0 form, of the denoise G-buffer and the
+ * one k_wf_finish FALLS BACK to -- not k_wf_finish's first walk, the single-ray walk of the quantised 4-wide tree:
+ * crt_debug_walk_rays; and not the wide tree the wavefront kernels of crt_trace walk: crt_debug_trace_rays), the
+ * reference's loop over every primitive under CRT_ACCEL_NONE; and elementwise evaluation of the device math (fn codes: 0 sin 1 cos 2 exp 3 log2 4 exp2
  * 5 pow 6 sqrt 7 div 8 tan). */
 int crt_debug_intersect(crt_ctx *ctx, const float *rays, size_t n, float *out);
 /* Test hook: n rays through the traversal kernel crt_trace launches for the context's current tree and options (the
@@ -768,6 +769,23 @@ int crt_debug_intersect(crt_ctx *ctx, const float *rays, size_t n, float *out);
  * without a scene or tree, with a stale tree, and where there is no wavefront tree (CRT_ACCEL_NONE, "pipeline" = 0).
  * The counters of crt_counters are not touched. */
 int crt_debug_trace_rays(crt_ctx *ctx, const float *rays, size_t n, uint32_t *out, uint64_t report[8]);
+/* Test hook: n rays through the SINGLE-RAY walks as the kernels call them, one lane per ray in 64-lane blocks with
+ * k_wf_finish's stack (the non-counting instantiations; the counters of crt_counters are not touched).
+ *   walk 0: as k_wf_finish walks its stragglers' rays -- the single-ray walk of the quantised 4-wide tree where that tree
+ *           is live and no 8-wide tree is (crt_debug_read_accel header [10] = 1, [11] = 0), repeated on the BVH2 when its
+ *           stack would overflow; else the BVH2 walk.  Shadow rays any-hit, primed with the given t_light / light index.
+ *   walk 1: as the "pipeline" = 0 kernel walks -- the BVH2 only; a shadow ray tests the light's own primitive itself
+ *           (t_light of the ray record is not read) and then walks any-hit.
+ *   rays: n x 12 floats, the layout of crt_debug_trace_rays
+ *   out:  n x 4 uint32   [0] [1] as crt_debug_trace_rays writes them; [2] flags: bit 0 = the 4-wide tree was walked,
+ *                        bit 1 = that walk gave up and the BVH2 walk repeated the ray; [3] walk 1, shadow ray: the bits of
+ *                        the t_light the kernel computed (0x7F800000 bits of CRT_INFINITY: the ray misses the light), else 0
+ *   report (may be NULL): [0] rays that walked the 4-wide tree, [1] rays that fell back, [2] stack entries per lane,
+ *                        [3] inner levels of the 4-wide tree, [4] recorded depth of the BVH2, [5] 1 = walk 0 takes the
+ *                        4-wide tree, [6] [7] 0
+ * Works under "pipeline" 0 and 1 (the trees are the same).  A sync point.  CRT_EINVAL for a non-finite ray, a bad kind /
+ * light or walk; CRT_ESTATE without a scene or tree, with a stale tree and under CRT_ACCEL_NONE. */
+int crt_debug_walk_rays(crt_ctx *ctx, int walk, const float *rays, size_t n, uint32_t *out, uint64_t report[8]);
 int crt_debug_math(crt_ctx *ctx, int fn, const float *a, const float *b, float *out, size_t n);
 /* Test hook: the context's current acceleration structure, copied to the caller with plain device-to-host copies (no
  * kernel runs).  `what` selects one part; *bytes (may be NULL) receives the part's size; out == NULL only reports it.

@@ -637,6 +637,22 @@ class Rays:
         return np.clip(o, -self.M, self.M).astype(np.float32), d
 
 
+WALK_N = 500                          # rays per class of the chain case in test_single_ray_walks_gpu.py and its CPU side
+WALK_SEED = 10
+
+
+def state_rays(case, n, seed, prims=None):
+    """The rays test_traversal_rays_gpu.State(case, prims, ..., seed, n) makes, draw for draw: [(class name, o, d, light)]
+    -- the extension classes (light None), then one shadow class per light and per tie light."""
+    R = Rays(case, prims, seed=seed)
+    out = [(cname, o, d, None) for cname, o, d, _ in R.classes(n)]
+    for L, cname, kind in [(L, "shadow", None) for L in case.lights] + [(L, f"shadow_tie_{k}", k) for L, k in case.tie_lights]:
+        od = R.shadow_tie(L, n // 2) if kind else R.shadow(L, n)
+        o, d = od if od is not None else R.shadow(L, n // 2)
+        out.append((f"{cname}[light {L}]", o, d, L))
+    return out
+
+
 # ------------------------------------------------------------------ judged by a reference
 def resolve_exclude(ref, rng, nprim, o, d, mode):
     ex = np.full(len(o), MAXU, np.uint32)
