@@ -798,6 +798,24 @@ static napi_value js_read_moments(napi_env env, napi_callback_info info)
     return ta;
 }
 
+/* debugReadClipBox(h) -> Float32Array (tw*th*8): per pixel lo.rgb, N, hi.rgb, valid of the box the last temporal call of
+ * this frame clamped the history to under setOption(h, 'temporal_clip_pct', P) (include/crt.h "Clipped history"). */
+static napi_value js_debug_read_clip_box(napi_env env, napi_callback_info info)
+{
+    ARGS(1)
+    crt_ctx *ctx = get_ctx(env, argv[0]);
+    if (!ctx) return NULL;
+    uint32_t tl[4];
+    CRT_CHECK(env, ctx, "crt_tile", crt_tile(ctx, tl));
+    size_t px = (size_t)tl[2] * tl[3];
+    void *data = NULL;
+    napi_value ab, ta;
+    NAPI_OK(env, napi_create_arraybuffer(env, px * 32, &data, &ab));
+    CRT_CHECK(env, ctx, "crt_debug_read_clip_box", crt_debug_read_clip_box(ctx, (float *)data));
+    NAPI_OK(env, napi_create_typedarray(env, napi_float32_array, px * 8, ab, 0, &ta));
+    return ta;
+}
+
 static napi_value js_read_gbuffer(napi_env env, napi_callback_info info)
 {
     ARGS(1)
@@ -1475,6 +1493,7 @@ static napi_value init(napi_env env, napi_value exports)
         {"denoiseTemporal", js_denoise_temporal}, {"denoiseTemporalAsync", js_denoise_temporal_async},
         {"denoiseSvgfDefaults", js_denoise_svgf_defaults}, {"denoiseSvgf", js_denoise_svgf}, {"denoiseSvgfAsync", js_denoise_svgf_async},
         {"readMoments", js_read_moments},
+        {"debugReadClipBox", js_debug_read_clip_box},
         {"readFrameAdaptive", js_read_frame_adaptive}, {"denoiseFrame", js_denoise_frame}, {"denoiseFrameAsync", js_denoise_frame_async},
         {"denoiseAdaptiveFrame", js_denoise_adaptive_frame}, {"denoiseAdaptiveFrameAsync", js_denoise_adaptive_frame_async},
         {"gatherAsync", js_gather_async}, {"readFrameRgba8Async", js_read_frame_rgba8_async}, {"readFrameAccumAsync", js_read_frame_accum_async},

@@ -36,6 +36,12 @@ def parse_args(argv=None):
                     help="with --orbit N --denoise K --temporal --variance: option svgf_spatial_pct = PCT (25..10000, 400 when "
                          "given bare): a pixel with too short a history for a temporal variance takes one from the spread of "
                          "its 7x7 neighbourhood, times PCT / 100")
+    ap.add_argument("--clip", type=int, nargs="?", const=100, default=None, metavar="PCT",
+                    help="with --orbit N --denoise K --temporal: option temporal_clip_pct = PCT (25..10000, 100 when given "
+                         "bare): the reprojected history of a pixel is clamped to the mean +- PCT / 100 standard deviations of "
+                         "the frame's own colours over its 7x7 neighbourhood.  It is for lighting that changes on surfaces that "
+                         "do not (the shadows --animate drags over the floor, a light that is switched): under a fixed camera "
+                         "with fixed lighting it costs some of the history's benefit")
     ap.add_argument("--animate", action="store_true",
                     help="with --orbit N --denoise K --temporal: before frame k every sphere is moved to its frame-0 centre plus "
                          "(0, 0.5 radius sin(2 pi k / 16), 0) (update_primitives + refit_accel), and option temporal_motion keeps "
@@ -76,6 +82,8 @@ def parse_args(argv=None):
         ap.error("--variance goes with --orbit N --denoise K --temporal")
     if args.spatial is not None and (not args.variance or not 25 <= args.spatial <= 10000):
         ap.error("--spatial [PCT] goes with --orbit N --denoise K --temporal --variance, PCT in 25..10000")
+    if args.clip is not None and (not args.temporal or not 25 <= args.clip <= 10000):
+        ap.error("--clip [PCT] goes with --orbit N --denoise K --temporal, PCT in 25..10000")
     if args.animate and not args.temporal:
         ap.error("--animate goes with --orbit N --denoise K --temporal")
     if args.animate_device and (not args.temporal or args.animate):
@@ -122,6 +130,8 @@ def main(argv=None):
                 r.set_option("refit_rebuild_pct", args.rebuild_pct)
             if args.spatial is not None:
                 r.set_option("svgf_spatial_pct", args.spatial)
+            if args.clip is not None:
+                r.set_option("temporal_clip_pct", args.clip)
             for k, cam in enumerate(scene.orbit_cameras(ps.camera, args.orbit)):
                 if args.animate:
                     for i in spheres:

@@ -105,6 +105,7 @@ SIGNATURES = {
     "crt_denoise_svgf": (C.c_int, [_P, _P, _P, _P, _P, _P]),
     "crt_denoise_svgf_defaults": (C.c_int, [_P]),
     "crt_debug_read_moments": (C.c_int, [_P, _P]),
+    "crt_debug_read_clip_box": (C.c_int, [_P, _P]),
 }
 
 

@@ -917,6 +917,13 @@ int crt_set_option(crt_ctx *c, const char *name, int64_t value)
         c->svgf_spatial_pct = (int)value;
         return CRT_OK;
     }
+    if (!std::strcmp(name, "temporal_clip_pct")) {          // 
+        if (value != 0 && (value < 25 || value > 10000)) return fail(c, CRT_EINVAL, "crt_set_option: temporal_clip_pct is 0 (off) or 25..10000");
+        if (!value && c->dn.relit) c->dn.drop();               // (history across a light edit is this option's)
+        if (!value) { c->dn.box.release(); c->dn.box_ran = false; }
+        c->dn.clip_pct = (int)value;
+        return CRT_OK;
+    }
     if (!std::strcmp(name, "frame_ring")) {
         c->frame_ring = (uint32_t)std::min<int64_t>(256, std::max<int64_t>(0, value));
         c->ring_from = c->sample + 1u;                          // (a new ring starts empty)

@@ -273,9 +273,15 @@ struct crt_ctx {
         bool motion = false;
         DevBuf<unsigned char> snap;
         DevBuf<float2> uv;          // crt_read_motion's output
+        // option "temporal_clip_pct" (DESIGN.md 6l): the blend clamps the reprojected history to the box of the frame's own
+        // 7x7 neighbourhood, and the history outlives crt_update_lights.
+        int clip_pct = 0;           // the option's value P (0 = off)
+        DevBuf<float4> box;         // 2 per tile pixel: (lo, N), (hi, valid); allocated only with the option on
+        bool box_ran = false;       // the temporal call that wrote CURRENT ran the box kernel (crt_debug_read_clip_box)
+        bool relit = false;         // the history has outlived a light edit: setting the option back to 0 drops it
 
         // Drop the history (the geometry snapshot goes with it).
-        void drop() { cur.clear(); prev.clear(); snap.release(); }
+        void drop() { cur.clear(); prev.clear(); snap.release(); relit = box_ran = false; }
     } dn;
 
     // The frame-level filters of a partitioned context (crt_denoise_frame, crt_denoise_adaptive_frame, crt_read_frame_adaptive;

@@ -264,6 +264,18 @@ int crt_debug_read_moments(crt_ctx *c, float *out)
     return dn_finish(c, n, nullptr, nullptr, nullptr);
 }
 
+int crt_debug_read_clip_box(crt_ctx *c, float *out)
+{
+    if (!c || !out) return CRT_EINVAL;
+    CRT_TRY(dn_begin(c, "crt_debug_read_clip_box", 0, nullptr, 0, "", DN_TEMPORAL));
+    if (!c->dn.cur.valid || c->dn.cur.frame != c->frame_id || !c->dn.box_ran || c->dn.clip_pct == 0)
+        return fail(c, CRT_ESTATE, "crt_debug_read_clip_box: the last temporal call of this frame ran no box pass (option "
+                                   "\"temporal_clip_pct\" off, no usable PREVIOUS slot, or no call in this frame yet)");
+    const size_t n = (size_t)c->tw * c->th;
+    if (n) HIPCHK(c, hipMemcpyAsync(out, c->dn.box.p, 2 * n * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+    return dn_finish(c, n, nullptr, nullptr, nullptr);
+}
+
 // The tile classes of the context's current camera, tile rectangle and root node: the inputs of the next
 // run, or of the one the flush below ends.  A run's set-up makes its table from the same inputs with the same launch.
 static int tile_class_inputs(crt_ctx *c, const char *what, size_t n_tiles, WfParams &W)

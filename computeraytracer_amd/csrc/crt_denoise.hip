@@ -384,6 +384,96 @@ __device__ __forceinline__ bool dn_known(float m1, float ms, float Mw, float n, 
     return true;
 }
 
+// ---------------------------------------------------------------- the clip box (option "temporal_clip_pct")
+// DESIGN.md 6l defines it operation by operation (tests/denoise_clip_ref.py is its numpy restatement).  Launched before
+// k_dn_reproject on the same grid: every pixel that can reuse history gets lo = mu - gamma sigma and hi = mu + gamma sigma
+// per channel from the frame's own c_new over the 7x7 taps of its key, and the blend clamps the reprojected h to them.
+//
+// The block's 22 x 22 halo is staged once in LDS as four planes (key, r, g, b) in k_dn_spatial_var's layout (explained
+// there): pitch 48 dwords, two planes per set of rows.  accum -> c_new is converted once per staged cell.
+constexpr int kSvRadius = 3, kSvTile = 16 + 2 * kSvRadius, kSvPitch = 48, kSvPair = kSvTile * kSvPitch;
+constexpr uint32_t kDnNoTap = 0xFFFFFFFEu;                       // the key of a cell no pixel accepts (keys are < 2^26, or kNoHit)
+__device__ __forceinline__ constexpr int dn_sv_plane(int k) { return (k >> 1) * kSvPair + (k & 1) * (kSvPitch / 2); }
+
+template <bool ADAPT>
+__global__ __launch_bounds__(256) void k_dn_clip_box(const std::conditional_t<ADAPT, DnAdaptive<DnClipParams>, DnClipParams> P)
+{
+    __shared__ float tile[2 * kSvPair];
+    const int x = dn_x16(), y = dn_y16();
+    const int tw = (int)P.tw, th = (int)P.th;
+    const bool inside = x < tw && y < th;
+    const size_t p = (size_t)y * P.tw + (size_t)x;
+    // c_new of the pixel at (qx, qy) inside the rectangle: k_dn_reproject's expression
+    const auto c_new_at = [&](int qx, int qy) {
+        const float4 a = P.accum[(size_t)qy * P.tw + (size_t)qx];
+        float n = P.n;
+        if constexpr (ADAPT) n = (float)P.counts[(size_t)((uint32_t)qy >> 3) * P.tiles_x + ((uint32_t)qx >> 3)];
+        return xyz_to_linear_rgb(f3{a.x, a.y, a.z} / n);
+    };
+    uint32_t key_p = kNoHit;
+    bool need = false;
+    if (inside) {
+        key_p = P.key[p];
+        if (key_p != kNoHit && (key_p >> 24) != kGlass) {
+            const f3 c = c_new_at(x, y);
+            need = finite4(float4{c.x, c.y, c.z, 0.0f});
+        }
+    }
+    // no pixel of the block can have a box (sky, glass): nothing is staged
+    const bool any = __syncthreads_or(need ? 1 : 0) != 0;
+    if (inside && !need) { P.box[2 * p] = float4{0, 0, 0, 0}; P.box[2 * p + 1] = float4{0, 0, 0, 0}; }
+    if (!any) return;
+    const int bx = (int)(blockIdx.x * 16u) - kSvRadius, by = (int)(blockIdx.y * 16u) - kSvRadius;
+    for (int i = (int)threadIdx.x; i < kSvTile * kSvTile; i += 256) {
+        const int cy = i / kSvTile, cx = i - cy * kSvTile;
+        const int qx = bx + cx, qy = by + cy;
+        uint32_t k = kDnNoTap;                                  // outside the rectangle, or a colour that is not finite
+        f3 c = f3{0, 0, 0};
+        if (qx >= 0 && qx < tw && qy >= 0 && qy < th) {
+            const f3 cq = c_new_at(qx, qy);
+            if (finite4(float4{cq.x, cq.y, cq.z, 0.0f})) { k = P.key[(size_t)qy * P.tw + (size_t)qx]; c = cq; }
+        }
+        const int cell = cy * kSvPitch + cx;
+        tile[dn_sv_plane(0) + cell] = bits_f(k);
+        tile[dn_sv_plane(1) + cell] = c.x; tile[dn_sv_plane(2) + cell] = c.y; tile[dn_sv_plane(3) + cell] = c.z;
+    }
+    __syncthreads();
+    if (!need) return;
+    const int c0 = ((int)(threadIdx.x >> 4) + kSvRadius) * kSvPitch + (int)(threadIdx.x & 15u) + kSvRadius;
+    // Both loops are unrolled in full; only the accepted taps' 49-bit mask stays in registers between them.
+    constexpr int kSide = 2 * kSvRadius + 1;
+    uint64_t accepted = 0;
+    float N = 0.0f;
+    f3 sum = f3{0, 0, 0}, S = f3{0, 0, 0};
+#pragma unroll
+    for (int dy = -kSvRadius; dy <= kSvRadius; dy++)
+#pragma unroll
+        for (int dx = -kSvRadius; dx <= kSvRadius; dx++) {
+            const int c = c0 + dy * kSvPitch + dx, i = (dy + kSvRadius) * kSide + dx + kSvRadius;
+            if (f_bits(tile[dn_sv_plane(0) + c]) != key_p) continue;        // (the centre always passes)
+            accepted |= 1ull << i;
+            N = N + 1.0f;
+            sum = sum + f3{tile[dn_sv_plane(1) + c], tile[dn_sv_plane(2) + c], tile[dn_sv_plane(3) + c]};
+        }
+    const f3 mu = sum / N;
+    // (a second pass, not m2 - m1^2: 6g's cancellation; the window is in LDS, so it costs no traffic)
+#pragma unroll
+    for (int dy = -kSvRadius; dy <= kSvRadius; dy++)
+#pragma unroll
+        for (int dx = -kSvRadius; dx <= kSvRadius; dx++) {
+            const int c = c0 + dy * kSvPitch + dx, i = (dy + kSvRadius) * kSide + dx + kSvRadius;
+            if (!((accepted >> i) & 1ull)) continue;
+            const f3 d = f3{tile[dn_sv_plane(1) + c], tile[dn_sv_plane(2) + c], tile[dn_sv_plane(3) + c]} - mu;
+            S = S + f3{d.x * d.x, d.y * d.y, d.z * d.z};
+        }
+    const f3 v = S / N;
+    const f3 r = f3{sqrt_(v.x), sqrt_(v.y), sqrt_(v.z)} * P.gamma;
+    const f3 lo = mu - r, hi = mu + r;
+    const bool valid = N >= 4.0f && finite4(float4{lo.x, lo.y, lo.z, 0.0f}) && finite4(float4{hi.x, hi.y, hi.z, 0.0f});
+    P.box[2 * p] = float4{lo.x, lo.y, lo.z, N};
+    P.box[2 * p + 1] = float4{hi.x, hi.y, hi.z, valid ? 1.0f : 0.0f};
+}
+
 template <bool MOMENTS, bool ADAPT>
 using DnReprojArg = std::conditional_t<ADAPT, DnAdaptive<std::conditional_t<MOMENTS, DnSvgfParams, DnReprojParams>>,
                                        std::conditional_t<MOMENTS, DnSvgfParams, DnReprojParams>>;
@@ -452,7 +542,11 @@ __global__ __launch_bounds__(256) void k_dn_reproject(const DnReprojArg<MOMENTS,
                     }
                 }
                 if (sw > 0.0f) {
-                    const f3 h = sc / sw;
+                    f3 h = sc / sw;
+                    if (P.box) {                                // 6l: the history clamped to the frame's own neighbourhood
+                        const float4 b0 = P.box[2 * p], b1 = P.box[2 * p + 1];
+                        if (b1.w != 0.0f) h = f3{min_(max_(h.x, b0.x), b1.x), min_(max_(h.y, b0.y), b1.y), min_(max_(h.z, b0.z), b1.z)};
+                    }
                     const float Hp = min_(sh / sw, P.max_history);
                     Hw = n + Hp;
                     c = (c_new * n + h * Hp) / Hw;
@@ -511,10 +605,8 @@ __global__ __launch_bounds__(256) void k_dn_motion(const DnReprojParams P, float
 // The block's 22 x 22 halo tile is staged once in LDS as nine planes (key, m1, Mw, normal, position); both passes read LDS
 // only.  Row pitch 48 dwords: the two rows a 32-lane half of the wave reads in one ds_read_b32 lie 48 = 16 (mod 32) banks
 // apart, 16 consecutive dwords each, so the 32 lanes hit 32 different banks.  A row holds 22 of its 48 dwords, so two
-// planes share one set of rows, the second from dword 24 on.
-constexpr int kSvRadius = 3, kSvTile = 16 + 2 * kSvRadius, kSvPitch = 48, kSvPair = kSvTile * kSvPitch;
-constexpr uint32_t kDnNoTap = 0xFFFFFFFEu;                       // the key of a cell no pixel accepts (keys are < 2^26, or kNoHit)
-__device__ __forceinline__ constexpr int dn_sv_plane(int k) { return (k >> 1) * kSvPair + (k & 1) * (kSvPitch / 2); }
+// planes share one set of rows, the second from dword 24 on (kSvPitch, dn_sv_plane: declared above k_dn_clip_box, which
+// stages its four planes the same way).
 
 // What a pixel's moments must hold to take part, as centre or as tap: m1 and Mw finite, Mw > 0.
 __device__ __forceinline__ bool dn_sv_holds(float m1, float Mw) { return dn_finite(m1) && dn_finite(Mw) && Mw > 0.0f; }
@@ -727,14 +819,34 @@ static hipError_t dn_launch_reproject(const DnFilter &F, const Params &P, const 
     return hipGetLastError();
 }
 
+// 6l's box pass for the blend that follows: box null (option "temporal_clip_pct" off) or no PREVIOUS launches nothing and
+// leaves P.box null.
+template <class Params>
+static hipError_t dn_launch_clip_box(const DnFilter &F, Params &P, const uint32_t *counts, float4 *box, float gamma)
+{
+    P.box = nullptr;
+    if (!box || !P.h_prev) return hipSuccess;
+    DnAdaptive<DnClipParams> A{};
+    A.accum = P.accum; A.key = F.key; A.box = box;
+    A.tw = F.tw; A.th = F.th; A.n = P.n; A.gamma = gamma;
+    A.counts = counts; A.tiles_x = (F.tw + 7u) / 8u;
+    if (counts) hipLaunchKernelGGL(k_dn_clip_box<true>, dn_grid16(F), dim3(256), 0, F.stream, A);
+    else hipLaunchKernelGGL(k_dn_clip_box<false>, dn_grid16(F), dim3(256), 0, F.stream, static_cast<const DnClipParams &>(A));
+    P.box = box;
+    return hipGetLastError();
+}
+
 // The blend into P.h_cur, then the passes reading h_cur first and writing c[0], c[1], ... (h_cur itself stays
 // unfiltered: it is the next frame's history).  counts: null, or the tile counts of the adaptive state.
-hipError_t dn_launch_temporal(const DnFilter &F, DnReprojParams P, const uint32_t *counts, float sigma_color, float4 **out)
+// box: null, or the 2 float4 per pixel of option "temporal_clip_pct" with its factor gamma.
+hipError_t dn_launch_temporal(const DnFilter &F, DnReprojParams P, const uint32_t *counts, float sigma_color, float4 *box, float gamma,
+                              float4 **out)
 {
     *out = P.h_cur;
     if ((size_t)F.tw * F.th == 0) return hipSuccess;
     P.rgba = F.iterations == 0 ? F.rgba : nullptr;
-    const hipError_t e = dn_launch_reproject<false>(F, P, counts);
+    hipError_t e = dn_launch_clip_box(F, P, counts, box, gamma);
+    if (e == hipSuccess) e = dn_launch_reproject<false>(F, P, counts);
     return e != hipSuccess ? e : dn_run_atrous(F, P.h_cur, sigma_color, out);
 }
 
@@ -793,8 +905,9 @@ hipError_t dn_launch_filter_adaptive(const DnFilter &F, const float4 *accum, con
 // (h_cur and m_cur stay unfiltered: they are the next frame's history).  counts: as dn_launch_temporal.
 // spatial_b: 0, or the factor of option "svgf_spatial_pct" -- k_dn_spatial_var then rewrites the v of the pixels the moments
 // do not cover before the passes read it; what stays behind in h_cur and m_cur does not depend on it.
+// box, gamma: as dn_launch_temporal.
 hipError_t dn_launch_svgf(const DnFilter &F, DnSvgfParams P, const uint32_t *counts, uint2 *kv, float *var, float sigma_variance,
-                          float spatial_b, float4 **out)
+                          float spatial_b, float4 *box, float gamma, float4 **out)
 {
     *out = F.c[0];
     if ((size_t)F.tw * F.th == 0) return hipSuccess;
@@ -802,7 +915,8 @@ hipError_t dn_launch_svgf(const DnFilter &F, DnSvgfParams P, const uint32_t *cou
     P.rgba = last0 ? F.rgba : nullptr;
     P.var = last0 ? var : nullptr;
     P.cv = F.c[0];
-    hipError_t e = dn_launch_reproject<true>(F, P, counts);
+    hipError_t e = dn_launch_clip_box(F, P, counts, box, gamma);
+    if (e == hipSuccess) e = dn_launch_reproject<true>(F, P, counts);
     if (e == hipSuccess && spatial_b != 0.0f) {
         DnAdaptive<DnSpatialParams> A{};
         A.m_cur = P.m_cur; A.gbuf = F.gbuf; A.key = F.key;

@@ -265,6 +265,7 @@ struct ThCall {
     float sigma_color;                  // !svgf
     float sigma_variance, min_frames;   // svgf
     float spatial_b;                    // svgf: 0, or the factor of option "svgf_spatial_pct" 
+    float gamma;                        // 0, or the factor of option "temporal_clip_pct" 
 };
 
 static int th_blend_and_filter(crt_ctx *c, const ThCall &t, bool rgba, bool hist, bool var, float4 **res)
@@ -284,6 +285,7 @@ static int th_blend_and_filter(crt_ctx *c, const ThCall &t, bool rgba, bool hist
         CRT_ENSURE(c, c->dn.kv, n);
         CRT_ENSURE(c, c->dn.var, n);
     }
+    if (t.gamma != 0.0f) CRT_ENSURE(c, c->dn.box, 2 * n);
     CRT_TRY(dn_ensure_gbuffer(c, promote ? &prev : &cur));
     // CURRENT becomes PREVIOUS, with its guides and its snapshot flag; the slot that was PREVIOUS ends here, as CURRENT
     // does when this frame is filtered again
@@ -300,14 +302,17 @@ static int th_blend_and_filter(crt_ctx *c, const ThCall &t, bool rgba, bool hist
     P.normal_tol2 = (float)std::min(3.0e38, (double)t.normal_tol * t.normal_tol);
     P.plane_tol = t.plane_tol;
     const DnFilter F = dn_filter(c, t.iterations, t.sigma_normal, t.sigma_plane, rgba);
+    float4 *box = t.gamma != 0.0f ? c->dn.box.p : nullptr;
+    c->dn.box_ran = false;
     if (t.svgf) {
         P.m_prev = P.h_prev && prev.has_m ? prev.m.p : nullptr;
         P.m_cur = cur.m.p;
         P.min_frames = t.min_frames;
-        HIPCHK(c, dn_launch_svgf(F, P, counts, c->dn.kv.p, var ? c->dn.var.p : nullptr, t.sigma_variance, t.spatial_b, res));
+        HIPCHK(c, dn_launch_svgf(F, P, counts, c->dn.kv.p, var ? c->dn.var.p : nullptr, t.sigma_variance, t.spatial_b, box, t.gamma, res));
     } else {
-        HIPCHK(c, dn_launch_temporal(F, P, counts, t.sigma_color, res));
+        HIPCHK(c, dn_launch_temporal(F, P, counts, t.sigma_color, box, t.gamma, res));
     }
+    c->dn.box_ran = box && P.h_prev;                             // (what the launchers ask before the box pass)
     std::memcpy(cur.cam, c->sc.cam, sizeof cur.cam);
     cur.guides = c->dn.set; cur.frame = c->frame_id;
     cur.valid = true; cur.has_m = t.svgf;
@@ -326,7 +331,7 @@ int crt_denoise_temporal(crt_ctx *c, const crt_denoise_temporal_params *params, 
     float *hw_host = history_out ? history_out : hw.empty() ? nullptr : hw.data();
     if (n) {
         const ThCall t{dp.iterations, dp.sigma_normal, dp.sigma_plane, dp.max_history, dp.normal_tol, dp.plane_tol, false,
-                       dp.sigma_color, 0.0f, 0.0f, 0.0f};
+                       dp.sigma_color, 0.0f, 0.0f, 0.0f, (float)c->dn.clip_pct / 100.0f};
         CRT_TRY(th_blend_and_filter(c, t, rgba8_out != nullptr, history_out || rgb_out, false, &res));
     }
     const int rc = dn_finish(c, n, res, rgb_out, rgba8_out, c->dn.hist.p, hw_host);
@@ -357,7 +362,8 @@ int crt_denoise_svgf(crt_ctx *c, const crt_denoise_svgf_params *params, float *r
     float4 *res = nullptr;
     if (n) {
         const ThCall t{dp.iterations, dp.sigma_normal, dp.sigma_plane, dp.max_history, dp.normal_tol, dp.plane_tol, true,
-                       0.0f, dp.sigma_variance, dp.min_frames, (float)c->svgf_spatial_pct / 100.0f};
+                       0.0f, dp.sigma_variance, dp.min_frames, (float)c->svgf_spatial_pct / 100.0f,
+                       (float)c->dn.clip_pct / 100.0f};
         CRT_TRY(th_blend_and_filter(c, t, rgba8_out != nullptr, history_out != nullptr, var_out != nullptr, &res));
         if (var_out) HIPCHK(c, hipMemcpyAsync(var_out, c->dn.var.p, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     }

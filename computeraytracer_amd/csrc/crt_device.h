@@ -289,6 +289,19 @@ struct DnReprojParams {
     // the 80-byte records as they are and as the previous slot saw them; raw_prev null = the same scene
     const unsigned char *raw, *raw_prev;
     uint32_t nprim;
+    // DESIGN.md 6l (option "temporal_clip_pct"): per pixel (lo, N), (hi, valid) as k_dn_clip_box left them; null = off
+    const float4 *box;
+};
+
+// k_dn_clip_box (option "temporal_clip_pct"): before k_dn_reproject, the colour box of every pixel from the
+// frame's own 7x7 neighbourhood; the blend clamps the reprojected history to it.
+struct DnClipParams {
+    const float4 *accum;            // this frame: XYZ sums of n samples
+    const uint32_t *key;
+    float4 *box;                    // out: 2 per pixel, (lo.rgb, N) and (hi.rgb, valid)
+    uint32_t tw, th;
+    float n;
+    float gamma;                    // the option's factor, P / 100
 };
 
 // k_dn_reproject<*, true>: the blend above plus the temporal moments of the pixel's luminance, and the

@@ -86,10 +86,13 @@ hipError_t dn_launch_filter(const DnFilter &F, const float4 *accum, float n, flo
 hipError_t dn_launch_filter_adaptive(const DnFilter &F, const float4 *accum, const float *q, const uint32_t *counts, uint2 *kv,
                                      float *var, float sigma_variance, float4 **out);
 // (counts: null in the uniform state, where P.n is every pixel's n; else the adaptive state's count per 8x8 tile)
-hipError_t dn_launch_temporal(const DnFilter &F, DnReprojParams P, const uint32_t *counts, float sigma_color, float4 **out);
+// (box: null, or 2 float4 per pixel for the clip boxes of option "temporal_clip_pct" with its factor gamma, DESIGN.md 6l: the box
+// pass runs before the blend where P.h_prev is there, and the blend clamps the reprojected history to it)
+hipError_t dn_launch_temporal(const DnFilter &F, DnReprojParams P, const uint32_t *counts, float sigma_color, float4 *box, float gamma,
+                              float4 **out);
 // (spatial_b: 0, or the factor of option "svgf_spatial_pct")
 hipError_t dn_launch_svgf(const DnFilter &F, DnSvgfParams P, const uint32_t *counts, uint2 *kv, float *var, float sigma_variance,
-                          float spatial_b, float4 **out);
+                          float spatial_b, float4 *box, float gamma, float4 **out);
 hipError_t dn_launch_motion(const DnReprojParams &P, float2 *out, hipStream_t stream);
 
 }  // namespace crt

@@ -894,7 +894,10 @@ int crt_update_lights(crt_ctx *c, uint32_t first, uint32_t count, const void *re
     }
     CRT_TRY(quiesce(c, true));
     std::copy(nl.begin(), nl.end(), c->lights.begin() + first);
-    c->dn.drop();
+    // option "temporal_clip_pct" (DESIGN.md 6l): the history stays -- both slots, the moments, a geometry snapshot -- and the
+    // blend clips what the new lighting has made stale
+    if (c->dn.clip_pct == 0) c->dn.drop();
+    else if (c->dn.cur.valid || c->dn.prev.valid) c->dn.relit = true;
     std::vector<float4> hl((size_t)count * 3);
     for (uint32_t k = 0; k < count; k++) light_rows(nl[k], &hl[3 * (size_t)k]);
     if (count) {

@@ -402,7 +402,11 @@ class Renderer:
         """The frame blended with the previous frame's reprojected result, then the a-trous filter: rgba8 (H, W, 4); with
         rgb=True also linear rgb (H, W, 4) float32 (channel 3 = the history weight Hw in samples), with history=True
         also Hw (H, W) float32 -- a tuple in that order.  A parameter left out takes the library's default
-        (crt_denoise_temporal_defaults).  Reads the accumulator only; finishes what is in flight."""
+        (crt_denoise_temporal_defaults).  Reads the accumulator only; finishes what is in flight.
+        set_option("temporal_clip_pct", P) (0 = off, the default; 25..10000) clamps the reprojected history of every pixel
+        to mean +- (P / 100) standard deviations of the frame's own colours over its 7x7 neighbourhood before the blend, so
+        lighting that changed on an unchanged surface (a shadow that moved on) stops trailing, and update_lights keeps the
+        history (include/crt.h "Clipped history"; debug_read_clip_box returns the boxes)."""
         return self._denoise(self._lib.crt_denoise_temporal, _lib.denoise_temporal_defaults(), dict(
             iterations=iterations, sigma_color=sigma_color, sigma_normal=sigma_normal, sigma_plane=sigma_plane,
             max_history=max_history, normal_tol=normal_tol, plane_tol=plane_tol), rgb, bool(history))
@@ -422,7 +426,10 @@ class Renderer:
         variance left after filtering, both (H, W) float32 -- a tuple in that order.  A parameter left out takes the
         library's default (crt_denoise_svgf_defaults).  Reads the accumulator only; finishes what is in flight.
         set_option("svgf_spatial_pct", P) (0 = off, the default; 25..10000) gives the pixels whose history is too short for
-        that variance one from the spread of their 7x7 neighbourhood, times P / 100; the history does not depend on it."""
+        that variance one from the spread of their 7x7 neighbourhood, times P / 100; the history does not depend on it.
+        set_option("temporal_clip_pct", P) clips the history as it does for denoise_temporal: the colour CURRENT keeps is
+        the clipped blend, the moments are untouched, so a relit pixel's variance rises and the passes blur it more for a
+        few frames."""
         _, _, tw, th = self.tile
         p = _lib.denoise_svgf_defaults()
         for k, v in dict(iterations=iterations, sigma_variance=sigma_variance, sigma_normal=sigma_normal, sigma_plane=sigma_plane,
@@ -445,6 +452,15 @@ class Renderer:
         _, _, tw, th = self.tile
         out = np.empty((th, tw, 4), np.float32)
         self._chk(self._lib.crt_debug_read_moments(self._h, out.ctypes.data))
+        return out
+
+    def debug_read_clip_box(self) -> np.ndarray:
+        """(H, W, 8) float32 per tile pixel: lo.rgb, N, hi.rgb, valid (1.0 / 0.0) -- the box the last temporal call of this
+        frame clamped the pixel's history to under option "temporal_clip_pct", the number of taps behind it, and whether it
+        was used; N = 0 where the pixel has no box (crt_debug_read_clip_box, a test hook)."""
+        _, _, tw, th = self.tile
+        out = np.empty((th, tw, 8), np.float32)
+        self._chk(self._lib.crt_debug_read_clip_box(self._h, out.ctypes.data))
         return out
 
     def read_motion(self) -> np.ndarray:

@@ -1,7 +1,7 @@
 #!/usr/bin/env node
 'use strict';
 // CLI: node host/index.js [--scene file.json] [--width W --height H] [--spp N] [--accel bvh2|lbvh|ploc|none]
-//                         [--out image.ppm] [--dump prefix] [--pack-only prefix] [--denoise K] [--orbit N [--temporal [--variance [--spatial [PCT]]]]]
+//                         [--out image.ppm] [--dump prefix] [--pack-only prefix] [--denoise K] [--orbit N [--temporal [--clip [PCT]] [--variance [--spatial [PCT]]]]]
 // --denoise K: --out gets the image denoised with K a-trous iterations (crt_denoise; with --adaptive the variance-guided
 //            crt_denoise_adaptive) instead of the plain average
 // --orbit N: N frames of --spp each, the eye turned about the look-at point (one upload and build, then setCamera per
@@ -12,6 +12,10 @@
 //            frame means (denoiseSvgf)
 // --spatial [PCT]: with --variance, option "svgf_spatial_pct" = PCT (25..10000, 400 when given bare): a pixel with too short
 //            a history for a temporal variance takes one from the spread of its 7x7 neighbourhood, times PCT / 100
+// --clip [PCT]: with --temporal, option "temporal_clip_pct" = PCT (25..10000, 100 when given bare): the reprojected history of
+//            a pixel is clamped to the mean +- PCT / 100 standard deviations of the frame's own colours over its 7x7
+//            neighbourhood -- for lighting that changes on surfaces that do not; under a fixed camera with fixed lighting
+//            it costs some of the history's benefit
 // --adaptive T [--adaptive-step N] [--adaptive-min M]: adaptive sampling (traceAdaptive), rounds of N (16) samples until
 //            every 8x8 tile has an error <= T or holds --spp samples; a tile below M (default min(--spp, 2N)) samples is
 //            sampled whatever its error; prints rounds, pixel-samples, seconds and the min / median / max tile count.
@@ -51,6 +55,10 @@ const spatial = !('spatial' in args) ? null : args.spatial === true ? 400 : Numb
 if (spatial !== null && !(args.variance && Number.isInteger(spatial) && spatial >= 25 && spatial <= 10000)) {
   console.error('--spatial [PCT] goes with --orbit N --denoise K --temporal --variance, PCT in 25..10000'); process.exit(2);
 }
+const clip = !('clip' in args) ? null : args.clip === true ? 100 : Number(args.clip);
+if (clip !== null && !(args.temporal && Number.isInteger(clip) && clip >= 25 && clip <= 10000)) {
+  console.error('--clip [PCT] goes with --orbit N --denoise K --temporal, PCT in 25..10000'); process.exit(2);
+}
 const r = Main({ sceneFile: args.scene, width: args.width ? num('width') : undefined, height: args.height ? num('height') : undefined,
   accel: args.accel || 'bvh2', device: num('device', 0) });
 // --adaptive: rounds of --adaptive-step samples until no tile is active; {rounds, ad: readAdaptive(), pixelSamples}
@@ -71,6 +79,7 @@ if (args.orbit) {
   // --adaptive with --temporal: few samples per frame, placed where the noise is, accumulated over time
   if ('adaptive' in args && args.temporal) r.setOption('adaptive_temporal', 1);
   if (spatial !== null) r.setOption('svgf_spatial_pct', spatial);
+  if (clip !== null) r.setOption('temporal_clip_pct', clip);
   orbitCameras(r.packed.camera, n).forEach((cam, k) => {
     r.setCamera(cam);
     if (args.temporal) r.setSampleOffset(k * spp);

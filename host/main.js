@@ -118,6 +118,7 @@ function Main(options = {}) {
     denoiseSvgf: (opts = {}) => a.denoiseSvgf(device, opts),
     denoiseSvgfAsync: (opts = {}) => a.denoiseSvgfAsync(device, opts),
     readMoments: () => a.readMoments(device),
+    debugReadClipBox: () => a.debugReadClipBox(device),
     setOption: (name, value) => a.setOption(device, name, value),
     counters: () => a.counters(device),
     enableCounters: (on) => a.enableCounters(device, !!on),

@@ -341,7 +341,8 @@ int crt_transform_primitives(crt_ctx *ctx, const crt_prim_transform *ops, uint32
  * renumbers that copy exactly as it does the records (an unchanged record still compares equal, byte for byte), and an
  * append adds the new records to it as well, so that a pixel on an appended primitive takes the camera-only path,
  * whose key and plane tests reject what was there before.  A new light list drops the history as crt_update_lights
- * does.  Transient device memory: one more copy of the records, and one of the history's copy where it is kept. */
+ * does without option "temporal_clip_pct" -- and with it too: that option keeps the history across crt_update_lights
+ * alone.  Transient device memory: one more copy of the records, and one of the history's copy where it is kept. */
 typedef struct { uint32_t first, count; } crt_prim_range;   /* primitives [first, first+count) */
 int crt_remove_primitives(crt_ctx *ctx, const crt_prim_range *ranges, uint32_t n_ranges, const void *lights, size_t nlight);
 int crt_append_primitives(crt_ctx *ctx, const void *records, uint32_t count, const void *lights, size_t nlight);
@@ -349,7 +350,9 @@ int crt_append_primitives(crt_ctx *ctx, const void *records, uint32_t count, con
  * only place where the caller sees the geometry.  A sync point like crt_read_gbuffer; it only reads, and it works on a
  * stale tree.  CRT_EINVAL for a range outside the scene or out NULL with count > 0. */
 int crt_read_primitives(crt_ctx *ctx, uint32_t first, uint32_t count, void *out);
-/* Replace light records [first, first+count) (count x 80 bytes, crt_upload_scene's validation; 1/area recomputed). */
+/* Replace light records [first, first+count) (count x 80 bytes, crt_upload_scene's validation; 1/area recomputed).  The
+ * history of the temporal filters is dropped, unless option "temporal_clip_pct" is on: then it is kept, and the blend clips
+ * what the new lighting has made stale ("Clipped history"). */
 int crt_update_lights(crt_ctx *ctx, uint32_t first, uint32_t count, const void *records);
 /* Recompute every box of the tree (BVH2 and 4-wide, float and quantised; the quantisation grid re-derived) from the
  * current primitives, topology kept.  Rebuilds with the builder that made the tree instead, and sets *rebuilt = 1
@@ -580,7 +583,9 @@ int crt_sample_offset(crt_ctx *ctx, uint32_t *out);
  * x_p's, n_p's place in the projection and in the taps' tests.  A pixel whose record is bitwise unchanged takes the path
  * below exactly; one whose emission or reflectance index changed, or whose old record is degenerate, takes no history.
  * crt_update_lights drops the history in both modes (it changes what every surface receives), and lighting that changed
- * because something else moved (a shadow sliding over a static floor) is stale history until the blend outweighs it.
+ * because something else moved (a shadow sliding over a static floor) is stale history until the blend outweighs it --
+ * unless option "temporal_clip_pct" is on ("Clipped history" below): it clips such history, and keeps it across
+ * crt_update_lights.
  * Setting the option back to 0 after such an edit drops the history.
  * Per pixel p with first hit x_p, normal n_p and key: no history is taken where there is no PREVIOUS, at a miss, on
  * glass (view-dependent) or where the pixel's own colour is not finite.  Otherwise x_p is projected into the previous
@@ -684,6 +689,35 @@ int crt_denoise_svgf(crt_ctx *ctx, const crt_denoise_svgf_params *params, float 
  * frame and carries moments (no crt_denoise_svgf in this frame yet, or a crt_denoise_temporal after it). */
 int crt_debug_read_moments(crt_ctx *ctx, float *out);
 
+/* ------------------------------------------------------------------ Clipped history
+ * The temporal filters reuse a pixel's history when the SURFACE is the same; they cannot tell when the LIGHTING on it has
+ * changed (a shadow that slid on, a light that was dimmed).  Option "temporal_clip_pct" = P (default 0 = off; 25..10000;
+ * anything else is CRT_EINVAL and the option keeps its value; DESIGN.md 6l defines it operation by operation) clips the
+ * reprojected history to the colour statistics of the frame's own neighbourhood -- variance clipping -- in
+ * crt_denoise_temporal and crt_denoise_svgf; every other filter ignores it.  With gamma = (float)P / 100:
+ * every pixel p that is neither a miss nor glass and whose own c_new = M (accum / n) is finite has a BOX.  Its taps are the
+ * pixels q with |dx|, |dy| <= 3 inside the rectangle (a crt_set_tile rectangle's edges are image borders) whose key equals
+ * p's and whose c_new_q (with q's own n in the adaptive state) is finite in all three channels; p itself is one.  Per
+ * channel, in binary32, row-major over the taps: N their number, mu = (sum c_q) / N, in a second pass
+ * S = sum (c_q - mu)^2, sigma = sqrt(S / N), lo = mu - gamma sigma, hi = mu + gamma sigma.  No geometric weights: a same-key
+ * neighbour across a crease only widens the box.  The box is VALID iff N >= 4 and all six bounds are finite.
+ * In the blend of "Temporal reuse", a pixel with an accepted tap and a valid box takes h' = min(max(h, lo), hi) per channel
+ * for h; taps, tests, Hp, Hw, the moments, the spatial variance estimate, "temporal_motion", crt_read_motion and the
+ * promotion of the slots are unchanged, and Hw, moments and motion are bit for bit those of P = 0.  CURRENT keeps the
+ * clipped blend, so the next frame's history is already rectified; a relit pixel's moments see a large (y - h1)^2, its v
+ * rises, and crt_denoise_svgf's passes blur it more for a few frames: that is intended.
+ * Lights: with P != 0 crt_update_lights keeps the history (both slots, the moments, any geometry snapshot); setting the
+ * option back to 0 after such an edit drops it, as "temporal_motion" going back to 0 does after a primitive edit.
+ * crt_remove_primitives and crt_append_primitives with a new light list keep dropping it.
+ * It costs one more pass over the frame (96 bytes per pixel on the device while the option is on; CRT_ENOMEM leaves the
+ * slots as they were) and, where nothing changed, some of the history's benefit: a box from 4 samples per pixel is narrower
+ * than the noise of its own mean.  DESIGN.md 6l has the tables.  With 0 every call launches what it launches without the
+ * option.
+ * Test hook: per pixel lo.rgb, N, hi.rgb, valid (1.0 / 0.0) of the last temporal call of this frame, tw*th*8 floats; a
+ * pixel without a box reports N = 0, valid = 0.  A sync point, and it only reads.  CRT_ESTATE unless that call ran the box
+ * pass (the option on and a usable PREVIOUS slot); CRT_EINVAL for NULL. */
+int crt_debug_read_clip_box(crt_ctx *ctx, float *out /* tw*th*8 floats */);
+
 /* Counters accumulate over crt_trace calls while enabled (off by default: the
  * counting kernel variant is slower). */
 int crt_enable_counters(crt_ctx *ctx, int on);
@@ -728,6 +762,9 @@ int crt_last_kernel_ms(crt_ctx *ctx, float *ms, uint32_t *launches);
  * "svgf_spatial_pct" (0 = off, default | 25..10000, anything else is CRT_EINVAL: crt_denoise_svgf gives the pixels whose
  * variance the temporal moments do not cover yet an estimate from their 7x7 neighbourhood, times that percentage, see
  * "Variance-guided temporal filter"; it drops nothing, and with 0 the call launches what it launches without the option);
+ * "temporal_clip_pct" (0 = off, default | 25..10000, anything else is CRT_EINVAL: the temporal filters clamp the reprojected
+ * history to the mean +- that percentage of a standard deviation of the frame's own 7x7 neighbourhood, and
+ * crt_update_lights keeps the history, see "Clipped history"; back to 0 after a kept light edit drops the history);
  * "ploc_radius" (1..32, anything else is CRT_EINVAL; default 8: clusters searched to either side by CRT_ACCEL_PLOC; at
  * crt_build_accel);
  * "refit_rebuild_pct" (0 = off, default | 100..100000, anything else is CRT_EINVAL: crt_refit_accel rebuilds once the
