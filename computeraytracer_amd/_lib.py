@@ -76,6 +76,7 @@ SIGNATURES = {
     "crt_debug_tile_classes": (C.c_int, [_P, _P, C.c_size_t]),
     "crt_debug_tile_classes_host": (C.c_int, [_P, _P, C.c_size_t]),
     "crt_debug_tile_class_setups": (C.c_int, [_P, _P]),
+    "crt_debug_mapped_gen_launches": (C.c_int, [_P, _P]),
     "crt_debug_math": (C.c_int, [_P, C.c_int, _P, _P, _P, C.c_size_t]),
     "crt_set_camera": (C.c_int, [_P, _P]),
     "crt_update_primitives": (C.c_int, [_P, C.c_uint32, C.c_uint32, _P]),

@@ -935,6 +935,7 @@ int crt_set_option(crt_ctx *c, const char *name, int64_t value)
     if (!std::strcmp(name, "wf_cull_miss")) { c->wf_cull_miss = value != 0; return CRT_OK; }
     if (!std::strcmp(name, "wf_cull_classes")) { c->wf_cull_classes = value != 0; return CRT_OK; }
     if (!std::strcmp(name, "wf_defer_nee")) { c->wf_defer_nee = value != 0; return CRT_OK; }
+    if (!std::strcmp(name, "wf_affinity")) { c->wf_affinity = value != 0; return CRT_OK; }   // read when a batch is published
     if (!std::strcmp(name, "wf_pipes")) { c->wf_pipes = (int)std::min<int64_t>(crt_ctx::kMaxPipes, std::max<int64_t>(1, value)); return CRT_OK; }
     if (!std::strcmp(name, "wf_pool")) { c->wf_pool = (uint32_t)std::max<int64_t>(0, value); return CRT_OK; }
     if (!std::strcmp(name, "wf_waves_per_cu")) { c->wf_waves_per_cu = (uint32_t)std::min<int64_t>(32, std::max<int64_t>(0, value)); return CRT_OK; }

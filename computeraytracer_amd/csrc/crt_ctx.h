@@ -201,6 +201,8 @@ struct crt_ctx {
     int wf_cull_miss = 1;           // k_wf_gen decides whole work chunks whose camera rays all miss the tree's root boxes
     int wf_cull_classes = 1;        // ... and looks the tile's class up first: the tiles that miss or enter for every sample are classified once per run
     int wf_defer_nee = 1;           // k_wf_shade finishes a path roulette ends at once and defers its pending NEE term
+    int wf_affinity = 0;            // 1: a batch's work shards are region-major and traversal waves stay with their XCD's region (measured, no gain)
+    uint64_t mapped_gen_launches = 0;   // k_wf_gen launches that took a MAP instantiation so far (crt_debug_mapped_gen_launches)
     uint64_t tile_cls_setups = 0;   // run set-ups that launched k_wf_tile_classes so far (crt_debug_tile_class_setups)
     bool cie_zero = false;          // the uploaded CIE table turns zero radiance into +0 for every wavelength (tc_culled_is_zero)
     int wf_chunk = 1;               // iterations per status record at most

@@ -330,6 +330,13 @@ int crt_debug_tile_class_setups(crt_ctx *c, uint64_t *out)
     return CRT_OK;
 }
 
+int crt_debug_mapped_gen_launches(crt_ctx *c, uint64_t *out)
+{
+    if (!c || !out) return CRT_EINVAL;
+    *out = c->mapped_gen_launches;
+    return CRT_OK;
+}
+
 int crt_debug_hit_pad(crt_ctx *c, float *out)
 {
     if (!c || !out) return CRT_EINVAL;

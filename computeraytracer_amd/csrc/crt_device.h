@@ -19,6 +19,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "crt_work_map.h"
+
 namespace crt {
 
 constexpr uint32_t kNoHit = 0xFFFFFFFFu;
@@ -169,7 +171,8 @@ struct WfWorkQ {
     uint32_t work_done;              // set once every work shard is exhausted (saves the scans)
     uint32_t work_per_shard;         // the queue's extent (k_wf_init copies WfSeg here for write_status)
     unsigned long long work_total;
-    uint32_t pad_[28];
+    uint32_t map_samples, map_tiles; // WfSeg::map_samples and the frame's tiles: the shard sizes under "wf_affinity" (crt_work_map.h)
+    uint32_t pad_[26];
 };
 static_assert(sizeof(WfWorkQ) == (kWfShards + 1) * 128, "whole lines");
 // One batch's share of the parameters (indexed by batch id like the queues and the staging buffers).
@@ -177,6 +180,8 @@ struct WfSeg {
     unsigned long long work_total;   // n_samples * npix_padded
     uint32_t work_per_shard;         // work items per shard (multiple of 64)
     uint32_t first_sample;
+    uint32_t map_samples;            // 0: shard s holds ids [s * work_per_shard, +work_per_shard); else the batch's samples, and the
+    uint32_t pad_;                   // shards are region-major (option "wf_affinity", crt_work_map.h: sizes differ per shard)
 };
 
 // What the host needs to know about an iteration, reduced on the device (write_status in crt_wavefront.hip) into one
@@ -261,9 +266,13 @@ struct WfParams {
     // launch turns into a staging store iff vis[slot] == 1, whatever the slot holds by then.
     uint8_t *dflag;                  // one byte per slot, 0 = no entry
     uint32_t defer;                  // k_wf_shade: create such entries in this launch (the host: rearm && wf_defer_nee; I11 of crt_wf_driver.cpp)
+    // DESIGN.md 5.11 (option "wf_affinity"): traversal waves start on a ray-list shard whose residue modulo 8 is their XCD's
+    // id and prefer that residue when they move on; for speed only, every shard is drained whatever the ids say
+    uint32_t affinity;
 };
 constexpr uint32_t kWfDeferred = 0x80u;                         // WfParams::dflag: an entry is pending; the low 5 bits are its batch id
 static_assert(kWfRing <= 32u, "a deferred entry's batch id has 5 bits");
+static_assert(sizeof(WfParams) + sizeof(WfFinishSegs) <= 4096u, "the kernels take WfParams by value: kernel arguments are 4 KiB at most");
 
 // k_dn_reproject (crt_denoise.hip): the blend of a frame with the reprojected history of the previous one.
 // The projection into the previous film plane is binary64 (binary32 places a tap no better than 5e-5 pixel at 480 pixels,

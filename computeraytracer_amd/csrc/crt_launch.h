@@ -26,6 +26,7 @@ hipError_t wf_launch_init(const WfParams &P, hipStream_t s);
 hipError_t wf_launch_tea(const WfParams &P, uint32_t *out, hipStream_t s);
 hipError_t wf_launch_tile_classes(const WfParams &P, uint32_t *out, hipStream_t s);   // out: (tiles + 15) / 16 words
 bool wf_gen_culls(const WfParams &P);
+bool wf_gen_mapped(const WfParams &P);
 hipError_t wf_launch_shade(const WfParams &P, uint32_t it, hipStream_t s);
 hipError_t wf_launch_gen(const WfParams &P, uint32_t it, hipStream_t s, const AsTiles *A);
 hipError_t wf_launch_trace(const WfParams &P, uint32_t it, uint32_t trace_blocks, hipStream_t s);

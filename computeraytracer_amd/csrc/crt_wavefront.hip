@@ -609,9 +609,10 @@ __device__ __noinline__ void write_status(const WfCtl *ctl, const WfWorkQ *wq, u
 #pragma unroll
         for (uint32_t k = 0; k < 8u; k++) {
             const uint32_t b = g + k;
-            const uint32_t wps = wq[b].work_per_shard;
+            const uint32_t wps = wq[b].work_per_shard, ms = wq[b].map_samples;
             const unsigned long long wtot = wq[b].work_total, lo = (unsigned long long)lane * wps;
-            const unsigned long long size = lo < wtot ? min((unsigned long long)wps, wtot - lo) : 0ull;
+            const unsigned long long size = ms ? (unsigned long long)wm_shard_size(ms, wq[b].map_tiles, lane)
+                                               : lo < wtot ? min((unsigned long long)wps, wtot - lo) : 0ull;
             unsigned long long cons = min(cur[k], size);
             const unsigned long long left = __ballot(cur[k] < size);
             uint32_t al = alive[k];
@@ -810,17 +811,40 @@ __device__ __forceinline__ uint32_t wf_as_tile(const AsTiles &A, uint32_t w)
 // traversal launch of its pipe and is bound by dependent round trips, not by arithmetic): up to two segments of
 // consecutive work items -- the wave's own shard of the listed queues, oldest first, or one other shard when all of its
 // own are dry.  (Ranges, totals and steps are multiples of 64.)  Returns the chunks found.
-struct GenWork { uint32_t q[2], w[2], n[2]; };              // per segment: queue (batch id), first work id (fits 32 bits: wf_batch_cap), chunks
+// Under "wf_affinity" (WfSeg::map_samples != 0) a shard's range is LOCAL, [0, wm_shard_size), and its chunks
+// map to (sample, tile) by crt_work_map.h: w is then the first local id of the segment, and gen_chunk_work turns a chunk into
+// its work id.  A wave whose own shards are dry looks at the shards of its own image region (residue modulo 8) first.
+// MAP: some listed queue may be mapped (wf_launch_gen looks); without it the code is the plain ranges' alone.
+struct GenWork { uint32_t q[2], w[2], n[2], sh[2]; };       // per segment: queue (batch id), first work id (fits 32 bits: wf_batch_cap), chunks, shard
+template <bool MAP> __device__ __forceinline__ uint32_t seg_map_samples(const WfParams &P, uint32_t sg) { return MAP ? P.seg[sg].map_samples : 0u; }
+template <bool MAP>
+__device__ __forceinline__ uint32_t seg_shard_size(const WfParams &P, uint32_t sg, uint32_t shard)
+{
+    const uint32_t ms = seg_map_samples<MAP>(P, sg);
+    if (ms) return wm_shard_size(ms, P.npix_padded >> 6, shard);
+    const uint32_t wps = P.seg[sg].work_per_shard;
+    const unsigned long long wtot = P.seg[sg].work_total, lo = (unsigned long long)shard * wps;
+    return lo < wtot ? (uint32_t)min((unsigned long long)wps, wtot - lo) : 0u;
+}
+// the work id of lane 0 of chunk kk of segment g
+template <bool MAP>
+__device__ __forceinline__ uint32_t gen_chunk_work(const WfParams &P, const GenWork &G, uint32_t g, uint32_t kk)
+{
+    const uint32_t ms = seg_map_samples<MAP>(P, G.q[g]);
+    if (ms == 0u) return G.w[g] + 64u * kk;
+    const WmChunk c = wm_chunk(ms, P.npix_padded >> 6, G.sh[g], (G.w[g] >> 6) + kk);
+    return c.sample * P.npix_padded + c.tile * 64u;
+}
+template <bool MAP>
 __device__ __forceinline__ uint32_t gen_reserve(const WfParams &P, uint32_t my_shard, uint32_t lane, uint32_t want, GenWork &G)
 {
-    G.q[0] = G.q[1] = 0; G.w[0] = G.w[1] = 0; G.n[0] = G.n[1] = 0;
+    G.q[0] = G.q[1] = 0; G.w[0] = G.w[1] = 0; G.n[0] = G.n[1] = 0; G.sh[0] = G.sh[1] = 0;
     uint32_t nseg = 0;
     for (uint32_t si = 0; si < P.seg_n && want > 0u && nseg < 2u; si++) {
         const uint32_t sg = P.seg_order[si];
         WfWorkQ *wq = P.wq + sg;
-        const uint32_t wps = P.seg[sg].work_per_shard;
-        const unsigned long long wtot = P.seg[sg].work_total, lo = (unsigned long long)my_shard * wps;
-        const uint32_t size = lo < wtot ? (uint32_t)min((unsigned long long)wps, wtot - lo) : 0u;
+        const uint32_t size = seg_shard_size<MAP>(P, sg, my_shard);
+        const uint32_t lo = seg_map_samples<MAP>(P, sg) ? 0u : my_shard * P.seg[sg].work_per_shard;
         // (one uniform load of the cursor: no atomic on a shard that is already dry)
         if (__hip_atomic_load(&wq->work[my_shard].cur, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= size) continue;
         uint32_t base = 0;
@@ -828,21 +852,25 @@ __device__ __forceinline__ uint32_t gen_reserve(const WfParams &P, uint32_t my_s
         base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
         if (base >= size) continue;
         const uint32_t got = min(want, (size - base) / 64u);
-        G.q[nseg] = sg; G.w[nseg] = (uint32_t)lo + base; G.n[nseg] = got; nseg++;
+        G.q[nseg] = sg; G.w[nseg] = lo + base; G.n[nseg] = got; G.sh[nseg] = my_shard; nseg++;
         want -= got;
     }
     for (uint32_t si = 0; si < P.seg_n && nseg == 0u; si++) {            // every shard of every listed queue, one try each
         const uint32_t sg = P.seg_order[si];
         WfWorkQ *wq = P.wq + sg;
         if (__hip_atomic_load(&wq->work_done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) continue;
+        const bool mapped = seg_map_samples<MAP>(P, sg) != 0u;
         const uint32_t wps = P.seg[sg].work_per_shard;
-        const unsigned long long wtot = P.seg[sg].work_total, lo_l = (unsigned long long)lane * wps;
-        const uint32_t size_l = lo_l < wtot ? (uint32_t)min((unsigned long long)wps, wtot - lo_l) : 0u;
+        const uint32_t size_l = seg_shard_size<MAP>(P, sg, lane);
         const uint32_t cur_l = __hip_atomic_load(&wq->work[lane].cur, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const unsigned long long avail = __ballot(cur_l < size_l);
+        unsigned long long avail = __ballot(cur_l < size_l);
         if (!avail) {                                                    // every shard is exhausted
             if (lane == 0) __hip_atomic_store(&wq->work_done, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             continue;
+        }
+        if (mapped) {                                                    // the other sample groups of this wave's region first
+            const unsigned long long own = avail & (0x0101010101010101ull << (my_shard & 7u));
+            if (own) avail = own;
         }
         const uint32_t rot = my_shard & 63u;
         const unsigned long long rmask = rot ? ((avail >> rot) | (avail << (64u - rot))) : avail;
@@ -853,7 +881,7 @@ __device__ __forceinline__ uint32_t gen_reserve(const WfParams &P, uint32_t my_s
         const uint32_t size_s = (uint32_t)__shfl((int)size_l, (int)s_pick, 64);
         if (base >= size_s) continue;
         const uint32_t got = min(want, (size_s - base) / 64u);
-        G.q[0] = sg; G.w[0] = s_pick * wps + base; G.n[0] = got; nseg = 1;
+        G.q[0] = sg; G.w[0] = (mapped ? 0u : s_pick * wps) + base; G.n[0] = got; G.sh[0] = s_pick; nseg = 1;
         want -= got;
     }
     return G.n[0] + G.n[1];
@@ -910,10 +938,11 @@ __device__ __forceinline__ bool root_step_misses(const v4u Q0, const v4u Q1, con
 // counters): they differ in when list positions are known, and the form without the cull keeps its one atomic per wave and
 // its 45 VGPRs.  A change to the slot word or the record layout is made in BOTH loops; tests/test_gen_cull_gpu.py compares
 // their images and counters.
-template <bool COUNT, bool ADAPT, bool CULL>
+template <bool COUNT, bool ADAPT, bool CULL, bool MAP>
 __global__ __launch_bounds__(64) void k_wf_gen(const WfParams P, uint32_t it, const AsTiles A)
 {
     static_assert(!(ADAPT && CULL), "the adaptive instantiation does not cull");
+    static_assert(!(ADAPT && MAP), "the adaptive queues keep the plain ranges");
     const DevScene &S = P.sc;
     const uint32_t ring = it & 3u, lbuf = it & 1u;
     WfCtl *ctl = P.ctl;
@@ -936,8 +965,9 @@ __global__ __launch_bounds__(64) void k_wf_gen(const WfParams P, uint32_t it, co
         uint32_t slot = 0, slot_of = 0xFFFFFFFFu;                        // the dead slots of chunk j + slot_of * gen_blocks
         uint32_t started = 0, started_q = 0;                             // paths started and not yet added to alive[started_q]
         uint32_t c_rays = 0, c_cull = 0;
-        // the classes of 16 consecutive tiles (consecutive chunks of a segment are consecutive tiles): a
-        // scalar load from the constant address space, like the root node -- the table is written before the run
+        // the classes of 16 consecutive tiles (consecutive chunks of a segment are consecutive tiles, or,
+        // under MAP, S_g chunks of one tile and then the next: the word is kept by tile >> 4 either way): a scalar load
+        // from the constant address space, like the root node -- the table is written before the run
         typedef const __attribute__((address_space(4))) uint32_t *cptr1u;
         const cptr1u tile_cls = (cptr1u)P.tile_cls;
         uint32_t cls_word = 0, cls_word_of = 0xFFFFFFFFu;
@@ -955,12 +985,12 @@ __global__ __launch_bounds__(64) void k_wf_gen(const WfParams P, uint32_t it, co
         };
         for (uint32_t round = 0; round < (uint32_t)CRT_WF_GEN_ROUNDS && filled < mine; round++) {
             GenWork G;
-            const uint32_t total = gen_reserve(P, my_shard, lane, mine - filled, G);
+            const uint32_t total = gen_reserve<MAP>(P, my_shard, lane, mine - filled, G);
             if (total == 0u) break;                                      // no work anywhere: the slots stay dead
             for (uint32_t k = 0; k < total; k++) {
                 const uint32_t g = k < G.n[0] ? 0u : 1u, kk = g ? k - G.n[0] : k;
                 const uint32_t sg = G.q[g];
-                const uint32_t w0 = G.w[g] + 64u * kk;
+                const uint32_t w0 = gen_chunk_work<MAP>(P, G, g, kk);
                 const uint32_t sample_off = w0 / P.npix_padded, pp0 = w0 % P.npix_padded;
                 const uint32_t tile = pp0 >> 6;
                 const uint32_t lx = (tile % P.tiles_x) * 8u + (lane & 7u), ly = (tile / P.tiles_x) * 8u + (lane >> 3);
@@ -1039,7 +1069,7 @@ __global__ __launch_bounds__(64) void k_wf_gen(const WfParams P, uint32_t it, co
         return;
     }
     GenWork G;
-    const uint32_t total = gen_reserve(P, my_shard, lane, mine, G);
+    const uint32_t total = gen_reserve<MAP>(P, my_shard, lane, mine, G);
     if (total == 0u) return;                                             // no work anywhere: the slots stay dead
     // ---- list positions of the whole wave's camera rays: one atomic.  Every item of an 8x8 tile inside the frame
     //      yields a path; an item outside a ragged tile is consumed without one (its slot stays dead).
@@ -1049,7 +1079,7 @@ __global__ __launch_bounds__(64) void k_wf_gen(const WfParams P, uint32_t it, co
         for (uint32_t g = 0; g < 2u; g++) {
             n_valid[g] = 0;
             for (uint32_t k = 0; k < G.n[g]; k++) {
-                const uint32_t tile = ADAPT ? wf_as_tile(A, G.w[g] + 64u * k) : ((G.w[g] + 64u * k) % P.npix_padded) >> 6;
+                const uint32_t tile = ADAPT ? wf_as_tile(A, G.w[g] + 64u * k) : (gen_chunk_work<MAP>(P, G, g, k) % P.npix_padded) >> 6;
                 const uint32_t lx = (tile % P.tiles_x) * 8u + (lane & 7u), ly = (tile / P.tiles_x) * 8u + (lane >> 3);
                 n_valid[g] += (uint32_t)__popcll(__ballot(lx < P.tw && ly < P.th));
             }
@@ -1068,7 +1098,7 @@ __global__ __launch_bounds__(64) void k_wf_gen(const WfParams P, uint32_t it, co
     for (uint32_t k = 0; k < total; k++) {
         const uint32_t g = k < G.n[0] ? 0u : 1u, kk = g ? k - G.n[0] : k;
         const uint32_t sg = G.q[g];
-        const uint32_t w0 = G.w[g] + 64u * kk;
+        const uint32_t w0 = gen_chunk_work<MAP>(P, G, g, kk);
         uint32_t sample_off = w0 / P.npix_padded, pp0 = w0 % P.npix_padded;
         if (ADAPT) {                                                     // the full-frame position of the active tile's chunk
             sample_off = w0 / (A.n_active * 64u);
@@ -1153,6 +1183,23 @@ __device__ __forceinline__ int stack_pop(const int *stk, const int *ovf, size_t 
     return v;
 }
 
+// Option "wf_affinity" (DESIGN.md 5.11): ray-list shard s holds the rays of paths born in image region s mod 8 (k_wf_gen fills
+// a shard's slots from the work shard of the same number, crt_work_map.h, and a slot never changes shard).  A traversal wave
+// reads the id of the XCD it runs on (HW_REG_XCC_ID, bits 3:0) and starts on a shard of that residue -- the same shard as
+// blockIdx.x % kWfShards wherever workgroups go round the XCDs in turn -- and, when it moves on, prefers that residue:
+// one XCD's L2 then sees one region's rays.  Placement only: a wave still takes any shard that holds rays.
+__device__ __forceinline__ uint32_t wf_xcc_id() { return (uint32_t)__builtin_amdgcn_s_getreg((3 << 11) | (0 << 6) | 20) & 7u; }
+__device__ __forceinline__ uint32_t wf_home_shard(const WfParams &P)
+{
+    return P.affinity ? wf_xcc_id() + 8u * ((blockIdx.x >> 3) & 7u) : blockIdx.x % kWfShards;
+}
+// the shards a moving wave looks at first: those of its home residue that hold rays, if any
+__device__ __forceinline__ unsigned long long wf_prefer_home(const WfParams &P, unsigned long long avail, uint32_t home)
+{
+    const unsigned long long own = avail & (0x0101010101010101ull << (home & 7u));
+    return P.affinity && own ? own : avail;
+}
+
 // Persistent waves.  A wave owns a chunk of one shard's ray list at a time; entry i of a shard:
 // entries of the four class lists in order (camera rays, bounce rays, shadow rays of camera hits, shadow rays).
 // Traversal is "while-while": a bounded run of inner-node steps (lanes that reach a leaf wait,
@@ -1191,7 +1238,8 @@ __global__ __launch_bounds__(64, CRT_WF_MIN_WAVES) void k_wf_trace(const WfParam
     const float t_min = 0.001f;
 
     // wave-uniform fetch state: current shard, its ext count, the reserved chunk [pos,end)
-    uint32_t cur_shard = blockIdx.x % kWfShards, sh_e0 = 0, sh_e1 = 0, sh_e2 = 0, sh_total = 0;   // class end offsets
+    const uint32_t home = wf_home_shard(P);
+    uint32_t cur_shard = home, sh_e0 = 0, sh_e1 = 0, sh_e2 = 0, sh_total = 0;   // class end offsets
     uint32_t chunk_pos = 0, chunk_end = 0;
     bool have_shard = false, exhausted = false;
     {   // start on this block's own shard (its counts are final: written by k_wf_shade); scan only when it is dry
@@ -1235,7 +1283,8 @@ __global__ __launch_bounds__(64, CRT_WF_MIN_WAVES) void k_wf_trace(const WfParam
                 const unsigned long long avail = __ballot(cur_l < tot);
                 if (!avail) { exhausted = true; break; }
                 const uint32_t rot = cur_shard & 63u;
-                const unsigned long long rmask = rot ? ((avail >> rot) | (avail << (64u - rot))) : avail;
+                const unsigned long long pick = wf_prefer_home(P, avail, home);
+                const unsigned long long rmask = rot ? ((pick >> rot) | (pick << (64u - rot))) : pick;
                 cur_shard = ((uint32_t)(__ffsll((long long)rmask) - 1) + rot) & 63u;
                 sh_e0 = __shfl(e0, (int)cur_shard, 64); sh_e1 = __shfl(e1, (int)cur_shard, 64);
                 sh_e2 = __shfl(e2, (int)cur_shard, 64); sh_total = __shfl(tot, (int)cur_shard, 64);
@@ -1609,7 +1658,8 @@ __global__ __launch_bounds__(64, CRT_WF_T2_WAVES) void k_wf_trace2(const WfParam
     const float t_min = 0.001f;
 
     // wave-uniform fetch state: current shard, its class end offsets, the reserved chunk [pos,end), the ring [head, head+n)
-    uint32_t cur_shard = blockIdx.x % kWfShards, sh_e0 = 0, sh_e1 = 0, sh_e2 = 0, sh_total = 0;
+    const uint32_t home = wf_home_shard(P);
+    uint32_t cur_shard = home, sh_e0 = 0, sh_e1 = 0, sh_e2 = 0, sh_total = 0;
     uint32_t chunk_pos = 0, chunk_end = 0, ring_head = 0, ring_n = 0;
     bool have_shard = false, exhausted = false;
     {
@@ -1650,7 +1700,8 @@ __global__ __launch_bounds__(64, CRT_WF_T2_WAVES) void k_wf_trace2(const WfParam
                     const unsigned long long avail = __ballot(cur_l < tot);
                     if (!avail) { exhausted = true; break; }
                     const uint32_t rot = cur_shard & 63u;
-                    const unsigned long long rmask = rot ? ((avail >> rot) | (avail << (64u - rot))) : avail;
+                    const unsigned long long pick = wf_prefer_home(P, avail, home);
+                    const unsigned long long rmask = rot ? ((pick >> rot) | (pick << (64u - rot))) : pick;
                     cur_shard = ((uint32_t)(__ffsll((long long)rmask) - 1) + rot) & 63u;
                     sh_e0 = __shfl(e0, (int)cur_shard, 64); sh_e1 = __shfl(e1, (int)cur_shard, 64);
                     sh_e2 = __shfl(e2, (int)cur_shard, 64); sh_total = __shfl(tot, (int)cur_shard, 64);
@@ -2105,6 +2156,8 @@ __global__ void k_wf_init(const WfParams P)
                 P.wq[P.batch_id].work_done = 0;
                 P.wq[P.batch_id].work_per_shard = P.seg[P.batch_id].work_per_shard;
                 P.wq[P.batch_id].work_total = P.seg[P.batch_id].work_total;
+                P.wq[P.batch_id].map_samples = P.seg[P.batch_id].map_samples;
+                P.wq[P.batch_id].map_tiles = P.npix_padded >> 6;
             }
         }
     }
@@ -2154,22 +2207,42 @@ bool wf_gen_culls(const WfParams &P)
     return P.cull_miss != 0u && (k == 1 || k == 3) && P.sc.nprim > 4u && P.sc.root4 >= 0 && P.sc.root4 != kNoNode;
 }
 
+// Does a k_wf_gen launch with these parameters take a MAP instantiation: is a listed queue's work region-major (option
+// "wf_affinity")?  The adaptive queues never are.
+bool wf_gen_mapped(const WfParams &P)
+{
+    bool mapped = false;
+    for (uint32_t k = 0; k < P.seg_n && k < kWfRing; k++) mapped = mapped || P.seg[P.seg_order[k]].map_samples != 0u;
+    return mapped;
+}
+
 hipError_t wf_launch_gen(const WfParams &P, uint32_t it, hipStream_t s, const AsTiles *A)
 {
     if (P.gen_blocks == 0u) return hipErrorInvalidValue;
     const dim3 gs(kWfShards * P.gen_blocks), bs(64);
     if (A) {                                                     // adaptive batches
-        if (P.count) hipLaunchKernelGGL((k_wf_gen<true, true, false>), gs, bs, 0, s, P, it, *A);
-        else hipLaunchKernelGGL((k_wf_gen<false, true, false>), gs, bs, 0, s, P, it, *A);
+        if (P.count) hipLaunchKernelGGL((k_wf_gen<true, true, false, false>), gs, bs, 0, s, P, it, *A);
+        else hipLaunchKernelGGL((k_wf_gen<false, true, false, false>), gs, bs, 0, s, P, it, *A);
         return hipGetLastError();
     }
+    const bool mapped = wf_gen_mapped(P);
     if (wf_gen_culls(P)) {
-        if (P.count) hipLaunchKernelGGL((k_wf_gen<true, false, true>), gs, bs, 0, s, P, it, AsTiles{});
-        else hipLaunchKernelGGL((k_wf_gen<false, false, true>), gs, bs, 0, s, P, it, AsTiles{});
+        if (mapped) {
+            if (P.count) hipLaunchKernelGGL((k_wf_gen<true, false, true, true>), gs, bs, 0, s, P, it, AsTiles{});
+            else hipLaunchKernelGGL((k_wf_gen<false, false, true, true>), gs, bs, 0, s, P, it, AsTiles{});
+        } else {
+            if (P.count) hipLaunchKernelGGL((k_wf_gen<true, false, true, false>), gs, bs, 0, s, P, it, AsTiles{});
+            else hipLaunchKernelGGL((k_wf_gen<false, false, true, false>), gs, bs, 0, s, P, it, AsTiles{});
+        }
         return hipGetLastError();
     }
-    if (P.count) hipLaunchKernelGGL((k_wf_gen<true, false, false>), gs, bs, 0, s, P, it, AsTiles{});
-    else hipLaunchKernelGGL((k_wf_gen<false, false, false>), gs, bs, 0, s, P, it, AsTiles{});
+    if (mapped) {
+        if (P.count) hipLaunchKernelGGL((k_wf_gen<true, false, false, true>), gs, bs, 0, s, P, it, AsTiles{});
+        else hipLaunchKernelGGL((k_wf_gen<false, false, false, true>), gs, bs, 0, s, P, it, AsTiles{});
+    } else {
+        if (P.count) hipLaunchKernelGGL((k_wf_gen<true, false, false, false>), gs, bs, 0, s, P, it, AsTiles{});
+        else hipLaunchKernelGGL((k_wf_gen<false, false, false, false>), gs, bs, 0, s, P, it, AsTiles{});
+    }
     return hipGetLastError();
 }
 

@@ -43,6 +43,7 @@ WfOptions wf_options(const crt_ctx *c)
     o.wf_pool = c->wf_pool; o.wf_waves_per_cu = c->wf_waves_per_cu; o.spp_per_launch = c->spp_per_launch;
     o.wf_pool_spp = c->wf_pool_spp; o.wf_ring = c->wf_ring; o.wf_pipes = c->wf_pipes; o.wf_trace_form = c->wf_trace_form;
     o.wf_cohort = c->wf_cohort; o.wf_chunk = c->wf_chunk; o.wf_tail_walk = c->wf_tail_walk; o.wf_gen_blocks = c->wf_gen_blocks;
+    o.wf_affinity = c->wf_affinity;
     o.wf_finish_at = c->wf_finish_at; o.wf_flush_at = c->wf_flush_at; o.wf_feed = c->wf_feed;
     o.quant4_tree = c->bvh4q.ok && !c->bvh8q.ok;
     return o;
@@ -207,7 +208,11 @@ static int wf_enqueue(crt_ctx *c, int p, uint32_t iters)
         HIPCHK(c, wf_launch_shade(W, pp.it, stream));
         if (pp.it > pp.it_first) HIPCHK(c, hipEventRecord(c->ev_status[p][(pp.it - 1u) % kStatusRing], stream));   // (blocking waits fall back on it)
         pp.st_counted[pp.it % kStatusRing] = W.count_alive != 0;
-        if (W.rearm) { HIPCHK(c, wf_launch_gen(W, pp.it, stream, r.as.active ? &r.as : nullptr)); c->last_launches++; }
+        if (W.rearm) {
+            HIPCHK(c, wf_launch_gen(W, pp.it, stream, r.as.active ? &r.as : nullptr));
+            c->last_launches++;
+            if (!r.as.active && wf_gen_mapped(W)) c->mapped_gen_launches++;
+        }
         if (pp.evict_next) {                                     // k_wf_finish may start once this launch is through
             for (WfBatch &b : r.open)
                 if ((pp.evict_next >> b.id) & 1u) {
@@ -742,6 +747,8 @@ int wf_trace_batch(crt_ctx *c, uint32_t n, const AsBatch *as)
     if (g.npix == 0 || n == 0) { int rc = wf_flush(c); if (!as) c->published += n; return rc; }
     unsigned long long work_total = g.work_total;
     uint32_t work_per_shard = g.work_per_shard;
+    // region-major shards (option "wf_affinity", read here: DESIGN.md 5.11); the adaptive queues keep the plain ranges
+    const uint32_t map_samples = as ? 0u : g.map_samples;
     if (as) {
         work_total = (unsigned long long)n * as->n_active * 64u;
         work_per_shard = (uint32_t)(((work_total + kWfShards - 1) / kWfShards + 63u) & ~63ull);
@@ -803,7 +810,7 @@ int wf_trace_batch(crt_ctx *c, uint32_t n, const AsBatch *as)
             for (uint32_t b = 0; b < kWfRing; b++) {
                 W.staging[b] = c->w_staging[b < r.ring ? b : 0].p;
                 W.side_base[b] = (b * (uint32_t)crt_ctx::kMaxPipes + (uint32_t)p) * kWfSideCap;
-                W.seg[b] = WfSeg{0, 64, 0};
+                W.seg[b] = WfSeg{0, 64, 0, 0, 0};
                 W.seg_order[b] = 0;
             }
             W.batch_id = 0; W.count_alive = 0; W.keep_pool = 0; W.evict_mask = 0; W.status_out = nullptr;
@@ -813,7 +820,8 @@ int wf_trace_batch(crt_ctx *c, uint32_t n, const AsBatch *as)
             W.band = c->band; W.stride = c->stride; W.phase = c->phase;
             W.tiles_x = g.tiles_x; W.tiles_y = g.tiles_y; W.npix_padded = g.npix_padded;
             W.list_cap = g.list_cap;
-            W.seg[0] = WfSeg{work_total, work_per_shard, first_sample};
+            W.seg[0] = WfSeg{work_total, work_per_shard, first_sample, map_samples, 0u};
+            W.affinity = map_samples ? 1u : 0u;
             W.seg_n = 1;
             W.n_samples = n;
             W.accum = accum_ptr(c); W.rgba = rgba_ptr(c);
@@ -871,7 +879,8 @@ int wf_trace_batch(crt_ctx *c, uint32_t n, const AsBatch *as)
             WfPipeView &pp = r.pipes[p];
             WfParams &W = r.W[p];
             nb.from_it[p] = 0xFFFFFFFFu;                         // (set when the host sees the queue reset complete: wf_check_ready)
-            W.seg[id] = WfSeg{work_total, work_per_shard, first_sample};
+            W.seg[id] = WfSeg{work_total, work_per_shard, first_sample, map_samples, 0u};
+            W.affinity = map_samples ? 1u : 0u;                  // (the traversal waves follow the newest batch's setting)
             W.n_samples = n;
             W.batch_id = id; W.keep_pool = 1;
             pp.tail_bound = 0; pp.blocks_now = r.trace_blocks;

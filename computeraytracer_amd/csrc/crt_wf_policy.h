@@ -22,6 +22,7 @@ struct WfOptions {
     uint32_t tw = 0, th = 0;        // the tile
     uint32_t wf_pool = 0, wf_waves_per_cu = 0, spp_per_launch = 0;   // 0 = auto
     int wf_pool_spp = 8, wf_ring = 32, wf_pipes = 2, wf_trace_form = 2, wf_cohort = 16, wf_chunk = 1, wf_tail_walk = 1, wf_gen_blocks = 128;
+    int wf_affinity = 0;            // region-major work shards (crt_work_map.h)
     uint32_t wf_finish_at = 32768, wf_flush_at = 4096;
     double wf_feed = 1.0;
     bool quant4_tree = false;       // the walked tree is the quantised 4-wide one (bvh4q.ok && !bvh8q.ok)
@@ -94,6 +95,7 @@ inline uint32_t wf_gen_blocks(const WfOptions &o, uint32_t list_cap) { return st
 
 struct WfConfig {
     uint32_t tiles_x, tiles_y, npix_padded, P, Pp, list_cap, work_per_shard;
+    uint32_t map_samples;           // WfSeg::map_samples: n under "wf_affinity" (the shards' sizes are then wm_shard_size's), else 0
     int K;
     unsigned long long work_total;
     size_t npix, list_per_pipe;
@@ -130,6 +132,7 @@ inline WfConfig wf_config(const WfOptions &o, uint32_t n)
     g.list_cap = ((Pp / 64u + kWfShards - 1) / kWfShards) * 64u + 256u;
     g.work_per_shard = (uint32_t)((g.work_total + kWfShards - 1) / kWfShards);
     g.work_per_shard = (g.work_per_shard + 63u) & ~63u;
+    g.map_samples = o.wf_affinity ? n : 0u;
     g.list_per_pipe = (size_t)8 * g.list_cap * kWfShards;                 // [2 parities][4 classes]
     return g;
 }

@@ -736,6 +736,13 @@ class Renderer:
         self._chk(self._lib.crt_debug_tile_class_setups(self._h, C.byref(n)))
         return int(n.value)
 
+    def mapped_gen_launches(self) -> int:
+        """Generate launches of this context that handed out region-major work so far (option "wf_affinity",
+        crt_debug_mapped_gen_launches)."""
+        n = C.c_uint64()
+        self._chk(self._lib.crt_debug_mapped_gen_launches(self._h, C.byref(n)))
+        return int(n.value)
+
     def debug_math(self, fn: int, a, b=None) -> np.ndarray:
         a = np.ascontiguousarray(a, np.float32)
         b = np.ascontiguousarray(b if b is not None else np.zeros_like(a), np.float32)

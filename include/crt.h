@@ -752,7 +752,11 @@ int crt_last_kernel_ms(crt_ctx *ctx, float *ms, uint32_t *launches);
  * per sample; same image, counters and launches either way); "wf_defer_nee" (1, default: a path that
  * Russian roulette ends while its NEE shadow ray is pending finishes in that shade step and frees its slot, the term is
  * added by the next shade launch; 0: the slot is held one more iteration; same image and counters either way, fewer
- * launches with 1); "frame_ring" = F (keep the
+ * launches with 1); "wf_affinity" (0, default: a shard of a batch's work queue is a contiguous range of
+ * work ids; 1: the 64 shards are region-major -- shard 8 g + k hands out the tiles of image region k for the samples
+ * congruent to g modulo 8 -- and a traversal wave starts on the ray lists of its own XCD's region; read when a batch is
+ * published, adaptive batches always take 0; same image and counters either way; measured on the benchmarked frame: a
+ * higher L2 hit rate and no gain in time); "frame_ring" = F (keep the
  * rgba8 frame of each of the last F samples for crt_read_sample_rgba8; 0 = off);
  * "temporal_motion" (0 | 1, anything else is CRT_EINVAL: 1 keeps the history of crt_denoise_temporal across
  * crt_update_primitives, see "Temporal reuse"; costs 80 bytes per primitive on the device once an edit has happened);
@@ -879,6 +883,10 @@ int crt_debug_tile_classes_host(crt_ctx *ctx, uint8_t *out, size_t n_tiles);
  * count).  It stays where it is wherever the classes do nothing: "wf_cull_classes" or "wf_cull_miss" 0, adaptive batches,
  * the 8-wide or unquantised tree, four primitives or fewer.  No sync, nothing is finished. */
 int crt_debug_tile_class_setups(crt_ctx *ctx, uint64_t *out);
+/* Test hook: how many k_wf_gen launches of this context have handed out region-major work so far (option "wf_affinity",
+ * the launches that listed a queue published with the option on).  It stays where it is with the option
+ * off and for adaptive batches.  No sync, nothing is finished. */
+int crt_debug_mapped_gen_launches(crt_ctx *ctx, uint64_t *out);
 
 #ifdef __cplusplus
 }
