@@ -593,6 +593,72 @@ static napi_value js_denoise(napi_env env, napi_callback_info info)
     return denoise_result(env, &out, NULL);
 }
 
+/* denoiseLatest(h, {...denoise's options, rgb}) -> {rgba8: Uint8Array(tw*th*4), rgb?: Float32Array(tw*th*4), sample}: denoise
+ * of the newest complete frame without finishing what is in flight (crt_denoise_latest); `sample` is the index of the frame
+ * shown, and rgb: true adds the linear rgb.  Throws (CRT_ESTATE) while no frame is complete yet.
+ * denoiseLatestInto(h, typedArray, {...denoise's options}) -> sample: the rgba8 straight into the caller's (pinned) frame
+ * buffer, as readSampleRgba8Into.  denoiseLatestAsync(h, {...}) -> Promise of the object (below). */
+static napi_value denoise_latest_result(napi_env env, size_t px, napi_value rgba8_ab, napi_value rgb_ab, uint32_t sample)
+{
+    napi_value ta, obj, v;
+    NAPI_OK(env, napi_create_object(env, &obj));
+    NAPI_OK(env, napi_create_typedarray(env, napi_uint8_array, px * 4, rgba8_ab, 0, &ta));
+    NAPI_OK(env, napi_set_named_property(env, obj, "rgba8", ta));
+    if (rgb_ab) {
+        NAPI_OK(env, napi_create_typedarray(env, napi_float32_array, px * 4, rgb_ab, 0, &ta));
+        NAPI_OK(env, napi_set_named_property(env, obj, "rgb", ta));
+    }
+    NAPI_OK(env, napi_create_uint32(env, sample, &v));
+    NAPI_OK(env, napi_set_named_property(env, obj, "sample", v));
+    return obj;
+}
+
+static int denoise_latest_options(napi_env env, const char *fn, napi_value opts, int have_opts, crt_denoise_params *p, bool *rgb)
+{
+    double it = 5.0, sc = 1.0, sn = 0.5, sx = 0.3;
+    const dn_opt o[] = {{"iterations", &it}, {"sigmaColor", &sc}, {"sigmaNormal", &sn}, {"sigmaPlane", &sx}};
+    if (!denoise_options(env, fn, opts, have_opts, o, 4, rgb ? "rgb" : NULL, rgb)) return 0;
+    p->iterations = (uint32_t)it; p->sigma_color = (float)sc; p->sigma_normal = (float)sn; p->sigma_plane = (float)sx;
+    return 1;
+}
+
+static napi_value js_denoise_latest(napi_env env, napi_callback_info info)
+{
+    DENOISE_ARGS
+    crt_denoise_params p;
+    bool rgb = false;
+    if (!denoise_latest_options(env, "denoiseLatest", argc > 1 ? argv[1] : NULL, argc > 1, &p, &rgb)) return NULL;
+    dn_out out;
+    if (!denoise_outputs(env, ctx, false, &out)) return NULL;
+    void *lin = NULL;
+    napi_value lin_ab = NULL;
+    if (rgb && napi_create_arraybuffer(env, out.px * 16, &lin, &lin_ab) != napi_ok) { napi_throw_error(env, NULL, "out of memory"); return NULL; }
+    uint32_t smp = 0;
+    CRT_CHECK(env, ctx, "crt_denoise_latest", crt_denoise_latest(ctx, &p, (float *)lin, (uint8_t *)out.rgba8, &smp));
+    return denoise_latest_result(env, out.px, out.rgba8_ab, lin_ab, smp);
+}
+
+static napi_value js_denoise_latest_into(napi_env env, napi_callback_info info)
+{
+    size_t argc = 3;
+    napi_value argv[3];
+    NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    if (argc < 2) { napi_throw_type_error(env, NULL, "too few arguments"); return NULL; }
+    crt_ctx *ctx = get_ctx(env, argv[0]);
+    if (!ctx) return NULL;
+    uint32_t t[4], smp = 0;
+    void *dst; size_t n;
+    crt_denoise_params p;
+    if (!get_bytes(env, argv[1], &dst, &n)) { napi_throw_type_error(env, NULL, "denoiseLatestInto: typed array expected"); return NULL; }
+    if (!denoise_latest_options(env, "denoiseLatestInto", argc > 2 ? argv[2] : NULL, argc > 2, &p, NULL)) return NULL;
+    CRT_CHECK(env, ctx, "crt_tile", crt_tile(ctx, t));
+    if (n < (size_t)t[2] * t[3] * 4) { napi_throw_range_error(env, NULL, "denoiseLatestInto: need tw*th*4 bytes"); return NULL; }
+    CRT_CHECK(env, ctx, "crt_denoise_latest", crt_denoise_latest(ctx, &p, NULL, (uint8_t *)dst, &smp));
+    napi_value out;
+    NAPI_OK(env, napi_create_uint32(env, smp, &out));
+    return out;
+}
+
 /* denoiseAdaptive(h, {iterations, sigmaVariance, sigmaNormal, sigmaPlane, variance}) -> Uint8Array (tw*th*4 rgba8), or
  * with variance: true -> {rgba8, variance: Float32Array(tw*th)}: the variance-guided filter of an adaptive render
  * (include/crt.h "Denoised preview of an adaptive render").  A missing option takes the library's default
@@ -1260,7 +1326,7 @@ static napi_value js_set_stream(napi_env env, napi_callback_info info)
  * GPU either.  Jobs of one context run in call order. */
 enum { JOB_TRACE, JOB_SYNC, JOB_READ_RGBA8, JOB_READ_ACCUM, JOB_GATHER, JOB_READ_FRAME_RGBA8, JOB_READ_FRAME_ACCUM, JOB_READ_SAMPLE_RGBA8,
        JOB_DENOISE_ADAPTIVE, JOB_DENOISE_TEMPORAL, JOB_DENOISE_SVGF, JOB_TRANSFORM_PRIMITIVES, JOB_READ_PRIMITIVES,
-       JOB_DENOISE_FRAME, JOB_DENOISE_ADAPTIVE_FRAME, JOB_REMOVE_PRIMITIVES, JOB_APPEND_PRIMITIVES };
+       JOB_DENOISE_FRAME, JOB_DENOISE_ADAPTIVE_FRAME, JOB_REMOVE_PRIMITIVES, JOB_APPEND_PRIMITIVES, JOB_DENOISE_LATEST };
 typedef struct job {
     napi_async_work work;
     napi_deferred deferred;
@@ -1268,7 +1334,10 @@ typedef struct job {
     int op, rc;
     uint32_t n, px;
     crt_denoise_adaptive_params dn;     /* JOB_DENOISE_ADAPTIVE, JOB_DENOISE_ADAPTIVE_FRAME */
-    crt_denoise_params df;              /* JOB_DENOISE_FRAME */
+    crt_denoise_params df;              /* JOB_DENOISE_FRAME, JOB_DENOISE_LATEST */
+    uint32_t sample;                    /* JOB_DENOISE_LATEST: the index of the frame shown */
+    void *rgb;                          /* ... and with rgb: true the linear rgb's ArrayBuffer memory (kept alive by rgb_ref) */
+    napi_ref rgb_ref;
     crt_denoise_temporal_params dt;     /* JOB_DENOISE_TEMPORAL */
     crt_denoise_svgf_params ds;         /* JOB_DENOISE_SVGF */
     crt_prim_transform *ops;            /* JOB_TRANSFORM_PRIMITIVES: the job's own copy of the n ops */
@@ -1296,6 +1365,7 @@ static void job_execute(napi_env env, void *data)
     case JOB_READ_SAMPLE_RGBA8: j->rc = crt_read_sample_rgba8(ctx, j->n, (uint8_t *)j->data); break;
     case JOB_DENOISE_ADAPTIVE: j->rc = crt_denoise_adaptive(ctx, &j->dn, NULL, (uint8_t *)j->data, NULL); break;
     case JOB_DENOISE_FRAME: j->rc = crt_denoise_frame(ctx, &j->df, NULL, (uint8_t *)j->data); break;
+    case JOB_DENOISE_LATEST: j->rc = crt_denoise_latest(ctx, &j->df, (float *)j->rgb, (uint8_t *)j->data, &j->sample); break;
     case JOB_DENOISE_ADAPTIVE_FRAME: j->rc = crt_denoise_adaptive_frame(ctx, &j->dn, NULL, (uint8_t *)j->data, NULL); break;
     case JOB_DENOISE_TEMPORAL: j->rc = crt_denoise_temporal(ctx, &j->dt, NULL, (uint8_t *)j->data, NULL); break;
     case JOB_DENOISE_SVGF: j->rc = crt_denoise_svgf(ctx, &j->ds, NULL, (uint8_t *)j->data, NULL, NULL); break;
@@ -1324,7 +1394,12 @@ static void job_complete(napi_env env, napi_status status, void *data)
                                j->op == JOB_DENOISE_ADAPTIVE || j->op == JOB_DENOISE_TEMPORAL || j->op == JOB_DENOISE_SVGF ||
                                j->op == JOB_DENOISE_FRAME || j->op == JOB_DENOISE_ADAPTIVE_FRAME;
             if (napi_get_reference_value(env, j->ab_ref, &ab) == napi_ok) {
-                if (j->op == JOB_READ_PRIMITIVES) napi_create_typedarray(env, napi_uint8_array, (size_t)j->n * 80, ab, 0, &result);
+                napi_value rgb_ab = NULL;
+                if (j->op == JOB_DENOISE_LATEST) {
+                    if (!j->rgb_ref || napi_get_reference_value(env, j->rgb_ref, &rgb_ab) == napi_ok)
+                        result = denoise_latest_result(env, j->px, ab, rgb_ab, j->sample);
+                }
+                else if (j->op == JOB_READ_PRIMITIVES) napi_create_typedarray(env, napi_uint8_array, (size_t)j->n * 80, ab, 0, &result);
                 else napi_create_typedarray(env, bytes8 ? napi_uint8_array : napi_float32_array, (size_t)j->px * 4, ab, 0, &result);
             }
         }
@@ -1338,6 +1413,7 @@ static void job_complete(napi_env env, napi_status status, void *data)
         napi_reject_deferred(env, j->deferred, errv);
     }
     if (j->ab_ref) napi_delete_reference(env, j->ab_ref);
+    if (j->rgb_ref) napi_delete_reference(env, j->rgb_ref);
     napi_delete_async_work(env, j->work);
     free(j->ops); free(j->edit); free(j->lights);
     /* the next job of this context */
@@ -1360,6 +1436,8 @@ static napi_value start_job(napi_env env, napi_callback_info info, int op)
     job *j = (job *)calloc(1, sizeof *j);
     j->sl = sl; j->op = op;
     if (op == JOB_DENOISE_FRAME && !denoise_plain_options(env, "denoiseFrameAsync", argc > 1 ? argv[1] : NULL, argc > 1, &j->df)) { free(j); return NULL; }
+    bool latest_rgb = false;
+    if (op == JOB_DENOISE_LATEST && !denoise_latest_options(env, "denoiseLatestAsync", argc > 1 ? argv[1] : NULL, argc > 1, &j->df, &latest_rgb)) { free(j); return NULL; }
     if ((op == JOB_DENOISE_ADAPTIVE || op == JOB_DENOISE_ADAPTIVE_FRAME) && !denoise_adaptive_options(env, "denoiseAdaptive", argc > 1 ? argv[1] : NULL, argc > 1, &j->dn, NULL)) { free(j); return NULL; }
     if (op == JOB_DENOISE_TEMPORAL && !denoise_temporal_options(env, argc > 1 ? argv[1] : NULL, argc > 1, &j->dt, NULL)) { free(j); return NULL; }
     if (op == JOB_DENOISE_SVGF && !denoise_svgf_options(env, argc > 1 ? argv[1] : NULL, argc > 1, &j->ds, NULL, NULL)) { free(j); return NULL; }
@@ -1397,7 +1475,8 @@ static napi_value start_job(napi_env env, napi_callback_info info, int op)
             napi_create_reference(env, ab, 1, &j->ab_ref) != napi_ok) { free(j); napi_throw_error(env, NULL, "out of memory"); return NULL; }
     }
     if (op == JOB_READ_RGBA8 || op == JOB_READ_ACCUM || op == JOB_READ_FRAME_RGBA8 || op == JOB_READ_FRAME_ACCUM || op == JOB_READ_SAMPLE_RGBA8 ||
-        op == JOB_DENOISE_ADAPTIVE || op == JOB_DENOISE_TEMPORAL || op == JOB_DENOISE_SVGF || op == JOB_DENOISE_FRAME || op == JOB_DENOISE_ADAPTIVE_FRAME) {
+        op == JOB_DENOISE_ADAPTIVE || op == JOB_DENOISE_TEMPORAL || op == JOB_DENOISE_SVGF || op == JOB_DENOISE_FRAME || op == JOB_DENOISE_ADAPTIVE_FRAME ||
+        op == JOB_DENOISE_LATEST) {
         const int frame = op == JOB_READ_FRAME_RGBA8 || op == JOB_READ_FRAME_ACCUM || op == JOB_DENOISE_FRAME || op == JOB_DENOISE_ADAPTIVE_FRAME;
         const int bytes8 = op != JOB_READ_ACCUM && op != JOB_READ_FRAME_ACCUM;
         uint32_t t[4];
@@ -1407,11 +1486,20 @@ static napi_value start_job(napi_env env, napi_callback_info info, int op)
         napi_value ab;
         if (napi_create_arraybuffer(env, (size_t)j->px * (bytes8 ? 4 : 16), &j->data, &ab) != napi_ok ||
             napi_create_reference(env, ab, 1, &j->ab_ref) != napi_ok) { free(j); napi_throw_error(env, NULL, "out of memory"); return NULL; }
+        if (latest_rgb && (napi_create_arraybuffer(env, (size_t)j->px * 16, &j->rgb, &ab) != napi_ok ||
+                           napi_create_reference(env, ab, 1, &j->rgb_ref) != napi_ok)) {
+            napi_delete_reference(env, j->ab_ref);
+            free(j);
+            napi_throw_error(env, NULL, "out of memory");
+            return NULL;
+        }
     }
     napi_value promise, name;
     if (napi_create_promise(env, &j->deferred, &promise) != napi_ok ||
         napi_create_string_utf8(env, "crt_async", NAPI_AUTO_LENGTH, &name) != napi_ok ||
         napi_create_async_work(env, NULL, name, job_execute, job_complete, j, &j->work) != napi_ok) {
+        if (j->ab_ref) napi_delete_reference(env, j->ab_ref);
+        if (j->rgb_ref) napi_delete_reference(env, j->rgb_ref);
         free(j->ops); free(j->edit); free(j->lights);
         free(j);
         napi_throw_error(env, NULL, "crt_napi: could not create the asynchronous job");
@@ -1423,6 +1511,7 @@ static napi_value start_job(napi_env env, napi_callback_info info, int op)
             sl->self = NULL;
             napi_delete_async_work(env, j->work);
             if (j->ab_ref) napi_delete_reference(env, j->ab_ref);
+            if (j->rgb_ref) napi_delete_reference(env, j->rgb_ref);
             free(j->ops); free(j->edit); free(j->lights);
             free(j);
             napi_throw_error(env, NULL, "crt_napi: could not pin the context handle");
@@ -1443,6 +1532,7 @@ static napi_value js_read_frame_rgba8_async(napi_env env, napi_callback_info inf
 static napi_value js_read_frame_accum_async(napi_env env, napi_callback_info info) { return start_job(env, info, JOB_READ_FRAME_ACCUM); }
 static napi_value js_denoise_adaptive_async(napi_env env, napi_callback_info info) { return start_job(env, info, JOB_DENOISE_ADAPTIVE); }
 static napi_value js_denoise_frame_async(napi_env env, napi_callback_info info) { return start_job(env, info, JOB_DENOISE_FRAME); }
+static napi_value js_denoise_latest_async(napi_env env, napi_callback_info info) { return start_job(env, info, JOB_DENOISE_LATEST); }
 static napi_value js_denoise_adaptive_frame_async(napi_env env, napi_callback_info info) { return start_job(env, info, JOB_DENOISE_ADAPTIVE_FRAME); }
 static napi_value js_denoise_temporal_async(napi_env env, napi_callback_info info) { return start_job(env, info, JOB_DENOISE_TEMPORAL); }
 static napi_value js_denoise_svgf_async(napi_env env, napi_callback_info info) { return start_job(env, info, JOB_DENOISE_SVGF); }
@@ -1479,7 +1569,9 @@ static napi_value init(napi_env env, napi_value exports)
         {"readFrameRgba8", js_read_frame_rgba8}, {"readFrameAccum", js_read_frame_accum}, {"imageSize", js_image_size},
         {"setRowBands", js_set_row_bands}, {"deviceBuffers", js_device_buffers}, {"frameDeviceBuffers", js_frame_device_buffers},
         {"bindOutput", js_bind_output}, {"setStream", js_set_stream},
-        {"denoise", js_denoise}, {"readGbuffer", js_read_gbuffer}, {"readMotion", js_read_motion},
+        {"denoise", js_denoise}, {"denoiseLatest", js_denoise_latest}, {"denoiseLatestInto", js_denoise_latest_into},
+        {"denoiseLatestAsync", js_denoise_latest_async},
+        {"readGbuffer", js_read_gbuffer}, {"readMotion", js_read_motion},
         {"setCamera", js_set_camera}, {"updatePrimitives", js_update_primitives}, {"updateLights", js_update_lights},
         {"refitAccel", js_refit_accel},
         {"transformPrimitives", js_transform_primitives}, {"transformPrimitivesAsync", js_transform_primitives_async},

@@ -64,6 +64,7 @@ SIGNATURES = {
     "crt_comm_destroy": (C.c_int, [_P]),
     "crt_layout_rows": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _P, _P]),
     "crt_denoise": (C.c_int, [_P, _P, _P, _P]),
+    "crt_denoise_latest": (C.c_int, [_P, _P, _P, _P, _P]),
     "crt_read_gbuffer": (C.c_int, [_P, _P]),
     "crt_read_motion": (C.c_int, [_P, _P]),
     "crt_debug_intersect": (C.c_int, [_P, _P, C.c_size_t, _P]),

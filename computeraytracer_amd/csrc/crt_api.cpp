@@ -917,6 +917,11 @@ int crt_set_option(crt_ctx *c, const char *name, int64_t value)
         c->svgf_spatial_pct = (int)value;
         return CRT_OK;
     }
+    if (!std::strcmp(name, "denoise_latest_wave_blocks")) {  // 
+        if (value != 0 && value != 1) return fail(c, CRT_EINVAL, "crt_set_option: denoise_latest_wave_blocks is 0 or 1");
+        c->dn.wave_blocks = value != 0;
+        return CRT_OK;
+    }
     if (!std::strcmp(name, "temporal_clip_pct")) {          // 
         if (value != 0 && (value < 25 || value > 10000)) return fail(c, CRT_EINVAL, "crt_set_option: temporal_clip_pct is 0 (off) or 25..10000");
         if (!value && c->dn.relit) c->dn.drop();               // (history across a light edit is this option's)

@@ -282,6 +282,11 @@ struct crt_ctx {
         bool box_ran = false;       // the temporal call that wrote CURRENT ran the box kernel (crt_debug_read_clip_box)
         bool relit = false;         // the history has outlived a light edit: setting the option back to 0 drops it
 
+        // crt_denoise_latest: recorded on the context's stream behind the snapshot of the accumulator; the
+        // passes on read_stream wait for it.  wave_blocks (option "denoise_latest_wave_blocks"): k_dn_atrous_w64 for them.
+        crt::Event ev_snap;
+        bool wave_blocks = false;
+
         // Drop the history (the geometry snapshot goes with it).
         void drop() { cur.clear(); prev.clear(); snap.release(); relit = box_ran = false; }
     } dn;

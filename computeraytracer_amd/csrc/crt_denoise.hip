@@ -85,9 +85,11 @@ __device__ __forceinline__ bool dn_finite(float v) { return abs_(v) <= kDnMaxFin
 __device__ __forceinline__ bool finite4(float4 c) { return dn_finite(c.x) && dn_finite(c.y) && dn_finite(c.z); }
 
 // ---------------------------------------------------------------- what the a-trous kernels share
-// The pixel of a thread where block -> 16x16 pixels: grid (ceil(tw/16), ceil(th/16)) blocks of 256 threads.
-__device__ __forceinline__ int dn_x16() { return (int)(blockIdx.x * 16u + (threadIdx.x & 15u)); }
-__device__ __forceinline__ int dn_y16() { return (int)(blockIdx.y * 16u + (threadIdx.x >> 4)); }
+// The pixel of a thread where block -> B x B pixels: grid (ceil(tw/B), ceil(th/B)) blocks of B * B threads.
+template <uint32_t B> __device__ __forceinline__ int dn_xb() { return (int)(blockIdx.x * B + (threadIdx.x & (B - 1u))); }
+template <uint32_t B> __device__ __forceinline__ int dn_yb() { return (int)(blockIdx.y * B + threadIdx.x / B); }
+__device__ __forceinline__ int dn_x16() { return dn_xb<16>(); }
+__device__ __forceinline__ int dn_y16() { return dn_yb<16>(); }
 
 // The B3 spline (1, 4, 6, 4, 1) / 16 at tap i + 2.
 __device__ __forceinline__ float dn_h(int i)
@@ -128,11 +130,13 @@ __device__ __forceinline__ float dn_guide_term(float e, const float4 *gbuf, size
     return dn_guide_term(e, f3{g1.x, g1.y, g1.z}, f3{g0.y, g0.z, g0.w}, n_p, x_p, inv_n, inv_x);
 }
 
-// One a-trous iteration (grid: dn_x16).  Taps at step * (-2..2)^2 inside the tile; the centre pixel's guides stay in
-// registers, a tap's guides are fetched only when its key matches.
-__global__ __launch_bounds__(256) void k_dn_atrous(const DnParams P)
+// One a-trous iteration.  Taps at step * (-2..2)^2 inside the tile; the centre pixel's guides stay in registers, a tap's
+// guides are fetched only when its key matches.  A pixel's result does not depend on B: the block shape only says which
+// lane computes it.
+template <uint32_t B>
+__device__ __forceinline__ void dn_atrous_pixel(const DnParams &P)
 {
-    const int x = dn_x16(), y = dn_y16();
+    const int x = dn_xb<B>(), y = dn_yb<B>();
     const int tw = (int)P.tw, th = (int)P.th, s = (int)P.step;
     if (x >= tw || y >= th) return;
     const size_t p = (size_t)y * P.tw + (size_t)x;
@@ -174,6 +178,12 @@ __global__ __launch_bounds__(256) void k_dn_atrous(const DnParams P)
     P.c_out[p] = float4{c.x, c.y, c.z, 0.0f};
     if (P.rgba) P.rgba[p] = linear_rgb_to_rgba8(c);
 }
+
+// grid: dn_x16
+__global__ __launch_bounds__(256) void k_dn_atrous(const DnParams P) { dn_atrous_pixel<16>(P); }
+// The same pass in one-wave blocks of 8x8 pixels, for launches beside a live wavefront pool (crt_denoise_latest, DESIGN.md
+// 6m): a block of several waves waits for as many free slots on one CU.
+__global__ __launch_bounds__(64) void k_dn_atrous_w64(const DnParams P) { dn_atrous_pixel<8>(P); }
 
 // ---------------------------------------------------------------- the variance-guided filter (crt_denoise_adaptive)
 // DESIGN.md 6d defines it operation by operation (tests/denoise_adaptive_ref.py is its numpy restatement).  The colour
@@ -770,7 +780,8 @@ static void dn_guide_sigmas(const DnFilter &F, float &inv_n, float &inv_x)
 
 // F.iterations passes of k_dn_atrous: the first reads `first`, each writes the buffer of F.c that it does not read
 // (F.c[0] where `first` is neither), and the last also writes rgba.  Leaves the buffer that holds the result in *out.
-static hipError_t dn_run_atrous(const DnFilter &F, float4 *first, float sigma_color, float4 **out)
+// wave_blocks: k_dn_atrous_w64 in its place (the same bits).
+static hipError_t dn_run_atrous(const DnFilter &F, float4 *first, float sigma_color, float4 **out, bool wave_blocks = false)
 {
     hipError_t e = hipSuccess;
     *out = first;
@@ -782,23 +793,37 @@ static hipError_t dn_run_atrous(const DnFilter &F, float4 *first, float sigma_co
         P.tw = F.tw; P.th = F.th; P.step = 1u << i;
         P.inv_c = dn_clamped((double)(1u << i) / ((double)sigma_color * sigma_color));
         dn_guide_sigmas(F, P.inv_n, P.inv_x);
-        hipLaunchKernelGGL(k_dn_atrous, dn_grid16(F), dim3(256), 0, F.stream, P);
+        if (wave_blocks) hipLaunchKernelGGL(k_dn_atrous_w64, dim3((F.tw + 7u) / 8u, (F.th + 7u) / 8u), dim3(64), 0, F.stream, P);
+        else hipLaunchKernelGGL(k_dn_atrous, dn_grid16(F), dim3(256), 0, F.stream, P);
         e = hipGetLastError();
         *out = P.c_out;
     }
     return e;
 }
 
-// accum -> c[0], then the passes between c[0] and c[1].
-hipError_t dn_launch_filter(const DnFilter &F, const float4 *accum, float n, float sigma_color, float4 **out)
+// The two halves of the plain filter.  accum -> F.c[0] (and its rgba8 when no pass follows) ...
+hipError_t dn_launch_prepare(const DnFilter &F, const float4 *accum, float n, hipStream_t stream)
 {
     const size_t npix = (size_t)F.tw * F.th;
-    *out = F.c[0];
     if (npix == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_dn_prepare, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, F.stream, accum, n, F.c[0],
+    hipLaunchKernelGGL(k_dn_prepare, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, stream, accum, n, F.c[0],
                        F.iterations == 0 ? F.rgba : nullptr, npix);
-    const hipError_t e = hipGetLastError();
-    return e != hipSuccess ? e : dn_run_atrous(F, F.c[0], sigma_color, out);
+    return hipGetLastError();
+}
+
+// ... and the passes between F.c[0] and F.c[1], on F.stream.
+hipError_t dn_launch_passes(const DnFilter &F, float sigma_color, bool wave_blocks, float4 **out)
+{
+    *out = F.c[0];
+    if ((size_t)F.tw * F.th == 0) return hipSuccess;
+    return dn_run_atrous(F, F.c[0], sigma_color, out, wave_blocks);
+}
+
+hipError_t dn_launch_filter(const DnFilter &F, const float4 *accum, float n, float sigma_color, float4 **out)
+{
+    *out = F.c[0];
+    const hipError_t e = dn_launch_prepare(F, accum, n, F.stream);
+    return e != hipSuccess ? e : dn_launch_passes(F, sigma_color, false, out);
 }
 
 // The instantiation of k_dn_reproject that P asks for: <true, *, *> where the PREVIOUS slot has a geometry snapshot,

@@ -62,9 +62,11 @@ extern "C" {
 // allocated one before an unallocated one: nothing is allocated while a free set has buffers, and with three sets and
 // two slots there always is a free one.  `dying` is a slot the caller is about to overwrite or let go: its set counts
 // as free, and the slot is cleared once the allocations have succeeded, before its guides are overwritten.
-static int dn_ensure_gbuffer(crt_ctx *c, crt_ctx::DnSlot *dying = nullptr)
+// Its two halves: the set chosen and allocated (*set: -1 while the G-buffer is valid), then the launch on `stream`.
+static int dn_gbuffer_alloc(crt_ctx *c, crt_ctx::DnSlot *dying, int *set_out)
 {
     crt_ctx::Denoise &d = c->dn;
+    *set_out = -1;
     if (d.valid) return CRT_OK;
     int set = -1;
     for (int k = 0; k < 3; k++) {
@@ -75,11 +77,27 @@ static int dn_ensure_gbuffer(crt_ctx *c, crt_ctx::DnSlot *dying = nullptr)
     const size_t n = (size_t)c->tw * c->th;
     CRT_ENSURE(c, c->dn.sets[set].gbuf, 2 * n);
     CRT_ENSURE(c, c->dn.sets[set].key, n);
-    if (dying) dying->clear();
-    HIPCHK(c, dn_launch_gbuffer(c->sc, c->x0, c->y0, c->tw, c->th, d.sets[set].gbuf.p, d.sets[set].key.p, c->accel_mode == CRT_ACCEL_NONE, c->stream));
+    *set_out = set;
+    return CRT_OK;
+}
+
+static int dn_gbuffer_build(crt_ctx *c, int set, hipStream_t stream)
+{
+    crt_ctx::Denoise &d = c->dn;
+    if (set < 0) return CRT_OK;
+    HIPCHK(c, dn_launch_gbuffer(c->sc, c->x0, c->y0, c->tw, c->th, d.sets[set].gbuf.p, d.sets[set].key.p, c->accel_mode == CRT_ACCEL_NONE, stream));
     d.set = set;
     d.valid = true;
     return CRT_OK;
+}
+
+static int dn_ensure_gbuffer(crt_ctx *c, crt_ctx::DnSlot *dying = nullptr)
+{
+    int set = -1;
+    CRT_TRY(dn_gbuffer_alloc(c, dying, &set));
+    if (set < 0) return CRT_OK;
+    if (dying) dying->clear();
+    return dn_gbuffer_build(c, set, c->stream);
 }
 
 // The colour buffers and the rgba8 of every filter, and what its launchers share (once the G-buffer is there).
@@ -114,6 +132,64 @@ int crt_denoise(crt_ctx *c, const crt_denoise_params *params, float *rgb_out, ui
         HIPCHK(c, dn_launch_filter(F, accum_ptr(c), (float)c->sample, dp.sigma_color, &res));
     }
     return dn_finish(c, n, res, rgb_out, rgba8_out);
+}
+
+// What crt_denoise_latest puts on read_stream, behind the snapshot: the G-buffer if it is not there, the passes, the
+// copies to the caller.  The caller synchronises read_stream whatever this returns.
+static int dn_latest_passes(crt_ctx *c, const DnFilter &F, int set, float sigma_color, size_t n, float *rgb_out, uint8_t *rgba8_out)
+{
+    CRT_TRY(dn_gbuffer_build(c, set, F.stream));
+    float4 *res = nullptr;
+    HIPCHK(c, dn_launch_passes(F, sigma_color, c->dn.wave_blocks, &res));
+    if (rgb_out) HIPCHK(c, hipMemcpyAsync(rgb_out, res, n * sizeof(float4), hipMemcpyDeviceToHost, F.stream));
+    if (rgba8_out) HIPCHK(c, hipMemcpyAsync(rgba8_out, c->dn.rgba.p, n * sizeof(uchar4), hipMemcpyDeviceToHost, F.stream));
+    return CRT_OK;
+}
+
+// crt_denoise of the newest complete frame, without a flush.  In stream order the accumulator holds the
+// complete frame of sample resolved_upto (wf_resolve_batch sets it where it enqueues the resolve pass), so a snapshot
+// enqueued on the context's stream now is that frame's average whatever the pool does meanwhile, and everything after the
+// snapshot runs on read_stream: it waits for nothing the pipeline enqueues later, and the pipeline waits for that one pass of it.
+int crt_denoise_latest(crt_ctx *c, const crt_denoise_params *params, float *rgb_out, uint8_t *rgba8_out, uint32_t *sample)
+{
+    if (!c) return CRT_EINVAL;
+    const char *what = "crt_denoise_latest";
+    const crt_denoise_params dp = params ? *params : kDnDefaults;
+    const float sig[3] = {dp.sigma_color, dp.sigma_normal, dp.sigma_plane};
+    CRT_TRY(dn_check_params(c, what, dp.iterations, sig, 3, "every sigma"));
+    if (c->as_on) return as_refuse(c, what);
+    CRT_TRY(dn_check_state(c, what, true));                      // (true: "no sample traced yet" is decided by s below)
+    HIPCHK(c, hipSetDevice(c->device));
+    CRT_TRY(wf_tick(c));
+    const uint32_t s = c->resolved_upto;                         // after the tick: it may have enqueued a resolve pass
+    if (s == 0) {
+        if (sample) *sample = 0;
+        return fail(c, CRT_ESTATE, "%s: no complete frame yet (%u samples requested): try again later", what, c->sample);
+    }
+    const size_t n = (size_t)c->tw * c->th;
+    if (n) {
+        // every allocation before the first launch: a failed one leaves nothing enqueued
+        int set = -1;
+        CRT_TRY(dn_gbuffer_alloc(c, nullptr, &set));
+        CRT_TRY(dn_ensure_buffers(c, n));
+        if (!c->read_stream) HIPCHK(c, c->read_stream.create(hipStreamNonBlocking));
+        if (!c->dn.ev_snap) HIPCHK(c, c->dn.ev_snap.create(hipEventDisableTiming));
+        DnFilter F = dn_filter(c, dp.iterations, dp.sigma_normal, dp.sigma_plane, rgba8_out != nullptr);
+        const crt_ctx::DnGuideSet &g = c->dn.sets[set >= 0 ? set : c->dn.set];
+        F.gbuf = g.gbuf.p; F.key = g.key.p;
+        F.stream = c->read_stream;
+        // the snapshot: behind the resolve pass of s, ahead of any resolve pass enqueued later
+        HIPCHK(c, dn_launch_prepare(F, accum_ptr(c), (float)s, c->stream));
+        HIPCHK(c, hipEventRecord(c->dn.ev_snap, c->stream));
+        HIPCHK(c, hipStreamWaitEvent(c->read_stream, c->dn.ev_snap, 0));
+        // read_stream is idle again before this call returns, also where a launch failed: c->dn's buffers and a G-buffer
+        // marked valid are never in use on two streams (every other filter runs on the context's stream and ends idle)
+        const int rc = dn_latest_passes(c, F, set, dp.sigma_color, n, rgb_out, rgba8_out);
+        if (rc) { (void)hipStreamSynchronize(c->read_stream); return rc; }
+        HIPCHK(c, hipStreamSynchronize(c->read_stream));
+    }
+    if (sample) *sample = s;
+    return CRT_OK;
 }
 
 // The variance-guided filter of the adaptive state.  sigma_variance 8: the best of 1..24 at 16 and 32

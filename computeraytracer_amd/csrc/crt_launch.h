@@ -84,6 +84,10 @@ hipError_t dn_launch_gbuffer(const DevScene &S, uint32_t x0, uint32_t y0, uint32
                              int brute, hipStream_t stream);
 // (each leaves the buffer that holds the result in *out)
 hipError_t dn_launch_filter(const DnFilter &F, const float4 *accum, float n, float sigma_color, float4 **out);
+// (its two halves, for a caller that splits them across streams -- crt_denoise_latest, DESIGN.md 6m: the snapshot
+// accum / n -> F.c[0] on `stream`, then the passes on F.stream; wave_blocks: in one-wave blocks of 8x8 pixels)
+hipError_t dn_launch_prepare(const DnFilter &F, const float4 *accum, float n, hipStream_t stream);
+hipError_t dn_launch_passes(const DnFilter &F, float sigma_color, bool wave_blocks, float4 **out);
 hipError_t dn_launch_filter_adaptive(const DnFilter &F, const float4 *accum, const float *q, const uint32_t *counts, uint2 *kv,
                                      float *var, float sigma_variance, float4 **out);
 // (counts: null in the uniform state, where P.n is every pixel's n; else the adaptive state's count per 8x8 tile)

@@ -371,6 +371,20 @@ class Renderer:
         return self._denoise(self._lib.crt_denoise, _lib.DenoiseParams(), dict(
             iterations=iterations, sigma_color=sigma_color, sigma_normal=sigma_normal, sigma_plane=sigma_plane), rgb)
 
+    def denoise_latest(self, iterations: int = 5, sigma_color: float = 1.0, sigma_normal: float = 0.5,
+                       sigma_plane: float = 0.3, rgb: bool = True, rgba8: bool = True):
+        """denoise() of the newest complete frame without finishing what is in flight (crt_denoise_latest): (linear rgb
+        (H, W, 4) float32 or None, rgba8 (H, W, 4) or None, s), the filtered frame of exactly s samples.  CrtError
+        (CRT_ESTATE) while no frame is complete yet."""
+        _, _, tw, th = self.tile
+        p = _lib.DenoiseParams(int(iterations), float(sigma_color), float(sigma_normal), float(sigma_plane))
+        lin = np.empty((th, tw, 4), np.float32) if rgb else None
+        out = np.empty((th, tw, 4), np.uint8) if rgba8 else None
+        s = C.c_uint32()
+        self._chk(self._lib.crt_denoise_latest(self._h, C.byref(p), lin.ctypes.data if rgb else None,
+                                               out.ctypes.data if rgba8 else None, C.byref(s)))
+        return lin, out, s.value
+
     def denoise_adaptive(self, iterations: int | None = None, sigma_variance: float | None = None,
                          sigma_normal: float | None = None, sigma_plane: float | None = None, rgb: bool = False,
                          var: bool = False):

@@ -11,8 +11,19 @@
  *                                                                        the batch that holds it, never flushes)
  *
  *   node host/display_loop.js [--scene f.json | --packed prefix] [--width W --height H] [--frames 640] [--lag 64] [--ring 128] [--check 1]
+ *                             [--cohort C] [--denoise K]
+ *   --cohort C: option "wf_cohort" = C (calls merged per batch: 16 by default, times up to 8 on a frame below 2 Mpixels).
  *   --check 1: every shown frame is compared with a synchronous trace(1); sync(); readRgba8() loop on a second context.
  * Prints one JSON line: ms per shown frame, frames shown, whether every index appeared once and in order.
+ *
+ *   --denoise K: the FILTERED display loop (DESIGN.md 6m).  A filtered frame exists only for the newest complete sample
+ *   index (the filter reads the accumulator, and no ring keeps accumulators), so this loop shows that one:
+ *   frame k:   trace(1)                       request sample k
+ *              denoiseLatestInto(frame, K)    show the newest complete frame, filtered with K passes, and its index --
+ *                                             no flush: the trace calls stay a cohort ahead
+ *   and ends on sync + denoise of the final count.  Prints the sample index shown per frame and one JSON line: ms per
+ *   frame, the indices shown (non-decreasing), how many frames had nothing complete to show yet.  With --check 1 every
+ *   shown frame is compared with sync + denoise of the same index on a second context.
  */
 const path = require('path');
 const { loadAddon } = require('./main');
@@ -47,6 +58,8 @@ function make() {
   return h;
 }
 const h = make();
+if ('cohort' in args) a.setOption(h, 'wf_cohort', num('cohort'));   // (a small frame merges up to 8 x as many calls per cohort)
+if ('denoise' in args) { denoiseLoop(h, args.denoise === true ? 5 : num('denoise')); return; }
 a.setOption(h, 'frame_ring', ring);
 let ref = null;
 if (check) ref = make();
@@ -77,3 +90,44 @@ console.log(JSON.stringify({ width: packed.width, height: packed.height, frames,
 a.unpinHost(frame);
 a.destroy(h);
 if (ref) a.destroy(ref);
+
+function denoiseLoop(h, K) {
+  const opts = { iterations: K };
+  const ref = check ? make() : null;
+  const frame = new Uint8Array(packed.width * packed.height * 4);
+  a.pinHost(frame);
+  const indices = [];
+  let nothingYet = 0, nonDecreasing = true, equal = true, last = 0;
+  const t0 = process.hrtime.bigint();
+  for (let k = 1; k <= frames; k++) {
+    a.trace(h, 1);
+    let s = 0;
+    try { s = a.denoiseLatestInto(h, frame, opts); } catch (e) {
+      if (!/no complete frame yet/.test(String(e.message))) throw e;   // (only that refusal is part of the loop)
+      nothingYet++;
+      continue;
+    }
+    if (s < last || s > k) nonDecreasing = false;
+    last = s;
+    indices.push(s);
+    if (!args.quiet) console.log(`frame ${k}: sample ${s}`);
+    if (ref) {
+      while (a.sampleCount(ref) < s) a.trace(ref, 1);
+      a.sync(ref);
+      const want = a.denoise(ref, opts);
+      for (let i = 0; i < want.length; i++) if (want[i] !== frame[i]) { equal = false; break; }
+    }
+  }
+  const ms = Number(process.hrtime.bigint() - t0) / 1e6;
+  a.sync(h);
+  const final = a.denoise(h, opts);                            // the loop ends on the synced filter of everything requested
+  const end = a.denoiseLatestInto(h, frame, opts);
+  let endEqual = end === frames;
+  for (let i = 0; endEqual && i < final.length; i++) if (final[i] !== frame[i]) endEqual = false;
+  console.log(JSON.stringify({ width: packed.width, height: packed.height, frames, denoise: K, shown: indices.length, nothing_complete_yet: nothingYet,
+    samples_shown: indices, non_decreasing: nonDecreasing, equal_to_synced_denoise: ref ? equal : null, ends_on_synced_denoise: endEqual,
+    final_sample: end, ms_per_frame: ms / frames }));
+  a.unpinHost(frame);
+  a.destroy(h);
+  if (ref) a.destroy(ref);
+}

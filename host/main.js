@@ -64,6 +64,11 @@ function Main(options = {}) {
     readRgba8: () => a.readRgba8(device),
     // denoised preview of the current average (include/crt.h "Denoised preview"): rgba8 of the tile; reads only
     denoise: (opts = {}) => a.denoise(device, opts),
+    // ... of the newest COMPLETE frame without finishing what is in flight (crt_denoise_latest): {rgba8, rgb?, sample}, the
+    // filtered frame of exactly `sample` samples; Into writes the rgba8 into a (pinned) typed array and returns `sample`
+    denoiseLatest: (opts = {}) => a.denoiseLatest(device, opts),
+    denoiseLatestInto: (out, opts = {}) => a.denoiseLatestInto(device, out, opts),
+    denoiseLatestAsync: (opts = {}) => a.denoiseLatestAsync(device, opts),
     readGbuffer: () => a.readGbuffer(device),
     // scene edits (include/crt.h "Scene edits"): each finishes what is in flight and restarts the accumulation;
     // the reference's queue.writeBuffer of the camera / primitive / light buffer

@@ -254,6 +254,24 @@ typedef struct {
 /* NULL params = defaults {5, 1.0, 0.5, 0.3}.  rgb_out: tw*th*4 floats (linear rgb + pad) or NULL; rgba8_out: tw*th*4
  * bytes (the reference's colour tail: exposure, gamma, unorm8) or NULL.  CRT_EINVAL for iterations > 10 or a bad sigma. */
 int crt_denoise(crt_ctx *ctx, const crt_denoise_params *params, float *rgb_out, uint8_t *rgba8_out);
+/* crt_denoise of the newest COMPLETE frame, without a flush: to crt_denoise what crt_read_latest_rgba8 is to
+ * crt_read_rgba8 -- the filtered preview of a display loop that keeps its crt_trace(1) calls a cohort ahead.  Batches in
+ * flight stay in flight and samples merged into an unpublished cohort stay unpublished; the call gives the driver one
+ * turn (as crt_read_latest_rgba8 does), takes s = the newest sample whose resolve pass is enqueued, and returns the filtered
+ * frame of exactly s samples: rgb_out and rgba8_out are, bit for bit, what crt_denoise with the same parameters returns on
+ * a context that holds exactly s samples of the same scene; *sample = s (`sample` may be NULL).  Parameters, defaults and
+ * CRT_EINVAL cases are crt_denoise's.  It blocks until its own outputs are written and waits for nothing the pipeline
+ * enqueued after the resolve pass of sample s: the context's stream gets one snapshot pass (accumulator / s into the
+ * filter's buffer), everything else runs on a second stream.  It only reads the frame state: the accumulator, the rgba8
+ * framebuffer, `sample`, the counters, the frame ring and the history slots of the temporal filters stay as they are (the
+ * G-buffer is built on first use and kept, as by crt_denoise, in a guide set no history slot names), and a later crt_sync
+ * leaves the accumulator bit for bit what it would have been without the call.
+ * CRT_ESTATE where crt_denoise refuses (no scene or accel structure, a stale tree, row bands, the adaptive state), and when
+ * s == 0 -- no complete frame yet: *sample is set to 0 and the caller tries again later; CRT_ENOMEM as crt_denoise.  A
+ * refused call enqueues nothing and writes nothing to rgb_out / rgba8_out.  With nothing in flight ("pipeline" = 0,
+ * CRT_ACCEL_NONE, "wf_defer" = 0, after crt_sync) the call equals crt_denoise and *sample = crt_sample_count.
+ * Option "denoise_latest_wave_blocks" = 1 (default 0) runs its passes in one-wave blocks of 8x8 pixels (the same bits). */
+int crt_denoise_latest(crt_ctx *ctx, const crt_denoise_params *params, float *rgb_out, uint8_t *rgba8_out, uint32_t *sample);
 /* The G-buffer: tw*th*8 floats, the crt_debug_intersect record per pixel (t, px,py,pz, nx,ny,nz, index_bits;
  * index 0xFFFFFFFF = miss). */
 int crt_read_gbuffer(crt_ctx *ctx, float *out);
@@ -769,6 +787,8 @@ int crt_last_kernel_ms(crt_ctx *ctx, float *ms, uint32_t *launches);
  * "temporal_clip_pct" (0 = off, default | 25..10000, anything else is CRT_EINVAL: the temporal filters clamp the reprojected
  * history to the mean +- that percentage of a standard deviation of the frame's own 7x7 neighbourhood, and
  * crt_update_lights keeps the history, see "Clipped history"; back to 0 after a kept light edit drops the history);
+ * "denoise_latest_wave_blocks" (0 | 1, anything else is CRT_EINVAL; default 0: 1 runs the passes of crt_denoise_latest in
+ * one-wave blocks of 8x8 pixels instead of 16x16 -- the same bits, measured slower beside a live pool);
  * "ploc_radius" (1..32, anything else is CRT_EINVAL; default 8: clusters searched to either side by CRT_ACCEL_PLOC; at
  * crt_build_accel);
  * "refit_rebuild_pct" (0 = off, default | 100..100000, anything else is CRT_EINVAL: crt_refit_accel rebuilds once the
