@@ -898,6 +898,40 @@ static napi_value js_read_gbuffer(napi_env env, napi_callback_info info)
     return ta;
 }
 
+/* renderAovs(h, n, {hits: Uint32Array(tw*th), alpha: Float32Array(tw*th), depth: Float32Array(tw*th),
+ * normal: Float32Array(tw*th*4), albedo: Float32Array(tw*th*4)}): the feature planes of n samples (0: what the accumulator
+ * holds) into the caller's typed arrays; a plane left out is not rendered (include/crt.h "Feature planes").  Blocking. */
+static napi_value js_render_aovs(napi_env env, napi_callback_info info)
+{
+    ARGS(3)
+    crt_ctx *ctx = get_ctx(env, argv[0]);
+    if (!ctx) return NULL;
+    uint32_t n = 0, tl[4];
+    NAPI_OK(env, napi_get_value_uint32(env, argv[1], &n));
+    CRT_CHECK(env, ctx, "crt_tile", crt_tile(ctx, tl));
+    const size_t px = (size_t)tl[2] * tl[3];
+    static const char *names[5] = {"hits", "alpha", "depth", "normal", "albedo"};
+    static const size_t bytes_per_px[5] = {4, 4, 4, 16, 16};
+    void *p[5] = {NULL, NULL, NULL, NULL, NULL};
+    for (int i = 0; i < 5; i++) {
+        bool has = false;
+        napi_value v;
+        NAPI_OK(env, napi_has_named_property(env, argv[2], names[i], &has));
+        if (!has) continue;
+        NAPI_OK(env, napi_get_named_property(env, argv[2], names[i], &v));
+        size_t len = 0;
+        if (!get_bytes(env, v, &p[i], &len) || len != px * bytes_per_px[i]) {
+            char m[128];
+            snprintf(m, sizeof m, "renderAovs: %s must be a typed array of %zu bytes", names[i], px * bytes_per_px[i]);
+            napi_throw_type_error(env, NULL, m);
+            return NULL;
+        }
+    }
+    const crt_aov_planes out = {(uint32_t *)p[0], (float *)p[1], (float *)p[2], (float *)p[3], (float *)p[4]};
+    CRT_CHECK(env, ctx, "crt_render_aovs", crt_render_aovs(ctx, n, &out));
+    return undefined(env);
+}
+
 /* readMotion(h) -> Float32Array (tw*th*2): per pixel the film position (u, v) where the last denoiseTemporal looked for
  * it in the previous frame, NaN where there is none (include/crt.h crt_read_motion). */
 static napi_value js_read_motion(napi_env env, napi_callback_info info)
@@ -1571,7 +1605,7 @@ static napi_value init(napi_env env, napi_value exports)
         {"bindOutput", js_bind_output}, {"setStream", js_set_stream},
         {"denoise", js_denoise}, {"denoiseLatest", js_denoise_latest}, {"denoiseLatestInto", js_denoise_latest_into},
         {"denoiseLatestAsync", js_denoise_latest_async},
-        {"readGbuffer", js_read_gbuffer}, {"readMotion", js_read_motion},
+        {"readGbuffer", js_read_gbuffer}, {"readMotion", js_read_motion}, {"renderAovs", js_render_aovs},
         {"setCamera", js_set_camera}, {"updatePrimitives", js_update_primitives}, {"updateLights", js_update_lights},
         {"refitAccel", js_refit_accel},
         {"transformPrimitives", js_transform_primitives}, {"transformPrimitivesAsync", js_transform_primitives_async},

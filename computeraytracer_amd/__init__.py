@@ -4,11 +4,14 @@ dispatched by src/main.js).  The compute path is libcrt.so (hand-written HIP,
 C ABI in include/crt.h); this package is the thin Python host side."""
 from .scene import PackedScene, cornell, load_scene, pack_scene  # noqa: F401
 
-__all__ = ["PackedScene", "cornell", "load_scene", "pack_scene", "Renderer"]
+__all__ = ["PackedScene", "cornell", "load_scene", "pack_scene", "Renderer", "spectrum_rgb"]
 
 
 def __getattr__(name):
     if name == "Renderer":          # lazy: importing the package must not need a GPU
         from .renderer import Renderer
         return Renderer
+    if name == "spectrum_rgb":
+        from .renderer import spectrum_rgb
+        return spectrum_rgb
     raise AttributeError(name)

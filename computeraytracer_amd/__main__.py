@@ -1,5 +1,6 @@
 """python -m computeraytracer_amd [--scene file.json] [--width W --height H] [--spp N] [--out image.png] [--denoise K] [--orbit N [--temporal [--variance] [--animate | --animate-device [--rebuild-pct P] | --blink P]]]
                                 [--adaptive THRESHOLD [--adaptive-filtered] [--adaptive-step N] [--counts-out counts.png]]
+                                [--alpha] [--aov-out PREFIX]
 --adaptive goes with --orbit: every frame is sampled adaptively up to --spp, and with --denoise K --temporal [--variance] the
 temporal filters blend it with each pixel's own tile count (option "adaptive_temporal")."""
 import argparse
@@ -73,7 +74,18 @@ def parse_args(argv=None):
                     help="with --adaptive: a tile below M samples is sampled whatever its error (default: min(--spp, 2N))")
     ap.add_argument("--counts-out", default=None,
                     help="with --adaptive: the per-tile sample counts as a grey PNG (with --orbit: the last frame's)")
+    ap.add_argument("--alpha", action="store_true",
+                    help="the PNG's alpha channel is the coverage of each pixel: the share of its camera rays that hit "
+                         "something, floor(alpha * 255 + 0.5) (crt_render_aovs over the samples the image holds; also with "
+                         "--adaptive, not with --orbit)")
+    ap.add_argument("--aov-out", default=None, metavar="PREFIX",
+                    help="the feature planes of the samples the image holds (crt_render_aovs): PREFIX_albedo.png, "
+                         "PREFIX_normal.png (n * 0.5 + 0.5) and PREFIX_depth.npy (also with --adaptive, not with --orbit)")
     args = ap.parse_args(argv)
+    if (args.alpha or args.aov_out) and args.orbit is not None:
+        ap.error("--alpha and --aov-out do not go with --orbit")
+    if args.alpha and args.out.endswith(".ppm"):
+        ap.error("--alpha needs a PNG: a PPM has no alpha channel")
     if args.orbit is not None and (args.orbit < 1 or args.checkpoint):
         ap.error("--orbit needs N >= 1 and no --checkpoint")
     if args.temporal and (args.orbit is None or args.denoise is None):
@@ -208,13 +220,28 @@ def main(argv=None):
         r.frame(args.spp).sync()
         dt = time.time() - t0
         rgba = r.read_rgba8() if args.denoise is None else r.denoise(args.denoise)
+        info = {"width": ps.width, "height": ps.height, "sample": r.sample, "seconds": round(dt, 4), "out": args.out}
+        rgba = _aovs(r, args, rgba, info)
         (image.write_ppm if args.out.endswith(".ppm") else image.write_png)(args.out, rgba)
         if args.checkpoint:
             image.save_checkpoint(args.checkpoint, r)
-        info = {"width": ps.width, "height": ps.height, "sample": r.sample, "seconds": round(dt, 4), "out": args.out}
         if args.denoise is not None:
             info["denoise"] = args.denoise
         print(json.dumps(info))
+
+
+def _aovs(r, args, rgba, info):
+    """--alpha and --aov-out: the feature planes of the samples the image holds; returns the rgba8 to write."""
+    want = (("alpha",) if args.alpha else ()) + (("depth", "normal", "albedo") if args.aov_out else ())
+    if not want:
+        return rgba
+    planes = r.render_aovs(0, want)
+    if args.aov_out:
+        info["aov_out"] = image.write_aovs(args.aov_out, planes)
+    if args.alpha:
+        info["alpha"] = True
+        rgba = image.with_alpha(rgba, planes["alpha"])
+    return rgba
 
 
 def _closing_spheres(ps) -> int:
@@ -259,11 +286,12 @@ def _adaptive(r, ps, args):
     counts, rounds = _adaptive_rounds(r, args)
     dt = time.time() - t0
     rgba = r.read_rgba8() if args.denoise is None else r.denoise_adaptive(args.denoise)
-    (image.write_ppm if args.out.endswith(".ppm") else image.write_png)(args.out, rgba)
     info = {"width": ps.width, "height": ps.height, "adaptive": args.adaptive, "rounds": rounds,
             "pixel_samples": _pixel_samples(counts, ps), "seconds": round(dt, 4),
             "tile_samples": {"min": int(counts.min()), "median": float(np.median(counts)), "max": int(counts.max())},
             "out": args.out}
+    rgba = _aovs(r, args, rgba, info)
+    (image.write_ppm if args.out.endswith(".ppm") else image.write_png)(args.out, rgba)
     if args.denoise is not None:
         info["denoise"] = args.denoise
     if args.counts_out:

@@ -67,6 +67,9 @@ SIGNATURES = {
     "crt_denoise_latest": (C.c_int, [_P, _P, _P, _P, _P]),
     "crt_read_gbuffer": (C.c_int, [_P, _P]),
     "crt_read_motion": (C.c_int, [_P, _P]),
+    "crt_render_aovs": (C.c_int, [_P, C.c_uint32, _P]),
+    "crt_spectrum_rgb": (C.c_int, [_P, _P, _P]),
+    "crt_read_albedo_table": (C.c_int, [_P, _P]),
     "crt_debug_intersect": (C.c_int, [_P, _P, C.c_size_t, _P]),
     "crt_debug_trace_rays": (C.c_int, [_P, _P, C.c_size_t, _P, _P]),
     "crt_debug_walk_rays": (C.c_int, [_P, C.c_int, _P, C.c_size_t, _P, _P]),
@@ -132,6 +135,11 @@ class PrimTransform(C.Structure):
 class DenoiseParams(C.Structure):
     """crt_denoise_params of include/crt.h."""
     _fields_ = [("iterations", C.c_uint32), ("sigma_color", C.c_float), ("sigma_normal", C.c_float), ("sigma_plane", C.c_float)]
+
+
+class AovPlanes(C.Structure):
+    """crt_aov_planes of include/crt.h."""
+    _fields_ = [("hits", C.c_void_p), ("alpha", C.c_void_p), ("depth", C.c_void_p), ("normal", C.c_void_p), ("albedo", C.c_void_p)]
 
 
 class DenoiseAdaptiveParams(C.Structure):

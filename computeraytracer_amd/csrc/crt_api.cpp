@@ -261,6 +261,7 @@ int crt_upload_scene(crt_ctx *c, const void *primitives, size_t nprim, const voi
     HIPCHK(c, c->d_cie.alloc(3 * kNCie));
     HIPCHK(c, hipMemcpy(c->d_cie.p, cie, 3 * kNCie * sizeof(float), hipMemcpyHostToDevice));
     c->cie_zero = tc_culled_is_zero(cie);                        // (what k_wf_gen stores for a MISS tile's chunk: DESIGN.md 5.9)
+    aov_rebuild_albedo(c, spectra, nspectra, cie);               // (host only: DESIGN.md 6n)
     std::vector<float4> hl(nlight * 3);
     for (size_t i = 0; i < nlight; i++) light_rows(c->lights[i], &hl[3 * i]);
     HIPCHK(c, c->d_lights.alloc(hl.size()));

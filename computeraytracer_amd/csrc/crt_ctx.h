@@ -6,6 +6,7 @@
 //   crt_scene.cpp       scene upload, tree build, scene edits and the refit
 //   crt_wf_driver.cpp   the wavefront driver (decisions: crt_wf_policy.h)
 //   crt_denoise_api.cpp the preview filters' entry points
+//   crt_aov_api.cpp     the feature planes' entry points
 //   crt_debug.cpp       the debug read-outs
 #pragma once
 #include <hip/hip_runtime.h>
@@ -304,6 +305,15 @@ struct crt_ctx {
         DevBuf<uint32_t> flags;     // ... and the flags the selection kernel writes beside it
     } fdn;
 
+    // The feature planes (crt_aov.hip).
+    std::vector<float> albedo;      // the albedo table: crt_spectrum_rgb of every spectra row, rebuilt by crt_upload_scene
+    DevBuf<float> d_albedo;         // ... on the device: made by the first crt_render_aovs after the upload
+    struct Aov {                    // the planes of the tile, each allocated by the first call that asks for it
+        DevBuf<uint32_t> hits;
+        DevBuf<float> alpha, depth;
+        DevBuf<float4> normal, albedo;
+    } aov;
+
     // scene edits (crt_refit.hip)
     float s_prims = 0.0f;           // max |corner coordinate| of the primitives: hit_pad = max(s_prims, |eye|) * 2^-17
     float tree_pad = 0.0f;          // the hit_pad the tree's boxes were made with (a larger one needs a refit)
@@ -411,6 +421,9 @@ int dn_finish(crt_ctx *c, size_t n, const float4 *res, float *rgb_out, uint8_t *
 int dn_adaptive_params(crt_ctx *c, const char *what, const crt_denoise_adaptive_params *params, crt_denoise_adaptive_params *out);
 int dn_check_state(crt_ctx *c, const char *what, bool adaptive = false);
 int dn_adaptive_run(crt_ctx *c, const crt_denoise_adaptive_params &dp, bool rgba, bool var, float4 **res, const float **var_dev);
+
+// crt_aov_api.cpp: the albedo table of a new scene (crt_upload_scene)
+void aov_rebuild_albedo(crt_ctx *c, const float *spectra, size_t nspectra, const float *cie);
 
 // crt_wf_driver.cpp
 struct AsBatch {                    // one batch of a crt_trace_adaptive call: its samples off + 1 .. off + n of every active tile

@@ -357,4 +357,19 @@ struct DnFilter {
     hipStream_t stream;
 };
 
+// k_aov (crt_aov.hip): the feature planes of the camera rays of samples first + 1 .. first + n of every pixel
+// of the rectangle.  A plane whose pointer is null is not stored.
+struct AovParams {
+    const float *albedo;            // the albedo table: 3 floats per spectra row (crt_spectrum_rgb of the row)
+    const uint32_t *counts;         // null: every pixel takes n; else per 8x8 tile of the rectangle, row-major, its n
+    uint32_t *hits;                 // per pixel: h, the camera rays that hit something
+    float *alpha;                   // (float)h / (float)n
+    float *depth;                   // mean t of the hits (CRT_INFINITY at h = 0)
+    float4 *normal;                 // mean hit normal, w = +0 (zeros at h = 0)
+    float4 *albedo_out;             // mean albedo of the hit primitives, w = +0 (zeros at h = 0)
+    uint32_t x0, y0, tw, th, tiles_x;
+    uint32_t first, n;
+    int brute;                      // CRT_ACCEL_NONE: the reference's loop over every primitive
+};
+
 }  // namespace crt

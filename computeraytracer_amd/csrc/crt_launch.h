@@ -1,4 +1,4 @@
-// crt_launch.h -- every host entry into the device code, declared once: the launchers of the eight .hip files, the GPU tree
+// crt_launch.h -- every host entry into the device code, declared once: the launchers of the nine .hip files, the GPU tree
 // builders and the level lists of the refit.  The .hip file that defines one and every host unit that calls one include
 // this header.  (Parameter structs: crt_device.h.)
 #pragma once
@@ -99,5 +99,8 @@ hipError_t dn_launch_temporal(const DnFilter &F, DnReprojParams P, const uint32_
 hipError_t dn_launch_svgf(const DnFilter &F, DnSvgfParams P, const uint32_t *counts, uint2 *kv, float *var, float sigma_variance,
                           float spatial_b, float4 *box, float gamma, float4 **out);
 hipError_t dn_launch_motion(const DnReprojParams &P, float2 *out, hipStream_t stream);
+
+// crt_aov.hip
+hipError_t aov_launch(const DevScene &S, const AovParams &P, hipStream_t stream);
 
 }  // namespace crt

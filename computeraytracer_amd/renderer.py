@@ -19,6 +19,21 @@ from .scene import PackedScene
 
 _ACCEL = {"none": ACCEL_NONE, "brute": ACCEL_NONE, "bvh2": ACCEL_BVH2, "bvh": ACCEL_BVH2, "lbvh": ACCEL_LBVH, ACCEL_LBVH: ACCEL_LBVH,
           "ploc": ACCEL_PLOC, ACCEL_PLOC: ACCEL_PLOC, ACCEL_NONE: ACCEL_NONE, ACCEL_BVH2: ACCEL_BVH2}
+AOV_PLANES = ("hits", "alpha", "depth", "normal", "albedo")
+
+
+def spectrum_rgb(spectrum, cie) -> np.ndarray:
+    """crt_spectrum_rgb: the linear sRGB reflectance of spectrum (301 floats) under an equal-energy illuminant with white
+    Y = 1, given the scene's CIE table (3 x 471): one row of Renderer.albedo_table.  Needs no context and no GPU."""
+    s = np.ascontiguousarray(spectrum, np.float32)
+    c = np.ascontiguousarray(cie, np.float32)
+    if s.size != 301 or c.size != 3 * 471:
+        raise ValueError("spectrum must be 301 floats, cie 3 x 471")
+    out = np.empty(3, np.float32)
+    rc = _lib.load().crt_spectrum_rgb(s.ctypes.data, c.ctypes.data, out.ctypes.data)
+    if rc != 0:
+        raise CrtError(rc, "crt_spectrum_rgb failed")
+    return out
 
 
 class Renderer:
@@ -493,6 +508,30 @@ class Renderer:
         _, _, tw, th = self.tile
         out = np.empty((th, tw, 8), np.float32)
         self._chk(self._lib.crt_read_gbuffer(self._h, out.ctypes.data))
+        return out
+
+    # -- feature planes (include/crt.h, "Feature planes")
+    def render_aovs(self, n_samples: int = 0, planes=AOV_PLANES) -> dict:
+        """The feature planes of the tile (crt_render_aovs), averaged over the camera rays of n_samples samples from the
+        sample offset on; n_samples = 0: the samples the accumulator holds (in the adaptive state each 8x8 tile's own
+        count).  A dict of the planes asked for: hits (H, W) uint32, alpha and depth (H, W) float32, normal and albedo
+        (H, W, 4) float32 with channel 3 = 0.  Finishes what is in flight; only reads."""
+        _, _, tw, th = self.tile
+        unknown = [p for p in planes if p not in AOV_PLANES]
+        if unknown:
+            raise ValueError(f"unknown planes {unknown}: choose from {AOV_PLANES}")
+        out = {p: np.empty((th, tw, 4) if p in ("normal", "albedo") else (th, tw), np.uint32 if p == "hits" else np.float32)
+               for p in AOV_PLANES if p in planes}
+        arg = _lib.AovPlanes(**{p: a.ctypes.data for p, a in out.items()})
+        self._chk(self._lib.crt_render_aovs(self._h, int(n_samples), C.byref(arg)))
+        return out
+
+    def albedo_table(self) -> np.ndarray:
+        """(nspectra, 3) float32: spectrum_rgb of every spectra row of the uploaded scene, the table render_aovs reads."""
+        if self.scene is None:
+            raise ValueError("upload a scene first")
+        out = np.empty((np.asarray(self.scene.spectra).size // 301, 3), np.float32)
+        self._chk(self._lib.crt_read_albedo_table(self._h, out.ctypes.data))
         return out
 
     # -- multi-GPU: the frame across the ranks of a communicator (include/crt.h, "Multi-GPU")

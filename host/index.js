@@ -22,6 +22,9 @@
 //            With --orbit N every frame is sampled so and its mean samples per pixel are printed; with --denoise K
 //            --temporal [--variance] besides, option "adaptive_temporal" lets frame k start at sample index k * spp + 1
 //            and the temporal filters blend every pixel with its own tile's count
+// --aov-out PREFIX: the feature planes of the samples the image holds (renderAovs(0); also with --adaptive, not with
+//            --orbit), each as the raw bytes of its typed array: PREFIX_hits.bin (u32), PREFIX_alpha.bin, PREFIX_depth.bin
+//            (f32), PREFIX_normal.bin, PREFIX_albedo.bin (4 x f32 per pixel)
 const fs = require('fs');
 const { Main, writePPM, orbitCameras } = require('./main');
 const sceneLoader = require('./sceneLoader');
@@ -59,8 +62,14 @@ const clip = !('clip' in args) ? null : args.clip === true ? 100 : Number(args.c
 if (clip !== null && !(args.temporal && Number.isInteger(clip) && clip >= 25 && clip <= 10000)) {
   console.error('--clip [PCT] goes with --orbit N --denoise K --temporal, PCT in 25..10000'); process.exit(2);
 }
+if ('aov-out' in args && (args.orbit || args['aov-out'] === true)) { console.error('--aov-out PREFIX writes the planes of one frame: give it a prefix, and no --orbit'); process.exit(2); }
 const r = Main({ sceneFile: args.scene, width: args.width ? num('width') : undefined, height: args.height ? num('height') : undefined,
   accel: args.accel || 'bvh2', device: num('device', 0) });
+function writeAovs() {
+  if (!('aov-out' in args)) return;
+  for (const [name, plane] of Object.entries(r.renderAovs(0)))
+    fs.writeFileSync(`${args['aov-out']}_${name}.bin`, Buffer.from(plane.buffer, plane.byteOffset, plane.byteLength));
+}
 // --adaptive: rounds of --adaptive-step samples until no tile is active; {rounds, ad: readAdaptive(), pixelSamples}
 function adaptiveRounds() {
   const step = num('adaptive-step', 16), minS = num('adaptive-min', Math.min(spp, 2 * step));
@@ -102,6 +111,7 @@ if ('adaptive' in args) {
   const { rounds, ad, pixelSamples } = adaptiveRounds(), counts = Array.from(ad.counts).sort((a, b) => a - b);
   const seconds = Number(process.hrtime.bigint() - t1) / 1e9;
   if (args.out) writePPM(args.out, 'denoise' in args ? r.denoiseAdaptive({ iterations: num('denoise') }) : r.readRgba8(), r.width, r.height);
+  writeAovs();
   const mid = counts.length >> 1, median = counts.length % 2 ? counts[mid] : (counts[mid - 1] + counts[mid]) / 2;
   console.log(JSON.stringify({ width: r.width, height: r.height, adaptive: num('adaptive'), rounds, pixel_samples: pixelSamples, seconds,
     tile_samples: { min: counts[0], median, max: counts[counts.length - 1] }, ...('denoise' in args ? { denoise: num('denoise') } : {}) }));
@@ -115,6 +125,7 @@ const dt = Number(process.hrtime.bigint() - t0) / 1e9;
 const c = r.counters();
 const rgba = r.readRgba8();
 if (args.out) writePPM(args.out, 'denoise' in args ? r.denoise({ iterations: num('denoise') }) : rgba, r.width, r.height);
+writeAovs();
 if (args.dump) {
   fs.writeFileSync(`${args.dump}.rgba8.bin`, Buffer.from(rgba.buffer));
   fs.writeFileSync(`${args.dump}.accum.bin`, Buffer.from(r.readAccum().buffer));

@@ -70,6 +70,17 @@ function Main(options = {}) {
     denoiseLatestInto: (out, opts = {}) => a.denoiseLatestInto(device, out, opts),
     denoiseLatestAsync: (opts = {}) => a.denoiseLatestAsync(device, opts),
     readGbuffer: () => a.readGbuffer(device),
+    // feature planes (include/crt.h "Feature planes"): anti-aliased hits, alpha, depth, normal and albedo of the camera
+    // rays of n samples (0: the samples the accumulator holds), as typed arrays over the tile; reads only
+    renderAovs: (n = 0, planes = ['hits', 'alpha', 'depth', 'normal', 'albedo']) => {
+      const [, , tw, th] = a.tile(device), out = {};
+      for (const p of planes) {
+        if (!['hits', 'alpha', 'depth', 'normal', 'albedo'].includes(p)) throw new TypeError(`renderAovs: unknown plane ${p}`);
+        out[p] = p === 'hits' ? new Uint32Array(tw * th) : new Float32Array(tw * th * (p === 'normal' || p === 'albedo' ? 4 : 1));
+      }
+      a.renderAovs(device, n, out);
+      return out;
+    },
     // scene edits (include/crt.h "Scene edits"): each finishes what is in flight and restarts the accumulation;
     // the reference's queue.writeBuffer of the camera / primitive / light buffer
     setCamera: (camera) => a.setCamera(device, camera),

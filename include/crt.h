@@ -276,6 +276,50 @@ int crt_denoise_latest(crt_ctx *ctx, const crt_denoise_params *params, float *rg
  * index 0xFFFFFFFF = miss). */
 int crt_read_gbuffer(crt_ctx *ctx, float *out);
 
+/* ------------------------------------------------------------------ Feature planes
+ * What compositing and an external denoiser ask for beside the beauty image: anti-aliased alpha, depth,
+ * normal and albedo.  crt_read_gbuffer is ONE ray per pixel, a filter guide; these planes are averages over the very
+ * camera rays the image was averaged over, so a silhouette pixel is fractional and a pixel that sees two primitives
+ * reports both.  The camera ray of sample s of pixel (x, y) is a pure function of (x, y, s): the planes are rendered after
+ * the fact by a kernel of their own, and the path-tracing kernels are not involved.
+ *
+ * For every pixel (px, py) of the context's rectangle (global coordinates), with B = crt_sample_offset, the camera rays of
+ * samples B + 1 .. B + n are taken in this order; each one's closest hit is found as crt_read_gbuffer finds it.  The
+ * sums start at +0; a hit does h++, st = st + t, sn = sn + normal, sa = sa + A[reflectance index] (per component), every
+ * step one binary32 operation.  Then alpha = (float)h / (float)n and, with h > 0, depth = st / (float)h,
+ * normal = sn / (float)h (not renormalised), albedo = sa / (float)h.
+ * n_samples > 0: that many samples for every pixel (also at sample 0 and in the adaptive state).  n_samples == 0: what
+ * the accumulator holds -- crt_sample_count in the uniform state (CRT_ESTATE at 0), in the adaptive state the count of
+ * the pixel's 8x8 tile; a tile that holds 0 samples gives the h = 0 outputs and alpha = 0 / 0, a NaN.
+ * A, the albedo table, has one row per spectra row: crt_spectrum_rgb of it, rebuilt by crt_upload_scene on the host.
+ * The row is taken by the hit primitive's reflectance index (data4.y) whatever its material: emitters and glass get the
+ * colour of their reflectance row too.
+ * A sync point like crt_read_gbuffer (what is in flight finishes first), and it only reads: the accumulator, the rgba8
+ * framebuffer, `sample`, the counters, the frame ring, the adaptive state and the filters' state and history stay as
+ * they are, and the next crt_trace / crt_trace_adaptive continues bit for bit.  A crt_set_tile rectangle is rendered on
+ * its own and equals the crop of the full frame.  The device planes belong to the context (allocated on first use, before
+ * anything is enqueued: CRT_ENOMEM leaves nothing behind), and go with it.
+ * CRT_ESTATE without a scene or accel structure, with a stale tree (crt_update_primitives, crt_remove_primitives, ...:
+ * crt_refit_accel first), and under a row-band partition where crt_read_gbuffer refuses; CRT_EINVAL for out == NULL or
+ * when B + n would pass 2^32 - 1.
+ * Out of scope: a frame-level form across a crt_comm_partition; feeding these planes into the library's own filters. */
+typedef struct {
+    uint32_t *hits;   /* tw*th    camera rays of the pixel that hit something, h                            */
+    float *alpha;     /* tw*th    (float)h / (float)n                                                       */
+    float *depth;     /* tw*th    mean t of the hits; 2139095040.0f (the kernels' CRT_INFINITY) at h = 0    */
+    float *normal;    /* tw*th*4  mean hit normal (not renormalised), channel 3 = +0; zeros at h = 0        */
+    float *albedo;    /* tw*th*4  mean albedo of the hit primitives, channel 3 = +0; zeros at h = 0         */
+} crt_aov_planes;     /* any pointer may be NULL (that plane is neither allocated nor stored); row-major over the
+                       * context's rectangle, row 0 = top */
+int crt_render_aovs(crt_ctx *ctx, uint32_t n_samples, const crt_aov_planes *out);
+/* One row of the albedo table (no context, no GPU): the reflectance spectrum[301] under an equal-energy illuminant with
+ * white Y = 1, as linear sRGB.  In binary64, k ascending from 0 to 300: X = sum (double)spectrum[k] * cieX[k + 40], Y and
+ * Z likewise, N = sum cieY[k + 40]; x = X / N, y = Y / N, z = Z / N; out[r] = (m0 x + m1 y) + m2 z with the XYZ -> linear
+ * sRGB matrix of the tone map (3.2404542, ...), each rounded once to float.  CRT_EINVAL for a NULL pointer. */
+int crt_spectrum_rgb(const float *spectrum /* 301 */, const float *cie /* 3*471 */, float out[3]);
+/* The table crt_render_aovs reads: nspectra*3 floats, row i = crt_spectrum_rgb of spectra row i.  No GPU work. */
+int crt_read_albedo_table(crt_ctx *ctx, float *out /* nspectra*3 */);
+
 /* ------------------------------------------------------------------ Scene edits
  * Move the camera or edit primitives and lights of the uploaded scene in place (DESIGN.md "Scene edits"), instead of
  * crt_upload_scene + crt_build_accel.  The tree's topology is kept; crt_refit_accel recomputes its boxes on the GPU.
