@@ -932,6 +932,62 @@ static napi_value js_render_aovs(napi_env env, napi_callback_info info)
     return undefined(env);
 }
 
+/* renderMattes(h, n, source, slots, {ids: Uint32Array(slots*tw*th), counts: Uint32Array(slots*tw*th), hits:
+ * Uint32Array(tw*th), overflow: Uint32Array(tw*th)}): the id mattes of n samples (0: what the accumulator holds) into the
+ * caller's typed arrays; source 0 = primitive, 1 = object (the id table), 2 = material; a plane left out is not rendered
+ * (include/crt.h "ID mattes").  Blocking. */
+static napi_value js_render_mattes(napi_env env, napi_callback_info info)
+{
+    ARGS(5)
+    crt_ctx *ctx = get_ctx(env, argv[0]);
+    if (!ctx) return NULL;
+    uint32_t n = 0, slots = 0, tl[4];
+    int32_t source = 0;
+    NAPI_OK(env, napi_get_value_uint32(env, argv[1], &n));
+    NAPI_OK(env, napi_get_value_int32(env, argv[2], &source));
+    NAPI_OK(env, napi_get_value_uint32(env, argv[3], &slots));
+    CRT_CHECK(env, ctx, "crt_tile", crt_tile(ctx, tl));
+    const size_t px = (size_t)tl[2] * tl[3];
+    static const char *names[4] = {"ids", "counts", "hits", "overflow"};
+    const size_t want[4] = {px * slots * 4, px * slots * 4, px * 4, px * 4};
+    void *p[4] = {NULL, NULL, NULL, NULL};
+    for (int i = 0; i < 4; i++) {
+        bool has = false;
+        napi_value v;
+        NAPI_OK(env, napi_has_named_property(env, argv[4], names[i], &has));
+        if (!has) continue;
+        NAPI_OK(env, napi_get_named_property(env, argv[4], names[i], &v));
+        size_t len = 0;
+        if (!get_bytes(env, v, &p[i], &len) || len != want[i]) {
+            char m[128];
+            snprintf(m, sizeof m, "renderMattes: %s must be a typed array of %zu bytes", names[i], want[i]);
+            napi_throw_type_error(env, NULL, m);
+            return NULL;
+        }
+    }
+    const crt_matte_planes out = {(uint32_t *)p[0], (uint32_t *)p[1], (uint32_t *)p[2], (uint32_t *)p[3]};
+    CRT_CHECK(env, ctx, "crt_render_mattes", crt_render_mattes(ctx, n, source, slots, &out));
+    return undefined(env);
+}
+
+/* setPrimitiveIds(h, first, Uint32Array): replaces entries [first, first + length) of the id table that source 1 reports
+ * (crt_set_primitive_ids); nothing else changes. */
+static napi_value js_set_primitive_ids(napi_env env, napi_callback_info info)
+{
+    ARGS(3)
+    crt_ctx *ctx = get_ctx(env, argv[0]);
+    if (!ctx) return NULL;
+    uint32_t first = 0;
+    NAPI_OK(env, napi_get_value_uint32(env, argv[1], &first));
+    void *p = NULL; size_t n = 0;
+    if (!get_bytes(env, argv[2], &p, &n) || n % 4) {
+        napi_throw_type_error(env, NULL, "setPrimitiveIds: ids must be a Uint32Array");
+        return NULL;
+    }
+    CRT_CHECK(env, ctx, "crt_set_primitive_ids", crt_set_primitive_ids(ctx, first, (uint32_t)(n / 4), n ? (const uint32_t *)p : NULL));
+    return undefined(env);
+}
+
 /* readMotion(h) -> Float32Array (tw*th*2): per pixel the film position (u, v) where the last denoiseTemporal looked for
  * it in the previous frame, NaN where there is none (include/crt.h crt_read_motion). */
 static napi_value js_read_motion(napi_env env, napi_callback_info info)
@@ -1606,6 +1662,7 @@ static napi_value init(napi_env env, napi_value exports)
         {"denoise", js_denoise}, {"denoiseLatest", js_denoise_latest}, {"denoiseLatestInto", js_denoise_latest_into},
         {"denoiseLatestAsync", js_denoise_latest_async},
         {"readGbuffer", js_read_gbuffer}, {"readMotion", js_read_motion}, {"renderAovs", js_render_aovs},
+        {"renderMattes", js_render_mattes}, {"setPrimitiveIds", js_set_primitive_ids},
         {"setCamera", js_set_camera}, {"updatePrimitives", js_update_primitives}, {"updateLights", js_update_lights},
         {"refitAccel", js_refit_accel},
         {"transformPrimitives", js_transform_primitives}, {"transformPrimitivesAsync", js_transform_primitives_async},

@@ -1,6 +1,6 @@
 """python -m computeraytracer_amd [--scene file.json] [--width W --height H] [--spp N] [--out image.png] [--denoise K] [--orbit N [--temporal [--variance] [--animate | --animate-device [--rebuild-pct P] | --blink P]]]
                                 [--adaptive THRESHOLD [--adaptive-filtered] [--adaptive-step N] [--counts-out counts.png]]
-                                [--alpha] [--aov-out PREFIX]
+                                [--alpha] [--aov-out PREFIX] [--matte-out PREFIX [--matte-source primitive|object|material] [--matte-slots K]]
 --adaptive goes with --orbit: every frame is sampled adaptively up to --spp, and with --denoise K --temporal [--variance] the
 temporal filters blend it with each pixel's own tile count (option "adaptive_temporal")."""
 import argparse
@@ -81,7 +81,19 @@ def parse_args(argv=None):
     ap.add_argument("--aov-out", default=None, metavar="PREFIX",
                     help="the feature planes of the samples the image holds (crt_render_aovs): PREFIX_albedo.png, "
                          "PREFIX_normal.png (n * 0.5 + 0.5) and PREFIX_depth.npy (also with --adaptive, not with --orbit)")
+    ap.add_argument("--matte-out", default=None, metavar="PREFIX",
+                    help="the id mattes of the samples the image holds (crt_render_mattes): PREFIX_ids.npy, PREFIX_counts.npy, "
+                         "PREFIX_overflow.npy and PREFIX_preview.png, the rank-0 id in false colour scaled by its coverage "
+                         "(also with --adaptive, not with --orbit)")
+    ap.add_argument("--matte-source", default="object", choices=("primitive", "object", "material"),
+                    help="with --matte-out: what an id is (default object: one per patch, sphere and mesh)")
+    ap.add_argument("--matte-slots", type=int, default=8, metavar="K",
+                    help="with --matte-out: ids kept per pixel, 1..16 (default 8); PREFIX_overflow.npy counts the hits left out")
     args = ap.parse_args(argv)
+    if args.matte_out and args.orbit is not None:
+        ap.error("--matte-out does not go with --orbit")
+    if not 1 <= args.matte_slots <= 16:
+        ap.error("--matte-slots must be 1..16")
     if (args.alpha or args.aov_out) and args.orbit is not None:
         ap.error("--alpha and --aov-out do not go with --orbit")
     if args.alpha and args.out.endswith(".ppm"):
@@ -231,7 +243,16 @@ def main(argv=None):
 
 
 def _aovs(r, args, rgba, info):
-    """--alpha and --aov-out: the feature planes of the samples the image holds; returns the rgba8 to write."""
+    """--alpha, --aov-out and --matte-out: the planes of the samples the image holds; returns the rgba8 to write."""
+    if args.matte_out:
+        planes = r.render_mattes(0, args.matte_source, args.matte_slots)
+        if args.adaptive is not None:                            # every pixel its own tile's count
+            import numpy as np
+            _, _, tw, th = r.tile
+            n = np.repeat(np.repeat(r.read_adaptive()[0], 8, 0), 8, 1)[:th, :tw]
+        else:
+            n = r.sample
+        info["matte_out"] = image.write_mattes(args.matte_out, planes, n)
     want = (("alpha",) if args.alpha else ()) + (("depth", "normal", "albedo") if args.aov_out else ())
     if not want:
         return rgba

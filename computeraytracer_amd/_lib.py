@@ -70,6 +70,9 @@ SIGNATURES = {
     "crt_render_aovs": (C.c_int, [_P, C.c_uint32, _P]),
     "crt_spectrum_rgb": (C.c_int, [_P, _P, _P]),
     "crt_read_albedo_table": (C.c_int, [_P, _P]),
+    "crt_render_mattes": (C.c_int, [_P, C.c_uint32, C.c_int, C.c_uint32, _P]),
+    "crt_set_primitive_ids": (C.c_int, [_P, C.c_uint32, C.c_uint32, _P]),
+    "crt_read_primitive_ids": (C.c_int, [_P, C.c_uint32, C.c_uint32, _P]),
     "crt_debug_intersect": (C.c_int, [_P, _P, C.c_size_t, _P]),
     "crt_debug_trace_rays": (C.c_int, [_P, _P, C.c_size_t, _P, _P]),
     "crt_debug_walk_rays": (C.c_int, [_P, C.c_int, _P, C.c_size_t, _P, _P]),
@@ -140,6 +143,11 @@ class DenoiseParams(C.Structure):
 class AovPlanes(C.Structure):
     """crt_aov_planes of include/crt.h."""
     _fields_ = [("hits", C.c_void_p), ("alpha", C.c_void_p), ("depth", C.c_void_p), ("normal", C.c_void_p), ("albedo", C.c_void_p)]
+
+
+class MattePlanes(C.Structure):
+    """crt_matte_planes of include/crt.h."""
+    _fields_ = [("ids", C.c_void_p), ("counts", C.c_void_p), ("hits", C.c_void_p), ("overflow", C.c_void_p)]
 
 
 class DenoiseAdaptiveParams(C.Structure):

@@ -234,6 +234,7 @@ int crt_upload_scene(crt_ctx *c, const void *primitives, size_t nprim, const voi
     c->dn.drop();
     c->prims.swap(prims);
     c->prims_moved = false;
+    matte_ids_identity(c);                                       // (host only: DESIGN.md 6o)
     c->lights.swap(lts);
     std::memcpy(c->camera, camera, sizeof c->camera);
     c->W = (uint32_t)camera[11];                                 // ComputeShader.wgsl:85

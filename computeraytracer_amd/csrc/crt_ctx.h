@@ -7,6 +7,7 @@
 //   crt_wf_driver.cpp   the wavefront driver (decisions: crt_wf_policy.h)
 //   crt_denoise_api.cpp the preview filters' entry points
 //   crt_aov_api.cpp     the feature planes' entry points
+//   crt_matte_api.cpp   the id mattes' entry points and the id table
 //   crt_debug.cpp       the debug read-outs
 #pragma once
 #include <hip/hip_runtime.h>
@@ -314,6 +315,15 @@ struct crt_ctx {
         DevBuf<float4> normal, albedo;
     } aov;
 
+    // The id mattes (crt_matte.hip).
+    std::vector<uint32_t> prim_ids; // the id table, beside `prims`: one id per primitive, the identity after crt_upload_scene;
+                                    // crt_set_primitive_ids replaces entries, the topology edits compact and extend it
+    DevBuf<uint32_t> d_prim_ids;    // ... on the device: made by the first crt_render_mattes of source OBJECT that needs it,
+                                    // dropped whenever the host table changes
+    struct Matte {                  // the planes of the tile, each allocated by the first call that asks for it
+        DevBuf<uint32_t> ids, counts, hits, overflow;
+    } matte;
+
     // scene edits (crt_refit.hip)
     float s_prims = 0.0f;           // max |corner coordinate| of the primitives: hit_pad = max(s_prims, |eye|) * 2^-17
     float tree_pad = 0.0f;          // the hit_pad the tree's boxes were made with (a larger one needs a refit)
@@ -424,6 +434,13 @@ int dn_adaptive_run(crt_ctx *c, const crt_denoise_adaptive_params &dp, bool rgba
 
 // crt_aov_api.cpp: the albedo table of a new scene (crt_upload_scene)
 void aov_rebuild_albedo(crt_ctx *c, const float *spectra, size_t nspectra, const float *cie);
+
+// crt_matte_api.cpp: the id table of a new scene (crt_upload_scene: the identity) and under the topology edits.  All host
+// only; each drops the device copy.  matte_ids_reserve is called before anything changes (it may throw std::bad_alloc).
+void matte_ids_identity(crt_ctx *c);
+void matte_ids_reserve(crt_ctx *c, size_t n_new);
+void matte_ids_remove(crt_ctx *c, const crt_prim_range *live, size_t m);      // ascending, disjoint, non-empty ranges
+void matte_ids_append(crt_ctx *c, uint32_t count);
 
 // crt_wf_driver.cpp
 struct AsBatch {                    // one batch of a crt_trace_adaptive call: its samples off + 1 .. off + n of every active tile

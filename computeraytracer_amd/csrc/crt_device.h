@@ -372,4 +372,20 @@ struct AovParams {
     int brute;                      // CRT_ACCEL_NONE: the reference's loop over every primitive
 };
 
+// k_matte (crt_matte.hip): the id mattes of the camera rays of samples first + 1 .. first + n of every pixel
+// of the rectangle.  A plane whose pointer is null is not stored.
+struct MatteParams {
+    const uint32_t *table;          // CRT_MATTE_OBJECT: the id table, one entry per primitive in array order; else unused
+    const uint32_t *counts;         // null: every pixel takes n; else per 8x8 tile of the rectangle, row-major, its n
+    uint32_t *ids;                  // slots planes of tw * th: plane r = the id of rank r (0xFFFFFFFF: no entry)
+    uint32_t *counts_out;           // slots planes: the camera rays that hit that id (0: no entry)
+    uint32_t *hits;                 // per pixel: h, the camera rays that hit something
+    uint32_t *overflow;             // per pixel: the hits whose id found no slot
+    uint32_t x0, y0, tw, th, tiles_x;
+    uint32_t first, n;
+    uint32_t slots;                 // 1 .. CRT_MATTE_MAX_SLOTS: entries of a pixel's table (sizes the kernel's dynamic LDS)
+    int source;                     // CRT_MATTE_PRIMITIVE, _OBJECT, _MATERIAL
+    int brute;                      // CRT_ACCEL_NONE: the reference's loop over every primitive
+};
+
 }  // namespace crt

@@ -1,4 +1,4 @@
-// crt_launch.h -- every host entry into the device code, declared once: the launchers of the nine .hip files, the GPU tree
+// crt_launch.h -- every host entry into the device code, declared once: the launchers of the ten .hip files, the GPU tree
 // builders and the level lists of the refit.  The .hip file that defines one and every host unit that calls one include
 // this header.  (Parameter structs: crt_device.h.)
 #pragma once
@@ -102,5 +102,8 @@ hipError_t dn_launch_motion(const DnReprojParams &P, float2 *out, hipStream_t st
 
 // crt_aov.hip
 hipError_t aov_launch(const DevScene &S, const AovParams &P, hipStream_t stream);
+
+// crt_matte.hip
+hipError_t matte_launch(const DevScene &S, const MatteParams &P, hipStream_t stream);
 
 }  // namespace crt

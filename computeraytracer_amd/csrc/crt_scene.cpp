@@ -813,6 +813,7 @@ int crt_remove_primitives(crt_ctx *c, const crt_prim_range *ranges, uint32_t n_r
         }
         c->prims.resize(n_new);
         for (size_t i = live[0].first; i < n_new; i++) c->prims[i].index = (uint32_t)i;
+        matte_ids_remove(c, live.data(), m);                     // the id table: compacted alike, a survivor keeps its id
     }
     return topo_commit(c, e, total != 0);
 }
@@ -844,6 +845,7 @@ int crt_append_primitives(crt_ctx *c, const void *records, uint32_t count, const
     CRT_TRY(topo_alloc(c, e, n_new, count ? grown(c->d_raw.n) : 0, count && keep ? grown(d.snap.n) : 0, count != 0));
     if (c->prims.capacity() < n_new)                             // (the mirror grows as d_raw does; std::bad_alloc: nothing has changed)
         c->prims.reserve(std::max(n_new, c->prims.capacity() + c->prims.capacity() / 2));
+    matte_ids_reserve(c, n_new);                                 // (and the id table beside it)
     CRT_TRY(prims_edit_history(c));
     if (count) {
         if (e.raw.p) {
@@ -859,6 +861,7 @@ int crt_append_primitives(crt_ctx *c, const void *records, uint32_t count, const
             HIPCHK(c, hipMemcpyAsync(d.snap.p + n * 80, records, (size_t)count * 80, hipMemcpyHostToDevice, c->stream));
         }
         c->prims.insert(c->prims.end(), np.begin(), np.end());
+        matte_ids_append(c, count);                              // primitive n + k gets the id n + k
     }
     return topo_commit(c, e, count != 0);
 }

@@ -56,6 +56,41 @@ def write_aovs(prefix: str, planes: dict) -> list:
     return [prefix + "_albedo.png", prefix + "_normal.png", prefix + "_depth.npy"]
 
 
+def id_colour(ids) -> np.ndarray:
+    """ids (uint32, any shape) -> (..., 3) uint8: a fixed hash of the id (the lowbias32 mixer), its three low bytes
+    lifted into 64..255 so that no id is dark."""
+    x = np.asarray(ids, np.uint32).astype(np.uint64)             # (64-bit products, masked back to 32 bits)
+    m = np.uint64(0xFFFFFFFF)
+    x ^= x >> np.uint64(16)
+    x = (x * np.uint64(0x7FEB352D)) & m
+    x ^= x >> np.uint64(15)
+    x = (x * np.uint64(0x846CA68B)) & m
+    x ^= x >> np.uint64(16)
+    rgb = np.stack([(x >> np.uint64(s)) & np.uint64(0xFF) for s in (0, 8, 16)], -1)
+    return (np.uint64(64) + rgb * np.uint64(3) // np.uint64(4)).astype(np.uint8)
+
+
+def id_preview(planes: dict, n) -> np.ndarray:
+    """A false-colour view of Renderer.render_mattes' dict, (H, W, 4) uint8, opaque: id_colour of each pixel's rank-0 id
+    scaled by that id's coverage count / n (n: a scalar or an (H, W) array); black where the pixel has no entry."""
+    ids, counts = np.asarray(planes["ids"])[0], np.asarray(planes["counts"])[0]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        cov = counts.astype(np.float32) / np.asarray(n).astype(np.float32)
+    rgb = id_colour(ids).astype(np.float32) / np.float32(255) * np.where(counts > 0, cov, np.float32(0))[..., None]
+    return unorm8(np.concatenate([rgb, np.ones(ids.shape + (1,), np.float32)], -1))
+
+
+def write_mattes(prefix: str, planes: dict, n) -> list:
+    """PREFIX_ids.npy, PREFIX_counts.npy, PREFIX_overflow.npy (the planes as they are) and PREFIX_preview.png (id_preview)
+    from Renderer.render_mattes' dict; returns the paths written."""
+    paths = []
+    for p in ("ids", "counts", "overflow"):
+        np.save(f"{prefix}_{p}.npy", planes[p])
+        paths.append(f"{prefix}_{p}.npy")
+    write_png(prefix + "_preview.png", id_preview(planes, n))
+    return paths + [prefix + "_preview.png"]
+
+
 def save_checkpoint(path: str, renderer) -> None:
     """alt_color_buffer + sample: everything needed to resume."""
     np.savez_compressed(path, accum=renderer.read_accum(), sample=np.uint32(renderer.sample), tile=np.asarray(renderer.tile))

@@ -20,6 +20,9 @@ from .scene import PackedScene
 _ACCEL = {"none": ACCEL_NONE, "brute": ACCEL_NONE, "bvh2": ACCEL_BVH2, "bvh": ACCEL_BVH2, "lbvh": ACCEL_LBVH, ACCEL_LBVH: ACCEL_LBVH,
           "ploc": ACCEL_PLOC, ACCEL_PLOC: ACCEL_PLOC, ACCEL_NONE: ACCEL_NONE, ACCEL_BVH2: ACCEL_BVH2}
 AOV_PLANES = ("hits", "alpha", "depth", "normal", "albedo")
+MATTE_PLANES = ("ids", "counts", "hits", "overflow")
+MATTE_SOURCES = {"primitive": 0, "object": 1, "material": 2}
+MATTE_NONE = 0xFFFFFFFF          # the id of a rank without an entry
 
 
 def spectrum_rgb(spectrum, cie) -> np.ndarray:
@@ -34,6 +37,16 @@ def spectrum_rgb(spectrum, cie) -> np.ndarray:
     if rc != 0:
         raise CrtError(rc, "crt_spectrum_rgb failed")
     return out
+
+
+def matte_coverage(planes: dict, n, id: int) -> np.ndarray:
+    """(H, W) float32: the share of each pixel's n camera rays that hit `id`, count / n as one float32 division, from
+    Renderer.render_mattes' dict (0 where the id holds no rank).  n is the sample count the planes were rendered with: a
+    scalar, or an (H, W) array in the adaptive state (each pixel its tile's count; 0 / 0 is NaN)."""
+    ids, counts = np.asarray(planes["ids"]), np.asarray(planes["counts"])
+    count = np.where(ids == np.uint32(id), counts, np.uint32(0)).sum(axis=0, dtype=np.uint32)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return (count.astype(np.float32) / np.asarray(n).astype(np.float32)).astype(np.float32)
 
 
 class Renderer:
@@ -85,6 +98,8 @@ class Renderer:
                                              spectra.ctypes.data, spectra.size // 301,
                                              cie.ctypes.data, cam.ctypes.data))
         self.scene = ps
+        if getattr(ps, "object_ids", None) is not None:
+            self.set_primitive_ids(0, ps.object_ids)
         return self
 
     def set_tile(self, x0: int, y0: int, x1: int, y1: int):
@@ -532,6 +547,40 @@ class Renderer:
             raise ValueError("upload a scene first")
         out = np.empty((np.asarray(self.scene.spectra).size // 301, 3), np.float32)
         self._chk(self._lib.crt_read_albedo_table(self._h, out.ctypes.data))
+        return out
+
+    # -- id mattes (include/crt.h, "ID mattes")
+    def render_mattes(self, n_samples: int = 0, source="object", slots: int = 8, planes=MATTE_PLANES) -> dict:
+        """The id mattes of the tile (crt_render_mattes) over the camera rays of n_samples samples from the sample offset
+        on; n_samples = 0: the samples the accumulator holds (in the adaptive state each 8x8 tile's own count).  source:
+        "primitive", "object" (the id table: set_primitive_ids) or "material".  A dict of the planes asked for, all
+        uint32: ids and counts (slots, H, W), rank 0 first, MATTE_NONE / 0 where a rank has no entry; hits and overflow
+        (H, W).  matte_coverage turns an id's counts into its coverage.  Finishes what is in flight; only reads."""
+        _, _, tw, th = self.tile
+        unknown = [p for p in planes if p not in MATTE_PLANES]
+        if unknown:
+            raise ValueError(f"unknown planes {unknown}: choose from {MATTE_PLANES}")
+        if source not in MATTE_SOURCES and source not in MATTE_SOURCES.values():
+            raise ValueError(f"unknown source {source!r}: choose from {tuple(MATTE_SOURCES)}")
+        out = {p: np.empty((int(slots), th, tw) if p in ("ids", "counts") else (th, tw), np.uint32)
+               for p in MATTE_PLANES if p in planes}
+        arg = _lib.MattePlanes(**{p: a.ctypes.data for p, a in out.items()})
+        self._chk(self._lib.crt_render_mattes(self._h, int(n_samples), int(MATTE_SOURCES.get(source, source)), int(slots), C.byref(arg)))
+        return out
+
+    def set_primitive_ids(self, first: int, ids):
+        """Replace entries [first, first + len(ids)) of the id table (crt_set_primitive_ids): the ids source "object"
+        reports.  Touches nothing else: no reset, no stale tree."""
+        a = np.ascontiguousarray(ids, np.uint32).reshape(-1)
+        self._chk(self._lib.crt_set_primitive_ids(self._h, int(first), len(a), a.ctypes.data if len(a) else None))
+        return self
+
+    def primitive_ids(self, first: int = 0, count: int | None = None) -> np.ndarray:
+        """Entries [first, first + count) of the id table (uint32; count None: to the end).  No GPU work."""
+        if count is None:
+            count = len(self.scene.primitives) - int(first)
+        out = np.zeros(int(count), np.uint32)
+        self._chk(self._lib.crt_read_primitive_ids(self._h, int(first), int(count), out.ctypes.data if count else None))
         return out
 
     # -- multi-GPU: the frame across the ranks of a communicator (include/crt.h, "Multi-GPU")

@@ -67,6 +67,7 @@ class PackedScene:
     cie: np.ndarray                   # float32 [3, 471]
     patches: np.ndarray = field(default_factory=lambda: np.zeros(0, PATCH_DTYPE))
     spectrum_index: dict = field(default_factory=dict)
+    object_ids: np.ndarray | None = None   # uint32 [nprim]: the id of each primitive's object (None: the identity)
 
     @property
     def width(self) -> int:
@@ -81,7 +82,7 @@ class PackedScene:
         cam[11] = width
         cam[12] = height
         return PackedScene(self.primitives, self.lights, cam, self.spectra, self.cie,
-                           self.patches, self.spectrum_index)
+                           self.patches, self.spectrum_index, self.object_ids)
 
 
 # --------------------------------------------------------------------------- spectra
@@ -311,11 +312,17 @@ def expand_meshes(scene: dict, base_dir: str | None = None) -> list:
 
 def pack_scene(scene: dict, cie: np.ndarray | None = None, base_dir: str | None = None) -> PackedScene:
     """Flatten (main.js:114-137) and pack (main.js:138-393) a scene dict in the
-    reference's JSON schema."""
+    reference's JSON schema.  object_ids: one id per patch, sphere, loose triangle and mesh, counted in primitive order
+    (every triangle of a mesh carries the mesh's id)."""
     objects = scene.get("objects", {})
     patches = objects.get("patches", [])
     spheres = objects.get("spheres", [])
-    tris = list(objects.get("triangles", [])) + expand_meshes(scene, base_dir)
+    loose = list(objects.get("triangles", []))
+    meshes = [expand_meshes({"objects": {"meshes": [m]}}, base_dir) for m in objects.get("meshes", [])]
+    tris = loose + [t for m in meshes for t in m]
+    single = len(patches) + len(spheres) + len(loose)
+    object_ids = np.concatenate([np.arange(single, dtype=np.uint32)]
+                                + [np.full(len(m), single + j, np.uint32) for j, m in enumerate(meshes)])
     spectra, key_index = resample_spectra(scene["spectra"])
 
     def names(items, key):
@@ -351,7 +358,7 @@ def pack_scene(scene: dict, cie: np.ndarray | None = None, base_dir: str | None 
 
     return PackedScene(primitives=prims, lights=lights_of(prims), camera=pack_camera(scene["camera"]),
                        spectra=spectra, cie=cie if cie is not None else load_cie(),
-                       patches=pp, spectrum_index=key_index)
+                       patches=pp, spectrum_index=key_index, object_ids=object_ids)
 
 
 def load_scene(path: str | None = None) -> dict:

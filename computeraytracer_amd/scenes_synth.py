@@ -160,6 +160,13 @@ def atrium250k(width: int = 1920, height: int = 1080) -> PackedScene:
                            np.concatenate(refl))
 
 
+def atrium250k_object_ids() -> np.ndarray:
+    """The object id of every primitive of atrium250k (uint32 [253 958]; Renderer.set_primitive_ids, or PackedScene's
+    object_ids): patches 0..5 keep 0..5, the 131 072 floor triangles are object 6, column k is object 7 + k."""
+    return np.concatenate([np.arange(6, dtype=np.uint32), np.full(131072, 6, np.uint32),
+                           np.repeat(np.arange(7, 71, dtype=np.uint32), 1920)])
+
+
 # --------------------------------------------------------------------------- S3
 def soup(n: int = 10_000_000, width: int = 1920, height: int = 1080, seed: int = SEED_SOUP) -> PackedScene:
     """S3: n random triangles, v0 ~ U[0,555]^3, e1,e2 ~ U[-2,2]^3, reflectance uniform over

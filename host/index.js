@@ -25,6 +25,9 @@
 // --aov-out PREFIX: the feature planes of the samples the image holds (renderAovs(0); also with --adaptive, not with
 //            --orbit), each as the raw bytes of its typed array: PREFIX_hits.bin (u32), PREFIX_alpha.bin, PREFIX_depth.bin
 //            (f32), PREFIX_normal.bin, PREFIX_albedo.bin (4 x f32 per pixel)
+// --matte-out PREFIX [--matte-source primitive|object|material] [--matte-slots K]: the id mattes of the samples the image
+//            holds (renderMattes(0); also with --adaptive, not with --orbit), each as the raw bytes of its Uint32Array:
+//            PREFIX_ids.bin, PREFIX_counts.bin (K planes, rank 0 first), PREFIX_hits.bin, PREFIX_overflow.bin
 const fs = require('fs');
 const { Main, writePPM, orbitCameras } = require('./main');
 const sceneLoader = require('./sceneLoader');
@@ -63,12 +66,18 @@ if (clip !== null && !(args.temporal && Number.isInteger(clip) && clip >= 25 && 
   console.error('--clip [PCT] goes with --orbit N --denoise K --temporal, PCT in 25..10000'); process.exit(2);
 }
 if ('aov-out' in args && (args.orbit || args['aov-out'] === true)) { console.error('--aov-out PREFIX writes the planes of one frame: give it a prefix, and no --orbit'); process.exit(2); }
+if ('matte-out' in args && (args.orbit || args['matte-out'] === true)) { console.error('--matte-out PREFIX writes the mattes of one frame: give it a prefix, and no --orbit'); process.exit(2); }
 const r = Main({ sceneFile: args.scene, width: args.width ? num('width') : undefined, height: args.height ? num('height') : undefined,
   accel: args.accel || 'bvh2', device: num('device', 0) });
 function writeAovs() {
   if (!('aov-out' in args)) return;
   for (const [name, plane] of Object.entries(r.renderAovs(0)))
     fs.writeFileSync(`${args['aov-out']}_${name}.bin`, Buffer.from(plane.buffer, plane.byteOffset, plane.byteLength));
+}
+function writeMattes() {
+  if (!('matte-out' in args)) return;
+  for (const [name, plane] of Object.entries(r.renderMattes(0, args['matte-source'] || 'object', num('matte-slots', 8))))
+    fs.writeFileSync(`${args['matte-out']}_${name}.bin`, Buffer.from(plane.buffer, plane.byteOffset, plane.byteLength));
 }
 // --adaptive: rounds of --adaptive-step samples until no tile is active; {rounds, ad: readAdaptive(), pixelSamples}
 function adaptiveRounds() {
@@ -112,6 +121,7 @@ if ('adaptive' in args) {
   const seconds = Number(process.hrtime.bigint() - t1) / 1e9;
   if (args.out) writePPM(args.out, 'denoise' in args ? r.denoiseAdaptive({ iterations: num('denoise') }) : r.readRgba8(), r.width, r.height);
   writeAovs();
+  writeMattes();
   const mid = counts.length >> 1, median = counts.length % 2 ? counts[mid] : (counts[mid - 1] + counts[mid]) / 2;
   console.log(JSON.stringify({ width: r.width, height: r.height, adaptive: num('adaptive'), rounds, pixel_samples: pixelSamples, seconds,
     tile_samples: { min: counts[0], median, max: counts[counts.length - 1] }, ...('denoise' in args ? { denoise: num('denoise') } : {}) }));
@@ -126,6 +136,7 @@ const c = r.counters();
 const rgba = r.readRgba8();
 if (args.out) writePPM(args.out, 'denoise' in args ? r.denoise({ iterations: num('denoise') }) : rgba, r.width, r.height);
 writeAovs();
+writeMattes();
 if (args.dump) {
   fs.writeFileSync(`${args.dump}.rgba8.bin`, Buffer.from(rgba.buffer));
   fs.writeFileSync(`${args.dump}.accum.bin`, Buffer.from(r.readAccum().buffer));

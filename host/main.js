@@ -37,6 +37,7 @@ function Main(options = {}) {
 
   const device = a.create(options.device || 0);
   a.uploadScene(device, packed.primitives, packed.lights, packed.spectra, packed.cie, packed.camera);
+  a.setPrimitiveIds(device, 0, packed.objectIds); // what renderMattes' source 'object' reports (host only)
   if (options.tile) a.setTile(device, ...options.tile);
   a.buildAccel(device, ACCEL[options.accel || 'bvh2']);
 
@@ -81,6 +82,22 @@ function Main(options = {}) {
       a.renderAovs(device, n, out);
       return out;
     },
+    // id mattes (include/crt.h "ID mattes"): per pixel the ids its camera rays hit, ranked by how many rays hit each, over
+    // n samples (0: the samples the accumulator holds); source 'primitive' | 'object' (the id table) | 'material'; ids and
+    // counts are `slots` planes of tw * th, rank 0 first (0xFFFFFFFF / 0: no entry); reads only
+    renderMattes: (n = 0, source = 'object', slots = 8, planes = ['ids', 'counts', 'hits', 'overflow']) => {
+      const src = ['primitive', 'object', 'material'].indexOf(source);
+      if (src < 0) throw new TypeError(`renderMattes: unknown source ${source}`);
+      const [, , tw, th] = a.tile(device), out = {};
+      for (const p of planes) {
+        if (!['ids', 'counts', 'hits', 'overflow'].includes(p)) throw new TypeError(`renderMattes: unknown plane ${p}`);
+        out[p] = new Uint32Array(tw * th * (p === 'ids' || p === 'counts' ? slots : 1));
+      }
+      a.renderMattes(device, n, src, slots, out);
+      return out;
+    },
+    // entries [first, first + ids.length) of the id table source 'object' reports; nothing else changes
+    setPrimitiveIds: (first, ids) => a.setPrimitiveIds(device, first, ids instanceof Uint32Array ? ids : Uint32Array.from(ids)),
     // scene edits (include/crt.h "Scene edits"): each finishes what is in flight and restarts the accumulation;
     // the reference's queue.writeBuffer of the camera / primitive / light buffer
     setCamera: (camera) => a.setCamera(device, camera),

@@ -158,10 +158,23 @@ function pack(scene, cie, baseDir) {
     writeRecord(lights, i * 80, 0, d1, d2, d3, idx(p.emission), idx(p.reflectance), type(p.type), p.index);
   });
 
+  // one object id per patch, sphere, loose triangle and mesh, in primitive order (crt_set_primitive_ids): every triangle
+  // of a mesh carries the mesh's id
+  const ob = scene.objects || {};
+  const single = (ob.patches || []).length + (ob.spheres || []).length + (ob.triangles || []).length;
+  const objectIds = new Uint32Array(prims.length);
+  for (let i = 0; i < single; i++) objectIds[i] = i;
+  let at = single;
+  (ob.meshes || []).forEach((m, j) => {
+    const k = expandMeshes({ objects: { meshes: [m] } }, baseDir).length;
+    objectIds.fill(single + j, at, at + k);
+    at += k;
+  });
+
   const c = scene.camera; // main.js:313-324
   const camera = new Float32Array([...c.eye, 0, ...c.lookat, 0, ...c.up, c.width, c.height, c.focalLength, 0, 0]);
 
-  return { primitives, patches, lights, camera, spectra, cie: cie || loadCie(), keyIndex, width: c.width, height: c.height };
+  return { primitives, patches, lights, camera, spectra, cie: cie || loadCie(), keyIndex, objectIds, width: c.width, height: c.height };
 }
 
 function loadScene(file) {

@@ -320,6 +320,64 @@ int crt_spectrum_rgb(const float *spectrum /* 301 */, const float *cie /* 3*471 
 /* The table crt_render_aovs reads: nspectra*3 floats, row i = crt_spectrum_rgb of spectra row i.  No GPU work. */
 int crt_read_albedo_table(crt_ctx *ctx, float *out /* nspectra*3 */);
 
+/* ------------------------------------------------------------------ ID mattes
+ * What compositing asks for to isolate one object: per pixel, which ids its camera rays hit and how many
+ * rays hit each -- an anti-aliased matte per primitive, object or material, in the Cryptomatte style.  crt_read_gbuffer
+ * reports one primitive per pixel, from one ray; the planes of crt_render_aovs average over primitives without saying
+ * which.  Like those planes the mattes are rendered after the fact, over the very camera rays the image holds, by a
+ * kernel of their own; every output is an integer.
+ *
+ * Rays.  For every pixel of the context's rectangle, with B = crt_sample_offset, the camera rays of samples B + 1 .. B + n
+ * are taken in this order; each one's closest hit is found exactly as crt_render_aovs finds it (the reference's loop over
+ * every primitive under CRT_ACCEL_NONE and for a non-finite ray).  n is crt_render_aovs': n_samples > 0 is that many
+ * samples for every pixel (also at sample 0 and in the adaptive state); n_samples == 0 is what the accumulator holds --
+ * crt_sample_count in the uniform state (CRT_ESTATE at 0), in the adaptive state the count of the pixel's 8x8 tile.
+ * The id of a hit of the primitive at array position i, by `source`:
+ *   CRT_MATTE_PRIMITIVE  i
+ *   CRT_MATTE_OBJECT     entry i of the id table (below)
+ *   CRT_MATTE_MATERIAL   material << 24 | reflectance index (data4.z, data4.y): the key the preview filters compare
+ * The table.  Each pixel keeps a table of `slots` entries (1 .. CRT_MATTE_MAX_SLOTS), empty at the start.  For every hit,
+ * in sample order: h++; if the id is in the table its count goes up by one; else, if the table holds fewer than `slots`
+ * entries, the entry (id, 1) is added; else overflow++.
+ * Ranking.  The entries are ranked by count descending, equal counts by id ascending (unsigned); rank r goes to plane r.
+ * A rank without an entry holds id 0xFFFFFFFF and count 0.
+ * So for every pixel: sum of counts + overflow = hits <= n.  With overflow == 0 the result is the exact ranking over all
+ * the ids the pixel saw and does not depend on the sample order.  With overflow > 0 it is NOT: an id that first appeared
+ * after the table had filled is counted in `overflow` only, however many rays hit it, and the ranking is that of the
+ * first `slots` ids in sample order -- ask for more slots.  The coverage of an id is count / n; the C call returns
+ * integers only and the bindings divide.
+ * The contract is crt_render_aovs': a sync point; it only reads -- the accumulator, the rgba8 framebuffer, `sample`, the
+ * counters, the frame ring, the adaptive state and the filters' state and history stay as they are, and the next
+ * crt_trace / crt_trace_adaptive continues bit for bit; a crt_set_tile rectangle equals the crop of the full frame; the
+ * device planes belong to the context and every allocation is made before anything is enqueued (CRT_ENOMEM leaves
+ * nothing behind).  CRT_ESTATE in crt_render_aovs' cases: no scene or accel structure, a stale tree, row bands,
+ * n_samples == 0 at sample 0, the adaptive state after a call that failed part-way.  CRT_EINVAL for out == NULL, slots
+ * outside 1 .. 16, an unknown source, or when B + n would pass 2^32 - 1.
+ * Out of scope: a frame-level form across a crt_comm_partition; Cryptomatte / EXR files; the exact ranking of a pixel
+ * that sees more than `slots` ids; editing ids on the device; feeding ids into the library's own filters. */
+enum { CRT_MATTE_PRIMITIVE = 0, CRT_MATTE_OBJECT = 1, CRT_MATTE_MATERIAL = 2 };
+#define CRT_MATTE_MAX_SLOTS 16
+typedef struct {
+    uint32_t *ids;       /* slots*tw*th  plane r (tw*th values, row-major, row 0 = top) = the id of rank r; 0xFFFFFFFF = no entry */
+    uint32_t *counts;    /* slots*tw*th  camera rays of the pixel that hit that id; 0 where there is no entry */
+    uint32_t *hits;      /* tw*th        camera rays that hit anything: crt_render_aovs' hits plane */
+    uint32_t *overflow;  /* tw*th        hits whose id found no slot (above) */
+} crt_matte_planes;      /* any pointer may be NULL: that plane is neither allocated nor stored */
+int crt_render_mattes(crt_ctx *ctx, uint32_t n_samples, int source, uint32_t slots, const crt_matte_planes *out);
+/* The id table: one uint32_t per primitive, on the host beside the records.  crt_upload_scene makes it the identity
+ * (entry i = i); the device copy is made by the first crt_render_mattes of source OBJECT that needs it and dropped
+ * whenever the table changes, so the upload and the scene edits allocate on the device what they did without it.
+ * crt_set_primitive_ids replaces entries [first, first+count) and touches nothing else: the accumulator is not reset, the
+ * tree does not go stale, no history is dropped.  CRT_EINVAL, with nothing changed, for a range outside the scene, ids ==
+ * NULL with count > 0, or an id of 0xFFFFFFFF (reserved for "no entry"); CRT_ESTATE without a scene.
+ * crt_read_primitive_ids copies from the host table: no GPU work, the same range checks.
+ * Under the scene edits: crt_update_primitives and crt_transform_primitives leave the table alone;
+ * crt_remove_primitives compacts it exactly as it compacts the records (a survivor keeps its id); crt_append_primitives
+ * gives appended primitive nprim + k the id nprim + k (the caller then sets the ids it wants).  The host memory the table
+ * needs is reserved before anything changes, and a refused edit leaves the table as it was. */
+int crt_set_primitive_ids(crt_ctx *ctx, uint32_t first, uint32_t count, const uint32_t *ids);
+int crt_read_primitive_ids(crt_ctx *ctx, uint32_t first, uint32_t count, uint32_t *out);
+
 /* ------------------------------------------------------------------ Scene edits
  * Move the camera or edit primitives and lights of the uploaded scene in place (DESIGN.md "Scene edits"), instead of
  * crt_upload_scene + crt_build_accel.  The tree's topology is kept; crt_refit_accel recomputes its boxes on the GPU.
