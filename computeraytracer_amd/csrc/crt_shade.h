@@ -129,6 +129,57 @@ __device__ __forceinline__ bool hit_test_rec(const float4 A, const float4 B, con
     return true;
 }
 
+// Straight-line forms of the triangle and the patch test for k_wf_trace2's task round (CRT_WF_T2_FLAT): the
+// operations of hit_test_rec<false> in its order on its operands, every quantity computed by every lane, the rejects
+// gathered into the one predicate that is returned with t.  A lane hit_test_rec would have turned away early computes
+// values nobody reads (a division by zero gives an infinity or a NaN here, no trap); the caller selects (t, index, slot)
+// into its best hit where the predicate holds.  `&` and `|` on purpose: `&&` is a branch per term.
+__device__ __forceinline__ bool beats_flat(float t, float t_min, float t_max, uint32_t index, uint32_t b_index, uint32_t b_slot)
+{
+    return (t >= t_min) & ((t < t_max) | ((t == t_max) & ((b_slot == kNoHit) | (index > b_index))));
+}
+
+__device__ __forceinline__ bool tri_accepts_flat(const float4 A, const float4 B, const float4 C, float hit_pad, f3 o, f3 d,
+                                                 uint32_t exclude, float t_min, float t_max, uint32_t b_index, uint32_t b_slot, float &t)
+{
+    const uint32_t index = f_bits(B.w);
+    const f3 v0 = xyz(A), e1 = xyz(B), e2 = xyz(C);
+    const f3 pvec = cross(d, e2);
+    const float det = dot(e1, pvec);
+    const float inv = 1.0f / det;
+    const f3 tvec = o - v0;
+    const float u = dot(tvec, pvec) * inv;
+    const f3 qvec = cross(tvec, e1);
+    const float v = dot(d, qvec) * inv;
+    t = dot(e2, qvec) * inv;
+    const f3 p = ray_at(o, d, t);
+    const f3 v1 = v0 + e1, v2 = v0 + e2;
+    const f3 lo = f3{min_(v0.x, min_(v1.x, v2.x)) - hit_pad, min_(v0.y, min_(v1.y, v2.y)) - hit_pad, min_(v0.z, min_(v1.z, v2.z)) - hit_pad};
+    const f3 hi = f3{max_(v0.x, max_(v1.x, v2.x)) + hit_pad, max_(v0.y, max_(v1.y, v2.y)) + hit_pad, max_(v0.z, max_(v1.z, v2.z)) + hit_pad};
+    const bool in = (p.x >= lo.x) & (p.x <= hi.x) & (p.y >= lo.y) & (p.y <= hi.y) & (p.z >= lo.z) & (p.z <= hi.z);
+    const bool wins = beats_flat(t, t_min, t_max, index, b_index, b_slot);
+    return (exclude != index) & (det != 0.0f) & (u >= 0.0f) & (u <= 1.0f) & (v >= 0.0f) & ((u + v) <= 1.0f) & wins & in;
+}
+
+__device__ __forceinline__ bool patch_accepts_flat(const float4 A, const float4 B, const float4 C, const float4 D, f3 o, f3 d,
+                                                   uint32_t exclude, float t_min, float t_max, uint32_t b_index, uint32_t b_slot, float &t)
+{
+    const uint32_t index = f_bits(B.w);
+    f3 n = xyz(D);
+    float ndotd = dot(n, d);
+    const bool flip = ndotd > 0.0f;                            // :541-545
+    n = f3{flip ? -n.x : n.x, flip ? -n.y : n.y, flip ? -n.z : n.z};
+    ndotd = flip ? -ndotd : ndotd;
+    const f3 P0 = xyz(A);
+    t = dot(n, P0 - o) / ndotd;                                // :554
+    const f3 m = ray_at(o, d, t) - P0;
+    const float u = dot(m, xyz(B)) / D.w;                      // :563
+    const float v = dot(m, xyz(C)) / C.w;                      // :564
+    const bool grazing = abs_(ndotd) < 0.0001f;                // :546
+    const bool wins = beats_flat(t, t_min, t_max, index, b_index, b_slot);
+    return (exclude != index) & !grazing & wins & !((u < 0.0f) | (u > 1.0f) | (v < 0.0f) | (v > 1.0f));
+}
+
 // The same with the record fetched from the scene (primD only for a patch that is not excluded).
 template <bool LITERAL>
 __device__ __forceinline__ bool hit_test(const DevScene &S, uint32_t slot, f3 o, f3 d, uint32_t exclude,

@@ -1596,6 +1596,33 @@ __global__ __launch_bounds__(64, CRT_WF_MIN_WAVES) void k_wf_trace(const WfParam
 #ifndef CRT_WF_STALL_AT
 #define CRT_WF_STALL_AT 16
 #endif
+// Four compile-time variants of what k_wf_trace2 spends AROUND its node and leaf steps (the same rays get the
+// same answers under every combination, profiles/trace2_passes.txt has each one's A/B):
+//  CRT_WF_T2_DOUBLE     an inner pass that starts with CRT_WF_T2_DOUBLE_AT lanes on an inner node takes two node steps behind one
+//                       set of ballots and break / leaf-round / pick-up tests.  ON: -5 % SALU and -2.6 % VALU instructions, the
+//                       step 0.6-1.0 ms shorter; any threshold from 1 to 48 measures the same.
+//  CRT_WF_T2_FLAT       the triangle and patch tests of the task round in their straight-line forms (crt_shade.h); 2: the
+//                       triangle test only.  OFF: alone the patch form spills (48 B of scratch for 12, +19 % vector loads, +5 % on
+//                       the launch); beside the double step it does not, and measures -0.35 ms: inside the noise.
+//  CRT_WF_T2_LATE_SLOT  the task round keeps the winner's index only (it is in the key); a shadow ray's any-hit is decided by
+//                       index, and the slot P.hit wants is looked up once, when an extension ray is through.  OFF: -10 % LDS
+//                       instructions, but the look-up is +10 % vector loads and the launch +5 %.
+//  CRT_WF_T2_SETUP64    (not built: the ring's refills are all full at 32 and fewer than 32 lanes are idle then, 5.12.)
+#ifndef CRT_WF_T2_DOUBLE
+#define CRT_WF_T2_DOUBLE 1
+#endif
+#ifndef CRT_WF_T2_DOUBLE_AT
+#define CRT_WF_T2_DOUBLE_AT 40
+#endif
+#ifndef CRT_WF_T2_FLAT
+#define CRT_WF_T2_FLAT 0
+#endif
+#ifndef CRT_WF_T2_LATE_SLOT
+#define CRT_WF_T2_LATE_SLOT 0
+#endif
+#if defined(CRT_WF_T2_SETUP64) && CRT_WF_T2_SETUP64
+#error "CRT_WF_T2_SETUP64 was not built (DESIGN.md 5.12): the ring set-up stays at 32 lanes"
+#endif
 constexpr int kStk2 = kWfStackLds2;
 #ifndef CRT_WF_RING
 #define CRT_WF_RING 32
@@ -1630,7 +1657,9 @@ __global__ __launch_bounds__(64, CRT_WF_T2_WAVES) void k_wf_trace2(const WfParam
     __shared__ float4 ring[4][kRing2];           // ready rays: (o, exclude) (d, slot | shadow << 31) (id', t_max) (oid', -)
     __shared__ uint2 ring_l[kRing2];             //             (b_index, b_slot): the light's primitive for a shadow ray
     __shared__ unsigned long long cell[64];      // per lane: hit_key of its ray's best hit so far
+#if !CRT_WF_T2_LATE_SLOT
     __shared__ uint32_t cslot[64];               // ... and that primitive's slot
+#endif
     __shared__ uint2 tasks[64];                  // (primitive slot, owner lane): written by the owner, so a task lane's loads start after ONE DS read
     WfCtl *ctl = P.ctl;
     const uint4 *__restrict__ nodesq = P.sc.nodes4q;
@@ -1670,7 +1699,11 @@ __global__ __launch_bounds__(64, CRT_WF_T2_WAVES) void k_wf_trace2(const WfParam
     bool active = false;
     int pend = 0;                                   // a leaf put aside, 0 = none
     f3 o = f3{0, 0, 0}, d = f3{0, 0, 0}, id = f3{0, 0, 0}, oid = f3{0, 0, 0};
-    uint32_t excl = 0, slot = 0, b_index = kNoHit, b_slot = kNoHit, b_slot_in = kNoHit;
+    uint32_t excl = 0, slot = 0, b_index = kNoHit;
+    uint32_t b_in = kNoHit;                          // the light's primitive as a shadow ray brings it: its slot (CRT_WF_T2_LATE_SLOT: its index)
+#if !CRT_WF_T2_LATE_SLOT
+    uint32_t b_slot = kNoHit;
+#endif
     float t_max = 0.0f;
     bool shadow = false;
     int node = kNoNode, sp = 0;
@@ -1678,6 +1711,16 @@ __global__ __launch_bounds__(64, CRT_WF_T2_WAVES) void k_wf_trace2(const WfParam
     uint32_t c_nodes = 0, c_prims = 0;
     uint32_t d_inner_it = 0, d_inner_act = 0, d_leaf_it = 0, d_leaf_act = 0, d_prim_it = 0, d_refill = 0, d_refill_lanes = 0, d_scans = 0;   // lane 0 only
     uint32_t d_max_sp = 0;                           // COUNT: the deepest stack this lane reached
+    // the ray is through: its visibility bit / (t, slot) go out
+    auto ray_out = [&]() {
+#if CRT_WF_T2_LATE_SLOT
+        if (shadow) stnt(&g_vis[slot], (b_index == b_in) ? 1u : 0u);
+        else stnt(&g_hit[slot], float2{t_max, bits_f(b_index == kNoHit ? kNoHit : P.sc.slot_of_index[b_index])});   // the one look-up per ray
+#else
+        if (shadow) stnt(&g_vis[slot], (b_slot == b_in) ? 1u : 0u);
+        else stnt(&g_hit[slot], float2{t_max, bits_f(b_slot)});
+#endif
+    };
 
     for (;;) {
         // ---- idle lanes pick ready rays up from the ring; an empty ring is refilled with the next chunk first
@@ -1771,8 +1814,14 @@ __global__ __launch_bounds__(64, CRT_WF_T2_WAVES) void k_wf_trace2(const WfParam
                     oid = xyz(R3);
                     const uint32_t sg = f_bits(R3.w);
                     gx = (sg & 1u) != 0u; gy = (sg & 2u) != 0u; gz = (sg & 4u) != 0u;
-                    b_index = RL.x; b_slot = RL.y; b_slot_in = b_slot;
+                    b_index = RL.x;
+#if CRT_WF_T2_LATE_SLOT
+                    b_in = b_index;
+                    cell[lane] = hit_key(t_max, b_index);
+#else
+                    b_slot = RL.y; b_in = b_slot;
                     cell[lane] = hit_key(t_max, b_index); cslot[lane] = b_slot;
+#endif
                     node = root; sp = 0; pend = 0;
                     active = true;
                 }
@@ -1853,12 +1902,30 @@ __global__ __launch_bounds__(64, CRT_WF_T2_WAVES) void k_wf_trace2(const WfParam
                     uint32_t bs = bs0;
                     // (D, the patch record's fourth part, was fetched with the other three: 94 % of the rounds on S2 hold a wall patch
                     // among their tasks, and fetched behind the category test it was a dependent round trip in every one of them)
+#if CRT_WF_T2_FLAT
+                    // one level of branches (the primitive's kind), straight-line code inside each, one select at the end
+                    const uint32_t cat = f_bits(A.w) & 3u;
+                    bool ok;
+                    float t = tm;
+                    // (unit normal and e1.e1 with the operations of the upload, crt_api.cpp: the same bits as the stored part)
+                    if (!fetchD && cat == 0u) { const f3 nn = normalize(cross(xyz(B), xyz(C))); D = float4{nn.x, nn.y, nn.z, dot(xyz(B), xyz(B))}; }
+                    if (cat == 2u) {
+                        ok = tri_accepts_flat(A, B, C, hit_pad, to, td, t_excl, t_min, tm, bi, bs, t);
+                    } else if (cat == 0u && CRT_WF_T2_FLAT != 2) {
+                        ok = patch_accepts_flat(A, B, C, D, to, td, t_excl, t_min, tm, bi, bs, t);
+                    } else {
+                        uint32_t si = bi, ss = bs;
+                        ok = hit_test_rec<false>(A, B, C, D, hit_pad, ps, to, td, t_excl, t_min, t, si, ss);
+                    }
+                    tm = ok ? t : tm; bi = ok ? f_bits(B.w) : bi; bs = ok ? ps : bs;
+#else
                     if ((f_bits(A.w) & 3u) == 2u) tri_test(A, B, C, ps, to, td, t_excl, t_min, hit_pad, tm, bi, bs);
                     else {
                         // (unit normal and e1.e1 with the operations of the upload, crt_api.cpp: the same bits as the stored part)
                         if (!fetchD && (f_bits(A.w) & 3u) == 0u) { const f3 nn = normalize(cross(xyz(B), xyz(C))); D = float4{nn.x, nn.y, nn.z, dot(xyz(B), xyz(B))}; }
                         hit_test_rec<false>(A, B, C, D, hit_pad, ps, to, td, t_excl, t_min, tm, bi, bs);
                     }
+#endif
                     if (COUNT && __ballot((f_bits(A.w) & 3u) != 2u) != 0ull) d_scans += 64u;   // (probe: rounds that also run the patch / sphere test; read back / 64)
                     acc = bs != bs0;
                     if (acc) {
@@ -1869,91 +1936,109 @@ __global__ __launch_bounds__(64, CRT_WF_T2_WAVES) void k_wf_trace2(const WfParam
                 }
                 __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
                 __builtin_amdgcn_wave_barrier();
+#if !CRT_WF_T2_LATE_SLOT
                 if (acc && cell[owner] == key) cslot[owner] = ps;        // the round's winner for that ray names its slot
                 __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
                 __builtin_amdgcn_wave_barrier();
+#endif
                 if (incl) {
                     const unsigned long long v = cell[lane];
                     const uint32_t low = (uint32_t)v;
                     t_max = bits_f((uint32_t)(v >> 32));
                     b_index = low == 0xFFFFFFFFu ? kNoHit : 0xFFFFFFFEu - low;
+#if CRT_WF_T2_LATE_SLOT
+                    const bool beaten = b_index != b_in;                 // (index and slot name the same primitive)
+#else
                     b_slot = cslot[lane];
+                    const bool beaten = b_slot != b_in;
+#endif
                     bool done = false;
-                    if (shadow && b_slot != b_slot_in) done = true;      // any-hit: something beats the light
+                    if (shadow && beaten) done = true;                   // any-hit: something beats the light
                     else if (node == kNoNode && pend == 0) done = true;
-                    if (done) {
-                        if (shadow) stnt(&g_vis[slot], (b_slot == b_slot_in) ? 1u : 0u);
-                        else stnt(&g_hit[slot], float2{t_max, bits_f(b_slot)});
-                        active = false;
-                    }
+                    if (done) { ray_out(); active = false; }
                 }
             } else {
-                if (COUNT) { d_inner_it++; d_inner_act += (uint32_t)ni; }
-                if (inner) {
-                    float k0, k1, k2, k3;
-                    int r0, r1, r2, r3;
-                    // one 64-byte node: 16-bit plane coordinates, near / far plane picked by the ray's signs
-                    const uint4 *nq = (const uint4 *)((const char *)nodesq + ((uint32_t)node << 6));   // (32-bit offset: the tree is below 4 GB)
-                    const uint4 Q0 = nq[0], Q1 = nq[1], Q2 = nq[2], Q3 = nq[3];
-                    const uint32_t nxa = gx ? Q1.z : Q0.x, nxb = gx ? Q1.w : Q0.y, fxa = gx ? Q0.x : Q1.z, fxb = gx ? Q0.y : Q1.w;
-                    const uint32_t nya = gy ? Q2.x : Q0.z, nyb = gy ? Q2.y : Q0.w, fya = gy ? Q0.z : Q2.x, fyb = gy ? Q0.w : Q2.y;
-                    const uint32_t nza = gz ? Q2.z : Q1.x, nzb = gz ? Q2.w : Q1.y, fza = gz ? Q1.x : Q2.z, fzb = gz ? Q1.y : Q2.w;
+                // ---- inner pass: one node step, or two behind this one set of ballots and tests where most of the wave is on an inner
+                // node (a lane that reaches a leaf in the first step hands it to `pend` if it can and idles otherwise; the breaks, the
+                // leaf-round trigger and the pick-up wait for the pair).  The answers do not depend on the order: 5.12.
+#if CRT_WF_T2_DOUBLE
+                const int steps = ni >= CRT_WF_T2_DOUBLE_AT ? 2 : 1;
+#else
+                const int steps = 1;
+#endif
+                bool on = inner;
+#pragma unroll 1
+                for (int st = 0; st < steps; st++) {
+                    if (st > 0) {
+                        if (active && node < 0 && pend == 0 && sp > 0) {
+                            pend = node;
+                            sp--; node = stack_pop2(stk, ovf, ovl, sp);
+                        }
+                        on = active && node >= 0 && node != kNoNode;
+                    }
+                    if (COUNT) { d_inner_it++; d_inner_act += st > 0 ? (uint32_t)__popcll(__ballot(on)) : (uint32_t)ni; }
+                    if (on) {
+                        float k0, k1, k2, k3;
+                        int r0, r1, r2, r3;
+                        // one 64-byte node: 16-bit plane coordinates, near / far plane picked by the ray's signs
+                        const uint4 *nq = (const uint4 *)((const char *)nodesq + ((uint32_t)node << 6));   // (32-bit offset: the tree is below 4 GB)
+                        const uint4 Q0 = nq[0], Q1 = nq[1], Q2 = nq[2], Q3 = nq[3];
+                        const uint32_t nxa = gx ? Q1.z : Q0.x, nxb = gx ? Q1.w : Q0.y, fxa = gx ? Q0.x : Q1.z, fxb = gx ? Q0.y : Q1.w;
+                        const uint32_t nya = gy ? Q2.x : Q0.z, nyb = gy ? Q2.y : Q0.w, fya = gy ? Q0.z : Q2.x, fyb = gy ? Q0.w : Q2.y;
+                        const uint32_t nza = gz ? Q2.z : Q1.x, nzb = gz ? Q2.w : Q1.y, fza = gz ? Q1.x : Q2.z, fzb = gz ? Q1.y : Q2.w;
 #if CRT_WF_PKFMA
-                    // the 24 plane distances as 12 packed fmas (v_pk_fma_f32: children 0/1 and 2/3 of a plane share a dword).  Measured 4 %
-                    // SLOWER on the step (profiles/r03_ab_pkfma.txt: the packed form pairs registers and spills in the set-up): off.
-                    {
-                        const v2f ix = v2f{id.x, id.x}, iy = v2f{id.y, id.y}, iz = v2f{id.z, id.z};
-                        const v2f ox = v2f{oid.x, oid.x}, oy = v2f{oid.y, oid.y}, oz = v2f{oid.z, oid.z};
+                        // the 24 plane distances as 12 packed fmas (v_pk_fma_f32: children 0/1 and 2/3 of a plane share a dword).  Measured 4 %
+                        // SLOWER on the step (profiles/r03_ab_pkfma.txt: the packed form pairs registers and spills in the set-up): off.
+                        {
+                            const v2f ix = v2f{id.x, id.x}, iy = v2f{id.y, id.y}, iz = v2f{id.z, id.z};
+                            const v2f ox = v2f{oid.x, oid.x}, oy = v2f{oid.y, oid.y}, oz = v2f{oid.z, oid.z};
 #define CRT_PK(Q, I, O) __builtin_elementwise_fma(v2f{(float)((Q) & 0xFFFFu), (float)((Q) >> 16)}, I, O)
-                        const v2f tnx_a = CRT_PK(nxa, ix, ox), tnx_b = CRT_PK(nxb, ix, ox), tfx_a = CRT_PK(fxa, ix, ox), tfx_b = CRT_PK(fxb, ix, ox);
-                        const v2f tny_a = CRT_PK(nya, iy, oy), tny_b = CRT_PK(nyb, iy, oy), tfy_a = CRT_PK(fya, iy, oy), tfy_b = CRT_PK(fyb, iy, oy);
-                        const v2f tnz_a = CRT_PK(nza, iz, oz), tnz_b = CRT_PK(nzb, iz, oz), tfz_a = CRT_PK(fza, iz, oz), tfz_b = CRT_PK(fzb, iz, oz);
+                            const v2f tnx_a = CRT_PK(nxa, ix, ox), tnx_b = CRT_PK(nxb, ix, ox), tfx_a = CRT_PK(fxa, ix, ox), tfx_b = CRT_PK(fxb, ix, ox);
+                            const v2f tny_a = CRT_PK(nya, iy, oy), tny_b = CRT_PK(nyb, iy, oy), tfy_a = CRT_PK(fya, iy, oy), tfy_b = CRT_PK(fyb, iy, oy);
+                            const v2f tnz_a = CRT_PK(nza, iz, oz), tnz_b = CRT_PK(nzb, iz, oz), tfz_a = CRT_PK(fza, iz, oz), tfz_b = CRT_PK(fzb, iz, oz);
 #undef CRT_PK
 #define CRT_QK(K, NX, NY, NZ, FX, FY, FZ) { \
-                            const float tn_ = __builtin_fmaxf(__builtin_fmaxf(NX, NY), __builtin_fmaxf(NZ, t_min)); \
-                            const float tf_ = __builtin_fminf(__builtin_fminf(FX, FY), __builtin_fminf(FZ, t_max)); \
-                            K = (tn_ <= tf_ * 1.0000005f) ? tn_ : 3.0e38f; }
-                        CRT_QK(k0, tnx_a.x, tny_a.x, tnz_a.x, tfx_a.x, tfy_a.x, tfz_a.x)
-                        CRT_QK(k1, tnx_a.y, tny_a.y, tnz_a.y, tfx_a.y, tfy_a.y, tfz_a.y)
-                        CRT_QK(k2, tnx_b.x, tny_b.x, tnz_b.x, tfx_b.x, tfy_b.x, tfz_b.x)
-                        CRT_QK(k3, tnx_b.y, tny_b.y, tnz_b.y, tfx_b.y, tfy_b.y, tfz_b.y)
+                                const float tn_ = __builtin_fmaxf(__builtin_fmaxf(NX, NY), __builtin_fmaxf(NZ, t_min)); \
+                                const float tf_ = __builtin_fminf(__builtin_fminf(FX, FY), __builtin_fminf(FZ, t_max)); \
+                                K = (tn_ <= tf_ * 1.0000005f) ? tn_ : 3.0e38f; }
+                            CRT_QK(k0, tnx_a.x, tny_a.x, tnz_a.x, tfx_a.x, tfy_a.x, tfz_a.x)
+                            CRT_QK(k1, tnx_a.y, tny_a.y, tnz_a.y, tfx_a.y, tfy_a.y, tfz_a.y)
+                            CRT_QK(k2, tnx_b.x, tny_b.x, tnz_b.x, tfx_b.x, tfy_b.x, tfz_b.x)
+                            CRT_QK(k3, tnx_b.y, tny_b.y, tnz_b.y, tfx_b.y, tfy_b.y, tfz_b.y)
 #undef CRT_QK
-                    }
+                        }
 #else
 #define CRT_QBOX(K, NXQ, NYQ, NZQ, FXQ, FYQ, FZQ) { \
-                        const float tn_ = __builtin_fmaxf(__builtin_fmaxf(fma_((float)(NXQ), id.x, oid.x), fma_((float)(NYQ), id.y, oid.y)), \
-                                                          __builtin_fmaxf(fma_((float)(NZQ), id.z, oid.z), t_min)); \
-                        const float tf_ = __builtin_fminf(__builtin_fminf(fma_((float)(FXQ), id.x, oid.x), fma_((float)(FYQ), id.y, oid.y)), \
-                                                          __builtin_fminf(fma_((float)(FZQ), id.z, oid.z), t_max)); \
-                        K = (tn_ <= tf_ * 1.0000005f) ? tn_ : 3.0e38f; }
-                    CRT_QBOX(k0, nxa & 0xFFFFu, nya & 0xFFFFu, nza & 0xFFFFu, fxa & 0xFFFFu, fya & 0xFFFFu, fza & 0xFFFFu)
-                    CRT_QBOX(k1, nxa >> 16, nya >> 16, nza >> 16, fxa >> 16, fya >> 16, fza >> 16)
-                    CRT_QBOX(k2, nxb & 0xFFFFu, nyb & 0xFFFFu, nzb & 0xFFFFu, fxb & 0xFFFFu, fyb & 0xFFFFu, fzb & 0xFFFFu)
-                    CRT_QBOX(k3, nxb >> 16, nyb >> 16, nzb >> 16, fxb >> 16, fyb >> 16, fzb >> 16)
+                            const float tn_ = __builtin_fmaxf(__builtin_fmaxf(fma_((float)(NXQ), id.x, oid.x), fma_((float)(NYQ), id.y, oid.y)), \
+                                                              __builtin_fmaxf(fma_((float)(NZQ), id.z, oid.z), t_min)); \
+                            const float tf_ = __builtin_fminf(__builtin_fminf(fma_((float)(FXQ), id.x, oid.x), fma_((float)(FYQ), id.y, oid.y)), \
+                                                              __builtin_fminf(fma_((float)(FZQ), id.z, oid.z), t_max)); \
+                            K = (tn_ <= tf_ * 1.0000005f) ? tn_ : 3.0e38f; }
+                        CRT_QBOX(k0, nxa & 0xFFFFu, nya & 0xFFFFu, nza & 0xFFFFu, fxa & 0xFFFFu, fya & 0xFFFFu, fza & 0xFFFFu)
+                        CRT_QBOX(k1, nxa >> 16, nya >> 16, nza >> 16, fxa >> 16, fya >> 16, fza >> 16)
+                        CRT_QBOX(k2, nxb & 0xFFFFu, nyb & 0xFFFFu, nzb & 0xFFFFu, fxb & 0xFFFFu, fyb & 0xFFFFu, fzb & 0xFFFFu)
+                        CRT_QBOX(k3, nxb >> 16, nyb >> 16, nzb >> 16, fxb >> 16, fyb >> 16, fzb >> 16)
 #undef CRT_QBOX
 #endif
-                    r0 = (int)Q3.x; r1 = (int)Q3.y; r2 = (int)Q3.z; r3 = (int)Q3.w;
-                    if (COUNT) c_nodes += 4;
-                    // sort the four (key, ref) pairs by entry distance: 5 compare-exchanges
+                        r0 = (int)Q3.x; r1 = (int)Q3.y; r2 = (int)Q3.z; r3 = (int)Q3.w;
+                        if (COUNT) c_nodes += 4;
+                        // sort the four (key, ref) pairs by entry distance: 5 compare-exchanges
 #define CRT_CAS(ka, ra, kb, rb) { const bool sw_ = kb < ka; const float tk_ = sw_ ? kb : ka; kb = sw_ ? ka : kb; ka = tk_; \
-                                  const int tr_ = sw_ ? rb : ra; rb = sw_ ? ra : rb; ra = tr_; }
-                    CRT_CAS(k0, r0, k1, r1) CRT_CAS(k2, r2, k3, r3) CRT_CAS(k0, r0, k2, r2) CRT_CAS(k1, r1, k3, r3) CRT_CAS(k1, r1, k2, r2)
+                                      const int tr_ = sw_ ? rb : ra; rb = sw_ ? ra : rb; ra = tr_; }
+                        CRT_CAS(k0, r0, k1, r1) CRT_CAS(k2, r2, k3, r3) CRT_CAS(k0, r0, k2, r2) CRT_CAS(k1, r1, k3, r3) CRT_CAS(k1, r1, k2, r2)
 #undef CRT_CAS
-                    if (k0 < 3.0e38f) {
-                        // descend into the nearest; the others wait on the stack, farthest pushed first
-                        if (k3 < 3.0e38f) { if (sp < kStk2) stk[sp * 64] = r3; else ovf[(size_t)(sp - kStk2) * ovl] = r3; sp++; }
-                        if (k2 < 3.0e38f) { if (sp < kStk2) stk[sp * 64] = r2; else ovf[(size_t)(sp - kStk2) * ovl] = r2; sp++; }
-                        if (k1 < 3.0e38f) { if (sp < kStk2) stk[sp * 64] = r1; else ovf[(size_t)(sp - kStk2) * ovl] = r1; sp++; }
-                        if (COUNT) d_max_sp = max(d_max_sp, (uint32_t)sp);
-                        node = r0;
-                    } else if (sp > 0) {
-                        sp--; node = stack_pop2(stk, ovf, ovl, sp);
-                    } else {
-                        node = kNoNode;                                  // nothing left to walk ...
-                        if (pend == 0) {                                 // ... and no postponed leaf either: the ray is through
-                            if (shadow) stnt(&g_vis[slot], (b_slot == b_slot_in) ? 1u : 0u);
-                            else stnt(&g_hit[slot], float2{t_max, bits_f(b_slot)});
-                            active = false;
+                        if (k0 < 3.0e38f) {
+                            // descend into the nearest; the others wait on the stack, farthest pushed first
+                            if (k3 < 3.0e38f) { if (sp < kStk2) stk[sp * 64] = r3; else ovf[(size_t)(sp - kStk2) * ovl] = r3; sp++; }
+                            if (k2 < 3.0e38f) { if (sp < kStk2) stk[sp * 64] = r2; else ovf[(size_t)(sp - kStk2) * ovl] = r2; sp++; }
+                            if (k1 < 3.0e38f) { if (sp < kStk2) stk[sp * 64] = r1; else ovf[(size_t)(sp - kStk2) * ovl] = r1; sp++; }
+                            if (COUNT) d_max_sp = max(d_max_sp, (uint32_t)sp);
+                            node = r0;
+                        } else if (sp > 0) {
+                            sp--; node = stack_pop2(stk, ovf, ovl, sp);
+                        } else {
+                            node = kNoNode;                                  // nothing left to walk ...
+                            if (pend == 0) { ray_out(); active = false; }    // ... and no postponed leaf either: the ray is through
                         }
                     }
                 }
