@@ -988,6 +988,83 @@ static napi_value js_set_primitive_ids(napi_env env, napi_callback_info info)
     return undefined(env);
 }
 
+/* queryRays(h, Float32Array(n*8), mode, {hit: Uint32Array(n), prim: Uint32Array(n), id: Uint32Array(n), t: Float32Array(n),
+ * position: Float32Array(n*4), normal: Float32Array(n*4), uv: Float32Array(n*2)}): what n caller rays hit -- each ray 8
+ * floats (o, t_max, d, exclude bits), mode 0 = the closest hit, 1 = any hit (the `hit` plane alone) -- into the caller's
+ * typed arrays; a plane left out is not computed (include/crt.h "Ray queries").  Blocking for the query alone: work in
+ * flight is neither finished nor disturbed. */
+static const char *const query_names[7] = {"hit", "prim", "id", "t", "position", "normal", "uv"};
+static const size_t query_bytes[7] = {4, 4, 4, 4, 16, 16, 8};
+
+static int query_planes(napi_env env, napi_value obj, size_t n, const char *who, crt_query_planes *out)
+{
+    void *p[7] = {NULL, NULL, NULL, NULL, NULL, NULL, NULL};
+    for (int i = 0; i < 7; i++) {
+        bool has = false;
+        napi_value v;
+        if (napi_has_named_property(env, obj, query_names[i], &has) != napi_ok) has = false;
+        if (!has) continue;
+        size_t len = 0;
+        if (napi_get_named_property(env, obj, query_names[i], &v) != napi_ok || !get_bytes(env, v, &p[i], &len) || len != n * query_bytes[i]) {
+            char m[128];
+            snprintf(m, sizeof m, "%s: %s must be a typed array of %zu bytes", who, query_names[i], n * query_bytes[i]);
+            napi_throw_type_error(env, NULL, m);
+            return 0;
+        }
+    }
+    const crt_query_planes q = {(uint32_t *)p[0], (uint32_t *)p[1], (uint32_t *)p[2], (float *)p[3], (float *)p[4], (float *)p[5], (float *)p[6]};
+    *out = q;
+    return 1;
+}
+
+static napi_value js_query_rays(napi_env env, napi_callback_info info)
+{
+    ARGS(4)
+    crt_ctx *ctx = get_ctx(env, argv[0]);
+    if (!ctx) return NULL;
+    void *rays = NULL; size_t bytes = 0;
+    if (!get_bytes(env, argv[1], &rays, &bytes) || bytes % sizeof(crt_ray)) {
+        napi_throw_type_error(env, NULL, "queryRays: rays must be a Float32Array of 8 floats per ray");
+        return NULL;
+    }
+    int32_t mode = 0;
+    NAPI_OK(env, napi_get_value_int32(env, argv[2], &mode));
+    const size_t n = bytes / sizeof(crt_ray);
+    crt_query_planes out;
+    if (!query_planes(env, argv[3], n, "queryRays", &out)) return NULL;
+    CRT_CHECK(env, ctx, "crt_query_rays", crt_query_rays(ctx, n ? (const crt_ray *)rays : NULL, n, mode, &out));
+    return undefined(env);
+}
+
+/* pick(h, x, y) -> {hit, prim, id, t, position: Float32Array(4), normal: Float32Array(4), uv: Float32Array(2)}: what the
+ * camera ray of pixel (x, y) of the full image hits (crt_pick; global coordinates), hit = 0 with prim = id = 0xFFFFFFFF
+ * where it hits nothing.  Blocking for the query alone. */
+static napi_value js_pick(napi_env env, napi_callback_info info)
+{
+    ARGS(3)
+    crt_ctx *ctx = get_ctx(env, argv[0]);
+    if (!ctx) return NULL;
+    uint32_t xy[2] = {0, 0};
+    NAPI_OK(env, napi_get_value_uint32(env, argv[1], &xy[0]));
+    NAPI_OK(env, napi_get_value_uint32(env, argv[2], &xy[1]));
+    napi_value ab, res, v;
+    void *data = NULL;
+    NAPI_OK(env, napi_create_arraybuffer(env, 64, &data, &ab));      /* position, normal, uv, then hit, prim, id, t */
+    float *f = (float *)data;
+    uint32_t *u = (uint32_t *)data + 10;
+    const crt_query_planes out = {u, u + 1, u + 2, f + 13, f, f + 4, f + 8};
+    CRT_CHECK(env, ctx, "crt_pick", crt_pick(ctx, xy, 1, &out));
+    NAPI_OK(env, napi_create_object(env, &res));
+    NAPI_OK(env, napi_create_uint32(env, u[0], &v)); NAPI_OK(env, napi_set_named_property(env, res, "hit", v));
+    NAPI_OK(env, napi_create_uint32(env, u[1], &v)); NAPI_OK(env, napi_set_named_property(env, res, "prim", v));
+    NAPI_OK(env, napi_create_uint32(env, u[2], &v)); NAPI_OK(env, napi_set_named_property(env, res, "id", v));
+    NAPI_OK(env, napi_create_double(env, (double)f[13], &v)); NAPI_OK(env, napi_set_named_property(env, res, "t", v));
+    NAPI_OK(env, napi_create_typedarray(env, napi_float32_array, 4, ab, 0, &v)); NAPI_OK(env, napi_set_named_property(env, res, "position", v));
+    NAPI_OK(env, napi_create_typedarray(env, napi_float32_array, 4, ab, 16, &v)); NAPI_OK(env, napi_set_named_property(env, res, "normal", v));
+    NAPI_OK(env, napi_create_typedarray(env, napi_float32_array, 2, ab, 32, &v)); NAPI_OK(env, napi_set_named_property(env, res, "uv", v));
+    return res;
+}
+
 /* readMotion(h) -> Float32Array (tw*th*2): per pixel the film position (u, v) where the last denoiseTemporal looked for
  * it in the previous frame, NaN where there is none (include/crt.h crt_read_motion). */
 static napi_value js_read_motion(napi_env env, napi_callback_info info)
@@ -1663,6 +1740,7 @@ static napi_value init(napi_env env, napi_value exports)
         {"denoiseLatestAsync", js_denoise_latest_async},
         {"readGbuffer", js_read_gbuffer}, {"readMotion", js_read_motion}, {"renderAovs", js_render_aovs},
         {"renderMattes", js_render_mattes}, {"setPrimitiveIds", js_set_primitive_ids},
+        {"queryRays", js_query_rays}, {"pick", js_pick},
         {"setCamera", js_set_camera}, {"updatePrimitives", js_update_primitives}, {"updateLights", js_update_lights},
         {"refitAccel", js_refit_accel},
         {"transformPrimitives", js_transform_primitives}, {"transformPrimitivesAsync", js_transform_primitives_async},

@@ -1,6 +1,7 @@
 """python -m computeraytracer_amd [--scene file.json] [--width W --height H] [--spp N] [--out image.png] [--denoise K] [--orbit N [--temporal [--variance] [--animate | --animate-device [--rebuild-pct P] | --blink P]]]
                                 [--adaptive THRESHOLD [--adaptive-filtered] [--adaptive-step N] [--counts-out counts.png]]
                                 [--alpha] [--aov-out PREFIX] [--matte-out PREFIX [--matte-source primitive|object|material] [--matte-slots K]]
+                                [--pick X,Y]
 --adaptive goes with --orbit: every frame is sampled adaptively up to --spp, and with --denoise K --temporal [--variance] the
 temporal filters blend it with each pixel's own tile count (option "adaptive_temporal")."""
 import argparse
@@ -89,7 +90,21 @@ def parse_args(argv=None):
                     help="with --matte-out: what an id is (default object: one per patch, sphere and mesh)")
     ap.add_argument("--matte-slots", type=int, default=8, metavar="K",
                     help="with --matte-out: ids kept per pixel, 1..16 (default 8); PREFIX_overflow.npy counts the hits left out")
+    ap.add_argument("--pick", default=None, metavar="X,Y",
+                    help="after the render, what lies under pixel (X, Y) of the image (crt_pick): its primitive, object id, t, "
+                         "position and normal go into the JSON line as \"pick\" (null where the pixel's ray hits nothing; not "
+                         "with --orbit)")
     args = ap.parse_args(argv)
+    if args.pick is not None:
+        try:
+            x, y = (int(v) for v in args.pick.split(","))
+            if x < 0 or y < 0:
+                raise ValueError
+        except ValueError:
+            ap.error("--pick takes X,Y: two non-negative integers")
+        args.pick = (x, y)
+        if args.orbit is not None:
+            ap.error("--pick does not go with --orbit")
     if args.matte_out and args.orbit is not None:
         ap.error("--matte-out does not go with --orbit")
     if not 1 <= args.matte_slots <= 16:
@@ -234,6 +249,7 @@ def main(argv=None):
         rgba = r.read_rgba8() if args.denoise is None else r.denoise(args.denoise)
         info = {"width": ps.width, "height": ps.height, "sample": r.sample, "seconds": round(dt, 4), "out": args.out}
         rgba = _aovs(r, args, rgba, info)
+        _pick(r, args, info)
         (image.write_ppm if args.out.endswith(".ppm") else image.write_png)(args.out, rgba)
         if args.checkpoint:
             image.save_checkpoint(args.checkpoint, r)
@@ -263,6 +279,20 @@ def _aovs(r, args, rgba, info):
         info["alpha"] = True
         rgba = image.with_alpha(rgba, planes["alpha"])
     return rgba
+
+
+def _pick(r, args, info):
+    """--pick X,Y: what the pixel's camera ray hits, into the JSON line."""
+    if args.pick is None:
+        return
+    x, y = args.pick
+    w, h = r.image_size
+    if x >= w or y >= h:
+        raise SystemExit(f"--pick {x},{y}: outside the {w} x {h} image")
+    hit = r.pick(x, y)
+    info["pick"] = None if hit is None else {"x": x, "y": y, "primitive": hit["prim"], "id": hit["id"], "t": hit["t"],
+                                             "position": [float(v) for v in hit["position"]],
+                                             "normal": [float(v) for v in hit["normal"]]}
 
 
 def _closing_spheres(ps) -> int:
@@ -312,6 +342,7 @@ def _adaptive(r, ps, args):
             "tile_samples": {"min": int(counts.min()), "median": float(np.median(counts)), "max": int(counts.max())},
             "out": args.out}
     rgba = _aovs(r, args, rgba, info)
+    _pick(r, args, info)
     (image.write_ppm if args.out.endswith(".ppm") else image.write_png)(args.out, rgba)
     if args.denoise is not None:
         info["denoise"] = args.denoise

@@ -13,6 +13,7 @@ LIB_PATH = os.environ.get("CRT_LIB") or os.path.join(_HERE, "libcrt.so")   # CRT
 
 NCOUNTERS = 8
 ACCEL_NONE, ACCEL_BVH2, ACCEL_LBVH, ACCEL_PLOC = 0, 1, 2, 3
+QUERY_CLOSEST, QUERY_ANY = 0, 1
 CNT = dict(rays=0, nodes=1, prims=2, paths=3, bounces=4, shadow=5, hits=6, walked=7)
 
 # name -> (restype, argtypes); kept in one place so tests can check that every
@@ -73,6 +74,9 @@ SIGNATURES = {
     "crt_render_mattes": (C.c_int, [_P, C.c_uint32, C.c_int, C.c_uint32, _P]),
     "crt_set_primitive_ids": (C.c_int, [_P, C.c_uint32, C.c_uint32, _P]),
     "crt_read_primitive_ids": (C.c_int, [_P, C.c_uint32, C.c_uint32, _P]),
+    "crt_query_rays": (C.c_int, [_P, _P, C.c_size_t, C.c_int, _P]),
+    "crt_query_rays_device": (C.c_int, [_P, _P, C.c_size_t, C.c_int, _P, _P]),
+    "crt_pick": (C.c_int, [_P, _P, C.c_size_t, _P]),
     "crt_debug_intersect": (C.c_int, [_P, _P, C.c_size_t, _P]),
     "crt_debug_trace_rays": (C.c_int, [_P, _P, C.c_size_t, _P, _P]),
     "crt_debug_walk_rays": (C.c_int, [_P, C.c_int, _P, C.c_size_t, _P, _P]),
@@ -148,6 +152,17 @@ class AovPlanes(C.Structure):
 class MattePlanes(C.Structure):
     """crt_matte_planes of include/crt.h."""
     _fields_ = [("ids", C.c_void_p), ("counts", C.c_void_p), ("hits", C.c_void_p), ("overflow", C.c_void_p)]
+
+
+class Ray(C.Structure):
+    """crt_ray of include/crt.h (32 bytes; renderer.RAY_DTYPE is the numpy form)."""
+    _fields_ = [("o", C.c_float * 3), ("t_max", C.c_float), ("d", C.c_float * 3), ("exclude", C.c_uint32)]
+
+
+class QueryPlanes(C.Structure):
+    """crt_query_planes of include/crt.h."""
+    _fields_ = [("hit", C.c_void_p), ("prim", C.c_void_p), ("id", C.c_void_p), ("t", C.c_void_p), ("position", C.c_void_p),
+                ("normal", C.c_void_p), ("uv", C.c_void_p)]
 
 
 class DenoiseAdaptiveParams(C.Structure):

@@ -194,6 +194,7 @@ void crt_destroy(crt_ctx *c)
     c->pub_stream.sync();
     for (const Stream &s : c->fin_stream) s.sync();
     c->read_stream.sync();
+    c->query.stream.sync();
     delete c;
 }
 
@@ -235,6 +236,7 @@ int crt_upload_scene(crt_ctx *c, const void *primitives, size_t nprim, const voi
     c->prims.swap(prims);
     c->prims_moved = false;
     matte_ids_identity(c);                                       // (host only: DESIGN.md 6o)
+    c->query.release();                                          // (the ray queries' staging: DESIGN.md 6p)
     c->lights.swap(lts);
     std::memcpy(c->camera, camera, sizeof c->camera);
     c->W = (uint32_t)camera[11];                                 // ComputeShader.wgsl:85

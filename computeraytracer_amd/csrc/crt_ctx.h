@@ -8,6 +8,7 @@
 //   crt_denoise_api.cpp the preview filters' entry points
 //   crt_aov_api.cpp     the feature planes' entry points
 //   crt_matte_api.cpp   the id mattes' entry points and the id table
+//   crt_query_api.cpp   the ray queries' entry points
 //   crt_debug.cpp       the debug read-outs
 #pragma once
 #include <hip/hip_runtime.h>
@@ -324,6 +325,20 @@ struct crt_ctx {
         DevBuf<uint32_t> ids, counts, hits, overflow;
     } matte;
 
+    // Ray queries (crt_query.hip): the host forms' stream and staging, made by the first call that needs
+    // them; a buffer grows by at least half.  Released by crt_upload_scene; the device form uses none of this.
+    struct Query {
+        crt::Stream stream;         // non-blocking: a query waits for nothing the pipeline has enqueued
+        DevBuf<float4> rays;        // 2 per ray (crt_ray)
+        DevBuf<uint2> xy;           // crt_pick: the pixel coordinates
+        DevBuf<uint32_t> hit, prim, id;
+        DevBuf<float> t;
+        DevBuf<float4> position, normal;
+        DevBuf<float2> uv;
+        void release() { rays.release(); xy.release(); hit.release(); prim.release(); id.release(); t.release(); position.release();
+                         normal.release(); uv.release(); }
+    } query;
+
     // scene edits (crt_refit.hip)
     float s_prims = 0.0f;           // max |corner coordinate| of the primitives: hit_pad = max(s_prims, |eye|) * 2^-17
     float tree_pad = 0.0f;          // the hit_pad the tree's boxes were made with (a larger one needs a refit)
@@ -441,6 +456,7 @@ void matte_ids_identity(crt_ctx *c);
 void matte_ids_reserve(crt_ctx *c, size_t n_new);
 void matte_ids_remove(crt_ctx *c, const crt_prim_range *live, size_t m);      // ascending, disjoint, non-empty ranges
 void matte_ids_append(crt_ctx *c, uint32_t count);
+int matte_ids_device(crt_ctx *c);   // the device copy, made if it is missing (an allocation and a blocking copy; else nothing)
 
 // crt_wf_driver.cpp
 struct AsBatch {                    // one batch of a crt_trace_adaptive call: its samples off + 1 .. off + n of every active tile

@@ -28,10 +28,7 @@ struct DnParams {
     float inv_x;                // 1 / sigma_plane
 };
 
-// The primary ray of sample kDnSample of each pixel: its stratum (8 + r) / 16 lies within 1/16 pixel of the
-// pixel's centre on both axes, and it is a pure function of (x, y).
-constexpr uint32_t kDnSample = 8;
-
+// The primary ray of sample kDnSample (crt_device.h) of each pixel.
 // grid = tiles_x * tiles_y blocks of 64 threads, block -> 8x8 pixel tile (spatially coherent rays, like k_trace).
 __global__ __launch_bounds__(64) void k_dn_gbuffer(const DevScene S, uint32_t x0, uint32_t y0, uint32_t tw, uint32_t th,
                                                   uint32_t tiles_x, float4 *__restrict__ gbuf, uint32_t *__restrict__ key, int brute)

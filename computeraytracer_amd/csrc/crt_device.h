@@ -388,4 +388,24 @@ struct MatteParams {
     int brute;                      // CRT_ACCEL_NONE: the reference's loop over every primitive
 };
 
+// The G-buffer's ray of a pixel (k_dn_gbuffer) and crt_pick's: the primary ray of sample kDnSample.  Its stratum
+// (8 + r) / 16 lies within 1/16 pixel of the pixel's centre on both axes, and it is a pure function of (x, y).
+constexpr uint32_t kDnSample = 8;
+
+// k_query (crt_query.hip): the closest hit, or whether there is any, of n rays -- the caller's, or the
+// G-buffer's rays of n pixels.  A plane whose pointer is null is not stored.
+struct QueryParams {
+    const float4 *rays;             // caller rays: 2 per ray, (o.xyz, t_max) (d.xyz, exclude bits) = crt_ray; pick: unused
+    const uint2 *xy;                // pick: global pixel coordinates per ray; else unused
+    const uint32_t *table;          // the id table, one entry per primitive in array order; read only where `id` is stored
+    uint32_t *hit;                  // 1 = a primitive was hit
+    uint32_t *prim;                 // its array position (kNoHit at a miss)
+    uint32_t *id;                   // table[prim] (kNoHit at a miss)
+    float *t;                       // the hit's t (at a miss the ray's own t_max)
+    float4 *position, *normal;      // hit_attributes' (zeros at a miss), w = +0
+    float2 *uv;                     // hit_uv_rec's (zeros at a miss)
+    size_t n;
+    int wide_ok;                    // 0: the BVH2 even where there is a quantised 4-wide tree (option "pipeline" = 0)
+};
+
 }  // namespace crt

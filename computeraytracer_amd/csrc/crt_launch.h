@@ -1,4 +1,4 @@
-// crt_launch.h -- every host entry into the device code, declared once: the launchers of the ten .hip files, the GPU tree
+// crt_launch.h -- every host entry into the device code, declared once: the launchers of the eleven .hip files, the GPU tree
 // builders and the level lists of the refit.  The .hip file that defines one and every host unit that calls one include
 // this header.  (Parameter structs: crt_device.h.)
 #pragma once
@@ -105,5 +105,8 @@ hipError_t aov_launch(const DevScene &S, const AovParams &P, hipStream_t stream)
 
 // crt_matte.hip
 hipError_t matte_launch(const DevScene &S, const MatteParams &P, hipStream_t stream);
+
+// crt_query.hip (mode: CRT_QUERY_CLOSEST / CRT_QUERY_ANY; pick: P.xy in place of P.rays; brute: CRT_ACCEL_NONE)
+hipError_t query_launch(const DevScene &S, const QueryParams &P, int mode, bool pick, bool brute, hipStream_t stream);
 
 }  // namespace crt

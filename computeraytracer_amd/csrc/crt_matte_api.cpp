@@ -46,6 +46,18 @@ void matte_ids_append(crt_ctx *c, uint32_t count)
     c->d_prim_ids.release();
 }
 
+// The device copy of the table for a kernel that reads it (crt_render_mattes of source OBJECT, the `id` plane of the ray
+// queries): made if a change has dropped it.
+int matte_ids_device(crt_ctx *c)
+{
+    if (c->d_prim_ids.n >= c->prim_ids.size()) return CRT_OK;
+    HIPCHK(c, c->d_prim_ids.alloc(c->prim_ids.size()));
+    const hipError_t e = hipMemcpy(c->d_prim_ids.p, c->prim_ids.data(), c->prim_ids.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
+    if (e != hipSuccess) c->d_prim_ids.release();
+    HIPCHK(c, e);
+    return CRT_OK;
+}
+
 }  // namespace crt
 
 // the range checks the two table calls share
@@ -109,12 +121,7 @@ int crt_render_mattes(crt_ctx *c, uint32_t n_samples, int source, uint32_t slots
         if (out->counts) CRT_ENSURE(c, m.counts, n * slots);
         if (out->hits) CRT_ENSURE(c, m.hits, n);
         if (out->overflow) CRT_ENSURE(c, m.overflow, n);
-        if (source == CRT_MATTE_OBJECT && c->d_prim_ids.n < c->prim_ids.size()) {
-            HIPCHK(c, c->d_prim_ids.alloc(c->prim_ids.size()));
-            const hipError_t e = hipMemcpy(c->d_prim_ids.p, c->prim_ids.data(), c->prim_ids.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
-            if (e != hipSuccess) c->d_prim_ids.release();
-            HIPCHK(c, e);
-        }
+        if (source == CRT_MATTE_OBJECT) CRT_TRY(matte_ids_device(c));
         MatteParams P{};
         P.table = source == CRT_MATTE_OBJECT ? c->d_prim_ids.p : nullptr;
         P.counts = per_tile ? c->as_counts.p : nullptr;

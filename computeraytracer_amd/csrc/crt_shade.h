@@ -210,6 +210,28 @@ __device__ __forceinline__ void hit_attributes_rec(const float4 A, const float4 
     }
 }
 
+// Surface coordinates of the winning primitive (crt_query_rays): what hit_test_rec computed for it on
+// its way to accepting t, recomputed from the same record with its operations in its order -- a triangle's barycentric
+// (u, v) (the ray's t does not enter), a patch's (u, v) along its edges at ray_at(o, d, t).  A sphere has none: +0, +0.
+__device__ __forceinline__ void hit_uv_rec(const float4 A, const float4 B, const float4 C, const float4 D, f3 o, f3 d, float t,
+                                           float &u, float &v)
+{
+    const uint32_t cat = f_bits(A.w) & 3u;
+    u = 0.0f; v = 0.0f;
+    if (cat == 2u) {
+        const f3 v0 = xyz(A), e1 = xyz(B), e2 = xyz(C);
+        const f3 pvec = cross(d, e2);
+        const float inv = 1.0f / dot(e1, pvec);
+        const f3 tvec = o - v0;
+        u = dot(tvec, pvec) * inv;
+        v = dot(d, cross(tvec, e1)) * inv;
+    } else if (cat == 0u) {
+        const f3 m = ray_at(o, d, t) - xyz(A);
+        u = dot(m, xyz(B)) / D.w;                              // :563
+        v = dot(m, xyz(C)) / C.w;                              // :564
+    }
+}
+
 __device__ __forceinline__ void hit_attributes(const DevScene &S, uint32_t slot, f3 o, f3 d, float t,
                                                f3 &pos, f3 &nrm, uint32_t &meta)
 {

@@ -23,6 +23,27 @@ AOV_PLANES = ("hits", "alpha", "depth", "normal", "albedo")
 MATTE_PLANES = ("ids", "counts", "hits", "overflow")
 MATTE_SOURCES = {"primitive": 0, "object": 1, "material": 2}
 MATTE_NONE = 0xFFFFFFFF          # the id of a rank without an entry
+QUERY_PLANES = ("hit", "prim", "id", "t", "position", "normal", "uv")
+QUERY_MODES = {"closest": 0, "any": 1}
+QUERY_NONE = 0xFFFFFFFF          # prim and id at a miss; the exclude index that excludes nothing
+QUERY_NO_LIMIT = 2139095040.0    # t_max: the kernels' "infinity" (+inf means the same)
+RAY_DTYPE = np.dtype([("o", np.float32, 3), ("t_max", np.float32), ("d", np.float32, 3), ("exclude", np.uint32)])   # crt_ray
+_QUERY_SHAPE = {"hit": ((), np.uint32), "prim": ((), np.uint32), "id": ((), np.uint32), "t": ((), np.float32),
+                "position": ((4,), np.float32), "normal": ((4,), np.float32), "uv": ((2,), np.float32)}
+
+
+def pack_rays(origins, directions, t_max=None, exclude=None) -> np.ndarray:
+    """n crt_ray records (RAY_DTYPE) from (n, 3) origins and directions; t_max None = no limit, a scalar or (n,) float32;
+    exclude None = nothing, a scalar or (n,) uint32."""
+    o = np.asarray(origins, np.float32).reshape(-1, 3)
+    d = np.asarray(directions, np.float32).reshape(-1, 3)
+    if len(o) != len(d):
+        raise ValueError("origins and directions must have the same length")
+    rays = np.zeros(len(o), RAY_DTYPE)
+    rays["o"], rays["d"] = o, d
+    rays["t_max"] = np.float32(QUERY_NO_LIMIT) if t_max is None else np.asarray(t_max, np.float32)
+    rays["exclude"] = np.uint32(QUERY_NONE) if exclude is None else np.asarray(exclude, np.uint32)
+    return rays
 
 
 def spectrum_rgb(spectrum, cie) -> np.ndarray:
@@ -581,6 +602,82 @@ class Renderer:
             count = len(self.scene.primitives) - int(first)
         out = np.zeros(int(count), np.uint32)
         self._chk(self._lib.crt_read_primitive_ids(self._h, int(first), int(count), out.ctypes.data if count else None))
+        return out
+
+    # -- ray queries (include/crt.h, "Ray queries")
+    @staticmethod
+    def _query_planes(mode, planes):
+        if mode not in QUERY_MODES and mode not in QUERY_MODES.values():
+            raise ValueError(f"unknown mode {mode!r}: choose from {tuple(QUERY_MODES)}")
+        mode = int(QUERY_MODES.get(mode, mode))
+        if planes is None:
+            planes = ("hit",) if mode == 1 else QUERY_PLANES
+        unknown = [p for p in planes if p not in QUERY_PLANES]
+        if unknown:
+            raise ValueError(f"unknown planes {unknown}: choose from {QUERY_PLANES}")
+        return mode, [p for p in QUERY_PLANES if p in planes]
+
+    def query_rays(self, origins=None, directions=None, t_max=None, exclude=None, mode="closest", planes=None, rays=None) -> dict:
+        """What the rays hit (crt_query_rays): the closest hit of each ray, or with mode "any" only whether there is one.
+        Rays: (n, 3) origins and directions with optional t_max (None = no limit) and exclude (a primitive index, None =
+        nothing) -- or rays=: n packed records (RAY_DTYPE, see pack_rays), or a torch tensor (n, 8) float32, contiguous, on
+        this context's device, each row (o, t_max, d, exclude bits) (crt_query_rays_device on torch's current stream: nothing
+        is copied through the host and nothing waits).  A dict of the planes asked for (default: all; mode "any": hit
+        alone): hit, prim, id uint32 (n,), t float32 (n,), position and normal float32 (n, 4), uv float32 (n, 2) -- numpy
+        arrays, or torch tensors for a torch input.  Does not finish or disturb what is in flight; only reads."""
+        mode, names = self._query_planes(mode, planes)
+        if rays is not None and not isinstance(rays, np.ndarray) and type(rays).__module__.split(".")[0] == "torch":
+            return self._query_rays_torch(rays, mode, names)
+        if rays is None:
+            rays = pack_rays(origins, directions, t_max, exclude)
+        else:
+            rays = np.ascontiguousarray(rays)
+            if rays.dtype != RAY_DTYPE:
+                rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 8).view(RAY_DTYPE).reshape(-1)
+        n = len(rays)
+        out = {p: np.empty((n,) + _QUERY_SHAPE[p][0], _QUERY_SHAPE[p][1]) for p in names}
+        arg = _lib.QueryPlanes(**{p: a.ctypes.data for p, a in out.items()})
+        self._chk(self._lib.crt_query_rays(self._h, rays.ctypes.data if n else None, n, mode, C.byref(arg)))
+        return out
+
+    def _query_rays_torch(self, rays, mode, names) -> dict:
+        import torch
+        if rays.device.type != "cuda" or rays.device.index != self.device:
+            raise ValueError(f"rays are on {rays.device}, the context on cuda:{self.device}")
+        if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8 or not rays.is_contiguous():
+            raise ValueError("rays must be a contiguous (n, 8) float32 tensor: (o, t_max, d, exclude bits) per row")
+        n = rays.shape[0]
+        kinds = {np.uint32: torch.int32, np.float32: torch.float32}     # (uint32 planes as int32 storage: view them as needed)
+        with torch.cuda.device(self.device):
+            out = {p: torch.empty((n,) + _QUERY_SHAPE[p][0], dtype=kinds[_QUERY_SHAPE[p][1]], device=rays.device) for p in names}
+            if n == 0:                                          # (an empty tensor has no pointer to pass)
+                return out
+            arg = _lib.QueryPlanes(**{p: a.data_ptr() for p, a in out.items()})
+            stream = torch.cuda.current_stream(rays.device).cuda_stream
+            self._chk(self._lib.crt_query_rays_device(self._h, rays.data_ptr() if n else None, n, mode, C.byref(arg), stream))
+        return out
+
+    def pick(self, x: int, y: int):
+        """What is under pixel (x, y) of the full image (crt_pick; global coordinates, whatever the tile): a dict of
+        scalars -- prim, id, t, position (3,), normal (3,), uv (2,) -- of the G-buffer's ray of that pixel, or None where
+        it hits nothing.  Does not finish or disturb what is in flight."""
+        got = self.pick_pixels([(x, y)])
+        if not got["hit"][0]:
+            return None
+        return dict(prim=int(got["prim"][0]), id=int(got["id"][0]), t=float(got["t"][0]), position=got["position"][0, :3].copy(),
+                    normal=got["normal"][0, :3].copy(), uv=got["uv"][0].copy())
+
+    def pick_pixels(self, xy, planes=QUERY_PLANES) -> dict:
+        """crt_pick for n pixels at once: xy (n, 2) global (x, y); the planes as query_rays returns them."""
+        _, names = self._query_planes("closest", planes)
+        p = np.ascontiguousarray(np.asarray(xy, np.int64).reshape(-1, 2))
+        if ((p < 0) | (p > 0xFFFFFFFF)).any():
+            raise ValueError("pixel coordinates must be non-negative")
+        p = np.ascontiguousarray(p.astype(np.uint32))
+        n = len(p)
+        out = {k: np.empty((n,) + _QUERY_SHAPE[k][0], _QUERY_SHAPE[k][1]) for k in names}
+        arg = _lib.QueryPlanes(**{k: a.ctypes.data for k, a in out.items()})
+        self._chk(self._lib.crt_pick(self._h, p.ctypes.data if n else None, n, C.byref(arg)))
         return out
 
     # -- multi-GPU: the frame across the ranks of a communicator (include/crt.h, "Multi-GPU")

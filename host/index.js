@@ -28,6 +28,8 @@
 // --matte-out PREFIX [--matte-source primitive|object|material] [--matte-slots K]: the id mattes of the samples the image
 //            holds (renderMattes(0); also with --adaptive, not with --orbit), each as the raw bytes of its Uint32Array:
 //            PREFIX_ids.bin, PREFIX_counts.bin (K planes, rank 0 first), PREFIX_hits.bin, PREFIX_overflow.bin
+// --pick X,Y: after the render, what lies under pixel (X, Y) of the image (pick): primitive, object id, t, position and
+//            normal go into the JSON line as "pick" (null where the pixel's ray hits nothing; not with --orbit)
 const fs = require('fs');
 const { Main, writePPM, orbitCameras } = require('./main');
 const sceneLoader = require('./sceneLoader');
@@ -67,6 +69,12 @@ if (clip !== null && !(args.temporal && Number.isInteger(clip) && clip >= 25 && 
 }
 if ('aov-out' in args && (args.orbit || args['aov-out'] === true)) { console.error('--aov-out PREFIX writes the planes of one frame: give it a prefix, and no --orbit'); process.exit(2); }
 if ('matte-out' in args && (args.orbit || args['matte-out'] === true)) { console.error('--matte-out PREFIX writes the mattes of one frame: give it a prefix, and no --orbit'); process.exit(2); }
+let pickXY = null;
+if ('pick' in args) {
+  const m = /^(\d+),(\d+)$/.exec(String(args.pick));
+  if (!m || args.orbit) { console.error('--pick takes X,Y, two non-negative integers, and no --orbit'); process.exit(2); }
+  pickXY = [Number(m[1]), Number(m[2])];
+}
 const r = Main({ sceneFile: args.scene, width: args.width ? num('width') : undefined, height: args.height ? num('height') : undefined,
   accel: args.accel || 'bvh2', device: num('device', 0) });
 function writeAovs() {
@@ -78,6 +86,12 @@ function writeMattes() {
   if (!('matte-out' in args)) return;
   for (const [name, plane] of Object.entries(r.renderMattes(0, args['matte-source'] || 'object', num('matte-slots', 8))))
     fs.writeFileSync(`${args['matte-out']}_${name}.bin`, Buffer.from(plane.buffer, plane.byteOffset, plane.byteLength));
+}
+function pickInfo() {
+  if (!pickXY) return {};
+  if (pickXY[0] >= r.width || pickXY[1] >= r.height) { console.error(`--pick ${pickXY}: outside the ${r.width} x ${r.height} image`); process.exit(2); }
+  const h = r.pick(pickXY[0], pickXY[1]);
+  return { pick: h && { x: pickXY[0], y: pickXY[1], primitive: h.prim, id: h.id, t: h.t, position: Array.from(h.position), normal: Array.from(h.normal) } };
 }
 // --adaptive: rounds of --adaptive-step samples until no tile is active; {rounds, ad: readAdaptive(), pixelSamples}
 function adaptiveRounds() {
@@ -124,7 +138,7 @@ if ('adaptive' in args) {
   writeMattes();
   const mid = counts.length >> 1, median = counts.length % 2 ? counts[mid] : (counts[mid - 1] + counts[mid]) / 2;
   console.log(JSON.stringify({ width: r.width, height: r.height, adaptive: num('adaptive'), rounds, pixel_samples: pixelSamples, seconds,
-    tile_samples: { min: counts[0], median, max: counts[counts.length - 1] }, ...('denoise' in args ? { denoise: num('denoise') } : {}) }));
+    tile_samples: { min: counts[0], median, max: counts[counts.length - 1] }, ...('denoise' in args ? { denoise: num('denoise') } : {}), ...pickInfo() }));
   r.destroy();
   process.exit(0);
 }
@@ -142,5 +156,5 @@ if (args.dump) {
   fs.writeFileSync(`${args.dump}.accum.bin`, Buffer.from(r.readAccum().buffer));
 }
 console.log(JSON.stringify({ width: r.width, height: r.height, spp, sample: r.sample, seconds: dt,
-  rays: c[0], mrays_per_s: c[0] / dt / 1e6, kernel_ms: r.lastTraceMs()[0] }));
+  rays: c[0], mrays_per_s: c[0] / dt / 1e6, kernel_ms: r.lastTraceMs()[0], ...pickInfo() }));
 r.destroy();

@@ -14,6 +14,7 @@
  *           queue.writeBuffer(camera / primitives / lights)   setCamera / updatePrimitives + refitAccel / updateLights
  *           (no counterpart)                      transformPrimitives: ranges moved on the device, nothing uploaded
  *           (no counterpart)                      removePrimitives / appendPrimitives: the primitive list edited on the device
+ *           (no counterpart)                      queryRays / pick: what caller rays, or the ray under a pixel, hit
  *   620     requestAnimationFrame(frame) forever  run(spp): spp frames, optionally fused
  */
 const fs = require('fs');
@@ -27,6 +28,7 @@ function loadAddon() {
 }
 
 const ACCEL = { none: 0, brute: 0, bvh2: 1, bvh: 1, lbvh: 2, ploc: 3 };
+const QUERY_PLANES = ['hit', 'prim', 'id', 't', 'position', 'normal', 'uv'];
 
 function Main(options = {}) {
   const a = loadAddon();
@@ -98,6 +100,28 @@ function Main(options = {}) {
     },
     // entries [first, first + ids.length) of the id table source 'object' reports; nothing else changes
     setPrimitiveIds: (first, ids) => a.setPrimitiveIds(device, first, ids instanceof Uint32Array ? ids : Uint32Array.from(ids)),
+    // ray queries (include/crt.h "Ray queries"): what caller rays hit -- rays: Float32Array of 8 floats per ray (o, t_max,
+    // d, exclude bits; t_max 2139095040 or Infinity = no limit, exclude bits 0xFFFFFFFF = nothing), mode 'closest' | 'any'
+    // (which reports `hit` alone) -- as typed arrays of n entries (position, normal: 4 floats each, uv: 2); does not
+    // finish or disturb what is in flight
+    queryRays: (rays, mode = 'closest', planes = mode === 'any' ? ['hit'] : QUERY_PLANES) => {
+      const m = ['closest', 'any'].indexOf(mode);
+      if (m < 0) throw new TypeError(`queryRays: unknown mode ${mode}`);
+      if (!(rays instanceof Float32Array) || rays.length % 8) throw new TypeError('queryRays: rays must be a Float32Array of 8 floats per ray');
+      const n = rays.length / 8, out = {};
+      for (const p of planes) {
+        if (!QUERY_PLANES.includes(p)) throw new TypeError(`queryRays: unknown plane ${p}`);
+        out[p] = ['hit', 'prim', 'id'].includes(p) ? new Uint32Array(n) : new Float32Array(n * (p === 't' ? 1 : p === 'uv' ? 2 : 4));
+      }
+      a.queryRays(device, rays, m, out);
+      return out;
+    },
+    // what lies under pixel (x, y) of the full image: {prim, id, t, position, normal, uv} of the pixel's camera ray (the
+    // G-buffer's), or null where it hits nothing
+    pick: (x, y) => {
+      const h = a.pick(device, x, y);
+      return h.hit ? { prim: h.prim, id: h.id, t: h.t, position: h.position.subarray(0, 3), normal: h.normal.subarray(0, 3), uv: h.uv } : null;
+    },
     // scene edits (include/crt.h "Scene edits"): each finishes what is in flight and restarts the accumulation;
     // the reference's queue.writeBuffer of the camera / primitive / light buffer
     setCamera: (camera) => a.setCamera(device, camera),

@@ -378,6 +378,76 @@ int crt_render_mattes(crt_ctx *ctx, uint32_t n_samples, int source, uint32_t slo
 int crt_set_primitive_ids(crt_ctx *ctx, uint32_t first, uint32_t count, const uint32_t *ids);
 int crt_read_primitive_ids(crt_ctx *ctx, uint32_t first, uint32_t count, uint32_t *out);
 
+/* ------------------------------------------------------------------ Ray queries
+ * "Here are my rays, what do they hit?" (DESIGN.md 6p): closest-hit and occlusion queries for caller rays, from host
+ * memory or from device memory on a stream of the caller's, and the same for the camera ray under a pixel.  A kernel of
+ * its own walks the tree the stragglers' kernel walks; the path tracer is not involved and is NOT stopped.
+ *
+ * Definition.  A ray (o, d, t_max, exclude) hits primitive i at distance t exactly when the reference's loop over every
+ * primitive (ComputeShader.wgsl:503-518) accepts it with that exclude index, started with the ray's t_max and no hit
+ * held: 0.001 <= t <= t_max -- the end is inclusive, an equal t is accepted while nothing is held -- and every other rule
+ * is the hit test's own (the triangle's pad, the patch's grazing cut, the sphere's far root when the near one is below
+ * 0.001).  CRT_QUERY_CLOSEST reports the smallest t; equal t goes to the later primitive, as everywhere in this library.
+ * d need not be normalised: t is in units of |d|.  exclude = 0xFFFFFFFF excludes nothing.  t_max = 2139095040.0f (the
+ * kernels' "infinity") or +inf is "no limit"; a NaN or negative t_max can never be beaten and gives a miss -- it is not
+ * an error, device rays cannot be validated.  A ray whose origin or direction has a component that is NaN or of
+ * magnitude >= 3.0e38 is a miss in every accel mode: it is never walked and never sent through the loop over all
+ * primitives.  This differs on purpose from crt_read_gbuffer and the debug hooks, which give such a ray the reference's
+ * loop: a public call must not spend nprim tests on each ray of a garbage batch.
+ * CRT_QUERY_ANY reports `hit` alone, 1 exactly when CRT_QUERY_CLOSEST would hit: the walk stops at the first accepted
+ * primitive, and which one that is depends on the tree, so every other plane must be NULL (CRT_EINVAL).
+ * uv: the surface coordinates the hit test itself computed for the winning primitive, its operations in its order,
+ * recomputed after the walk from the same record.  Triangle (v0, e1, e2): pvec = cross(d, e2), inv = 1 / dot(e1, pvec),
+ * tvec = o - v0, u = dot(tvec, pvec) * inv, v = dot(d, cross(tvec, e1)) * inv (the hit is v0 + u e1 + v e2).  Patch
+ * (P0, e1, e2): m = (o + t d) - P0, u = dot(m, e1) / dot(e1, e1), v = dot(m, e2) / dot(e2, e2).  Spheres: +0, +0.
+ * Which walk: the quantised 4-wide tree where the stragglers' kernel walks it (a ray whose stack it cannot hold is
+ * repeated on the BVH2); the BVH2 under options "quantize" 0, "wf_width" 8 and "pipeline" 0; the reference's loop under
+ * CRT_ACCEL_NONE.  The result does not depend on it.
+ *
+ * Contract, the same for the three calls.  They read only the scene, the tree and the id table: the accumulator, the
+ * framebuffer, `sample`, the counters, the frame ring, the adaptive state, the filters' state and history and the
+ * G-buffer stay as they are.  They do NOT flush: batches in flight stay in flight, samples merged into an unpublished
+ * cohort stay unpublished, the pipeline's driver gets no turn.  They work at sample 0, in the adaptive state, under
+ * crt_set_tile, row bands and a crt_comm_partition: none of these bears on a ray.  CRT_ESTATE without a scene or an accel
+ * structure, and while the tree is stale (after an edit, until crt_refit_accel or crt_build_accel).  CRT_EINVAL for out
+ * == NULL, every plane NULL, an unknown mode, rays == NULL with n > 0, rays or a 4-wide plane (position, normal) not
+ * 16-byte aligned, n >= 2^32.  n == 0 succeeds and does nothing.
+ * crt_query_rays (host pointers) runs on a non-blocking stream the context owns and waits for that stream only.  Its
+ * staging buffers belong to the context, grow by at least half and are released by crt_upload_scene and crt_destroy;
+ * every allocation -- staging, and the id table's device copy where `id` is asked for and a change has dropped it -- is
+ * made before anything is enqueued, so CRT_ENOMEM enqueues nothing and writes nothing to `out`.  Growing a buffer frees
+ * the old one, and hipFree waits for the device: a call that grows (the first, or a larger n than any before) can wait
+ * for work in flight; the calls after it do not.
+ * crt_query_rays_device takes rays_dev and the pointers of *out_dev (a struct in host memory) as device pointers reachable
+ * from the context's device, enqueues ONE launch on hip_stream (a hipStream_t as crt_set_stream takes it; NULL = the null
+ * stream) and returns without waiting.  It allocates nothing but the id table's device copy, and that only when needed.
+ * The caller orders its reads after the launch, and must have finished its queries before any call that changes the
+ * scene or the tree (crt_upload_scene, crt_build_accel, the scene edits, crt_refit_accel, crt_set_primitive_ids) and
+ * before crt_destroy: those calls wait for the context's streams, not for the caller's.
+ * crt_pick (host pointers) queries the G-buffer's ray of each pixel (x, y): the primary ray of sample 8 with the pixel's
+ * own seed, generated in the kernel, no limit, no exclude.  Coordinates are global and must be below W and H (CRT_EINVAL);
+ * crt_set_tile does not move them.  For a finite camera ray, t, position, normal and prim are bit for bit
+ * crt_read_gbuffer's record of that pixel.  It follows crt_query_rays' contract, so a click in a display loop does not
+ * stop the pipeline.
+ * Out of scope: caller rays through the wavefront kernel's ray lists; sorting or compacting rays; a per-ray t_min;
+ * instancing; a frame-level form across ranks. */
+typedef struct { float o[3]; float t_max; float d[3]; uint32_t exclude; } crt_ray;   /* 32 bytes; arrays 16-byte aligned */
+enum { CRT_QUERY_CLOSEST = 0, CRT_QUERY_ANY = 1 };
+typedef struct {
+    uint32_t *hit;      /* n    1 = a primitive was hit, else 0                                              */
+    uint32_t *prim;     /* n    array position of the hit primitive; 0xFFFFFFFF at a miss                    */
+    uint32_t *id;       /* n    entry `prim` of the id table (crt_set_primitive_ids); 0xFFFFFFFF at a miss   */
+    float *t;           /* n    the hit's t; at a miss the ray's own t_max, bit for bit                      */
+    float *position;    /* n*4  the hit point o + t d, channel 3 = +0; zeros at a miss                       */
+    float *normal;      /* n*4  the unit normal (faces the ray on patches and triangles, outward on
+                                spheres), channel 3 = +0; zeros at a miss                                    */
+    float *uv;          /* n*2  surface coordinates (above); +0, +0 on spheres and at a miss                 */
+} crt_query_planes;     /* any pointer may be NULL: that plane is neither allocated nor stored */
+int crt_query_rays(crt_ctx *ctx, const crt_ray *rays, size_t n, int mode, const crt_query_planes *out);
+int crt_query_rays_device(crt_ctx *ctx, const crt_ray *rays_dev, size_t n, int mode, const crt_query_planes *out_dev,
+                          void *hip_stream);
+int crt_pick(crt_ctx *ctx, const uint32_t *xy /* n pairs, global pixel coordinates */, size_t n, const crt_query_planes *out);
+
 /* ------------------------------------------------------------------ Scene edits
  * Move the camera or edit primitives and lights of the uploaded scene in place (DESIGN.md "Scene edits"), instead of
  * crt_upload_scene + crt_build_accel.  The tree's topology is kept; crt_refit_accel recomputes its boxes on the GPU.
