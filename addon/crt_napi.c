@@ -1036,6 +1036,84 @@ static napi_value js_query_rays(napi_env env, napi_callback_info info)
     return undefined(env);
 }
 
+/* radianceRays(h, Float32Array(n*8), Uint32Array(n*4) | null, nSamples, planes?) -> {xyz: Float32Array(n*4), y2:
+ * Float32Array(n), rgba8: Uint8Array(n*4)}: the path tracer's radiance along n caller rays -- each ray 8 floats (o, t_max,
+ * d, exclude bits), each key (x, y, first sample, 0), null = (i, 0, 1) -- summed over nSamples paths per ray (include/crt.h
+ * "Radiance queries").  planes: an array of the names wanted (default: all three).  Blocking for the call alone: work in
+ * flight is neither finished nor disturbed. */
+static napi_value js_radiance_rays(napi_env env, napi_callback_info info)
+{
+    size_t argc = 5;
+    napi_value argv[5];
+    NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    if (argc < 4) {
+        napi_throw_type_error(env, NULL, "radianceRays: expected (handle, rays, keys | null, nSamples, planes?)");
+        return NULL;
+    }
+    crt_ctx *ctx = get_ctx(env, argv[0]);
+    if (!ctx) return NULL;
+    void *rays = NULL, *keys = NULL; size_t bytes = 0, kbytes = 0;
+    if (!get_bytes(env, argv[1], &rays, &bytes) || bytes % sizeof(crt_ray)) {
+        napi_throw_type_error(env, NULL, "radianceRays: rays must be a Float32Array of 8 floats per ray");
+        return NULL;
+    }
+    const size_t n = bytes / sizeof(crt_ray);
+    napi_valuetype kt = napi_undefined;
+    NAPI_OK(env, napi_typeof(env, argv[2], &kt));
+    const bool have_keys = kt != napi_null && kt != napi_undefined;
+    if (have_keys && (!get_bytes(env, argv[2], &keys, &kbytes) || kbytes != n * sizeof(crt_path_key))) {
+        napi_throw_type_error(env, NULL, "radianceRays: keys must be null or a Uint32Array of 4 per ray");
+        return NULL;
+    }
+    uint32_t n_samples = 0;
+    NAPI_OK(env, napi_get_value_uint32(env, argv[3], &n_samples));
+    static const char *const names[3] = {"xyz", "y2", "rgba8"};
+    bool want[3] = {true, true, true};
+    if (argc >= 5) {
+        napi_valuetype pt = napi_undefined;
+        NAPI_OK(env, napi_typeof(env, argv[4], &pt));
+        if (pt != napi_undefined && pt != napi_null) {
+            bool is_array = false;
+            uint32_t count = 0;
+            if (napi_is_array(env, argv[4], &is_array) != napi_ok || !is_array || napi_get_array_length(env, argv[4], &count) != napi_ok) {
+                napi_throw_type_error(env, NULL, "radianceRays: planes must be an array of plane names");
+                return NULL;
+            }
+            want[0] = want[1] = want[2] = false;
+            for (uint32_t i = 0; i < count; i++) {
+                napi_value v;
+                char name[16];
+                size_t len = 0;
+                int k = -1;
+                if (napi_get_element(env, argv[4], i, &v) == napi_ok && napi_get_value_string_utf8(env, v, name, sizeof name, &len) == napi_ok)
+                    for (int j = 0; j < 3; j++) if (!strcmp(name, names[j])) k = j;
+                if (k < 0) {
+                    napi_throw_type_error(env, NULL, "radianceRays: planes holds a name other than xyz, y2, rgba8");
+                    return NULL;
+                }
+                want[k] = true;
+            }
+        }
+    }
+    static const size_t elem[3] = {16, 4, 4};
+    static const napi_typedarray_type kind[3] = {napi_float32_array, napi_float32_array, napi_uint8_array};
+    static const size_t per[3] = {4, 1, 4};
+    void *data[3] = {NULL, NULL, NULL};
+    napi_value ab[3], res, v;
+    for (int j = 0; j < 3; j++)
+        if (want[j]) NAPI_OK(env, napi_create_arraybuffer(env, n * elem[j], &data[j], &ab[j]));
+    const crt_radiance_planes out = {(float *)data[0], (float *)data[1], (uint8_t *)data[2]};
+    if (n)                                                       /* (an empty ArrayBuffer may have no address: every plane would be NULL) */
+        CRT_CHECK(env, ctx, "crt_radiance_rays", crt_radiance_rays(ctx, (const crt_ray *)rays, have_keys ? (const crt_path_key *)keys : NULL, n, n_samples, &out));
+    NAPI_OK(env, napi_create_object(env, &res));
+    for (int j = 0; j < 3; j++) {
+        if (!want[j]) continue;
+        NAPI_OK(env, napi_create_typedarray(env, kind[j], n * per[j], ab[j], 0, &v));
+        NAPI_OK(env, napi_set_named_property(env, res, names[j], v));
+    }
+    return res;
+}
+
 /* pick(h, x, y) -> {hit, prim, id, t, position: Float32Array(4), normal: Float32Array(4), uv: Float32Array(2)}: what the
  * camera ray of pixel (x, y) of the full image hits (crt_pick; global coordinates), hit = 0 with prim = id = 0xFFFFFFFF
  * where it hits nothing.  Blocking for the query alone. */
@@ -1740,7 +1818,7 @@ static napi_value init(napi_env env, napi_value exports)
         {"denoiseLatestAsync", js_denoise_latest_async},
         {"readGbuffer", js_read_gbuffer}, {"readMotion", js_read_motion}, {"renderAovs", js_render_aovs},
         {"renderMattes", js_render_mattes}, {"setPrimitiveIds", js_set_primitive_ids},
-        {"queryRays", js_query_rays}, {"pick", js_pick},
+        {"queryRays", js_query_rays}, {"pick", js_pick}, {"radianceRays", js_radiance_rays},
         {"setCamera", js_set_camera}, {"updatePrimitives", js_update_primitives}, {"updateLights", js_update_lights},
         {"refitAccel", js_refit_accel},
         {"transformPrimitives", js_transform_primitives}, {"transformPrimitivesAsync", js_transform_primitives_async},

@@ -1,7 +1,7 @@
 """python -m computeraytracer_amd [--scene file.json] [--width W --height H] [--spp N] [--out image.png] [--denoise K] [--orbit N [--temporal [--variance] [--animate | --animate-device [--rebuild-pct P] | --blink P]]]
                                 [--adaptive THRESHOLD [--adaptive-filtered] [--adaptive-step N] [--counts-out counts.png]]
                                 [--alpha] [--aov-out PREFIX] [--matte-out PREFIX [--matte-source primitive|object|material] [--matte-slots K]]
-                                [--pick X,Y]
+                                [--pick X,Y] [--panorama WxH [--panorama-eye x,y,z]]
 --adaptive goes with --orbit: every frame is sampled adaptively up to --spp, and with --denoise K --temporal [--variance] the
 temporal filters blend it with each pixel's own tile count (option "adaptive_temporal")."""
 import argparse
@@ -94,7 +94,30 @@ def parse_args(argv=None):
                     help="after the render, what lies under pixel (X, Y) of the image (crt_pick): its primitive, object id, t, "
                          "position and normal go into the JSON line as \"pick\" (null where the pixel's ray hits nothing; not "
                          "with --orbit)")
+    ap.add_argument("--panorama", default=None, metavar="WxH",
+                    help="after the render, a W x H equirectangular image of the scene around --panorama-eye at --spp samples "
+                         "per ray (crt_radiance_rays), written beside --out as <stem>_pano.png; its size goes into the JSON "
+                         "line as \"panorama\" (not with --orbit)")
+    ap.add_argument("--panorama-eye", default=None, metavar="x,y,z", help="with --panorama: the view point (default: the camera's eye)")
     args = ap.parse_args(argv)
+    if args.panorama is not None:
+        try:
+            w, h = (int(v) for v in args.panorama.lower().split("x"))
+            if w < 1 or h < 1:
+                raise ValueError
+        except ValueError:
+            ap.error("--panorama takes WxH: two positive integers")
+        args.panorama = (w, h)
+        if args.orbit is not None:
+            ap.error("--panorama does not go with --orbit")
+    if args.panorama_eye is not None:
+        try:
+            eye = tuple(float(v) for v in args.panorama_eye.split(","))
+            if len(eye) != 3 or args.panorama is None:
+                raise ValueError
+        except ValueError:
+            ap.error("--panorama-eye takes x,y,z and goes with --panorama")
+        args.panorama_eye = eye
     if args.pick is not None:
         try:
             x, y = (int(v) for v in args.pick.split(","))
@@ -250,6 +273,7 @@ def main(argv=None):
         info = {"width": ps.width, "height": ps.height, "sample": r.sample, "seconds": round(dt, 4), "out": args.out}
         rgba = _aovs(r, args, rgba, info)
         _pick(r, args, info)
+        _panorama(r, ps, args, info)
         (image.write_ppm if args.out.endswith(".ppm") else image.write_png)(args.out, rgba)
         if args.checkpoint:
             image.save_checkpoint(args.checkpoint, r)
@@ -279,6 +303,18 @@ def _aovs(r, args, rgba, info):
         info["alpha"] = True
         rgba = image.with_alpha(rgba, planes["alpha"])
     return rgba
+
+
+def _panorama(r, ps, args, info):
+    """--panorama WxH: an equirectangular view through crt_radiance_rays, <out stem>_pano.png."""
+    if args.panorama is None:
+        return
+    w, h = args.panorama
+    eye = args.panorama_eye if args.panorama_eye is not None else tuple(float(v) for v in ps.camera[0:3])
+    _, rgba = r.panorama(w, h, eye, max(1, args.spp))
+    path = os.path.splitext(args.out)[0] + "_pano.png"
+    image.write_png(path, rgba)
+    info["panorama"] = {"width": w, "height": h, "eye": list(eye), "samples": max(1, args.spp), "out": path}
 
 
 def _pick(r, args, info):
@@ -343,6 +379,7 @@ def _adaptive(r, ps, args):
             "out": args.out}
     rgba = _aovs(r, args, rgba, info)
     _pick(r, args, info)
+    _panorama(r, ps, args, info)
     (image.write_ppm if args.out.endswith(".ppm") else image.write_png)(args.out, rgba)
     if args.denoise is not None:
         info["denoise"] = args.denoise

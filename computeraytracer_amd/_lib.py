@@ -77,6 +77,9 @@ SIGNATURES = {
     "crt_query_rays": (C.c_int, [_P, _P, C.c_size_t, C.c_int, _P]),
     "crt_query_rays_device": (C.c_int, [_P, _P, C.c_size_t, C.c_int, _P, _P]),
     "crt_pick": (C.c_int, [_P, _P, C.c_size_t, _P]),
+    "crt_radiance_rays": (C.c_int, [_P, _P, _P, C.c_size_t, C.c_uint32, _P]),
+    "crt_radiance_rays_device": (C.c_int, [_P, _P, _P, C.c_size_t, C.c_uint32, _P, _P]),
+    "crt_debug_radiance_lanes": (C.c_int, [_P, C.c_size_t, _P]),
     "crt_debug_intersect": (C.c_int, [_P, _P, C.c_size_t, _P]),
     "crt_debug_trace_rays": (C.c_int, [_P, _P, C.c_size_t, _P, _P]),
     "crt_debug_walk_rays": (C.c_int, [_P, C.c_int, _P, C.c_size_t, _P, _P]),
@@ -163,6 +166,16 @@ class QueryPlanes(C.Structure):
     """crt_query_planes of include/crt.h."""
     _fields_ = [("hit", C.c_void_p), ("prim", C.c_void_p), ("id", C.c_void_p), ("t", C.c_void_p), ("position", C.c_void_p),
                 ("normal", C.c_void_p), ("uv", C.c_void_p)]
+
+
+class PathKey(C.Structure):
+    """crt_path_key of include/crt.h (16 bytes; renderer.PATH_KEY_DTYPE is the numpy form)."""
+    _fields_ = [("x", C.c_uint32), ("y", C.c_uint32), ("first_sample", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class RadiancePlanes(C.Structure):
+    """crt_radiance_planes of include/crt.h."""
+    _fields_ = [("xyz", C.c_void_p), ("y2", C.c_void_p), ("rgba8", C.c_void_p)]
 
 
 class DenoiseAdaptiveParams(C.Structure):

@@ -9,6 +9,7 @@
 //   crt_aov_api.cpp     the feature planes' entry points
 //   crt_matte_api.cpp   the id mattes' entry points and the id table
 //   crt_query_api.cpp   the ray queries' entry points
+//   crt_radiance_api.cpp  the radiance queries' entry points
 //   crt_debug.cpp       the debug read-outs
 #pragma once
 #include <hip/hip_runtime.h>
@@ -335,8 +336,13 @@ struct crt_ctx {
         DevBuf<float> t;
         DevBuf<float4> position, normal;
         DevBuf<float2> uv;
+        // radiance queries (crt_radiance.hip): they share the stream and `rays`
+        DevBuf<uint4> keys;         // crt_path_key
+        DevBuf<float4> rad_xyz;
+        DevBuf<float> rad_y2;
+        DevBuf<uchar4> rad_rgba8;
         void release() { rays.release(); xy.release(); hit.release(); prim.release(); id.release(); t.release(); position.release();
-                         normal.release(); uv.release(); }
+                         normal.release(); uv.release(); keys.release(); rad_xyz.release(); rad_y2.release(); rad_rgba8.release(); }
     } query;
 
     // scene edits (crt_refit.hip)

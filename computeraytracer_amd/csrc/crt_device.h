@@ -408,4 +408,21 @@ struct QueryParams {
     int wide_ok;                    // 0: the BVH2 even where there is a quantised 4-wide tree (option "pipeline" = 0)
 };
 
+// k_radiance (crt_radiance.hip): n_samples paths along each of n caller rays, summed per ray.  A plane whose
+// pointer is null is not stored.
+struct RadianceParams {
+    const float4 *rays;             // 2 per ray, (o.xyz, t_max) (d.xyz, exclude bits) = crt_ray
+    const uint4 *keys;              // (x, y, first sample, 0) = crt_path_key per ray; null: (i, 0, 1)
+    float4 *xyz;                    // the sum of the paths' XYZ, w = +0
+    float *y2;                      // the sum of Y * Y
+    uchar4 *rgba8;                  // tonemap_rgba8(xyz, n_samples)
+    size_t n;
+    uint32_t n_samples;
+    int wide_ok;                    // as QueryParams'
+};
+
+// The grid of k_radiance: at most this many 64-lane blocks per compute unit, beyond which lanes stride (the
+// more blocks the better, up to one ray per lane, on every grid measured).
+constexpr uint32_t kRadianceWavesPerCu = 128;
+
 }  // namespace crt

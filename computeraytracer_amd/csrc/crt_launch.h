@@ -109,4 +109,9 @@ hipError_t matte_launch(const DevScene &S, const MatteParams &P, hipStream_t str
 // crt_query.hip (mode: CRT_QUERY_CLOSEST / CRT_QUERY_ANY; pick: P.xy in place of P.rays; brute: CRT_ACCEL_NONE)
 hipError_t query_launch(const DevScene &S, const QueryParams &P, int mode, bool pick, bool brute, hipStream_t stream);
 
+// crt_radiance.hip (brute: CRT_ACCEL_NONE).  radiance_blocks: the grid of a launch of n rays on a device of num_cu compute
+// units, min(ceil(n / 64), num_cu * kRadianceWavesPerCu) blocks of 64 lanes; lane g of all of them owns rays g, g + G, ...
+uint32_t radiance_blocks(size_t n, uint32_t num_cu);
+hipError_t radiance_launch(const DevScene &S, const RadianceParams &P, bool brute, uint32_t num_cu, hipStream_t stream);
+
 }  // namespace crt

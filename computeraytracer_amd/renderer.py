@@ -30,6 +30,9 @@ QUERY_NO_LIMIT = 2139095040.0    # t_max: the kernels' "infinity" (+inf means th
 RAY_DTYPE = np.dtype([("o", np.float32, 3), ("t_max", np.float32), ("d", np.float32, 3), ("exclude", np.uint32)])   # crt_ray
 _QUERY_SHAPE = {"hit": ((), np.uint32), "prim": ((), np.uint32), "id": ((), np.uint32), "t": ((), np.float32),
                 "position": ((4,), np.float32), "normal": ((4,), np.float32), "uv": ((2,), np.float32)}
+RADIANCE_PLANES = ("xyz", "y2", "rgba8")
+PATH_KEY_DTYPE = np.dtype([("x", np.uint32), ("y", np.uint32), ("first_sample", np.uint32), ("reserved", np.uint32)])   # crt_path_key
+_RADIANCE_SHAPE = {"xyz": ((4,), np.float32), "y2": ((), np.float32), "rgba8": ((4,), np.uint8)}
 
 
 def pack_rays(origins, directions, t_max=None, exclude=None) -> np.ndarray:
@@ -44,6 +47,19 @@ def pack_rays(origins, directions, t_max=None, exclude=None) -> np.ndarray:
     rays["t_max"] = np.float32(QUERY_NO_LIMIT) if t_max is None else np.asarray(t_max, np.float32)
     rays["exclude"] = np.uint32(QUERY_NONE) if exclude is None else np.asarray(exclude, np.uint32)
     return rays
+
+
+def pack_keys(x, y, first_sample=1) -> np.ndarray:
+    """n crt_path_key records (PATH_KEY_DTYPE) from (n,) x and y and a scalar or (n,) first_sample, all uint32: the paths
+    of a ray with key (x, y, s0) are seeded as samples s0, s0 + 1, ... of pixel (x, y)."""
+    x = np.asarray(x, np.int64).reshape(-1)
+    y, s = np.broadcast_to(np.asarray(y, np.int64), x.shape), np.broadcast_to(np.asarray(first_sample, np.int64), x.shape)
+    for name, a in (("x", x), ("y", y), ("first_sample", s)):
+        if ((a < 0) | (a > 0xFFFFFFFF)).any():
+            raise ValueError(f"{name} must fit an unsigned 32-bit integer")
+    keys = np.zeros(len(x), PATH_KEY_DTYPE)
+    keys["x"], keys["y"], keys["first_sample"] = x, y, s
+    return keys
 
 
 def spectrum_rgb(spectrum, cie) -> np.ndarray:
@@ -679,6 +695,115 @@ class Renderer:
         arg = _lib.QueryPlanes(**{k: a.ctypes.data for k, a in out.items()})
         self._chk(self._lib.crt_pick(self._h, p.ctypes.data if n else None, n, C.byref(arg)))
         return out
+
+    # -- radiance queries (include/crt.h, "Radiance queries")
+    @staticmethod
+    def _radiance_args(n_samples, planes):
+        n_samples = int(n_samples)
+        if not 1 <= n_samples <= 0xFFFFFFFF:
+            raise ValueError("n_samples must be 1 .. 2^32 - 1")
+        if planes is None:
+            planes = RADIANCE_PLANES
+        unknown = [p for p in planes if p not in RADIANCE_PLANES]
+        if unknown:
+            raise ValueError(f"unknown planes {unknown}: choose from {RADIANCE_PLANES}")
+        names = [p for p in RADIANCE_PLANES if p in planes]
+        if not names:
+            raise ValueError(f"no plane asked for: choose from {RADIANCE_PLANES}")
+        return n_samples, names
+
+    def radiance_rays(self, origins=None, directions=None, keys=None, n_samples=1, t_max=None, exclude=None, planes=None,
+                      rays=None) -> dict:
+        """How much light arrives along the rays (crt_radiance_rays): n_samples paths of the path tracer from each ray,
+        summed.  Rays as for query_rays (directions must be unit vectors; t_max and exclude bear on the first segment
+        only).  keys: n records (PATH_KEY_DTYPE, see pack_keys) or an (n, 4) integer array (x, y, first_sample, 0): the
+        paths of a ray are seeded as samples first_sample, first_sample + 1, ... of pixel (x, y); None = (i, 0, 1).  With a
+        torch (n, 8) float32 tensor on this context's device as rays= the call is crt_radiance_rays_device on torch's
+        current stream, and keys is a torch (n, 4) int32 or uint32 tensor there, or None.  A dict of the planes asked for
+        (default: all): xyz float32 (n, 4) the sum of the paths' XYZ, y2 float32 (n,) the sum of Y * Y, rgba8 uint8 (n, 4)
+        the tone-mapped mean -- numpy arrays, or torch tensors for a torch input.  Does not finish or disturb what is in
+        flight; only reads."""
+        n_samples, names = self._radiance_args(n_samples, planes)
+        if rays is not None and not isinstance(rays, np.ndarray) and type(rays).__module__.split(".")[0] == "torch":
+            return self._radiance_rays_torch(rays, keys, n_samples, names)
+        if rays is None:
+            rays = pack_rays(origins, directions, t_max, exclude)
+        else:
+            rays = np.ascontiguousarray(rays)
+            if rays.dtype != RAY_DTYPE:
+                rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 8).view(RAY_DTYPE).reshape(-1)
+        n = len(rays)
+        if keys is not None:
+            keys = np.ascontiguousarray(keys)
+            if keys.dtype != PATH_KEY_DTYPE:
+                if keys.dtype.kind not in "iu":
+                    raise ValueError("keys must be PATH_KEY_DTYPE records or an (n, 4) integer array")
+                keys = np.ascontiguousarray(keys.reshape(-1, 4).astype(np.uint32)).view(PATH_KEY_DTYPE).reshape(-1)
+            if len(keys) != n:
+                raise ValueError(f"{len(keys)} keys for {n} rays")
+        out = {p: np.empty((n,) + _RADIANCE_SHAPE[p][0], _RADIANCE_SHAPE[p][1]) for p in names}
+        arg = _lib.RadiancePlanes(**{p: a.ctypes.data for p, a in out.items()})
+        self._chk(self._lib.crt_radiance_rays(self._h, rays.ctypes.data if n else None, keys.ctypes.data if keys is not None and n else None,
+                                              n, n_samples, C.byref(arg)))
+        return out
+
+    def _radiance_rays_torch(self, rays, keys, n_samples, names) -> dict:
+        import torch
+        if rays.device.type != "cuda" or rays.device.index != self.device:
+            raise ValueError(f"rays are on {rays.device}, the context on cuda:{self.device}")
+        if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8 or not rays.is_contiguous():
+            raise ValueError("rays must be a contiguous (n, 8) float32 tensor: (o, t_max, d, exclude bits) per row")
+        n = rays.shape[0]
+        if keys is not None:
+            if not isinstance(keys, torch.Tensor) or keys.device != rays.device:
+                raise ValueError(f"keys must be a torch tensor on {rays.device}, as the rays are")
+            if keys.dtype not in (torch.int32, torch.uint32) or tuple(keys.shape) != (n, 4) or not keys.is_contiguous():
+                raise ValueError("keys must be a contiguous (n, 4) int32 or uint32 tensor: (x, y, first_sample, 0) per row")
+        kinds = {np.float32: torch.float32, np.uint8: torch.uint8}
+        with torch.cuda.device(self.device):
+            out = {p: torch.empty((n,) + _RADIANCE_SHAPE[p][0], dtype=kinds[_RADIANCE_SHAPE[p][1]], device=rays.device) for p in names}
+            if n == 0:                                          # (an empty tensor has no pointer to pass)
+                return out
+            arg = _lib.RadiancePlanes(**{p: a.data_ptr() for p, a in out.items()})
+            stream = torch.cuda.current_stream(rays.device).cuda_stream
+            self._chk(self._lib.crt_radiance_rays_device(self._h, rays.data_ptr(), keys.data_ptr() if keys is not None else None,
+                                                         n, n_samples, C.byref(arg), stream))
+        return out
+
+    def radiance_lanes(self, n: int) -> int:
+        """crt_debug_radiance_lanes: the lanes G of the grid a radiance call of n rays launches (lane g owns rays g, g + G, ...)."""
+        v = C.c_uint64()
+        self._chk(self._lib.crt_debug_radiance_lanes(self._h, int(n), C.byref(v)))
+        return int(v.value)
+
+    @staticmethod
+    def panorama_rays(width: int, height: int, eye, first_sample: int = 1):
+        """The rays and keys of panorama(): (width * height RAY_DTYPE records, as many PATH_KEY_DTYPE records), row-major."""
+        width, height = int(width), int(height)
+        if width < 1 or height < 1:
+            raise ValueError("width and height must be at least 1")
+        u, v = np.meshgrid(np.arange(width, dtype=np.float32), np.arange(height, dtype=np.float32))
+        pi = np.float32(np.pi)
+        phi = ((u + np.float32(0.5)) / np.float32(width) * np.float32(2.0) - np.float32(1.0)) * pi
+        theta = (v + np.float32(0.5)) / np.float32(height) * pi
+        st = np.sin(theta, dtype=np.float32)
+        d = np.stack([st * np.sin(phi, dtype=np.float32), np.cos(theta, dtype=np.float32), st * np.cos(phi, dtype=np.float32)], axis=-1)
+        d = (d / np.sqrt((d * d).sum(axis=-1, dtype=np.float32), dtype=np.float32)[..., None]).astype(np.float32).reshape(-1, 3)
+        o = np.broadcast_to(np.asarray(eye, np.float32).reshape(1, 3), d.shape)
+        return pack_rays(o, d), pack_keys(u.reshape(-1).astype(np.uint32), v.reshape(-1).astype(np.uint32), first_sample)
+
+    def panorama(self, width: int, height: int, eye, n_samples: int, first_sample: int = 1):
+        """An equirectangular (360 x 180 degree) image of the scene around `eye`: (xyz (H, W, 4) float32 sums over n_samples
+        paths, rgba8 (H, W, 4) the tone-mapped mean), through radiance_rays.  The rays are made on the host in float32.
+        Pixel (u, v), u = 0 .. width-1 from left to right, v = 0 .. height-1 from top to bottom, looks along
+            phi = ((u + 0.5) / width * 2 - 1) * pi        (azimuth: 0 at the image's centre column, -pi at its left edge)
+            theta = (v + 0.5) / height * pi                 (polar angle from +y: 0 at the top row's upper edge)
+            d = normalize(sin(theta) sin(phi), cos(theta), sin(theta) cos(phi))
+        so the centre looks along +z, the right half towards +x and the top towards +y.  Its key is (u, v, first_sample):
+        its paths are seeded as samples first_sample .. first_sample + n_samples - 1 of pixel (u, v)."""
+        rays, keys = self.panorama_rays(width, height, eye, first_sample)
+        got = self.radiance_rays(rays=rays, keys=keys, n_samples=n_samples, planes=("xyz", "rgba8"))
+        return got["xyz"].reshape(int(height), int(width), 4), got["rgba8"].reshape(int(height), int(width), 4)
 
     # -- multi-GPU: the frame across the ranks of a communicator (include/crt.h, "Multi-GPU")
     @staticmethod

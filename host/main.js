@@ -15,6 +15,7 @@
  *           (no counterpart)                      transformPrimitives: ranges moved on the device, nothing uploaded
  *           (no counterpart)                      removePrimitives / appendPrimitives: the primitive list edited on the device
  *           (no counterpart)                      queryRays / pick: what caller rays, or the ray under a pixel, hit
+ *           (no counterpart)                      radianceRays: the path tracer's radiance along caller rays
  *   620     requestAnimationFrame(frame) forever  run(spp): spp frames, optionally fused
  */
 const fs = require('fs');
@@ -29,6 +30,7 @@ function loadAddon() {
 
 const ACCEL = { none: 0, brute: 0, bvh2: 1, bvh: 1, lbvh: 2, ploc: 3 };
 const QUERY_PLANES = ['hit', 'prim', 'id', 't', 'position', 'normal', 'uv'];
+const RADIANCE_PLANES = ['xyz', 'y2', 'rgba8'];
 
 function Main(options = {}) {
   const a = loadAddon();
@@ -115,6 +117,18 @@ function Main(options = {}) {
       }
       a.queryRays(device, rays, m, out);
       return out;
+    },
+    // how much light arrives along caller rays (include/crt.h "Radiance queries"): rays as for queryRays, keys a
+    // Uint32Array of (x, y, first sample, 0) per ray or null (= (i, 0, 1)), nSamples paths per ray summed; returns
+    // {xyz: Float32Array(n*4), y2: Float32Array(n), rgba8: Uint8Array(n*4)}, or the planes named.  Blocking for the call
+    // alone: work in flight is neither finished nor disturbed.
+    radianceRays: (rays, keys = null, nSamples = 1, planes = RADIANCE_PLANES) => {
+      if (!(rays instanceof Float32Array) || rays.length % 8) throw new TypeError('radianceRays: rays must be a Float32Array of 8 floats per ray');
+      if (keys !== null && (!(keys instanceof Uint32Array) || keys.length !== rays.length / 2)) throw new TypeError('radianceRays: keys must be null or a Uint32Array of 4 per ray');
+      if (!Number.isInteger(nSamples) || nSamples < 1 || nSamples > 0xFFFFFFFF) throw new TypeError('radianceRays: nSamples must be an integer from 1 to 2^32 - 1');
+      for (const p of planes) if (!RADIANCE_PLANES.includes(p)) throw new TypeError(`radianceRays: unknown plane ${p}`);
+      if (!planes.length) throw new TypeError('radianceRays: no plane asked for');
+      return a.radianceRays(device, rays, keys, nSamples, planes);
     },
     // what lies under pixel (x, y) of the full image: {prim, id, t, position, normal, uv} of the pixel's camera ray (the
     // G-buffer's), or null where it hits nothing

@@ -448,6 +448,69 @@ int crt_query_rays_device(crt_ctx *ctx, const crt_ray *rays_dev, size_t n, int m
                           void *hip_stream);
 int crt_pick(crt_ctx *ctx, const uint32_t *xy /* n pairs, global pixel coordinates */, size_t n, const crt_query_planes *out);
 
+/* ------------------------------------------------------------------ Radiance queries
+ * "Here are my rays, how much light arrives along them?" (DESIGN.md 6q): the path tracer's radiance for caller rays -- a
+ * panorama, a fisheye or thin-lens view, an irradiance probe, a light-meter reading, the texels of a lightmap (crt_query_rays
+ * returns the uv to bake into) -- from host memory or from device memory on a stream of the caller's.  A kernel of its own
+ * beside the path tracer, built as the ray queries' kernel is; the pipeline is not involved and is NOT stopped.
+ *
+ * Definition.  For ray i with record (o, t_max, d, exclude) and key (x, y, s0) -- keys == NULL means x = (uint32_t)i,
+ * y = 0, s0 = 1 -- the sums start at +0, and for j = 0 .. n_samples-1, in this order:
+ *   1. s = s0 + j in uint32_t arithmetic (it wraps);
+ *   2. rng = {y, x*100u, s, tea(x, y*100u)}, as ComputeShader.wgsl:98 seeds sample s of pixel (x, y);
+ *   3. two rnd(rng) draws whose values are not used: the camera's two jitter draws, which put the stream where the
+ *      reference has it when path_trace starts;
+ *   4. sample_wavelengths (one draw);
+ *   5. the reference's path_trace (:119-295) from (o, d) with that stream and those wavelengths, with exactly two
+ *      extensions, both of the FIRST segment only: `exclude` takes the place of the initial 0xFFFFFFFF, and a first hit
+ *      must satisfy crt_query_rays' definition with the ray's t_max (2139095040.0f or +inf = no limit; a NaN or negative
+ *      limit makes the first segment a miss).  With exclude = 0xFFFFFFFF and no limit the path is the reference's own, bit
+ *      for bit: with the rays of a camera and keys (x, y, s) the sums are what crt_read_accum holds;
+ *   6. c = spectral_to_xyz(radiance, wavelengths);
+ *   7. xyz = xyz + c, per component;
+ *   8. y2 = y2 + (c.y * c.y), both operations rounded.
+ * Then rgba8 = the reference's colour tail of xyz / (float)n_samples (what crt_read_rgba8 shows for n_samples samples).
+ * d is used as given and every radiometric quantity assumes a unit vector: the caller normalises.
+ * A caller ray whose o or d has a component that is NaN or of magnitude >= 3.0e38 is never walked and gets zeros in every
+ * plane (crt_query_rays' rule and its reason).  A bounce ray that becomes non-finite inside a path is handled as the
+ * path tracer handles it, by the loop over every primitive.
+ * The context's camera does not enter, except through hit_pad (crt_debug_hit_pad: max(primitive scale, |eye|) * 2^-17),
+ * which is part of the triangles' acceptance rule.  crt_set_sample_offset does not enter: the keys carry the sample
+ * index.  crt_set_tile, row bands, the adaptive state and a crt_comm_partition do not enter.
+ * Which walk: crt_query_rays' (the quantised 4-wide tree where the stragglers' kernel walks it, else the BVH2; shadow
+ * rays primed with the light's own hit; the reference's loop under CRT_ACCEL_NONE).  The result does not depend on it,
+ * nor on which lane ran a ray or what ran beside it: a ray's output is a function of its record, its key and n_samples.
+ *
+ * Contract: crt_query_rays', word for word where it applies.  The calls read only the scene, the lights, the spectra
+ * tables and the tree: the accumulator, the framebuffer, `sample`, the counters (crt_counters counts none of these rays),
+ * the frame ring, the adaptive state, the filters' state and history and the G-buffer stay as they are.  They do NOT
+ * flush and give the pipeline's driver no turn.  CRT_ESTATE without a scene or an accel structure, and while the tree is
+ * stale.  CRT_EINVAL for out == NULL, every plane NULL, rays == NULL with n > 0, rays, keys or xyz not 16-byte aligned,
+ * n >= 2^32, n_samples == 0.  n == 0 succeeds and does nothing.
+ * crt_radiance_rays (host pointers) runs on the ray queries' stream and reuses their ray staging; its own staging buffers
+ * grow by at least half and are released by crt_upload_scene and crt_destroy; every allocation is made before anything is
+ * enqueued, so CRT_ENOMEM enqueues nothing and writes nothing to `out`.  (Growing frees the old buffer and hipFree waits
+ * for the device, as for crt_query_rays.)
+ * crt_radiance_rays_device takes rays_dev, keys_dev and the pointers of *out_dev (a struct in host memory) as device
+ * pointers, enqueues ONE launch on hip_stream (NULL = the null stream), allocates nothing and returns without waiting.
+ * The launch keeps no state in device memory, so calls on different streams cannot disturb each other.  The caller orders
+ * its reads after the launch and must have finished its calls before any call that changes the scene or the tree and
+ * before crt_destroy, as for crt_query_rays_device.
+ * Out of scope: caller rays through the wavefront pool; a t_max or exclude beyond the first segment; per-ray sample
+ * counts; sorting or compacting rays; a frame-level form across ranks; splitting the radiance by bounce or by light. */
+typedef struct { uint32_t x, y, first_sample, reserved; } crt_path_key;   /* 16 bytes; arrays 16-byte aligned; reserved = 0 */
+typedef struct {
+    float   *xyz;     /* n*4  sum over the samples of the path's XYZ (what crt_read_accum holds per pixel), channel 3 = +0 */
+    float   *y2;      /* n    sum over the samples of Y*Y: q = q + (Y*Y), both operations rounded (DESIGN.md 6c's second moment) */
+    uint8_t *rgba8;   /* n*4  the reference's colour tail of xyz / (float)n_samples (what crt_read_rgba8 shows) */
+} crt_radiance_planes; /* any pointer may be NULL; all NULL is CRT_EINVAL; xyz 16-byte aligned */
+int crt_radiance_rays(crt_ctx *ctx, const crt_ray *rays, const crt_path_key *keys, size_t n, uint32_t n_samples,
+                      const crt_radiance_planes *out);
+int crt_radiance_rays_device(crt_ctx *ctx, const crt_ray *rays_dev, const crt_path_key *keys_dev, size_t n, uint32_t n_samples,
+                             const crt_radiance_planes *out_dev, void *hip_stream);
+/* Test hook: the lanes G of the persistent grid a call of n rays launches (lane g owns rays g, g + G, ...). */
+int crt_debug_radiance_lanes(crt_ctx *ctx, size_t n, uint64_t *out);
+
 /* ------------------------------------------------------------------ Scene edits
  * Move the camera or edit primitives and lights of the uploaded scene in place (DESIGN.md "Scene edits"), instead of
  * crt_upload_scene + crt_build_accel.  The tree's topology is kept; crt_refit_accel recomputes its boxes on the GPU.
